@@ -7,7 +7,7 @@ pxmcmc/mcmc.py:158-161) of a batch of 16 chains per GPU: spherical-wavelet synth
 operator (L=256, B=2, J_min=2), identity measurement, S2_Wavelets_L1 prox, complex128 state
 (the reference's layout), synthetic band-limited data already resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Started plainly with --gpus N > 1 (no torchrun environment) the script launches its own N ranks as a child
@@ -621,6 +621,36 @@ def leg_failures(out):
     return bad
 
 
+DUMP_BUDGET_BYTES = 63_000_000  # --dump-outputs: the arrays of all files together (64 MB less room for the .npy headers)
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: write each named array as <path>/<name>.npy in float64.  A complex array whose imaginary part is
+    zero everywhere (the real-valued chain state) is written as its real part, any other complex array as [..., 2]
+    (real, imaginary).  Over the byte budget, every array is cut to the same fixed, seeded sample of flat indices per
+    row (sorted; chosen from the shape alone, so two runs with the same arguments sample the same elements).
+    Returns {name: written shape}."""
+    import torch
+
+    host = {}
+    for name, t in arrays.items():
+        if t.is_complex():
+            t = t.real if not bool((t.imag != 0).any()) else torch.view_as_real(t)
+        host[name] = t.detach().to(torch.float64).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > budget:
+        keep = budget / total
+        for name, a in host.items():
+            rows = a.reshape(a.shape[0], -1) if a.ndim > 1 else a[None]
+            n = max(1, int(rows.shape[1] * keep))
+            idx = np.sort(np.random.default_rng(seed).choice(rows.shape[1], n, replace=False))
+            host[name] = rows[:, idx]
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in host.items()}
+
+
 def pmc_child(which):
     """body of the rocprofv3 --pmc child passes of the side legs: the same launches, a few of each, nothing printed"""
     import torch
@@ -659,6 +689,9 @@ def main():
     ap.add_argument("--config5-cap", type=int, default=C5_TUNE_CAP,
                     help="iterations of the configs[4] PxMALA run (delta adapts from 1e-6; the timed stretch follows the first lap "
                          "with the window acceptance inside [0.3, 0.7])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the state the timed path left after its last step (X = the chains' "
+                         "samples, preds = forward(X)) as DIR/<name>.npy, float64; rank 0's chains")
     ap.add_argument("--pmc-child", default="", help=argparse.SUPPRESS)  # internal: body of the side legs' rocprofv3 --pmc passes
     args = ap.parse_args()
     if args.pmc_child:
@@ -764,6 +797,10 @@ def main():
     # (iii) the timed region --repeats times back to back; value = MEDIAN region, min / max beside it
     dt_ranks = [timed_region() for _ in range(max(args.repeats, 1))]
     dt_rank = dt_ranks[0]
+    dumped = None
+    if args.dump_outputs and rank == 0:  # outside the clock, before the roofline legs below advance the state further
+        X, preds = sampler._engine_state()
+        dumped = dump_outputs(args.dump_outputs, {"X": X, "preds": preds})
     # roofline leg: the same steps once more through the same engine, launched eagerly (no graph replay) so that
     # every k_sht_gemm launch can be bracketed by HIP events on its stream (events cannot be read back from
     # inside a graph replay)
@@ -1028,6 +1065,8 @@ def main():
                 except Exception as exc:  # reported in the line AND in the exit code (leg_failures)
                     out["parity"]["error"] = repr(exc)
             out["cpu_baseline"] = cpu
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         failures = leg_failures(out)
         out["legs_ok"] = not failures
         out["leg_failures"] = failures

@@ -259,6 +259,35 @@ def test_bench_tuned_iteration_window_rule():
     assert ok and n == 200 and a == 0.5                      # tuned from the start: the first full window
 
 
+def test_bench_dump_outputs_files_dtype_and_budget(tmp_path):
+    """bench.py --dump-outputs: real-valued complex state written as its float64 real part, other complex arrays as
+    (real, imaginary) pairs; over the byte budget the same seeded column sample on every call, under the budget."""
+    import importlib.util
+
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_mod_d", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    X = torch.complex(torch.randn(4, 1000, generator=g, dtype=torch.float64), torch.zeros(4, 1000, dtype=torch.float64))
+    P = torch.randn(4, 300, generator=g, dtype=torch.complex128)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), {"X": X, "preds": P})
+    assert shapes == {"X": [4, 1000], "preds": [4, 300, 2]}
+    x = np.load(tmp_path / "a" / "X.npy")
+    assert x.dtype == np.float64 and np.array_equal(x, X.real.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "preds.npy"), torch.view_as_real(P).numpy())
+    budget = 20_000
+    s1 = bench.dump_outputs(str(tmp_path / "b"), {"X": X, "preds": P}, budget=budget)
+    s2 = bench.dump_outputs(str(tmp_path / "c"), {"X": X, "preds": P}, budget=budget)
+    assert s1 == s2 and s1["X"][0] == 4 and s1["X"][1] < 1000
+    assert sum(np.load(tmp_path / "b" / f"{k}.npy").nbytes for k in s1) <= budget
+    for k in s1:
+        assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), np.load(tmp_path / "c" / f"{k}.npy"))
+    xs = np.load(tmp_path / "b" / "X.npy")
+    assert all(np.isin(xs[r], x[r]).all() for r in range(4))  # a sample of the written rows, not new numbers
+
+
 def test_pfa511_tables_match_the_numpy_model():
     """The host tables of the exact-length phi-DFT unit (csrc/dft_pfa.h: 511 = 7 x 73, Good-Thomas + Rader over Z_8 x Z_9) against
     the lane / register-exact numpy model scripts/dev/proto_pfa511.py, which is itself checked against numpy.fft here: gather
