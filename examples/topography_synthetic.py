@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from pxmcmc_amd import ops  # noqa: E402
 from pxmcmc_amd.forward import SphericalWaveletTransformOperator  # noqa: E402
-from pxmcmc_amd.mcmc import MYULA, PxMALA, PxMCMCParams  # noqa: E402
+from pxmcmc_amd.mcmc import MYULA, SKROCK, PxMALA, PxMCMCParams  # noqa: E402
 from pxmcmc_amd.prior import S2_Wavelets_L1  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
 from pxmcmc_amd.uncertainty import chain_to_images, credible_interval_range  # noqa: E402
@@ -28,7 +28,8 @@ from pxmcmc_amd.uncertainty import chain_to_images, credible_interval_range  # n
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--L", type=int, default=32, help="Angular bandlimit. Default 32.")
-    ap.add_argument("--algo", type=str, default="myula", help="'myula' or 'pxmala'")
+    ap.add_argument("--algo", type=str, default="myula", help="'myula', 'pxmala' or 'skrock'")
+    ap.add_argument("--s", type=int, default=5, help="SKROCK: number of Chebyshev stages (gradient evaluations per iteration)")
     ap.add_argument("--setting", type=str, default="synthesis")
     ap.add_argument("--sigma", type=float, default=0.05, help="Noise level added to the data.")
     ap.add_argument("--mu", type=float, default=1.0)
@@ -66,14 +67,16 @@ def main(argv=None):
         norm2 = float(torch.linalg.norm(y) / torch.linalg.norm(x))
         x = y / torch.linalg.norm(y)
     delta = 0.8 / (norm2 / args.sigma ** 2 + 1 / lmda)
+    if args.algo == "skrock":  # SKROCK is stable up to (2 - 4 eta / 3) s^2 / L: the same margin, s^2 times the step
+        delta *= args.s ** 2
 
     params = PxMCMCParams(nsamples=args.nsamples, nburn=args.nburn, ngap=args.ngap, delta=delta, lmda=lmda, mu=args.mu,
-                          complex=False, verbosity=max(1, args.ngap * 10))
+                          s=args.s, complex=False, verbosity=max(1, args.ngap * 10))
     regulariser = S2_Wavelets_L1(setting, forwardop.transform.inverse, forwardop.transform.inverse_adjoint,
                                  params.lmda * params.mu, L=L, B=B, J_min=J_min)
     print(f"Number of data points: {len(data)}")
     print(f"Number of model parameters: {forwardop.nparams}")
-    cls = MYULA if args.algo == "myula" else PxMALA
+    cls = {"myula": MYULA, "pxmala": PxMALA, "skrock": SKROCK}[args.algo]
     mcmc = cls(forwardop, regulariser, params, nchains=args.chains)
     start = datetime.now()
     mcmc.run(start_point=np.zeros(forwardop.nparams))

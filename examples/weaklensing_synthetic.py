@@ -10,7 +10,7 @@ reads a HEALPix kappa map with healpy, absent here):
          inverse SHT, shear through WeakLensing.forward
       -> build_mask(L, size) (Euclid-like: ecliptic band + galactic plane, pxmcmc/utils.py:320-349), ngal = 30
       -> ForwardOperator(gammas, 1 / inv_cov, setting, SphericalWaveletTransform, WeakLensing)
-      -> S2_Wavelets_L1 -> MYULA / PxMALA(tune_delta=True) -> save_mcmc.
+      -> S2_Wavelets_L1 -> MYULA / PxMALA(tune_delta=True) / SKROCK -> save_mcmc.
 
     python examples/weaklensing_synthetic.py --L 64 --algo pxmala --nsamples 20 --ngap 20 --nburn 100 --outdir /tmp
 """
@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from pxmcmc_amd import ops  # noqa: E402
 from pxmcmc_amd.forward import ForwardOperator  # noqa: E402
-from pxmcmc_amd.mcmc import MYULA, PxMALA, PxMCMCParams  # noqa: E402
+from pxmcmc_amd.mcmc import MYULA, SKROCK, PxMALA, PxMCMCParams  # noqa: E402
 from pxmcmc_amd.measurements import WeakLensing  # noqa: E402
 from pxmcmc_amd.prior import S2_Wavelets_L1  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
@@ -68,7 +68,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--outdir", type=str, default=".")
     ap.add_argument("--jobid", type=str, default="0")
-    ap.add_argument("--algo", type=str, default="myula", help="'myula' or 'pxmala'")
+    ap.add_argument("--algo", type=str, default="myula", help="'myula', 'pxmala' or 'skrock'")
+    ap.add_argument("--s", type=int, default=5, help="SKROCK: number of Chebyshev stages (gradient evaluations per iteration)")
     ap.add_argument("--setting", type=str, default="synthesis")
     ap.add_argument("--delta", type=float, default=1e-6, help="PxMCMC step size. Default 1e-6 (main.py:73)")
     ap.add_argument("--mu", type=float, default=1.0)
@@ -92,7 +93,7 @@ def main(argv=None):
     forward_operator = ForwardOperator(gammas_truth, 1 / measurement.inv_cov, setting, transform=transform,
                                        measurement=measurement, nparams=transform.ncoefs)
     params = PxMCMCParams(nsamples=args.nsamples, nburn=args.nburn, ngap=args.ngap, delta=args.delta, lmda=args.delta / 2,
-                          mu=args.mu, complex=False, verbosity=max(1, args.ngap * 10))
+                          mu=args.mu, s=args.s, complex=False, verbosity=max(1, args.ngap * 10))
     prior = S2_Wavelets_L1(setting, transform.inverse, transform.inverse_adjoint, params.lmda * params.mu, L=L, B=B,
                            J_min=J_min)
     print(f"Number of data points: {gammas_truth.size}")
@@ -101,8 +102,10 @@ def main(argv=None):
         mcmc = MYULA(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
     elif args.algo == "pxmala":
         mcmc = PxMALA(forward_operator, prior, params, tune_delta=True, nchains=args.chains, seed=args.seed)
+    elif args.algo == "skrock":
+        mcmc = SKROCK(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
     else:
-        raise ValueError("algo must be 'myula' or 'pxmala' (SKROCK is out of scope, SURVEY.md section 2)")
+        raise ValueError("algo must be 'myula', 'pxmala' or 'skrock'")
 
     now = datetime.now()
     t0 = time.perf_counter()

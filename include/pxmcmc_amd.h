@@ -292,6 +292,22 @@ int pxm_chain_step_it(const void* X, const void* proxf, const void* gradg, const
                       double delta, double lmda, const void* noise, int noise_complex, uint64_t seed,
                       uint64_t chain0, uint64_t iter, const uint64_t* iter_dev, void* X_out, int64_t n,
                       int C, int dtype, pxm_stream_t stream);
+/* One stage of the SKROCK Chebyshev recursion (pxmcmc/mcmc.py:349-368 with the recursion coefficients of Pereyra,
+ * Vargas-Mieles & Zygalakis 2020, not mcmc.py:370-383; the gradient of pxmcmc/mcmc.py:84-89 folded into a, b, c):
+ *   out = a U + b P + c gradg + e V + r Z        (every array [C][n]; T [n] shared by chains)
+ * P: b == 0 -> no term; proxf given -> P = proxf (analysis setting / user prior); proxf NULL -> P = soft(U, T or T_scalar)
+ * as pxm_myula_step.  gradg, V: NULL -> no term.  Z: r == 0 -> no term (no noise code runs); noise given -> that array
+ * (real, or complex with noise_complex); NULL -> the Philox stream of pxm_myula_step keyed (seed, chain0 + c, element,
+ * iter), noise_complex = (0 | 1) | PXM_NOISE_F64 -- SKROCK.chain_step's randn [+ 1j randn] (pxmcmc/mcmc.py:338-347).
+ * out must not alias an input.  _it: the Philox iteration is iter + *iter_dev, read when the kernel runs (graph replay). */
+int pxm_skrock_stage(const void* U, const void* proxf, const double* T, double T_scalar, const void* gradg,
+                     const void* V, double a, double b, double c, double e, double r, const void* noise,
+                     int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter, void* out, int64_t n,
+                     int C, int dtype, pxm_stream_t stream);
+int pxm_skrock_stage_it(const void* U, const void* proxf, const double* T, double T_scalar, const void* gradg,
+                        const void* V, double a, double b, double c, double e, double r, const void* noise,
+                        int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter, const uint64_t* iter_dev,
+                        void* out, int64_t n, int C, int dtype, pxm_stream_t stream);
 /* N(0,1) draws of the Philox4x32-10 stream keyed (seed, chain0+c, iter): out [C][n] (f64 or c128) */
 int pxm_randn(void* out, int64_t n, int C, int dtype, uint64_t seed, uint64_t chain0, uint64_t iter,
               pxm_stream_t stream);

@@ -1,5 +1,5 @@
 """
-Samplers of the reference (pxmcmc/mcmc.py:6-289: PxMCMCParams, PxMCMC, MYULA, PxMALA) driving
+Samplers of the reference (pxmcmc/mcmc.py:6-383: PxMCMCParams, PxMCMC, MYULA, PxMALA, SKROCK) driving
 the HIP kernels.  The plugin protocol is the reference's: the sampler only touches
 ``forward.forward / calc_gradg / data / invcov / nparams`` and ``prior.proxf / prior.prior``.
 
@@ -24,7 +24,9 @@ Extensions (all optional, defaults reproduce the reference's one-chain behaviour
   noise per component (real-signal symmetry).  Same results, half the transform
   work (default on; complex data, as in the reference-literal topography set-up, is never paired).
 
-SKROCK (pxmcmc/mcmc.py:292-383) is out of scope.
+SKROCK (pxmcmc/mcmc.py:292-383) follows the published recursion (Pereyra, Vargas-Mieles & Zygalakis 2020), which
+differs from the reference's literal code for s >= 2 (see :class:`SKROCK`); it takes the keywords above except
+``ring_shortcut`` / ``real_pairs``, which it accepts and ignores.
 """
 import time
 
@@ -45,7 +47,7 @@ class PxMCMCParams:
     :param lmda: prox parameter
     :param delta: Forward-Euler step size
     :param mu: regularisation parameter
-    :param s: max order of Chebyshev polynomials (SKROCK; unused here)
+    :param s: max order of Chebyshev polynomials: the number of stages of :class:`SKROCK` (unused by MYULA / PxMALA)
     :param nsamples: number of samples to save
     :param nburn: burn-in size
     :param ngap: thinning: iterations between saved samples
@@ -261,6 +263,144 @@ class PxMCMC:
         w = np.stack([np.random.randn(N) + (np.random.randn(N) * 1j if self.complex else 0) for _ in range(C)])
         return ops.as_device(w)
 
+    # ---- stepping engine: static buffers, a device iteration counter, HIP-graph replay between observable events ----
+    # (the sampler supplies _engine_start -- filling XA / XB / P / cnt / cnt0 / reset / one -- and _graph_ok)
+    _GRAPH_PAIRS = 4  # iterations per graph replay = 2 * _GRAPH_PAIRS (fewer, longer launches of the host)
+
+    def _engine_capture(self, eng, X, preds, i0):
+        """capture the two graphs of an engine (2 and 2 * _GRAPH_PAIRS iterations); state is (X, preds, i0) afterwards"""
+        eng["graph"] = eng["graph_long"] = None
+        if self._graph_ok():
+            try:
+                stream = torch.cuda.Stream()
+                stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(stream):
+                    eng["one"](eng["XA"], eng["XB"])  # warm-up outside capture (lazy allocations, attributes)
+                    eng["one"](eng["XB"], eng["XA"])
+                torch.cuda.current_stream().wait_stream(stream)
+                torch.cuda.synchronize()
+                eng["XA"].copy_(X)
+                eng["P"].copy_(preds)
+                eng["cnt"].set(eng["cnt0"](i0))
+                eng["reset"]()
+                # two graphs: 2 iterations (short advances between observable events) and 2 * _GRAPH_PAIRS
+                # iterations (long advances: fewer launches by the host).  A plan torn down while a capture is in
+                # progress (the garbage collector may run at any point) only queues its device frees: the
+                # library empties the queue at the end of the scope.
+                graphs = []
+                for pairs in (1, self._GRAPH_PAIRS):
+                    g = torch.cuda.CUDAGraph()
+                    with ops.capture_scope(), torch.cuda.graph(g):
+                        for _ in range(pairs):
+                            eng["one"](eng["XA"], eng["XB"])
+                            eng["one"](eng["XB"], eng["XA"])
+                    graphs.append(g)
+                # capture does not execute: state is still (X, preds, i0)
+                eng["graph"], eng["graph_long"] = graphs
+            except Exception as exc:  # capture unsupported in this environment: eager stepping, same results
+                eng["graph"] = eng["graph_long"] = None
+                eng["graph_error"] = repr(exc)
+                eng["XA"].copy_(X)
+                eng["P"].copy_(preds)
+                eng["cnt"].set(eng["cnt0"](i0))
+                eng["reset"]()
+
+    def _engine_advance(self, k):
+        """advance the engine's state by k iterations (graph replays of 2 * _GRAPH_PAIRS + eager remainder)"""
+        eng = self._eng
+        if eng["side"] == "B" and k > 0:  # realign so that replays start from XA
+            eng["one"](eng["XB"], eng["XA"])
+            eng["side"] = "A"
+            k -= 1
+        if eng["graph"] is not None:
+            per = 2 * self._GRAPH_PAIRS
+            while k >= per:
+                eng["graph_long"].replay()
+                eng["P_valid"] = not (eng["ring"] or eng.get("lazy"))
+                k -= per
+            while k >= 2:
+                eng["graph"].replay()
+                eng["P_valid"] = not (eng["ring"] or eng.get("lazy"))
+                k -= 2
+        while k >= 2:
+            eng["one"](eng["XA"], eng["XB"])
+            eng["one"](eng["XB"], eng["XA"])
+            k -= 2
+        if k == 1:
+            eng["one"](eng["XA"], eng["XB"])
+            eng["side"] = "B"
+
+    def _engine_state(self):
+        """(X, preds) of the current state as [C, .] arrays (pair-packed engines unpack here: observation only)"""
+        eng = self._eng
+        if eng["ring"] and not eng["P_valid"]:  # forward(X) of the carried rings, on demand
+            eng["plan"].ring_preds(eng["P"].shape[0], out=eng["P"])
+            eng["P_valid"] = True
+        elif eng.get("lazy") and not eng["P_valid"]:  # an engine whose steps do not form forward(X'): on demand
+            eng["P"].copy_(ops.as_device(self.forward.forward(eng["XA"] if eng["side"] == "A" else eng["XB"])))
+            eng["P_valid"] = True
+        # observation point: the host is about to read the state -- an expired device wait since the last one raises
+        if eng.get("plan") is not None:
+            eng["plan"].raise_on_fault()
+        X = eng["XA"] if eng["side"] == "A" else eng["XB"]
+        if eng["pairs"]:
+            return self._unpack(X), self._unpack(eng["P"])
+        return X, eng["P"]
+
+    def _engine_stop(self):
+        """unregister the iteration counter and drop the engine's buffers, graph and closures (the closures
+        reference the sampler: without this the plan would only be released by a later garbage collection)"""
+        eng = getattr(self, "_eng", None)
+        if eng is not None and eng.get("cnt") is not None:
+            eng["cnt"].close()
+            eng["graph"] = eng["graph"] is not None  # keep the flags (ring, pairs, graph) for inspection
+            for k in ("one", "XA", "XB", "P", "plan", "cnt", "cnt0", "graph_long", "reset"):
+                eng[k] = None
+
+    def _run_engine(self, X_curr, curr_preds):
+        """
+        Same schedule as the reference loop (pxmcmc/mcmc.py:157-181), but iterations between two events
+        (save / progress print) are advanced together: by HIP-graph replays when capture is available.
+        """
+        nburn, ngap, verb = int(self.nburn), int(self.ngap), int(self.verbosity)
+        self._engine_start(X_curr, curr_preds, 0)
+        try:
+            i = 0  # iterations done
+            j = 0
+            while j < self.nsamples:
+                # next iteration index (0-based) at which something observable happens
+                if i < nburn:
+                    nxt_save = nburn
+                elif ngap == 0:
+                    nxt_save = i
+                else:
+                    nxt_save = i + (-(i - nburn)) % ngap
+                nxt_print = i + (verb - 1 - i % verb) if verb > 0 else nxt_save
+                stop = min(nxt_save, nxt_print)
+                self._engine_advance(stop - i + 1)  # run iterations i..stop
+                i = stop
+                X_curr, curr_preds = self._engine_state()
+                if i >= nburn:
+                    if ngap == 0 or (i - nburn) % ngap == 0:
+                        if self._eng.get("plan") is None:  # generic engine: the operators' own plans
+                            self._check_device_status()
+                        logPi, L2, prior = self._logpi_dev(X_curr, curr_preds)
+                        self._tracking(j, X_curr, curr_preds, logPi, L2, prior)
+                        j += 1
+                    if verb > 0 and (i + 1) % verb == 0:
+                        first = (lambda a: a[j - 1] if self.nchains == 1 else a[0, j - 1])
+                        self._print_progress(j - 1, first(self.logPi), L2=first(self.L2s), prior=first(self.priors))
+                elif verb > 0 and (i + 1) % verb == 0:
+                    print("Burning in...")
+                i += 1
+            X_curr, curr_preds = self._engine_state()
+            self._check_device_status()
+            self.X_curr, self.curr_preds, self.niter = X_curr.clone(), curr_preds.clone(), i
+            self.used_graph = self._eng["graph"] is not None
+            self.graph_error = self._eng.get("graph_error")
+        finally:
+            self._engine_stop()
+        print("\nDONE")
 
 class _DevCounter:
     """caller-owned device iteration counter of the generic stepping engine (the fused engines use the plan's)"""
@@ -370,8 +510,6 @@ class MYULA(PxMCMC):
         return ops.as_device(w)
 
     # ---- HIP-graph engine for the fused wavelet path ----------------------------------------------
-    _GRAPH_PAIRS = 4  # iterations per graph replay = 2 * _GRAPH_PAIRS (fewer, longer launches of the host)
-
     def _graph_ok(self):
         return (self._fused_wav or self._generic_engine_ok()) and self.rng == "philox" and self.use_graph
 
@@ -464,93 +602,6 @@ class MYULA(PxMCMC):
         self._engine_capture(eng, X, preds, i0)
         return eng
 
-    def _engine_capture(self, eng, X, preds, i0):
-        """capture the two graphs of an engine (2 and 2 * _GRAPH_PAIRS iterations); state is (X, preds, i0) afterwards"""
-        eng["graph"] = eng["graph_long"] = None
-        if self._graph_ok():
-            try:
-                stream = torch.cuda.Stream()
-                stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(stream):
-                    eng["one"](eng["XA"], eng["XB"])  # warm-up outside capture (lazy allocations, attributes)
-                    eng["one"](eng["XB"], eng["XA"])
-                torch.cuda.current_stream().wait_stream(stream)
-                torch.cuda.synchronize()
-                eng["XA"].copy_(X)
-                eng["P"].copy_(preds)
-                eng["cnt"].set(eng["cnt0"](i0))
-                eng["reset"]()
-                # two graphs: 2 iterations (short advances between observable events) and 2 * _GRAPH_PAIRS
-                # iterations (long advances: fewer launches by the host).  A plan torn down while a capture is in
-                # progress (the garbage collector may run at any point) only queues its device frees: the
-                # library empties the queue at the end of the scope.
-                graphs = []
-                for pairs in (1, self._GRAPH_PAIRS):
-                    g = torch.cuda.CUDAGraph()
-                    with ops.capture_scope(), torch.cuda.graph(g):
-                        for _ in range(pairs):
-                            eng["one"](eng["XA"], eng["XB"])
-                            eng["one"](eng["XB"], eng["XA"])
-                    graphs.append(g)
-                # capture does not execute: state is still (X, preds, i0)
-                eng["graph"], eng["graph_long"] = graphs
-            except Exception as exc:  # capture unsupported in this environment: eager stepping, same results
-                eng["graph"] = eng["graph_long"] = None
-                eng["graph_error"] = repr(exc)
-                eng["XA"].copy_(X)
-                eng["P"].copy_(preds)
-                eng["cnt"].set(eng["cnt0"](i0))
-                eng["reset"]()
-
-    def _engine_advance(self, k):
-        """advance the engine's state by k MYULA iterations (graph replays of 2 * _GRAPH_PAIRS + eager remainder)"""
-        eng = self._eng
-        if eng["side"] == "B" and k > 0:  # realign so that replays start from XA
-            eng["one"](eng["XB"], eng["XA"])
-            eng["side"] = "A"
-            k -= 1
-        if eng["graph"] is not None:
-            per = 2 * self._GRAPH_PAIRS
-            while k >= per:
-                eng["graph_long"].replay()
-                eng["P_valid"] = not eng["ring"]
-                k -= per
-            while k >= 2:
-                eng["graph"].replay()
-                eng["P_valid"] = not eng["ring"]
-                k -= 2
-        while k >= 2:
-            eng["one"](eng["XA"], eng["XB"])
-            eng["one"](eng["XB"], eng["XA"])
-            k -= 2
-        if k == 1:
-            eng["one"](eng["XA"], eng["XB"])
-            eng["side"] = "B"
-
-    def _engine_state(self):
-        """(X, preds) of the current state as [C, .] arrays (pair-packed engines unpack here: observation only)"""
-        eng = self._eng
-        if eng["ring"] and not eng["P_valid"]:  # forward(X) of the carried rings, on demand
-            eng["plan"].ring_preds(eng["P"].shape[0], out=eng["P"])
-            eng["P_valid"] = True
-        # observation point: the host is about to read the state -- an expired device wait since the last one raises
-        if eng.get("plan") is not None:
-            eng["plan"].raise_on_fault()
-        X = eng["XA"] if eng["side"] == "A" else eng["XB"]
-        if eng["pairs"]:
-            return self._unpack(X), self._unpack(eng["P"])
-        return X, eng["P"]
-
-    def _engine_stop(self):
-        """unregister the iteration counter and drop the engine's buffers, graph and closures (the closures
-        reference the sampler: without this the plan would only be released by a later garbage collection)"""
-        eng = getattr(self, "_eng", None)
-        if eng is not None and eng.get("cnt") is not None:
-            eng["cnt"].close()
-            eng["graph"] = eng["graph"] is not None  # keep the flags (ring, pairs, graph) for inspection
-            for k in ("one", "XA", "XB", "P", "plan", "cnt", "cnt0", "graph_long", "reset"):
-                eng[k] = None
-
     def run(self, start_point=None):
         """Run the algorithm (pxmcmc/mcmc.py:150-183)."""
         self._prepare()
@@ -591,51 +642,6 @@ class MYULA(PxMCMC):
             X_curr, curr_preds = self._unpack(X_curr), self._unpack(curr_preds)
         self._check_device_status()
         self.X_curr, self.curr_preds, self.niter = X_curr, curr_preds, i
-        print("\nDONE")
-
-    def _run_engine(self, X_curr, curr_preds):
-        """
-        Same schedule as the reference loop (pxmcmc/mcmc.py:157-181), but iterations between two events
-        (save / progress print) are advanced together: by HIP-graph replays when capture is available.
-        """
-        nburn, ngap, verb = int(self.nburn), int(self.ngap), int(self.verbosity)
-        self._engine_start(X_curr, curr_preds, 0)
-        try:
-            i = 0  # iterations done
-            j = 0
-            while j < self.nsamples:
-                # next iteration index (0-based) at which something observable happens
-                if i < nburn:
-                    nxt_save = nburn
-                elif ngap == 0:
-                    nxt_save = i
-                else:
-                    nxt_save = i + (-(i - nburn)) % ngap
-                nxt_print = i + (verb - 1 - i % verb) if verb > 0 else nxt_save
-                stop = min(nxt_save, nxt_print)
-                self._engine_advance(stop - i + 1)  # run iterations i..stop
-                i = stop
-                X_curr, curr_preds = self._engine_state()
-                if i >= nburn:
-                    if ngap == 0 or (i - nburn) % ngap == 0:
-                        if self._eng.get("plan") is None:  # generic engine: the operators' own plans
-                            self._check_device_status()
-                        logPi, L2, prior = self._logpi_dev(X_curr, curr_preds)
-                        self._tracking(j, X_curr, curr_preds, logPi, L2, prior)
-                        j += 1
-                    if verb > 0 and (i + 1) % verb == 0:
-                        first = (lambda a: a[j - 1] if self.nchains == 1 else a[0, j - 1])
-                        self._print_progress(j - 1, first(self.logPi), L2=first(self.L2s), prior=first(self.priors))
-                elif verb > 0 and (i + 1) % verb == 0:
-                    print("Burning in...")
-                i += 1
-            X_curr, curr_preds = self._engine_state()
-            self._check_device_status()
-            self.X_curr, self.curr_preds, self.niter = X_curr.clone(), curr_preds.clone(), i
-            self.used_graph = self._eng["graph"] is not None
-            self.graph_error = self._eng.get("graph_error")
-        finally:
-            self._engine_stop()
         print("\nDONE")
 
     def chain_step(self, X, proxf, gradg):
@@ -917,3 +923,155 @@ class PxMALA(MYULA):
             return r
         v = complex(r[0].item())
         return v if v.imag != 0 else v.real
+
+
+def skrock_coefficients(s, eta=0.05):
+    """Recursion coefficients of SKROCK (Pereyra, Vargas-Mieles & Zygalakis, SIAM J. Imaging Sci. 13(2), 2020):
+    ``(omega_0, omega_1, mus, nus, ks)`` with ``mus / nus / ks`` indexed 0..s (entry 0 unused, as pxmcmc/mcmc.py:370-383).
+
+    omega_0 = 1 + eta / s^2, omega_1 = T_s(omega_0) / T_s'(omega_0); mu_1 = omega_1 / omega_0, nu_1 = s omega_1 / 2,
+    kappa_1 = s omega_1 / omega_0; for j >= 2 mu_j = 2 omega_1 T_{j-1}(omega_0) / T_j(omega_0),
+    nu_j = 2 omega_0 T_{j-1}(omega_0) / T_j(omega_0), kappa_j = 1 - nu_j."""
+    s = int(s)
+    w0 = 1 + eta / (s * s)
+    T = [1.0, w0]  # T_j(w0) by the three-term recurrence
+    U = [1.0, 2 * w0]  # U_j(w0): T_s'(x) = s U_{s-1}(x)
+    for _ in range(2, s + 1):
+        T.append(2 * w0 * T[-1] - T[-2])
+        U.append(2 * w0 * U[-1] - U[-2])
+    w1 = T[s] / (s * U[s - 1])
+    mus, nus, ks = np.zeros(s + 1), np.zeros(s + 1), np.zeros(s + 1)
+    mus[1], nus[1], ks[1] = w1 / w0, s * w1 / 2, s * w1 / w0
+    for j in range(2, s + 1):
+        ratio = T[j - 1] / T[j]
+        mus[j] = 2 * w1 * ratio
+        nus[j] = 2 * w0 * ratio
+        ks[j] = 1 - nus[j]
+    return w0, w1, mus, nus, ks
+
+
+class SKROCK(PxMCMC):
+    """
+    The SKROCK chain (pxmcmc/mcmc.py:292-383): ``s`` gradient evaluations per iteration along a Chebyshev recursion, which
+    in return admits a step ``delta`` about ``s^2`` times larger on the stiff part of the posterior; no accept step.
+
+    .. note::
+
+       The recursion is the published one (Pereyra, Vargas-Mieles & Zygalakis 2020, :func:`skrock_coefficients`), not
+       the reference's literal code, which diverges for ``s >= 2``: it divides by ``T_j(omega_1)`` instead of
+       ``T_j(omega_0)`` (mcmc.py:380), sets ``kappa_j = 1 - nu_0`` instead of ``1 - nu_j`` (mcmc.py:383) and adds
+       ``kappa_s`` as a scalar minus ``K_{s-2}`` instead of ``kappa_s K_{s-2}`` (mcmc.py:364-367).  For ``s = 1`` the two
+       agree exactly.
+
+    One iteration, with ``Z ~ N(0, I)`` (``+ i N(0, I)`` when ``params.complex``) and
+    ``grad log pi(U) = -(U - proxf(U)) / lmda - calc_gradg(forward(U))`` (mcmc.py:84-89)::
+
+        K_0 = X
+        K_1 = X + mu_1 delta grad log pi(X + nu_1 sqrt(2 delta) Z) + kappa_1 sqrt(2 delta) Z
+        K_j = mu_j delta grad log pi(K_{j-1}) + nu_j K_{j-1} + kappa_j K_{j-2}     (j = 2..s)
+        X'  = K_s
+
+    Every stage is one HIP kernel (``pxm_skrock_stage``; the stock synthesis L1 prox is formed inside it); the Philox
+    noise of stages 0 and 1 is regenerated from the same counters.  ``forward(X')`` is formed only where it is observed.
+    The keywords ``nchains / rng / seed / chain_offset / use_graph / noise_bits`` are MYULA's; ``real_pairs`` (and
+    ``ring_shortcut``) are accepted and have no effect: the state stays in the reference layout.
+    """
+
+    def __init__(self, forward, prox, mcmcparams=PxMCMCParams(), **kwargs):
+        super().__init__(forward, prox, mcmcparams, **kwargs)
+        s = self.s
+        if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)) or s < 1:
+            raise ValueError("SKROCK needs an integer number of stages s >= 1")
+        self.s = int(s)
+        self.eta = 0.05
+        self.omega_0, self.omega_1, self.mus, self.nus, self.ks = skrock_coefficients(self.s, self.eta)
+        self._it = 0
+
+    # ---- one iteration on device buffers ----------------------------------------------------------------
+    def _stage_coefs(self):
+        """(a, b, c, e, r) of stage 0, stage 1 and stages 2..s: out = a U + b P + c gradg + e V + r Z"""
+        d, l = float(self.delta), self.lmda
+        sq = np.sqrt(2 * d)
+        m1 = self.mus[1] * d
+        coefs = [(1.0, 0.0, 0.0, 0.0, self.nus[1] * sq), (-m1 / l, m1 / l, -m1, 1.0, self.ks[1] * sq)]
+        for j in range(2, self.s + 1):
+            m = self.mus[j] * d
+            coefs.append((self.nus[j] - m / l, m / l, -m, self.ks[j], 0.0))
+        return coefs
+
+    def _iterate(self, X, out, Y, KA, KB, noise, it, iter_dev):
+        """X' = K_s of one iteration into ``out`` (Y, KA, KB: scratch of X's shape; none of them aliases X or out)"""
+        f = self.forward
+        coefs = self._stage_coefs()
+        fused = _is_stock_l1(self.prior)
+        T = self.prior.T_dev if fused else None
+        kw = dict(noise=noise, noise_complex=bool(self.complex), seed=self.seed, chain0=self.chain_offset, it=it,
+                  iter_dev=iter_dev, noise64=self.noise64)
+        ops.skrock_stage(X, *coefs[0], out=Y, **kw)  # Y = X + nu_1 sqrt(2 delta) Z
+        bufs = (out, KA, KB)  # K_j lives in bufs[(s - j) % 3]: K_s lands in out
+        s = self.s
+        for j in range(1, s + 1):
+            U = Y if j == 1 else bufs[(s - j + 1) % 3]
+            V = X if j <= 2 else bufs[(s - j + 2) % 3]
+            g = ops.as_device(f.calc_gradg(ops.as_device(f.forward(U))), U.dtype)
+            px = None if fused else ops.as_device(self.prior.proxf(U), U.dtype)
+            # (stage 1 regenerates stage 0's Z from the same counters; stages j >= 2 have r = 0: no noise term)
+            ops.skrock_stage(U, *coefs[j], T=T, proxf=px, gradg=g, V=V, out=bufs[(s - j) % 3], **kw)
+        return out
+
+    def chain_step(self, X):
+        """
+        Takes a step in the chain (pxmcmc/mcmc.py:338-347): draws Z and runs the s-stage recursion.
+
+        :param X: current sample ([N] or a [C, N] batch; numpy or device array)
+        """
+        x, squeeze = ops._batched(ops.as_device(X, self._state_dtype(X)))
+        noise = None
+        if self.rng == "numpy":
+            noise = self._host_noise(x)
+        else:
+            self._it += 1
+        Y, KA, KB, out = (torch.empty_like(x) for _ in range(4))
+        self._iterate(x, out, Y, KA, KB, noise, self._it, None)
+        out = out[0] if squeeze else out
+        return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
+
+    # ---- stepping engine ------------------------------------------------------------------------------------
+    def _graph_ok(self):
+        return self.rng == "philox" and self.use_graph and type(self).chain_step is SKROCK.chain_step
+
+    def _engine_start(self, X, preds, i0):
+        """static state (XA, XB, P; Y and two rotating K buffers), a device iteration counter and, with the Philox stream,
+        captured graphs of 2 and 2 * _GRAPH_PAIRS iterations.  preds (P) is formed on demand only."""
+        self._engine_stop()
+        X = ops.as_device(X).contiguous()
+        self._eng = eng = {"pairs": False, "plan": None, "ring": False, "lazy": True, "P_valid": True, "side": "A",
+                           "generic": True}
+        eng["XA"], eng["XB"], eng["P"] = X.clone(), torch.empty_like(X), ops.as_device(preds).clone()
+        eng["cnt"] = _DevCounter(i0)
+        eng["cnt0"] = lambda i: i
+        eng["reset"] = lambda: None
+        Y, KA, KB = (torch.empty_like(X) for _ in range(3))
+        numpy_rng = self.rng == "numpy"
+        own_step = type(self).chain_step is not SKROCK.chain_step
+
+        def one(src, dst):
+            if own_step:  # a subclass's chain_step: eager, through it
+                dst.copy_(ops.as_device(self.chain_step(src), dst.dtype))
+            else:
+                noise = self._host_noise(src) if numpy_rng else None
+                self._iterate(src, dst, Y, KA, KB, noise, 0, eng["cnt"].t)
+                eng["cnt"].add(1)
+            eng["P_valid"] = False
+
+        eng["one"] = one
+        self._engine_capture(eng, X, preds, i0)
+        return eng
+
+    def run(self, start_point=None):
+        """Run the algorithm (pxmcmc/mcmc.py:308-336): the reference's schedule and tracking arrays; iterations between
+        two observable events (save / progress print) are advanced together, from a captured HIP graph with the device
+        Philox stream."""
+        self._it = 0
+        X_curr, curr_preds = self._initial_sample(start_point)
+        return self._run_engine(X_curr, curr_preds)

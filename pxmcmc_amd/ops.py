@@ -198,6 +198,38 @@ def chain_step(X, proxf, gradg, delta, lmda, noise=None, noise_complex=False, se
     return out[0] if squeeze else out
 
 
+def skrock_stage(U, a, b=0.0, c=0.0, e=0.0, r=0.0, T=None, proxf=None, gradg=None, V=None, noise=None, noise_complex=False,
+                 seed=0, chain0=0, it=0, iter_dev=None, out=None, noise64=False):
+    """One stage of the SKROCK recursion (pxmcmc/mcmc.py:349-368, paper coefficients): ``out = a U + b P + c gradg + e V + r Z``.
+
+    P (when ``b != 0``): ``proxf`` if given, else ``soft(U, T)`` formed in the kernel.  ``gradg`` / ``V``: optional.
+    Z (when ``r != 0``): ``noise`` if given, else the device Philox stream of :func:`myula_step` at (seed, chain0 + c, it)
+    [+ ``*iter_dev``].  ``out``: result buffer (must not alias an input)."""
+    u, squeeze = _batched(as_device(U))
+    args = []
+    for t in (proxf if b != 0 else None, gradg, V):
+        if t is None:
+            args.append(None)
+            continue
+        t, _ = _batched(as_device(t, u.dtype))
+        if t.shape != u.shape:
+            raise ValueError("skrock_stage: proxf / gradg / V must have the state's shape")
+        args.append(t)
+    px, g, v = args
+    if b != 0 and px is None and T is None:
+        raise ValueError("skrock_stage: a prox term needs proxf or the threshold T")
+    Tv, Ts = _vecT(T, u.shape[1], u.device) if (b != 0 and px is None) else (None, 0.0)
+    w, wc = _noise_args(noise, u, noise_complex) if r != 0 else (None, int(bool(noise_complex)))
+    out = torch.empty_like(u) if out is None else _out_like(out, u)
+    check(
+        lib.pxm_skrock_stage_it(
+            _p(u), _p(px), _p(Tv), Ts, _p(g), _p(v), float(a), float(b), float(c), float(e), float(r), _p(w), wc | _nf(noise64),
+            seed, chain0, it, _p(iter_dev), _p(out), u.shape[1], u.shape[0], _dt(u), _stream()
+        )
+    )
+    return out[0] if squeeze else out
+
+
 def randn(n, C_=1, complex_=False, seed=0, chain0=0, it=0, noise64=False):
     """N(0,1) draws of the device Philox stream keyed (seed, chain0 + c, it); noise64: Box-Muller in double precision"""
     out = torch.empty((C_, n), dtype=_CPLX if complex_ else _REAL, device=device())
