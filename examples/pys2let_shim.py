@@ -22,6 +22,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = C.CDLL(os.environ.get("PXM_LIB_PATH") or os.path.join(_HERE, "..", "pxmcmc_amd", "lib", "libpxmcmc_amd.so"))
 _LIB.pxm_last_error.restype = C.c_char_p
 _LIB.pxm_wav_ncoefs.restype = C.c_int64
+_LIB.pxm_dwav_ncoefs.restype = C.c_int64
+_LIB.pxm_dwav_ncoefs.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]
 _vp = C.c_void_p
 
 
@@ -36,22 +38,32 @@ def _stream():
 
 
 class _Wavelets:
-    """one `pxm_wav_plan` per (L, B, J_min): pys2let is stateless, the plans are cached here"""
+    """one `pxm_wav_plan` (N = 1) or `pxm_dwav_plan` (N > 1, directional) per (L, B, J_min, N): pys2let is stateless,
+    the plans are cached here"""
 
     cache = {}
 
-    def __init__(self, L, B, J_min):
+    def __init__(self, L, B, J_min, N=1):
         self.plan = _vp()
-        _ok(_LIB.pxm_wav_plan_create(int(L), C.c_double(B), int(J_min), 1, 0, C.byref(self.plan)))
+        self.N = N
         nscal = C.c_int64()
-        self.ncoefs = int(_ok(_LIB.pxm_wav_ncoefs(int(L), C.c_double(B), int(J_min), C.byref(nscal))))
+        if N == 1:
+            _ok(_LIB.pxm_wav_plan_create(int(L), C.c_double(B), int(J_min), 1, 0, C.byref(self.plan)))
+            self.ncoefs = int(_ok(_LIB.pxm_wav_ncoefs(int(L), C.c_double(B), int(J_min), C.byref(nscal))))
+        else:  # f_wav: the 2N - 1 orientation planes of every scale, one flat vector (DESIGN.md section 11)
+            _ok(_LIB.pxm_dwav_plan_create(int(L), C.c_double(B), int(J_min), int(N), 1, 0, C.byref(self.plan)))
+            self.ncoefs = int(_ok(_LIB.pxm_dwav_ncoefs(int(L), B, int(J_min), int(N), C.byref(nscal))))
         self.nscal, self.npix = int(nscal.value), L * (2 * L - 1)
+
+    def fn(self, name):
+        """the C entry point of one of the four transforms for this plan's kind"""
+        return getattr(_LIB, ("pxm_wav_" if self.N == 1 else "pxm_dwav_") + name)
 
     @classmethod
     def get(cls, B, L, J_min, N=1, spin=0, upsample=0):
-        if N != 1 or spin != 0 or upsample != 0:  # the reference's own defaults (pxmcmc/transforms.py:71,79-86)
-            raise NotImplementedError("pys2let_shim: axisymmetric (N=1), spin-0, multiresolution (upsample=0) wavelets only")
-        key = (int(L), float(B), int(J_min))
+        if spin != 0 or upsample != 0:  # the reference's own defaults (pxmcmc/transforms.py:71,79-86)
+            raise NotImplementedError("pys2let_shim: spin-0, multiresolution (upsample=0) wavelets only")
+        key = (int(L), float(B), int(J_min), int(N))
         if key not in cls.cache:
             cls.cache[key] = cls(*key)
         return cls.cache[key]
@@ -103,25 +115,25 @@ def pys2let_j_max(B, L, J_min):
 def analysis_px2wav(f, B, L, J_min, N=1, spin=0, upsample=0):
     """pxmcmc/transforms.py:111,164 -> (f_wav, f_scal)"""
     w = _Wavelets.get(B, L, J_min, N, spin, upsample)
-    return w.split(w.call(_LIB.pxm_wav_analysis, f, w.npix, w.ncoefs))
+    return w.split(w.call(w.fn("analysis"), f, w.npix, w.ncoefs))
 
 
 def analysis_adjoint_wav2px(f_wav, f_scal, B, L, J_min, N=1, spin=0, upsample=0):
     """pxmcmc/transforms.py:153 -> f"""
     w = _Wavelets.get(B, L, J_min, N, spin, upsample)
-    return w.call(_LIB.pxm_wav_analysis_adjoint, np.concatenate((f_scal, np.ravel(f_wav, order="F"))), w.ncoefs, w.npix)
+    return w.call(w.fn("analysis_adjoint"), np.concatenate((f_scal, np.ravel(f_wav, order="F"))), w.ncoefs, w.npix)
 
 
 def synthesis_wav2px(f_wav, f_scal, B, L, J_min, N=1, spin=0, upsample=0):
     """pxmcmc/transforms.py:126 -> f"""
     w = _Wavelets.get(B, L, J_min, N, spin, upsample)
-    return w.call(_LIB.pxm_wav_synthesis, np.concatenate((f_scal, np.ravel(f_wav, order="F"))), w.ncoefs, w.npix)
+    return w.call(w.fn("synthesis"), np.concatenate((f_scal, np.ravel(f_wav, order="F"))), w.ncoefs, w.npix)
 
 
 def synthesis_adjoint_px2wav(f, B, L, J_min, N=1, spin=0, upsample=0):
     """pxmcmc/transforms.py:138 -> (f_wav, f_scal)"""
     w = _Wavelets.get(B, L, J_min, N, spin, upsample)
-    return w.split(w.call(_LIB.pxm_wav_synthesis_adjoint, f, w.npix, w.ncoefs))
+    return w.split(w.call(w.fn("synthesis_adjoint"), f, w.npix, w.ncoefs))
 
 
 # ---- pyssht (MW sampling, the reference's default Method) -----------------------------------------------------------

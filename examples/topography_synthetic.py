@@ -37,6 +37,7 @@ def main(argv=None):
     ap.add_argument("--ngap", type=int, default=100)
     ap.add_argument("--nburn", type=int, default=0)
     ap.add_argument("--chains", type=int, default=1, help="independent chains batched on the GPU")
+    ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
     ap.add_argument("--outdir", type=str, default=".")
     ap.add_argument("--jobid", type=str, default="0")
     args = ap.parse_args(argv)
@@ -56,7 +57,8 @@ def main(argv=None):
     truth /= np.sqrt(np.mean(truth ** 2))
     data = truth + args.sigma * rng.normal(size=truth.size)
 
-    forwardop = SphericalWaveletTransformOperator(data, args.sigma, setting, L, B, J_min, max_chains=args.chains)
+    forwardop = SphericalWaveletTransformOperator(data, args.sigma, setting, L, B, J_min, dirs=args.dirs,
+                                                 max_chains=args.chains)
     lmda = 1e-6
     # step size inside the MYULA bound 1 / (L_f + 1 / lmda), L_f = ||S||^2 / sigma^2 (power iteration)
     import torch
@@ -73,7 +75,7 @@ def main(argv=None):
     params = PxMCMCParams(nsamples=args.nsamples, nburn=args.nburn, ngap=args.ngap, delta=delta, lmda=lmda, mu=args.mu,
                           s=args.s, complex=False, verbosity=max(1, args.ngap * 10))
     regulariser = S2_Wavelets_L1(setting, forwardop.transform.inverse, forwardop.transform.inverse_adjoint,
-                                 params.lmda * params.mu, L=L, B=B, J_min=J_min)
+                                 params.lmda * params.mu, L=L, B=B, J_min=J_min, dirs=args.dirs)
     print(f"Number of data points: {len(data)}")
     print(f"Number of model parameters: {forwardop.nparams}")
     cls = {"myula": MYULA, "pxmala": PxMALA, "skrock": SKROCK}[args.algo]

@@ -79,6 +79,7 @@ def main(argv=None):
     ap.add_argument("--ngap", type=int, default=50)
     ap.add_argument("--nburn", type=int, default=100)
     ap.add_argument("--chains", type=int, default=1, help="independent chains batched on the GPU")
+    ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
     ap.add_argument("--seed", type=int, default=3)
     args = ap.parse_args(argv)
 
@@ -89,13 +90,13 @@ def main(argv=None):
     measurement = WeakLensing(L, mask, ngal=np.full_like(mask, 30), max_chains=args.chains)
     gammas_truth, kappa_truth = prepare_gammas(synthetic_kappa_lm(L, args.seed), L, measurement)
 
-    transform = SphericalWaveletTransform(L, B, J_min, max_chains=args.chains)
+    transform = SphericalWaveletTransform(L, B, J_min, dirs=args.dirs, max_chains=args.chains)
     forward_operator = ForwardOperator(gammas_truth, 1 / measurement.inv_cov, setting, transform=transform,
                                        measurement=measurement, nparams=transform.ncoefs)
     params = PxMCMCParams(nsamples=args.nsamples, nburn=args.nburn, ngap=args.ngap, delta=args.delta, lmda=args.delta / 2,
                           mu=args.mu, s=args.s, complex=False, verbosity=max(1, args.ngap * 10))
     prior = S2_Wavelets_L1(setting, transform.inverse, transform.inverse_adjoint, params.lmda * params.mu, L=L, B=B,
-                           J_min=J_min)
+                           J_min=J_min, dirs=args.dirs)
     print(f"Number of data points: {gammas_truth.size}")
     print(f"Number of model parameters: {forward_operator.nparams}")
     if args.algo == "myula":

@@ -34,6 +34,7 @@ extern "C" {
 
 typedef struct pxm_sht_plan_s* pxm_sht_plan_t;
 typedef struct pxm_wav_plan_s* pxm_wav_plan_t;
+typedef struct pxm_dwav_plan_s* pxm_dwav_plan_t;
 typedef void* pxm_stream_t; /* hipStream_t */
 
 /* ---- library ------------------------------------------------------------ */
@@ -131,6 +132,29 @@ int pxm_wav_synthesis_adjoint(pxm_wav_plan_t plan, const void* f, void* X, int C
 int pxm_wav_analysis(pxm_wav_plan_t plan, const void* f, void* X, int C, pxm_stream_t stream);
 int pxm_wav_analysis_adjoint(pxm_wav_plan_t plan, const void* X, void* f, int C, pxm_stream_t stream);
 int64_t pxm_wav_table_bytes(pxm_wav_plan_t plan, int op /*0 synthesis,1 synthesis_adjoint*/);
+
+/* ---- directional scale-discretised wavelet transform (N = dirs >= 1, spin 0, upsample=0) ------------------------
+ * replaces pys2let.synthesis_wav2px / synthesis_adjoint_px2wav / analysis_px2wav / analysis_adjoint_wav2px with
+ * N > 1 (pxmcmc/transforms.py:95-98).  X: [C][ncoefs] c128, f: [C][L*(2L-1)] c128.  Layout
+ * [scaling | j = J_min .. J_max]: the scaling block is the MW grid at bl_scal; block j holds 2N-1 MW grids at bl_j,
+ * orientation-major [c][theta][phi] with gamma_c = 2 pi c / (2N-1).  With N = 1 the layout and the values are those of
+ * the pxm_wav_* plan.  The plan owns its inner SHT plans (one per (bl_j, -n)), the spin-0 plan at L and all scratch:
+ * nothing is allocated after creation; every call is enqueued on the given stream (graph-capturable). */
+int pxm_dwav_plan_create(int L, double B, int J_min, int N, int max_chains, unsigned flags, pxm_dwav_plan_t* plan);
+int pxm_dwav_plan_destroy(pxm_dwav_plan_t plan);
+int pxm_dwav_synthesis(pxm_dwav_plan_t plan, const void* X, void* f, int C, pxm_stream_t stream);
+int pxm_dwav_synthesis_adjoint(pxm_dwav_plan_t plan, const void* f, void* X, int C, pxm_stream_t stream);
+int pxm_dwav_analysis(pxm_dwav_plan_t plan, const void* f, void* X, int C, pxm_stream_t stream);
+int pxm_dwav_analysis_adjoint(pxm_dwav_plan_t plan, const void* X, void* f, int C, pxm_stream_t stream);
+/* host-only: number of coefficients of the directional layout (pxmcmc/transforms.py:156-166), scaling block in *nscal_out */
+int64_t pxm_dwav_ncoefs(int L, double B, int J_min, int N, int64_t* nscal_out);
+/* device bytes of the tables the plan reads: its inner plans' Wigner tables (shared per (L, spin)) + its own weights and
+ * phases */
+int64_t pxm_dwav_table_bytes(pxm_dwav_plan_t plan);
+/* OR of the status words of the inner SHT plans (as pxm_sht_status); synchronises */
+int pxm_dwav_status(pxm_dwav_plan_t plan, int clear, pxm_stream_t stream);
+/* launch shapes (test / timing aid): (block, n) items, workgroups per chain of the harmonic-split and gamma launches */
+int pxm_dwav_plan_info(pxm_dwav_plan_t plan, int* nitems, int* split_blocks, int* gamma_blocks);
 
 /* Device-resident Philox iteration counter OF ONE PLAN (HIP-graph replay of the MYULA step): when registered,
  * the plan's fused steps use iteration = iter + *counter, read on the device at execution time, so a captured

@@ -62,6 +62,16 @@ SIGNATURES = {
     "pxm_sht_inverse_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
     "pxm_sht_forward_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
     "pxm_sht_table_bytes": (c_i64, [c_vp, c_int]),
+    "pxm_dwav_plan_create": (c_int, [c_int, c_dbl, c_int, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),
+    "pxm_dwav_plan_destroy": (c_int, [c_vp]),
+    "pxm_dwav_synthesis": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_dwav_synthesis_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_dwav_analysis": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_dwav_analysis_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_dwav_ncoefs": (c_i64, [c_int, c_dbl, c_int, c_int, c_vp]),
+    "pxm_dwav_table_bytes": (c_i64, [c_vp]),
+    "pxm_dwav_status": (c_int, [c_vp, c_int, c_vp]),
+    "pxm_dwav_plan_info": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "pxm_wav_plan_create": (c_int, [c_int, c_dbl, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),
     "pxm_wav_plan_destroy": (c_int, [c_vp]),
     "pxm_wav_synthesis": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),

@@ -431,6 +431,7 @@ class MYULA(PxMCMC):
             and hasattr(getattr(f, "invcov", None), "diag")  # (a full covariance matrix goes through the generic kernels)
             and type(f).calc_gradg.__qualname__.startswith("ForwardOperator")
             and isinstance(getattr(f, "transform", None), SphericalWaveletTransform)
+            and f.transform.dirs == 1  # (the fused steps are WavPlan's: axisymmetric only)
             and isinstance(getattr(f, "measurement", None), Identity)
             and f.measurement.ndata == f.measurement.npix
             and _is_stock_l1(self.prior)

@@ -792,6 +792,61 @@ class WavPlan:
         return (ms.value, nl.value, nb.value, nf.value), (dms.value, dnl.value, dnb.value)
 
 
+class DirWavPlan:
+    """Directional (N = dirs >= 1) scale-discretised wavelet transforms, spin 0 (replaces the pys2let calls with N > 1;
+    include/pxmcmc_amd.h, pxm_dwav_*).  Layout [scaling | j = J_min .. J_max], block j = 2N - 1 orientation planes of
+    the MW grid at bl_j.  With N = 1 it computes what :class:`WavPlan` computes (without WavPlan's fused sampler steps)."""
+
+    def __init__(self, L, B, J_min, N, max_chains=1):
+        require_gpu()
+        self.L, self.B, self.J_min, self.N, self.max_chains = int(L), float(B), int(J_min), int(N), int(max_chains)
+        self.npix = L * (2 * L - 1)
+        nscal = C.c_int64()
+        self.ncoefs = int(check(lib.pxm_dwav_ncoefs(self.L, self.B, self.J_min, self.N, C.byref(nscal))))
+        self.nscal = int(nscal.value)
+        h = C.c_void_p()
+        check(lib.pxm_dwav_plan_create(self.L, self.B, self.J_min, self.N, self.max_chains, 0, C.byref(h)))
+        self._h = h
+        _register_plan(self)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and lib is not None:
+            lib.pxm_dwav_plan_destroy(h)
+            self._h = None
+
+    _run = WavPlan._run
+
+    def synthesis(self, X, out=None):
+        return self._run(lib.pxm_dwav_synthesis, X, self.ncoefs, self.npix, out=out)
+
+    def synthesis_adjoint(self, f):
+        return self._run(lib.pxm_dwav_synthesis_adjoint, f, self.npix, self.ncoefs)
+
+    def analysis(self, f):
+        return self._run(lib.pxm_dwav_analysis, f, self.npix, self.ncoefs)
+
+    def analysis_adjoint(self, X):
+        return self._run(lib.pxm_dwav_analysis_adjoint, X, self.ncoefs, self.npix)
+
+    def table_bytes(self):
+        """device bytes of the tables the plan reads (inner Wigner tables + its own weights and phases)"""
+        return int(lib.pxm_dwav_table_bytes(self._h))
+
+    def info(self):
+        """(items, split workgroups per chain, gamma workgroups per chain)"""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        check(lib.pxm_dwav_plan_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def status(self, clear=False):
+        """bit mask of the bounded device waits of the inner SHT plans that expired (0 = none); synchronises"""
+        return int(check(lib.pxm_dwav_status(self._h, int(bool(clear)), _stream())))
+
+    def raise_on_fault(self, clear=True):
+        raise_on_status(self.status(clear=clear), f"DirWavPlan(L={self.L}, N={self.N})")
+
+
 # ---- device-resident iteration counter (HIP-graph replay) -----------------------------------
 class IterCounter:
     """A device int64 registered as the Philox iteration counter of ONE wavelet plan for the lifetime of the

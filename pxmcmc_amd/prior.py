@@ -63,6 +63,10 @@ class L1:
 class S2_Wavelets_L1(L1):
     """
     L1 regulariser for wavelets on S2 with MW quadrature weighting (pxmcmc/prior.py:56-84).
+
+    ``dirs = N > 1`` (extension): every orientation plane of scale j carries that scale's ``mw_map_weights(bl_j)``, so
+    ``len(map_weights) == ncoefs`` of the directional layout.  The reference builds one grid of weights per scale
+    whatever N is, a vector of the wrong length for N > 1.
     """
 
     def __init__(self, setting, fwd, adj, T, L, B, J_min, dirs=1, spin=0):
@@ -76,7 +80,8 @@ class S2_Wavelets_L1(L1):
         self.spin = spin
         if setting == "synthesis":
             bls = _multires_bandlimits(L, B, J_min, dirs, spin)
-            self.map_weights = np.concatenate([mw_map_weights(int(el)) for el in bls])
+            planes = [1] + [2 * int(dirs) - 1] * (len(bls) - 1)
+            self.map_weights = np.concatenate([np.tile(mw_map_weights(int(el)), k) for el, k in zip(bls, planes)])
         else:
             raise NotImplementedError
         self.T = self.T * self.map_weights
@@ -95,6 +100,9 @@ class S2_Wavelets_L1_Power_Weights(S2_Wavelets_L1):
     """
 
     def __init__(self, setting, fwd, adj, T, L, B, J_min, dirs=1, spin=0, eta=1):
+        if dirs != 1:
+            # the reference reads the power and peak of psi_{l0}, identically zero for even N
+            raise NotImplementedError("S2_Wavelets_L1_Power_Weights: directional wavelets (dirs > 1) are not supported")
         super().__init__(setting, fwd, adj, T, L, B, J_min, dirs, spin)
         self.eta = eta
         if setting != "synthesis":

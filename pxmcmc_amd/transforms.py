@@ -46,7 +46,8 @@ class IdentityTransform(Transform):
 
 class SphericalWaveletTransform(Transform):
     """
-    Spherical wavelet transforms (pxmcmc/transforms.py:59-166), pixel space, ``upsample=0``.
+    Spherical wavelet transforms (pxmcmc/transforms.py:59-166), pixel space, ``upsample=0``, spin 0.  ``dirs = N > 1``:
+    directional wavelets; each wavelet block holds 2N - 1 orientation planes.
 
     :param int max_chains: largest chain batch the transform will be called with (extension)
     """
@@ -55,8 +56,10 @@ class SphericalWaveletTransform(Transform):
         if harmonic:
             # the harmonic variants are not in released pys2let either (reference tests/test_transforms.py:9-11)
             raise NotImplementedError("harmonic=True is out of scope (SURVEY.md section 2, row 3)")
-        if dirs != 1 or spin != 0:
-            raise NotImplementedError("only axisymmetric (dirs=1), spin-0 wavelets are on the hot path")
+        if spin != 0:
+            raise NotImplementedError("only spin-0 wavelets are on the hot path (spin wavelets: DESIGN.md section 11)")
+        if int(dirs) != dirs or dirs < 1:
+            raise ValueError("dirs must be a positive integer")
         self.L = L
         self.B = B
         self.J_min = J_min
@@ -66,14 +69,20 @@ class SphericalWaveletTransform(Transform):
         self.spin = spin
         self.params = {"B": B, "L": L, "J_min": J_min, "N": dirs, "spin": spin, "upsample": 0}
         self.max_chains = max_chains
-        self._plan = ops.WavPlan(L, B, J_min, max_chains=max_chains)
+        self._plan = self._make_plan(max_chains)
         self._get_ncoefs()
+
+    def _make_plan(self, C):
+        """dirs = 1: the axisymmetric plan with the fused sampler steps; dirs > 1: the directional plan (SO(3) stages)"""
+        if self.dirs == 1:
+            return ops.WavPlan(self.L, self.B, self.J_min, max_chains=C)
+        return ops.DirWavPlan(self.L, self.B, self.J_min, int(self.dirs), max_chains=C)
 
     def ensure_chains(self, C):
         """Grow the plan's chain capacity (workspace is allocated at plan creation)."""
         if C > self.max_chains:
             self.max_chains = C
-            self._plan = ops.WavPlan(self.L, self.B, self.J_min, max_chains=C)
+            self._plan = self._make_plan(C)
 
     def forward(self, X):
         """image -> wavelet coefficients (pys2let.analysis_px2wav, transforms.py:101-112)."""

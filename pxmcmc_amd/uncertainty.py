@@ -22,18 +22,22 @@ def credible_interval_range(chain, alpha=0.05):
     return np.diff(quantiles, axis=0)[0]
 
 
-def wavelet_credible_interval_range(chain, L, B, J_min, alpha=0.05):
+def wavelet_credible_interval_range(chain, L, B, J_min, alpha=0.05, dirs=1):
     """credible-interval maps per wavelet scale, MW (theta, phi) format (pxmcmc/uncertainty.py:19-40): the quantile
-    range of every coefficient at once, cut at the block boundaries of the coefficient vector"""
+    range of every coefficient at once, cut at the block boundaries of the coefficient vector.  ``dirs = N > 1``
+    (extension): wavelet block j comes back as (2N - 1, bl_j, 2 bl_j - 1), one map per orientation."""
     bls = [int(bl) for bl in _multires_bandlimits(L, B, J_min)]
-    edges = np.cumsum([mw_size(bl) for bl in bls])
+    planes = [1] + [2 * int(dirs) - 1] * (len(bls) - 1)
+    edges = np.cumsum([k * mw_size(bl) for bl, k in zip(bls, planes)])
     on_device = isinstance(chain, torch.Tensor) and chain.is_cuda
     chain = chain if on_device else np.asarray(chain)
     if chain.shape[1] != edges[-1]:
         raise ValueError("chain has %d parameters, the wavelet layout %d" % (chain.shape[1], edges[-1]))
     ci = credible_interval_range(chain, alpha)
     blocks = np.split(ci.cpu().numpy() if on_device else ci, edges[:-1])
-    return [blk.reshape(bl, 2 * bl - 1) for blk, bl in zip(blocks, bls)]
+    if dirs == 1:
+        return [blk.reshape(bl, 2 * bl - 1) for blk, bl in zip(blocks, bls)]
+    return [blk.reshape(bl, 2 * bl - 1) if k == 1 else blk.reshape(k, bl, 2 * bl - 1) for blk, bl, k in zip(blocks, bls, planes)]
 
 
 def credible_region_threshold(logpis, alpha=0.05):

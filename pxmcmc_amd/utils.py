@@ -54,20 +54,45 @@ def _multires_bandlimits(L, B, J_min, dirs=1, spin=0):
     return np.array([int(np.nonzero(r)[0].max()) + 1 for r in rows], dtype=int)
 
 
+def dir_component(L, N):
+    """[ext] the directionality component s_lm [L*L] of s2let's directional wavelets:
+    ``nu sqrt(2^-g C(g, (g - m)/2))`` for m = -g, -g + 2, .., g with g = gamma_l the largest integer <= min(N - 1, l) of
+    the parity of N - 1, 0 elsewhere; nu = 1 for odd N, i for even N.  N = 1: s_l0 = 1."""
+    from math import comb
+
+    s = np.zeros(L * L, dtype=complex)
+    nu = 1.0 if N % 2 else 1j
+    for el in range(L):
+        g = min(N - 1, el)
+        if (N - 1 - g) % 2:
+            g -= 1
+        if g < 0:
+            continue
+        for m in range(-g, g + 1, 2):
+            s[el * el + el + m] = nu * np.sqrt(2.0 ** -g * comb(g, (g - m) // 2))
+    return s
+
+
 def wavelet_tiling(B, L, N=1, J_min=0, spin=0):
-    """[ext] pys2let.wavelet_tiling (pxmcmc/utils.py:117, prior.py:121,132) for axisymmetric spin-0 wavelets:
+    """[ext] pys2let.wavelet_tiling (pxmcmc/utils.py:117, prior.py:121,132) for spin-0 wavelets:
     ``phi_l[L] = sqrt((2l+1)/4pi) kappa0(l)`` and ``psi_lm[L*L, nscales]`` with
-    ``psi_{l0} = sqrt((2l+1)/8pi^2) kappa_j(l)``, one column per scale j = J_min..J_max.  The harmonic
-    normalisation is parity-unpinned; only supports, ``sum |.|^2`` and peak degrees
-    are consumed by the callers."""
-    if N != 1 or spin != 0:
-        raise NotImplementedError("only axisymmetric (N=1), spin-0 wavelets are on the hot path")
+    ``psi_lm = sqrt((2l+1)/8pi^2) kappa_j(l) s_lm``, one column per scale j = J_min..J_max; s_lm is the directionality
+    component (:func:`dir_component`, s_l0 = 1 for N = 1).  The harmonic normalisation is parity-unpinned (DESIGN.md
+    section 2); only supports, ``sum |.|^2`` and peak degrees are consumed by the callers."""
+    if spin != 0:
+        raise NotImplementedError("only spin-0 wavelets are on the hot path")
     k0, k = ops.tiling_axisym(L, B, J_min)
     el = np.arange(L)
     phi_l = np.sqrt((2 * el + 1) / (4 * np.pi)) * k0
     psi_lm = np.zeros((L * L, k.shape[0] - J_min), dtype=complex)
+    if N == 1:
+        for col, j in enumerate(range(J_min, k.shape[0])):
+            psi_lm[el * el + el, col] = np.sqrt((2 * el + 1) / (8 * np.pi ** 2)) * k[j]
+        return phi_l, psi_lm
+    s = dir_component(L, N)
+    ell = np.repeat(el, 2 * el + 1)
     for col, j in enumerate(range(J_min, k.shape[0])):
-        psi_lm[el * el + el, col] = np.sqrt((2 * el + 1) / (8 * np.pi ** 2)) * k[j]
+        psi_lm[:, col] = (np.sqrt((2 * el + 1) / (8 * np.pi ** 2)) * k[j])[ell] * s
     return phi_l, psi_lm
 
 
