@@ -166,26 +166,18 @@ int pxm_dwav_plan_info(pxm_dwav_plan_t plan, int* nitems, int* split_blocks, int
 int pxm_wav_set_iter_counter(pxm_wav_plan_t plan, uint64_t* counter_dev);
 int pxm_wav_release_iter_counter(pxm_wav_plan_t plan, const uint64_t* counter_dev);
 int pxm_wav_iter_counter_add(pxm_wav_plan_t plan, uint64_t inc, pxm_stream_t stream);
-/* Device status of a plan.  Two kernels of this library wait on each other with BOUNDED spins instead of barriers: the
- * wave pairs of the fused phi-DFT kernels (csrc/dft5.hip, d5_pair_sync: an LDS counter per pair) and, with PXM_FLOW=1
- * (experimental; read when a plan's Gram lists are built), the forward-adjoint tasks of the dataflow GEMM launch (per-
- * order counters).  A wait that expires does not hang the GPU -- the kernel runs on with data its partner has not
- * written -- and ORs a bit into the plan's status word; the results of that launch are invalid.  The reference fails
- * loudly on bad state (pxmcmc/mcmc.py:104-109); so does the sampler here: it reads the word wherever it already
- * synchronises (saved samples, progress prints, end of run) and raises.
+/* Device status of a plan.  The wave pairs of the fused phi-DFT kernels (csrc/dft5.hip, d5_pair_sync: an LDS counter
+ * per pair) wait on each other with BOUNDED spins instead of barriers.  A wait that expires does not hang the GPU -- the
+ * kernel runs on with data its partner has not written -- and ORs a bit into the plan's status word; the results of
+ * that launch are invalid.  The reference fails loudly on bad state (pxmcmc/mcmc.py:104-109); so does the sampler here:
+ * it reads the word wherever it already synchronises (saved samples, progress prints, end of run) and raises.
  *   pxm_wav_status / pxm_sht_status : bit mask since the last clear, 0 = every wait was satisfied; `clear` != 0 resets
- *                                     it after reading.  Synchronises the stream.  < 0: error.
- *   pxm_wav_flow_status             : the PXM_STATUS_FLOW_WAIT bit as 0 / 1 (round-3 interface).
- *   pxm_wav_flow_enabled            : 1 when this plan's ring-space step takes the dataflow launch (known after
- *                                     pxm_wav_ring_set_data), 0 when it runs the two ordinary launches.
+ *                                     it after reading.  Synchronises the stream.  < 0: error.  Bit 0 is unused.
  * PXM_DEBUG_PAIR_SYNC_LIMIT=<n> (read at plan creation) sets the bound of the pair wait; 0 forces every wait to
  * expire -- the test of this report path. */
-#define PXM_STATUS_FLOW_WAIT 1
 #define PXM_STATUS_PAIR_SYNC 2
 int pxm_wav_status(pxm_wav_plan_t plan, int clear, pxm_stream_t stream);
 int pxm_sht_status(pxm_sht_plan_t plan, int clear, pxm_stream_t stream);
-int pxm_wav_flow_status(pxm_wav_plan_t plan, pxm_stream_t stream);
-int pxm_wav_flow_enabled(pxm_wav_plan_t plan);
 /* scales whose 511-point rings the fused rings -> X' -> rings launch takes through the exact-length phi-DFT unit (0: Bluestein) */
 int pxm_wav_exact_dft_scales(pxm_wav_plan_t plan);
 

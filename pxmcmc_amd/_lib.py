@@ -33,8 +33,6 @@ SIGNATURES = {
     "pxm_wav_set_iter_counter": (c_int, [c_vp, c_vp]),
     "pxm_wav_release_iter_counter": (c_int, [c_vp, c_vp]),
     "pxm_wav_iter_counter_add": (c_int, [c_vp, c_u64, c_vp]),
-    "pxm_wav_flow_status": (c_int, [c_vp, c_vp]),
-    "pxm_wav_flow_enabled": (c_int, [c_vp]),
     "pxm_wav_exact_dft_scales": (c_int, [c_vp]),
     "pxm_wav_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_sht_status": (c_int, [c_vp, c_int, c_vp]),
@@ -166,7 +164,7 @@ class PxmError(RuntimeError):
 
 
 NOISE_F64 = 16  # PXM_NOISE_F64: OR-ed into the mode / noise_complex / dtype argument of the noise-drawing entry points
-STATUS_FLOW_WAIT, STATUS_PAIR_SYNC = 1, 2  # bits of pxm_wav_status / pxm_sht_status
+STATUS_PAIR_SYNC = 2  # bit of pxm_wav_status / pxm_sht_status (bit 0 is unused)
 
 
 def _load():

@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -60,12 +61,18 @@ int64_t ranges_checked();          // spans verified since the last reset (all p
 void ranges_checked_add(int64_t n);
 void ranges_checked_reset();
 
-// hipFuncSetAttribute is per device: true the first time it is asked for the CURRENT device (one flag word per call site)
-inline bool first_on_this_device(std::atomic<uint64_t>& seen) {
+// Dynamic LDS beyond 64 KB has to be allowed per kernel and per device: raises the limit of every kernel in the list to
+// 160 KB on the CURRENT device, once per call site (`done`: one bit per device, set only after every call succeeded, so
+// a failed attempt is repeated by the next caller).  Nothing in dry-run mode.
+inline int allow_dynamic_lds(std::atomic<uint64_t>& done, std::initializer_list<const void*> kernels) {
+  if (dry_run()) return 0;
   int d = 0;
-  if (hipGetDevice(&d) != hipSuccess) d = 0;
+  PXM_HIP(hipGetDevice(&d));
   const uint64_t bit = 1ull << (d & 63);
-  return !(seen.fetch_or(bit) & bit);
+  if (done.load() & bit) return 0;
+  for (const void* k : kernels) PXM_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  done.fetch_or(bit);
+  return 0;
 }
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }

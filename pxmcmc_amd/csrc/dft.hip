@@ -170,15 +170,8 @@ int make_dft_plan(int L, DftPlan* p) {
     if (rc) return rc;
     p->use6 = true;
   }
-  static bool attr_set = false;
-  if (!attr_set && !dry_run()) {
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px2ring), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ring2px), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024));
-    attr_set = true;
-  }
-  return 0;
+  static std::atomic<uint64_t> lds_done{0};
+  return allow_dynamic_lds(lds_done, {reinterpret_cast<const void*>(k_px2ring), reinterpret_cast<const void*>(k_ring2px)});
 }
 
 void free_dft_plan(DftPlan* p) {

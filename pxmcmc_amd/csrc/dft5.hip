@@ -39,13 +39,6 @@
 #ifndef PXM_D5_ABLATE
 #define PXM_D5_ABLATE 0
 #endif
-// update epilogue of the fused kernel: Philox + Box-Muller of a lane's four elements ahead of the operand loads (1,
-// default: 124 VGPR, no spills, 66.6 us per grouped launch), between the loads and their use (0: 8 spilled registers,
-// one of them a freshly loaded threshold, i.e. an s_waitcnt vmcnt(0) right behind the loads: 68.4 us) or behind the
-// loads as a block (2: 12 spills)
-#ifndef PXM_D5_PHILOX_FIRST
-#define PXM_D5_PHILOX_FIRST 1
-#endif
 
 namespace pxm {
 
@@ -101,14 +94,8 @@ struct Dft5Group {
 // for every global load AND STORE in flight -- the stores of the updated coefficients sat in front of the exchange
 // barrier of the forward transform, the ring stores of a chain group in front of nothing at all.  Global memory needs
 // no intra-kernel ordering here: a workgroup only re-reads global data it has not written (the in-place ring stores
-// come after every ring load of the workgroup has been consumed into LDS).  -DPXM_D5_FULL_BARRIER: the old barrier.
-__device__ __forceinline__ void d5_barrier() {
-#ifdef PXM_D5_FULL_BARRIER
-  __syncthreads();
-#else
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-}
+// come after every ring load of the workgroup has been consumed into LDS).
+__device__ __forceinline__ void d5_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Synchronisation of the TWO waves of a ring set (the even- and odd-bin halves exchange their shares through LDS):
 // an LDS counter per wave pair instead of a workgroup barrier.  With s_barrier the four ring sets of a workgroup moved
@@ -118,17 +105,12 @@ __device__ __forceinline__ void d5_barrier() {
 // ds_writes publishes them.  The spin is bounded (a lost partner would otherwise hang the GPU); a wait that EXPIRES
 // sets bit PXM_STATUS_PAIR_SYNC of the owning plan's status word -- the kernel runs on with data its partner has not
 // written, and the host finds the bit wherever it already synchronises (pxm_wav_status / pxm_sht_status: the sampler
-// raises at its next save point instead of returning a silently corrupted chain).  -DPXM_D5_NO_PAIR_SYNC: workgroup
-// barriers as before.
+// raises at its next save point instead of returning a silently corrupted chain).
 struct D5Sync {
   unsigned* err;
   unsigned limit;
 };
 __device__ __forceinline__ void d5_pair_sync(unsigned* cnt, unsigned target, int lane, const D5Sync& sy) {
-#ifdef PXM_D5_NO_PAIR_SYNC
-  (void)cnt; (void)target; (void)lane; (void)sy;
-  d5_barrier();
-#else
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   if (lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   unsigned spins = 0;
@@ -138,7 +120,6 @@ __device__ __forceinline__ void d5_pair_sync(unsigned* cnt, unsigned target, int
     __builtin_amdgcn_s_sleep(1);
   if (!ready && sy.err && lane == 0) __hip_atomic_fetch_or(sy.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   asm volatile("" ::: "memory");
-#endif
 }
 
 __device__ __forceinline__ void d5_wave_sync() {
@@ -541,10 +522,12 @@ __device__ __forceinline__ void ring2px_body5(const Dft5Args& a, double* __restr
       double2 xs[4], wn[4];
       double Ts[4];
       int64_t eo[4];  // element offset from e0 (or to the ring's element 0)
-#if PXM_D5_PHILOX_FIRST == 1
       // The noise of the four elements BEFORE the operand loads, one element at a time: the fp64 Box-Muller keeps ~40
       // registers live, and evaluated between the loads and their use (beside xs / Ts / the addresses) it cost 250
-      // spilled registers in this kernel (93 instead of 70 us per launch).
+      // spilled registers in this kernel (93 instead of 70 us per launch).  Ahead of the loads: 124 VGPR, no spills,
+      // 66.6 us per grouped launch; element by element between the loads and their use: 8 spilled registers, one of
+      // them a freshly loaded threshold, i.e. an s_waitcnt vmcnt(0) right behind the loads (68.4 us); behind the loads
+      // as a block: 12 spills.
       double2 wph[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -552,7 +535,6 @@ __device__ __forceinline__ void ring2px_body5(const Dft5Args& a, double* __restr
         if (!out.noise) wph[u] = px_noise_philox_t<N64>(out, ch_s, e0 + (int64_t)(8 * R0) * (g0 + u), it_eff);
         __builtin_amdgcn_sched_barrier(0);
       }
-#endif
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int p = g0 + u;
@@ -575,16 +557,6 @@ __device__ __forceinline__ void ring2px_body5(const Dft5Args& a, double* __restr
 #pragma unroll
         for (int u = 0; u < 4; ++u) wn[u] = double2{0.0, 0.0};
       }
-#if PXM_D5_PHILOX_FIRST == 2
-      double2 wph[4];
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        wph[u] = double2{0.0, 0.0};
-        if (!out.noise) wph[u] = px_noise_philox_t<N64>(out, ch_s, e0 + (int64_t)(8 * R0) * (g0 + u), it_eff);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#endif
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int p = g0 + u;
@@ -595,11 +567,7 @@ __device__ __forceinline__ void ring2px_body5(const Dft5Args& a, double* __restr
         const int64_t off = (int64_t)(8 * R0) * p;
         const double2 y{x[p].x, -x[p].y};
         double2 w = wn[u];
-#if PXM_D5_PHILOX_FIRST
         if (!out.noise) w = wph[u];
-#elif !(PXM_D5_ABLATE & 1)
-        if (!out.noise) w = px_noise_philox_t<N64>(out, ch, e0 + off, it_eff);
-#endif
         x[p] = px_update(out, xs[u], Ts[u], y, w);
         reinterpret_cast<double2*>(out.f)[ce0 + off] = x[p];
       }
@@ -848,7 +816,7 @@ __device__ __forceinline__ void ring2px_body_pfa(const Dft5Args& a, const PfaTab
         for (int u = 0; u < 4; ++u) wn[u] = double2{0.0, 0.0};
       }
       __builtin_amdgcn_sched_barrier(0);
-#if !(PXM_D5_ABLATE & 1) && !defined(PXM_NOISE_F64_POLY) && !defined(PXM_PFA_NO_SPLIT_NOISE)
+#if !(PXM_D5_ABLATE & 1) && !defined(PXM_NOISE_F64_POLY)
       // fp64 noise of a chain pair (the benchmarked mode): the Philox bits of the four elements first -- four independent
       // integer chains --, then the fp64 Box-Muller step element by element (its ~40 live registers are why the elements
       // are not interleaved there)
@@ -1176,15 +1144,11 @@ extern "C" int pxm_debug_set_dft_trace(unsigned long long* buf) {
 template <bool RING_OUT, bool N64>
 __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_ring2px_group5(const Dft5Group* __restrict__ ents, int nent,
                                                                                        double* __restrict__ ws, int ncol, PxOut out,
-                                                                                       int C, unsigned* __restrict__ zero_words,
-                                                                                       int n_zero) {
+                                                                                       int C) {
   extern __shared__ double2 lds5[];
 #ifdef PXM_D5_TRACE
   const unsigned long long trace_t0 = wall_clock64();
 #endif
-  // (the per-m counters of the dataflow GEMM launch that follows this kernel in a stepping loop: plans.hip)
-  if (zero_words && blockIdx.x == 0)
-    for (int i = threadIdx.x; i < n_zero; i += 512) zero_words[i] = 0;
   PXM_D5_GROUP_DECODE
   out.ring0 = g.ring0;
   if (g.r0 == 9) {  // exact-length unit (entries of the lists with the workgroup shape of that unit: DftGroupList::d_fused)
@@ -1644,15 +1608,10 @@ static Dft5Args dft5_args(const DftPlan& p) {
 
 template <int R0>
 static int dft5_attr() {
-  static std::atomic<uint64_t> seen{0};
-  if (first_on_this_device(seen)) {
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px2ring5<R0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ring2px5<R0, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ring2px5<R0, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ring2px5<R0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ring2px5<R0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  }
-  return 0;
+  static std::atomic<uint64_t> done{0};
+  return allow_dynamic_lds(done, {reinterpret_cast<const void*>(k_px2ring5<R0>), reinterpret_cast<const void*>(k_ring2px5<R0, false, false>),
+                                  reinterpret_cast<const void*>(k_ring2px5<R0, true, false>), reinterpret_cast<const void*>(k_ring2px5<R0, false, true>),
+                                  reinterpret_cast<const void*>(k_ring2px5<R0, true, true>)});
 }
 
 template <int R0>
@@ -1809,22 +1768,16 @@ int dft5_group_create(const std::vector<const DftPlan*>& plans, const std::vecto
   if (int rc = dev_upload(out->d, v.data(), v.size() * sizeof(Dft5Group))) return rc;
   if (any_pfa) {
     // LDS of the exact-length body: 8 planes of PFA_PLANE slots (aliased by the stage of 2 rings x 511 x 4 slots) + the filter
-    // spectrum: 74 880 B, inside the 81 920 B of the Bluestein workgroups (two workgroups per CU either way)
+    // spectrum: 81 056 B, inside the 81 920 B of the Bluestein workgroups (two workgroups per CU either way)
     static_assert(((size_t)8 * PFA_PLANE + 72 + NOISE_LOG_N + 256 + 1) * 16 <= (size_t)2 * D5_RMAX * D5_PLANE * 16 + (size_t)D5_TW * 16, "PFA workgroup LDS");
         if (int rc = dev_alloc(&out->d_fused, vf.size() * sizeof(Dft5Group), "DFT group entries (fused launch)")) return rc;
     if (int rc = dev_upload(out->d_fused, vf.data(), vf.size() * sizeof(Dft5Group))) return rc;
     out->blocks_fused = b0f;
   }
-  static bool attr = false;
-  if (!attr && !dry_run()) {
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((k_ring2px_group5<true, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((k_ring2px_group5<true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((k_ring2px_group5<false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((k_ring2px_group5<false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px2ring_group5), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
-  return 0;
+  static std::atomic<uint64_t> lds_done{0};
+  return allow_dynamic_lds(lds_done, {reinterpret_cast<const void*>(k_ring2px_group5<true, false>), reinterpret_cast<const void*>(k_ring2px_group5<true, true>),
+                                      reinterpret_cast<const void*>(k_ring2px_group5<false, false>), reinterpret_cast<const void*>(k_ring2px_group5<false, true>),
+                                      reinterpret_cast<const void*>(k_px2ring_group5)});
 }
 
 void dft_group_destroy(DftGroupList* g) {
@@ -1836,8 +1789,7 @@ void dft_group_destroy(DftGroupList* g) {
   g->n = 0;
 }
 
-int dft5_group_launch(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st, Profiler* prof,
-                      unsigned* zero_words, int n_zero) {
+int dft5_group_launch(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st, Profiler* prof) {
   // algorithmic bytes: rings read + written (16 B per slot and coefficient, every padded slot), state read, new state
   // written (live slots), thresholds read once
   PXM_REQUIRE(g.ring_end <= out.chain_stride, "dft5_group_launch: a scale's coefficient block ends past chain_stride");
@@ -1848,10 +1800,10 @@ int dft5_group_launch(const DftGroupList& g, double* ws, int ncol, const PxOut& 
   const int blocks = g.d_fused ? g.blocks_fused : g.blocks;
   if (out.X && !out.noise && out.noise64)
     hipExtLaunchKernelGGL((k_ring2px_group5<true, true>), dim3(blocks), dim3(g.threads), g.lds, st, ev0, ev1, 0,
-                          ents, g.n, ws, ncol, out, C, zero_words, n_zero);
+                          ents, g.n, ws, ncol, out, C);
   else
     hipExtLaunchKernelGGL((k_ring2px_group5<true, false>), dim3(blocks), dim3(g.threads), g.lds, st, ev0, ev1, 0,
-                          ents, g.n, ws, ncol, out, C, zero_words, n_zero);
+                          ents, g.n, ws, ncol, out, C);
   PXM_HIP(hipGetLastError());
   return 0;
 }
@@ -1869,11 +1821,9 @@ int dft5_group_ring2px(const DftGroupList& g, double* ws, int ncol, const PxOut&
   const Dft5Group* ents = reinterpret_cast<const Dft5Group*>(g.d_fused ? g.d_fused : g.d);
   const int blocks = g.d_fused ? g.blocks_fused : g.blocks;
   if (out.X && !out.noise && out.noise64)
-    hipLaunchKernelGGL((k_ring2px_group5<false, true>), dim3(blocks), dim3(g.threads), g.lds, st, ents, g.n, ws, ncol, out, C,
-                       (unsigned*)nullptr, 0);
+    hipLaunchKernelGGL((k_ring2px_group5<false, true>), dim3(blocks), dim3(g.threads), g.lds, st, ents, g.n, ws, ncol, out, C);
   else
-    hipLaunchKernelGGL((k_ring2px_group5<false, false>), dim3(blocks), dim3(g.threads), g.lds, st, ents, g.n, ws, ncol, out, C,
-                       (unsigned*)nullptr, 0);
+    hipLaunchKernelGGL((k_ring2px_group5<false, false>), dim3(blocks), dim3(g.threads), g.lds, st, ents, g.n, ws, ncol, out, C);
   PXM_HIP(hipGetLastError());
   return 0;
 }
@@ -1956,21 +1906,12 @@ static Dft6Args dft6_args(const DftPlan& p) {
 // chains per workgroup: 2 (8 waves, 2 workgroups per CU: 4 waves per SIMD); 1 for a single chain
 static size_t dft6_lds(int R) { return (size_t)4 * R * D5_PLANE * 16 + (size_t)D5_TW * 16; }  // (>= the stage: n R 16 B)
 static int dft6_attr() {
-  static std::atomic<uint64_t> seen{0};
-  if (first_on_this_device(seen)) {
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px2ring6<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px2ring6<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((k_ring2px6<false, 0>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((k_ring2px6<true, 0>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((k_ring2px6<false, 1>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((k_ring2px6<true, 1>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  }
-  return 0;
+  static std::atomic<uint64_t> done{0};
+  return allow_dynamic_lds(done, {reinterpret_cast<const void*>(k_px2ring6<0>), reinterpret_cast<const void*>(k_px2ring6<1>),
+                                  reinterpret_cast<const void*>(k_ring2px6<false, 0>), reinterpret_cast<const void*>(k_ring2px6<true, 0>),
+                                  reinterpret_cast<const void*>(k_ring2px6<false, 1>), reinterpret_cast<const void*>(k_ring2px6<true, 1>)});
 }
-static int dft6_chains_per_wg(int C) {
-  static const int forced = getenv("PXM_D6_R") ? atoi(getenv("PXM_D6_R")) : 0;  // A/B: 1 | 2
-  return forced == 1 || forced == 2 ? forced : (C == 1 ? 1 : 2);
-}
+static int dft6_chains_per_wg(int C) { return C == 1 ? 1 : 2; }
 int dft6_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t st) {
   if (int rc = dft6_attr()) return rc;
   const int R = dft6_chains_per_wg(C);

@@ -172,7 +172,7 @@ int drain_deferred() {
 
 extern "C" {
 
-int pxm_version(void) { return 400; }  // 4.0: PXM_NOISE_F64 launch flag, pxm_wav_status / pxm_sht_status / pxm_wav_flow_enabled
+int pxm_version(void) { return 500; }  // 5.0: pxm_wav_flow_status / pxm_wav_flow_enabled removed
 
 int pxm_noise_bits(void) { return 32; }  // the DEFAULT of the stepping entry points; PXM_NOISE_F64 selects 64 per call
 

@@ -32,8 +32,8 @@ struct TaskList {
 };
 
 static int upload_tasks(std::vector<GemmTask> v, bool paired, TaskList* out, std::vector<int> bls, int ncol,
-                        const double* ws_base, const char* name, std::vector<int> los = {}, bool keep_order = false,
-                        int pk = 0, std::vector<char> tab_shared = {}) {
+                        const double* ws_base, const char* name, std::vector<int> los = {}, int pk = 0,
+                        std::vector<char> tab_shared = {}) {
   out->pk = pk;
   tab_shared.resize(bls.size(), 0);
   out->tab_shared = tab_shared;
@@ -53,10 +53,10 @@ static int upload_tasks(std::vector<GemmTask> v, bool paired, TaskList* out, std
   // (almost) resident at once and the per-CU bins win (L=256: 24.5 vs 26.5 us Gram, 31.4 vs 32.1 us groups); with
   // many rounds per slot the queues win (L=512: 200 vs 218 us, 218 vs 231 us).
   const char* order_env = getenv("PXM_GEMM_ORDER");
-  const std::string order = keep_order ? "kept" : (order_env ? order_env : (v.size() > 2048 ? "xcd" : "bins"));
+  const std::string order = order_env ? order_env : (v.size() > 2048 ? "xcd" : "bins");
   const int64_t fixed = order == "xcd" ? 32 : 0;  // start-up / drain of a task in contraction steps
   auto work = [fixed](const GemmTask& a) { return (int64_t)(a.k_end - a.k_beg + fixed) * a.n_rt; };
-  if (!keep_order) std::stable_sort(v.begin(), v.end(), [&](const GemmTask& a, const GemmTask& b) { return work(a) > work(b); });
+  std::stable_sort(v.begin(), v.end(), [&](const GemmTask& a, const GemmTask& b) { return work(a) > work(b); });
   if (order == "xcd" && !v.empty()) {
     constexpr int NQ = 8;  // XCDs of gfx950
     std::map<int64_t, int> unit_of;
@@ -214,8 +214,8 @@ struct pxm_sht_plan_s {
 };
 
 namespace pxm {
-// Device status word of a plan: kernels OR a bit in when a bounded wait expires (dft5.hip d5_pair_sync, sht_gemm.hip
-// k_sht_gemm_flow) instead of hanging the GPU; the host reads it wherever it synchronises anyway.
+// Device status word of a plan: kernels OR a bit in when a bounded wait expires (dft5.hip d5_pair_sync) instead of
+// hanging the GPU; the host reads it wherever it synchronises anyway.
 static int status_alloc(unsigned** d) {
   if (int rc = dev_alloc(d, 4 * sizeof(unsigned), "plan status word")) return rc;
   return dev_zero(*d, 4 * sizeof(unsigned));
@@ -374,35 +374,6 @@ namespace pxm {
 
 constexpr int WAV_MAX_SCALES = 40;  // scaling function + wavelet scales of one plan (B = 1.2 at L = 512: 36)
 
-// H_L[m][el][col] = sum_i kc[i][el] * H_i[m][el][col]  over the scales whose band holds (el, m)
-struct CombineArgs {
-  int nsc;
-  int L, Rp, ncol;
-  int bl[WAV_MAX_SCALES], Rp_i[WAV_MAX_SCALES];
-  int64_t offH[WAV_MAX_SCALES];
-  const double* kc;  // [nsc][Rp] synthesis coefficients c_s * kappa
-};
-
-__global__ void k_wav_combine(CombineArgs a, const double* __restrict__ ws, double* __restrict__ HL) {
-  const int64_t total = (int64_t)(2 * a.L - 1) * a.Rp * a.ncol;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int col = (int)(i % a.ncol);
-    const int el = (int)((i / a.ncol) % a.Rp);
-    const int m = (int)(i / ((int64_t)a.ncol * a.Rp)) - (a.L - 1);
-    const int am = m < 0 ? -m : m;
-    double acc = 0;
-    if (el < a.L && el >= am) {
-      for (int s = 0; s < a.nsc; ++s) {
-        if (el >= a.bl[s]) continue;
-        const double k = a.kc[s * a.Rp + el];
-        if (k == 0.0) continue;
-        acc += k * ws[a.offH[s] + ((int64_t)(m + a.bl[s] - 1) * a.Rp_i[s] + el) * a.ncol + col];
-      }
-    }
-    HL[i] = acc;
-  }
-}
-
 }  // namespace pxm
 
 // Side streams and their fork / join events are per-device and live for the whole process: every plan borrows
@@ -450,31 +421,24 @@ struct pxm_wav_plan_s {
   std::vector<DftPlan> dft;  // per scale
   DftPlan dftL;
   double* ws = nullptr;
-  std::vector<int64_t> offG, offH;
+  std::vector<int64_t> offG;
   int64_t offGL = 0, offHL = 0, offS = 0;
-  int64_t offGR = 0, offGD = 0, offHD = 0;
+  int64_t offGD = 0, offHD = 0;
   int64_t offHDc = 0;  // chain-less copy of the data term B^T DFT(data): [m + L - 1][row][2] (re, im), what the Gram epilogue reads
   TaskList gram, adj_invadj_D;   // Gram step of the ring-space MYULA iteration; B^T DFT(data)
-  bool use_gram = true;  // ring-space residual buffer and the rings of the data (ring-space MYULA step)
   bool have_data_rings = false;
   int64_t offHA = 0, offHB = 0;  // L-layout class buffers of the fused combine (disjoint l-supports per class)
-  bool fused_combine = true;
-  bool fused_dft = true;        // PXM_NO_FUSED_DFT=1 (read once at plan creation): separate DFT kernels
-  bool dft_small_first = true;  // PXM_DFT_TOP_FIRST=1: non-grouped launch order
-  static bool fused_combine_env_ok() { return !getenv("PXM_NO_FUSED_COMBINE") && !getenv("PXM_NO_GRAM"); }
   double* d_kc_syn = nullptr;  // [nsc][Rp]  c_s * kappa   (synthesis and its adjoint)
   double* d_kc_ana = nullptr;  // [nsc][Rp]  c_a * kappa   (analysis and its adjoint)
   TaskList syn_fwd, syn_inv, adj_invadj, adj_fwdadj;  // synthesis / synthesis-adjoint stages
-  TaskList adj_invadj_R;                               // same as adj_invadj, operand = residual rings G_R
   TaskList ana_fwd, ana_inv, anadj_invadj, anadj_fwdadj;  // analysis / analysis-adjoint stages
-  CombineArgs comb_syn, comb_ana;
   int64_t table_bytes[2] = {0, 0};
   // side streams: the DFT launches of the small scales are latency-bound (a few workgroups each);
   // they run beside the large scales' launches instead of in front of them
-  static constexpr int NSIDE = 3;  // capacity; PXM_NSIDE (default 2) of them are used
+  static constexpr int NSIDE = 3;  // capacity (the streams of the per-device pool) ...
+  static constexpr int nside = 2;  // ... of which a plan uses two
   hipStream_t side[NSIDE] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[NSIDE] = {nullptr, nullptr, nullptr};
-  int nside = 2;
   bool plain_group = true;  // blocks <-> rings of the member scales in one grid (PXM_NO_PLAIN_DFT_GROUP=1: per scale)
   std::vector<int> lane_of;  // per scale: -1 = caller's stream, else side stream index
   DftGroupList dft_group;   // every scale's rings -> X' -> rings kernel in one grid (ring-space step)
@@ -487,7 +451,7 @@ struct pxm_wav_plan_s {
   bool wl_failed = false;       // a pxm_wav_wl_attach gave up part-way: the weak-lensing entry points refuse the plan
   double* d_twin = nullptr;     // [2 bl - 1][Rp_bl][ncol_t]
   int64_t offGT = 0;            // d_twin relative to ws (doubles)
-  int ncol_t = 0;               // doubles per row of the twin array: 4 (narrow: its two slots and nothing else) or ncol
+  int ncol_t = 0;               // doubles per row of the twin array: 4 (narrow: its two slots and nothing else)
   // narrow ring array of the spin-2 stage (recursion kernels <-> DFT at L): 2 Cmax doubles per row instead of a 128-B line of
   // eight chain slots -- both its producers and its consumers take the row stride as an argument
   double* d_g2n = nullptr;
@@ -504,7 +468,7 @@ struct pxm_wav_plan_s {
   int ncol_gn = 0;
   DftGroupList dft_group_n;
   TaskList wl_syn_fwd, wl_adj_fwdadj;  // packed per-scale lists of the weak-lensing path reading / writing the twin array
-  std::vector<int> el_lo_s, sup_lo_s;  // per scale: rows / contraction steps skipped, first degree of the support
+  std::vector<int> el_lo_s;  // per scale: first degree of the support (rows / contraction steps below it are skipped)
   ShtTables* T2 = nullptr;
   RecTables* rec2 = nullptr;  // ... or the table-free spin-2 ring stage (sht_rec.hip) when the plan carries few chains
   int64_t offG2 = 0;
@@ -514,15 +478,7 @@ struct pxm_wav_plan_s {
   const double* wl_gw = nullptr;       // [ndata] covariance weight (caller-owned) or null
   int64_t wl_ndata = 0;
   std::vector<ShtTables*> held;  // table-cache entries this plan retains (each once)
-  // dataflow launch of the ring-space step: Gram + forward-adjoint tasks in one grid, per-m counters instead of a
-  // launch boundary (sht_gemm.hip: k_sht_gemm_flow).  Opt-in (PXM_FLOW=1): bit-identical to the two launches and one
-  // kernel fewer per iteration, but not faster -- 55.4 us against 22.2 + 33.3 us
-  bool use_flow = false;
-  TaskList flow;
-  std::vector<GemmTask> h_adj_fwdadj;  // host copy of the forward-adjoint tasks (the flow list is built with the Gram list)
-  unsigned* d_flow_flags = nullptr;    // [L] per-m counters (the time-out flag is bit 0 of d_status)
-  double flow_bytes = 0, flow_mfma = 0;
-  unsigned* d_status = nullptr;  // device status word of THIS plan: bit 0 dataflow wait, bit 1 DFT pair wait (pxm_wav_status)
+  unsigned* d_status = nullptr;  // device status word of THIS plan: bit 1 DFT pair wait (pxm_wav_status)
   uint64_t* iter_dev = nullptr;  // device-resident Philox iteration counter of THIS plan (pxm_wav_set_iter_counter)
   Profiler prof;                 // live kernel timing of THIS plan (pxm_wav_profile_*)
 };
@@ -558,9 +514,8 @@ static GemmSide wav_side(const pxm_wav_plan_s* p, int s, int which, const SideOv
   switch (which) {
     case 0:  // synthesis: G_s --A_s--> c_s kappa_s(l) * (...) written straight into the class buffer in L layout
       g.x_base = G; g.x_L = b; g.x_Rp = Rb;
-      g.fuse.row_lo = p->sup_lo_s[s]; g.fuse.row_hi = b;
-      if (p->fused_combine) { g.y_base = hcls; g.y_L = L; g.y_Rp = p->Rp; g.fuse.rscale = p->d_kc_syn + (size_t)s * p->Rp; }
-      else { g.y_base = p->offH[s]; g.y_L = b; g.y_Rp = Rb; g.fuse = GemmFuse(); }
+      g.fuse.row_lo = p->el_lo_s[s]; g.fuse.row_hi = b;
+      g.y_base = hcls; g.y_L = L; g.y_Rp = p->Rp; g.fuse.rscale = p->d_kc_syn + (size_t)s * p->Rp;
       break;
     case 1:  // synthesis adjoint: H_L (scaled by c_s kappa_s per el) --A_s^T--> G_s
       g.x_base = hl; g.x_L = L; g.x_Rp = p->Rp; g.y_base = G; g.y_L = b; g.y_Rp = Rb;
@@ -570,11 +525,10 @@ static GemmSide wav_side(const pxm_wav_plan_s* p, int s, int which, const SideOv
       g.x_base = hl; g.x_L = L; g.x_Rp = p->Rp; g.y_base = G; g.y_L = b; g.y_Rp = Rb;
       g.kscale = p->d_kc_ana + (size_t)s * p->Rp;
       break;
-    default:  // analysis adjoint: G_s --B_s^T--> class buffer (or H_s)
+    default:  // analysis adjoint: G_s --B_s^T--> class buffer
       g.x_base = G; g.x_L = b; g.x_Rp = Rb;
-      g.fuse.row_lo = p->sup_lo_s[s]; g.fuse.row_hi = b;
-      if (p->fused_combine) { g.y_base = hcls; g.y_L = L; g.y_Rp = p->Rp; g.fuse.rscale = p->d_kc_ana + (size_t)s * p->Rp; }
-      else { g.y_base = p->offH[s]; g.y_L = b; g.y_Rp = Rb; g.fuse = GemmFuse(); }
+      g.fuse.row_lo = p->el_lo_s[s]; g.fuse.row_hi = b;
+      g.y_base = hcls; g.y_L = L; g.y_Rp = p->Rp; g.fuse.rscale = p->d_kc_ana + (size_t)s * p->Rp;
       break;
   }
   return g;
@@ -669,20 +623,14 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
   int64_t w = 0;
   p->offGL = w; w += arr_size(L, p->ncol);
   p->offHL = w; w += arr_size(L, p->ncol);
-  p->offGR = w; w += arr_size(L, p->ncol);
   p->offGD = w; w += arr_size(L, p->ncol);
   p->offHD = w; w += arr_size(L, p->ncol);
   p->offHDc = w; w += (int64_t)(2 * L - 1) * p->Rp * 2;
-  p->use_gram = p->fused_combine_env_ok();
   p->offHA = w; w += arr_size(L, p->ncol);
   p->offHB = w; w += arr_size(L, p->ncol);
-  p->fused_combine = !getenv("PXM_NO_FUSED_COMBINE");
-  p->fused_dft = !getenv("PXM_NO_FUSED_DFT");
-  p->dft_small_first = !getenv("PXM_DFT_TOP_FIRST");
   p->plain_group = !getenv("PXM_NO_PLAIN_DFT_GROUP");
   for (int s = 0; s < p->nsc; ++s) {
     p->offG.push_back(w); w += arr_size(p->bl[s], p->ncol);
-    p->offH.push_back(w); w += arr_size(p->bl[s], p->ncol);
   }
   p->offG2 = w; w += arr_size(L, p->ncol);  // (spin-2 rings of the weak-lensing attachment: 1/8 or so of the workspace)
   p->offS = w; w += (int64_t)p->Rp * p->ncol;
@@ -703,21 +651,16 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
   if ((rc = dev_alloc(&p->d_kc_ana, kc_ana.size() * sizeof(double), "analysis kernel rows c kappa [nsc][Rp]"))) return rc;
   if ((rc = dev_upload(p->d_kc_syn, kc_syn.data(), kc_syn.size() * sizeof(double)))) return rc;
   if ((rc = dev_upload(p->d_kc_ana, kc_ana.data(), kc_ana.size() * sizeof(double)))) return rc;
-  // support cut per scale: first degree with a non-zero kernel (compact support of kappa_j)
-  // sup_lo: the support itself (row masks of the fused combine: class buffers are shared by scales with disjoint
-  // supports); el_lo: the rows / contraction steps actually skipped (PXM_NO_SUPPORT_CUT=1: none, for A/B timing)
-  std::vector<int> el_lo(p->nsc, 0), sup_lo(p->nsc, 0);
-  for (int s = 0; s < p->nsc; ++s) {
-    int lo = 0;
-    while (lo < p->bl[s] && kc_syn[(size_t)s * p->Rp + lo] == 0.0) ++lo;
-    sup_lo[s] = lo;
-    if (!getenv("PXM_NO_SUPPORT_CUT")) el_lo[s] = lo;
-  }
+  // support cut per scale: first degree with a non-zero kernel (compact support of kappa_j).  The rows / contraction
+  // steps below it are skipped, and it is the row mask of the fused combine (class buffers are shared by scales with
+  // disjoint supports).
+  std::vector<int> el_lo(p->nsc, 0);
+  for (int s = 0; s < p->nsc; ++s)
+    while (el_lo[s] < p->bl[s] && kc_syn[(size_t)s * p->Rp + el_lo[s]] == 0.0) ++el_lo[s];
   // task lists
   std::vector<GemmTask> v_syn_fwd, v_adj_fwdadj, v_ana_inv, v_anadj_invadj, v;
   // the four per-scale stages as GemmSide descriptors
   p->el_lo_s = el_lo;
-  p->sup_lo_s = sup_lo;
   auto side = [&](int s, int which) { return wav_side(p, s, which); };
   const int kinds[4] = {TAB_FWD, TAB_FWD_ADJ, TAB_INV, TAB_INV_ADJ};
   std::vector<GemmTask>* lists[4] = {&v_syn_fwd, &v_adj_fwdadj, &v_ana_inv, &v_anadj_invadj};
@@ -732,11 +675,10 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
   }
   p->table_bytes[0] += p->TL->bytes[TAB_INV];
   p->table_bytes[1] += p->TL->bytes[TAB_INV_ADJ];
-  p->h_adj_fwdadj = v_adj_fwdadj;
   // Few-chain plans (<= 2 chains): the forward / forward-adjoint group launches in PACKED form -- the 2 C live columns of
   // every slab side by side in one MFMA column tile, and scales of equal bandlimit (the two L-band-limited ones) streaming
-  // their table in one pass.  PXM_NO_GEMM_PACK=1: the 16-columns-per-slab lists (A/B, tests).
-  const int pk = (max_chains <= 2 && !getenv("PXM_NO_GEMM_PACK")) ? 2 * max_chains : 0;
+  // their table in one pass.
+  const int pk = max_chains <= 2 ? 2 * max_chains : 0;
   std::vector<char> shared(p->nsc, 0);
   if (pk) {
     v_syn_fwd.clear();
@@ -745,65 +687,40 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
     if ((rc = wav_packed_lists(p, 1, TAB_FWD_ADJ, -1, 0, v_adj_fwdadj, nullptr))) return rc;
   }
   p->pk = pk;
-  if ((rc = upload_tasks(v_syn_fwd, true, &p->syn_fwd, p->bl, p->ncol, p->ws, "synthesis forward (all scales)", el_lo, false, pk, shared))) return rc;
-  if ((rc = upload_tasks(v_adj_fwdadj, true, &p->adj_fwdadj, p->bl, p->ncol, p->ws, "synthesis-adjoint forward-adjoint (all scales)", el_lo, false, pk, shared))) return rc;
+  if ((rc = upload_tasks(v_syn_fwd, true, &p->syn_fwd, p->bl, p->ncol, p->ws, "synthesis forward (all scales)", el_lo, pk, shared))) return rc;
+  if ((rc = upload_tasks(v_adj_fwdadj, true, &p->adj_fwdadj, p->bl, p->ncol, p->ws, "synthesis-adjoint forward-adjoint (all scales)", el_lo, pk, shared))) return rc;
   if ((rc = upload_tasks(v_ana_inv, true, &p->ana_inv, p->bl, p->ncol, p->ws, "analysis inverse (all scales)", el_lo))) return rc;
   if ((rc = upload_tasks(v_anadj_invadj, true, &p->anadj_invadj, p->bl, p->ncol, p->ws, "analysis-adjoint inverse-adjoint (all scales)", el_lo))) return rc;
   v.clear();
   GemmFuse sum2;
   sum2.x2_base = p->offHB;
-  if (p->fused_combine) append_gemm_tasks(*p->TL, TAB_INV, p->ncol, p->offHA, L, p->Rp, p->offGL, L, p->Rp, nullptr, p->offS, p->ws, v, 0, sum2);
-  else append_gemm_tasks(*p->TL, TAB_INV, p->ncol, p->offHL, L, p->Rp, p->offGL, L, p->Rp, nullptr, p->offS, p->ws, v);
+  append_gemm_tasks(*p->TL, TAB_INV, p->ncol, p->offHA, L, p->Rp, p->offGL, L, p->Rp, nullptr, p->offS, p->ws, v, 0, sum2);
   if ((rc = upload_tasks(v, true, &p->syn_inv, {L}, p->ncol, p->ws, "synthesis inverse at L"))) return rc;
   v.clear();
   append_gemm_tasks(*p->TL, TAB_INV_ADJ, p->ncol, p->offGL, L, p->Rp, p->offHL, L, p->Rp, nullptr, p->offS, p->ws, v);
   if ((rc = upload_tasks(v, true, &p->adj_invadj, {L}, p->ncol, p->ws, "inverse-adjoint at L"))) return rc;
   v.clear();
-  append_gemm_tasks(*p->TL, TAB_INV_ADJ, p->ncol, p->offGR, L, p->Rp, p->offHL, L, p->Rp, nullptr, p->offS, p->ws, v);
-  if ((rc = upload_tasks(v, true, &p->adj_invadj_R, {L}, p->ncol, p->ws, "inverse-adjoint at L (residual rings)"))) return rc;
-  v.clear();
   append_gemm_tasks(*p->TL, TAB_FWD, p->ncol, p->offGL, L, p->Rp, p->offHL, L, p->Rp, nullptr, p->offS, p->ws, v);
   if ((rc = upload_tasks(v, true, &p->ana_fwd, {L}, p->ncol, p->ws, "analysis forward at L"))) return rc;
   v.clear();
-  if (p->fused_combine) append_gemm_tasks(*p->TL, TAB_FWD_ADJ, p->ncol, p->offHA, L, p->Rp, p->offGL, L, p->Rp, nullptr, p->offS, p->ws, v, 0, sum2);
-  else append_gemm_tasks(*p->TL, TAB_FWD_ADJ, p->ncol, p->offHL, L, p->Rp, p->offGL, L, p->Rp, nullptr, p->offS, p->ws, v);
+  append_gemm_tasks(*p->TL, TAB_FWD_ADJ, p->ncol, p->offHA, L, p->Rp, p->offGL, L, p->Rp, nullptr, p->offS, p->ws, v, 0, sum2);
   if ((rc = upload_tasks(v, true, &p->anadj_fwdadj, {L}, p->ncol, p->ws, "analysis-adjoint forward-adjoint at L"))) return rc;
-  // combine descriptors
-  CombineArgs c;
-  c.nsc = p->nsc;
-  c.L = L;
-  c.Rp = p->Rp;
-  c.ncol = p->ncol;
-  for (int s = 0; s < p->nsc; ++s) {
-    c.bl[s] = p->bl[s];
-    c.Rp_i[s] = round_up(p->bl[s], 16);
-    c.offH[s] = p->offH[s];
-  }
-  c.kc = p->d_kc_syn;
-  p->comb_syn = c;
-  c.kc = p->d_kc_ana;
-  p->comb_ana = c;
   // scales at the full bandlimit stay on the caller's stream; the rest are dealt over the side streams
   p->lane_of.assign(p->nsc, -1);
-  if (!getenv("PXM_NO_SIDE_STREAMS")) {
-    if (const char* e = getenv("PXM_NSIDE")) p->nside = std::max(1, std::min((int)pxm_wav_plan_s::NSIDE, atoi(e)));
-    SidePool* sp = nullptr;
-    if ((rc = side_pool(&sp))) return rc;
-    for (int i = 0; i < p->nside; ++i) {  // borrowed from the per-device pool, never destroyed
-      p->side[i] = sp->side[i];
-      p->ev_join[i] = sp->ev_join[i];
-    }
-    p->ev_fork = sp->ev_fork;
-    int k = 0;
-    for (int s = p->nsc - 1; s >= 0; --s)
-      if (p->bl[s] < L) p->lane_of[s] = (k++) % p->nside;
+  SidePool* sp = nullptr;
+  if ((rc = side_pool(&sp))) return rc;
+  for (int i = 0; i < p->nside; ++i) {  // borrowed from the per-device pool, never destroyed
+    p->side[i] = sp->side[i];
+    p->ev_join[i] = sp->ev_join[i];
   }
-  if (!getenv("PXM_NO_DFT_GROUP")) {
-    std::vector<const DftPlan*> dp;
-    for (int s = 0; s < p->nsc; ++s) dp.push_back(&p->dft[s]);
-    rc = dft5_group_create(dp, p->offG, p->coef_off, p->ncol, p->ws, &p->dft_group);
-    if (rc < 0) return rc;  // rc == 1: no group -> per-scale launches
-  }
+  p->ev_fork = sp->ev_fork;
+  int k = 0;
+  for (int s = p->nsc - 1; s >= 0; --s)
+    if (p->bl[s] < L) p->lane_of[s] = (k++) % p->nside;
+  std::vector<const DftPlan*> dp;
+  for (int s = 0; s < p->nsc; ++s) dp.push_back(&p->dft[s]);
+  rc = dft5_group_create(dp, p->offG, p->coef_off, p->ncol, p->ws, &p->dft_group);
+  if (rc < 0) return rc;  // rc == 1: no group -> per-scale launches
   *plan = guard.release();
   return 0;
 }
@@ -819,11 +736,10 @@ int pxm_wav_plan_destroy(pxm_wav_plan_t p) {
   deferred_free(p->d_kc_syn);
   deferred_free(p->d_kc_ana);
   deferred_free(p->d_wlk);
-  deferred_free(p->d_flow_flags);
   deferred_free(p->d_status);
   // (side streams / events belong to the per-device pool)
-  TaskList* tls[] = {&p->syn_fwd, &p->syn_inv, &p->adj_invadj, &p->adj_fwdadj, &p->adj_invadj_R, &p->gram, &p->adj_invadj_D,
-                     &p->ana_fwd, &p->ana_inv, &p->anadj_invadj, &p->anadj_fwdadj, &p->wl_inv, &p->wl_invadj, &p->flow};
+  TaskList* tls[] = {&p->syn_fwd, &p->syn_inv, &p->adj_invadj, &p->adj_fwdadj, &p->gram, &p->adj_invadj_D,
+                     &p->ana_fwd, &p->ana_inv, &p->anadj_invadj, &p->anadj_fwdadj, &p->wl_inv, &p->wl_invadj};
   for (TaskList* t : tls) free_tasks(t);
   profiler_release(&p->prof);
   for (ShtTables* T : p->held) release_tables(T);
@@ -915,25 +831,12 @@ int64_t pxm_wav_workspace_nonfinite(pxm_wav_plan_t p, pxm_stream_t stream) {
   return (int64_t)h;
 }
 
-// bit mask of the bounded waits of this plan's kernels that EXPIRED since the last clear (0 = none): bit 0 a wait of
-// the dataflow GEMM launch, bit 1 a wave-pair wait of the fused phi-DFT kernels.  Synchronises the stream.
+// bit mask of the bounded waits of this plan's kernels that EXPIRED since the last clear (0 = none): bit 1 a wave-pair
+// wait of the fused phi-DFT kernels.  Synchronises the stream.
 int pxm_wav_status(pxm_wav_plan_t p, int clear, pxm_stream_t stream) {
   PXM_REQUIRE(p, "pxm_wav_status: null plan");
   return status_read(p->d_status, (hipStream_t)stream, clear);
 }
-// 0 / 1: the dataflow bit of pxm_wav_status (kept for callers of the round-3 interface); synchronises
-int pxm_wav_flow_status(pxm_wav_plan_t p, pxm_stream_t stream) {
-  PXM_REQUIRE(p, "pxm_wav_flow_status: null plan");
-  const int st = status_read(p->d_status, (hipStream_t)stream, 0);
-  return st < 0 ? st : (st & PXM_STATUS_FLOW_WAIT_BIT ? 1 : 0);
-}
-// 1 when this plan's ring-space step takes the dataflow launch (PXM_FLOW=1 and every condition of wav_make_gram_lists
-// held), 0 otherwise -- known once pxm_wav_ring_set_data has run
-int pxm_wav_flow_enabled(pxm_wav_plan_t p) {
-  PXM_REQUIRE(p, "pxm_wav_flow_enabled: null plan");
-  return p->use_flow ? 1 : 0;
-}
-
 // number of scales whose rings the fused rings -> X' -> rings launch of this plan transforms with the exact-length unit
 // (csrc/dft_pfa.h: ring length 511), 0 when the launch is not grouped or PXM_DFT_PFA=0
 int pxm_wav_exact_dft_scales(pxm_wav_plan_t p) {
@@ -955,14 +858,6 @@ static int wav_check(pxm_wav_plan_t p, const void* a, const void* b, int C, cons
     set_error(std::string(who) + ": C outside [1, max_chains]");
     return -1;
   }
-  return 0;
-}
-
-static int launch_combine(const CombineArgs& c, const double* ws, double* HL, hipStream_t st) {
-  const int64_t total = (int64_t)(2 * c.L - 1) * c.Rp * c.ncol;
-  int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(k_wav_combine, dim3(blocks), dim3(256), 0, st, c, ws, HL);
-  PXM_HIP(hipGetLastError());
   return 0;
 }
 
@@ -1084,7 +979,6 @@ static int wav_rings_to_blocks(pxm_wav_plan_t p, PxOut proto, int C, hipStream_t
 // G_s -> coefficient blocks (with out's epilogue) and, in the same kernels, the rings of the written blocks
 // back into G_s.  Only when every scale has a fused kernel (wav_can_fuse_dft).
 static bool wav_can_fuse_dft(pxm_wav_plan_t p) {
-  if (!p->fused_dft) return false;
   for (int s = 0; s < p->nsc; ++s)
     if (!dft_can_fuse(p->dft[s])) return false;
   return true;
@@ -1093,20 +987,17 @@ static bool wav_can_fuse_dft(pxm_wav_plan_t p) {
 static int wav_rings_update_rings(pxm_wav_plan_t p, PxOut proto, int C, hipStream_t st) {
   if (p->dft_group.d && p->dft_group.all) {  // one grid for every scale, small scales first
     proto.chain_stride = p->ncoefs;
-    // (it also zeroes the counters of the dataflow GEMM launch: it runs between two of them in a stepping loop)
-    return dft5_group_launch(p->dft_group, p->ws, p->ncol, proto, C, st, &p->prof, p->use_flow ? p->d_flow_flags : nullptr,
-                             p->use_flow ? p->L : 0);
+    return dft5_group_launch(p->dft_group, p->ws, p->ncol, proto, C, st, &p->prof);
   }
   bool used[pxm_wav_plan_s::NSIDE];
   int rc = wav_fork(p, st, used);
   if (rc) return rc;
   // side-stream (small) scales are enqueued first: the full-size kernels fill every wave slot of the chip
   // (2 waves per SIMD by registers), so whatever is enqueued behind them only runs in their tail
-  const bool small_first = p->dft_small_first;
   for (int pass = 0; pass < 2; ++pass)
     for (int s = p->nsc - 1; s >= 0; --s) {
       const bool side = p->lane_of[s] >= 0;
-      if (side != (small_first ? pass == 0 : pass == 1)) continue;
+      if (side != (pass == 0)) continue;
       PxOut out = proto;
       out.chain_stride = p->ncoefs;
       out.ring0 = p->coef_off[s];
@@ -1122,7 +1013,6 @@ int pxm_wav_synthesis(pxm_wav_plan_t p, const void* X, void* f, int C, pxm_strea
   hipStream_t st = (hipStream_t)stream;
   if ((rc = wav_blocks_to_rings(p, X, C, st))) return rc;
   if ((rc = run_tasks(p->syn_fwd, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
-  if (!p->fused_combine && (rc = launch_combine(p->comb_syn, p->ws, p->ws + p->offHL, st))) return rc;
   if ((rc = run_tasks(p->syn_inv, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
   PxOut out;
   out.f = (double*)f;
@@ -1240,12 +1130,11 @@ int pxm_wav_image_step(pxm_wav_plan_t p, const void* X, const void* data, const 
     if ((rc = wav_blocks_to_rings(p, X_out, C, st))) return rc;
   }
   if ((rc = run_tasks(p->syn_fwd, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
-  if (!p->fused_combine && (rc = launch_combine(p->comb_syn, p->ws, p->ws + p->offHL, st))) return rc;
   if ((rc = run_tasks(p->syn_inv, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;             // rings of S X'
   PxOut po;
   po.f = (double*)preds_out;
   po.chain_stride = (int64_t)p->L * (2 * p->L - 1);
-  if (p->dftL.use5 && p->fused_dft) {  // (only the wave paths implement the residual epilogue)  // rings -> preds -> residual -> rings, one kernel
+  if (p->dftL.use5) {  // (only the wave paths implement the residual epilogue)  // rings -> preds -> residual -> rings, one kernel
     image_residual(po, data, invcov, invcov_complex);
     rc = launch_ring2px2ring(p->dftL, p->ws + p->offGL, p->ncol, po, C, st);
     return rc < 0 ? rc : (rc ? -1 : 0);
@@ -1255,19 +1144,6 @@ int pxm_wav_image_step(pxm_wav_plan_t p, const void* X, const void* data, const 
 }
 
 // ---- ring-space MYULA step (identity measurement, uniform inverse covariance) -------------------------
-}  // extern "C"
-namespace pxm {
-// G_R[m][t][c] = w * (n * G_L[m][t][c] - G_D[m][t][0]) : the DFT of the image-space residual w (preds - data)
-__global__ void k_ring_residual(const double2* __restrict__ GL, const double2* __restrict__ GD, double2* __restrict__ GR,
-                                int64_t total, int Cp, double n, double2 w) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const double2 g = GL[i], d = GD[(i / Cp) * Cp];
-    GR[i] = cmul(w, double2{n * g.x - d.x, n * g.y - d.y});
-  }
-}
-}  // namespace pxm
-extern "C" {
-
 }  // extern "C"
 namespace pxm {
 // HDc[(mi Rp + row) 2 + {0, 1}] = H_D[(mi Rp + row) ncol + {0, 1}]: chain 0 of the H-layout data term, without the
@@ -1283,7 +1159,7 @@ extern "C" {
 // Gram tables + the two extra task lists of the ring-space step (first pxm_wav_ring_set_data of a plan)
 static int wav_make_gram_lists(pxm_wav_plan_t p) {
   int rc;
-  if (p->use_gram && !p->gram.d) {
+  if (!p->gram.d) {
     if ((rc = get_tables(p->L, 0, 1u << TAB_GRAM, &p->TL))) return rc;
     wav_hold(p, p->TL);
     std::vector<GemmTask> v;
@@ -1298,49 +1174,6 @@ static int wav_make_gram_lists(pxm_wav_plan_t p) {
     v.clear();
     append_gemm_tasks(*p->TL, TAB_INV_ADJ, p->ncol, p->offGD, p->L, p->Rp, p->offHD, p->L, p->Rp, nullptr, p->offS, p->ws, v);
     if ((rc = upload_tasks(v, true, &p->adj_invadj_D, {p->L}, p->ncol, p->ws, "inverse-adjoint of the data rings"))) return rc;
-    // dataflow list: [Gram tasks, longest first | forward-adjoint tasks of every scale, longest first]; a
-    // forward-adjoint task of order m waits until the Gram tasks of m (one per block of 128 rows) have signalled
-    const char* fe = getenv("PXM_FLOW");
-    if (p->ncol <= 32 && p->fused_combine && wav_can_fuse_dft(p) && p->dft_group.d && p->dft_group.all && fe && atoi(fe) != 0) {
-      std::vector<GemmTask> gv, av = p->h_adj_fwdadj, fl;
-      GemmFuse fz2;
-      fz2.x2_base = p->offHB;
-      fz2.hd_base = p->offHDc;
-      fz2.hd_stride = 2;
-      append_gemm_tasks(*p->TL, TAB_GRAM, p->ncol, p->offHA, p->L, p->Rp, p->offHL, p->L, p->Rp, nullptr, p->offS, p->ws, gv, 0, fz2);
-      auto work = [](const GemmTask& a) { return (int64_t)(a.k_end - a.k_beg) * a.n_rt; };
-      std::stable_sort(gv.begin(), gv.end(), [&](const GemmTask& a, const GemmTask& b) { return work(a) > work(b); });
-      // consumers in the order their producers finish (PXM_FLOW_ORDER=ready, default): high orders first -- their
-      // Gram chains are the short ones; =lpt: longest first, which parks the tasks of m < 16 in the slots until the
-      // 16-chunk Gram chains are through
-      const char* fo = getenv("PXM_FLOW_ORDER");
-      if (fo && std::string(fo) == "lpt")
-        std::stable_sort(av.begin(), av.end(), [&](const GemmTask& a, const GemmTask& b) { return work(a) > work(b); });
-      else
-        std::stable_sort(av.begin(), av.end(), [&](const GemmTask& a, const GemmTask& b) {
-          return a.m_unit / 16 != b.m_unit / 16 ? a.m_unit / 16 > b.m_unit / 16 : work(a) > work(b);
-        });
-      std::vector<int> n_gram(p->L, 0);
-      for (GemmTask& t : gv) {
-        PXM_REQUIRE(t.m_unit >= 0 && t.m_unit < p->L, "flow list: Gram task order outside [0, L)");
-        t.variant = 1;
-        t.signal_idx = t.m_unit;
-        ++n_gram[t.m_unit];
-      }
-      for (GemmTask& t : av) {
-        PXM_REQUIRE(t.m_unit >= 0 && t.m_unit < p->L && n_gram[t.m_unit] > 0, "flow list: forward-adjoint task without a Gram producer");
-        t.variant = 2;
-        t.wait_idx = t.m_unit;
-        t.wait_target = n_gram[t.m_unit];
-      }
-      fl = gv;
-      fl.insert(fl.end(), av.begin(), av.end());
-      // (upload_tasks re-sorts by work: the list keeps its two parts because the order is forced to "flow")
-      if ((rc = upload_tasks(fl, true, &p->flow, p->bl, p->ncol, p->ws, "dataflow Gram + forward-adjoint", {}, true))) return rc;
-      if ((rc = dev_alloc(&p->d_flow_flags, (size_t)p->L * sizeof(unsigned), "dataflow counters"))) return rc;
-      if ((rc = dev_zero(p->d_flow_flags, (size_t)p->L * sizeof(unsigned)))) return rc;
-      p->use_flow = true;
-    }
   }
   return 0;
 }
@@ -1354,26 +1187,21 @@ int pxm_wav_ring_set_data(pxm_wav_plan_t p, const void* data, pxm_stream_t strea
   in.f = (const double*)data;
   in.chain_stride = (int64_t)p->L * (2 * p->L - 1);
   if ((rc = launch_px2ring(p->dftL, in, p->ws + p->offGD, p->ncol, 1, st))) return rc;  // chain 0 of G_D
-  if (p->use_gram) {
-    if ((rc = run_tasks(p->adj_invadj_D, p->ws, p->ws, p->ncol, 1, st, GemmAffine(), &p->prof))) return rc;  // H_D = B^T DFT(data)
-    const int64_t rows = (int64_t)(2 * p->L - 1) * p->Rp;
-    hipLaunchKernelGGL(k_pack_data_term, dim3((unsigned)std::min<int64_t>((rows + 255) / 256, 2048)), dim3(256), 0, st,
-                       reinterpret_cast<const double2*>(p->ws + p->offHD), reinterpret_cast<double2*>(p->ws + p->offHDc), rows,
-                       p->ncol / 2);
-    PXM_HIP(hipGetLastError());
-  }
+  if ((rc = run_tasks(p->adj_invadj_D, p->ws, p->ws, p->ncol, 1, st, GemmAffine(), &p->prof))) return rc;  // H_D = B^T DFT(data)
+  const int64_t rows = (int64_t)(2 * p->L - 1) * p->Rp;
+  hipLaunchKernelGGL(k_pack_data_term, dim3((unsigned)std::min<int64_t>((rows + 255) / 256, 2048)), dim3(256), 0, st,
+                     reinterpret_cast<const double2*>(p->ws + p->offHD), reinterpret_cast<double2*>(p->ws + p->offHDc), rows,
+                     p->ncol / 2);
+  PXM_HIP(hipGetLastError());
   p->have_data_rings = true;
   return 0;
 }
 
-// coefficient blocks -> harmonic class buffers (-> rings of S X when the Gram step is not used)
+// coefficient blocks -> harmonic class buffers (what the Gram step reads; pxm_wav_ring_preds forms the rings on demand)
 static int wav_coeffs_to_rings(pxm_wav_plan_t p, const void* X, int C, hipStream_t st, uint64_t* bump = nullptr) {
   int rc;
   if ((rc = wav_blocks_to_rings(p, X, C, st, bump))) return rc;
-  if ((rc = run_tasks(p->syn_fwd, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
-  if (p->use_gram) return 0;
-  if (!p->fused_combine && (rc = launch_combine(p->comb_syn, p->ws, p->ws + p->offHL, st))) return rc;
-  return run_tasks(p->syn_inv, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof);
+  return run_tasks(p->syn_fwd, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof);
 }
 
 int pxm_wav_ring_init(pxm_wav_plan_t p, const void* X, int C, pxm_stream_t stream) {
@@ -1385,7 +1213,7 @@ int pxm_wav_ring_preds(pxm_wav_plan_t p, void* preds, int C, pxm_stream_t stream
   int rc = wav_check(p, preds, preds, C, "pxm_wav_ring_preds");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (p->use_gram && (rc = run_tasks(p->syn_inv, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;  // rings on demand
+  if ((rc = run_tasks(p->syn_inv, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;  // rings on demand
   PxOut out;
   out.f = (double*)preds;
   out.chain_stride = (int64_t)p->L * (2 * p->L - 1);
@@ -1401,38 +1229,15 @@ int pxm_wav_ring_step(pxm_wav_plan_t p, const void* X, double w_re, double w_im,
   PXM_REQUIRE(X != X_out, "pxm_wav_ring_step: X_out must not alias X");
   PXM_REQUIRE((mode & ~PXM_NOISE_F64) >= 0 && (mode & ~PXM_NOISE_F64) <= 2, "pxm_wav_ring_step: mode must be 0, 1 or 2 (| PXM_NOISE_F64)");
   hipStream_t st = (hipStream_t)stream;
-  if (p->use_gram) {
-    // H' = w ((2L-1) B^T B H - B^T DFT(data)): inverse transform, ring residual and inverse-adjoint in one GEMM
-    GemmAffine aff;
-    aff.on = 1;
-    aff.ns = (double)(2 * p->L - 1);
-    aff.wr = w_re;
-    aff.wi = w_im;
-    aff.bump = p->iter_dev;  // the step's iteration number = counter after this bump
-    if (p->use_flow) {  // Gram + forward-adjoint tasks of every scale in ONE grid, per-m counters between them
-      note_stream(st);
-      aff.ncol_live = 2 * C;
-      const int ct = p->ncol >= 32 ? 2 : 1, cg = std::min(C, 8 * ct);
-      rc = launch_gemm_flow(p->flow.d, p->flow.n, 2, p->ws, p->ws, p->ncol, ct,
-                            tasklist_bytes(p->gram, cg) + tasklist_bytes(p->adj_fwdadj, cg),
-                            (p->gram.mfma_units + p->adj_fwdadj.mfma_units) * ct * 2048.0, st, aff, p->d_flow_flags,
-                            p->d_status, &p->prof);
-      if (rc) return rc;
-    } else {
-      if ((rc = run_tasks(p->gram, p->ws, p->ws, p->ncol, C, st, aff, &p->prof))) return rc;
-      if ((rc = run_tasks(p->adj_fwdadj, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
-    }
-  } else {
-    if (p->iter_dev && (rc = pxm_wav_iter_counter_add(p, 1, stream))) return rc;
-    const int Cp = p->ncol / 2;
-    const int64_t total = (int64_t)(2 * p->L - 1) * p->Rp * Cp;
-    hipLaunchKernelGGL(k_ring_residual, dim3(2048), dim3(256), 0, st, reinterpret_cast<const double2*>(p->ws + p->offGL),
-                       reinterpret_cast<const double2*>(p->ws + p->offGD), reinterpret_cast<double2*>(p->ws + p->offGR),
-                       total, Cp, (double)(2 * p->L - 1), double2{w_re, w_im});
-    PXM_HIP(hipGetLastError());
-    if ((rc = run_tasks(p->adj_invadj_R, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
-    if ((rc = run_tasks(p->adj_fwdadj, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
-  }
+  // H' = w ((2L-1) B^T B H - B^T DFT(data)): inverse transform, ring residual and inverse-adjoint in one GEMM
+  GemmAffine aff;
+  aff.on = 1;
+  aff.ns = (double)(2 * p->L - 1);
+  aff.wr = w_re;
+  aff.wi = w_im;
+  aff.bump = p->iter_dev;  // the step's iteration number = counter after this bump
+  if ((rc = run_tasks(p->gram, p->ws, p->ws, p->ncol, C, st, aff, &p->prof))) return rc;
+  if ((rc = run_tasks(p->adj_fwdadj, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
   PxOut out;
   out.f = (double*)X_out;
   out.X = (const double*)X;
@@ -1451,9 +1256,7 @@ int pxm_wav_ring_step(pxm_wav_plan_t p, const void* X, double w_re, double w_im,
     // rings -> X_out -> rings of X_out in one kernel per scale, then the per-scale forward GEMMs
     if ((rc = wav_rings_update_rings(p, out, C, st))) return rc;
     if ((rc = run_tasks(p->syn_fwd, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
-    if (p->use_gram) return 0;
-    if (!p->fused_combine && (rc = launch_combine(p->comb_syn, p->ws, p->ws + p->offHL, st))) return rc;
-    return run_tasks(p->syn_inv, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof);
+    return 0;
   }
   if ((rc = wav_rings_to_blocks(p, out, C, st))) return rc;
   return wav_coeffs_to_rings(p, X_out, C, st);
@@ -1471,7 +1274,6 @@ int pxm_wav_ring_step(pxm_wav_plan_t p, const void* X, double w_re, double w_im,
 // plan is left with e.g. the narrow harmonic side but no twin lists -- pxm_wav_wl_attach marks it `wl_failed` and every
 // weak-lensing entry point, a second attach included, refuses it: destroy the plan)
 static int wl_attach_impl(pxm_wav_plan_t p, const int32_t* pix2data, const double* weight, int64_t ndata) {
-  PXM_REQUIRE(p->fused_combine, "pxm_wav_wl_attach: needs the fused wavelet combine (PXM_NO_FUSED_COMBINE is set)");
   PXM_REQUIRE(p->L >= 3, "pxm_wav_wl_attach: Bandlimit must be at least 3 for a spin-2 field");
   const int64_t P = (int64_t)p->L * (2 * p->L - 1);
   PXM_REQUIRE(ndata >= 0 && ndata <= P && (pix2data || ndata == P), "pxm_wav_wl_attach: bad mask description");
@@ -1484,19 +1286,18 @@ static int wl_attach_impl(pxm_wav_plan_t p, const int32_t* pix2data, const doubl
   }
   // one chain, two top scales of equal bandlimit outside the DFT group (L = 512, B = 2: scales 8 and 9): twin ring array
   int twin_cand = -1;
-  if (p->twin_s < 0 && p->pk == 2 && p->Cmax == 1 && !getenv("PXM_NO_TWIN"))
+  if (p->twin_s < 0 && p->pk == 2 && p->Cmax == 1)
     for (int s = 0; s + 1 < p->nsc && twin_cand < 0; ++s)
       if (p->bl[s + 1] == p->bl[s] && p->T[s + 1] == p->T[s] && !wav_in_group(p, s) && !wav_in_group(p, s + 1)) twin_cand = s;
-  const bool narrow = !getenv("PXM_NO_NARROW");
   if (!p->T2 && !p->rec2 && rec_wanted(p->L, 2, p->Cmax)) {
     // few chains: Wigner rows of the two spin-2 contractions by recursion (no 2 x 8 L^3-byte tables, no table build)
-    p->ncol_g2 = narrow ? 2 * p->Cmax : p->ncol;
+    p->ncol_g2 = 2 * p->Cmax;
     if (p->ncol_g2 != p->ncol) {
       const size_t nb = (size_t)(2 * p->L - 1) * p->Rp * p->ncol_g2 * sizeof(double);
       if ((rc = dev_alloc(&p->d_g2n, nb, "narrow spin-2 ring array"))) return rc;
       if ((rc = dev_zero(p->d_g2n, nb))) return rc;
     }
-    if (narrow && twin_cand >= 0) {  // narrow harmonic side (the weak-lensing lists of the twin path are this path's own)
+    if (twin_cand >= 0) {  // narrow harmonic side (the weak-lensing lists of the twin path are this path's own)
       p->ncol_h = 2 * p->Cmax;
       const int64_t sz = (int64_t)(2 * p->L - 1) * p->Rp * p->ncol_h + p->ncol;  // (+ slack for the 16-column address model)
       if ((rc = dev_alloc(&p->d_hn, (size_t)(3 * sz) * sizeof(double), "narrow class buffers and H_L of the weak-lensing path"))) return rc;
@@ -1523,15 +1324,14 @@ static int wl_attach_impl(pxm_wav_plan_t p, const int32_t* pix2data, const doubl
   }
   if (twin_cand >= 0) {
     const int s = twin_cand;
-    // narrow: 4 doubles per row (the two slots); PXM_NO_NARROW=1: the plan's eight-slot lines
-    p->ncol_t = narrow ? 4 : p->ncol;
+    p->ncol_t = 4;  // narrow: 4 doubles per row (the two slots)
     // (+ one row: the address model of the GEMM stage counts a row's width from a slab's first column, and slot 1 starts at 2)
     const int64_t n = (int64_t)(2 * p->bl[s] - 1) * round_up(p->bl[s], 16) * p->ncol_t + p->ncol_t;
     if ((rc = dev_alloc(&p->d_twin, (size_t)n * sizeof(double), "twin ring array of the two top scales"))) return rc;
     if ((rc = dev_zero(p->d_twin, (size_t)n * sizeof(double)))) return rc;
     p->offGT = p->d_twin - p->ws;
     bool narrow_g = false;
-    if (narrow && p->ncol_h && p->dft_group.d && p->dft_group.five && p->plain_group && !getenv("PXM_NO_NARROW_GROUP")) {
+    if (p->ncol_h && p->dft_group.d && p->dft_group.five && p->plain_group) {
       // the member scales of the DFT group on rows of 2 Cmax doubles as well: own arrays, own group descriptors
       p->ncol_gn = 2 * p->Cmax;
       p->offGn = p->offG;
@@ -1557,8 +1357,8 @@ static int wl_attach_impl(pxm_wav_plan_t p, const int32_t* pix2data, const doubl
     std::vector<char> shared;
     if ((rc = wav_packed_lists(p, 0, TAB_FWD, s, p->offGT, vf, &shared, p->ncol_t, p->ncol_h != 0, narrow_g))) return rc;
     if ((rc = wav_packed_lists(p, 1, TAB_FWD_ADJ, s, p->offGT, va, nullptr, p->ncol_t, p->ncol_h != 0, narrow_g))) return rc;
-    if ((rc = upload_tasks(vf, true, &p->wl_syn_fwd, p->bl, p->ncol, p->ws, "weak-lensing synthesis forward (twin scales)", p->el_lo_s, false, p->pk, shared))) return rc;
-    if ((rc = upload_tasks(va, true, &p->wl_adj_fwdadj, p->bl, p->ncol, p->ws, "weak-lensing forward-adjoint (twin scales)", p->el_lo_s, false, p->pk, shared))) return rc;
+    if ((rc = upload_tasks(vf, true, &p->wl_syn_fwd, p->bl, p->ncol, p->ws, "weak-lensing synthesis forward (twin scales)", p->el_lo_s, p->pk, shared))) return rc;
+    if ((rc = upload_tasks(va, true, &p->wl_adj_fwdadj, p->bl, p->ncol, p->ws, "weak-lensing forward-adjoint (twin scales)", p->el_lo_s, p->pk, shared))) return rc;
     p->twin_s = s;
   }
   p->wl_gidx = pix2data;
@@ -1657,7 +1457,6 @@ int pxm_wav_analysis_adjoint(pxm_wav_plan_t p, const void* X, void* f, int C, px
   hipStream_t st = (hipStream_t)stream;
   if ((rc = wav_blocks_to_rings(p, X, C, st))) return rc;
   if ((rc = run_tasks(p->anadj_invadj, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
-  if (!p->fused_combine && (rc = launch_combine(p->comb_ana, p->ws, p->ws + p->offHL, st))) return rc;
   if ((rc = run_tasks(p->anadj_fwdadj, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
   PxOut out;
   out.f = (double*)f;

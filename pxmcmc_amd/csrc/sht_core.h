@@ -46,10 +46,6 @@ struct GemmTask {
   int n_rt;            // row tiles in this task (1..8)
   int nslab;           // live slabs: 1 (all m stored) or 2 (+-m pair)
   double sign1;        // factor on the -m outputs ((-1)^m)
-  // dataflow launch (k_sht_gemm_flow): kernel variant of this task (1 = Gram: two operands + affine epilogue,
-  // 2 = forward-adjoint: per-k operand scale), the counter it waits for (index, value; -1 = none) and the one it
-  // increments when its rows are stored (-1 = none); ignored by the ordinary launches
-  int variant, wait_idx, wait_target, signal_idx;
   int m_unit;          // the order this task belongs to: m (paired tables: m >= 0 serves +-m) or m + L - 1
   int hd_stride;       // doubles between consecutive rows of the affine constants: 2 = the chain-less [m][row] complex
                        // array of the Gram step (whole 64-B segments per wave), ncol = columns 0, 1 of an H-layout array
@@ -184,10 +180,6 @@ inline double gemm_alg_bytes(int L, bool paired, int C, int el_lo = 0) {
 }
 
 int gemm_rows_per_task(int ncol);
-// dataflow launch of a [Gram tasks | forward-adjoint tasks] list over ONE column group (sht_gemm.hip: k_sht_gemm_flow)
-int launch_gemm_flow(const GemmTask* d_tasks, int n_tasks, int nslab, const double* X, double* Y, int ncol, int ct,
-                     double alg_bytes, double flops, hipStream_t stream, const GemmAffine& aff, unsigned* flags,
-                     unsigned* err, Profiler* prof);
 // host model of every address k_sht_gemm forms for a task list (sht_gemm.hip); < 0 + error text when a range leaves
 // its allocation
 int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags, int ncol, const double* ws_base,
@@ -228,8 +220,8 @@ struct DftPlan {
   unsigned* d_status = nullptr;
   unsigned spin_limit = 1u << 18;
 };
-// bits of a plan's status word (pxm_wav_status / pxm_sht_status)
-enum { PXM_STATUS_FLOW_WAIT_BIT = 1, PXM_STATUS_PAIR_SYNC_BIT = 2 };
+// bit of a plan's status word (pxm_wav_status / pxm_sht_status); bit 0 is unused
+enum { PXM_STATUS_PAIR_SYNC_BIT = 2 };
 
 int make_dft_plan(int L, DftPlan* p);
 void free_dft_plan(DftPlan* p);
@@ -301,7 +293,7 @@ int dft5_group_create(const std::vector<const DftPlan*>& plans, const std::vecto
                       const std::vector<int64_t>& ring0, int ncol, const double* ws_base,
                       DftGroupList* out);  // 1 = not available
 int dft5_group_launch(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st,
-                      Profiler* prof = nullptr, unsigned* zero_words = nullptr, int n_zero = 0);
+                      Profiler* prof = nullptr);
 // the plain transforms of every member scale in one grid each (blocks <-> rings of the generic wavelet operators)
 int dft5_group_px2ring(const DftGroupList& g, double* ws, int ncol, const PxIn& in, int C, hipStream_t st);
 int dft5_group_ring2px(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st);

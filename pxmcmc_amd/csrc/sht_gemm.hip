@@ -35,10 +35,8 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // ---------------------------------------------------------------------------------------
 constexpr int KC = 16;  // contraction rows per staged chunk
 // NW waves per workgroup, RT row tiles of 16 rows per wave: a task covers NW*RT row tiles.
-// NSET: register sets of the table AND operand streams, i.e. both run NSET-1 chunks (of 16 k) ahead.  2 everywhere:
-// occupancy hides the load latency (60 VGPR at 16 columns, 4 workgroups per CU); 3 / 4 sets measured 10-15 % slower
-// on the grouped launches, and 4 % / 16 % slower on the Gram launch too (PXM_GEMM_GRAM_NSET=3|4 for A/B runs: its
-// short tasks re-read their last chunk in the deeper prologue, its long chains are not what bounds it).
+// NSET: register sets of the table AND operand streams, i.e. both run NSET-1 chunks (of 16 k) ahead (the depth each
+// launcher instantiates, and why, is at launch_gemm / launch_gemm_packed below).
 // timing-only ablations (development; results are wrong): PXM_GEMM_ABLATE & 1 no MFMA, & 2 no table loads,
 // & 4 no operand staging (loads, LDS stores and the per-chunk barrier)
 #ifndef PXM_GEMM_ABLATE
@@ -63,20 +61,6 @@ __device__ __forceinline__ double stage_scale(double a, double sc) { return a * 
 __device__ __forceinline__ double2 stage_scale(double2 a, double sc) { return double2{a.x * sc, a.y * sc}; }
 // TWO: the tasks of the launch sum a second operand in while staging; SK: they scale the operand per contraction row
 // (compile-time, so that the launches without them issue no loads for them)
-// FLOW (dataflow launch, k_sht_gemm_flow below): 0 = none; 1 = producer: the result rows are written with agent-scope
-// (write-through) stores, so that a consumer workgroup on another XCD -- another L2 -- can read them inside the same
-// launch; 2 = consumer: the operand is staged with agent-scope loads (they do not hit a stale line of this XCD's L2).
-template <class T>
-__device__ __forceinline__ T ld_agent(const T* p);
-template <>
-__device__ __forceinline__ double ld_agent<double>(const double* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <>
-__device__ __forceinline__ double2 ld_agent<double2>(const double2* p) {
-  const double* q = reinterpret_cast<const double*>(p);
-  return double2{ld_agent(q), ld_agent(q + 1)};
-}
 template <int CT, int NSLAB>
 struct GemmGeom {
   static constexpr int NCT = CT * NSLAB;
@@ -89,7 +73,7 @@ struct GemmGeom {
 // for up to two transforms (the two L-band-limited wavelet scales).  With one chain the unpacked launch spends two MFMA
 // column tiles per table fragment on 4 live columns and streams the 512-table once per scale; packed, one tile carries the
 // 8 live columns of both scales: half the table bytes and a quarter of the MFMAs.  Instantiated with CT = NSLAB = 1.
-template <int CT, int NSLAB, int NW, int RT, int NSET, bool TWO, bool SK, int FLOW, int PK = 0>
+template <int CT, int NSLAB, int NW, int RT, int NSET, bool TWO, bool SK, int PK = 0>
 __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks, const int bid,
                                               const double* __restrict__ X, double* __restrict__ Y, int ncol, int col0,
                                               const GemmAffine& aff, double (*xs)[KC][GemmGeom<CT, NSLAB>::PITCH]) {
@@ -168,8 +152,7 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
   {                                                                                                 \
     const int cs = min((CH), nch - 1);                                                              \
     _Pragma("unroll") for (int i = 0; i < IT; ++i) {                                                \
-      st[SET][i] = FLOW == 2 ? ld_agent(reinterpret_cast<const stage_t*>(sp[i] + (int64_t)cs * KC * xn))  \
-                             : *reinterpret_cast<const stage_t*>(sp[i] + (int64_t)cs * KC * xn);  \
+      st[SET][i] = *reinterpret_cast<const stage_t*>(sp[i] + (int64_t)cs * KC * xn);                \
       if (TWO) st2[SET][i] = *reinterpret_cast<const stage_t*>(sp2[i] + (int64_t)cs * KC * xn);   \
       if (SK) ssc[SET][i] = skp[i][cs * KC];                                                        \
     }                                                                                               \
@@ -341,10 +324,7 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
           v = (cl & 1) ? (aff.wr * u + aff.wi * pu) : (aff.wr * u - aff.wi * pu);
           if (col0 + cin + cl >= aff.ncol_live) v = 0.0;  // padding chains stay at zero (they have no prox / damping)
         }
-        if (row >= t.row_lo[grp] && row < t.row_hi[grp]) {
-          if (FLOW == 1) __hip_atomic_store(yb + (int64_t)(4 * q) * ncol, sgn * rsv[r][grp][q] * v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          else yb[(int64_t)(4 * q) * ncol] = sgn * rsv[r][grp][q] * v;
-        }
+        if (row >= t.row_lo[grp] && row < t.row_hi[grp]) yb[(int64_t)(4 * q) * ncol] = sgn * rsv[r][grp][q] * v;
       }
     }
   }
@@ -376,61 +356,14 @@ __global__ __launch_bounds__(64 * NW) void k_sht_gemm(const GemmTask* __restrict
                                                       int ncol, int col0, GemmAffine aff) {
   __shared__ double xs[2][KC][GemmGeom<CT, NSLAB>::PITCH];
   if (aff.bump && blockIdx.x == 0 && threadIdx.x == 0) *aff.bump += 1;  // Philox iteration counter of the ring-space step
-  sht_gemm_body<CT, NSLAB, NW, RT, NSET, TWO, SK, 0>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs);
+  sht_gemm_body<CT, NSLAB, NW, RT, NSET, TWO, SK>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs);
 }
 // packed column tile (few-chain plans): PK live columns per slab, up to 16 / PK slabs in the one tile
 template <int PK, int NW, int RT, int NSET, bool TWO, bool SK>
 __global__ __launch_bounds__(64 * NW) void k_sht_gemm_pk(const GemmTask* __restrict__ tasks, const double* __restrict__ X,
                                                          double* __restrict__ Y, int ncol, int col0, GemmAffine aff) {
   __shared__ double xs[2][KC][GemmGeom<1, 1>::PITCH];
-  sht_gemm_body<1, 1, NW, RT, NSET, TWO, SK, 0, PK>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs);
-}
-
-// ---------------------------------------------------------------------------------------
-// Dataflow launch of the ring-space step: the Gram tasks and the forward-adjoint tasks of EVERY scale in one grid.
-// A forward-adjoint task (m, scale, row block) reads H'[m], which the one or two Gram tasks of that m write: it waits
-// on a per-m counter the Gram tasks increment when their rows are stored, instead of on a launch boundary -- the
-// forward-adjoint tasks of the orders whose (short) Gram tasks are done fill the CUs the long Gram chains (m < 16:
-// 16 dependent chunks) leave idle.  Deadlock-free by construction: the Gram tasks come first in the grid, so every
-// one of them has been dispatched before the first waiting task, and they wait for nothing; the wait is bounded
-// all the same (a counter that never arrives raises *err instead of hanging the GPU).  Visibility across XCDs (one
-// L2 each): the producers store their rows write-through (agent scope) and signal after s_waitcnt vmcnt(0); the
-// consumers stage the operand with agent-scope loads (sht_gemm_body: FLOW).  The counters are zeroed by the grouped
-// DFT launch that runs between two dataflow launches of a stepping loop.
-// ---------------------------------------------------------------------------------------
-template <int CT, int NSLAB, int NW, int RT, int NSET>
-__global__ __launch_bounds__(64 * NW) void k_sht_gemm_flow(const GemmTask* __restrict__ tasks, const double* __restrict__ X,
-                                                           double* __restrict__ Y, int ncol, int col0, GemmAffine aff,
-                                                           unsigned* __restrict__ flags, unsigned* __restrict__ err) {
-  __shared__ double xs[2][KC][GemmGeom<CT, NSLAB>::PITCH];
-  if (aff.bump && blockIdx.x == 0 && threadIdx.x == 0) *aff.bump += 1;
-  const int variant = tasks[blockIdx.x].variant, wait_idx = tasks[blockIdx.x].wait_idx,
-            wait_target = tasks[blockIdx.x].wait_target, signal_idx = tasks[blockIdx.x].signal_idx;
-  if (wait_idx >= 0) {
-    if (threadIdx.x == 0) {
-      unsigned spins = 0;
-      while ((int)__hip_atomic_load(flags + wait_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < wait_target) {
-        if (++spins > (1u << 22)) {  // (~1 s: the producers of a live launch arrive within tens of microseconds)
-          __hip_atomic_fetch_or(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // PXM_STATUS_FLOW_WAIT
-          break;
-        }
-        __builtin_amdgcn_s_sleep(8);
-      }
-    }
-    __syncthreads();
-  }
-  if (variant == 1) {
-    sht_gemm_body<CT, NSLAB, NW, RT, NSET, true, false, 1>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs);
-  } else {
-    GemmAffine none;
-    none.ncol_live = aff.ncol_live;
-    sht_gemm_body<CT, NSLAB, NW, RT, NSET, false, true, 2>(tasks, blockIdx.x, X, Y, ncol, col0, none, xs);
-  }
-  if (signal_idx >= 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's write-through stores have been acknowledged
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(flags + signal_idx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  sht_gemm_body<1, 1, NW, RT, NSET, TWO, SK, PK>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs);
 }
 
 // ---- live profiler: event pairs around GEMM / grouped-DFT launches, owned by a plan ----------------
@@ -564,27 +497,24 @@ int launch_gemm(const GemmTask* d_tasks, int n_tasks, int nslab, int flags, cons
   dim3 grid(n_tasks), block(512);
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (prof) prof->next(prof->gemm, &ev0, &ev1, alg_bytes, flops, n_tasks);
-  // look-ahead of the table / operand streams in chunks + 1: PXM_GEMM_NSET (all launches), PXM_GEMM_GRAM_NSET (Gram)
-  static const int all_nset = getenv("PXM_GEMM_NSET") ? atoi(getenv("PXM_GEMM_NSET")) : 2;
-  static const int gram_nset = getenv("PXM_GEMM_GRAM_NSET") ? atoi(getenv("PXM_GEMM_GRAM_NSET")) : all_nset;
-  const int nset = (aff.on ? gram_nset : all_nset) == 3 ? 3 : 2;
-#define PXM_GEMM_L4(CT_, NS_, NSET_, TWO_, SK_) \
-  hipExtLaunchKernelGGL((k_sht_gemm<CT_, NS_, 8, 1, NSET_, TWO_, SK_>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff)
-#define PXM_GEMM_L3(CT_, NS_, NSET_)                                   \
-  switch (flags & 3) {                                                 \
-    case 0: PXM_GEMM_L4(CT_, NS_, NSET_, false, false); break;         \
-    case 1: PXM_GEMM_L4(CT_, NS_, NSET_, true, false); break;          \
-    case 2: PXM_GEMM_L4(CT_, NS_, NSET_, false, true); break;          \
-    default: PXM_GEMM_L4(CT_, NS_, NSET_, true, true); break;          \
+  // look-ahead NSET = 2 (one chunk ahead) on every launch: occupancy hides the load latency (60 VGPR at 16 columns,
+  // 4 workgroups per CU); 3 / 4 sets measured 10-15 % slower on the grouped launches, and 4 % / 16 % slower on the
+  // Gram launch too (its short tasks re-read their last chunk in the deeper prologue, its long chains are not what
+  // bounds it)
+#define PXM_GEMM_L4(CT_, NS_, TWO_, SK_) \
+  hipExtLaunchKernelGGL((k_sht_gemm<CT_, NS_, 8, 1, 2, TWO_, SK_>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff)
+#define PXM_GEMM_L3(CT_, NS_)                                   \
+  switch (flags & 3) {                                          \
+    case 0: PXM_GEMM_L4(CT_, NS_, false, false); break;         \
+    case 1: PXM_GEMM_L4(CT_, NS_, true, false); break;          \
+    case 2: PXM_GEMM_L4(CT_, NS_, false, true); break;          \
+    default: PXM_GEMM_L4(CT_, NS_, true, true); break;          \
   }
-#define PXM_GEMM_L2(CT_, NS_) \
-  if (nset == 3) { PXM_GEMM_L3(CT_, NS_, 3) } else { PXM_GEMM_L3(CT_, NS_, 2) }
   if (nslab == 2) {
-    if (ct == 1) { PXM_GEMM_L2(1, 2) } else { PXM_GEMM_L2(2, 2) }
+    if (ct == 1) { PXM_GEMM_L3(1, 2) } else { PXM_GEMM_L3(2, 2) }
   } else {
-    if (ct == 1) { PXM_GEMM_L2(1, 1) } else { PXM_GEMM_L2(2, 1) }
+    if (ct == 1) { PXM_GEMM_L3(1, 1) } else { PXM_GEMM_L3(2, 1) }
   }
-#undef PXM_GEMM_L2
 #undef PXM_GEMM_L3
 #undef PXM_GEMM_L4
   PXM_HIP(hipGetLastError());
@@ -600,41 +530,21 @@ int launch_gemm_packed(const GemmTask* d_tasks, int n_tasks, int pk, int flags, 
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (prof) prof->next(prof->gemm, &ev0, &ev1, alg_bytes, flops, n_tasks);
   GemmAffine aff;
-  // look-ahead of the table / operand streams: NSET - 1 chunks.  The packed launches carry a quarter of the MFMA work per table
-  // byte of the 16-columns-per-slab ones and 44 - 54 VGPRs: with one chunk of look-ahead their waves spent half their cycles
-  // in s_waitcnt (SQ_WAIT_INST_ANY 425 M of 825 M wave-cycles, 2.5 TB/s); PXM_GEMM_PK_NSET = 2 | 3 | 4 for A/B runs
-  static const int pk_nset = getenv("PXM_GEMM_PK_NSET") ? atoi(getenv("PXM_GEMM_PK_NSET")) : 3;
-#define PXM_PK_L(PK_, NSET_, TWO_, SK_) \
-  hipExtLaunchKernelGGL((k_sht_gemm_pk<PK_, 8, 1, NSET_, TWO_, SK_>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff)
-#define PXM_PK_N(PK_, NSET_)                                     \
-  switch (flags & 3) {                                           \
-    case 0: PXM_PK_L(PK_, NSET_, false, false); break;           \
-    case 1: PXM_PK_L(PK_, NSET_, true, false); break;            \
-    case 2: PXM_PK_L(PK_, NSET_, false, true); break;            \
-    default: PXM_PK_L(PK_, NSET_, true, true); break;            \
+  // look-ahead NSET = 3 (two chunks ahead).  The packed launches carry a quarter of the MFMA work per table byte of the
+  // 16-columns-per-slab ones and 44 - 54 VGPRs: with one chunk of look-ahead their waves spent half their cycles in
+  // s_waitcnt (SQ_WAIT_INST_ANY 425 M of 825 M wave-cycles, 2.5 TB/s)
+#define PXM_PK_L(PK_, TWO_, SK_) \
+  hipExtLaunchKernelGGL((k_sht_gemm_pk<PK_, 8, 1, 3, TWO_, SK_>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff)
+#define PXM_PK_N(PK_)                                     \
+  switch (flags & 3) {                                    \
+    case 0: PXM_PK_L(PK_, false, false); break;           \
+    case 1: PXM_PK_L(PK_, true, false); break;            \
+    case 2: PXM_PK_L(PK_, false, true); break;            \
+    default: PXM_PK_L(PK_, true, true); break;            \
   }
-#define PXM_PK_F(PK_)                                            \
-  if (pk_nset == 2) { PXM_PK_N(PK_, 2) } else if (pk_nset == 4) { PXM_PK_N(PK_, 4) } else { PXM_PK_N(PK_, 3) }
-  if (pk == 2) { PXM_PK_F(2) } else { PXM_PK_F(4) }
+  if (pk == 2) { PXM_PK_N(2) } else { PXM_PK_N(4) }
 #undef PXM_PK_N
-#undef PXM_PK_F
 #undef PXM_PK_L
-  PXM_HIP(hipGetLastError());
-  return 0;
-}
-
-int launch_gemm_flow(const GemmTask* d_tasks, int n_tasks, int nslab, const double* X, double* Y, int ncol, int ct,
-                     double alg_bytes, double flops, hipStream_t stream, const GemmAffine& aff, unsigned* flags,
-                     unsigned* err, Profiler* prof) {
-  if (n_tasks == 0) return 0;
-  PXM_REQUIRE(nslab == 2 && (ct == 1 || ct == 2), "launch_gemm_flow: +-m paired tables, one or two column tiles");
-  dim3 grid(n_tasks), block(512);
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (prof) prof->next(prof->gemm, &ev0, &ev1, alg_bytes, flops, n_tasks);
-  if (ct == 1)
-    hipExtLaunchKernelGGL((k_sht_gemm_flow<1, 2, 8, 1, 2>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, 0, aff, flags, err);
-  else
-    hipExtLaunchKernelGGL((k_sht_gemm_flow<2, 2, 8, 1, 2>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, 0, aff, flags, err);
   PXM_HIP(hipGetLastError());
   return 0;
 }
@@ -700,9 +610,6 @@ static void append_tasks_impl(const ShtTables& T, int kind, int ncol, const Gemm
     const int n_rt_total = (Rp - row_beg) / 16;
     for (int rt = 0; rt < n_rt_total; rt += rpt) {
       GemmTask g;
-      g.variant = 0;
-      g.wait_idx = g.signal_idx = -1;
-      g.wait_target = 0;
       g.m_unit = T.paired ? m : m + T.L - 1;
       g.tab_off = (T.d_tab[kind] + T.m_off[kind][i] + tab_skip + (int64_t)rt * rt_stride) - ws_base;
       g.rt_stride = rt_stride;

@@ -429,10 +429,6 @@ bool rec_geometry(int L, int spin, int C, int* R_out, int* NW_out, size_t* lds_o
   const int n_units_est = spin == 0 ? (L + 1) / 2 : L;
   int R = 4;
   while (R > 1 && (int64_t)n_units_est * ((nb + R - 1) / R) < 2048) R >>= 1;
-  if (const char* e = std::getenv("PXM_REC_R")) {
-    const int v = std::atoi(e);
-    if (v == 1 || v == 2 || v == 4) R = v;
-  }
   for (;; R <<= 1) {
     // waves: runs of up to R consecutive blocks of one hemisphere (block b is northern when its centre ring is)
     int nw = 0;
@@ -542,12 +538,10 @@ int rec_tables_create(int L, int spin, int C, int Rp, int ncol, RecTables** out,
     return x.first != y.first ? x.first > y.first : x.second < y.second;
   });
   std::vector<int> units;
-  bool pair_orders = true;
-  if (const char* e = std::getenv("PXM_REC_PAIR")) pair_orders = std::atoi(e) != 0;
   for (size_t lo = 0, hi = ord.size(); lo < hi;) {
     const int a0 = ord[lo++].second;
     int b0 = -1;
-    if (pair_orders && lo < hi && ord[lo - 1].first + ord[hi - 1].first <= L + 2) b0 = ord[--hi].second;
+    if (lo < hi && ord[lo - 1].first + ord[hi - 1].first <= L + 2) b0 = ord[--hi].second;
     units.push_back(a0);
     units.push_back(b0);
   }
@@ -631,12 +625,9 @@ static int launch_e2r_nc(const RecTables& T, const RecArgs& a, hipStream_t st, h
 }
 
 template <int R, int NC>
-static int r2e_allow_lds() {  // (dynamic LDS beyond 64 KB has to be allowed per kernel, once)
-  static std::atomic<uint64_t> seen{0};
-  if (first_on_this_device(seen)) {
-    PXM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rec_r2e<R, NC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  }
-  return 0;
+static int r2e_allow_lds() {
+  static std::atomic<uint64_t> done{0};
+  return allow_dynamic_lds(done, {reinterpret_cast<const void*>(k_rec_r2e<R, NC>)});
 }
 
 template <int NC>

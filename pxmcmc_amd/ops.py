@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 import torch
 
-from ._lib import NOISE_F64, STATUS_FLOW_WAIT, STATUS_PAIR_SYNC, PxmError, check, lib, require_gpu
+from ._lib import NOISE_F64, STATUS_PAIR_SYNC, PxmError, check, lib, require_gpu
 
 _CPLX, _REAL = torch.complex128, torch.float64
 
@@ -110,9 +110,7 @@ def raise_on_status(status, what):
         bits = []
         if status & STATUS_PAIR_SYNC:
             bits.append("a wave-pair wait or ring-group wait of the fused phi-DFT kernels expired (csrc/dft5.hip: d5_pair_sync, pfa_group_sync)")
-        if status & STATUS_FLOW_WAIT:
-            bits.append("a wait of the dataflow GEMM launch expired (PXM_FLOW=1)")
-        if status & ~(STATUS_PAIR_SYNC | STATUS_FLOW_WAIT):
+        if status & ~STATUS_PAIR_SYNC:
             bits.append(f"unknown status bits {status:#x}")
         raise PxmError(f"{what}: device status {status:#x}: " + "; ".join(bits) + " -- the results of this plan since its last "
                        "status check are invalid")
@@ -700,17 +698,9 @@ class WavPlan:
     def table_bytes(self, op):
         return int(lib.pxm_wav_table_bytes(self._h, op))
 
-    def flow_status(self):
-        """0: every wait of the dataflow GEMM launches of this plan was satisfied (include/pxmcmc_amd.h); synchronises"""
-        return int(check(lib.pxm_wav_flow_status(self._h, _stream())))
-
     def exact_dft_scales(self):
         """scales whose 511-point rings the fused step transforms with the exact-length unit (csrc/dft_pfa.h); 0 = Bluestein"""
         return int(check(lib.pxm_wav_exact_dft_scales(self._h)))
-
-    def flow_enabled(self):
-        """True when the ring-space step of this plan takes the dataflow launch (PXM_FLOW=1; known after ring_set_data)"""
-        return bool(check(lib.pxm_wav_flow_enabled(self._h)))
 
     def status(self, clear=False):
         """bit mask of the bounded device waits of this plan that expired (0 = none; include/pxmcmc_amd.h); synchronises"""

@@ -1,7 +1,7 @@
-"""Time the ring stage of inverse / inverse_adjoint at L = 512 with one chain: recursion kernels (PXM_REC=1, PXM_REC_R = ring
-blocks per wave, PXM_REC_PAIR = orders per unit) against the ring-table GEMM.  Run on the GPU box (best under
-rocprofv3 --kernel-trace: the transforms also run a DFT stage and a layout pass):
-    python scripts/timing/time_rec.py [L] [variants: e.g. 2:1,1:1,4:0  = R:pair]"""
+"""Time the ring stage of inverse / inverse_adjoint at L = 512 with one chain: recursion kernels (PXM_REC=1) against the
+ring-table GEMM (PXM_REC=0).  Run on the GPU box (best under rocprofv3 --kernel-trace: the transforms also run a DFT stage
+and a layout pass):
+    python scripts/timing/time_rec.py [L]"""
 import os
 import sys
 import time
@@ -13,7 +13,6 @@ import torch
 from pxmcmc_amd import ops
 
 L = int(sys.argv[1]) if len(sys.argv) > 1 else 512
-VARIANTS = sys.argv[2].split(",") if len(sys.argv) > 2 else ["4:1", "2:1", "1:1"]
 NCH = int(os.environ.get("NCH", "1"))
 rng = np.random.default_rng(0)
 
@@ -33,12 +32,7 @@ for spin in (2, 0):
     flm = ops.as_device(rng.normal(size=(NCH, L * L)) + 1j * rng.normal(size=(NCH, L * L)))
     f = ops.as_device(rng.normal(size=(NCH, L * (2 * L - 1))) + 1j * rng.normal(size=(NCH, L * (2 * L - 1))))
     res = {}
-    cases = [("gemm", {"PXM_REC": "0"})]
-    for v in VARIANTS:
-        R, pair = v.split(":")
-        cases.append((f"rec R={R} pair={pair}", {"PXM_REC": "1", "PXM_REC_R": R, "PXM_REC_PAIR": pair}))
-    for tag, env in cases:
-        os.environ.pop("PXM_REC_R", None)
+    for tag, env in (("gemm", {"PXM_REC": "0"}), ("rec", {"PXM_REC": "1"})):
         os.environ.update(env)
         p = ops.ShtPlan(L, spin, max_chains=NCH)
         t_inv = timeit(lambda: p.inverse(flm))

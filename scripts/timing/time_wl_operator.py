@@ -1,7 +1,7 @@
 """Launch classes of the ring stages of one forward + gradient of the fused wavelet + weak-lensing operator at L = 512, one chain
-(the four ring launches of a BASELINE configs[4] iteration), event-timed per launch.  Environment variants (PXM_REC, PXM_REC_R,
-PXM_NO_GEMM_PACK, PXM_GEMM_ORDER, ...) are read at plan creation: one process per variant.
-    PXM_NO_GEMM_PACK=1 python scripts/timing/time_wl_operator.py"""
+(the four ring launches of a BASELINE configs[4] iteration), event-timed per launch.  Environment variants (PXM_REC,
+PXM_GEMM_ORDER, ...) are read at plan creation: one process per variant.
+    PXM_GEMM_ORDER=xcd python scripts/timing/time_wl_operator.py"""
 import os
 import sys
 

@@ -239,24 +239,6 @@ def test_pair_sync_expiry_is_reported_not_silent(monkeypatch):
     assert not any(pl.status() for pl in ops.live_plans())
 
 
-def test_dataflow_launch_is_really_taken(monkeypatch):
-    """PXM_FLOW=1: `pxm_wav_flow_enabled` says whether the plan's ring-space step takes k_sht_gemm_flow (round-3 advisor:
-    the bit-identity test could have compared the two-launch path with itself), and the engine's observation points read
-    the status word that launch reports its time-outs in."""
-    import torch
-
-    from pxmcmc_amd import ops
-
-    L, B, J_min = 32, 2.0, 2
-    d = ops.as_device(np.random.default_rng(1).normal(size=L * (2 * L - 1)), torch.float64)
-    for flow in ("1", "0"):
-        monkeypatch.setenv("PXM_FLOW", flow)
-        plan = ops.WavPlan(L, B, J_min, max_chains=3)
-        plan.ring_set_data(torch.complex(d, d).contiguous())
-        assert plan.flow_enabled() == (flow == "1")
-        assert plan.status() == 0
-
-
 # ---- INTEGRATION.md section 2: the reference-side rebinding, executed ----------------------------------------------
 def test_pys2let_pyssht_shim_call_shapes_match_oracle():
     """examples/pys2let_shim.py is the module a maintainer of the reference would import in place of pys2let / pyssht
