@@ -115,6 +115,7 @@ class PxMCMC:
         self.noise_bits = int(noise_bits)
         self.noise64 = self.noise_bits == 64
         self._pairs = False
+        self._stock_prox = _is_stock_l1(prior)  # the library's own prox: the step kernels may apply it themselves
         self.nsamples = int(self.nsamples)
         for op in (getattr(forward, "transform", None), getattr(forward, "measurement", None)):
             if hasattr(op, "ensure_chains"):
@@ -133,17 +134,41 @@ class PxMCMC:
             cplx = cplx or (start.is_complex() if isinstance(start, torch.Tensor) else np.iscomplexobj(start))
         return torch.complex128 if cplx else torch.float64
 
-    def _logpi_dev(self, X, preds):
-        """per-chain (logPi, L2, prior) tensors; pxmcmc/mcmc.py:71-82 (L2 carries no factor 1/2)."""
+    def _l2_dev(self, preds):
+        """L2 = vdot(d, invcov @ d) of a [C, ndata] prediction batch -> complex128 [C] (pxmcmc/mcmc.py:78-79)"""
+        inputs = self._l2_inputs(preds)
+        if inputs is not None:
+            return ops.reduce_l2(*inputs)
+        p = ops.as_device(preds)  # full inverse covariance (forward.py:75-78): d = preds - data, vdot(-d, W(-d)) = vdot(d, W d)
+        dt = self.forward._resid_dtype(p) if hasattr(self.forward, "_resid_dtype") else p.dtype
+        d = ops.residual_grad(p.to(dt), self._l2_data_dev(dt), self.forward.invcov.ones)
+        return ops.reduce_vdot(d, self.forward.invcov.matvec(d))
+
+    def _l2_data_dev(self, dt):
+        """the data vector on the device in the residual's dtype (cached: no host copy per iteration)"""
+        cache = getattr(self, "_l2_data", None)
+        if cache is None or cache[0] is not self.forward.data or cache[1].dtype != dt:
+            src = getattr(self.forward, "data_dev", None)
+            src = ops.as_device(self.forward.data) if src is None else src
+            self._l2_data = cache = (self.forward.data, src.reshape(-1).to(dt).contiguous())
+        return cache[1]
+
+    def _l2_inputs(self, preds):
+        """(preds, data, diagonal of invcov) as the L2 reduction takes them; None with a full inverse covariance"""
+        if hasattr(self.forward.invcov, "matvec"):
+            return None
         p = ops.as_device(preds)
         dt = self.forward._resid_dtype(p) if hasattr(self.forward, "_resid_dtype") else p.dtype
-        data = ops.as_device(self.forward.data).reshape(-1).to(dt)
-        if hasattr(self.forward.invcov, "matvec"):  # full inverse covariance (forward.py:75-78): vdot(d, invcov @ d)
-            d = ops.residual_grad(p.to(dt), data, self.forward.invcov.ones)  # preds - data: vdot(-d, W(-d)) = vdot(d, W d)
-            L2 = ops.reduce_vdot(d, self.forward.invcov.matvec(d))
-        else:
-            invcov = self.forward.invcov.diag if hasattr(self.forward.invcov, "diag") else ops.as_device(self.forward.invcov.diagonal())
-            L2 = ops.reduce_l2(p.to(dt), data, invcov)
+        ic = getattr(self, "_l2_invcov", None)
+        if ic is None or ic[0] is not self.forward.invcov:
+            inv = self.forward.invcov
+            diag = inv.diag if hasattr(inv, "diag") else ops.as_device(inv.diagonal())
+            self._l2_invcov = ic = (inv, ops.as_device(diag).reshape(-1).contiguous())
+        return p.to(dt), self._l2_data_dev(dt), ic[1]
+
+    def _logpi_dev(self, X, preds):
+        """per-chain (logPi, L2, prior) tensors; pxmcmc/mcmc.py:71-82 (L2 carries no factor 1/2)."""
+        L2 = self._l2_dev(preds)
         prior = self.prior.prior(X)
         if not isinstance(prior, torch.Tensor):
             prior = torch.as_tensor(np.atleast_1d(np.asarray(prior, dtype=float)), device=L2.device)
@@ -263,51 +288,98 @@ class PxMCMC:
         w = np.stack([np.random.randn(N) + (np.random.randn(N) * 1j if self.complex else 0) for _ in range(C)])
         return ops.as_device(w)
 
-    # ---- stepping engine: static buffers, a device iteration counter, HIP-graph replay between observable events ----
-    # (the sampler supplies _engine_start -- filling XA / XB / P / cnt / cnt0 / reset / one -- and _graph_ok)
+    # ---- stepping engine: static buffers, an iteration counter, HIP-graph replay between observable events ----------
+    # (each sampler's _engine_start builds one through _engine_new + _engine_ready)
     _GRAPH_PAIRS = 4  # iterations per graph replay = 2 * _GRAPH_PAIRS (fewer, longer launches of the host)
 
-    def _engine_capture(self, eng, X, preds, i0):
-        """capture the two graphs of an engine (2 and 2 * _GRAPH_PAIRS iterations); state is (X, preds, i0) afterwards"""
-        eng["graph"] = eng["graph_long"] = None
-        if self._graph_ok():
-            try:
-                stream = torch.cuda.Stream()
-                stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(stream):
-                    eng["one"](eng["XA"], eng["XB"])  # warm-up outside capture (lazy allocations, attributes)
-                    eng["one"](eng["XB"], eng["XA"])
-                torch.cuda.current_stream().wait_stream(stream)
-                torch.cuda.synchronize()
-                eng["XA"].copy_(X)
+    def _engine_capture(self, warm, restore, bodies):
+        """Capture one HIP graph per callable of ``bodies`` -- the only place the samplers capture.  ``warm()`` runs first,
+        outside capture on a side stream (lazy allocations, attributes); ``restore()`` then puts the state back and each
+        body is captured under ``ops.capture_scope()``: a plan torn down while a capture is in progress (the garbage
+        collector may run at any point) only queues its device frees, which the library empties at the end of the scope.
+        Capture does not execute, so the state is the restored one afterwards.  Returns (graphs, None), or, when capture
+        fails, (None, repr(exc)) with the state restored: eager stepping, same results."""
+        try:
+            stream = torch.cuda.Stream()
+            stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(stream):
+                warm()
+            torch.cuda.current_stream().wait_stream(stream)
+            torch.cuda.synchronize()
+            restore()
+            graphs = []
+            for body in bodies:
+                g = torch.cuda.CUDAGraph()
+                with ops.capture_scope(), torch.cuda.graph(g):
+                    body()
+                graphs.append(g)
+            return graphs, None
+        except Exception as exc:  # capture unsupported in this environment
+            restore()
+            return None, repr(exc)
+
+    def _engine_new(self, X, preds, cnt, plan=None, pairs=False):
+        """``self._eng``, with every key it ever holds; the builder then sets ``one`` and whichever hooks it needs"""
+        self._eng = {
+            "XA": X.clone(),  # ping-pong state buffers: the state is in XA (side "A") or XB (side "B")
+            "XB": torch.empty_like(X),
+            "side": "A",  # which of XA / XB holds the current state
+            "P": preds.clone(),  # forward(state): written by every step, or formed on demand (form_preds)
+            "form_preds": None,  # form_preds(X) writes P of the state X; set when the steps do not write P
+            "P_stale": False,  # P lags the state (set by _engine_advance, cleared by _engine_state; form_preds only)
+            "one": None,  # one(src, dst): one iteration from the state in src to dst
+            "cnt": cnt,  # iteration counter read by the steps: the plan's ops.IterCounter, or a _Counter
+            "cnt0": lambda i: i,  # counter value at which the next step is iteration i
+            "reset": lambda: None,  # rebuilds plan-carried state from (XA, P) after a restore
+            "plan": plan,  # WavPlan of the fused steps (None: the steps run on the operators' own plans)
+            "pairs": pairs,  # state and preds carried pair-packed (MYULA real_pairs)
+            "ring": False,  # fused ring-space step (scalar sig_d)
+            "graph": None,  # captured graph of 2 iterations (None: eager stepping)
+            "graph_long": None,  # captured graph of 2 * _GRAPH_PAIRS iterations
+            "graph_error": None,  # repr of the exception that made capture fall back to eager stepping
+        }
+        return self._eng
+
+    def _engine_ready(self, X, preds, i0, graph_ok):
+        """point the counter at iteration i0 and, if ``graph_ok``, capture the graphs of 2 and 2 * _GRAPH_PAIRS
+        iterations; (X, preds) is the start state as the engine carries it"""
+        eng = self._eng
+        eng["cnt"].set(eng["cnt0"](i0))
+        if graph_ok:
+            XA, XB, one = eng["XA"], eng["XB"], eng["one"]
+
+            def two():
+                one(XA, XB)
+                one(XB, XA)
+
+            def restore():
+                XA.copy_(X)
                 eng["P"].copy_(preds)
                 eng["cnt"].set(eng["cnt0"](i0))
                 eng["reset"]()
-                # two graphs: 2 iterations (short advances between observable events) and 2 * _GRAPH_PAIRS
-                # iterations (long advances: fewer launches by the host).  A plan torn down while a capture is in
-                # progress (the garbage collector may run at any point) only queues its device frees: the
-                # library empties the queue at the end of the scope.
-                graphs = []
-                for pairs in (1, self._GRAPH_PAIRS):
-                    g = torch.cuda.CUDAGraph()
-                    with ops.capture_scope(), torch.cuda.graph(g):
-                        for _ in range(pairs):
-                            eng["one"](eng["XA"], eng["XB"])
-                            eng["one"](eng["XB"], eng["XA"])
-                    graphs.append(g)
-                # capture does not execute: state is still (X, preds, i0)
-                eng["graph"], eng["graph_long"] = graphs
-            except Exception as exc:  # capture unsupported in this environment: eager stepping, same results
-                eng["graph"] = eng["graph_long"] = None
-                eng["graph_error"] = repr(exc)
-                eng["XA"].copy_(X)
-                eng["P"].copy_(preds)
-                eng["cnt"].set(eng["cnt0"](i0))
-                eng["reset"]()
+
+            bodies = [lambda n=n: [two() for _ in range(n)] for n in (1, self._GRAPH_PAIRS)]
+            graphs, eng["graph_error"] = self._engine_capture(two, restore, bodies)
+            eng["graph"], eng["graph_long"] = graphs or (None, None)
+        return eng
+
+    def _engine_start_generic(self, X, preds, i0, step, lazy, graph_ok):
+        """The engine of the steps that run on the operators' own plans: ``step(eng, src, dst)`` per iteration on static
+        buffers, the noise kernels reading the iteration number from a device counter (``eng["cnt"].t``).  With ``lazy``
+        the steps do not write P: forward(X) is formed where the state is observed."""
+        X = ops.as_device(X).contiguous()
+        preds = ops.as_device(preds)
+        eng = self._engine_new(X, preds, _Counter(i0))
+        eng["one"] = lambda src, dst: step(eng, src, dst)
+        if lazy:
+            eng["form_preds"] = lambda X: eng["P"].copy_(ops.as_device(self.forward.forward(X)))
+        return self._engine_ready(X, preds, i0, graph_ok)
 
     def _engine_advance(self, k):
         """advance the engine's state by k iterations (graph replays of 2 * _GRAPH_PAIRS + eager remainder)"""
         eng = self._eng
+        if k > 0 and eng["form_preds"] is not None:
+            eng["P_stale"] = True
         if eng["side"] == "B" and k > 0:  # realign so that replays start from XA
             eng["one"](eng["XB"], eng["XA"])
             eng["side"] = "A"
@@ -316,11 +388,9 @@ class PxMCMC:
             per = 2 * self._GRAPH_PAIRS
             while k >= per:
                 eng["graph_long"].replay()
-                eng["P_valid"] = not (eng["ring"] or eng.get("lazy"))
                 k -= per
             while k >= 2:
                 eng["graph"].replay()
-                eng["P_valid"] = not (eng["ring"] or eng.get("lazy"))
                 k -= 2
         while k >= 2:
             eng["one"](eng["XA"], eng["XB"])
@@ -333,16 +403,13 @@ class PxMCMC:
     def _engine_state(self):
         """(X, preds) of the current state as [C, .] arrays (pair-packed engines unpack here: observation only)"""
         eng = self._eng
-        if eng["ring"] and not eng["P_valid"]:  # forward(X) of the carried rings, on demand
-            eng["plan"].ring_preds(eng["P"].shape[0], out=eng["P"])
-            eng["P_valid"] = True
-        elif eng.get("lazy") and not eng["P_valid"]:  # an engine whose steps do not form forward(X'): on demand
-            eng["P"].copy_(ops.as_device(self.forward.forward(eng["XA"] if eng["side"] == "A" else eng["XB"])))
-            eng["P_valid"] = True
-        # observation point: the host is about to read the state -- an expired device wait since the last one raises
-        if eng.get("plan") is not None:
-            eng["plan"].raise_on_fault()
         X = eng["XA"] if eng["side"] == "A" else eng["XB"]
+        if eng["P_stale"]:  # preds on demand: forward(X) of the current state
+            eng["form_preds"](X)
+            eng["P_stale"] = False
+        # observation point: the host is about to read the state -- an expired device wait since the last one raises
+        if eng["plan"] is not None:
+            eng["plan"].raise_on_fault()
         if eng["pairs"]:
             return self._unpack(X), self._unpack(eng["P"])
         return X, eng["P"]
@@ -351,10 +418,10 @@ class PxMCMC:
         """unregister the iteration counter and drop the engine's buffers, graph and closures (the closures
         reference the sampler: without this the plan would only be released by a later garbage collection)"""
         eng = getattr(self, "_eng", None)
-        if eng is not None and eng.get("cnt") is not None:
+        if eng is not None and eng["cnt"] is not None:
             eng["cnt"].close()
             eng["graph"] = eng["graph"] is not None  # keep the flags (ring, pairs, graph) for inspection
-            for k in ("one", "XA", "XB", "P", "plan", "cnt", "cnt0", "graph_long", "reset"):
+            for k in ("one", "XA", "XB", "P", "form_preds", "plan", "cnt", "cnt0", "graph_long", "reset"):
                 eng[k] = None
 
     def _run_engine(self, X_curr, curr_preds):
@@ -366,7 +433,7 @@ class PxMCMC:
         self._engine_start(X_curr, curr_preds, 0)
         try:
             i = 0  # iterations done
-            j = 0
+            j = 0  # saved samples (excludes burn-in and thinned samples)
             while j < self.nsamples:
                 # next iteration index (0-based) at which something observable happens
                 if i < nburn:
@@ -382,7 +449,7 @@ class PxMCMC:
                 X_curr, curr_preds = self._engine_state()
                 if i >= nburn:
                     if ngap == 0 or (i - nburn) % ngap == 0:
-                        if self._eng.get("plan") is None:  # generic engine: the operators' own plans
+                        if self._eng["plan"] is None:  # steps on the operators' own plans: poll those
                             self._check_device_status()
                         logPi, L2, prior = self._logpi_dev(X_curr, curr_preds)
                         self._tracking(j, X_curr, curr_preds, logPi, L2, prior)
@@ -397,22 +464,31 @@ class PxMCMC:
             self._check_device_status()
             self.X_curr, self.curr_preds, self.niter = X_curr.clone(), curr_preds.clone(), i
             self.used_graph = self._eng["graph"] is not None
-            self.graph_error = self._eng.get("graph_error")
+            self.graph_error = self._eng["graph_error"]
         finally:
             self._engine_stop()
         print("\nDONE")
 
-class _DevCounter:
-    """caller-owned device iteration counter of the generic stepping engine (the fused engines use the plan's)"""
 
-    def __init__(self, start):
-        self.t = torch.full((1,), int(start), dtype=torch.int64, device=ops.device())
+class _Counter:
+    """iteration counter of the engines that step on the operators' own plans (the fused engines use the plan's
+    ops.IterCounter): a device int64 ``t`` that the noise kernels read when they run (graph replay), or, with
+    ``host=True``, a host int ``i`` that the eager-only engine passes to each call"""
+
+    def __init__(self, start, host=False):
+        self.i = int(start)
+        self.t = None if host else torch.full((1,), self.i, dtype=torch.int64, device=ops.device())
 
     def set(self, v):
-        self.t.fill_(int(v))
+        self.i = int(v)
+        if self.t is not None:
+            self.t.fill_(self.i)
 
     def add(self, inc=1):
-        ops.counter_add(self.t, inc)
+        if self.t is None:
+            self.i += inc
+        else:
+            ops.counter_add(self.t, inc)
 
     def close(self):
         pass
@@ -423,6 +499,7 @@ class MYULA(PxMCMC):
 
     def __init__(self, forward, prox, mcmcparams=PxMCMCParams(), **kwargs):
         super().__init__(forward, prox, mcmcparams, **kwargs)
+        self._own_step = type(self).chain_step is not MYULA.chain_step  # a subclass's chain_step: called as it is
 
     def _fusable_wavelet(self):
         f = self.forward
@@ -434,8 +511,8 @@ class MYULA(PxMCMC):
             and f.transform.dirs == 1  # (the fused steps are WavPlan's: axisymmetric only)
             and isinstance(getattr(f, "measurement", None), Identity)
             and f.measurement.ndata == f.measurement.npix
-            and _is_stock_l1(self.prior)
-            and type(self).chain_step is MYULA.chain_step
+            and self._stock_prox
+            and not self._own_step
         )
 
     def _advance(self, X, preds, i, delta=None):
@@ -459,13 +536,17 @@ class MYULA(PxMCMC):
         if self._fused_prox:
             return ops.myula_step(X, gradg, self.prior.T_dev, delta, self.lmda, **kw)
         proxf = ops.as_device(self.prior.proxf(X), X.dtype)
-        if type(self).chain_step is not MYULA.chain_step:
+        if self._own_step:
             return ops.as_device(self.chain_step(X, proxf, gradg), X.dtype)
         return ops.chain_step(X, proxf, gradg, delta, self.lmda, **kw)
 
     def _prepare(self):
         self._fused_wav = self._fusable_wavelet() and isinstance(self.delta, float)
-        self._fused_prox = _is_stock_l1(self.prior) and type(self).chain_step is MYULA.chain_step
+        self._fused_prox = self._stock_prox and not self._own_step
+        # the calls of the reference's loop, one by one: host noise, a tensor delta or a subclass's chain_step (and,
+        # without graph replay, the operators that have no fused step)
+        self._eager_only = self.rng == "numpy" or not (
+            self._fused_wav or (self.use_graph and isinstance(self.delta, float) and not self._own_step))
         self._it = 0
         self._pairs = False
 
@@ -510,86 +591,22 @@ class MYULA(PxMCMC):
             w[c] = np.random.randn(N)
         return ops.as_device(w)
 
-    # ---- HIP-graph engine for the fused wavelet path ----------------------------------------------
-    def _graph_ok(self):
-        return (self._fused_wav or self._generic_engine_ok()) and self.rng == "philox" and self.use_graph
-
-    def _generic_engine_ok(self):
-        """Operators without a fused kernel path (PathIntegralOperator, the analysis setting, user plugins ...) step
-        through the same engine: calc_gradg / proxf / chain_step / forward on static buffers with the device Philox
-        counter, replayed from a HIP graph when the operators can be captured (eager stepping otherwise)."""
-        return (not self._fused_wav and self.rng == "philox" and self.use_graph and isinstance(self.delta, float)
-                and type(self).chain_step is MYULA.chain_step)
-
+    # ---- stepping engines ---------------------------------------------------------------------------------------
     def _engine_start(self, X, preds, i0):
-        """Static ping-pong state (XA, XB, P), a device iteration counter and a captured graph of 2 * _GRAPH_PAIRS
-        iterations."""
+        """Static ping-pong state (XA, XB, P), an iteration counter and, with the Philox stream, captured graphs of 2 and
+        2 * _GRAPH_PAIRS iterations"""
         self._engine_stop()  # an engine left over from an interrupted run gives its counter / buffers back first
+        if self._eager_only:
+            return self._engine_start_eager(X, preds, i0)
+        if self._fused_wav:
+            return self._engine_start_fused(X, preds, i0)
         f = self.forward
-        if not self._fused_wav:
-            return self._engine_start_generic(X, preds, i0)
-        plan = f.transform._plan
-        data = f.data_dev_c128
-        self._eng = eng = {}
-        eng["pairs"] = self._pairs
-        if self._pairs:  # two real chains per complex slot: X, preds are carried pair-packed
-            plan, data = self._pair_plan, self._pair_data
-            X, preds = self._pack(X), self._pack(preds)
-        eng["plan"] = plan
-        eng["XA"], eng["XB"], eng["P"] = X.clone(), torch.empty_like(X), preds.clone()
-        eng["cnt"] = ops.IterCounter(plan, i0)  # per-plan device counter: the steps below read it at execution time
-        eng["side"] = "A"  # which buffer holds the current state
-        args = (data, f.invcov.diag, self.prior.T_dev, float(self.delta), self.lmda)
-        # params.complex: randn + 1j randn (pxmcmc/mcmc.py:193-195) -> PXM_MODE_CPLX_NOISE in the fused epilogues
-        kw = dict(noise_complex=bool(self.complex), seed=self.seed, chain0=self.chain_offset, it=0, pairs=self._pairs,
-                  noise64=self.noise64)
-        # Uniform inverse covariance (scalar sig_d): the image-space residual is applied on the rings and the
-        # L-level iDFT/DFT pair between forward() and calc_gradg() drops out (pxm_wav_ring_step); preds is
-        # then materialised only when it is observed.
-        d = f.invcov.diag
-        eng["ring"] = bool(self.ring_shortcut and d.numel() > 0 and bool((d == d[0]).all()))
-        eng["P_valid"] = True
-        eng["cnt0"] = lambda i: i  # counter value that makes the next step use Philox iteration i
-        if eng["ring"]:
-            w = complex(d[0].item())
-            plan.ring_set_data(data)
-            plan.ring_init(eng["XA"])
-            eng["reset"] = lambda: plan.ring_init(eng["XA"])  # plan-carried state of (XA, P)
-            eng["cnt0"] = lambda i: i - 1  # ring_step increments the counter before using it
-            eng["cnt"].set(eng["cnt0"](i0))
-
-            def one(src, dst):
-                # (ring_step advances the registered iteration counter itself, before using it)
-                plan.ring_step(src, w, self.prior.T_dev, float(self.delta), self.lmda, out=dst, **kw)
-                eng["P_valid"] = False
-        else:
-            plan.image_init(eng["P"], data, f.invcov.diag)  # residual rings of the start state, carried by the plan
-            eng["reset"] = lambda: plan.image_init(eng["P"], data, f.invcov.diag)
-
-            def one(src, dst):
-                # calc_gradg + proxf + chain_step + forward of the new state (preds written in place)
-                plan.image_step(src, *args, out=dst, preds_out=eng["P"], **kw)
-                eng["cnt"].add(1)
-
-        eng["one"] = one
-        self._engine_capture(eng, X, preds, i0)
-        return eng
-
-    def _engine_start_generic(self, X, preds, i0):
-        """The engine for operators without a fused path: one iteration = the reference's four calls
-        (pxmcmc/mcmc.py:158-163) on static buffers; the noise kernels read the iteration number from a device counter."""
-        f = self.forward
-        self._eng = eng = {"pairs": False, "plan": None, "ring": False, "P_valid": True, "side": "A", "generic": True}
-        X = ops.as_device(X).contiguous()
-        eng["XA"], eng["XB"], eng["P"] = X.clone(), torch.empty_like(X), ops.as_device(preds).clone()
-        eng["cnt"] = _DevCounter(i0)
-        eng["cnt0"] = lambda i: i
-        eng["reset"] = lambda: None
-        kw = dict(noise_complex=bool(self.complex), seed=self.seed, chain0=self.chain_offset, it=0, iter_dev=eng["cnt"].t,
-                  noise64=self.noise64)
         delta, lmda = float(self.delta), self.lmda
 
-        def one(src, dst):
+        def step(eng, src, dst):
+            # the reference's four calls (pxmcmc/mcmc.py:158-163) on the operators' own plans
+            kw = dict(noise_complex=bool(self.complex), seed=self.seed, chain0=self.chain_offset, it=0,
+                      iter_dev=eng["cnt"].t, noise64=self.noise64)
             gradg = ops.as_device(f.calc_gradg(eng["P"]), src.dtype)
             if self._fused_prox:
                 ops.myula_step(src, gradg, self.prior.T_dev, delta, lmda, out=dst, **kw)
@@ -599,51 +616,69 @@ class MYULA(PxMCMC):
             eng["P"].copy_(ops.as_device(f.forward(dst)))
             eng["cnt"].add(1)
 
+        return self._engine_start_generic(X, preds, i0, step, lazy=False, graph_ok=True)
+
+    def _engine_start_fused(self, X, preds, i0):
+        """The fused wavelet steps of WavPlan, on the plan's registered iteration counter"""
+        f = self.forward
+        plan, data = f.transform._plan, f.data_dev_c128
+        if self._pairs:  # two real chains per complex slot: X, preds are carried pair-packed
+            plan, data = self._pair_plan, self._pair_data
+            X, preds = self._pack(X), self._pack(preds)
+        # per-plan device counter: the steps below read it at execution time
+        eng = self._engine_new(X, preds, ops.IterCounter(plan, i0), plan=plan, pairs=self._pairs)
+        d, T, delta, lmda = f.invcov.diag, self.prior.T_dev, float(self.delta), self.lmda
+        # params.complex: randn + 1j randn (pxmcmc/mcmc.py:193-195) -> PXM_MODE_CPLX_NOISE in the fused epilogues
+        kw = dict(noise_complex=bool(self.complex), seed=self.seed, chain0=self.chain_offset, it=0, pairs=self._pairs,
+                  noise64=self.noise64)
+        # Uniform inverse covariance (scalar sig_d): the image-space residual is applied on the rings and the
+        # L-level iDFT/DFT pair between forward() and calc_gradg() drops out (pxm_wav_ring_step); preds is
+        # then formed only when it is observed.
+        eng["ring"] = bool(self.ring_shortcut and d.numel() > 0 and bool((d == d[0]).all()))
+        if eng["ring"]:
+            w = complex(d[0].item())
+            plan.ring_set_data(data)
+            eng["reset"] = lambda: plan.ring_init(eng["XA"])  # plan-carried state of (XA, P)
+            eng["cnt0"] = lambda i: i - 1  # ring_step advances the counter itself, before using it
+            eng["form_preds"] = lambda X: plan.ring_preds(eng["P"].shape[0], out=eng["P"])  # of the carried rings
+            eng["one"] = lambda src, dst: plan.ring_step(src, w, T, delta, lmda, out=dst, **kw)
+        else:
+            eng["reset"] = lambda: plan.image_init(eng["P"], data, d)  # residual rings of the state, carried by the plan
+
+            def one(src, dst):
+                # calc_gradg + proxf + chain_step + forward of the new state (preds written in place)
+                plan.image_step(src, data, d, T, delta, lmda, out=dst, preds_out=eng["P"], **kw)
+                eng["cnt"].add(1)
+
+            eng["one"] = one
+        eng["reset"]()
+        return self._engine_ready(X, preds, i0, self.use_graph)
+
+    def _engine_start_eager(self, X, preds, i0):
+        """The engine of _eager_only: the calls of the reference's loop, iteration by iteration -- _advance with the
+        host iteration number (host noise in the reference's draw order), then forward (the synthesis of the
+        pair-packed state)"""
+        if self._pairs:
+            X, preds = self._pack(X), self._pack(preds)
+        eng = self._engine_new(X, preds, _Counter(i0, host=True), pairs=self._pairs)
+        forward = self._pair_plan.synthesis if self._pairs else (lambda X: ops.as_device(self.forward.forward(X)))
+
+        def one(src, dst):
+            X_prop = self._advance(src, eng["P"], eng["cnt"].i)
+            dst.copy_(X_prop)
+            eng["P"].copy_(forward(X_prop))
+            eng["cnt"].add(1)
+
         eng["one"] = one
-        self._engine_capture(eng, X, preds, i0)
-        return eng
+        return self._engine_ready(X, preds, i0, graph_ok=False)
 
     def run(self, start_point=None):
         """Run the algorithm (pxmcmc/mcmc.py:150-183)."""
         self._prepare()
-        i = 0  # total samples
-        j = 0  # saved samples (excludes burn-in and thinned samples)
         X_curr, curr_preds = self._initial_sample(start_point)
         if self._pairs_ok(X_curr):
             self._pairs_start()
-        if self.rng == "philox" and (self._fused_wav or self._generic_engine_ok()):
-            return self._run_engine(X_curr, curr_preds)
-        if self._pairs:
-            X_curr, curr_preds = self._pack(X_curr), self._pack(curr_preds)
-        while j < self.nsamples:
-            X_prop = self._advance(X_curr, curr_preds, i)
-            if self._pairs:  # identity measurement: forward = synthesis, on the pair-packed state
-                prop_preds = self._pair_plan.synthesis(X_prop)
-            else:
-                prop_preds = ops.as_device(self.forward.forward(X_prop))
-
-            X_curr = X_prop
-            curr_preds = prop_preds
-
-            if i >= self.nburn:
-                if self.ngap == 0 or (i - self.nburn) % self.ngap == 0:
-                    Xs, Ps = (self._unpack(X_curr), self._unpack(curr_preds)) if self._pairs else (X_curr, curr_preds)
-                    self._check_device_status()
-                    logPi, L2, prior = self._logpi_dev(Xs, Ps)
-                    self._tracking(j, Xs, Ps, logPi, L2, prior)
-                    j += 1
-                if self.verbosity > 0 and (i + 1) % self.verbosity == 0:
-                    first = (lambda a: a[j - 1] if self.nchains == 1 else a[0, j - 1])
-                    self._print_progress(j - 1, first(self.logPi), L2=first(self.L2s), prior=first(self.priors))
-            else:
-                if self.verbosity > 0 and (i + 1) % self.verbosity == 0:
-                    print("Burning in...")
-            i += 1
-        if self._pairs:
-            X_curr, curr_preds = self._unpack(X_curr), self._unpack(curr_preds)
-        self._check_device_status()
-        self.X_curr, self.curr_preds, self.niter = X_curr, curr_preds, i
-        print("\nDONE")
+        return self._run_engine(X_curr, curr_preds)
 
     def chain_step(self, X, proxf, gradg):
         """
@@ -692,39 +727,6 @@ class PxMALA(MYULA):
         self.transitions_trace = []
         self.proposals_trace = []
 
-    def _l2_dev(self, preds):
-        """L2 = vdot(d, invcov @ d) of a [C, ndata] prediction batch -> complex128 [C] (pxmcmc/mcmc.py:78-79)"""
-        inputs = self._l2_inputs(preds)
-        if inputs is not None:
-            return ops.reduce_l2(*inputs)
-        p = ops.as_device(preds)  # full inverse covariance: d = data - preds, then vdot(d, invcov @ d)
-        dt = self.forward._resid_dtype(p) if hasattr(self.forward, "_resid_dtype") else p.dtype
-        data = self._l2_data_dev(dt)
-        d = ops.residual_grad(p.to(dt), data, self.forward.invcov.ones)
-        return ops.reduce_vdot(d, self.forward.invcov.matvec(d))
-
-    def _l2_data_dev(self, dt):
-        """the data vector on the device in the residual's dtype (cached: no host copy per iteration)"""
-        cache = getattr(self, "_l2_data", None)
-        if cache is None or cache[0] is not self.forward.data or cache[1].dtype != dt:
-            src = getattr(self.forward, "data_dev", None)
-            src = ops.as_device(self.forward.data) if src is None else src
-            self._l2_data = cache = (self.forward.data, src.reshape(-1).to(dt).contiguous())
-        return cache[1]
-
-    def _l2_inputs(self, preds):
-        """(preds, data, diagonal of invcov) as the L2 reduction takes them; None with a full inverse covariance"""
-        if hasattr(self.forward.invcov, "matvec"):
-            return None
-        p = ops.as_device(preds)
-        dt = self.forward._resid_dtype(p) if hasattr(self.forward, "_resid_dtype") else p.dtype
-        ic = getattr(self, "_l2_invcov", None)
-        if ic is None or ic[0] is not self.forward.invcov:
-            inv = self.forward.invcov
-            diag = inv.diag if hasattr(inv, "diag") else ops.as_device(inv.diagonal())
-            self._l2_invcov = ic = (inv, ops.as_device(diag).reshape(-1).contiguous())
-        return p.to(dt), self._l2_data_dev(dt), ic[1]
-
     def run(self, start_point=None):
         """Run the algorithm (pxmcmc/mcmc.py:218-275); every chain carries its own delta and accept flag.
 
@@ -754,7 +756,7 @@ class PxMALA(MYULA):
         logpiXc, L2Xc = logpiXc.to(torch.complex128).contiguous(), L2Xc.to(torch.complex128).contiguous()
         priorXc = priorXc.to(torch.float64).contiguous()
         # stock prior (library L1 / S2 soft threshold + weighted L1 norm): the fused proposal kernel applies
-        stock = _is_stock_l1(self.prior) and type(self.prior).prior is L1.prior and type(self).chain_step is MYULA.chain_step
+        stock = self._fused_prox and type(self.prior).prior is L1.prior
         T_dev = self.prior.T_dev if stock else None
         w_prior = getattr(self.prior, "_weights_dev", None) if stock else None
         X_prop, proxf_prop = torch.empty_like(X_curr), torch.empty_like(X_curr)
@@ -787,7 +789,7 @@ class PxMALA(MYULA):
                                    scratch=prop_scratch if fused_tail else None, **kw)
                 Xp, pxp, ltc, prp = X_prop, proxf_prop, lt_cp, prior_p
             else:  # user-supplied prior / chain_step: the reference's own sequence of calls (mcmc.py:231-242)
-                if type(self).chain_step is MYULA.chain_step:
+                if not self._own_step:
                     Xp = ops.chain_step(X_curr, proxf_curr, gradg_curr, delta_dev, self.lmda, noise=noise,
                                         noise_complex=bool(self.complex), noise64=self.noise64, **kw)
                 else:
@@ -825,29 +827,22 @@ class PxMALA(MYULA):
         graph = None
         self.graph_error = None
         if self.use_graph and not host_rng and stock:
-            snap = [t.clone() for t in (X_curr, curr_preds, gradg_curr, proxf_curr, logpiXc, L2Xc, priorXc, delta_dev)]
-            try:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    iteration(0, it_dev)  # warm-up outside capture (lazy allocations, attributes)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                for t, s_ in zip((X_curr, curr_preds, gradg_curr, proxf_curr, logpiXc, L2Xc, priorXc, delta_dev), snap):
+            state = (X_curr, curr_preds, gradg_curr, proxf_curr, logpiXc, L2Xc, priorXc, delta_dev)
+            snap = [t.clone() for t in state]
+
+            def restore():
+                for t, s_ in zip(state, snap):
                     t.copy_(s_)
-                g = torch.cuda.CUDAGraph()
-                with ops.capture_scope(), torch.cuda.graph(g):
-                    if fused_tail:
-                        iteration(0, it_dev, bump=it_dev)  # (the counter advances inside pxm_pxmala_finish)
-                    else:
-                        iteration(0, it_dev)
-                        ops.counter_add(it_dev, 1)
-                graph = g
-            except Exception as exc:
-                graph = None
-                self.graph_error = repr(exc)
-                for t, s_ in zip((X_curr, curr_preds, gradg_curr, proxf_curr, logpiXc, L2Xc, priorXc, delta_dev), snap):
-                    t.copy_(s_)
+
+            def body():
+                if fused_tail:
+                    iteration(0, it_dev, bump=it_dev)  # (the counter advances inside pxm_pxmala_finish)
+                else:
+                    iteration(0, it_dev)
+                    ops.counter_add(it_dev, 1)
+
+            graphs, self.graph_error = self._engine_capture(lambda: iteration(0, it_dev), restore, [body])
+            graph = graphs[0] if graphs else None
             it_dev.zero_()
         self.used_graph = graph is not None
 
@@ -986,6 +981,7 @@ class SKROCK(PxMCMC):
         self.s = int(s)
         self.eta = 0.05
         self.omega_0, self.omega_1, self.mus, self.nus, self.ks = skrock_coefficients(self.s, self.eta)
+        self._own_step = type(self).chain_step is not SKROCK.chain_step  # a subclass's chain_step: called as it is
         self._it = 0
 
     # ---- one iteration on device buffers ----------------------------------------------------------------
@@ -1004,8 +1000,7 @@ class SKROCK(PxMCMC):
         """X' = K_s of one iteration into ``out`` (Y, KA, KB: scratch of X's shape; none of them aliases X or out)"""
         f = self.forward
         coefs = self._stage_coefs()
-        fused = _is_stock_l1(self.prior)
-        T = self.prior.T_dev if fused else None
+        T = self.prior.T_dev if self._stock_prox else None
         kw = dict(noise=noise, noise_complex=bool(self.complex), seed=self.seed, chain0=self.chain_offset, it=it,
                   iter_dev=iter_dev, noise64=self.noise64)
         ops.skrock_stage(X, *coefs[0], out=Y, **kw)  # Y = X + nu_1 sqrt(2 delta) Z
@@ -1015,7 +1010,7 @@ class SKROCK(PxMCMC):
             U = Y if j == 1 else bufs[(s - j + 1) % 3]
             V = X if j <= 2 else bufs[(s - j + 2) % 3]
             g = ops.as_device(f.calc_gradg(ops.as_device(f.forward(U))), U.dtype)
-            px = None if fused else ops.as_device(self.prior.proxf(U), U.dtype)
+            px = None if self._stock_prox else ops.as_device(self.prior.proxf(U), U.dtype)
             # (stage 1 regenerates stage 0's Z from the same counters; stages j >= 2 have r = 0: no noise term)
             ops.skrock_stage(U, *coefs[j], T=T, proxf=px, gradg=g, V=V, out=bufs[(s - j) % 3], **kw)
         return out
@@ -1038,36 +1033,24 @@ class SKROCK(PxMCMC):
         return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
 
     # ---- stepping engine ------------------------------------------------------------------------------------
-    def _graph_ok(self):
-        return self.rng == "philox" and self.use_graph and type(self).chain_step is SKROCK.chain_step
-
     def _engine_start(self, X, preds, i0):
         """static state (XA, XB, P; Y and two rotating K buffers), a device iteration counter and, with the Philox stream,
         captured graphs of 2 and 2 * _GRAPH_PAIRS iterations.  preds (P) is formed on demand only."""
         self._engine_stop()
         X = ops.as_device(X).contiguous()
-        self._eng = eng = {"pairs": False, "plan": None, "ring": False, "lazy": True, "P_valid": True, "side": "A",
-                           "generic": True}
-        eng["XA"], eng["XB"], eng["P"] = X.clone(), torch.empty_like(X), ops.as_device(preds).clone()
-        eng["cnt"] = _DevCounter(i0)
-        eng["cnt0"] = lambda i: i
-        eng["reset"] = lambda: None
         Y, KA, KB = (torch.empty_like(X) for _ in range(3))
         numpy_rng = self.rng == "numpy"
-        own_step = type(self).chain_step is not SKROCK.chain_step
 
-        def one(src, dst):
-            if own_step:  # a subclass's chain_step: eager, through it
+        def step(eng, src, dst):
+            if self._own_step:  # a subclass's chain_step: eager, through it
                 dst.copy_(ops.as_device(self.chain_step(src), dst.dtype))
             else:
                 noise = self._host_noise(src) if numpy_rng else None
                 self._iterate(src, dst, Y, KA, KB, noise, 0, eng["cnt"].t)
                 eng["cnt"].add(1)
-            eng["P_valid"] = False
 
-        eng["one"] = one
-        self._engine_capture(eng, X, preds, i0)
-        return eng
+        graph_ok = not numpy_rng and self.use_graph and not self._own_step
+        return self._engine_start_generic(X, preds, i0, step, lazy=True, graph_ok=graph_ok)
 
     def run(self, start_point=None):
         """Run the algorithm (pxmcmc/mcmc.py:308-336): the reference's schedule and tracking arrays; iterations between

@@ -225,7 +225,7 @@ def test_myula_directional_graph_equals_eager_and_fused_gate():
         s = MYULA(op, reg, p, nchains=C, seed=4, use_graph=use_graph)
         _quiet(s.run, start_point=X0)
         assert not s._fused_wav
-        # (use_graph=False: the reference's eager loop, which does not go through the engine)
+        # (use_graph=False: the engine's eager-only form, the reference's calls iteration by iteration)
         assert getattr(s, "used_graph", False) == use_graph, getattr(s, "graph_error", None)
         runs.append(s)
     np.testing.assert_array_equal(runs[0].chain, runs[1].chain)
