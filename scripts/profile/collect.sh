@@ -15,7 +15,7 @@ shift 2
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 [ -f "$ROOT/bench.py" ] || { echo "collect.sh: $ROOT/bench.py not found (run from the repo root or set GRAFT_REPO_ROOT)" >&2; exit 2; }
 OUT=$ROOT/gpurun_out/$TAG
-BENCH_FLAGS="--no-cpu-baseline --no-layout-compare --no-config-legs --no-noise-leg"
+BENCH_FLAGS="--full --no-cpu-baseline --no-layout-compare --no-config-legs --no-noise-leg"
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 case $WHAT in

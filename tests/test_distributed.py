@@ -303,7 +303,7 @@ def test_bench_gpus2_self_launch_rehearsal(nranks):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--steps", "6", "--warmup", "2", "--ramp", "10",
-           "--repeats", "3", "--config5-cap", "400"]
+           "--repeats", "3", "--config5-cap", "400", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

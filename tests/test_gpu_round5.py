@@ -29,8 +29,8 @@ def test_bench_side_leg_failure_is_loud():
 
         bench.config2_leg = boom
         bench.config5_leg = lambda pmc=None: {{"finite": True}}
-        sys.argv = ["bench.py", "--steps", "4", "--warmup", "1", "--ramp", "0", "--no-cpu-baseline", "--no-layout-compare",
-                    "--no-noise-leg"]
+        sys.argv = ["bench.py", "--steps", "4", "--warmup", "1", "--ramp", "0", "--full", "--no-cpu-baseline",
+                    "--no-layout-compare", "--no-noise-leg"]
         bench.main()
         """
     )
@@ -42,6 +42,30 @@ def test_bench_side_leg_failure_is_loud():
     assert any("leg exploded" in m for m in out["leg_failures"])
     assert res.returncode == 3, res.returncode
     assert "leg exploded" in res.stderr
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py` without --full: the headline fields, the --dump-outputs files of the timed path, and none of the
+    side legs' fields."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--ramp", "0", "--repeats", "3",
+           "--dump-outputs", str(tmp_path / "dump")]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "MYULA samples/sec at L=256 synthesis" and out["unit"] == "samples/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f64" and out["steps"] == 4 and out["warmup"] == 1
+    assert sorted(out["repeats"]["ms_per_step"])[1] == out["ms_per_step"]
+    assert abs(out["value"] - 16 * 1e3 / out["ms_per_step"]) <= 1e-9 * out["value"]
+    for key in ("cpu_baseline", "parity", "roofline", "dft_kernel", "noise_leg", "value_f32_noise", "configs", "barrier_us",
+                "legs_ok"):
+        assert key not in out, key
+    assert "samples_per_s_one_gpu_reference_layout" not in out["config"]
+    for name, shape in out["dump_outputs"]["shapes"].items():
+        a = np.load(tmp_path / "dump" / f"{name}.npy")
+        assert list(a.shape) == shape and a.dtype == np.float64 and np.isfinite(a).all()
+    assert out["dump_outputs"]["shapes"]["X"] == [16, 305060]
 
 
 def test_live_plan_registry_sees_plans_owned_by_anyone():

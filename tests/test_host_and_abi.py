@@ -288,6 +288,34 @@ def test_bench_dump_outputs_files_dtype_and_budget(tmp_path):
     assert all(np.isin(xs[r], x[r]).all() for r in range(4))  # a sample of the written rows, not new numbers
 
 
+def test_bench_side_legs_run_with_full_only(monkeypatch):
+    """A plain `bench.py` run goes from its arguments to the GPU without starting a side leg (CPU legs, rocprofv3
+    child passes); `--full` starts them first.  The GPU check that follows ends both runs here."""
+    import importlib.util
+    import sys
+
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_mod_f", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    def side_leg(*args, **kw):
+        raise AssertionError("side leg started")
+
+    for name in ("cpu_legs", "live_traffic", "pmc_passes"):
+        monkeypatch.setattr(bench, name, side_leg)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    with pytest.raises(SystemExit, match="needs an MI355X"):
+        bench.main()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--full"])
+    with pytest.raises(AssertionError, match="side leg started"):
+        bench.main()
+
+
 def test_pfa511_tables_match_the_numpy_model():
     """The host tables of the exact-length phi-DFT unit (csrc/dft_pfa.h: 511 = 7 x 73, Good-Thomas + Rader over Z_8 x Z_9) against
     the lane / register-exact numpy model scripts/dev/proto_pfa511.py, which is itself checked against numpy.fft here: gather
