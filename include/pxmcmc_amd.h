@@ -41,7 +41,7 @@ typedef void* pxm_stream_t; /* hipStream_t */
 int pxm_version(void);
 /* Precision of the Box-Muller step of the Philox noise stream (pxmcmc/mcmc.py:193-195 draws fp64 randn).  Every
  * entry point that can draw noise takes the flag PXM_NOISE_F64, OR-ed into its `mode` (pxm_wav_*_step), `noise_complex`
- * (pxm_myula_step*, pxm_chain_step*, pxm_pxmala_propose) or `dtype` (pxm_randn) argument:
+ * (pxm_myula_step, pxm_chain_step, pxm_skrock_stage, pxm_pxmala_propose) or `dtype` (pxm_randn) argument:
  *   absent   Box-Muller on the f32 transcendental units (v_log_f32 / v_sin_f32 / v_cos_f32 with the exact fp64 exponent:
  *            deviates ~1e-6 relative, tail to 8.5 sigma) -- the default, pxm_noise_bits() == 32;
  *   present  log / sqrt / sincos evaluated in double precision (branch-free polynomials, csrc/philox.h): deviates equal
@@ -286,44 +286,32 @@ int pxm_soft(const void* X, const double* T, double T_scalar, void* out, int64_t
 int pxm_residual_grad(const void* preds, const void* data, const void* invcov, int invcov_complex,
                       void* out, int64_t n, int C, int dtype, pxm_stream_t stream);
 /* MYULA.chain_step fused with L1 prox (pxmcmc/mcmc.py:185-201 + prior.py:49-50).
- * delta_dev: per-chain step sizes [C] on the device or NULL -> delta. */
+ * delta_dev: per-chain step sizes [C] on the device or NULL -> delta.
+ * iter_dev: caller-owned device iteration counter or NULL: the Philox iteration is iter + *iter_dev, read when the kernel
+ * runs, so a HIP graph of an iteration replays with fresh noise once the captured sequence ends with pxm_counter_add
+ * (MYULA's generic-operator stepping engine, pxmcmc/mcmc.py:157-164). */
 int pxm_myula_step(const void* X, const void* gradg, const double* T, double T_scalar,
                    const double* delta_dev, double delta, double lmda, const void* noise,
-                   int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter, void* X_out,
-                   int64_t n, int C, int dtype, pxm_stream_t stream);
-/* chain_step with proxf given (PxMALA keeps proxf of the current state, mcmc.py:231) */
+                   int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter,
+                   const uint64_t* iter_dev, void* X_out, int64_t n, int C, int dtype,
+                   pxm_stream_t stream);
+/* chain_step with proxf given (PxMALA keeps proxf of the current state, mcmc.py:231); iter_dev as pxm_myula_step */
 int pxm_chain_step(const void* X, const void* proxf, const void* gradg, const double* delta_dev,
                    double delta, double lmda, const void* noise, int noise_complex, uint64_t seed,
-                   uint64_t chain0, uint64_t iter, void* X_out, int64_t n, int C, int dtype,
-                   pxm_stream_t stream);
-/* The same two steps with a caller-owned device iteration counter: the Philox iteration is iter + *iter_dev, read
- * when the kernel runs (NULL: iter alone), so a HIP graph of an iteration replays with fresh noise once the
- * captured sequence ends with pxm_counter_add.  (MYULA's generic-operator stepping engine, pxmcmc/mcmc.py:157-164.) */
-int pxm_myula_step_it(const void* X, const void* gradg, const double* T, double T_scalar,
-                      const double* delta_dev, double delta, double lmda, const void* noise,
-                      int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter,
-                      const uint64_t* iter_dev, void* X_out, int64_t n, int C, int dtype,
-                      pxm_stream_t stream);
-int pxm_chain_step_it(const void* X, const void* proxf, const void* gradg, const double* delta_dev,
-                      double delta, double lmda, const void* noise, int noise_complex, uint64_t seed,
-                      uint64_t chain0, uint64_t iter, const uint64_t* iter_dev, void* X_out, int64_t n,
-                      int C, int dtype, pxm_stream_t stream);
+                   uint64_t chain0, uint64_t iter, const uint64_t* iter_dev, void* X_out, int64_t n,
+                   int C, int dtype, pxm_stream_t stream);
 /* One stage of the SKROCK Chebyshev recursion (pxmcmc/mcmc.py:349-368 with the recursion coefficients of Pereyra,
  * Vargas-Mieles & Zygalakis 2020, not mcmc.py:370-383; the gradient of pxmcmc/mcmc.py:84-89 folded into a, b, c):
  *   out = a U + b P + c gradg + e V + r Z        (every array [C][n]; T [n] shared by chains)
  * P: b == 0 -> no term; proxf given -> P = proxf (analysis setting / user prior); proxf NULL -> P = soft(U, T or T_scalar)
  * as pxm_myula_step.  gradg, V: NULL -> no term.  Z: r == 0 -> no term (no noise code runs); noise given -> that array
  * (real, or complex with noise_complex); NULL -> the Philox stream of pxm_myula_step keyed (seed, chain0 + c, element,
- * iter), noise_complex = (0 | 1) | PXM_NOISE_F64 -- SKROCK.chain_step's randn [+ 1j randn] (pxmcmc/mcmc.py:338-347).
- * out must not alias an input.  _it: the Philox iteration is iter + *iter_dev, read when the kernel runs (graph replay). */
+ * iter [+ *iter_dev]), noise_complex = (0 | 1) | PXM_NOISE_F64 -- SKROCK.chain_step's randn [+ 1j randn]
+ * (pxmcmc/mcmc.py:338-347).  out must not alias an input. */
 int pxm_skrock_stage(const void* U, const void* proxf, const double* T, double T_scalar, const void* gradg,
                      const void* V, double a, double b, double c, double e, double r, const void* noise,
-                     int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter, void* out, int64_t n,
-                     int C, int dtype, pxm_stream_t stream);
-int pxm_skrock_stage_it(const void* U, const void* proxf, const double* T, double T_scalar, const void* gradg,
-                        const void* V, double a, double b, double c, double e, double r, const void* noise,
-                        int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter, const uint64_t* iter_dev,
-                        void* out, int64_t n, int C, int dtype, pxm_stream_t stream);
+                     int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter, const uint64_t* iter_dev,
+                     void* out, int64_t n, int C, int dtype, pxm_stream_t stream);
 /* N(0,1) draws of the Philox4x32-10 stream keyed (seed, chain0+c, iter): out [C][n] (f64 or c128) */
 int pxm_randn(void* out, int64_t n, int C, int dtype, uint64_t seed, uint64_t chain0, uint64_t iter,
               pxm_stream_t stream);
@@ -353,13 +341,6 @@ int pxm_quantile_range(const double* chain, int64_t nsamples, int64_t nparams, i
 int pxm_logtransition(const void* X1, const void* X2, const void* proxf, const void* gradg,
                       const double* delta_dev, double delta, double lmda, double* out, double* scratch,
                       int64_t n, int C, int dtype, pxm_stream_t stream);
-/* Metropolis accept + state swap + delta adaptation for every chain (pxmcmc/mcmc.py:244-260,
- * 277-279).  logalpha_terms: [C][4] = (logtrans_pc, logpi_p, logtrans_cp, logpi_c) real parts.
- * For accepted chains copies prop -> curr for each of nbuf (buffer pairs, sizes in elements).
- * u: injected uniforms [C] or NULL (Philox).  accept_out [C] int32; delta_dev updated when tune. */
-int pxm_pxmala_accept(const double* logalpha_terms, const double* u, uint64_t seed, uint64_t chain0,
-                      uint64_t iter, int32_t* accept_out, double* delta_dev, int tune, double lmda,
-                      int64_t it_index, int C, pxm_stream_t stream);
 /* One PxMALA iteration with every per-iteration quantity on the device (pxmcmc/mcmc.py:230-260).
  *   pxm_pxmala_propose : X' = chain_step(X, proxf, gradg) with per-chain delta_dev [C]; proxf' = soft(X', T);
  *                        logtrans_out[c] = calc_logtransition(X, X', proxf, gradg) as (re, im);
@@ -370,7 +351,7 @@ int pxm_pxmala_accept(const double* logalpha_terms, const double* u, uint64_t se
  *                        proxf == proxf_prop == NULL: the prox arrays are neither read nor written -- proxf = soft(X, T)
  *                        (the stock L1 prox, pxmcmc/prior.py:49-50) is formed in the kernel, and pxm_pxmala_finish forms
  *                        soft(X', T) the same way: 40 % fewer bytes in the pass and one array less in the conditional copy.
- *   pxm_pxmala_accept2 : logalpha = Re(logtrans_pc + logpi' - logtrans_cp - logpi), logpi' = -mu prior' - L2';
+ *   pxm_pxmala_accept  : logalpha = Re(logtrans_pc + logpi' - logtrans_cp - logpi), logpi' = -mu prior' - L2';
  *                        accept iff log(u) < logalpha (u injected [C] or the Philox uniform of (seed, chain, iteration));
  *                        accepted chains take (logpi', L2', prior') into their state scalars (logpi_c, L2_c as (re, im),
  *                        prior_c); delta_dev adapted when tune (:277-279) with the iteration number iter + *iter_dev;
@@ -382,7 +363,7 @@ int pxm_pxmala_accept(const double* logalpha_terms, const double* u, uint64_t se
  *                        d = data - preds' [n_data, data_dtype; invcov as for pxm_reduce_l2]; (ii) ONE workgroup that
  *                        totals those and the deferred sums of pxm_pxmala_propose (`propose_scratch`: that call's scratch) in
  *                        the order of the separate reductions, stores logtrans_pc / logtrans_cp / L2' as (re, im) [C] and
- *                        prior' [C] for observers, and runs the test of pxm_pxmala_accept2.  bump_counter: optional
+ *                        prior' [C] for observers, and runs the test of pxm_pxmala_accept.  bump_counter: optional
  *                        device counter advanced by one AFTER every chain has read iter_dev (replaces pxm_counter_add
  *                        in a captured iteration).  scratch: 2 * pxm_reduce_scratch_doubles(C) doubles.
  *   pxm_select_copy_many : up to 4 arrays per call, dst_a[c] = src_a[c] for accepted chains.
@@ -392,11 +373,11 @@ int pxm_pxmala_propose(const void* X, const void* proxf, const void* gradg, cons
                        int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter, const uint64_t* iter_dev,
                        void* X_prop, void* proxf_prop, double* logtrans_out, double* prior_out, double* scratch,
                        int64_t n, int C, int dtype, pxm_stream_t stream);
-int pxm_pxmala_accept2(const double* logtrans_pc, const double* logtrans_cp, const double* prior_p, const double* L2_p,
-                       double mu, double* logpi_c, double* L2_c, double* prior_c, const double* u, uint64_t seed,
-                       uint64_t chain0, uint64_t iter, const uint64_t* iter_dev, int32_t* accept_out, double* delta_dev,
-                       int tune, double lmda, int32_t* acc_trace, double* delta_trace, int chunk, int C,
-                       pxm_stream_t stream);
+int pxm_pxmala_accept(const double* logtrans_pc, const double* logtrans_cp, const double* prior_p, const double* L2_p,
+                      double mu, double* logpi_c, double* L2_c, double* prior_c, const double* u, uint64_t seed,
+                      uint64_t chain0, uint64_t iter, const uint64_t* iter_dev, int32_t* accept_out, double* delta_dev,
+                      int tune, double lmda, int32_t* acc_trace, double* delta_trace, int chunk, int C,
+                      pxm_stream_t stream);
 int pxm_pxmala_finish(const void* X_prop, const void* X_curr, const void* proxf_prop, const double* T, double T_scalar,
                       const void* gradg_prop, int64_t n, int dtype, const void* preds_prop, const void* data, const void* invcov, int invcov_complex,
                       int64_t n_data, int data_dtype, const double* propose_scratch, double mu, double lmda, double* logpi_c,
@@ -407,9 +388,6 @@ int pxm_pxmala_finish(const void* X_prop, const void* X_curr, const void* proxf_
 int pxm_select_copy_many(const int32_t* flag, int narrays, const void* const* src, void* const* dst, const int64_t* n,
                          const int* esize, int C, pxm_stream_t stream);
 int pxm_counter_add(uint64_t* counter_dev, uint64_t inc, pxm_stream_t stream);
-/* per-chain conditional copy: dst[c] = src[c] where flag[c] != 0; n elements of esize bytes */
-int pxm_select_copy(const int32_t* flag, const void* src, void* dst, int64_t n, int esize, int C,
-                    pxm_stream_t stream);
 
 /* ---- weak-lensing measurement helpers (pxmcmc/measurements.py:151-171, 242-304) --------- */
 /* out = flm .* kernel with entries [0,4) zeroed: harmonic_mapping (:162-171). kernel: [L*L] */
@@ -425,15 +403,13 @@ int pxm_wl_mask_scatter(const void* g, const int64_t* idx, const double* w, void
 /* ---- sparse path-integral measurement (pxmcmc/measurements.py:59-83) ---------------------- */
 /* y[c][row] = sum_k vals[k] x[c][indices[k]], k in [indptr[row], indptr[row+1]): PathIntegral.forward with
  * the CSR of path_matrix, PathIntegral.adjoint with the CSR of path_matrix.getH().  vals: float64, or
- * complex128 iff vals_complex; x: [C][ncols], y: [C][nrows], float64 (dtype 0) or complex128 (dtype 1). */
+ * complex128 iff vals_complex; x: [C][ncols], y: [C][nrows], float64 (dtype 0) or complex128 (dtype 1).
+ * scratch: NULL, or a caller-owned buffer of ncols * C elements of x's type through which a chain batch is first copied
+ * chain-minor ([ncols][C]), so that a gathered non-zero reads its C chains from one contiguous segment instead of C
+ * cache lines.  Identical sums in identical order either way (bit-equal results). */
 int pxm_csr_matvec(const int64_t* indptr, const int32_t* indices, const void* vals, int vals_complex,
-                   int64_t nrows, int64_t ncols, const void* x, void* y, int C, int dtype, pxm_stream_t stream);
-/* The same product for a chain batch, through a caller-owned scratch of ncols * C elements of x's type: the operand is
- * first copied chain-minor ([ncols][C]) so that a gathered non-zero reads its C chains from one contiguous segment
- * instead of C cache lines.  Identical sums in identical order (bit-equal results); scratch NULL = pxm_csr_matvec. */
-int pxm_csr_matvec_batched(const int64_t* indptr, const int32_t* indices, const void* vals, int vals_complex,
-                           int64_t nrows, int64_t ncols, const void* x, void* y, int C, int dtype, void* scratch,
-                           pxm_stream_t stream);
+                   int64_t nrows, int64_t ncols, const void* x, void* y, int C, int dtype, void* scratch,
+                   pxm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -101,26 +101,13 @@ SIGNATURES = {
     "pxm_residual_grad": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_myula_step": (
         c_int,
-        [c_vp, c_vp, c_vp, c_dbl, c_vp, c_dbl, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_i64, c_int, c_int, c_vp],
-    ),
-    "pxm_chain_step": (
-        c_int,
-        [c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_i64, c_int, c_int, c_vp],
-    ),
-    "pxm_myula_step_it": (
-        c_int,
         [c_vp, c_vp, c_vp, c_dbl, c_vp, c_dbl, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_vp, c_i64, c_int, c_int, c_vp],
     ),
-    "pxm_chain_step_it": (
+    "pxm_chain_step": (
         c_int,
         [c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_vp, c_i64, c_int, c_int, c_vp],
     ),
     "pxm_skrock_stage": (
-        c_int,
-        [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_i64,
-         c_int, c_int, c_vp],
-    ),
-    "pxm_skrock_stage_it": (
         c_int,
         [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_vp,
          c_i64, c_int, c_int, c_vp],
@@ -131,13 +118,12 @@ SIGNATURES = {
     "pxm_reduce_l2": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_reduce_vdot": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_logtransition": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
-    "pxm_pxmala_accept": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp, c_vp, c_int, c_dbl, c_i64, c_int, c_vp]),
     "pxm_pxmala_propose": (
         c_int,
         [c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
          c_i64, c_int, c_int, c_vp],
     ),
-    "pxm_pxmala_accept2": (
+    "pxm_pxmala_accept": (
         c_int,
         [c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp, c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_int, c_dbl, c_vp, c_vp,
          c_int, c_int, c_vp],
@@ -150,12 +136,10 @@ SIGNATURES = {
     ),
     "pxm_select_copy_many": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
     "pxm_counter_add": (c_int, [c_vp, c_u64, c_vp]),
-    "pxm_select_copy": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_wl_harmonic_mapping": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "pxm_wl_mask_gather": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp]),
     "pxm_wl_mask_scatter": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp]),
-    "pxm_csr_matvec": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_vp, c_int, c_int, c_vp]),
-    "pxm_csr_matvec_batched": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    "pxm_csr_matvec": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
 }
 
 

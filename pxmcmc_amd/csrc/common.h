@@ -27,6 +27,10 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
     }                                \
   } while (0)
 
+// The noise_complex argument of the noise-drawing entry points: (0 | 1) | PXM_NOISE_F64, where complex noise (1) needs a
+// complex state (dtype 1).  `fn` is the entry point the caller used; it names the error.  0, or -1 with the error set.
+int check_noise_arg(const char* fn, int noise_complex, int dtype);
+
 // ---- capture-safe teardown (host_api.cpp) ---------------------------------------------------
 // hipFree / hipEventDestroy are illegal while a stream capture is in progress, and a plan can be torn down at
 // any moment (Python's garbage collector).  Plans therefore never free device memory directly: they hand it to

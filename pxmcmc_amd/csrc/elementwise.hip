@@ -504,31 +504,6 @@ __global__ void k_l1_store(const double* __restrict__ red, double* __restrict__ 
   if (c < C) out[c] = red[2 * c];
 }
 
-__global__ void k_pxmala_accept(const double* __restrict__ terms, const double* __restrict__ u, uint64_t seed,
-                                uint64_t chain0, uint64_t iter, int32_t* __restrict__ accept, double* __restrict__ delta_dev,
-                                int tune, double lmda, int64_t it_index, int C) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  // logalpha = logtransXpXc + logpiXp - logtransXcXp - logpiXc   (pxmcmc/mcmc.py:244)
-  const double logalpha = terms[4 * c + 0] + terms[4 * c + 1] - terms[4 * c + 2] - terms[4 * c + 3];
-  const double uu = u ? u[c] : philox_uniform(seed, chain0 + c, iter);  // iter is passed by the host every step
-  const int acc = log(uu) < logalpha ? 1 : 0;
-  accept[c] = acc;
-  if (tune) {  // pxmcmc/mcmc.py:277-279
-    double d = delta_dev[c] * (1 + (acc - 0.5) / pow((double)(it_index + 1), 0.75));
-    d = fmin(fmax(d, lmda * 1e-8), lmda / 2);
-    delta_dev[c] = d;
-  }
-}
-
-__global__ void k_select_copy(const int32_t* __restrict__ flag, const uint64_t* __restrict__ src, uint64_t* __restrict__ dst,
-                              int64_t nwords) {
-  const int c = blockIdx.y;
-  if (!flag[c]) return;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nwords; i += (int64_t)gridDim.x * blockDim.x)
-    dst[(int64_t)c * nwords + i] = src[(int64_t)c * nwords + i];
-}
-
 __global__ void k_wl_mapping(const double2* __restrict__ flm, const double* __restrict__ kernel, double2* __restrict__ out,
                              int64_t n) {
   const int64_t base = (int64_t)blockIdx.y * n;
@@ -673,14 +648,13 @@ int pxm_residual_grad(const void* preds, const void* data, const void* invcov, i
   return 0;
 }
 
-int pxm_myula_step_it(const void* X, const void* gradg, const double* T, double T_scalar, const double* delta_dev,
-                      double delta, double lmda, const void* noise, int noise_complex, uint64_t seed, uint64_t chain0,
-                      uint64_t iter, const uint64_t* iter_dev, void* X_out, int64_t n, int C, int dtype,
-                      pxm_stream_t stream) {
+int pxm_myula_step(const void* X, const void* gradg, const double* T, double T_scalar, const double* delta_dev,
+                   double delta, double lmda, const void* noise, int noise_complex, uint64_t seed, uint64_t chain0,
+                   uint64_t iter, const uint64_t* iter_dev, void* X_out, int64_t n, int C, int dtype,
+                   pxm_stream_t stream) {
   CHECK_ARGS("pxm_myula_step");
   PXM_REQUIRE(X && gradg && X_out, "pxm_myula_step: null buffer");
-  PXM_REQUIRE((noise_complex & ~(1 | PXM_NOISE_F64)) == 0, "pxm_myula_step: noise_complex must be 0 or 1 (| PXM_NOISE_F64)");
-  PXM_REQUIRE(dtype == 1 || !(noise_complex & 1), "pxm_myula_step: complex noise needs a complex state");
+  if (int rc = check_noise_arg("pxm_myula_step", noise_complex, dtype)) return rc;
   dim3 g = ew_grid(n, C), b(256);
   NoiseSrc ns = make_noise_src(noise, noise_complex, seed, chain0, iter, iter_dev);
   if (dtype)
@@ -693,20 +667,12 @@ int pxm_myula_step_it(const void* X, const void* gradg, const double* T, double 
   return 0;
 }
 
-int pxm_myula_step(const void* X, const void* gradg, const double* T, double T_scalar, const double* delta_dev,
-                   double delta, double lmda, const void* noise, int noise_complex, uint64_t seed, uint64_t chain0,
-                   uint64_t iter, void* X_out, int64_t n, int C, int dtype, pxm_stream_t stream) {
-  return pxm_myula_step_it(X, gradg, T, T_scalar, delta_dev, delta, lmda, noise, noise_complex, seed, chain0, iter, nullptr,
-                           X_out, n, C, dtype, stream);
-}
-
-int pxm_chain_step_it(const void* X, const void* proxf, const void* gradg, const double* delta_dev, double delta,
-                      double lmda, const void* noise, int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter,
-                      const uint64_t* iter_dev, void* X_out, int64_t n, int C, int dtype, pxm_stream_t stream) {
+int pxm_chain_step(const void* X, const void* proxf, const void* gradg, const double* delta_dev, double delta,
+                   double lmda, const void* noise, int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter,
+                   const uint64_t* iter_dev, void* X_out, int64_t n, int C, int dtype, pxm_stream_t stream) {
   CHECK_ARGS("pxm_chain_step");
   PXM_REQUIRE(X && proxf && gradg && X_out, "pxm_chain_step: null buffer");
-  PXM_REQUIRE((noise_complex & ~(1 | PXM_NOISE_F64)) == 0, "pxm_chain_step: noise_complex must be 0 or 1 (| PXM_NOISE_F64)");
-  PXM_REQUIRE(dtype == 1 || !(noise_complex & 1), "pxm_chain_step: complex noise needs a complex state");
+  if (int rc = check_noise_arg("pxm_chain_step", noise_complex, dtype)) return rc;
   dim3 g = ew_grid(n, C), b(256);
   NoiseSrc ns = make_noise_src(noise, noise_complex, seed, chain0, iter, iter_dev);
   if (dtype)
@@ -717,13 +683,6 @@ int pxm_chain_step_it(const void* X, const void* proxf, const void* gradg, const
                        (const double*)gradg, (const double*)nullptr, 0.0, delta_dev, delta, lmda, ns, (double*)X_out, n);
   PXM_HIP(hipGetLastError());
   return 0;
-}
-
-int pxm_chain_step(const void* X, const void* proxf, const void* gradg, const double* delta_dev, double delta,
-                   double lmda, const void* noise, int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter,
-                   void* X_out, int64_t n, int C, int dtype, pxm_stream_t stream) {
-  return pxm_chain_step_it(X, proxf, gradg, delta_dev, delta, lmda, noise, noise_complex, seed, chain0, iter, nullptr, X_out,
-                           n, C, dtype, stream);
 }
 
 int pxm_randn(void* out, int64_t n, int C, int dtype, uint64_t seed, uint64_t chain0, uint64_t iter,
@@ -830,8 +789,7 @@ int pxm_pxmala_propose(const void* X, const void* proxf, const void* gradg, cons
               "pxm_pxmala_propose: proxf and proxf_prop are given together, or both null (prox = soft(., T) formed in the kernels)");
   PXM_REQUIRE((logtrans_out == nullptr) == (prior_out == nullptr),
               "pxm_pxmala_propose: logtrans_out and prior_out are given together, or both null (totals deferred to pxm_pxmala_finish)");
-  PXM_REQUIRE((noise_complex & ~(1 | PXM_NOISE_F64)) == 0, "pxm_pxmala_propose: noise_complex must be 0 or 1 (| PXM_NOISE_F64)");
-  PXM_REQUIRE(dtype == 1 || !(noise_complex & 1), "pxm_pxmala_propose: complex noise needs a complex state");
+  if (int rc = check_noise_arg("pxm_pxmala_propose", noise_complex, dtype)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int RS = red_slices(n);
   dim3 g(RS, C), b(512);  // (8 waves per slice: 25.5 us against 29.8 with 4 and 33.8 with 16 at n = 1.2 M complex, one chain)
@@ -860,14 +818,14 @@ static AcceptArgs make_accept_args(double mu, double lmda, double* logpi_c, doub
   return a;
 }
 
-int pxm_pxmala_accept2(const double* logtrans_pc, const double* logtrans_cp, const double* prior_p, const double* L2_p,
-                       double mu, double* logpi_c, double* L2_c, double* prior_c, const double* u, uint64_t seed,
-                       uint64_t chain0, uint64_t iter, const uint64_t* iter_dev, int32_t* accept_out, double* delta_dev,
-                       int tune, double lmda, int32_t* acc_trace, double* delta_trace, int chunk, int C,
-                       pxm_stream_t stream) {
+int pxm_pxmala_accept(const double* logtrans_pc, const double* logtrans_cp, const double* prior_p, const double* L2_p,
+                      double mu, double* logpi_c, double* L2_c, double* prior_c, const double* u, uint64_t seed,
+                      uint64_t chain0, uint64_t iter, const uint64_t* iter_dev, int32_t* accept_out, double* delta_dev,
+                      int tune, double lmda, int32_t* acc_trace, double* delta_trace, int chunk, int C,
+                      pxm_stream_t stream) {
   PXM_REQUIRE(C >= 1 && logtrans_pc && logtrans_cp && prior_p && L2_p && logpi_c && L2_c && prior_c && accept_out && delta_dev,
-              "pxm_pxmala_accept2: null buffer");
-  PXM_REQUIRE((acc_trace == nullptr) == (delta_trace == nullptr) && (!acc_trace || chunk >= 1), "pxm_pxmala_accept2: bad trace buffers");
+              "pxm_pxmala_accept: null buffer");
+  PXM_REQUIRE((acc_trace == nullptr) == (delta_trace == nullptr) && (!acc_trace || chunk >= 1), "pxm_pxmala_accept: bad trace buffers");
   hipLaunchKernelGGL(k_pxmala_accept2, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const double2*)logtrans_pc,
                      (const double2*)logtrans_cp, prior_p, (const double2*)L2_p,
                      make_accept_args(mu, lmda, logpi_c, L2_c, prior_c, u, seed, chain0, iter, iter_dev, accept_out, delta_dev, tune,
@@ -947,27 +905,6 @@ int pxm_select_copy_many(const int32_t* flag, int narrays, const void* const* sr
 int pxm_counter_add(uint64_t* counter_dev, uint64_t inc, pxm_stream_t stream) {
   PXM_REQUIRE(counter_dev, "pxm_counter_add: null counter");
   hipLaunchKernelGGL(k_counter_add, dim3(1), dim3(1), 0, (hipStream_t)stream, counter_dev, inc);
-  PXM_HIP(hipGetLastError());
-  return 0;
-}
-
-int pxm_pxmala_accept(const double* logalpha_terms, const double* u, uint64_t seed, uint64_t chain0, uint64_t iter,
-                      int32_t* accept_out, double* delta_dev, int tune, double lmda, int64_t it_index, int C,
-                      pxm_stream_t stream) {
-  PXM_REQUIRE(C >= 1 && logalpha_terms && accept_out, "pxm_pxmala_accept: bad arguments");
-  PXM_REQUIRE(!tune || delta_dev, "pxm_pxmala_accept: tune needs delta_dev");
-  hipLaunchKernelGGL(k_pxmala_accept, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, logalpha_terms, u, seed,
-                     chain0, iter, accept_out, delta_dev, tune, lmda, it_index, C);
-  PXM_HIP(hipGetLastError());
-  return 0;
-}
-
-int pxm_select_copy(const int32_t* flag, const void* src, void* dst, int64_t n, int esize, int C, pxm_stream_t stream) {
-  PXM_REQUIRE(C >= 1 && flag && src && dst && n >= 0 && esize > 0 && esize % 8 == 0, "pxm_select_copy: bad arguments");
-  if (n == 0) return 0;
-  const int64_t nwords = n * (esize / 8);
-  hipLaunchKernelGGL(k_select_copy, ew_grid(nwords, C), dim3(256), 0, (hipStream_t)stream, flag, (const uint64_t*)src,
-                     (uint64_t*)dst, nwords);
   PXM_HIP(hipGetLastError());
   return 0;
 }

@@ -19,6 +19,12 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line) {
   return -2;
 }
 
+int check_noise_arg(const char* fn, int noise_complex, int dtype) {
+  PXM_REQUIRE((noise_complex & ~(1 | PXM_NOISE_F64)) == 0, std::string(fn) + ": noise_complex must be 0 or 1 (| PXM_NOISE_F64)");
+  PXM_REQUIRE(dtype == 1 || !(noise_complex & 1), std::string(fn) + ": complex noise needs a complex state");
+  return 0;
+}
+
 // ---- deferred frees ---------------------------------------------------------------------------
 static std::mutex g_grave_mu;
 static std::vector<void*> g_grave_mem;
@@ -172,7 +178,7 @@ int drain_deferred() {
 
 extern "C" {
 
-int pxm_version(void) { return 500; }  // 5.0: pxm_wav_flow_status / pxm_wav_flow_enabled removed
+int pxm_version(void) { return 600; }  // 6.0: one entry point per operation; pxm_pxmala_accept has a new signature
 
 int pxm_noise_bits(void) { return 32; }  // the DEFAULT of the stepping entry points; PXM_NOISE_F64 selects 64 per call
 

@@ -1039,6 +1039,29 @@ int pxm_wav_synthesis_adjoint(pxm_wav_plan_t p, const void* f, void* X, int C, p
   return wav_synthesis_adjoint_impl(p, in, out, C, (hipStream_t)stream);
 }
 
+// The MYULA update of the three fused wavelet steps: checks that X_out does not alias X and the mode word (0, 1 or 2,
+// | PXM_NOISE_F64) in the name of the entry point `fn`, and fills the update fields of the ring2px output `out`.
+static int wav_update_out(pxm_wav_plan_t p, const char* fn, const void* X, const double* T, double T_scalar, double delta,
+                          double lmda, const void* noise, int mode, uint64_t seed, uint64_t chain0, uint64_t iter, void* X_out,
+                          PxOut* out) {
+  PXM_REQUIRE(X != X_out, std::string(fn) + ": X_out must not alias X");
+  PXM_REQUIRE((mode & ~PXM_NOISE_F64) >= 0 && (mode & ~PXM_NOISE_F64) <= 2, std::string(fn) + ": mode must be 0, 1 or 2 (| PXM_NOISE_F64)");
+  out->f = (double*)X_out;
+  out->X = (const double*)X;
+  out->T = T;
+  out->T_scalar = T_scalar;
+  out->delta = delta;
+  out->lmda = lmda;
+  out->noise = (const double*)noise;
+  out->mode = mode & ~PXM_NOISE_F64;
+  out->noise64 = (mode & PXM_NOISE_F64) ? 1 : 0;
+  out->seed = seed;
+  out->chain0 = chain0;
+  out->iter = iter;
+  out->iter_dev = p->iter_dev;
+  return 0;
+}
+
 int pxm_wav_gradg_step(pxm_wav_plan_t p, const void* X, const void* preds, const void* data, const void* invcov,
                        int invcov_complex, const double* T, double T_scalar, double delta, double lmda,
                        const void* noise, int mode, uint64_t seed, uint64_t chain0, uint64_t iter,
@@ -1046,28 +1069,14 @@ int pxm_wav_gradg_step(pxm_wav_plan_t p, const void* X, const void* preds, const
   int rc = wav_check(p, X, X_out, C, "pxm_wav_gradg_step");
   if (rc) return rc;
   PXM_REQUIRE(preds && data && invcov, "pxm_wav_gradg_step: null argument");
-  PXM_REQUIRE(X != X_out, "pxm_wav_gradg_step: X_out must not alias X");
-  PXM_REQUIRE((mode & ~PXM_NOISE_F64) >= 0 && (mode & ~PXM_NOISE_F64) <= 2, "pxm_wav_gradg_step: mode must be 0, 1 or 2 (| PXM_NOISE_F64)");
+  PxOut out;
+  if ((rc = wav_update_out(p, "pxm_wav_gradg_step", X, T, T_scalar, delta, lmda, noise, mode, seed, chain0, iter, X_out, &out))) return rc;
   PxIn in;
   in.f = (const double*)preds;
   in.chain_stride = (int64_t)p->L * (2 * p->L - 1);
   in.data = (const double*)data;
   in.invcov = (const double*)invcov;
   in.invcov_complex = invcov_complex;
-  PxOut out;
-  out.f = (double*)X_out;
-  out.X = (const double*)X;
-  out.T = T;
-  out.T_scalar = T_scalar;
-  out.delta = delta;
-  out.lmda = lmda;
-  out.noise = (const double*)noise;
-  out.mode = mode & ~PXM_NOISE_F64;
-  out.noise64 = (mode & PXM_NOISE_F64) ? 1 : 0;
-  out.seed = seed;
-  out.chain0 = chain0;
-  out.iter = iter;
-  out.iter_dev = p->iter_dev;
   return wav_synthesis_adjoint_impl(p, in, out, C, (hipStream_t)stream);
 }
 
@@ -1104,23 +1113,9 @@ int pxm_wav_image_step(pxm_wav_plan_t p, const void* X, const void* data, const 
   int rc = wav_check(p, X, X_out, C, "pxm_wav_image_step");
   if (rc) return rc;
   PXM_REQUIRE(data && invcov && preds_out, "pxm_wav_image_step: null argument");
-  PXM_REQUIRE(X != X_out, "pxm_wav_image_step: X_out must not alias X");
-  PXM_REQUIRE((mode & ~PXM_NOISE_F64) >= 0 && (mode & ~PXM_NOISE_F64) <= 2, "pxm_wav_image_step: mode must be 0, 1 or 2 (| PXM_NOISE_F64)");
-  hipStream_t st = (hipStream_t)stream;
   PxOut out;
-  out.f = (double*)X_out;
-  out.X = (const double*)X;
-  out.T = T;
-  out.T_scalar = T_scalar;
-  out.delta = delta;
-  out.lmda = lmda;
-  out.noise = (const double*)noise;
-  out.mode = mode & ~PXM_NOISE_F64;
-  out.noise64 = (mode & PXM_NOISE_F64) ? 1 : 0;
-  out.seed = seed;
-  out.chain0 = chain0;
-  out.iter = iter;
-  out.iter_dev = p->iter_dev;
+  if ((rc = wav_update_out(p, "pxm_wav_image_step", X, T, T_scalar, delta, lmda, noise, mode, seed, chain0, iter, X_out, &out))) return rc;
+  hipStream_t st = (hipStream_t)stream;
   if ((rc = run_tasks(p->adj_invadj, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;          // residual rings -> H_L
   if ((rc = run_tasks(p->adj_fwdadj, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;          // -> rings of every scale
   if (wav_can_fuse_dft(p)) {
@@ -1226,8 +1221,8 @@ int pxm_wav_ring_step(pxm_wav_plan_t p, const void* X, double w_re, double w_im,
   int rc = wav_check(p, X, X_out, C, "pxm_wav_ring_step");
   if (rc) return rc;
   PXM_REQUIRE(p->have_data_rings, "pxm_wav_ring_step: call pxm_wav_ring_set_data first");
-  PXM_REQUIRE(X != X_out, "pxm_wav_ring_step: X_out must not alias X");
-  PXM_REQUIRE((mode & ~PXM_NOISE_F64) >= 0 && (mode & ~PXM_NOISE_F64) <= 2, "pxm_wav_ring_step: mode must be 0, 1 or 2 (| PXM_NOISE_F64)");
+  PxOut out;
+  if ((rc = wav_update_out(p, "pxm_wav_ring_step", X, T, T_scalar, delta, lmda, noise, mode, seed, chain0, iter, X_out, &out))) return rc;
   hipStream_t st = (hipStream_t)stream;
   // H' = w ((2L-1) B^T B H - B^T DFT(data)): inverse transform, ring residual and inverse-adjoint in one GEMM
   GemmAffine aff;
@@ -1238,20 +1233,6 @@ int pxm_wav_ring_step(pxm_wav_plan_t p, const void* X, double w_re, double w_im,
   aff.bump = p->iter_dev;  // the step's iteration number = counter after this bump
   if ((rc = run_tasks(p->gram, p->ws, p->ws, p->ncol, C, st, aff, &p->prof))) return rc;
   if ((rc = run_tasks(p->adj_fwdadj, p->ws, p->ws, p->ncol, C, st, GemmAffine(), &p->prof))) return rc;
-  PxOut out;
-  out.f = (double*)X_out;
-  out.X = (const double*)X;
-  out.T = T;
-  out.T_scalar = T_scalar;
-  out.delta = delta;
-  out.lmda = lmda;
-  out.noise = (const double*)noise;
-  out.mode = mode & ~PXM_NOISE_F64;
-  out.noise64 = (mode & PXM_NOISE_F64) ? 1 : 0;
-  out.seed = seed;
-  out.chain0 = chain0;
-  out.iter = iter;
-  out.iter_dev = p->iter_dev;
   if (wav_can_fuse_dft(p)) {
     // rings -> X_out -> rings of X_out in one kernel per scale, then the per-scale forward GEMMs
     if ((rc = wav_rings_update_rings(p, out, C, st))) return rc;

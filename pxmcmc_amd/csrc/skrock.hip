@@ -131,17 +131,16 @@ using namespace pxm;
 
 extern "C" {
 
-int pxm_skrock_stage_it(const void* U, const void* proxf, const double* T, double T_scalar, const void* gradg, const void* V,
-                        double a, double b, double c, double e, double r, const void* noise, int noise_complex,
-                        uint64_t seed, uint64_t chain0, uint64_t iter, const uint64_t* iter_dev, void* out, int64_t n, int C,
-                        int dtype, pxm_stream_t stream) {
+int pxm_skrock_stage(const void* U, const void* proxf, const double* T, double T_scalar, const void* gradg, const void* V,
+                     double a, double b, double c, double e, double r, const void* noise, int noise_complex, uint64_t seed,
+                     uint64_t chain0, uint64_t iter, const uint64_t* iter_dev, void* out, int64_t n, int C, int dtype,
+                     pxm_stream_t stream) {
   PXM_REQUIRE(n >= 0 && C >= 1 && C <= 65535 && (dtype == 0 || dtype == 1), "pxm_skrock_stage: bad n / C / dtype");
   if (n == 0) return 0;
   PXM_REQUIRE(U && out, "pxm_skrock_stage: null buffer");
   PXM_REQUIRE(out != U && out != proxf && out != gradg && out != V && out != noise,
               "pxm_skrock_stage: out must not alias an input");
-  PXM_REQUIRE((noise_complex & ~(1 | PXM_NOISE_F64)) == 0, "pxm_skrock_stage: noise_complex must be 0 or 1 (| PXM_NOISE_F64)");
-  PXM_REQUIRE(dtype == 1 || !(noise_complex & 1), "pxm_skrock_stage: complex noise needs a complex state");
+  if (int rc = check_noise_arg("pxm_skrock_stage", noise_complex, dtype)) return rc;
   const int pm = b == 0.0 ? 0 : (proxf ? 2 : 1);
   const bool nz = r != 0.0;
   const SkNoise ns{(const double*)noise, noise_complex & 1, (noise_complex & PXM_NOISE_F64) ? 1 : 0, seed, chain0, iter, iter_dev};
@@ -153,13 +152,6 @@ int pxm_skrock_stage_it(const void* U, const void* proxf, const double* T, doubl
   else sk_launch<false>(pm, nz, g, st, u, p, T, T_scalar, gr, v, k, ns, (double*)out, n);
   PXM_HIP(hipGetLastError());
   return 0;
-}
-
-int pxm_skrock_stage(const void* U, const void* proxf, const double* T, double T_scalar, const void* gradg, const void* V,
-                     double a, double b, double c, double e, double r, const void* noise, int noise_complex, uint64_t seed,
-                     uint64_t chain0, uint64_t iter, void* out, int64_t n, int C, int dtype, pxm_stream_t stream) {
-  return pxm_skrock_stage_it(U, proxf, T, T_scalar, gradg, V, a, b, c, e, r, noise, noise_complex, seed, chain0, iter, nullptr,
-                             out, n, C, dtype, stream);
 }
 
 }  // extern "C"

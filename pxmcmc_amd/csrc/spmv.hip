@@ -109,8 +109,9 @@ __global__ void k_chains_to_minor(const T* __restrict__ x, T* __restrict__ xt, i
 
 using namespace pxm;
 
-static int csr_matvec_impl(const int64_t* indptr, const int32_t* indices, const void* vals, int vals_complex, int64_t nrows,
-                           int64_t ncols, const void* x, void* y, int C, int dtype, void* scratch, pxm_stream_t stream) {
+extern "C" int pxm_csr_matvec(const int64_t* indptr, const int32_t* indices, const void* vals, int vals_complex,
+                              int64_t nrows, int64_t ncols, const void* x, void* y, int C, int dtype, void* scratch,
+                              pxm_stream_t stream) {
   PXM_REQUIRE(indptr && nrows >= 0 && ncols >= 0 && C >= 1, "pxm_csr_matvec: bad arguments");
   if (nrows == 0) return 0;  // no paths: nothing to write
   PXM_REQUIRE(y && (x || ncols == 0), "pxm_csr_matvec: null vector");
@@ -148,16 +149,4 @@ static int csr_matvec_impl(const int64_t* indptr, const int32_t* indices, const 
   }
   PXM_HIP(hipGetLastError());
   return 0;
-}
-
-extern "C" int pxm_csr_matvec(const int64_t* indptr, const int32_t* indices, const void* vals, int vals_complex,
-                              int64_t nrows, int64_t ncols, const void* x, void* y, int C, int dtype,
-                              pxm_stream_t stream) {
-  return csr_matvec_impl(indptr, indices, vals, vals_complex, nrows, ncols, x, y, C, dtype, nullptr, stream);
-}
-
-extern "C" int pxm_csr_matvec_batched(const int64_t* indptr, const int32_t* indices, const void* vals, int vals_complex,
-                                      int64_t nrows, int64_t ncols, const void* x, void* y, int C, int dtype,
-                                      void* scratch, pxm_stream_t stream) {
-  return csr_matvec_impl(indptr, indices, vals, vals_complex, nrows, ncols, x, y, C, dtype, scratch, stream);
 }

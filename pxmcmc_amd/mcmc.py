@@ -732,7 +732,7 @@ class PxMALA(MYULA):
 
         One iteration is a fixed sequence of device operations on static buffers -- proposal + prox + forward
         transition + prior in one pass (pxm_pxmala_propose), forward model, gradient, L2, reverse transition,
-        Metropolis test / delta adaptation / traces on the device (pxm_pxmala_accept2), one conditional copy of the
+        Metropolis test / delta adaptation / traces on the device (pxm_pxmala_accept), one conditional copy of the
         accepted states -- and, with the device Philox stream, is replayed from a captured HIP graph between
         observable events (save candidates, progress prints, trace flushes)."""
         self._prepare()
@@ -818,8 +818,8 @@ class PxMALA(MYULA):
             self._last_transitions = (ltc, ltp)  # q(X'|X), q(X|X') of this iteration (pxmcmc/mcmc.py:240-241)
             self._last_proposal = (prp, L2p)
             u = np.array([np.random.rand() for _ in range(C)]) if host_rng else None
-            ops.pxmala_accept2(ltp, ltc, prp, L2p, self.mu, logpiXc, L2Xc, priorXc, accept, delta_dev, self.tune_delta,
-                               self.lmda, u=u, iter_dev=counter, acc_trace=acc_buf, delta_trace=delta_buf, **kw)
+            ops.pxmala_accept(ltp, ltc, prp, L2p, self.mu, logpiXc, L2Xc, priorXc, accept, delta_dev, self.tune_delta,
+                              self.lmda, u=u, iter_dev=counter, acc_trace=acc_buf, delta_trace=delta_buf, **kw)
             ops.select_copy_many(accept, [(Xp, X_curr), (pp.to(curr_preds.dtype), curr_preds), (gp, gradg_curr), (pxp, proxf_curr)])
 
         # HIP graph of one iteration (device Philox stream only; any operator that synchronises or cannot be

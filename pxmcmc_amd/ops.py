@@ -161,7 +161,7 @@ def myula_step(X, gradg, T, delta, lmda, noise=None, noise_complex=False, seed=0
     w, wc = _noise_args(noise, x, noise_complex)
     out = torch.empty_like(x) if out is None else _out_like(out, x)
     check(
-        lib.pxm_myula_step_it(
+        lib.pxm_myula_step(
             _p(x), _p(g), _p(Tv), Ts, _p(dd), ds, float(lmda), _p(w), wc | _nf(noise64), seed, chain0, it, _p(iter_dev), _p(out), x.shape[1],
             x.shape[0], _dt(x), _stream()
         )
@@ -188,7 +188,7 @@ def chain_step(X, proxf, gradg, delta, lmda, noise=None, noise_complex=False, se
     w, wc = _noise_args(noise, x, noise_complex)
     out = torch.empty_like(x) if out is None else _out_like(out, x)
     check(
-        lib.pxm_chain_step_it(
+        lib.pxm_chain_step(
             _p(x), _p(px), _p(g), _p(dd), ds, float(lmda), _p(w), wc | _nf(noise64), seed, chain0, it, _p(iter_dev), _p(out), x.shape[1],
             x.shape[0], _dt(x), _stream()
         )
@@ -220,7 +220,7 @@ def skrock_stage(U, a, b=0.0, c=0.0, e=0.0, r=0.0, T=None, proxf=None, gradg=Non
     w, wc = _noise_args(noise, u, noise_complex) if r != 0 else (None, int(bool(noise_complex)))
     out = torch.empty_like(u) if out is None else _out_like(out, u)
     check(
-        lib.pxm_skrock_stage_it(
+        lib.pxm_skrock_stage(
             _p(u), _p(px), _p(Tv), Ts, _p(g), _p(v), float(a), float(b), float(c), float(e), float(r), _p(w), wc | _nf(noise64),
             seed, chain0, it, _p(iter_dev), _p(out), u.shape[1], u.shape[0], _dt(u), _stream()
         )
@@ -315,16 +315,6 @@ def logtransition(X1, X2, proxf, gradg, delta, lmda):
     return out
 
 
-def pxmala_accept(terms, delta_dev, tune, lmda, it_index, u=None, seed=0, chain0=0, it=0):
-    """Metropolis test + delta adaptation per chain (pxmcmc/mcmc.py:244-260,277-279)."""
-    t = as_device(terms, _REAL)
-    C_ = t.shape[0]
-    uu = None if u is None else as_device(u, _REAL).reshape(-1)
-    acc = torch.empty(C_, dtype=torch.int32, device=t.device)
-    check(lib.pxm_pxmala_accept(_p(t), _p(uu), seed, chain0, it, _p(acc), _p(delta_dev), int(bool(tune)), float(lmda), int(it_index), C_, _stream()))
-    return acc
-
-
 def reduce_scratch_doubles(C_):
     return int(lib.pxm_reduce_scratch_doubles(int(C_)))
 
@@ -358,14 +348,14 @@ def pxmala_propose(X, proxf, gradg, T, prior_weights, delta_dev, lmda, Xp, proxf
     )
 
 
-def pxmala_accept2(lt_pc, lt_cp, prior_p, L2_p, mu, logpi_c, L2_c, prior_c, accept, delta_dev, tune, lmda, u=None, seed=0,
-                   chain0=0, it=0, iter_dev=None, acc_trace=None, delta_trace=None):
+def pxmala_accept(lt_pc, lt_cp, prior_p, L2_p, mu, logpi_c, L2_c, prior_c, accept, delta_dev, tune, lmda, u=None, seed=0,
+                  chain0=0, it=0, iter_dev=None, acc_trace=None, delta_trace=None):
     """Metropolis test + state scalars + delta adaptation + traces on the device (pxmcmc/mcmc.py:244-260,277-279)."""
     C_ = accept.shape[0]
     uu = None if u is None else as_device(u, _REAL).reshape(-1)
     chunk = 0 if acc_trace is None else acc_trace.shape[0]
     check(
-        lib.pxm_pxmala_accept2(
+        lib.pxm_pxmala_accept(
             _p(lt_pc), _p(lt_cp), _p(prior_p), _p(L2_p), float(mu), _p(logpi_c), _p(L2_c), _p(prior_c), _p(uu), seed, chain0,
             int(it), _p(iter_dev), _p(accept), _p(delta_dev), int(bool(tune)), float(lmda), _p(acc_trace), _p(delta_trace),
             int(chunk), C_, _stream(),
@@ -425,16 +415,6 @@ def counter_add(counter, inc=1):
     check(lib.pxm_counter_add(_p(counter), int(inc), _stream()))
 
 
-def select_copy(flag, src, dst):
-    """dst[c] = src[c] for chains with flag[c] != 0 (in place on dst)."""
-    s, _ = _batched(src)
-    d, _ = _batched(dst)
-    if s.shape != d.shape or s.dtype != d.dtype:
-        raise ValueError("select_copy: shape / dtype mismatch")
-    check(lib.pxm_select_copy(_p(flag), _p(s), _p(d), s.shape[1], s.element_size(), s.shape[0], _stream()))
-    return dst
-
-
 # ---- sparse measurement ----------------------------------------------------------------
 class CsrMatrix:
     """A scipy.sparse matrix resident on the GPU in CSR form (int64 indptr, int32 indices, f64 / c128 values)."""
@@ -463,8 +443,8 @@ class CsrMatrix:
         out = torch.empty((x.shape[0], self.shape[0]), dtype=x.dtype, device=x.device)
         # chain batches gather from a chain-minor copy of the operand (caller-owned scratch, stream-ordered reuse)
         scratch = torch.empty(x.numel(), dtype=x.dtype, device=x.device) if x.shape[0] > 1 else None
-        check(lib.pxm_csr_matvec_batched(_p(self.indptr), _p(self.indices), _p(self.vals), int(self.is_complex), self.shape[0],
-                                         self.shape[1], _p(x), _p(out), x.shape[0], _dt(x), _p(scratch), _stream()))
+        check(lib.pxm_csr_matvec(_p(self.indptr), _p(self.indices), _p(self.vals), int(self.is_complex), self.shape[0],
+                                 self.shape[1], _p(x), _p(out), x.shape[0], _dt(x), _p(scratch), _stream()))
         return out[0] if squeeze else out
 
 
@@ -485,33 +465,55 @@ def live_plans():
     return [pl for pl in plans if getattr(pl, "_h", None)]
 
 
-class ShtPlan:
-    """MW spin spherical-harmonic transforms at bandlimit L (replaces the pyssht calls)."""
+class _Plan:
+    """What the plan classes share: the device handle ``_h`` (made by ``create(*args, &h)``, listed in the live-plan
+    registry, given back to ``destroy`` with the object), the batched call of a transform, and the device status word
+    (``status_fn``) reported in the name ``label``."""
 
-    def __init__(self, L, spin=0, max_chains=1):
-        require_gpu()
-        self.L, self.spin, self.max_chains = int(L), int(spin), int(max_chains)
-        self.npix, self.nlm = L * (2 * L - 1), L * L
+    def __init__(self, create, args, destroy, status_fn, label):
+        self._destroy, self._status_fn, self._label = destroy, status_fn, label
         h = C.c_void_p()
-        check(lib.pxm_sht_plan_create(self.L, self.spin, self.max_chains, 0, C.byref(h)))
+        check(create(*args, C.byref(h)))
         self._h = h
         _register_plan(self)
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h and lib is not None:  # lib is None during interpreter shutdown
-            lib.pxm_sht_plan_destroy(h)
+            self._destroy(h)
             self._h = None
 
-    def _run(self, fn, x, n_in, n_out):
+    def _run(self, fn, x, n_in, n_out, out=None):
         x, squeeze = _batched(as_device(x, _CPLX))
         if x.shape[1] != n_in:
             raise AssertionError(f"expected length {n_in}, got {x.shape[1]}")
         if x.shape[0] > self.max_chains:
             raise ValueError("more chains than the plan was created for")
-        out = torch.empty((x.shape[0], n_out), dtype=_CPLX, device=x.device)
+        if out is None:
+            out = torch.empty((x.shape[0], n_out), dtype=_CPLX, device=x.device)
+        elif out.shape != (x.shape[0], n_out) or out.dtype != _CPLX or not out.is_contiguous():
+            raise ValueError("out= buffer has the wrong shape / dtype / layout")
         check(fn(self._h, _p(x), _p(out), x.shape[0], _stream()))
         return out[0] if squeeze else out
+
+    def status(self, clear=False):
+        """bit mask of the bounded device waits of this plan that expired (0 = none; include/pxmcmc_amd.h); synchronises"""
+        return int(check(self._status_fn(self._h, int(bool(clear)), _stream())))
+
+    def raise_on_fault(self, clear=True):
+        """raise PxmError if a kernel of this plan reported an expired wait since the last check (``clear``: reset the word)"""
+        raise_on_status(self.status(clear=clear), self._label)
+
+
+class ShtPlan(_Plan):
+    """MW spin spherical-harmonic transforms at bandlimit L (replaces the pyssht calls)."""
+
+    def __init__(self, L, spin=0, max_chains=1):
+        require_gpu()
+        self.L, self.spin, self.max_chains = int(L), int(spin), int(max_chains)
+        self.npix, self.nlm = L * (2 * L - 1), L * L
+        super().__init__(lib.pxm_sht_plan_create, (self.L, self.spin, self.max_chains, 0), lib.pxm_sht_plan_destroy,
+                         lib.pxm_sht_status, f"ShtPlan(L={self.L}, spin={self.spin})")
 
     def inverse(self, flm):
         return self._run(lib.pxm_sht_inverse, flm, self.nlm, self.npix)
@@ -533,15 +535,8 @@ class ShtPlan:
         table-free recursion kernels (csrc/sht_rec.hip) instead of the ring-table GEMM"""
         return int(check(lib.pxm_sht_uses_recursion(self._h)))
 
-    def status(self, clear=False):
-        """bit mask of the bounded device waits of this plan that expired (0 = none); synchronises"""
-        return int(check(lib.pxm_sht_status(self._h, int(bool(clear)), _stream())))
 
-    def raise_on_fault(self, clear=True):
-        raise_on_status(self.status(clear=clear), f"ShtPlan(L={self.L}, spin={self.spin})")
-
-
-class WavPlan:
+class WavPlan(_Plan):
     """Axisymmetric scale-discretised wavelet transforms (replaces the pys2let calls)."""
 
     def __init__(self, L, B, J_min, max_chains=1):
@@ -551,29 +546,8 @@ class WavPlan:
         nscal = C.c_int64()
         self.ncoefs = int(check(lib.pxm_wav_ncoefs(self.L, self.B, self.J_min, C.byref(nscal))))
         self.nscal = int(nscal.value)
-        h = C.c_void_p()
-        check(lib.pxm_wav_plan_create(self.L, self.B, self.J_min, self.max_chains, 0, C.byref(h)))
-        self._h = h
-        _register_plan(self)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h and lib is not None:
-            lib.pxm_wav_plan_destroy(h)
-            self._h = None
-
-    def _run(self, fn, x, n_in, n_out, out=None):
-        x, squeeze = _batched(as_device(x, _CPLX))
-        if x.shape[1] != n_in:
-            raise AssertionError(f"expected length {n_in}, got {x.shape[1]}")
-        if x.shape[0] > self.max_chains:
-            raise ValueError("more chains than the plan was created for")
-        if out is None:
-            out = torch.empty((x.shape[0], n_out), dtype=_CPLX, device=x.device)
-        elif out.shape != (x.shape[0], n_out) or out.dtype != _CPLX or not out.is_contiguous():
-            raise ValueError("out= buffer has the wrong shape / dtype / layout")
-        check(fn(self._h, _p(x), _p(out), x.shape[0], _stream()))
-        return out[0] if squeeze else out
+        super().__init__(lib.pxm_wav_plan_create, (self.L, self.B, self.J_min, self.max_chains, 0), lib.pxm_wav_plan_destroy,
+                         lib.pxm_wav_status, f"WavPlan(L={self.L})")
 
     def synthesis(self, X, out=None):
         return self._run(lib.pxm_wav_synthesis, X, self.ncoefs, self.npix, out=out)
@@ -587,6 +561,17 @@ class WavPlan:
     def analysis_adjoint(self, X):
         return self._run(lib.pxm_wav_analysis_adjoint, X, self.ncoefs, self.npix)
 
+    def _update_args(self, x, T, noise, noise_complex, pairs, out):
+        """the MYULA-update arguments of the fused steps: thresholds, noise (``pairs``: two real chains per complex slot,
+        PXM_MODE_REAL_PAIRS) and the result buffer (fresh, or a distinct tensor of the state's shape)"""
+        Tv, Ts = _vecT(T, self.ncoefs, x.device)
+        w, wc = _pair_noise_args(noise, x) if pairs else _noise_args(noise, x, noise_complex)
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != _CPLX or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+            raise ValueError("out= buffer must be a distinct contiguous complex128 tensor of the state's shape")
+        return Tv, Ts, w, wc, out
+
     def gradg_step(self, X, preds, data, invcov, T, delta, lmda, noise=None, noise_complex=False, seed=0, chain0=0, it=0, out=None,
                    pairs=False, noise64=False):
         """Fused calc_gradg + proxf + chain_step (pxmcmc/mcmc.py:158-160) for the synthesis setting.
@@ -599,12 +584,7 @@ class WavPlan:
         ic = as_device(invcov).reshape(-1)
         if d.numel() != self.npix or ic.numel() != self.npix:
             raise ValueError("data / invcov length mismatch")
-        Tv, Ts = _vecT(T, self.ncoefs, x.device)
-        w, wc = _pair_noise_args(noise, x) if pairs else _noise_args(noise, x, noise_complex)
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != _CPLX or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
-            raise ValueError("out= buffer must be a distinct contiguous complex128 tensor of the state's shape")
+        Tv, Ts, w, wc, out = self._update_args(x, T, noise, noise_complex, pairs, out)
         check(
             lib.pxm_wav_gradg_step(
                 self._h, _p(x), _p(p), _p(d), _p(ic), int(ic.is_complex()), _p(Tv), Ts, float(delta), float(lmda),
@@ -636,12 +616,7 @@ class WavPlan:
         if x.shape[1] != self.ncoefs or x.shape[0] > self.max_chains:
             raise AssertionError("image_step: shape mismatch")
         d, ic = self._image_args(data, invcov)
-        Tv, Ts = _vecT(T, self.ncoefs, x.device)
-        w, wc = _pair_noise_args(noise, x) if pairs else _noise_args(noise, x, noise_complex)
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != _CPLX or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
-            raise ValueError("out= buffer must be a distinct contiguous complex128 tensor of the state's shape")
+        Tv, Ts, w, wc, out = self._update_args(x, T, noise, noise_complex, pairs, out)
         if preds_out is None:
             preds_out = torch.empty((x.shape[0], self.npix), dtype=_CPLX, device=x.device)
         elif preds_out.shape != (x.shape[0], self.npix) or preds_out.dtype != _CPLX or not preds_out.is_contiguous():
@@ -674,12 +649,7 @@ class WavPlan:
         x, squeeze = _batched(as_device(X, _CPLX))
         if x.shape[1] != self.ncoefs or x.shape[0] > self.max_chains:
             raise AssertionError("ring_step: shape mismatch")
-        Tv, Ts = _vecT(T, self.ncoefs, x.device)
-        wn, wc = _pair_noise_args(noise, x) if pairs else _noise_args(noise, x, noise_complex)
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != _CPLX or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
-            raise ValueError("out= buffer must be a distinct contiguous complex128 tensor of the state's shape")
+        Tv, Ts, wn, wc, out = self._update_args(x, T, noise, noise_complex, pairs, out)
         w = complex(w)
         check(
             lib.pxm_wav_ring_step(
@@ -701,14 +671,6 @@ class WavPlan:
     def exact_dft_scales(self):
         """scales whose 511-point rings the fused step transforms with the exact-length unit (csrc/dft_pfa.h); 0 = Bluestein"""
         return int(check(lib.pxm_wav_exact_dft_scales(self._h)))
-
-    def status(self, clear=False):
-        """bit mask of the bounded device waits of this plan that expired (0 = none; include/pxmcmc_amd.h); synchronises"""
-        return int(check(lib.pxm_wav_status(self._h, int(bool(clear)), _stream())))
-
-    def raise_on_fault(self, clear=True):
-        """raise PxmError if a kernel of this plan reported an expired wait since the last check (``clear``: reset the word)"""
-        raise_on_status(self.status(clear=clear), f"WavPlan(L={self.L})")
 
     # ---- weak-lensing measurement fused with the synthesis (pxm_wav_wl_*) ----
     def wl_attach(self, pix2data, weight, ndata):
@@ -782,7 +744,7 @@ class WavPlan:
         return (ms.value, nl.value, nb.value, nf.value), (dms.value, dnl.value, dnb.value)
 
 
-class DirWavPlan:
+class DirWavPlan(_Plan):
     """Directional (N = dirs >= 1) scale-discretised wavelet transforms, spin 0 (replaces the pys2let calls with N > 1;
     include/pxmcmc_amd.h, pxm_dwav_*).  Layout [scaling | j = J_min .. J_max], block j = 2N - 1 orientation planes of
     the MW grid at bl_j.  With N = 1 it computes what :class:`WavPlan` computes (without WavPlan's fused sampler steps)."""
@@ -794,18 +756,8 @@ class DirWavPlan:
         nscal = C.c_int64()
         self.ncoefs = int(check(lib.pxm_dwav_ncoefs(self.L, self.B, self.J_min, self.N, C.byref(nscal))))
         self.nscal = int(nscal.value)
-        h = C.c_void_p()
-        check(lib.pxm_dwav_plan_create(self.L, self.B, self.J_min, self.N, self.max_chains, 0, C.byref(h)))
-        self._h = h
-        _register_plan(self)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h and lib is not None:
-            lib.pxm_dwav_plan_destroy(h)
-            self._h = None
-
-    _run = WavPlan._run
+        super().__init__(lib.pxm_dwav_plan_create, (self.L, self.B, self.J_min, self.N, self.max_chains, 0),
+                         lib.pxm_dwav_plan_destroy, lib.pxm_dwav_status, f"DirWavPlan(L={self.L}, N={self.N})")
 
     def synthesis(self, X, out=None):
         return self._run(lib.pxm_dwav_synthesis, X, self.ncoefs, self.npix, out=out)
@@ -828,13 +780,6 @@ class DirWavPlan:
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         check(lib.pxm_dwav_plan_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
-
-    def status(self, clear=False):
-        """bit mask of the bounded device waits of the inner SHT plans that expired (0 = none); synchronises"""
-        return int(check(lib.pxm_dwav_status(self._h, int(bool(clear)), _stream())))
-
-    def raise_on_fault(self, clear=True):
-        raise_on_status(self.status(clear=clear), f"DirWavPlan(L={self.L}, N={self.N})")
 
 
 # ---- device-resident iteration counter (HIP-graph replay) -----------------------------------

@@ -123,7 +123,8 @@ def test_reductions_and_logtransition_golden():
     np.testing.assert_allclose(_np(ops.reduce_l2(Z, d, icc)), exp, rtol=1e-12)
 
 
-def test_tune_delta_and_accept_golden():
+def test_pxmala_accept_tune_delta_golden():
+    """pxm_pxmala_accept's Metropolis flag and delta adaptation against the reference's tuning sequence (g4_pxmala.npz)"""
     import torch
 
     from pxmcmc_amd import ops
@@ -131,10 +132,17 @@ def test_tune_delta_and_accept_golden():
     g = golden("g4_pxmala.npz")
     lmda, delta = g["params"][:2]
     d = torch.full((1,), float(delta), dtype=torch.float64, device="cuda")
+
+    def dev(*v):
+        return torch.tensor([v], dtype=torch.float64, device="cuda")
+
     for i, a in enumerate(g["tune_acc"]):
-        # logalpha = +-inf forces the accept flag to the recorded one
-        terms = np.array([[np.inf if a else -np.inf, 0.0, 0.0, 0.0]])
-        acc = ops.pxmala_accept(terms, d, True, lmda, i, u=np.array([0.5]))
+        # logalpha = Re(lt_pc) - mu prior' - Re(L2') - Re(lt_cp) - Re(logpi) = +-inf forces the accept flag to the recorded
+        # one; iter = i adapts delta with the exponent of iteration i
+        lt_pc, lt_cp, prior_p, L2_p = dev(np.inf if a else -np.inf, 0.0), dev(0.0, 0.0), dev(0.0), dev(0.0, 0.0)
+        logpi_c, L2_c, prior_c = dev(0.0, 0.0), dev(0.0, 0.0), dev(0.0)
+        acc = torch.empty(1, dtype=torch.int32, device="cuda")
+        ops.pxmala_accept(lt_pc, lt_cp, prior_p, L2_p, 1.0, logpi_c, L2_c, prior_c, acc, d, True, lmda, u=np.array([0.5]), it=i)
         assert int(acc[0]) == int(a)
         np.testing.assert_allclose(float(d[0]), g["tune_seq"][i], rtol=1e-14)
 

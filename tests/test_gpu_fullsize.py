@@ -607,7 +607,7 @@ def test_config5_fused_weaklensing_operator_closed_form_L512():
 def test_config5_pxmala_trajectory_matches_oracle_L272():
     """A PxMALA trajectory on the KERNEL PATH of BASELINE configs[4] -- bandlimit above 256 (four-wave phi-DFT at M = 2048),
     unpaired spin-2 ring tables, the fused wavelet + weak-lensing operator with a mask and galaxy counts, the one-pass
-    `pxm_pxmala_propose` / `pxm_pxmala_accept2` kernels, two chains -- against oracle.pxmcmc_np.pxmala_run
+    `pxm_pxmala_propose` / `pxm_pxmala_accept` kernels, two chains -- against oracle.pxmcmc_np.pxmala_run
     (pxmcmc/mcmc.py:218-289) on the same injected normals and uniforms, iteration by iteration: the acceptance trace, the
     per-chain delta adaptation, BOTH calc_logtransition values of every iteration (the literal squared sum over
     ~350 k complex terms, mcmc.py:281-289: where a reduction-order difference would flip an accept), the saved samples

@@ -302,7 +302,7 @@ def test_generic_engine_graph_replay_matches_eager_loop(setting, nchains):
 
 @pytest.mark.parametrize("cplx_mat,cplx_vec", [(False, False), (False, True), (True, True)])
 def test_csr_matvec_chain_batches_are_bit_equal_to_single_chains(cplx_mat, cplx_vec):
-    """pxm_csr_matvec_batched gathers a chain batch from a chain-minor copy of the operand and carries the chains in
+    """pxm_csr_matvec with a scratch gathers a chain batch from a chain-minor copy of the operand and carries the chains in
     register blocks (8 real / 4 complex, then 4, 2, 1): every chain's sum has the order of the single-chain product, so
     the batch equals the chain-by-chain results bit for bit, for every batch size up to beyond two register blocks."""
     import scipy.sparse as sp
@@ -327,7 +327,7 @@ def test_csr_matvec_chain_batches_are_bit_equal_to_single_chains(cplx_mat, cplx_
 
 
 def test_generic_engine_complex_noise_and_identity_operators():
-    """The generic stepping engine with params.complex = True (complex Philox noise through pxm_myula_step_it) and with
+    """The generic stepping engine with params.complex = True (complex Philox noise through pxm_myula_step) and with
     the toy identity operators of BASELINE config 1: graph replay equals the eager loop bit for bit, and the imaginary
     part of the state carries noise of the expected size."""
     from pxmcmc_amd.forward import ForwardOperator

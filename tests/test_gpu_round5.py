@@ -363,7 +363,7 @@ def test_config5_one_chain_path_equals_the_two_chain_path_L512():
 def test_pxmala_fused_tail_equals_separate_calls(C):
     """pxm_pxmala_finish (deferred totals of the proposal pass + reverse transition sum and L2 in one grid + totals and
     Metropolis test in one workgroup, the iteration counter advanced inside) against the separate calls it replaces
-    (pxm_pxmala_propose totals, pxm_reduce_l2, pxm_logtransition, pxm_pxmala_accept2, pxm_counter_add): the slices are
+    (pxm_pxmala_propose totals, pxm_reduce_l2, pxm_logtransition, pxm_pxmala_accept, pxm_counter_add): the slices are
     summed by the same bodies and added in the same order, so chains, traces and both transition values are IDENTICAL --
     graph replay and eager stepping, real and complex states, 1 / 3 / 17 chains (17: more chains than waves)."""
     from pxmcmc_amd.forward import ForwardOperator
