@@ -166,7 +166,7 @@ int pxm_dwav_plan_info(pxm_dwav_plan_t plan, int* nitems, int* split_blocks, int
 int pxm_wav_set_iter_counter(pxm_wav_plan_t plan, uint64_t* counter_dev);
 int pxm_wav_release_iter_counter(pxm_wav_plan_t plan, const uint64_t* counter_dev);
 int pxm_wav_iter_counter_add(pxm_wav_plan_t plan, uint64_t inc, pxm_stream_t stream);
-/* Device status of a plan.  The wave pairs of the fused phi-DFT kernels (csrc/dft5.hip, d5_pair_sync: an LDS counter
+/* Device status of a plan.  The wave pairs of the fused phi-DFT kernels (csrc/dft_wave.h, d5_pair_sync: an LDS counter
  * per pair) wait on each other with BOUNDED spins instead of barriers.  A wait that expires does not hang the GPU -- the
  * kernel runs on with data its partner has not written -- and ORs a bit into the plan's status word; the results of
  * that launch are invalid.  The reference fails loudly on bad state (pxmcmc/mcmc.py:104-109); so does the sampler here:

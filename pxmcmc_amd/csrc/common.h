@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <complex>
 #include <cstdint>
 #include <initializer_list>
 #include <string>
@@ -102,5 +103,9 @@ struct BluesteinTables {
   std::vector<double> tw;     // [M/2][2] exp(-2 pi i k / M)
 };
 BluesteinTables make_bluestein(int n, int M_force = 0);  // M_force: a power of two >= 2n-1, 0 = smallest
+// the table math all three Bluestein units of the phi-DFT stage share, in long double: the chirp c_j, j < n, and
+// FFT_M(h) / M of the chirp filter h_j = conj(c_|j|) (j mod M), in bit-reversed or natural order
+void bluestein_chirp_spectrum(int n, int M, bool natural, std::vector<std::complex<long double>>& chirp,
+                              std::vector<std::complex<long double>>& spec);
 
 }  // namespace pxm

@@ -1,11 +1,11 @@
-// phi-DFT stage of the MW transforms: length n = 2L-1 (odd) DFTs of every ring of every chain,
-// by Bluestein's chirp-z algorithm on an in-LDS power-of-two FFT (DIF forward, bit-reversed
-// pointwise product with the pre-transformed chirp filter, DIT back -- no bit-reversal pass).
-// The stage also transposes between the image layout [c][t][p] and the ring layout
-// [m][t][c] through LDS, and carries the fused elementwise prologue/epilogue of the MYULA step
-// (residual on read, prox + Langevin update on write).
+// phi-DFT stage of the MW transforms: length n = 2L-1 (odd) DFTs of every ring of every chain.  This file holds the
+// unit selection and launch dispatch of a DftPlan (sht_core.h: DftUnit) and the radix-2 unit: Bluestein's chirp-z
+// algorithm on an in-LDS power-of-two FFT (DIF forward, bit-reversed pointwise product with the pre-transformed chirp
+// filter, DIT back -- no bit-reversal pass).
+// Every unit also transposes between the image layout [c][t][p] and the ring layout [m][t][c] through LDS, and carries
+// the fused elementwise prologue/epilogue of the MYULA step (residual on read, prox + Langevin update on write).
+#include "dft_unit.h"
 #include "elem.h"
-#include "sht_core.h"
 #include "update.h"
 
 #include <cstdlib>
@@ -136,12 +136,26 @@ __global__ void k_ring2px(DftArgs a, const double* __restrict__ G, int ncol, PxO
 }
 
 int make_dft_plan(int L, DftPlan* p) {
-  BluesteinTables b = make_bluestein(2 * L - 1);
   p->L = L;
-  p->n = b.n;
+  p->n = 2 * L - 1;
+  p->Rp = round_up(L, 16);
+  // PXM_DFT_NO_W=1: the radix-2 unit for every size; PXM_DFT_PFA=0: the pair unit's Bluestein body for n = 511 as well
+  const bool radix2_only = getenv("PXM_DFT_NO_W") != nullptr;
+  const char* pfa_env = getenv("PXM_DFT_PFA");
+  const bool pfa = !(pfa_env && atoi(pfa_env) == 0);
+  if (!radix2_only && pair_r0(p->n)) {
+    p->unit = DFT_PAIR;
+    if (const char* e = getenv("PXM_DEBUG_PAIR_SYNC_LIMIT")) p->spin_limit = (unsigned)std::max(0, atoi(e));
+    return pair_make_tables(p->n, pfa, &p->pair);
+  }
+  if (!radix2_only && p->n <= 1023) {
+    p->unit = DFT_QUAD;
+    return quad_make_tables(p->n, &p->quad);
+  }
+  p->unit = DFT_RADIX2;
+  BluesteinTables b = make_bluestein(p->n);
   p->M = b.M;
   p->logM = b.logM;
-  p->Rp = round_up(L, 16);
   // chains per workgroup: as many as fit in ~128 KB of LDS, at most 8 (128-B ring-layout segments)
   int R = 8;
   while (R > 1 && (size_t)R * b.M * 16 > 128 * 1024) R >>= 1;
@@ -156,31 +170,15 @@ int make_dft_plan(int L, DftPlan* p) {
   if ((rc = dev_upload(p->d_chirp, b.chirp.data(), b.chirp.size() * sizeof(double)))) return rc;
   if ((rc = dev_upload(p->d_bhat, b.bhat.data(), b.bhat.size() * sizeof(double)))) return rc;
   if ((rc = dev_upload(p->d_tw, b.tw.data(), b.tw.size() * sizeof(double)))) return rc;
-  // L <= 256: eight points per lane, a pair of waves per ring set (dft5.hip); PXM_DFT_NO_W=1: the radix-2 in-LDS
-  // kernels of this file for every size (independent implementation, kept as the L > 512 path and as a cross-check)
-  if (dft5_r0(b.n) && !getenv("PXM_DFT_NO_W")) {
-    rc = dft5_make_tables(b.n, &p->t5);
-    if (rc) return rc;
-    dft5_geometry(b.n, &p->R5, &p->TR5, &p->lds5);
-    p->use5 = true;
-    if (const char* e = getenv("PXM_DEBUG_PAIR_SYNC_LIMIT")) p->spin_limit = (unsigned)std::max(0, atoi(e));
-  }
-  if (b.n > 512 && b.n <= 1023 && !getenv("PXM_DFT_NO_W")) {
-    rc = dft6_make_tables(b.n, &p->t6);  // 256 < L <= 512: four waves per ring, 8 points per lane
-    if (rc) return rc;
-    p->use6 = true;
-  }
   static std::atomic<uint64_t> lds_done{0};
   return allow_dynamic_lds(lds_done, {reinterpret_cast<const void*>(k_px2ring), reinterpret_cast<const void*>(k_ring2px)});
 }
 
 void free_dft_plan(DftPlan* p) {
-  if (p->d_chirp) deferred_free(p->d_chirp);
-  if (p->d_bhat) deferred_free(p->d_bhat);
-  if (p->d_tw) deferred_free(p->d_tw);
-  if (p->t5.d_all) deferred_free(p->t5.d_all);  // (the wave kernels' tables: leaked until round 3)
-  if (p->t6.d_all) deferred_free(p->t6.d_all);
-  p->d_chirp = p->d_bhat = p->d_tw = p->t5.d_all = p->t6.d_all = nullptr;
+  for (double** d : {&p->d_chirp, &p->d_bhat, &p->d_tw, &p->pair.d_all, &p->quad.d_all}) {
+    if (*d) deferred_free(*d);
+    *d = nullptr;
+  }
 }
 
 static DftArgs make_args(const DftPlan& p) {
@@ -198,8 +196,11 @@ static DftArgs make_args(const DftPlan& p) {
 }
 
 int launch_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t stream) {
-  if (p.use5) return dft5_px2ring(p, in, G, ncol, C, stream);
-  if (p.use6) return dft6_px2ring(p, in, G, ncol, C, stream);
+  switch (p.unit) {
+    case DFT_PAIR: return pair_px2ring(p, in, G, ncol, C, stream);
+    case DFT_QUAD: return quad_px2ring(p, in, G, ncol, C, stream);
+    case DFT_RADIX2: break;
+  }
   const int Cp = ncol / 2;
   dim3 grid(p.L, (Cp + p.R - 1) / p.R), block(p.threads);
   hipLaunchKernelGGL(k_px2ring, grid, block, p.lds, stream, make_args(p), in, G, ncol, C);
@@ -208,13 +209,16 @@ int launch_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C,
 }
 
 int launch_ring2px2ring(const DftPlan& p, double* G, int ncol, const PxOut& out, int C, hipStream_t stream) {
-  if (p.use5) return dft5_ring2px(p, G, ncol, out, C, stream, true);
-  return 1;
+  PXM_REQUIRE(dft_can_fuse(p), "launch_ring2px2ring: the plan's DFT unit has no fused rings -> pixels -> rings kernel");
+  return pair_ring2px(p, G, ncol, out, C, stream, true);
 }
 
 int launch_ring2px(const DftPlan& p, const double* G, int ncol, const PxOut& out, int C, hipStream_t stream) {
-  if (p.use5) return dft5_ring2px(p, G, ncol, out, C, stream);
-  if (p.use6) return dft6_ring2px(p, G, ncol, out, C, stream);
+  switch (p.unit) {
+    case DFT_PAIR: return pair_ring2px(p, G, ncol, out, C, stream, false);
+    case DFT_QUAD: return quad_ring2px(p, G, ncol, out, C, stream);
+    case DFT_RADIX2: break;
+  }
   dim3 grid(p.L, (C + p.R - 1) / p.R), block(p.threads);
   hipLaunchKernelGGL(k_ring2px, grid, block, p.lds, stream, make_args(p), G, ncol, out, C);
   PXM_HIP(hipGetLastError());

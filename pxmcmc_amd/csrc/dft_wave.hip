@@ -1,4 +1,10 @@
-// phi-DFT stage, eight-points-per-lane path (every ring length n = 2L-1 <= 511, i.e. L <= 256).
+// phi-DFT stage, the two Bluestein units that run a ring on whole waves with eight points per lane: the pair unit (below)
+// with the grouped launches of a wavelet plan's scales, which also dispatch to the exact-length bodies of n = 511
+// (dft_pfa.h), and the quad unit (further down).  (The two share one translation unit: compiled on its own, the quad
+// unit's kernels leave the module and the inlining of the shared epilogue helpers into the fused pair kernels changes --
+// 37 spilled VGPRs in the grouped rings -> X' -> rings kernel instead of none.)
+//
+// Pair unit: a pair of waves per ring set, every ring length n = 2L-1 <= 511, i.e. L <= 256.
 //
 // Bluestein at M = 2 Mh, Mh = max(64, nextpow2(n)) = 64 r0, r0 in {1, 2, 4, 8}.  The chirped input a[j] is zero
 // above n <= Mh, so the first radix-2 (DIF) stage of the M-point transform is free: the even bins are the
@@ -9,20 +15,9 @@
 // through LDS (workgroup barrier) and each finishes FOUR of the eight elements a lane holds (epilogue, Philox).
 // 84-127 VGPR, no spills: 4 waves per SIMD -- the one-wave M = 1024 kernels of round 1 (dft3.hip, removed) held 16 points per lane at
 // 203 VGPR, 2 waves per SIMD, and were bound by VALU issue latency at that occupancy with 1.5x the instructions
-// (DESIGN.md section 9).  Inside a wave every transpose of the transform needs wave-local ordering only.
-//
-// Mh-point transform, j = j0 + r0 j1 + 8 r0 j2 (j0 < r0; j1, j2 < 8), bin k = k2 + 8 k1 + 64 k0 (k0 < r0):
-//   lane = g + 8 j1, g = j0 + r0 rho (rho = ring of the wave), registers p = j2: element j = lam + 8 r0 p of ring
-//   rho, lam = j0 + r0 j1 -- consecutive lanes hold consecutive elements;
-//   pass 1: radix 8 over j2 -> k2, twiddle W_Mh^(lam k2);         T1: lane g + 8 j1, reg k2 -> lane g + 8 k2, reg j1
-//   pass 2: radix 8 over j1 -> k1, twiddle W_(8 r0)^(j0 k1);      T2: lane g + 8 k2, reg k1 -> lane k1 + 8 k2, reg g
-//   pass 3: radix r0 over j0 -> k0 for every ring;                bin k of ring rho in reg k0 + r0 rho
-// and the mirror image back (scripts/proto_dft5.py is the lane- and register-exact numpy model of this file).
-// The transposes go through a per-wave LDS plane of 8 x 72 complex: T1 at 72 k2 + 8 j1 + g, T2 at 72 k2 + 9 k1 + g;
-// with these pitches every ds_write_b128 (8 contiguous lanes per pass) and ds_read_b128 (the four 16-lane groups
-// {0-3,12-15,20-27} ...) of both directions is bank-conflict-free.
-#include "elem.h"
-#include "sht_core.h"
+// (DESIGN.md section 9).  Inside a wave every transpose of the transform needs wave-local ordering only (dft_wave.h).
+#include "dft_unit.h"
+#include "dft_wave.h"
 #include "update.h"
 
 #include <hip/hip_ext.h>
@@ -34,30 +29,8 @@
 #include <cstring>
 #include <vector>
 
-// timing-only ablations for DESIGN.md (wrong results): 1 no Philox, 2 no table loads, 4 no LDS transposes, 8 no ring stores
-// (px2ring6), 16 no input loads (dft6 kernels), 32 no pixel stores (ring2px6)
-#ifndef PXM_D5_ABLATE
-#define PXM_D5_ABLATE 0
-#endif
-
 namespace pxm {
 
-#if PXM_D5_ABLATE & 2
-#define D5_TAB(EXPR) (double2{0.8, 0.6})
-#else
-#define D5_TAB(EXPR) (EXPR)
-#endif
-
-#if PXM_D5_ABLATE & 4
-#define D5_PW(DST, V) ((void)0)
-#define D5_PR(V, SRC) ((void)0)
-#else
-#define D5_PW(DST, V) (DST) = (V)
-#define D5_PR(V, SRC) (V) = (SRC)
-#endif
-
-constexpr int D5_PLANE = 8 * 72;  // complex elements of one wave's transpose plane
-constexpr int D5_TW = 512;        // LDS copy of the pass twiddles: tw1 rows k = 1..7 ([7][64]) then wt ([8][8])
 constexpr int D5_RMAX = 4;        // most chains (units: ring sets) per workgroup; the launch bound of the kernels
 
 struct Dft5Args {
@@ -89,198 +62,6 @@ struct Dft5Group {
   int pfa_passes;    // ... and the ring pairs a workgroup of that body handles one after the other (1 or 2)
 };
 
-// Workgroup barrier of these kernels: every exchange between waves goes through LDS, so only the LDS counter has to
-// drain before the barrier.  __syncthreads() is fence + s_barrier = s_waitcnt vmcnt(0) lgkmcnt(0): it also waited
-// for every global load AND STORE in flight -- the stores of the updated coefficients sat in front of the exchange
-// barrier of the forward transform, the ring stores of a chain group in front of nothing at all.  Global memory needs
-// no intra-kernel ordering here: a workgroup only re-reads global data it has not written (the in-place ring stores
-// come after every ring load of the workgroup has been consumed into LDS).
-__device__ __forceinline__ void d5_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Synchronisation of the TWO waves of a ring set (the even- and odd-bin halves exchange their shares through LDS):
-// an LDS counter per wave pair instead of a workgroup barrier.  With s_barrier the four ring sets of a workgroup moved
-// in lock-step -- all eight waves hit the LDS in the same phase and the vector ALUs in the next -- although only the
-// pairs exchange anything between the staging barriers; decoupled, the pairs drift apart and one pair's transposes
-// overlap another's butterflies.  LDS operations of a wave are performed in order, so the ds_add behind the wave's
-// ds_writes publishes them.  The spin is bounded (a lost partner would otherwise hang the GPU); a wait that EXPIRES
-// sets bit PXM_STATUS_PAIR_SYNC of the owning plan's status word -- the kernel runs on with data its partner has not
-// written, and the host finds the bit wherever it already synchronises (pxm_wav_status / pxm_sht_status: the sampler
-// raises at its next save point instead of returning a silently corrupted chain).
-struct D5Sync {
-  unsigned* err;
-  unsigned limit;
-};
-__device__ __forceinline__ void d5_pair_sync(unsigned* cnt, unsigned target, int lane, const D5Sync& sy) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  unsigned spins = 0;
-  bool ready;
-  while (!(ready = __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= (int)target) &&
-         ++spins < sy.limit)
-    __builtin_amdgcn_s_sleep(1);
-  if (!ready && sy.err && lane == 0) __hip_atomic_fetch_or(sy.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ void d5_wave_sync() {
-#if PXM_D5_ABLATE & 4
-  return;
-#endif
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// v * exp(SGN i pi k / 4)
-template <int SGN>
-__device__ __forceinline__ double2 mul_w8(double2 v, int k) {
-  constexpr double s = 0.70710678118654752440;
-  switch (k & 3) {
-    case 0: return v;
-    case 1: return SGN < 0 ? double2{s * (v.x + v.y), s * (v.y - v.x)} : double2{s * (v.x - v.y), s * (v.x + v.y)};
-    case 2: return SGN < 0 ? double2{v.y, -v.x} : double2{-v.y, v.x};
-    default: return SGN < 0 ? double2{s * (v.y - v.x), -s * (v.x + v.y)} : double2{-s * (v.x + v.y), s * (v.x - v.y)};
-  }
-}
-__device__ __forceinline__ void d5_swap(double2& a, double2& b) {
-  const double2 t = a;
-  a = b;
-  b = t;
-}
-
-// in-register DFTs over consecutive registers x[B .. B + R), natural order in and out
-template <int SGN, int B>
-__device__ __forceinline__ void dft8r(double2 (&x)[8]) {
-  static_assert(B == 0, "one 8-point transform per lane");
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const double2 u = x[i], v = x[i + 4];
-    x[i] = cadd(u, v);
-    x[i + 4] = mul_w8<SGN>(csub(u, v), i);
-  }
-#pragma unroll
-  for (int h = 0; h < 8; h += 4)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const double2 u = x[h + i], v = x[h + i + 2];
-      x[h + i] = cadd(u, v);
-      x[h + i + 2] = mul_w8<SGN>(csub(u, v), 2 * i);
-    }
-#pragma unroll
-  for (int i = 0; i < 8; i += 2) {
-    const double2 u = x[i], v = x[i + 1];
-    x[i] = cadd(u, v);
-    x[i + 1] = csub(u, v);
-  }
-  d5_swap(x[1], x[4]);  // bit reversal (compile-time register renaming)
-  d5_swap(x[3], x[6]);
-}
-template <int SGN, int B>
-__device__ __forceinline__ void dft4r(double2 (&x)[8]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const double2 u = x[B + i], v = x[B + i + 2];
-    x[B + i] = cadd(u, v);
-    x[B + i + 2] = mul_w8<SGN>(csub(u, v), 2 * i);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; i += 2) {
-    const double2 u = x[B + i], v = x[B + i + 1];
-    x[B + i] = cadd(u, v);
-    x[B + i + 1] = csub(u, v);
-  }
-  d5_swap(x[B + 1], x[B + 2]);
-}
-template <int B>
-__device__ __forceinline__ void dft2r(double2 (&x)[8]) {
-  const double2 u = x[B], v = x[B + 1];
-  x[B] = cadd(u, v);
-  x[B + 1] = csub(u, v);
-}
-// pass 3 / 3': radix r0 over j0 for each of the 8 / r0 rings of the wave
-template <int SGN, int R0>
-__device__ __forceinline__ void pass3(double2 (&x)[8]) {
-  if (R0 == 8) dft8r<SGN, 0>(x);
-  if (R0 == 4) {
-    dft4r<SGN, 0>(x);
-    dft4r<SGN, 4>(x);
-  }
-  if (R0 == 2) {
-    dft2r<0>(x);
-    dft2r<2>(x);
-    dft2r<4>(x);
-    dft2r<6>(x);
-  }
-}
-
-// per-lane constants of the transposes and twiddle look-ups
-struct D5Lane {
-  int lo, hi;  // lane & 7, lane >> 3
-};
-
-// forward Mh-point transform of the wave's rings: natural order -> bins (reg k0 + r0 rho, lane k1 + 8 k2)
-template <int R0>
-__device__ __forceinline__ void d5_fwd(double2 (&z)[8], double2* plane, int lane, const D5Lane& q, const double2* tw) {
-  dft8r<-1, 0>(z);
-#pragma unroll
-  for (int k = 1; k < 8; ++k) z[k] = cmul(z[k], D5_TAB(tw[(k - 1) * 64 + lane]));
-#pragma unroll
-  for (int k = 0; k < 8; ++k) D5_PW(plane[72 * k + lane], z[k]);  // T1
-  d5_wave_sync();
-#pragma unroll
-  for (int k = 0; k < 8; ++k) D5_PR(z[k], plane[72 * q.hi + 8 * k + q.lo]);
-  d5_wave_sync();
-  dft8r<-1, 0>(z);
-  if (R0 > 1) {
-#pragma unroll
-    for (int k = 1; k < 8; ++k) z[k] = cmul(z[k], D5_TAB(tw[448 + k * 8 + (q.lo & (R0 - 1))]));  // W^(j0(g) k1)
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) D5_PW(plane[72 * q.hi + 9 * k + q.lo], z[k]);  // T2
-  d5_wave_sync();
-#pragma unroll
-  for (int k = 0; k < 8; ++k) D5_PR(z[k], plane[72 * q.hi + 9 * q.lo + k]);
-  d5_wave_sync();
-  pass3<-1, R0>(z);
-}
-
-// the mirror image: bins -> natural order (unnormalised inverse transform)
-template <int R0>
-__device__ __forceinline__ void d5_inv(double2 (&z)[8], double2* plane, int lane, const D5Lane& q, const double2* tw) {
-  pass3<+1, R0>(z);
-  if (R0 > 1) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if (k & (R0 - 1)) z[k] = cmulc(z[k], D5_TAB(tw[448 + (k & (R0 - 1)) * 8 + q.lo]));  // W^(-j0(reg) k1)
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) D5_PW(plane[72 * q.hi + 9 * q.lo + k], z[k]);  // T2'
-  d5_wave_sync();
-#pragma unroll
-  for (int k = 0; k < 8; ++k) D5_PR(z[k], plane[72 * q.hi + 9 * k + q.lo]);
-  d5_wave_sync();
-  dft8r<+1, 0>(z);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) D5_PW(plane[72 * q.hi + 8 * k + q.lo], z[k]);  // T1'
-  d5_wave_sync();
-#pragma unroll
-  for (int k = 0; k < 8; ++k) D5_PR(z[k], plane[72 * k + lane]);
-  d5_wave_sync();
-#pragma unroll
-  for (int k = 1; k < 8; ++k) z[k] = cmulc(z[k], D5_TAB(tw[(k - 1) * 64 + lane]));
-  dft8r<+1, 0>(z);
-}
-
-// cyclic convolution half: z (chirped input, natural order) -> forward transform -> filter spectrum bw -> back
-template <int R0>
-__device__ __forceinline__ void d5_conv(double2 (&z)[8], double2* plane, int lane, const D5Lane& q, const double2* tw,
-                                        const double2* __restrict__ bw) {
-  d5_fwd<R0>(z, plane, lane, q, tw);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) z[k] = cmul(z[k], D5_TAB(bw[(k & (R0 - 1)) * 64 + lane]));
-  d5_inv<R0>(z, plane, lane, q, tw);
-}
-
 // The two waves of a ring set run one half each (half 0: even bins, half 1: odd bins) and leave
 // their weighted share t_w[p] of every output element in x; d5_exchange then hands each wave the partner's share
 // of the FOUR elements it owns (p in [4 half, 4 half + 4)).
@@ -291,13 +72,11 @@ __device__ __forceinline__ void d5_dft_half(double2 (&x)[8], double2* plane, int
   const double2* __restrict__ cin = (half ? a.cO : a.cE) + jb;
   const double2* __restrict__ cout = (half ? a.dO : a.cE) + jb;
 #pragma unroll
-  for (int p = 0; p < 8; ++p) x[p] = cmul(x[p], D5_TAB(cin[8 * R0 * p]));
+  for (int p = 0; p < 8; ++p) x[p] = cmul(x[p], cin[8 * R0 * p]);
   d5_conv<R0>(x, plane, lane, q, tw, half ? a.bO : a.bE);
 #pragma unroll
-  for (int p = 0; p < 8; ++p) x[p] = cmul(x[p], D5_TAB(cout[8 * R0 * p]));
+  for (int p = 0; p < 8; ++p) x[p] = cmul(x[p], cout[8 * R0 * p]);
 }
-// lane-wise select on the (wave-uniform) half index: registers keep compile-time indices
-__device__ __forceinline__ double2 d5_sel(int half, double2 a, double2 b) { return double2{half ? a.x : b.x, half ? a.y : b.y}; }
 // The share of the partner's elements -> partner; x[0..4) <- own share + partner's share of the wave's OWN elements
 // p = 4 half + u (always kept in x[0..4): register indices stay compile-time).
 // SLOT selects one of two disjoint exchange regions of the planes (two exchanges may be in flight).
@@ -629,441 +408,9 @@ __device__ __forceinline__ void ring2px_body5(const Dft5Args& a, double* __restr
 #endif
 }
 
-
-// =============================================================================================================
-// Exact-length path for n = 511 (bandlimit 256): ONE wave per ring unit, Good-Thomas 7 x 73 + Rader over 8 x 9 (dft_pfa.h).
-// Workgroup = 8 waves = two ring groups of four waves (one ring x four chain slots each); a group stages its ring in LDS
-// (64-B segments of the ring arrays) and synchronises through its own LDS counter, every transpose of the transform is
-// local to a wave.  Every launch of a 511-point scale on eight-slot lines takes these bodies (fused rings -> X' -> rings,
-// plain rings -> pixels, pixels -> rings; grouped and single-scale); PXM_DFT_PFA=0 at plan creation keeps the Bluestein
-// unit for A/B runs and the unit-against-unit test; the narrow arrays of one-chain plans keep it too.
-// =============================================================================================================
 }  // namespace pxm
 #include "dft_pfa.h"
 namespace pxm {
-
-struct PfaTabs {
-  const uint16_t* gat;   // [64][8]  byte offset (16 k) of element k = gat(lane, q8) of the S1 layout
-  const uint16_t* kidx;  // [80][8]  byte offset (16 k) of output k(instance, k1), rows 0..72
-  const double2* B2;     // [8][9]
-};
-
-// stage of the exact-length body: [chain slot][k] per ring, rows of 514 slots.  The units gather / scatter pseudo-random k of
-// ONE chain slot: with the chain innermost (slot 4 k + r, as in the Bluestein bodies) a wave would touch 4 of the 16 bank
-// groups only (190 / 329 instead of ~94 / ~157 LDS cycles per gather / scatter, scripts/dev/proto_pfa511.py); 514 = 2 mod 8
-// keeps the cooperative fill (thread -> (chain, k): 4 chains x 2 k per group of eight lanes) free of write conflicts.
-constexpr int PFA_STAGE_S = 514;
-static_assert(4 * PFA_STAGE_S <= 4 * PFA_PLANE, "a ring group's stage fits in its four planes");
-
-// Synchronisation of the FOUR waves of a ring group (one ring, four chain slots) through an LDS counter, as d5_pair_sync does for
-// a wave pair: the two ring groups of a workgroup share nothing but the read-only tables, so each runs at its own pace -- a
-// workgroup barrier made every phase wait for the slowest of eight waves (7-10 us between a unit's last transform and the
-// end of its workgroup in the trace build).  Bounded spin; an expiry sets the plan's PXM_STATUS_PAIR_SYNC bit.
-__device__ __forceinline__ void pfa_group_sync(unsigned* cnt, unsigned target, int lane, const D5Sync& sy) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  unsigned spins = 0;
-  bool ready;
-  while (!(ready = __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= (int)target) &&
-         ++spins < sy.limit)
-    __builtin_amdgcn_s_sleep(1);
-  if (!ready && sy.err && lane == 0) __hip_atomic_fetch_or(sy.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("" ::: "memory");
-}
-
-// bxw: workgroup index along the rings; the workgroup takes the ring pairs bxw * passes + ps, ps < passes, one after the
-// other (passes = 2: half as many workgroups -- with one such workgroup per CU the latency-bound workgroups of the small
-// scales are resident from the start of the launch instead of forming a second round).
-template <bool RING_OUT, bool N64>
-__device__ __forceinline__ void ring2px_body_pfa(const Dft5Args& a, const PfaTabs& pt, double* __restrict__ G, int ncol,
-                                                 const PxOut& out, int C, int bxw, int by, int passes, double2* lds5) {
-  if ((by << 2) >= C) return;
-#ifdef PXM_D5_TRACE
-  unsigned long long d5_stamp[7] = {0, 0, 0, 0, 0, 0, 0};
-  unsigned long long d5_t0 = wall_clock64();
-#endif
-  constexpr int n = PFA_N, R = 4, S = PFA_STAGE_S;
-  // Everything derived from the thread id is formed from an OPAQUE copy of it, once in front of the pass loop and again at the top
-  // of every pass: hoisted out of the loop as invariants these values (lane roles, LDS and global bases) stay live through the
-  // whole pass and cost 65-90 spilled registers at the 128-VGPR budget.
-#define PXM_PFA_THREAD_SETUP                                                                                              \
-  int tid = threadIdx.x;                                                                                                  \
-  asm volatile("" : "+v"(tid));                                                                                           \
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;                                             \
-  const int r = wave & 3, grp = wave >> 2; /* chain slot of the unit; ring group (waves 0-3 / 4-7: one ring each per pass) */ \
-  const int c0 = by * R, ch = c0 + r;                                                                                     \
-  const int Cp = ncol >> 1;                                                                                               \
-  double2* stage = lds5 + grp * (4 * PFA_PLANE); /* the group's stage aliases the group's own four planes */              \
-  double2* plane = lds5 + wave * PFA_PLANE;                                                                               \
-  double2* B2l = lds5 + 8 * PFA_PLANE;                                                                                    \
-  const double2* const logt = B2l + 72;                                                                                   \
-  const double2* const sct = B2l + 72 + NOISE_LOG_N;                                                                      \
-  unsigned* const gcnt = reinterpret_cast<unsigned*>(B2l + 72 + NOISE_LOG_N + 256) + grp;                                 \
-  const int j1m = lane >> 3;                                                                                              \
-  const int x0k = (73 * (j1m < 7 ? j1m : 6)) % n; /* element j2 = 0 of the lane's S2 ring role */                         \
-  const int mstride = a.Rp * Cp;                  /* complex elements between consecutive m */                            \
-  /* ring <-> stage: thread of the group -> (chain rr, k = kq + 64 i), 64-B segments of the ring arrays */                 \
-  const int rr = tid & (R - 1), kq = (tid & 255) >> 2;                                                                    \
-  const bool cv = c0 + rr < Cp;                                                                                           \
-  double2* const Gc = reinterpret_cast<double2*>(G) + c0 + rr;
-#define PXM_PFA_RING_LOAD(TT)                                                                                             \
-  { /* all eight loads of the thread in flight together */                                                                \
-    const int tt_ = (TT);                                                                                                 \
-    const bool rv_ = cv && tt_ < a.L;                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                                       \
-      const int k = kq + 64 * i;                                                                                          \
-      v[i] = double2{0.0, 0.0};                                                                                           \
-      if (rv_ && k < n) v[i] = Gc[((k < a.L) ? k + a.L - 1 : k - a.L) * mstride + tt_ * Cp];                              \
-    }                                                                                                                     \
-  }
-  double2 v[8];
-  unsigned epoch = 0;
-  const D5Sync sy{a.err, a.spin_limit};
-  {
-    PXM_PFA_THREAD_SETUP
-    (void)ch; (void)stage; (void)plane; (void)logt; (void)sct; (void)gcnt; (void)x0k; (void)lane;
-    if (tid < 72) B2l[tid] = pt.B2[tid];
-    // fp64 noise: LDS copies of the two Box-Muller tables (129 + 256 entries behind the filter spectrum); behind them the two
-    // group counters: 81 056 B per workgroup
-#if !defined(PXM_NOISE_F64_POLY)
-    if (N64 && out.X && !out.noise && tid < NOISE_LOG_N + 256)  // (385 entries, 512 threads)
-      B2l[72 + tid] = tid < NOISE_LOG_N ? reinterpret_cast<const double2*>(&NOISE_LOG_TAB[0][0])[tid]
-                                        : reinterpret_cast<const double2*>(&NOISE_SINCOS_TAB[0][0])[tid - NOISE_LOG_N];
-#endif
-    if (tid < 2) reinterpret_cast<unsigned*>(B2l + 72 + NOISE_LOG_N + 256)[tid] = 0;
-    PXM_PFA_RING_LOAD((bxw * passes) * 2 + grp)
-  }
-  d5_barrier();  // the tables and the counters are in place (the only workgroup barrier of this body)
-#pragma nounroll
-  for (int ps = 0; ps < passes; ++ps) {
-  PXM_PFA_THREAD_SETUP
-  const int t = (bxw * passes + ps) * 2 + grp;
-  const bool tv = t < a.L;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {  // conjugated: inverse DFT by conjugation
-    const int k = kq + 64 * i;
-    if (k < n) stage[rr * S + k] = double2{v[i].x, -v[i].y};
-  }
-  pfa_group_sync(gcnt, epoch += 4, lane, sy);
-  PXM_D5_STAMP(0)  // ring staged
-  double2 z[8], o1[7], o2[7];
-  double2 x0;
-  {
-    const char* sb = reinterpret_cast<const char*>(stage + r * S);
-    const uint4 gv = reinterpret_cast<const uint4*>(pt.gat)[lane];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) z[q] = *reinterpret_cast<const double2*>(sb + pfa_u16(gv, q));
-    x0 = *reinterpret_cast<const double2*>(sb + 16 * x0k);
-  }
-  pfa_group_sync(gcnt, epoch += 4, lane, sy);  // the stage is dead: the planes may be written
-  PXM_D5_STAMP(1)  // unit gathered
-  pfa511_core(z, x0, o1, o2, plane, B2l, lane);
-  PXM_D5_STAMP(2)  // inverse transform done
-  // natural order in the plane: slot k = y[k]
-  {
-    char* pb_ = reinterpret_cast<char*>(plane);
-    const uint4 kv1 = reinterpret_cast<const uint4*>(pt.kidx)[lane];
-    const uint4 kv2 = reinterpret_cast<const uint4*>(pt.kidx)[64 + (lane < 9 ? lane : 8)];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) D5_PW(*reinterpret_cast<double2*>(pb_ + pfa_u16(kv1, k)), o1[k]);
-    if (lane < 9) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) D5_PW(*reinterpret_cast<double2*>(pb_ + pfa_u16(kv2, k)), o2[k]);
-    }
-    d5_wave_sync();
-  }
-  // The lane's eight elements lane + 64 p go through the epilogue FOUR at a time, from the plane and back into it (the
-  // natural-order plane is the input of the second transform's gather): never more than four elements in registers
-  // beside the epilogue's operands, as in the Bluestein body.
-  const bool act = ch < C && tv;
-  const int64_t e0 = out.ring0 + (int64_t)t * n + lane;  // the lane's first element; p advances by 64
-  const int64_t ce0 = (int64_t)ch * out.chain_stride + e0;
-  const bool last_ok = lane < 63;                        // element lane + 448 exists
-  const uint64_t it_eff = out.iter + (out.iter_dev ? *out.iter_dev : 0);
-  const int ch_s = __builtin_amdgcn_readfirstlane(ch);
-#pragma unroll
-  for (int g0 = 0; g0 < 8; g0 += 4) {
-    double2 x[4];
-    // (lane 63, p = 7: slot 511, never an element.  In the update branch the four elements stay in the plane until the noise
-    // has been drawn: 16 registers fewer across the fp64 Box-Muller)
-    if (!N64 || !(act && out.X)) {  // (f32 noise: reading early is the allocation without spills)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) D5_PR(x[u], plane[lane + 64 * (g0 + u)]);
-    }
-    if (act && out.X) {  // fused prox + MYULA update (pxmcmc/mcmc.py:185-201, prior.py:49-50); see ring2px_body5
-      double2 xs[4], wn[4], wph[4];
-      double Ts[4];
-      int eo[4];  // element offsets from e0 (32 bits: a ring is 511 elements)
-      // operand loads FIRST, the noise of the four elements while they are in flight (this body holds four elements, not
-      // eight, beside the epilogue's operands: the fp64 Box-Muller fits between the loads and their use without spills --
-      // in ring2px_body5 that order cost 250 spilled registers)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) eo[u] = (g0 + u < 7 || last_ok) ? 64 * (g0 + u) : -lane;  // (else: the ring's element 0)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) xs[u] = reinterpret_cast<const double2*>(out.X)[ce0 + eo[u]];
-      if (out.T) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) Ts[u] = out.T[e0 + eo[u]];
-      } else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) Ts[u] = out.T_scalar;
-      }
-      if (out.noise) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) wn[u] = px_noise_load(out, ch, e0 + eo[u]);
-      } else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) wn[u] = double2{0.0, 0.0};
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#if !(PXM_D5_ABLATE & 1) && !defined(PXM_NOISE_F64_POLY)
-      // fp64 noise of a chain pair (the benchmarked mode): the Philox bits of the four elements first -- four independent
-      // integer chains --, then the fp64 Box-Muller step element by element (its ~40 live registers are why the elements
-      // are not interleaved there)
-      if (N64 && !out.noise && out.mode == PXM_MODE_REAL_PAIRS && !(out.chain0 & 1)) {
-        uint4 pbits[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          pbits[u] = philox_bits(out.seed + PXM_PAIR_TWEAK, (out.chain0 >> 1) + ch_s, (uint64_t)(e0 + 64 * (g0 + u)), it_eff);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const NormalPair q_ = normal_pair_from_bits_tabs(pbits[u], logt, sct);
-          wph[u] = double2{q_.z0, q_.z1};
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      } else
-#endif
-      {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        wph[u] = double2{0.0, 0.0};
-#if !(PXM_D5_ABLATE & 1)
-#if defined(PXM_NOISE_F64_POLY)
-        if (!out.noise) wph[u] = px_noise_philox_t<N64>(out, ch_s, e0 + 64 * (g0 + u), it_eff);
-#else
-        if (!out.noise) wph[u] = N64 ? px_noise_philox_tabs(out, ch_s, e0 + 64 * (g0 + u), it_eff, logt, sct)
-                                     : px_noise_philox_t<false>(out, ch_s, e0 + 64 * (g0 + u), it_eff);
-#endif
-#endif
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      }
-      if (N64) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) D5_PR(x[u], plane[lane + 64 * (g0 + u)]);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int p = g0 + u;
-        if (p == 7 && !last_ok) {
-          x[u] = double2{0.0, 0.0};
-          continue;
-        }
-        const double2 y{x[u].x, -x[u].y};
-        const double2 w = out.noise ? wn[u] : wph[u];
-        x[u] = px_update(out, xs[u], Ts[u], y, w);
-        reinterpret_cast<double2*>(out.f)[ce0 + 64 * p] = x[u];
-      }
-    } else if (act) {  // plain / gathered output and the residual that goes back to the rings
-      bool ok[4];
-      int64_t ev[4];
-      double2 yv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        ok[u] = g0 + u < 7 || last_ok;
-        ev[u] = ok[u] ? e0 + 64 * (g0 + u) : out.ring0 + (int64_t)t * n;
-        yv[u] = double2{x[u].x, -x[u].y};
-      }
-      px_out_store_n<4>(out, ch, ev, yv, ok);
-      if (out.rdata) {
-        double2 rd[4], rc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) rd[u] = reinterpret_cast<const double2*>(out.rdata)[ev[u]];
-        if (out.rinvcov_complex) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) rc[u] = reinterpret_cast<const double2*>(out.rinvcov)[ev[u]];
-        } else {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) rc[u] = double2{out.rinvcov[ev[u]], 0.0};
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const double2 d = csub(yv[u], rd[u]);
-          yv[u] = out.rinvcov_complex ? cmul(rc[u], d) : double2{rc[u].x * d.x, rc[u].x * d.y};
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) x[u] = ok[u] ? yv[u] : double2{0.0, 0.0};
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) x[u] = double2{0.0, 0.0};  // padding chains / rings: their rings are kept at zero
-    }
-    if (RING_OUT) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) D5_PW(plane[lane + 64 * (g0 + u)], x[u]);
-    }
-#ifdef PXM_D5_TRACE
-    if (g0 == 0) PXM_D5_STAMP(3) else PXM_D5_STAMP(4)  // first / second half of the epilogue done
-#endif
-  }
-  if (!RING_OUT) {  // plain rings -> pixels: the pass ends here; the next ring may be staged once every plane of the group is dead
-    PXM_PFA_RING_LOAD(ps + 1 < passes ? (bxw * passes + ps + 1) * 2 + grp : a.L)
-    if (ps + 1 < passes) pfa_group_sync(gcnt, epoch += 4, lane, sy);
-    continue;
-  }
-  // ---- forward transform of the updated ring: natural order -> S1 layout through the plane
-  d5_wave_sync();
-  {
-    const char* pb_ = reinterpret_cast<const char*>(plane);
-    const uint4 gv = reinterpret_cast<const uint4*>(pt.gat)[lane];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) D5_PR(z[q], *reinterpret_cast<const double2*>(pb_ + pfa_u16(gv, q)));
-    D5_PR(x0, plane[x0k]);
-  }
-  d5_wave_sync();
-  pfa511_core(z, x0, o1, o2, plane, B2l, lane);
-  PXM_D5_STAMP(5)  // forward transform done
-  pfa_group_sync(gcnt, epoch += 4, lane, sy);  // every plane of the group is dead: its stage may be written
-  {
-    char* sb = reinterpret_cast<char*>(stage + r * S);
-    const uint4 kv1 = reinterpret_cast<const uint4*>(pt.kidx)[lane];
-    const uint4 kv2 = reinterpret_cast<const uint4*>(pt.kidx)[64 + (lane < 9 ? lane : 8)];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) *reinterpret_cast<double2*>(sb + pfa_u16(kv1, k)) = o1[k];
-    if (lane < 9) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) *reinterpret_cast<double2*>(sb + pfa_u16(kv2, k)) = o2[k];
-    }
-  }
-  // the next ring's loads are in flight across the stores (unconditional assignment -- zeros behind the last pass: a conditional
-  // one would keep the eight registers of v live through the whole pass)
-  PXM_PFA_RING_LOAD(ps + 1 < passes ? (bxw * passes + ps + 1) * 2 + grp : a.L)
-  pfa_group_sync(gcnt, epoch += 4, lane, sy);
-  PXM_D5_STAMP(6)  // results in the stage
-  if (cv && tv) {  // stage -> G rows of the ring
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int k = kq + 64 * i;
-      if (k < n) Gc[((k < a.L) ? k + a.L - 1 : k - a.L) * mstride + t * Cp] = stage[rr * S + k];
-    }
-  }
-  if (ps + 1 < passes) pfa_group_sync(gcnt, epoch += 4, lane, sy);  // the stage has been read: the next ring may be staged
-#ifdef PXM_D5_TRACE
-  if (tid == 0 && g_dft_trace) {
-    const unsigned long long slot = atomicAdd(g_dft_trace + 1, 1ull);
-    unsigned long long* rr_ = g_dft_trace + 8 + 8 * 4096 + 8 * slot;
-    rr_[0] = 9;  // six phase stamps + the end of the pass (bx / by are not recorded for this body)
-    for (int k = 0; k < 6; ++k) rr_[1 + k] = d5_stamp[k] - d5_t0;
-    rr_[7] = wall_clock64() - d5_t0;
-    d5_t0 = wall_clock64();
-  }
-#endif
-  }  // passes
-#undef PXM_PFA_THREAD_SETUP
-#undef PXM_PFA_RING_LOAD
-}
-
-// pixels -> rings of the same unit (the plain forward phi-DFT of a 511-point scale: px2ring_body5's job): every wave loads its
-// ring in natural order straight into its plane, gathers the S1 layout, transforms, and the four waves of a ring group put the
-// result through the group's stage into 64-B segments of the ring array.  ZFILL as in PXM_D5_STORE_RINGS(true): the last live
-// chain group also zeroes the padding slots of its (m, ring) lines.
-__device__ __forceinline__ void px2ring_body_pfa(const Dft5Args& a, const PfaTabs& pt, const PxIn& in, double* __restrict__ G, int ncol,
-                                                 int C, int bxw, int by, int passes, double2* lds5) {
-  if ((by << 2) >= C) return;
-  constexpr int n = PFA_N, R = 4, S = PFA_STAGE_S;
-  unsigned epoch = 0;
-  const D5Sync sy{a.err, a.spin_limit};
-  {
-    const int tid = threadIdx.x;
-    double2* B2l = lds5 + 8 * PFA_PLANE;
-    if (tid < 72) B2l[tid] = pt.B2[tid];
-    if (tid < 2) reinterpret_cast<unsigned*>(B2l + 72 + NOISE_LOG_N + 256)[tid] = 0;
-  }
-  d5_barrier();
-#pragma nounroll
-  for (int ps = 0; ps < passes; ++ps) {
-    int tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));  // (see ring2px_body_pfa: nothing derived from the thread id is hoisted out of the pass loop)
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int r = wave & 3, grp = wave >> 2;
-    const int c0 = by * R, ch = c0 + r;
-    const int Cp = ncol >> 1;
-    double2* stage = lds5 + grp * (4 * PFA_PLANE);
-    double2* plane = lds5 + wave * PFA_PLANE;
-    const double2* B2l = lds5 + 8 * PFA_PLANE;
-    unsigned* const gcnt = reinterpret_cast<unsigned*>(lds5 + 8 * PFA_PLANE + 72 + NOISE_LOG_N + 256) + grp;
-    const int j1m = lane >> 3;
-    const int x0k = (73 * (j1m < 7 ? j1m : 6)) % n;
-    const int t = (bxw * passes + ps) * 2 + grp;
-    const bool tv = t < a.L;
-    const bool act = ch < C && tv;
-    const int64_t e_ring = in.ring0 + (int64_t)(tv ? t : 0) * n;
-#pragma unroll
-    for (int g0 = 0; g0 < 8; g0 += 4) {  // the lane's elements lane + 64 p, four at a time (see px2ring_body5)
-      int64_t ev[4];
-      bool ok[4];
-      double2 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int j = lane + 64 * (g0 + u);
-        ok[u] = act && j < n;
-        ev[u] = e_ring + (j < n ? j : 0);
-      }
-      if (ch < C) px_in_load_n<4>(in, ch, ev, ok, v);
-      else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = double2{0.0, 0.0};
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) D5_PW(plane[lane + 64 * (g0 + u)], v[u]);  // (lane 63, p = 7: slot 511, a zero)
-    }
-    d5_wave_sync();
-    double2 z[8], o1[7], o2[7];
-    double2 x0;
-    {
-      const char* pb_ = reinterpret_cast<const char*>(plane);
-      const uint4 gv = reinterpret_cast<const uint4*>(pt.gat)[lane];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) D5_PR(z[q], *reinterpret_cast<const double2*>(pb_ + pfa_u16(gv, q)));
-      D5_PR(x0, plane[x0k]);
-    }
-    d5_wave_sync();
-    pfa511_core(z, x0, o1, o2, plane, B2l, lane);
-    pfa_group_sync(gcnt, epoch += 4, lane, sy);  // every plane of the group is dead: its stage may be written
-    {
-      char* sb = reinterpret_cast<char*>(stage + r * S);
-      const uint4 kv1 = reinterpret_cast<const uint4*>(pt.kidx)[lane];
-      const uint4 kv2 = reinterpret_cast<const uint4*>(pt.kidx)[64 + (lane < 9 ? lane : 8)];
-#pragma unroll
-      for (int k = 0; k < 7; ++k) *reinterpret_cast<double2*>(sb + pfa_u16(kv1, k)) = o1[k];
-      if (lane < 9) {
-#pragma unroll
-        for (int k = 0; k < 7; ++k) *reinterpret_cast<double2*>(sb + pfa_u16(kv2, k)) = o2[k];
-      }
-    }
-    pfa_group_sync(gcnt, epoch += 4, lane, sy);
-    {  // stage -> G rows of the ring
-      const int rr = tid & (R - 1), kq = (tid & 255) >> 2;
-      const int mstride = a.Rp * Cp;
-      double2* const Gc = reinterpret_cast<double2*>(G) + c0 + rr;
-      const bool zf = c0 + R >= C;
-      if (c0 + rr < Cp && tv) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int k = kq + 64 * i;
-          if (k < n) {
-            double2* line = Gc + ((k < a.L) ? k + a.L - 1 : k - a.L) * mstride + t * Cp;
-            *line = stage[rr * S + k];
-            if (zf)
-              for (int zz = R; c0 + rr + zz < Cp; zz += R) line[zz] = double2{0.0, 0.0};
-          }
-        }
-      }
-    }
-    if (ps + 1 < passes) pfa_group_sync(gcnt, epoch += 4, lane, sy);  // the stage has been read
-  }
-}
 
 template <int R0>
 __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_px2ring5(Dft5Args a, PxIn in, double* __restrict__ G,
@@ -1151,7 +498,7 @@ __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_ring2px_group5(const Dft5G
 #endif
   PXM_D5_GROUP_DECODE
   out.ring0 = g.ring0;
-  if (g.r0 == 9) {  // exact-length unit (entries of the lists with the workgroup shape of that unit: DftGroupList::d_fused)
+  if (g.r0 == 9) {  // exact-length unit (the entries of 511-point scales on eight-slot lines: workgroups of that unit)
     const double* pb = ws + g.tbase + g.pfa_off;
     const PfaTabs pt{reinterpret_cast<const uint16_t*>(pb + PFA_TAB_GAT), reinterpret_cast<const uint16_t*>(pb + PFA_TAB_KIDX),
                      reinterpret_cast<const double2*>(pb + PFA_TAB_B2)};
@@ -1159,7 +506,6 @@ __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_ring2px_group5(const Dft5G
     // latency-bound workgroups of the small scales are resident from the start instead of forming a second round)
     ring2px_body_pfa<RING_OUT, N64>(a, pt, G, ncol, out, C, bx, by, g.pfa_passes, lds5);
   }
-#ifndef PXM_D5_ONLY_PFA  // (development aid: an assembly listing of the exact-length body alone)
   switch (g.r0) {
     case 9: break;  // (done above)
     case 8: ring2px_body5<8, RING_OUT, N64>(a, G, ncol, out, C, bx, by, lds5); break;
@@ -1167,7 +513,6 @@ __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_ring2px_group5(const Dft5G
     case 2: ring2px_body5<2, RING_OUT, N64>(a, G, ncol, out, C, bx, by, lds5); break;
     default: ring2px_body5<1, RING_OUT, N64>(a, G, ncol, out, C, bx, by, lds5); break;
   }
-#endif
 #ifdef PXM_D5_TRACE
   if (threadIdx.x == 0 && g_dft_trace) {
     unsigned hw, xcc;
@@ -1205,17 +550,18 @@ __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_px2ring_group5(const Dft5G
 }
 
 // =============================================================================================================
-// Four waves per ring: 512 < n <= 1023 (256 < L <= 512), M = 2048 = 4 x 512.  The chirped input is zero above
-// n < 1024 = 2 x 512, so the first radix-4 (DIF) stage needs two inputs per output: wave w takes the bins 4k'+w as
-// the 512-point transform of
+// Quad unit: four waves per ring for 512 < n <= 1023 (256 < L <= 512), Bluestein at M = 2048 = 4 x 512.
+// The chirped input is zero above n < 1024 = 2 x 512, so the first radix-4 (DIF) stage needs two inputs per output:
+// wave w takes the bins 4k'+w as the 512-point transform of
 //     b_w[j'] = (a[j'] + (-i)^w a[j'+512]) W_2048^(j' w),        j' < 512,
-// runs the same 8-points-per-lane convolution core as above on them (d5_conv<8>), and
+// runs the same 8-points-per-lane convolution core as the pair unit on them (dft_wave.h: d5_conv<8>), and
 //     conv[j' + 512 q] = sum_w i^(q w) W_2048^(-j' w) y_w[j'],   q = 0, 1.
 // The four waves reduce their weighted shares in two pair exchanges through LDS (w <-> w^1, then w <-> w^2); each
 // wave finishes 4 of the 16 elements a lane position covers: p in {pb, pb+1}, pb = 4 (w & 1) + 2 (w >> 1), both
 // halves q.  Tables (zero-padded, no j < n tests on the transform path): cA_w = c W^(j'w), cB_w = (-i)^w c[.+512]
 // W^(j'w) on input, dA_w = c W^(-j'w), dB_w = i^w c[.+512] W^(-j'w) on output.  scripts/proto_dft5.py: dft_quad.
 // =============================================================================================================
+
 struct Dft6Args {
   int L, n, Rp;
   int lgR;                           // log2 of the chains per workgroup (4 waves each)
@@ -1254,7 +600,7 @@ __device__ __forceinline__ void d6_transform(double2 (&xl)[8], const double2 (&x
   const double2* __restrict__ dA = a.dA + w * 512 + lane;
   const double2* __restrict__ dB = a.dB + w * 512 + lane;
 #pragma unroll
-  for (int p = 0; p < 8; ++p) xl[p] = cadd(cmul(xl[p], D5_TAB(cA[64 * p])), cmul(xh[p], D5_TAB(cB[64 * p])));
+  for (int p = 0; p < 8; ++p) xl[p] = cadd(cmul(xl[p], cA[64 * p]), cmul(xh[p], cB[64 * p]));
   d5_conv<8>(xl, plane, lane, q, tw, a.bQ + w * 512);
   // ---- pair exchange 1 (w <-> w ^ 1): keep p in [4 wa, 4 wa + 4), send the shares of the other four
   double2 su[4], sv[4];
@@ -1262,10 +608,10 @@ __device__ __forceinline__ void d6_transform(double2 (&xl)[8], const double2 (&x
   for (int i = 0; i < 4; ++i) {
     const double2 yk = d5_sel(wa, xl[4 + i], xl[i]), ys = d5_sel(wa, xl[i], xl[4 + i]);
     const int pk = 64 * (4 * wa + i), ps = 64 * (4 * (1 - wa) + i);
-    su[i] = cmul(yk, D5_TAB(dA[pk]));
-    sv[i] = cmul(yk, D5_TAB(dB[pk]));
-    plane[64 * i + lane] = cmul(ys, D5_TAB(dA[ps]));
-    plane[256 + 64 * i + lane] = cmul(ys, D5_TAB(dB[ps]));
+    su[i] = cmul(yk, dA[pk]);
+    sv[i] = cmul(yk, dB[pk]);
+    plane[64 * i + lane] = cmul(ys, dA[ps]);
+    plane[256 + 64 * i + lane] = cmul(ys, dB[ps]);
   }
   d5_barrier();
 #pragma unroll
@@ -1319,15 +665,11 @@ __global__ __launch_bounds__(256 << LGR, 4) void k_px2ring6(Dft6Args a, PxIn in,
       ok[u] = ch < C && j < n;
       ev[u] = in.ring0 + (int64_t)t * n + (j < n ? j : 0);
     }
-#if PXM_D5_ABLATE & 16
-    for (int u = 0; u < 4; ++u) v[u] = double2{1e-3 * lane, 1e-3 * u};
-#else
     if (ch < C) px_in_load_n<4>(in, ch, ev, ok, v);
     else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = double2{0.0, 0.0};
     }
-#endif
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int j = lane + 64 * (2 * w + (u >> 1)) + 512 * (u & 1);
@@ -1358,12 +700,6 @@ __global__ __launch_bounds__(256 << LGR, 4) void k_px2ring6(Dft6Args a, PxIn in,
     const int rr = threadIdx.x & (R - 1), kq = threadIdx.x >> lgR, kstep = 256 /* workgroups of 256 R threads */;
     const int mstride = a.Rp * Cp;
     double2* Gc = reinterpret_cast<double2*>(G) + c0 + rr;
-#if PXM_D5_ABLATE & 8
-    double2 sink{0.0, 0.0};
-    if (c0 + rr < Cp)
-      for (int k = kq; k < n; k += kstep) sink = cadd(sink, stage[PXM_D6_SLOT(k, rr)]);
-    if (sink.x == 1.2345e300) Gc[t * Cp] = sink;
-#else
     const bool zf = c0 + R >= C;  // last live chain group: the padding slots of the line are zeroed (whole 128-B lines)
     if (c0 + rr < Cp)
       for (int k = kq; k < n; k += kstep) {
@@ -1371,7 +707,6 @@ __global__ __launch_bounds__(256 << LGR, 4) void k_px2ring6(Dft6Args a, PxIn in,
         *line = stage[PXM_D6_SLOT(k, rr)];
         if (zf) for (int z = R; c0 + rr + z < Cp; z += R) line[z] = double2{0.0, 0.0};
       }
-#endif
   }
 }
 
@@ -1393,11 +728,7 @@ __global__ __launch_bounds__(256 << LGR, 4) void k_ring2px6(Dft6Args a, const do
       for (int u = 0; u < NB; ++u) {
         const int k = kb + u * kstep;
         v[u] = double2{0.0, 0.0};
-#if PXM_D5_ABLATE & 16
-        v[u] = double2{1e-3 * k, 1e-3 * u};
-#else
         if (cv && k < n) v[u] = Gc[((k < a.L) ? k + a.L - 1 : k - a.L) * mstride + t * Cp];
-#endif
       }
 #pragma unroll
       for (int u = 0; u < NB; ++u) {
@@ -1460,16 +791,12 @@ __global__ __launch_bounds__(256 << LGR, 4) void k_ring2px6(Dft6Args a, const do
     int64_t ev[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) ev[u] = e0 + eo[u];
-#if PXM_D5_ABLATE & 32
-    if (yv[0].x + yv[1].x + yv[2].x + yv[3].x == 1.2345e300) px_out_store_n<4>(out, ch, ev, yv, ok);
-#else
     px_out_store_n<4>(out, ch, ev, yv, ok);
-#endif
   }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-int dft5_r0(int n) {  // 0: no eight-point path for this ring length
+int pair_r0(int n) {  // 0: no pair unit for this ring length
   if (n > 512) return 0;
   int Mh = 64;
   while (Mh < n) Mh <<= 1;
@@ -1509,34 +836,13 @@ void pfa511_host_tables(uint16_t* idx, double* b2) {
     }
 }
 
-int dft5_make_tables(int n, Dft5Tables* t) {
+int pair_make_tables(int n, bool pfa, PairTables* t) {
   typedef std::complex<long double> cld;
   const long double PI_L = 3.141592653589793238462643383279502884L;
-  const int r0 = dft5_r0(n), Mh = 64 * r0, M = 2 * Mh;
+  const int r0 = pair_r0(n), Mh = 64 * r0, M = 2 * Mh;
   auto ang = [&](long double num, long double den) { return cld(cosl(-PI_L * num / den), sinl(-PI_L * num / den)); };
-  std::vector<cld> chirp(n), filt(M, cld(0, 0));
-  for (int j = 0; j < n; ++j) chirp[j] = ang((long double)(((long long)j * j) % (2LL * n)), n);
-  for (int j = 0; j < n; ++j) {
-    filt[j] = std::conj(chirp[j]);
-    if (j) filt[M - j] = std::conj(chirp[j]);
-  }
-  // FFT_M(filter) / M in long double (radix-2 DIF, then undo the bit reversal)
-  int logM = 0;
-  while ((1 << logM) < M) ++logM;
-  for (int s = M / 2; s >= 1; s >>= 1)
-    for (int g = 0; g < M; g += 2 * s)
-      for (int p = 0; p < s; ++p) {
-        const cld w = ang(2.0L * p * (M / (2 * s)), M);
-        const cld u = filt[g + p], v = filt[g + p + s];
-        filt[g + p] = u + v;
-        filt[g + p + s] = (u - v) * w;
-      }
-  std::vector<cld> bhat(M);
-  for (int i = 0; i < M; ++i) {
-    int r = 0;
-    for (int bit = 0; bit < logM; ++bit) r |= ((i >> bit) & 1) << (logM - 1 - bit);
-    bhat[r] = filt[i] / (long double)M;
-  }
+  std::vector<cld> chirp, bhat;
+  bluestein_chirp_spectrum(n, M, true, chirp, bhat);
   std::vector<double> h;
   auto put = [&](const cld& v) {
     h.push_back((double)v.real());
@@ -1566,7 +872,7 @@ int dft5_make_tables(int n, Dft5Tables* t) {
   }
   // n = 511: the tables of the exact-length unit (dft_pfa.h, scripts/dev/proto_pfa511.py) behind the Bluestein ones
   size_t o_pfa = 0;
-  if (n == PFA_N && !(getenv("PXM_DFT_PFA") && atoi(getenv("PXM_DFT_PFA")) == 0)) {
+  if (n == PFA_N && pfa) {
     o_pfa = h.size();
     h.resize(h.size() + PFA_TAB_DOUBLES);
     pfa511_host_tables(reinterpret_cast<uint16_t*>(h.data() + o_pfa + PFA_TAB_GAT), h.data() + o_pfa + PFA_TAB_B2);
@@ -1574,7 +880,6 @@ int dft5_make_tables(int n, Dft5Tables* t) {
   t->pfa_off = (int)o_pfa;
   if (int rc = dev_alloc(&t->d_all, h.size() * sizeof(double), "phi-DFT tables (8 points per lane)")) return rc;
   if (int rc = dev_upload(t->d_all, h.data(), h.size() * sizeof(double))) return rc;
-  t->bytes = h.size() * sizeof(double);
   t->r0 = r0;
   t->cE = t->d_all + o_cE;
   t->cO = t->d_all + o_cO;
@@ -1586,194 +891,174 @@ int dft5_make_tables(int n, Dft5Tables* t) {
   return 0;
 }
 
-void dft5_geometry(int n, int* R, int* TR, size_t* lds) {
-  const int r0 = dft5_r0(n), rpw = 8 / r0;
-  // chains per workgroup: 4 = 64-B segments of the ring arrays, a compile-time constant of the kernels (index
-  // arithmetic of the staging folds).  (Until round 3 PXM_DFT_R=1|2 selected smaller workgroups for A/B runs: 79 / 92 us
-  // against 72 for the grouped launch -- fewer waves per barrier do not pay for 16 / 32-B segments.)
-  *R = D5_RMAX;
-  *TR = 1;
-  const size_t planes = (size_t)(*R) * 2 * D5_PLANE * 16, stage = (size_t)rpw * n * (*R) * 16;
-  // the planes (aliased by the stage) and behind them the LDS copy of the pass twiddles; with R = 4:
-  // 8 x 9216 + 8192 = 81 920 B -- exactly two workgroups (16 waves, 4 per SIMD) in the 160 KiB of a CU
-  *lds = std::max(planes, stage) + (size_t)D5_TW * 16;
-}
+// Geometry of the pair unit: D5_RMAX = 4 chains per workgroup (64-B segments of the ring arrays, a compile-time constant of
+// the kernels: the index arithmetic of the staging folds) and one ring set per workgroup.  (Until round 3 PXM_DFT_R=1|2
+// selected smaller workgroups for A/B runs: 79 / 92 us against 72 for the grouped launch -- fewer waves per barrier do not
+// pay for 16 / 32-B segments.)  LDS: the planes of the eight waves, aliased by the stage (8 / r0 rings of n <= 64 r0
+// slots x 4 chains), and behind them the LDS copy of the pass twiddles: 8 x 9216 + 8192 = 81 920 B -- exactly two
+// workgroups (16 waves, 4 per SIMD) in the 160 KiB of a CU.
+constexpr size_t D5_LDS = (size_t)2 * D5_RMAX * D5_PLANE * 16 + (size_t)D5_TW * 16;
+static_assert((size_t)512 * D5_RMAX * 16 <= (size_t)2 * D5_RMAX * D5_PLANE * 16, "the stage of a ring set fits in the planes");
+// the exact-length body in the same workgroups: 8 planes of PFA_PLANE slots (aliased by the stage of 2 rings x 511 x 4
+// slots) + the filter spectrum, the fp64 Box-Muller tables and the group counters: 81 056 B
+static_assert(((size_t)8 * PFA_PLANE + 72 + NOISE_LOG_N + 256 + 1) * 16 <= D5_LDS, "PFA workgroup LDS");
 
-static Dft5Args dft5_args(const DftPlan& p) {
-  const Dft5Tables& t = p.t5;
+static Dft5Args pair_args(const DftPlan& p) {
+  const PairTables& t = p.pair;
   auto c = [](const double* x) { return reinterpret_cast<const double2*>(x); };
-  return Dft5Args{p.L, p.n, p.Rp, p.R5 == 4 ? 2 : (p.R5 == 2 ? 1 : 0), c(t.cE), c(t.cO), c(t.dO), c(t.tw1), c(t.wt), c(t.bE), c(t.bO),
-                  p.d_status, p.spin_limit, (t.pfa_off && p.R5 == 4) ? t.d_all + t.pfa_off : nullptr};
+  return Dft5Args{p.L, p.n, p.Rp, 2 /* log2 D5_RMAX */, c(t.cE), c(t.cO), c(t.dO), c(t.tw1), c(t.wt), c(t.bE), c(t.bO),
+                  p.d_status, p.spin_limit, t.pfa_off ? t.d_all + t.pfa_off : nullptr};
 }
 
 template <int R0>
-static int dft5_attr() {
+static int pair_attr() {
   static std::atomic<uint64_t> done{0};
   return allow_dynamic_lds(done, {reinterpret_cast<const void*>(k_px2ring5<R0>), reinterpret_cast<const void*>(k_ring2px5<R0, false, false>),
                                   reinterpret_cast<const void*>(k_ring2px5<R0, true, false>), reinterpret_cast<const void*>(k_ring2px5<R0, false, true>),
                                   reinterpret_cast<const void*>(k_ring2px5<R0, true, true>)});
 }
 
+// ring sets (workgroups) along the rings: one ring set of 8 / r0 rings each, or a ring pair of the exact-length unit
 template <int R0>
-static int px2ring5_r(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t st) {
-  if (int rc = dft5_attr<R0>()) return rc;
-  const Dft5Args da = dft5_args(p);
-  const int Cp = ncol / 2, rings = (R0 == 8 && da.pfa && ncol >= 8) ? 2 : p.TR5 * (8 / R0);  // (exact-length unit: two rings per workgroup)
-  dim3 grid((p.L + rings - 1) / rings, (Cp + p.R5 - 1) / p.R5), block(128 * p.R5);
-  hipLaunchKernelGGL((k_px2ring5<R0>), grid, block, p.lds5, st, da, in, G, ncol, C);
+static int pair_ring_blocks(const Dft5Args& a, int ncol) {
+  const int rings = (R0 == 8 && a.pfa && ncol >= 8) ? 2 : 8 / R0;
+  return (a.L + rings - 1) / rings;
+}
+
+template <int R0>
+static int pair_px2ring_r(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t st) {
+  if (int rc = pair_attr<R0>()) return rc;
+  const Dft5Args da = pair_args(p);
+  dim3 grid(pair_ring_blocks<R0>(da, ncol), (ncol / 2 + D5_RMAX - 1) / D5_RMAX), block(128 * D5_RMAX);
+  hipLaunchKernelGGL((k_px2ring5<R0>), grid, block, D5_LDS, st, da, in, G, ncol, C);
   PXM_HIP(hipGetLastError());
   return 0;
 }
 
 template <int R0>
-static int ring2px5_r(const DftPlan& p, const double* G, int ncol, const PxOut& out, int C, hipStream_t st, bool ring_out) {
-  if (int rc = dft5_attr<R0>()) return rc;
-  const int rings = (R0 == 8 && dft5_args(p).pfa && ncol >= 8) ? 2 : p.TR5 * (8 / R0);  // (exact-length unit: two rings per workgroup)
-  dim3 grid((p.L + rings - 1) / rings, (C + p.R5 - 1) / p.R5), block(128 * p.R5);
+static int pair_ring2px_r(const DftPlan& p, const double* G, int ncol, const PxOut& out, int C, hipStream_t st, bool ring_out) {
+  if (int rc = pair_attr<R0>()) return rc;
+  const Dft5Args da = pair_args(p);
+  dim3 grid(pair_ring_blocks<R0>(da, ncol), (C + D5_RMAX - 1) / D5_RMAX), block(128 * D5_RMAX);
+  double* Gw = const_cast<double*>(G);
   // (the fp64-noise instantiations only where the launch draws Philox noise in double precision)
   const bool n64 = out.X && !out.noise && out.noise64;
   if (ring_out) {
-    if (n64) hipLaunchKernelGGL((k_ring2px5<R0, true, true>), grid, block, p.lds5, st, dft5_args(p), const_cast<double*>(G), ncol, out, C);
-    else hipLaunchKernelGGL((k_ring2px5<R0, true, false>), grid, block, p.lds5, st, dft5_args(p), const_cast<double*>(G), ncol, out, C);
+    if (n64) hipLaunchKernelGGL((k_ring2px5<R0, true, true>), grid, block, D5_LDS, st, da, Gw, ncol, out, C);
+    else hipLaunchKernelGGL((k_ring2px5<R0, true, false>), grid, block, D5_LDS, st, da, Gw, ncol, out, C);
   } else {
-    if (n64) hipLaunchKernelGGL((k_ring2px5<R0, false, true>), grid, block, p.lds5, st, dft5_args(p), const_cast<double*>(G), ncol, out, C);
-    else hipLaunchKernelGGL((k_ring2px5<R0, false, false>), grid, block, p.lds5, st, dft5_args(p), const_cast<double*>(G), ncol, out, C);
+    if (n64) hipLaunchKernelGGL((k_ring2px5<R0, false, true>), grid, block, D5_LDS, st, da, Gw, ncol, out, C);
+    else hipLaunchKernelGGL((k_ring2px5<R0, false, false>), grid, block, D5_LDS, st, da, Gw, ncol, out, C);
   }
   PXM_HIP(hipGetLastError());
   return 0;
 }
 
 #define PXM_D5_DISPATCH(FN, ...)         \
-  switch (p.t5.r0) {                     \
+  switch (p.pair.r0) {                   \
     case 8: return FN<8>(__VA_ARGS__);   \
     case 4: return FN<4>(__VA_ARGS__);   \
     case 2: return FN<2>(__VA_ARGS__);   \
     default: return FN<1>(__VA_ARGS__);  \
   }
 
-int dft5_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t st) {
-  PXM_D5_DISPATCH(px2ring5_r, p, in, G, ncol, C, st)
+int pair_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t st) {
+  PXM_D5_DISPATCH(pair_px2ring_r, p, in, G, ncol, C, st)
 }
-int dft5_ring2px(const DftPlan& p, const double* G, int ncol, const PxOut& out, int C, hipStream_t st, bool ring_out) {
-  PXM_D5_DISPATCH(ring2px5_r, p, G, ncol, out, C, st, ring_out)
+int pair_ring2px(const DftPlan& p, const double* G, int ncol, const PxOut& out, int C, hipStream_t st, bool ring_out) {
+  PXM_D5_DISPATCH(pair_ring2px_r, p, G, ncol, out, C, st, ring_out)
 }
 
 // ---- grouped launch (wavelet plan: every scale in one grid) -----------------------------------------------------
-int dft5_group_create(const std::vector<const DftPlan*>& plans, const std::vector<int64_t>& g_off,
-                      const std::vector<int64_t>& ring0, int ncol, const double* ws_base, DftGroupList* out) {
-  // members: the scales on the eight-points-per-lane path that share the workgroup shape of the largest of them
-  // (the others keep their own launches); longest workgroups first, the smaller scales fill the tail
+int dft_group_create(const std::vector<const DftPlan*>& plans, const std::vector<int64_t>& g_off,
+                     const std::vector<int64_t>& ring0, int ncol, const double* ws_base, DftGroupList* out) {
+  // members: the scales on the pair unit (the others keep their own launches); longest workgroups first, the smaller
+  // scales fill the tail
   std::vector<int> order;
   for (size_t i = 0; i < plans.size(); ++i)
-    if (plans[i]->use5) order.push_back((int)i);
+    if (plans[i]->unit == DFT_PAIR) order.push_back((int)i);
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return plans[x]->L > plans[y]->L; });
   if (order.size() < 2) return 1;
-  std::vector<Dft5Group> v, vf;
+  std::vector<Dft5Group> v;
   out->member.assign(plans.size(), 0);
-  int b0 = 0, b0f = 0;
-  bool any_pfa = false;
-  size_t lds = 0;
+  int b0 = 0;
+  // address ranges of a grouped launch (host model of the kernels' global accesses): the ring array of every entry
+  // -- rows (m, t) with t < L, all ncol columns: loads of dead rings / padding slots are predicated off or clamped
+  // INSIDE the array --, the seven table views and the table block of the exact-length body must each lie inside one
+  // registered allocation; the coefficient side (X, T, noise, output: caller-owned, chain_stride elements per chain)
+  // is checked against chain_stride at launch (ring_end below: the clamped loads of elements past a ring's end re-read
+  // the ring's element 0)
+  std::string why;
+  int64_t nchk = 0;
   for (int s : order) {
     const DftPlan& p = *plans[s];
-    if (p.R5 != plans[order[0]]->R5) continue;
+    const PairTables& t = p.pair;
+    const std::string entry = "DFT group entry " + std::to_string(v.size());
     Dft5Group g;
-    g.a = dft5_args(p);
+    g.a = pair_args(p);
     g.g_off = g_off[s];
     g.ring0 = ring0[s];
-    g.r0 = p.t5.r0;
-    g.tbase = p.t5.d_all - ws_base;
-    const double* tp[7] = {p.t5.cE, p.t5.cO, p.t5.dO, p.t5.tw1, p.t5.wt, p.t5.bE, p.t5.bO};
-    for (int k = 0; k < 7; ++k) g.toff[k] = (int)(tp[k] - p.t5.d_all);
-    const int rings = p.TR5 * (8 / g.r0);
+    g.r0 = t.r0;
+    g.tbase = t.d_all - ws_base;
+    const double* tp[7] = {t.cE, t.cO, t.dO, t.tw1, t.wt, t.bE, t.bO};
+    for (int k = 0; k < 7; ++k) g.toff[k] = (int)(tp[k] - t.d_all);
+    const int rings = 8 / t.r0;
     g.nbx = (p.L + rings - 1) / rings;
-    g.nby = (ncol / 2 + p.R5 - 1) / p.R5;
+    g.nby = (ncol / 2 + D5_RMAX - 1) / D5_RMAX;
     {
       const int per_line = 16 / ncol;  // rings per 128-B line: 8 for one complex slot per entry, 4 for two, < 2 otherwise
       g.xs = (g.nby == 1 && per_line > rings && per_line % rings == 0) ? per_line / rings : 1;
     }
     g.pfa_off = 0;
     g.pfa_passes = 1;
+    // n = 511 takes the exact-length body (one wave per ring unit: two rings x four chain slots per workgroup, half the
+    // workgroups) -- on eight-slot lines only: the narrow arrays of one-chain plans keep the Bluestein body
+    if (t.pfa_off && ncol >= 8) {
+      ++out->n_pfa;
+      g.r0 = 9;
+      g.pfa_off = t.pfa_off;
+      g.pfa_passes = (getenv("PXM_PFA_PASSES") && atoi(getenv("PXM_PFA_PASSES")) == 1) ? 1 : 2;
+      g.nbx = ((p.L + 1) / 2 + g.pfa_passes - 1) / g.pfa_passes;
+      g.xs = 1;
+    }
     g.b0 = b0;
     b0 += round_up(g.nbx, 8) * g.nby;  // (padded so that every scale starts on an XCD-label boundary)
-    lds = std::max(lds, p.lds5);
     out->px_elems += (double)p.L * p.n;
     out->member[s] = 1;
     v.push_back(g);
-    // the fused launch's entry of the same scale: n = 511 takes the exact-length body (one wave per ring unit: two rings
-    // x four chain slots per workgroup, half the workgroups)
-    Dft5Group f = g;
-    if (p.t5.pfa_off && p.R5 == 4 && ncol >= 8) {  // (eight-slot lines only: the narrow arrays of one-chain plans keep the Bluestein unit)
-      any_pfa = true;
-      ++out->n_pfa;
-      f.r0 = 9;
-      f.pfa_off = p.t5.pfa_off;
-      f.pfa_passes = (getenv("PXM_PFA_PASSES") && atoi(getenv("PXM_PFA_PASSES")) == 1) ? 1 : 2;
-      f.nbx = ((p.L + 1) / 2 + f.pfa_passes - 1) / f.pfa_passes;
-      f.xs = 1;
+
+    const int64_t ring_doubles = (int64_t)(2 * p.L - 1) * p.Rp * ncol;
+    ++nchk;
+    if (!dev_range_ok(ws_base + g.g_off, ws_base + g.g_off + ring_doubles, &why)) {
+      set_error(entry + ": ring array outside its buffer: " + why);
+      return -1;
     }
-    f.b0 = b0f;
-    b0f += round_up(f.nbx, 8) * f.nby;
-    vf.push_back(f);
-  }
-  if (v.size() < 2) {
-    out->member.clear();
-    out->px_elems = 0;
-    return 1;
-  }
-  // address ranges of a grouped launch (host model of the kernels' global accesses): the ring array of every entry
-  // -- rows (m, t) with t < L, all ncol columns: loads of dead rings / padding slots are predicated off or clamped
-  // INSIDE the array -- and the seven table views must each lie inside one registered allocation; the coefficient
-  // side (X, T, noise, output: caller-owned, chain_stride elements per chain) is checked against chain_stride at
-  // launch (ring_end below: the clamped loads of elements past a ring's end re-read the ring's element 0)
-  {
-    std::string why;
-    int64_t nchk = 0;
-    for (size_t i = 0; i < v.size(); ++i) {
-      const Dft5Group& g = v[i];
-      const int Mh = 64 * g.r0;
-      const int64_t ring_doubles = (int64_t)(2 * g.a.L - 1) * g.a.Rp * ncol;
+    const int Mh = 64 * t.r0;
+    const int64_t tsize[7] = {2 * Mh, 2 * Mh, 2 * Mh, 2 * 8 * 64, 2 * 64, 2 * t.r0 * 64, 2 * t.r0 * 64};
+    for (int k = 0; k < 7; ++k) {
       ++nchk;
-      if (!dev_range_ok(ws_base + g.g_off, ws_base + g.g_off + ring_doubles, &why)) {
-        set_error("DFT group entry " + std::to_string(i) + ": ring array outside its buffer: " + why);
+      const double* tb = ws_base + g.tbase + g.toff[k];
+      if (!dev_range_ok(tb, tb + tsize[k], &why)) {
+        set_error(entry + ": table view " + std::to_string(k) + " outside its buffer: " + why);
         return -1;
       }
-      const int64_t tsize[7] = {2 * Mh, 2 * Mh, 2 * Mh, 2 * 8 * 64, 2 * 64, 2 * g.r0 * 64, 2 * g.r0 * 64};
-      for (int k = 0; k < 7; ++k) {
-        ++nchk;
-        const double* tb = ws_base + g.tbase + g.toff[k];
-        if (!dev_range_ok(tb, tb + tsize[k], &why)) {
-          set_error("DFT group entry " + std::to_string(i) + ": table view " + std::to_string(k) + " outside its buffer: " + why);
-          return -1;
-        }
-      }
-      out->ring_end = std::max(out->ring_end, g.ring0 + (int64_t)g.a.L * g.a.n);
-      if (vf[i].r0 == 9) {  // the table block of the exact-length body
-        ++nchk;
-        const double* tb = ws_base + g.tbase + vf[i].pfa_off;
-        if (!dev_range_ok(tb, tb + PFA_TAB_DOUBLES, &why)) {
-          set_error("DFT group entry " + std::to_string(i) + ": PFA table block outside its buffer: " + why);
-          return -1;
-        }
+    }
+    out->ring_end = std::max(out->ring_end, g.ring0 + (int64_t)p.L * p.n);
+    if (g.r0 == 9) {
+      ++nchk;
+      const double* tb = ws_base + g.tbase + g.pfa_off;
+      if (!dev_range_ok(tb, tb + PFA_TAB_DOUBLES, &why)) {
+        set_error(entry + ": PFA table block outside its buffer: " + why);
+        return -1;
       }
     }
-    ranges_checked_add(nchk);
   }
+  ranges_checked_add(nchk);
   out->n = (int)v.size();
   out->all = v.size() == plans.size();
   out->blocks = b0;
-  out->lds = lds;
-  out->five = true;
-  out->threads = 128 * plans[order[0]]->R5;
   if (int rc = dev_alloc(&out->d, v.size() * sizeof(Dft5Group), "DFT group entries")) return rc;
   if (int rc = dev_upload(out->d, v.data(), v.size() * sizeof(Dft5Group))) return rc;
-  if (any_pfa) {
-    // LDS of the exact-length body: 8 planes of PFA_PLANE slots (aliased by the stage of 2 rings x 511 x 4 slots) + the filter
-    // spectrum: 81 056 B, inside the 81 920 B of the Bluestein workgroups (two workgroups per CU either way)
-    static_assert(((size_t)8 * PFA_PLANE + 72 + NOISE_LOG_N + 256 + 1) * 16 <= (size_t)2 * D5_RMAX * D5_PLANE * 16 + (size_t)D5_TW * 16, "PFA workgroup LDS");
-        if (int rc = dev_alloc(&out->d_fused, vf.size() * sizeof(Dft5Group), "DFT group entries (fused launch)")) return rc;
-    if (int rc = dev_upload(out->d_fused, vf.data(), vf.size() * sizeof(Dft5Group))) return rc;
-    out->blocks_fused = b0f;
-  }
   static std::atomic<uint64_t> lds_done{0};
   return allow_dynamic_lds(lds_done, {reinterpret_cast<const void*>(k_ring2px_group5<true, false>), reinterpret_cast<const void*>(k_ring2px_group5<true, true>),
                                       reinterpret_cast<const void*>(k_ring2px_group5<false, false>), reinterpret_cast<const void*>(k_ring2px_group5<false, true>),
@@ -1782,81 +1067,57 @@ int dft5_group_create(const std::vector<const DftPlan*>& plans, const std::vecto
 
 void dft_group_destroy(DftGroupList* g) {
   if (g->d) deferred_free(g->d);
-  if (g->d_fused) deferred_free(g->d_fused);
-  g->d = g->d_fused = nullptr;
-  g->blocks_fused = 0;
+  g->d = nullptr;
   g->n_pfa = 0;
   g->n = 0;
 }
 
-int dft5_group_launch(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st, Profiler* prof) {
+int dft_group_launch(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st, Profiler* prof) {
   // algorithmic bytes: rings read + written (16 B per slot and coefficient, every padded slot), state read, new state
   // written (live slots), thresholds read once
-  PXM_REQUIRE(g.ring_end <= out.chain_stride, "dft5_group_launch: a scale's coefficient block ends past chain_stride");
+  PXM_REQUIRE(g.ring_end <= out.chain_stride, "dft_group_launch: a scale's coefficient block ends past chain_stride");
   const double bytes = g.px_elems * (2.0 * 16 * (ncol / 2) + 2.0 * 16 * C + (out.T ? 8.0 : 0.0));
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (prof) prof->next(prof->dft, &ev0, &ev1, bytes, 0.0);
-  const Dft5Group* ents = reinterpret_cast<const Dft5Group*>(g.d_fused ? g.d_fused : g.d);
-  const int blocks = g.d_fused ? g.blocks_fused : g.blocks;
+  const Dft5Group* ents = reinterpret_cast<const Dft5Group*>(g.d);
   if (out.X && !out.noise && out.noise64)
-    hipExtLaunchKernelGGL((k_ring2px_group5<true, true>), dim3(blocks), dim3(g.threads), g.lds, st, ev0, ev1, 0,
+    hipExtLaunchKernelGGL((k_ring2px_group5<true, true>), dim3(g.blocks), dim3(128 * D5_RMAX), D5_LDS, st, ev0, ev1, 0,
                           ents, g.n, ws, ncol, out, C);
   else
-    hipExtLaunchKernelGGL((k_ring2px_group5<true, false>), dim3(blocks), dim3(g.threads), g.lds, st, ev0, ev1, 0,
+    hipExtLaunchKernelGGL((k_ring2px_group5<true, false>), dim3(g.blocks), dim3(128 * D5_RMAX), D5_LDS, st, ev0, ev1, 0,
                           ents, g.n, ws, ncol, out, C);
   PXM_HIP(hipGetLastError());
   return 0;
 }
 
-int dft5_group_px2ring(const DftGroupList& g, double* ws, int ncol, const PxIn& in, int C, hipStream_t st) {
-  PXM_REQUIRE(in.gidx || g.ring_end <= in.chain_stride, "dft5_group_px2ring: a scale's coefficient block ends past chain_stride");
-  hipLaunchKernelGGL(k_px2ring_group5, dim3(g.d_fused ? g.blocks_fused : g.blocks), dim3(g.threads), g.lds, st,
-                     reinterpret_cast<const Dft5Group*>(g.d_fused ? g.d_fused : g.d), g.n, ws, ncol, in, C);
+int dft_group_px2ring(const DftGroupList& g, double* ws, int ncol, const PxIn& in, int C, hipStream_t st) {
+  PXM_REQUIRE(in.gidx || g.ring_end <= in.chain_stride, "dft_group_px2ring: a scale's coefficient block ends past chain_stride");
+  hipLaunchKernelGGL(k_px2ring_group5, dim3(g.blocks), dim3(128 * D5_RMAX), D5_LDS, st, reinterpret_cast<const Dft5Group*>(g.d),
+                     g.n, ws, ncol, in, C);
   PXM_HIP(hipGetLastError());
   return 0;
 }
 
-int dft5_group_ring2px(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st) {
-  PXM_REQUIRE(out.gidx || g.ring_end <= out.chain_stride, "dft5_group_ring2px: a scale's coefficient block ends past chain_stride");
-  const Dft5Group* ents = reinterpret_cast<const Dft5Group*>(g.d_fused ? g.d_fused : g.d);
-  const int blocks = g.d_fused ? g.blocks_fused : g.blocks;
+int dft_group_ring2px(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st) {
+  PXM_REQUIRE(out.gidx || g.ring_end <= out.chain_stride, "dft_group_ring2px: a scale's coefficient block ends past chain_stride");
+  const Dft5Group* ents = reinterpret_cast<const Dft5Group*>(g.d);
   if (out.X && !out.noise && out.noise64)
-    hipLaunchKernelGGL((k_ring2px_group5<false, true>), dim3(blocks), dim3(g.threads), g.lds, st, ents, g.n, ws, ncol, out, C);
+    hipLaunchKernelGGL((k_ring2px_group5<false, true>), dim3(g.blocks), dim3(128 * D5_RMAX), D5_LDS, st, ents, g.n, ws, ncol, out, C);
   else
-    hipLaunchKernelGGL((k_ring2px_group5<false, false>), dim3(blocks), dim3(g.threads), g.lds, st, ents, g.n, ws, ncol, out, C);
+    hipLaunchKernelGGL((k_ring2px_group5<false, false>), dim3(g.blocks), dim3(128 * D5_RMAX), D5_LDS, st, ents, g.n, ws, ncol, out, C);
   PXM_HIP(hipGetLastError());
   return 0;
 }
 
-
-// ---- four waves per ring (512 < n <= 1023) --------------------------------------------------------------------------
-int dft6_make_tables(int n, Dft6Tables* t) {
+// ---- host side of the quad unit ----------------------------------------------------------------------------------------------------
+int quad_make_tables(int n, QuadTables* t) {
   typedef std::complex<long double> cld;
   const long double PI_L = 3.141592653589793238462643383279502884L;
   const int M = 2048;
   auto ang = [&](long double num, long double den) { return cld(cosl(-PI_L * num / den), sinl(-PI_L * num / den)); };
-  std::vector<cld> chirp(1024, cld(0, 0)), filt(M, cld(0, 0));
-  for (int j = 0; j < n; ++j) chirp[j] = ang((long double)(((long long)j * j) % (2LL * n)), n);
-  for (int j = 0; j < n; ++j) {
-    filt[j] = std::conj(chirp[j]);
-    if (j) filt[M - j] = std::conj(chirp[j]);
-  }
-  int logM = 0;
-  while ((1 << logM) < M) ++logM;
-  for (int s = M / 2; s >= 1; s >>= 1)
-    for (int g = 0; g < M; g += 2 * s)
-      for (int p = 0; p < s; ++p) {
-        const cld w = ang(2.0L * p * (M / (2 * s)), M);
-        const cld u = filt[g + p], v = filt[g + p + s];
-        filt[g + p] = u + v;
-        filt[g + p + s] = (u - v) * w;
-      }
-  std::vector<cld> bhat(M);
-  for (int i = 0; i < M; ++i) {
-    int r = 0;
-    for (int bit = 0; bit < logM; ++bit) r |= ((i >> bit) & 1) << (logM - 1 - bit);
-    bhat[r] = filt[i] / (long double)M;
-  }
+  std::vector<cld> chirp, bhat;
+  bluestein_chirp_spectrum(n, M, true, chirp, bhat);
+  chirp.resize(1024, cld(0, 0));
   std::vector<double> h;
   auto put = [&](const cld& v) {
     h.push_back((double)v.real());
@@ -1898,41 +1159,41 @@ int dft6_make_tables(int n, Dft6Tables* t) {
   return 0;
 }
 
-static Dft6Args dft6_args(const DftPlan& p) {
-  const Dft6Tables& t = p.t6;
+static Dft6Args quad_args(const DftPlan& p) {
+  const QuadTables& t = p.quad;
   auto c = [](const double* x) { return reinterpret_cast<const double2*>(x); };
   return Dft6Args{p.L, p.n, p.Rp, 1, c(t.cA), c(t.cB), c(t.dA), c(t.dB), c(t.tw1), c(t.wt), c(t.bQ)};
 }
 // chains per workgroup: 2 (8 waves, 2 workgroups per CU: 4 waves per SIMD); 1 for a single chain
-static size_t dft6_lds(int R) { return (size_t)4 * R * D5_PLANE * 16 + (size_t)D5_TW * 16; }  // (>= the stage: n R 16 B)
-static int dft6_attr() {
+static size_t quad_lds(int R) { return (size_t)4 * R * D5_PLANE * 16 + (size_t)D5_TW * 16; }  // (>= the stage: n R 16 B)
+static int quad_attr() {
   static std::atomic<uint64_t> done{0};
   return allow_dynamic_lds(done, {reinterpret_cast<const void*>(k_px2ring6<0>), reinterpret_cast<const void*>(k_px2ring6<1>),
                                   reinterpret_cast<const void*>(k_ring2px6<false, 0>), reinterpret_cast<const void*>(k_ring2px6<true, 0>),
                                   reinterpret_cast<const void*>(k_ring2px6<false, 1>), reinterpret_cast<const void*>(k_ring2px6<true, 1>)});
 }
-static int dft6_chains_per_wg(int C) { return C == 1 ? 1 : 2; }
-int dft6_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t st) {
-  if (int rc = dft6_attr()) return rc;
-  const int R = dft6_chains_per_wg(C);
+static int quad_chains_per_wg(int C) { return C == 1 ? 1 : 2; }
+int quad_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t st) {
+  if (int rc = quad_attr()) return rc;
+  const int R = quad_chains_per_wg(C);
   dim3 grid(p.L, (ncol / 2 + R - 1) / R), block(256 * R);
-  if (R == 1) hipLaunchKernelGGL(k_px2ring6<0>, grid, block, dft6_lds(R), st, dft6_args(p), in, G, ncol, C);
-  else hipLaunchKernelGGL(k_px2ring6<1>, grid, block, dft6_lds(R), st, dft6_args(p), in, G, ncol, C);
+  if (R == 1) hipLaunchKernelGGL(k_px2ring6<0>, grid, block, quad_lds(R), st, quad_args(p), in, G, ncol, C);
+  else hipLaunchKernelGGL(k_px2ring6<1>, grid, block, quad_lds(R), st, quad_args(p), in, G, ncol, C);
   PXM_HIP(hipGetLastError());
   return 0;
 }
-int dft6_ring2px(const DftPlan& p, const double* G, int ncol, const PxOut& out, int C, hipStream_t st) {
-  if (int rc = dft6_attr()) return rc;
-  const int R = dft6_chains_per_wg(C);
+int quad_ring2px(const DftPlan& p, const double* G, int ncol, const PxOut& out, int C, hipStream_t st) {
+  if (int rc = quad_attr()) return rc;
+  const int R = quad_chains_per_wg(C);
   dim3 grid(p.L, (C + R - 1) / R), block(256 * R);
   const bool n64 = out.X && !out.noise && out.noise64;
-  const Dft6Args a = dft6_args(p);
+  const Dft6Args a = quad_args(p);
   if (R == 1) {
-    if (n64) hipLaunchKernelGGL((k_ring2px6<true, 0>), grid, block, dft6_lds(R), st, a, G, ncol, out, C);
-    else hipLaunchKernelGGL((k_ring2px6<false, 0>), grid, block, dft6_lds(R), st, a, G, ncol, out, C);
+    if (n64) hipLaunchKernelGGL((k_ring2px6<true, 0>), grid, block, quad_lds(R), st, a, G, ncol, out, C);
+    else hipLaunchKernelGGL((k_ring2px6<false, 0>), grid, block, quad_lds(R), st, a, G, ncol, out, C);
   } else {
-    if (n64) hipLaunchKernelGGL((k_ring2px6<true, 1>), grid, block, dft6_lds(R), st, a, G, ncol, out, C);
-    else hipLaunchKernelGGL((k_ring2px6<false, 1>), grid, block, dft6_lds(R), st, a, G, ncol, out, C);
+    if (n64) hipLaunchKernelGGL((k_ring2px6<true, 1>), grid, block, quad_lds(R), st, a, G, ncol, out, C);
+    else hipLaunchKernelGGL((k_ring2px6<false, 1>), grid, block, quad_lds(R), st, a, G, ncol, out, C);
   }
   PXM_HIP(hipGetLastError());
   return 0;

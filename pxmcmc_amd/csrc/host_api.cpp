@@ -270,7 +270,7 @@ int pxm_host_sht_tables(int L, int spin, int m, double* Binv, double* Afwd) {
 
 }  // extern "C"
 namespace pxm {
-void pfa511_host_tables(uint16_t* idx, double* b2);  // dft5.hip
+void pfa511_host_tables(uint16_t* idx, double* b2);  // dft_wave.hip
 }
 extern "C" {
 int pxm_host_pfa511_tables(uint16_t* idx, double* b2) {

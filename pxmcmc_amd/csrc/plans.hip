@@ -214,7 +214,7 @@ struct pxm_sht_plan_s {
 };
 
 namespace pxm {
-// Device status word of a plan: kernels OR a bit in when a bounded wait expires (dft5.hip d5_pair_sync) instead of
+// Device status word of a plan: kernels OR a bit in when a bounded wait expires (dft_wave.h: d5_pair_sync) instead of
 // hanging the GPU; the host reads it wherever it synchronises anyway.
 static int status_alloc(unsigned** d) {
   if (int rc = dev_alloc(d, 4 * sizeof(unsigned), "plan status word")) return rc;
@@ -719,7 +719,7 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
     if (p->bl[s] < L) p->lane_of[s] = (k++) % p->nside;
   std::vector<const DftPlan*> dp;
   for (int s = 0; s < p->nsc; ++s) dp.push_back(&p->dft[s]);
-  rc = dft5_group_create(dp, p->offG, p->coef_off, p->ncol, p->ws, &p->dft_group);
+  rc = dft_group_create(dp, p->offG, p->coef_off, p->ncol, p->ws, &p->dft_group);
   if (rc < 0) return rc;  // rc == 1: no group -> per-scale launches
   *plan = guard.release();
   return 0;
@@ -890,11 +890,11 @@ static inline hipStream_t wav_stream(pxm_wav_plan_t p, int s, hipStream_t st) {
 }
 
 // coefficient blocks -> G_s (scales' px2ring) ; G_s -> coefficient blocks (ring2px with optional fused update)
-// The member scales of the plan's DFT group go in ONE grid (dft5.hip: k_px2ring_group5 / k_ring2px_group5<false>); a
+// The member scales of the plan's DFT group go in ONE grid (dft_wave.hip: k_px2ring_group5 / k_ring2px_group5<false>); a
 // scale outside the group (band-limits above 256: four-wave kernels) keeps its own launch, on the calling stream
 // while the group runs on a side stream.
 static inline bool wav_in_group(pxm_wav_plan_t p, int s) {
-  return p->dft_group.d && p->dft_group.five && p->plain_group && p->dft_group.member[s];
+  return p->dft_group.d && p->plain_group && p->dft_group.member[s];
 }
 // side stream 0 (made to wait for the fork event if no scale had claimed it), or the caller's stream without side streams
 static inline hipStream_t wav_group_stream(pxm_wav_plan_t p, hipStream_t st, bool used[pxm_wav_plan_s::NSIDE]) {
@@ -909,13 +909,13 @@ static inline hipStream_t wav_group_stream(pxm_wav_plan_t p, hipStream_t st, boo
 // twin (weak-lensing path, C == 1): scales twin_s and twin_s + 1 as the two "chains" of ONE launch on the twin array -- chain
 // stride = the distance of their coefficient blocks
 static int wav_blocks_to_rings(pxm_wav_plan_t p, const void* X, int C, hipStream_t st, uint64_t* bump = nullptr, bool twin = false) {
-  const bool grp = p->dft_group.d && p->dft_group.five && p->plain_group;
+  const bool grp = p->dft_group.d && p->plain_group;
   if (grp && p->dft_group.all) {  // every scale in the one grid: no side streams at all
     PxIn in;
     in.f = (const double*)X;
     in.chain_stride = p->ncoefs;
     in.bump = bump;
-    return dft5_group_px2ring(p->dft_group, p->ws, p->ncol, in, C, st);
+    return dft_group_px2ring(p->dft_group, p->ws, p->ncol, in, C, st);
   }
   bool used[pxm_wav_plan_s::NSIDE];
   int rc = wav_fork(p, st, used);
@@ -944,15 +944,15 @@ static int wav_blocks_to_rings(pxm_wav_plan_t p, const void* X, int C, hipStream
     in.chain_stride = p->ncoefs;
     if (!bumped) in.bump = bump;
     const bool ng = twin && p->dft_group_n.d;  // one-chain weak-lensing path: the member scales' narrow arrays
-    if ((rc = dft5_group_px2ring(ng ? p->dft_group_n : p->dft_group, p->ws, ng ? p->ncol_gn : p->ncol, in, C, wav_group_stream(p, st, used)))) return rc;
+    if ((rc = dft_group_px2ring(ng ? p->dft_group_n : p->dft_group, p->ws, ng ? p->ncol_gn : p->ncol, in, C, wav_group_stream(p, st, used)))) return rc;
   }
   return wav_join(p, st, used);
 }
 
 static int wav_rings_to_blocks(pxm_wav_plan_t p, PxOut proto, int C, hipStream_t st, bool twin = false) {
-  const bool grp = p->dft_group.d && p->dft_group.five && p->plain_group;
+  const bool grp = p->dft_group.d && p->plain_group;
   proto.chain_stride = p->ncoefs;
-  if (grp && p->dft_group.all) return dft5_group_ring2px(p->dft_group, p->ws, p->ncol, proto, C, st);
+  if (grp && p->dft_group.all) return dft_group_ring2px(p->dft_group, p->ws, p->ncol, proto, C, st);
   bool used[pxm_wav_plan_s::NSIDE];
   int rc = wav_fork(p, st, used);
   if (rc) return rc;
@@ -971,7 +971,7 @@ static int wav_rings_to_blocks(pxm_wav_plan_t p, PxOut proto, int C, hipStream_t
   }
   if (grp) {
     const bool ng = twin && p->dft_group_n.d;
-    if ((rc = dft5_group_ring2px(ng ? p->dft_group_n : p->dft_group, p->ws, ng ? p->ncol_gn : p->ncol, proto, C, wav_group_stream(p, st, used)))) return rc;
+    if ((rc = dft_group_ring2px(ng ? p->dft_group_n : p->dft_group, p->ws, ng ? p->ncol_gn : p->ncol, proto, C, wav_group_stream(p, st, used)))) return rc;
   }
   return wav_join(p, st, used);
 }
@@ -987,7 +987,7 @@ static bool wav_can_fuse_dft(pxm_wav_plan_t p) {
 static int wav_rings_update_rings(pxm_wav_plan_t p, PxOut proto, int C, hipStream_t st) {
   if (p->dft_group.d && p->dft_group.all) {  // one grid for every scale, small scales first
     proto.chain_stride = p->ncoefs;
-    return dft5_group_launch(p->dft_group, p->ws, p->ncol, proto, C, st, &p->prof);
+    return dft_group_launch(p->dft_group, p->ws, p->ncol, proto, C, st, &p->prof);
   }
   bool used[pxm_wav_plan_s::NSIDE];
   int rc = wav_fork(p, st, used);
@@ -1001,8 +1001,7 @@ static int wav_rings_update_rings(pxm_wav_plan_t p, PxOut proto, int C, hipStrea
       PxOut out = proto;
       out.chain_stride = p->ncoefs;
       out.ring0 = p->coef_off[s];
-      rc = launch_ring2px2ring(p->dft[s], p->ws + p->offG[s], p->ncol, out, C, wav_stream(p, s, st));
-      if (rc) return rc < 0 ? rc : -1;
+      if ((rc = launch_ring2px2ring(p->dft[s], p->ws + p->offG[s], p->ncol, out, C, wav_stream(p, s, st)))) return rc;
     }
   return wav_join(p, st, used);
 }
@@ -1129,10 +1128,9 @@ int pxm_wav_image_step(pxm_wav_plan_t p, const void* X, const void* data, const 
   PxOut po;
   po.f = (double*)preds_out;
   po.chain_stride = (int64_t)p->L * (2 * p->L - 1);
-  if (p->dftL.use5) {  // (only the wave paths implement the residual epilogue)  // rings -> preds -> residual -> rings, one kernel
+  if (dft_can_fuse(p->dftL)) {  // rings -> preds -> residual -> rings, one kernel (only the pair unit implements the residual epilogue)
     image_residual(po, data, invcov, invcov_complex);
-    rc = launch_ring2px2ring(p->dftL, p->ws + p->offGL, p->ncol, po, C, st);
-    return rc < 0 ? rc : (rc ? -1 : 0);
+    return launch_ring2px2ring(p->dftL, p->ws + p->offGL, p->ncol, po, C, st);
   }
   if ((rc = launch_ring2px(p->dftL, p->ws + p->offGL, p->ncol, po, C, st))) return rc;
   return pxm_wav_image_init(p, preds_out, data, invcov, invcov_complex, C, stream);
@@ -1312,7 +1310,7 @@ static int wl_attach_impl(pxm_wav_plan_t p, const int32_t* pix2data, const doubl
     if ((rc = dev_zero(p->d_twin, (size_t)n * sizeof(double)))) return rc;
     p->offGT = p->d_twin - p->ws;
     bool narrow_g = false;
-    if (p->ncol_h && p->dft_group.d && p->dft_group.five && p->plain_group) {
+    if (p->ncol_h && p->dft_group.d && p->plain_group) {
       // the member scales of the DFT group on rows of 2 Cmax doubles as well: own arrays, own group descriptors
       p->ncol_gn = 2 * p->Cmax;
       p->offGn = p->offG;
@@ -1329,7 +1327,7 @@ static int wl_attach_impl(pxm_wav_plan_t p, const int32_t* pix2data, const doubl
         if (p->dft_group.member[k]) p->offGn[k] = (p->d_gn - p->ws) + rel[k];
       std::vector<const DftPlan*> dp;
       for (int k = 0; k < p->nsc; ++k) dp.push_back(&p->dft[k]);
-      rc = dft5_group_create(dp, p->offGn, p->coef_off, p->ncol_gn, p->ws, &p->dft_group_n);
+      rc = dft_group_create(dp, p->offGn, p->coef_off, p->ncol_gn, p->ws, &p->dft_group_n);
       if (rc < 0) return rc;
       narrow_g = rc == 0 && p->dft_group_n.member == p->dft_group.member;
       if (!narrow_g) dft_group_destroy(&p->dft_group_n);

@@ -186,37 +186,39 @@ int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags,
                            const char* list_name);
 
 // ---- DFT stage ---------------------------------------------------------------
-// device tables of the eight-points-per-lane path (dft5.hip): one allocation, typed views into it
-struct Dft5Tables {
+// Three units transform the rings; a plan uses one, chosen at creation by its ring length n = 2L - 1:
+//   DFT_PAIR   n <= 511: eight points per lane, a pair of waves per ring set (dft_wave.hip); n = 511 on eight-slot lines
+//              runs the exact-length body (dft_pfa.h) unless PXM_DFT_PFA=0
+//   DFT_QUAD   511 < n <= 1023: four waves per ring, eight points per lane (dft_wave.hip)
+//   DFT_RADIX2 every larger n, and every n with PXM_DFT_NO_W=1: the radix-2 in-LDS unit (dft.hip; an independent
+//              implementation, the cross-check of the other two)
+enum DftUnit { DFT_RADIX2, DFT_PAIR, DFT_QUAD };
+
+// device tables of the pair unit: one allocation, typed views into it
+struct PairTables {
   double* d_all = nullptr;
-  size_t bytes = 0;
   int r0 = 0;  // Mh / 64
   int pfa_off = 0;  // n = 511: the table block of the exact-length unit inside the allocation (doubles), 0 = none
   const double *cE = nullptr, *cO = nullptr, *dO = nullptr, *tw1 = nullptr, *wt = nullptr, *bE = nullptr, *bO = nullptr;
 };
 
-// tables of the four-waves-per-ring kernels (512 < n <= 1023, dft5.hip k_*6)
-struct Dft6Tables {
+// device tables of the quad unit
+struct QuadTables {
   double* d_all = nullptr;
   const double *cA = nullptr, *cB = nullptr, *dA = nullptr, *dB = nullptr, *tw1 = nullptr, *wt = nullptr, *bQ = nullptr;
 };
 
 struct DftPlan {
-  int L = 0, n = 0, M = 0, logM = 0, Rp = 0;
-  int R = 0;        // chains per workgroup
-  int threads = 0;  // workgroup size
+  int L = 0, n = 0, Rp = 0;
+  DftUnit unit = DFT_RADIX2;
+  // radix-2 unit: M-point in-LDS transform, R chains per workgroup of `threads` threads, `lds` bytes of LDS
+  int M = 0, logM = 0, R = 0, threads = 0;
   size_t lds = 0;
   double *d_chirp = nullptr, *d_bhat = nullptr, *d_tw = nullptr;
-  // eight-points-per-lane path (dft5.hip): M = 2 Mh, two half-size convolutions per wave, every L <= 256 (default)
-  bool use5 = false;
-  Dft5Tables t5;
-  int R5 = 0, TR5 = 0;
-  size_t lds5 = 0;
-  // four waves per ring (dft5.hip, k_*6): M = 2048 = 4 x 512 for 256 < L <= 512 (default there)
-  bool use6 = false;
-  Dft6Tables t6;
+  PairTables pair;
+  QuadTables quad;
   // status word of the OWNING plan (set by the owner after make_dft_plan; null: expiries go unrecorded) and the bound
-  // of the wave-pair wait of the dft5 kernels (PXM_DEBUG_PAIR_SYNC_LIMIT, read at plan creation: 0 forces an expiry)
+  // of the wave-pair wait of the pair unit (PXM_DEBUG_PAIR_SYNC_LIMIT, read at plan creation: 0 forces an expiry)
   unsigned* d_status = nullptr;
   unsigned spin_limit = 1u << 18;
 };
@@ -264,50 +266,34 @@ struct PxOut {  // ring2px output: plain image, or the fused MYULA update of a c
   const double* gw = nullptr;
 };
 
-// grouped launches of a wavelet plan's member scales (dft5.hip): one grid for every scale
+// grouped launches of a wavelet plan's member scales (dft_wave.hip): one grid for every scale on the pair unit
 struct DftGroupList {
   void* d = nullptr;  // device array of per-scale descriptors
-  // the fused rings -> X' -> rings launch's own descriptors when a member scale takes the exact-length body (n = 511:
-  // two rings per workgroup, other block counts); null = the list above
-  void* d_fused = nullptr;
-  int blocks_fused = 0;
-  int n_pfa = 0;  // member scales that take the exact-length unit in the fused launch
-  bool five = false;  // descriptors of the eight-points-per-lane kernel (dft5.hip)
-  int threads = 512;  // ... and its workgroup size
   int n = 0, blocks = 0;
-  size_t lds = 0;
+  int n_pfa = 0;  // member scales that take the exact-length body (n = 511: two rings per workgroup, own block counts)
   double px_elems = 0;  // sum over scales of bl (2 bl - 1): coefficients per chain slot
   int64_t ring_end = 0; // largest ring0 + L n over the entries: the launches require it <= chain_stride
   std::vector<char> member;  // per scale: its rings <-> pixels launches are part of this group
   bool all = false;          // every scale is a member (needed by the fused rings -> X' -> rings step)
 };
+int dft_group_create(const std::vector<const DftPlan*>& plans, const std::vector<int64_t>& g_off,
+                     const std::vector<int64_t>& ring0, int ncol, const double* ws_base,
+                     DftGroupList* out);  // 1 = not available
 void dft_group_destroy(DftGroupList* g);
-// eight-points-per-lane path (dft5.hip)
-int dft5_r0(int n);  // Mh / 64 for ring length n, 0 = not covered (n > 512)
-int dft5_make_tables(int n, Dft5Tables* t);
-void pfa511_host_tables(uint16_t* idx, double* b2);  // exact-length unit of n = 511 (dft_pfa.h): idx[(64 + 80) * 8], b2[144]
-void dft5_geometry(int n, int* R, int* TR, size_t* lds);
-int dft5_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t st);
-int dft5_ring2px(const DftPlan& p, const double* G, int ncol, const PxOut& out, int C, hipStream_t st, bool ring_out = false);
-int dft5_group_create(const std::vector<const DftPlan*>& plans, const std::vector<int64_t>& g_off,
-                      const std::vector<int64_t>& ring0, int ncol, const double* ws_base,
-                      DftGroupList* out);  // 1 = not available
-int dft5_group_launch(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st,
-                      Profiler* prof = nullptr);
+// the fused rings -> X' -> rings step of every member scale in one grid
+int dft_group_launch(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st,
+                     Profiler* prof = nullptr);
 // the plain transforms of every member scale in one grid each (blocks <-> rings of the generic wavelet operators)
-int dft5_group_px2ring(const DftGroupList& g, double* ws, int ncol, const PxIn& in, int C, hipStream_t st);
-int dft5_group_ring2px(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st);
-int dft6_make_tables(int n, Dft6Tables* t);
-int dft6_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t st);
-int dft6_ring2px(const DftPlan& p, const double* G, int ncol, const PxOut& out, int C, hipStream_t st);
+int dft_group_px2ring(const DftGroupList& g, double* ws, int ncol, const PxIn& in, int C, hipStream_t st);
+int dft_group_ring2px(const DftGroupList& g, double* ws, int ncol, const PxOut& out, int C, hipStream_t st);
 
 // f(t,p) -> G[m][t][c]  (unnormalised, e^{-i m phi});  G -> f (e^{+i m phi})
 int launch_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t stream);
 int launch_ring2px(const DftPlan& p, const double* G, int ncol, const PxOut& out, int C, hipStream_t stream);
-// fused: rings -> out.f (with out's epilogue) and the rings of what was written, in place over G.
-// Returns 1 (nothing launched) when the plan's DFT size has no fused kernel.
+// fused: rings -> out.f (with out's epilogue) and the rings of what was written, in place over G -- only where
+// dft_can_fuse (an error otherwise)
 int launch_ring2px2ring(const DftPlan& p, double* G, int ncol, const PxOut& out, int C, hipStream_t stream);
-inline bool dft_can_fuse(const DftPlan& p) { return p.use5; }
+inline bool dft_can_fuse(const DftPlan& p) { return p.unit == DFT_PAIR; }
 
 // ---- layout repack (public harmonic layout el^2+el+m <-> internal [m][el][c]) ----------
 int launch_lm_to_mel(const double* flm, double* H, int L, int Rp, int ncol, int C, int spin, hipStream_t stream);

@@ -37,16 +37,7 @@ constexpr int KC = 16;  // contraction rows per staged chunk
 // NW waves per workgroup, RT row tiles of 16 rows per wave: a task covers NW*RT row tiles.
 // NSET: register sets of the table AND operand streams, i.e. both run NSET-1 chunks (of 16 k) ahead (the depth each
 // launcher instantiates, and why, is at launch_gemm / launch_gemm_packed below).
-// timing-only ablations (development; results are wrong): PXM_GEMM_ABLATE & 1 no MFMA, & 2 no table loads,
-// & 4 no operand staging (loads, LDS stores and the per-chunk barrier)
-#ifndef PXM_GEMM_ABLATE
-#define PXM_GEMM_ABLATE 0
-#endif
-#if PXM_GEMM_ABLATE & 1
-#define PXM_GEMM_MFMA(ACC, A, B) ACC[0] += (A) * (B);
-#else
 #define PXM_GEMM_MFMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f64_16x16x4f64(A, B, ACC, 0, 0, 0);
-#endif
 #ifdef PXM_GEMM_TRACE
 // development build only: per-workgroup timeline (start / end clock, placement, task shape) of every launch into a
 // caller-provided buffer [8 words per record], records appended through an atomic cursor in word 0
@@ -221,17 +212,11 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
 #ifdef PXM_GEMM_TRACE
       if (ch == 9) trace_c[4] = clock64();
 #endif
-#if !(PXM_GEMM_ABLATE & 4)
       PXM_STAGE_STORE(us, buf)
       PXM_GEMM_CSTAMP(1)  // operand of this chunk arrived and went to LDS
       PXM_STAGE_LOAD(us, it)
-#endif
-#if !(PXM_GEMM_ABLATE & 2)
       PXM_TAB_LOAD(ut, it)
-#endif
-#if !(PXM_GEMM_ABLATE & 4)
       __syncthreads();
-#endif
 #ifdef PXM_GEMM_TRACE
       if (ch == 0) trace_t1 = wall_clock64();  // first chunk staged: task fetch + first operand loads are behind us
 #endif

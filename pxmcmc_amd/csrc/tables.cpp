@@ -276,6 +276,39 @@ void quadrature_gram(int L, int par, double* Q, int ld) {
   }
 }
 
+void bluestein_chirp_spectrum(int n, int M, bool natural, std::vector<std::complex<long double>>& chirp,
+                              std::vector<std::complex<long double>>& spec) {
+  typedef std::complex<long double> cld;
+  auto ang = [](long double num, long double den) { return cld(cosl(-PI_L * num / den), sinl(-PI_L * num / den)); };
+  chirp.assign(n, cld(0, 0));
+  for (int j = 0; j < n; ++j) chirp[j] = ang((long double)(((long long)j * j) % (2LL * n)), n);
+  std::vector<cld> filt(M, cld(0, 0));
+  for (int j = 0; j < n; ++j) {
+    filt[j] = std::conj(chirp[j]);
+    if (j) filt[M - j] = std::conj(chirp[j]);
+  }
+  // iterative radix-2 DIF in long double: natural in, bit-reversed out
+  for (int s = M / 2; s >= 1; s >>= 1)
+    for (int g = 0; g < M; g += 2 * s)
+      for (int p = 0; p < s; ++p) {
+        const cld w = ang(2.0L * p * (M / (2 * s)), M);
+        const cld u = filt[g + p], v = filt[g + p + s];
+        filt[g + p] = u + v;
+        filt[g + p + s] = (u - v) * w;
+      }
+  int logM = 0;
+  while ((1 << logM) < M) ++logM;
+  spec.resize(M);
+  for (int i = 0; i < M; ++i) {
+    int r = i;
+    if (natural) {
+      r = 0;
+      for (int bit = 0; bit < logM; ++bit) r |= ((i >> bit) & 1) << (logM - 1 - bit);
+    }
+    spec[r] = filt[i] / (long double)M;
+  }
+}
+
 BluesteinTables make_bluestein(int n, int M_force) {
   BluesteinTables b;
   b.n = n;
@@ -285,28 +318,8 @@ BluesteinTables make_bluestein(int n, int M_force) {
   b.M = M;
   b.logM = 0;
   while ((1 << b.logM) < M) ++b.logM;
-  typedef std::complex<long double> cld;
-  std::vector<cld> chirp(n), filt(M, cld(0, 0));
-  for (int j = 0; j < n; ++j) {
-    long long r = ((long long)j * j) % (2LL * n);
-    long double ang = -PI_L * (long double)r / n;
-    chirp[j] = cld(cosl(ang), sinl(ang));
-  }
-  for (int j = 0; j < n; ++j) {
-    filt[j] = std::conj(chirp[j]);
-    if (j) filt[M - j] = std::conj(chirp[j]);
-  }
-  // iterative radix-2 DIF in long double: natural in, bit-reversed out -- the order the device wants
-  for (int s = M / 2; s >= 1; s >>= 1) {
-    for (int g = 0; g < M; g += 2 * s)
-      for (int p = 0; p < s; ++p) {
-        long double ang = -2 * PI_L * (long double)p * (M / (2 * s)) / M;
-        cld w(cosl(ang), sinl(ang));
-        cld u = filt[g + p], v = filt[g + p + s];
-        filt[g + p] = u + v;
-        filt[g + p + s] = (u - v) * w;
-      }
-  }
+  std::vector<std::complex<long double>> chirp, spec;
+  bluestein_chirp_spectrum(n, M, false, chirp, spec);  // (bit-reversed: the order the device wants)
   b.chirp.resize(2 * (size_t)n);
   for (int j = 0; j < n; ++j) {
     b.chirp[2 * j] = (double)chirp[j].real();
@@ -314,8 +327,8 @@ BluesteinTables make_bluestein(int n, int M_force) {
   }
   b.bhat.resize(2 * (size_t)M);
   for (int i = 0; i < M; ++i) {
-    b.bhat[2 * i] = (double)(filt[i].real() / M);
-    b.bhat[2 * i + 1] = (double)(filt[i].imag() / M);
+    b.bhat[2 * i] = (double)spec[i].real();
+    b.bhat[2 * i + 1] = (double)spec[i].imag();
   }
   b.tw.resize(M);
   for (int k = 0; k < M / 2; ++k) {

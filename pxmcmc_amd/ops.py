@@ -109,7 +109,7 @@ def raise_on_status(status, what):
     if status:
         bits = []
         if status & STATUS_PAIR_SYNC:
-            bits.append("a wave-pair wait or ring-group wait of the fused phi-DFT kernels expired (csrc/dft5.hip: d5_pair_sync, pfa_group_sync)")
+            bits.append("a wave-pair wait or ring-group wait of the fused phi-DFT kernels expired (csrc/dft_wave.h: d5_pair_sync)")
         if status & ~STATUS_PAIR_SYNC:
             bits.append(f"unknown status bits {status:#x}")
         raise PxmError(f"{what}: device status {status:#x}: " + "; ".join(bits) + " -- the results of this plan since its last "

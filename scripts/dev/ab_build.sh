@@ -1,6 +1,6 @@
 # A/B of library build variants (run on the GPU box from the repo root): variant libraries are built under
 # /tmp and loaded with PXM_LIB_PATH; prints ms per step and the DFT launch time with the f32-unit and the fp64 noise stream.
-#   bash scripts/dev/ab_build.sh "-DPXM_D5_ABLATE=1" "-DPXM_NOISE_F64_POLY" ...
+#   bash scripts/dev/ab_build.sh "-DPXM_NOISE_F64_POLY" ...
 set -o pipefail
 mkdir -p /tmp/pxm_ab
 i=0

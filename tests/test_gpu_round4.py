@@ -187,7 +187,7 @@ def test_sampler_noise_bits_64_graph_equals_eager_and_tracks_default():
 
 # ---- device status word ------------------------------------------------------------------------------------------
 def test_pair_sync_expiry_is_reported_not_silent(monkeypatch):
-    """The wave pairs of the fused phi-DFT kernels wait for each other with a BOUNDED LDS spin (csrc/dft5.hip,
+    """The wave pairs of the fused phi-DFT kernels wait for each other with a BOUNDED LDS spin (csrc/dft_wave.h,
     d5_pair_sync).  PXM_DEBUG_PAIR_SYNC_LIMIT=0 (read at plan creation) forces every wait to expire: the kernels run on
     (no hang), the plan's status word carries PXM_STATUS_PAIR_SYNC, and the sampler raises PxmError at its next
     observation point instead of returning a corrupted chain (the reference fails loudly on bad state,
