@@ -38,17 +38,17 @@ def _stream():
 
 
 class _Wavelets:
-    """one `pxm_wav_plan` (N = 1) or `pxm_dwav_plan` (N > 1, directional) per (L, B, J_min, N): pys2let is stateless,
-    the plans are cached here"""
+    """one `pxm_wav_plan` (N = 1, any spin) or `pxm_dwav_plan` (N > 1, directional, spin 0) per (L, B, J_min, N, spin):
+    pys2let is stateless, the plans are cached here"""
 
     cache = {}
 
-    def __init__(self, L, B, J_min, N=1):
+    def __init__(self, L, B, J_min, N=1, spin=0):
         self.plan = _vp()
         self.N = N
         nscal = C.c_int64()
-        if N == 1:
-            _ok(_LIB.pxm_wav_plan_create(int(L), C.c_double(B), int(J_min), 1, 0, C.byref(self.plan)))
+        if N == 1:  # spin s: spin-s images, spin-0 coefficients in the same layout (DESIGN.md section 12)
+            _ok(_LIB.pxm_wav_plan_create_spin(int(L), C.c_double(B), int(J_min), int(spin), 1, 0, C.byref(self.plan)))
             self.ncoefs = int(_ok(_LIB.pxm_wav_ncoefs(int(L), C.c_double(B), int(J_min), C.byref(nscal))))
         else:  # f_wav: the 2N - 1 orientation planes of every scale, one flat vector (DESIGN.md section 11)
             _ok(_LIB.pxm_dwav_plan_create(int(L), C.c_double(B), int(J_min), int(N), 1, 0, C.byref(self.plan)))
@@ -61,9 +61,11 @@ class _Wavelets:
 
     @classmethod
     def get(cls, B, L, J_min, N=1, spin=0, upsample=0):
-        if spin != 0 or upsample != 0:  # the reference's own defaults (pxmcmc/transforms.py:71,79-86)
-            raise NotImplementedError("pys2let_shim: spin-0, multiresolution (upsample=0) wavelets only")
-        key = (int(L), float(B), int(J_min), int(N))
+        if upsample != 0:  # the reference's own default (pxmcmc/transforms.py:79-86)
+            raise NotImplementedError("pys2let_shim: multiresolution (upsample=0) wavelets only")
+        if spin != 0 and N != 1:
+            raise NotImplementedError("pys2let_shim: spin wavelets are axisymmetric only (N = 1)")
+        key = (int(L), float(B), int(J_min), int(N), int(spin))
         if key not in cls.cache:
             cls.cache[key] = cls(*key)
         return cls.cache[key]

@@ -38,6 +38,7 @@ def main(argv=None):
     ap.add_argument("--nburn", type=int, default=0)
     ap.add_argument("--chains", type=int, default=1, help="independent chains batched on the GPU")
     ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
+    ap.add_argument("--spin", type=int, default=0, help="spin S of the field (S != 0: a complex spin-S field, dirs = 1)")
     ap.add_argument("--outdir", type=str, default=".")
     ap.add_argument("--jobid", type=str, default="0")
     args = ap.parse_args(argv)
@@ -47,17 +48,26 @@ def main(argv=None):
     # synthetic "topography": a band-limited real field with a red spectrum, sampled on the MW grid
     rng = np.random.default_rng(0)
     flm = np.zeros(L * L, dtype=complex)
-    for el in range(L):
-        m = np.arange(1, el + 1)
-        flm[el * el + el] = rng.normal() / (1 + el)
-        v = (rng.normal(size=el) + 1j * rng.normal(size=el)) / (np.sqrt(2) * (1 + el))
-        flm[el * el + el + m] = v
-        flm[el * el + el - m] = (-1.0) ** m * np.conj(v)
-    truth = ops.ShtPlan(L, 0).inverse(flm).cpu().numpy().real
-    truth /= np.sqrt(np.mean(truth ** 2))
-    data = truth + args.sigma * rng.normal(size=truth.size)
+    spin = args.spin
+    if spin == 0:
+        for el in range(L):
+            m = np.arange(1, el + 1)
+            flm[el * el + el] = rng.normal() / (1 + el)
+            v = (rng.normal(size=el) + 1j * rng.normal(size=el)) / (np.sqrt(2) * (1 + el))
+            flm[el * el + el + m] = v
+            flm[el * el + el - m] = (-1.0) ** m * np.conj(v)
+        truth = ops.ShtPlan(L, 0).inverse(flm).cpu().numpy().real
+    else:  # a spin-S field (shear, polarisation Q + iU) is complex: no l < |S| harmonics, no reality symmetry
+        for el in range(abs(spin), L):
+            flm[el * el : (el + 1) ** 2] = (rng.normal(size=2 * el + 1) + 1j * rng.normal(size=2 * el + 1)) / (np.sqrt(2) * (1 + el))
+        truth = ops.ShtPlan(L, spin).inverse(flm).cpu().numpy()
+    truth /= np.sqrt(np.mean(np.abs(truth) ** 2))
+    if spin == 0:
+        data = truth + args.sigma * rng.normal(size=truth.size)
+    else:
+        data = truth + args.sigma * (rng.normal(size=truth.size) + 1j * rng.normal(size=truth.size)) / np.sqrt(2)
 
-    forwardop = SphericalWaveletTransformOperator(data, args.sigma, setting, L, B, J_min, dirs=args.dirs,
+    forwardop = SphericalWaveletTransformOperator(data, args.sigma, setting, L, B, J_min, dirs=args.dirs, spin=spin,
                                                  max_chains=args.chains)
     lmda = 1e-6
     # step size inside the MYULA bound 1 / (L_f + 1 / lmda), L_f = ||S||^2 / sigma^2 (power iteration)
@@ -73,9 +83,9 @@ def main(argv=None):
         delta *= args.s ** 2
 
     params = PxMCMCParams(nsamples=args.nsamples, nburn=args.nburn, ngap=args.ngap, delta=delta, lmda=lmda, mu=args.mu,
-                          s=args.s, complex=False, verbosity=max(1, args.ngap * 10))
+                          s=args.s, complex=spin != 0, verbosity=max(1, args.ngap * 10))
     regulariser = S2_Wavelets_L1(setting, forwardop.transform.inverse, forwardop.transform.inverse_adjoint,
-                                 params.lmda * params.mu, L=L, B=B, J_min=J_min, dirs=args.dirs)
+                                 params.lmda * params.mu, L=L, B=B, J_min=J_min, dirs=args.dirs, spin=spin)
     print(f"Number of data points: {len(data)}")
     print(f"Number of model parameters: {forwardop.nparams}")
     cls = {"myula": MYULA, "pxmala": PxMALA, "skrock": SKROCK}[args.algo]
@@ -85,12 +95,15 @@ def main(argv=None):
     elapsed = datetime.now() - start
 
     path = save_mcmc(mcmc, params, args.outdir, filename=f"{args.algo}_{setting}_{args.jobid}", L=L, B=B, J_min=J_min,
-                     sigma=args.sigma, nparams=forwardop.nparams, setting=setting, time=str(elapsed), chains=args.chains)
+                     sigma=args.sigma, nparams=forwardop.nparams, setting=setting, time=str(elapsed), chains=args.chains,
+                     **({"spin": spin} if spin else {}))
     chain = mcmc.chain if args.chains == 1 else mcmc.chain[0]
-    images = chain_to_images(chain, forwardop.transform).real  # every saved sample mapped to the sphere
-    ci = credible_interval_range(images)
+    images = chain_to_images(chain, forwardop.transform)  # every saved sample mapped to the sphere
+    if spin == 0:
+        images = images.real
+    ci = credible_interval_range(images.real)  # (spin S: of the real part, e.g. Q of Q + iU)
     mean = images.mean(axis=0)
-    rel = np.sqrt(np.mean((mean - truth) ** 2)) / np.sqrt(np.mean(truth ** 2))
+    rel = np.sqrt(np.mean(np.abs(mean - truth) ** 2)) / np.sqrt(np.mean(np.abs(truth) ** 2))
     print(f"saved {path}; {mcmc.niter} iterations x {args.chains} chain(s) in {elapsed}; "
           f"posterior-mean error {rel:.3f} (noise {args.sigma:.3f}); median 95% CI width {np.median(ci):.3f}")
     return path, rel, ci

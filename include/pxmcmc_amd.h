@@ -54,7 +54,8 @@ int pxm_version(void);
 int pxm_noise_bits(void);
 /* Host-only (no GPU) check that every global address a launch of the plans' GEMM task lists and DFT groups can form
  * -- including the clamped / aliased loads whose values are discarded -- lies inside its buffer.  Builds the plans
- * named by `what` (1: SHT plan (L, spin); 2: wavelet plan (L, B, J_min) + Gram lists; 4: + weak-lensing lists) in
+ * named by `what` (1: SHT plan (L, spin); 2: wavelet plan (L, B, J_min) + Gram lists; 4: + weak-lensing lists; 8: the
+ * wavelet plan of bit 2 at `spin` instead of spin 0, without weak-lensing lists unless spin == 0) in
  * dry-run mode and returns the number of address ranges verified, < 0 on a violation (pxm_last_error names the task).
  * The same check runs at every real plan creation.  The dry-run switch is per thread (plans created concurrently on
  * other threads are real); not to be called during a stream capture. */
@@ -122,10 +123,14 @@ int pxm_sht_forward_adjoint(pxm_sht_plan_t plan, const void* flm, void* f, int C
 /* bytes of Legendre/Wigner ring table one transform launch streams (roofline accounting) */
 int64_t pxm_sht_table_bytes(pxm_sht_plan_t plan, int op /*0 inv,1 fwd,2 inv_adj,3 fwd_adj*/);
 
-/* ---- scale-discretised wavelet transform (N=1, spin 0, upsample=0) -------------- */
+/* ---- scale-discretised wavelet transform (N=1, upsample=0) -------------------- */
 /* replaces pys2let.synthesis_wav2px / synthesis_adjoint_px2wav / analysis_px2wav /
- * analysis_adjoint_wav2px (pxmcmc/transforms.py:95-98).  X: [C][ncoefs] c128, f: [C][L*(2L-1)] c128. */
+ * analysis_adjoint_wav2px (pxmcmc/transforms.py:95-98).  X: [C][ncoefs] c128, f: [C][L*(2L-1)] c128.
+ * pxm_wav_plan_create is the spin-0 plan; pxm_wav_plan_create_spin takes the spin s of the images (|s| < L): the
+ * coefficients stay spin-0 functions in the same layout, only the ring stage at L runs at spin s.
+ * A spin-s plan (s != 0) refuses pxm_wav_wl_attach and mode 2 (two real chains per slot) of the fused steps. */
 int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned flags, pxm_wav_plan_t* plan);
+int pxm_wav_plan_create_spin(int L, double B, int J_min, int spin, int max_chains, unsigned flags, pxm_wav_plan_t* plan);
 int pxm_wav_plan_destroy(pxm_wav_plan_t plan);
 int pxm_wav_synthesis(pxm_wav_plan_t plan, const void* X, void* f, int C, pxm_stream_t stream);
 int pxm_wav_synthesis_adjoint(pxm_wav_plan_t plan, const void* f, void* X, int C, pxm_stream_t stream);

@@ -71,6 +71,7 @@ SIGNATURES = {
     "pxm_dwav_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_dwav_plan_info": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "pxm_wav_plan_create": (c_int, [c_int, c_dbl, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),
+    "pxm_wav_plan_create_spin": (c_int, [c_int, c_dbl, c_int, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),
     "pxm_wav_plan_destroy": (c_int, [c_vp]),
     "pxm_wav_synthesis": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
     "pxm_wav_synthesis_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),

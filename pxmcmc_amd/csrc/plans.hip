@@ -411,6 +411,9 @@ static int side_pool(SidePool** out) {
 
 struct pxm_wav_plan_s {
   int L = 0, J_min = 0, J_max = 0, Cmax = 0, Cp = 0, ncol = 0, Rp = 0;
+  // spin of the images: only the L-level ring stage runs at it -- the coefficients of axisymmetric
+  // wavelets are spin-0 functions whatever the spin of f, so every per-scale stage stays the spin-0 one
+  int spin = 0;
   double B = 0;
   int nsc = 0;  // scaling + wavelet scales
   std::vector<int> bl;
@@ -570,19 +573,20 @@ static int wav_packed_lists(const pxm_wav_plan_s* p, int which, int kind, int tw
   return 0;
 }
 
-extern "C" {
-
-int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned flags, pxm_wav_plan_t* plan) {
-  (void)flags;
-  PXM_REQUIRE(plan, "pxm_wav_plan_create: null plan pointer");
-  PXM_REQUIRE(L >= 1 && B > 1.0 && J_min >= 0, "pxm_wav_plan_create: bad (L, B, J_min)");
-  PXM_REQUIRE(max_chains >= 1, "pxm_wav_plan_create: max_chains must be >= 1");
-  PXM_REQUIRE(dry_run() || pxm_device_count() > 0, "pxm_wav_plan_create: no HIP device visible (the HIP path is the only path)");
+// the one implementation behind pxm_wav_plan_create (spin 0) and pxm_wav_plan_create_spin; `who` names the entry point
+static int wav_plan_create_impl(const char* who, int L, double B, int J_min, int spin, int max_chains, pxm_wav_plan_t* plan) {
+  const std::string fn(who);
+  PXM_REQUIRE(plan, fn + ": null plan pointer");
+  PXM_REQUIRE(L >= 1 && B > 1.0 && J_min >= 0, fn + ": bad (L, B, J_min)");
+  PXM_REQUIRE(std::abs(spin) < L, fn + ": |spin| must be < L");
+  PXM_REQUIRE(max_chains >= 1, fn + ": max_chains must be >= 1");
+  PXM_REQUIRE(dry_run() || pxm_device_count() > 0, fn + ": no HIP device visible (the HIP path is the only path)");
   drain_deferred();
   // (owned by a guard until it is complete: every error return below releases what was built so far)
   std::unique_ptr<pxm_wav_plan_s, int (*)(pxm_wav_plan_t)> guard(new pxm_wav_plan_s(), pxm_wav_plan_destroy);
   pxm_wav_plan_s* p = guard.get();
   p->L = L;
+  p->spin = spin;
   p->B = B;
   p->J_min = J_min;
   p->J_max = j_max(L, B);
@@ -592,7 +596,7 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
   p->Rp = round_up(L, 16);
   p->bl = wav_bandlimits(L, B, J_min);
   p->nsc = (int)p->bl.size();
-  PXM_REQUIRE(p->nsc <= WAV_MAX_SCALES, "pxm_wav_plan_create: more than 39 wavelet scales are not supported");
+  PXM_REQUIRE(p->nsc <= WAV_MAX_SCALES, fn + ": more than 39 wavelet scales are not supported");
   int64_t off = 0;
   for (int b : p->bl) {
     p->coef_off.push_back(off);
@@ -602,7 +606,7 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
   int rc;
   if ((rc = status_alloc(&p->d_status))) return rc;
   // tables: every scale needs the forward pair (synthesis: FWD, its adjoint: FWD_ADJ) and, for the
-  // analysis setting, the inverse pair at its own bandlimit; L needs all four.
+  // analysis setting, the inverse pair at its own bandlimit (spin 0); L needs all four, at the plan's spin.
   p->T.resize(p->nsc);
   p->dft.resize(p->nsc);
   for (int s = 0; s < p->nsc; ++s) {
@@ -613,7 +617,7 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
     if (rc) return rc;
     p->dft[s].d_status = p->d_status;  // (before the DFT group is built: its entries carry a copy)
   }
-  rc = get_tables(L, 0, 0xF, &p->TL);
+  rc = get_tables(L, spin, 0xF, &p->TL);
   if (rc) return rc;
   wav_hold(p, p->TL);
   rc = make_dft_plan(L, &p->dftL);
@@ -637,12 +641,13 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
   if ((rc = dev_alloc(&p->ws, (size_t)w * sizeof(double), "wavelet plan workspace"))) return rc;
   if ((rc = dev_zero(p->ws, (size_t)w * sizeof(double)))) return rc;
   // wavelet kernels: synthesis f_lm = kappa0 W^phi + sqrt(2pi) sum_j kappa_j W^j; analysis W^j = kappa_j f / sqrt(2pi)
+  // (spin s: rows el < |s| zero -- a spin-s field has no harmonics there)
   std::vector<double> k0, kap;
   tiling_axisym(L, B, J_min, k0, kap);
   std::vector<double> kc_syn((size_t)p->nsc * p->Rp, 0.0), kc_ana((size_t)p->nsc * p->Rp, 0.0);
   const double cs = std::sqrt(2.0 * M_PI), ca = 1.0 / std::sqrt(2.0 * M_PI);
   for (int s = 0; s < p->nsc; ++s)
-    for (int el = 0; el < p->bl[s]; ++el) {
+    for (int el = std::abs(spin); el < p->bl[s]; ++el) {
       const double k = (s == 0) ? k0[el] : kap[(size_t)(J_min + s - 1) * L + el];
       kc_syn[(size_t)s * p->Rp + el] = (s == 0) ? k : cs * k;
       kc_ana[(size_t)s * p->Rp + el] = (s == 0) ? k : ca * k;
@@ -691,20 +696,22 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
   if ((rc = upload_tasks(v_adj_fwdadj, true, &p->adj_fwdadj, p->bl, p->ncol, p->ws, "synthesis-adjoint forward-adjoint (all scales)", el_lo, pk, shared))) return rc;
   if ((rc = upload_tasks(v_ana_inv, true, &p->ana_inv, p->bl, p->ncol, p->ws, "analysis inverse (all scales)", el_lo))) return rc;
   if ((rc = upload_tasks(v_anadj_invadj, true, &p->anadj_invadj, p->bl, p->ncol, p->ws, "analysis-adjoint inverse-adjoint (all scales)", el_lo))) return rc;
+  // the L-level stages: spin 0 pairs +-m on one table, spin s != 0 stores every m (unpaired lists, one slab per task)
+  const bool pairedL = p->TL->paired;
   v.clear();
   GemmFuse sum2;
   sum2.x2_base = p->offHB;
   append_gemm_tasks(*p->TL, TAB_INV, p->ncol, p->offHA, L, p->Rp, p->offGL, L, p->Rp, nullptr, p->offS, p->ws, v, 0, sum2);
-  if ((rc = upload_tasks(v, true, &p->syn_inv, {L}, p->ncol, p->ws, "synthesis inverse at L"))) return rc;
+  if ((rc = upload_tasks(v, pairedL, &p->syn_inv, {L}, p->ncol, p->ws, "synthesis inverse at L"))) return rc;
   v.clear();
   append_gemm_tasks(*p->TL, TAB_INV_ADJ, p->ncol, p->offGL, L, p->Rp, p->offHL, L, p->Rp, nullptr, p->offS, p->ws, v);
-  if ((rc = upload_tasks(v, true, &p->adj_invadj, {L}, p->ncol, p->ws, "inverse-adjoint at L"))) return rc;
+  if ((rc = upload_tasks(v, pairedL, &p->adj_invadj, {L}, p->ncol, p->ws, "inverse-adjoint at L"))) return rc;
   v.clear();
   append_gemm_tasks(*p->TL, TAB_FWD, p->ncol, p->offGL, L, p->Rp, p->offHL, L, p->Rp, nullptr, p->offS, p->ws, v);
-  if ((rc = upload_tasks(v, true, &p->ana_fwd, {L}, p->ncol, p->ws, "analysis forward at L"))) return rc;
+  if ((rc = upload_tasks(v, pairedL, &p->ana_fwd, {L}, p->ncol, p->ws, "analysis forward at L"))) return rc;
   v.clear();
   append_gemm_tasks(*p->TL, TAB_FWD_ADJ, p->ncol, p->offHA, L, p->Rp, p->offGL, L, p->Rp, nullptr, p->offS, p->ws, v, 0, sum2);
-  if ((rc = upload_tasks(v, true, &p->anadj_fwdadj, {L}, p->ncol, p->ws, "analysis-adjoint forward-adjoint at L"))) return rc;
+  if ((rc = upload_tasks(v, pairedL, &p->anadj_fwdadj, {L}, p->ncol, p->ws, "analysis-adjoint forward-adjoint at L"))) return rc;
   // scales at the full bandlimit stay on the caller's stream; the rest are dealt over the side streams
   p->lane_of.assign(p->nsc, -1);
   SidePool* sp = nullptr;
@@ -723,6 +730,18 @@ int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned fla
   if (rc < 0) return rc;  // rc == 1: no group -> per-scale launches
   *plan = guard.release();
   return 0;
+}
+
+extern "C" {
+
+int pxm_wav_plan_create(int L, double B, int J_min, int max_chains, unsigned flags, pxm_wav_plan_t* plan) {
+  (void)flags;
+  return wav_plan_create_impl("pxm_wav_plan_create", L, B, J_min, 0, max_chains, plan);
+}
+
+int pxm_wav_plan_create_spin(int L, double B, int J_min, int spin, int max_chains, unsigned flags, pxm_wav_plan_t* plan) {
+  (void)flags;
+  return wav_plan_create_impl("pxm_wav_plan_create_spin", L, B, J_min, spin, max_chains, plan);
 }
 
 int pxm_wav_plan_destroy(pxm_wav_plan_t p) {
@@ -1045,6 +1064,8 @@ static int wav_update_out(pxm_wav_plan_t p, const char* fn, const void* X, const
                           PxOut* out) {
   PXM_REQUIRE(X != X_out, std::string(fn) + ": X_out must not alias X");
   PXM_REQUIRE((mode & ~PXM_NOISE_F64) >= 0 && (mode & ~PXM_NOISE_F64) <= 2, std::string(fn) + ": mode must be 0, 1 or 2 (| PXM_NOISE_F64)");
+  PXM_REQUIRE(p->spin == 0 || (mode & ~PXM_NOISE_F64) != 2,
+              std::string(fn) + ": mode 2 (two real chains per complex slot) needs a spin-0 plan: a spin-s image is never real");
   out->f = (double*)X_out;
   out->X = (const double*)X;
   out->T = T;
@@ -1153,7 +1174,7 @@ extern "C" {
 static int wav_make_gram_lists(pxm_wav_plan_t p) {
   int rc;
   if (!p->gram.d) {
-    if ((rc = get_tables(p->L, 0, 1u << TAB_GRAM, &p->TL))) return rc;
+    if ((rc = get_tables(p->L, p->spin, 1u << TAB_GRAM, &p->TL))) return rc;
     wav_hold(p, p->TL);
     std::vector<GemmTask> v;
     GemmFuse fz;
@@ -1161,12 +1182,12 @@ static int wav_make_gram_lists(pxm_wav_plan_t p) {
     fz.hd_base = p->offHDc;
     fz.hd_stride = 2;
     append_gemm_tasks(*p->TL, TAB_GRAM, p->ncol, p->offHA, p->L, p->Rp, p->offHL, p->L, p->Rp, nullptr, p->offS, p->ws, v, 0, fz);
-    if ((rc = upload_tasks(v, true, &p->gram, {p->L}, p->ncol, p->ws, "Gram step"))) return rc;
+    if ((rc = upload_tasks(v, p->TL->paired, &p->gram, {p->L}, p->ncol, p->ws, "Gram step"))) return rc;
     p->gram.gram = true;
     p->gram.gram_table_bytes = (double)p->TL->bytes[TAB_GRAM];
     v.clear();
     append_gemm_tasks(*p->TL, TAB_INV_ADJ, p->ncol, p->offGD, p->L, p->Rp, p->offHD, p->L, p->Rp, nullptr, p->offS, p->ws, v);
-    if ((rc = upload_tasks(v, true, &p->adj_invadj_D, {p->L}, p->ncol, p->ws, "inverse-adjoint of the data rings"))) return rc;
+    if ((rc = upload_tasks(v, p->TL->paired, &p->adj_invadj_D, {p->L}, p->ncol, p->ws, "inverse-adjoint of the data rings"))) return rc;
   }
   return 0;
 }
@@ -1348,6 +1369,8 @@ static int wl_attach_impl(pxm_wav_plan_t p, const int32_t* pix2data, const doubl
 
 int pxm_wav_wl_attach(pxm_wav_plan_t p, const int32_t* pix2data, const double* weight, int64_t ndata) {
   PXM_REQUIRE(p, "pxm_wav_wl_attach: null plan");
+  PXM_REQUIRE(p->spin == 0, "pxm_wav_wl_attach: the weak-lensing kernel k_l maps a spin-0 field to the shear; this plan has spin " +
+                                std::to_string(p->spin));
   PXM_REQUIRE(!p->wl_failed, "pxm_wav_wl_attach: an earlier attach of this plan failed part-way; destroy the plan");
   const int rc = wl_attach_impl(p, pix2data, weight, ndata);
   if (rc) p->wl_failed = true;
@@ -1451,7 +1474,8 @@ int64_t pxm_wav_table_bytes(pxm_wav_plan_t p, int op) {
 // Host-only check of the address ranges (no GPU): runs the REAL plan builders in dry-run mode -- fake device
 // addresses, uploads and table kernels skipped -- so that every GEMM task list and DFT group entry of an SHT plan
 // (what & 1: bandlimit L, spin) and / or a wavelet plan (what & 2: (L, B, J_min), its Gram lists, and with what & 4
-// its weak-lensing lists) goes through check_gemm_task_ranges / the group check.  Returns the number of address
+// its weak-lensing lists; what & 8: the wavelet plan at `spin` instead of spin 0 -- weak-lensing lists only at spin 0)
+// goes through check_gemm_task_ranges / the group check.  Returns the number of address
 // ranges verified, < 0 (and pxm_last_error) if one leaves its buffer.  Test aid: PXM_RANGE_SELFTEST="<text>:<bytes>"
 // registers the dry-run allocations whose description contains <text> that much shorter (host_api.cpp) -- e.g. the
 // per-row scale vectors one row tile short, the round-2 fault -- and the check must then refuse the plan.
@@ -1469,9 +1493,10 @@ int64_t pxm_host_check_address_ranges(int L, double B, int J_min, int spin, int 
   }
   if (!rc && (what & 2)) {
     pxm_wav_plan_t wp = nullptr;
-    rc = pxm_wav_plan_create(L, B, J_min, max_chains, 0, &wp);
+    const int wspin = (what & 8) ? spin : 0;
+    rc = pxm_wav_plan_create_spin(L, B, J_min, wspin, max_chains, 0, &wp);
     if (!rc) rc = wav_make_gram_lists(wp);
-    if (!rc && (what & 4) && L >= 3) rc = pxm_wav_wl_attach(wp, nullptr, nullptr, (int64_t)L * (2 * L - 1));
+    if (!rc && (what & 4) && L >= 3 && wspin == 0) rc = pxm_wav_wl_attach(wp, nullptr, nullptr, (int64_t)L * (2 * L - 1));
     if (wp) pxm_wav_plan_destroy(wp);
   }
   tables_trim();  // the dry-run table entries (fake addresses) never outlive the call

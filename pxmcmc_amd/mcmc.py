@@ -557,6 +557,7 @@ class MYULA(PxMCMC):
         f = self.forward
         return bool(
             self._fused_wav and self.real_pairs and not self.complex
+            and self.forward.transform.spin == 0  # (a spin-s image is never real: the pair mode is spin 0 only)
             and not f.data_dev.is_complex() and not f.invcov.diag.is_complex()
             and (not X.is_complex() or not bool((X.imag != 0).any()))
         )

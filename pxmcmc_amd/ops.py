@@ -537,17 +537,19 @@ class ShtPlan(_Plan):
 
 
 class WavPlan(_Plan):
-    """Axisymmetric scale-discretised wavelet transforms (replaces the pys2let calls)."""
+    """Axisymmetric scale-discretised wavelet transforms (replaces the pys2let calls).  ``spin``: spin of the images;
+    the coefficients are spin-0 functions in the same layout whatever it is."""
 
-    def __init__(self, L, B, J_min, max_chains=1):
+    def __init__(self, L, B, J_min, max_chains=1, spin=0):
         require_gpu()
         self.L, self.B, self.J_min, self.max_chains = int(L), float(B), int(J_min), int(max_chains)
+        self.spin = int(spin)
         self.npix = L * (2 * L - 1)
         nscal = C.c_int64()
         self.ncoefs = int(check(lib.pxm_wav_ncoefs(self.L, self.B, self.J_min, C.byref(nscal))))
         self.nscal = int(nscal.value)
-        super().__init__(lib.pxm_wav_plan_create, (self.L, self.B, self.J_min, self.max_chains, 0), lib.pxm_wav_plan_destroy,
-                         lib.pxm_wav_status, f"WavPlan(L={self.L})")
+        super().__init__(lib.pxm_wav_plan_create_spin, (self.L, self.B, self.J_min, self.spin, self.max_chains, 0),
+                         lib.pxm_wav_plan_destroy, lib.pxm_wav_status, f"WavPlan(L={self.L}, spin={self.spin})")
 
     def synthesis(self, X, out=None):
         return self._run(lib.pxm_wav_synthesis, X, self.ncoefs, self.npix, out=out)

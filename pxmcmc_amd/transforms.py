@@ -46,8 +46,9 @@ class IdentityTransform(Transform):
 
 class SphericalWaveletTransform(Transform):
     """
-    Spherical wavelet transforms (pxmcmc/transforms.py:59-166), pixel space, ``upsample=0``, spin 0.  ``dirs = N > 1``:
-    directional wavelets; each wavelet block holds 2N - 1 orientation planes.
+    Spherical wavelet transforms (pxmcmc/transforms.py:59-166), pixel space, ``upsample=0``.  ``dirs = N > 1``:
+    directional wavelets; each wavelet block holds 2N - 1 orientation planes.  ``spin != 0``
+    (``dirs = 1`` only): images are spin-s MW maps, the coefficients keep the spin-0 layout.
 
     :param int max_chains: largest chain batch the transform will be called with (extension)
     """
@@ -56,10 +57,15 @@ class SphericalWaveletTransform(Transform):
         if harmonic:
             # the harmonic variants are not in released pys2let either (reference tests/test_transforms.py:9-11)
             raise NotImplementedError("harmonic=True is out of scope (SURVEY.md section 2, row 3)")
-        if spin != 0:
-            raise NotImplementedError("only spin-0 wavelets are on the hot path (spin wavelets: DESIGN.md section 11)")
         if int(dirs) != dirs or dirs < 1:
             raise ValueError("dirs must be a positive integer")
+        if int(spin) != spin:
+            raise ValueError("spin must be an integer")
+        if spin != 0 and dirs != 1:
+            raise NotImplementedError("spin wavelets are axisymmetric only (dirs = 1; DESIGN.md section 12)")
+        if abs(spin) >= L:
+            raise ValueError("|spin| must be < L")
+        spin = int(spin)
         self.L = L
         self.B = B
         self.J_min = J_min
@@ -75,7 +81,7 @@ class SphericalWaveletTransform(Transform):
     def _make_plan(self, C):
         """dirs = 1: the axisymmetric plan with the fused sampler steps; dirs > 1: the directional plan (SO(3) stages)"""
         if self.dirs == 1:
-            return ops.WavPlan(self.L, self.B, self.J_min, max_chains=C)
+            return ops.WavPlan(self.L, self.B, self.J_min, max_chains=C, spin=self.spin)
         return ops.DirWavPlan(self.L, self.B, self.J_min, int(self.dirs), max_chains=C)
 
     def ensure_chains(self, C):

@@ -74,13 +74,14 @@ def dir_component(L, N):
 
 
 def wavelet_tiling(B, L, N=1, J_min=0, spin=0):
-    """[ext] pys2let.wavelet_tiling (pxmcmc/utils.py:117, prior.py:121,132) for spin-0 wavelets:
+    """[ext] pys2let.wavelet_tiling (pxmcmc/utils.py:117, prior.py:121,132):
     ``phi_l[L] = sqrt((2l+1)/4pi) kappa0(l)`` and ``psi_lm[L*L, nscales]`` with
     ``psi_lm = sqrt((2l+1)/8pi^2) kappa_j(l) s_lm``, one column per scale j = J_min..J_max; s_lm is the directionality
     component (:func:`dir_component`, s_l0 = 1 for N = 1).  The harmonic normalisation is parity-unpinned (DESIGN.md
-    section 2); only supports, ``sum |.|^2`` and peak degrees are consumed by the callers."""
-    if spin != 0:
-        raise NotImplementedError("only spin-0 wavelets are on the hot path")
+    section 2); only supports, ``sum |.|^2`` and peak degrees are consumed by the callers.  ``spin = s != 0`` (N = 1
+    only): the spin-0 tiling with every degree l < |s| zeroed."""
+    if spin != 0 and N != 1:
+        raise NotImplementedError("spin wavelets are axisymmetric only (N = 1)")
     k0, k = ops.tiling_axisym(L, B, J_min)
     el = np.arange(L)
     phi_l = np.sqrt((2 * el + 1) / (4 * np.pi)) * k0
@@ -88,6 +89,9 @@ def wavelet_tiling(B, L, N=1, J_min=0, spin=0):
     if N == 1:
         for col, j in enumerate(range(J_min, k.shape[0])):
             psi_lm[el * el + el, col] = np.sqrt((2 * el + 1) / (8 * np.pi ** 2)) * k[j]
+        if spin != 0:
+            phi_l[: abs(spin)] = 0.0
+            psi_lm[: abs(spin) ** 2] = 0.0
         return phi_l, psi_lm
     s = dir_component(L, N)
     ell = np.repeat(el, 2 * el + 1)
