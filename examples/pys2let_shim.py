@@ -24,6 +24,8 @@ _LIB.pxm_last_error.restype = C.c_char_p
 _LIB.pxm_wav_ncoefs.restype = C.c_int64
 _LIB.pxm_dwav_ncoefs.restype = C.c_int64
 _LIB.pxm_dwav_ncoefs.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]
+_LIB.pxm_hwav_ncoefs.restype = C.c_int64
+_LIB.pxm_hwav_ncoefs.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]
 _vp = C.c_void_p
 
 
@@ -38,34 +40,39 @@ def _stream():
 
 
 class _Wavelets:
-    """one `pxm_wav_plan` (N = 1, any spin) or `pxm_dwav_plan` (N > 1, directional, spin 0) per (L, B, J_min, N, spin):
-    pys2let is stateless, the plans are cached here"""
+    """one `pxm_wav_plan` (N = 1, any spin), `pxm_dwav_plan` (N > 1, directional, spin 0) or, for the lm <-> lmn
+    functions, `pxm_hwav_plan` (harmonic space) per (L, B, J_min, N, spin, harmonic): pys2let is
+    stateless, the plans are cached here"""
 
     cache = {}
 
-    def __init__(self, L, B, J_min, N=1, spin=0):
+    def __init__(self, L, B, J_min, N=1, spin=0, harmonic=False):
         self.plan = _vp()
         self.N = N
+        self.prefix = "pxm_hwav_" if harmonic else "pxm_wav_" if N == 1 else "pxm_dwav_"
         nscal = C.c_int64()
-        if N == 1:  # spin s: spin-s images, spin-0 coefficients in the same layout (DESIGN.md section 12)
+        if harmonic:  # f_lm in, [scaling | (j, n) blocks of bl_j^2] out
+            _ok(_LIB.pxm_hwav_plan_create(int(L), C.c_double(B), int(J_min), int(N), int(spin), 1, 0, C.byref(self.plan)))
+            self.ncoefs = int(_ok(_LIB.pxm_hwav_ncoefs(int(L), B, int(J_min), int(N), C.byref(nscal))))
+        elif N == 1:  # spin s: spin-s images, spin-0 coefficients in the same layout (DESIGN.md section 12)
             _ok(_LIB.pxm_wav_plan_create_spin(int(L), C.c_double(B), int(J_min), int(spin), 1, 0, C.byref(self.plan)))
             self.ncoefs = int(_ok(_LIB.pxm_wav_ncoefs(int(L), C.c_double(B), int(J_min), C.byref(nscal))))
         else:  # f_wav: the 2N - 1 orientation planes of every scale, one flat vector (DESIGN.md section 11)
             _ok(_LIB.pxm_dwav_plan_create(int(L), C.c_double(B), int(J_min), int(N), 1, 0, C.byref(self.plan)))
             self.ncoefs = int(_ok(_LIB.pxm_dwav_ncoefs(int(L), B, int(J_min), int(N), C.byref(nscal))))
-        self.nscal, self.npix = int(nscal.value), L * (2 * L - 1)
+        self.nscal, self.npix = int(nscal.value), L * L if harmonic else L * (2 * L - 1)  # (npix: length of f or f_lm)
 
     def fn(self, name):
         """the C entry point of one of the four transforms for this plan's kind"""
-        return getattr(_LIB, ("pxm_wav_" if self.N == 1 else "pxm_dwav_") + name)
+        return getattr(_LIB, self.prefix + name)
 
     @classmethod
-    def get(cls, B, L, J_min, N=1, spin=0, upsample=0):
+    def get(cls, B, L, J_min, N=1, spin=0, upsample=0, harmonic=False):
         if upsample != 0:  # the reference's own default (pxmcmc/transforms.py:79-86)
             raise NotImplementedError("pys2let_shim: multiresolution (upsample=0) wavelets only")
         if spin != 0 and N != 1:
             raise NotImplementedError("pys2let_shim: spin wavelets are axisymmetric only (N = 1)")
-        key = (int(L), float(B), int(J_min), int(N), int(spin))
+        key = (int(L), float(B), int(J_min), int(N), int(spin), bool(harmonic))
         if key not in cls.cache:
             cls.cache[key] = cls(*key)
         return cls.cache[key]
@@ -136,6 +143,31 @@ def synthesis_adjoint_px2wav(f, B, L, J_min, N=1, spin=0, upsample=0):
     """pxmcmc/transforms.py:138 -> (f_wav, f_scal)"""
     w = _Wavelets.get(B, L, J_min, N, spin, upsample)
     return w.split(w.call(w.fn("synthesis_adjoint"), f, w.npix, w.ncoefs))
+
+
+# harmonic space (pxmcmc/transforms.py:89-93 with harmonic=True): f_lm [L^2] instead of the MW image
+def analysis_lm2lmn(flm, B, L, J_min, N=1, spin=0, upsample=0):
+    """-> (f_wav, f_scal)"""
+    w = _Wavelets.get(B, L, J_min, N, spin, upsample, harmonic=True)
+    return w.split(w.call(w.fn("analysis"), flm, w.npix, w.ncoefs))
+
+
+def analysis_adjoint_lmn2lm(f_wav, f_scal, B, L, J_min, N=1, spin=0, upsample=0):
+    """-> f_lm"""
+    w = _Wavelets.get(B, L, J_min, N, spin, upsample, harmonic=True)
+    return w.call(w.fn("analysis_adjoint"), np.concatenate((f_scal, np.ravel(f_wav, order="F"))), w.ncoefs, w.npix)
+
+
+def synthesis_lmn2lm(f_wav, f_scal, B, L, J_min, N=1, spin=0, upsample=0):
+    """-> f_lm"""
+    w = _Wavelets.get(B, L, J_min, N, spin, upsample, harmonic=True)
+    return w.call(w.fn("synthesis"), np.concatenate((f_scal, np.ravel(f_wav, order="F"))), w.ncoefs, w.npix)
+
+
+def synthesis_adjoint_lm2lmn(flm, B, L, J_min, N=1, spin=0, upsample=0):
+    """-> (f_wav, f_scal)"""
+    w = _Wavelets.get(B, L, J_min, N, spin, upsample, harmonic=True)
+    return w.split(w.call(w.fn("synthesis_adjoint"), flm, w.npix, w.ncoefs))
 
 
 # ---- pyssht (MW sampling, the reference's default Method) -----------------------------------------------------------

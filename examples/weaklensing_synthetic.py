@@ -11,6 +11,9 @@ reads a HEALPix kappa map with healpy, absent here):
       -> build_mask(L, size) (Euclid-like: ecliptic band + galactic plane, pxmcmc/utils.py:320-349), ngal = 30
       -> ForwardOperator(gammas, 1 / inv_cov, setting, SphericalWaveletTransform, WeakLensing)
       -> S2_Wavelets_L1 -> MYULA / PxMALA(tune_delta=True) / SKROCK -> save_mcmc.
+With --harmonic the posterior lives in harmonic space: the data are the shear harmonics of the smoothed field (full sky,
+no mask), the operator is WeakLensingHarmonic with SphericalWaveletTransform(harmonic=True), the prior L1, and the chain
+starts from the wavelet analysis of the Kaiser-Squires estimate (WeakLensingHarmonic.sks_estimate).
 
     python examples/weaklensing_synthetic.py --L 64 --algo pxmala --nsamples 20 --ngap 20 --nburn 100 --outdir /tmp
 """
@@ -27,8 +30,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pxmcmc_amd import ops  # noqa: E402
 from pxmcmc_amd.forward import ForwardOperator  # noqa: E402
 from pxmcmc_amd.mcmc import MYULA, SKROCK, PxMALA, PxMCMCParams  # noqa: E402
-from pxmcmc_amd.measurements import WeakLensing  # noqa: E402
-from pxmcmc_amd.prior import S2_Wavelets_L1  # noqa: E402
+from pxmcmc_amd.measurements import WeakLensing, WeakLensingHarmonic  # noqa: E402
+from pxmcmc_amd.prior import L1, S2_Wavelets_L1  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
 from pxmcmc_amd.transforms import SphericalWaveletTransform  # noqa: E402
 from pxmcmc_amd.utils import build_mask  # noqa: E402
@@ -81,9 +84,13 @@ def main(argv=None):
     ap.add_argument("--chains", type=int, default=1, help="independent chains batched on the GPU")
     ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--harmonic", action="store_true",
+                    help="harmonic-space posterior: WeakLensingHarmonic + harmonic wavelets + L1, started from sks_estimate")
     args = ap.parse_args(argv)
 
     L, B, J_min, setting = args.L, 2, 2, args.setting  # main.py:85-88
+    if args.harmonic:
+        return _main_harmonic(args, L, B, J_min, setting)
 
     # Euclid-like mask and synthetic shear data (main.py:90-93)
     mask = build_mask(L, size=args.mask_size)
@@ -125,6 +132,49 @@ def main(argv=None):
           f"per iteration; posterior-mean kappa error on the unmasked sky {rel:.3f}; masked fraction {1 - seen.mean():.3f}")
     return {"path": path, "rel_err": rel, "ms_per_iter": elapsed / max(niter, 1) * 1e3, "mcmc": mcmc,
             "operator": forward_operator, "mask": mask, "gammas": gammas_truth}
+
+
+def _main_harmonic(args, L, B, J_min, setting):
+    """--harmonic: shear harmonics glm = k_l (b_l kappa_lm) + noise, full sky; start point = analysis(sks_estimate(glm))"""
+    if setting != "synthesis":
+        raise ValueError("--harmonic runs the synthesis setting")
+    measurement = WeakLensingHarmonic(L)
+    klm_truth = synthetic_kappa_lm(L, args.seed) * beam(L)
+    sig_d = 0.37 / np.sqrt(2 * 30.0)  # shape noise of 30 galaxies per sample, per component
+    rng = np.random.default_rng(args.seed + 1)
+    glm = measurement.forward(klm_truth) + sig_d * (rng.normal(size=L * L) + 1j * rng.normal(size=L * L))
+    glm[:4] = 0
+    transform = SphericalWaveletTransform(L, B, J_min, dirs=args.dirs, harmonic=True, max_chains=args.chains)
+    forward_operator = ForwardOperator(glm, sig_d, setting, transform=transform, measurement=measurement,
+                                       nparams=transform.ncoefs)
+    params = PxMCMCParams(nsamples=args.nsamples, nburn=args.nburn, ngap=args.ngap, delta=args.delta, lmda=args.delta / 2,
+                          mu=args.mu, s=args.s, complex=True, verbosity=max(1, args.ngap * 10))
+    prior = L1(setting, None, None, params.lmda * params.mu)
+    X0 = transform.forward(measurement.sks_estimate(glm))
+    print(f"harmonic set-up: {L * L} shear harmonics, {forward_operator.nparams} wavelet coefficients")
+    if args.algo == "myula":
+        mcmc = MYULA(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
+    elif args.algo == "pxmala":
+        mcmc = PxMALA(forward_operator, prior, params, tune_delta=True, nchains=args.chains, seed=args.seed)
+    elif args.algo == "skrock":
+        mcmc = SKROCK(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
+    else:
+        raise ValueError("algo must be 'myula', 'pxmala' or 'skrock'")
+    now = datetime.now()
+    t0 = time.perf_counter()
+    mcmc.run(start_point=X0)
+    elapsed = time.perf_counter() - t0
+    filename = f"{args.algo}_harmonic_{setting}_{now.strftime('%d%m%y_%H%M%S')}_{args.jobid}"
+    path = save_mcmc(mcmc, params, args.outdir, filename=filename, L=L, B=B, J_min=J_min, nparams=forward_operator.nparams,
+                     setting=setting, time=str(elapsed), chains=args.chains)
+    chain = mcmc.chain if args.chains == 1 else mcmc.chain[0]
+    klm_mean = np.asarray(transform.inverse(chain.mean(axis=0)))
+    rel = np.linalg.norm(klm_mean[4:] - klm_truth[4:]) / np.linalg.norm(klm_truth[4:])
+    niter = int(mcmc.niter)
+    print(f"saved {path}; {niter} iterations x {args.chains} chain(s) in {elapsed:.2f} s = {elapsed / max(niter, 1) * 1e3:.3f} ms "
+          f"per iteration; posterior-mean kappa_lm error {rel:.3f} (harmonic, fused step: {getattr(mcmc, '_fused_harm', False)})")
+    return {"path": path, "rel_err": rel, "ms_per_iter": elapsed / max(niter, 1) * 1e3, "mcmc": mcmc,
+            "operator": forward_operator, "gammas": glm}
 
 
 if __name__ == "__main__":

@@ -35,6 +35,7 @@ extern "C" {
 typedef struct pxm_sht_plan_s* pxm_sht_plan_t;
 typedef struct pxm_wav_plan_s* pxm_wav_plan_t;
 typedef struct pxm_dwav_plan_s* pxm_dwav_plan_t;
+typedef struct pxm_hwav_plan_s* pxm_hwav_plan_t;
 typedef void* pxm_stream_t; /* hipStream_t */
 
 /* ---- library ------------------------------------------------------------ */
@@ -160,6 +161,41 @@ int64_t pxm_dwav_table_bytes(pxm_dwav_plan_t plan);
 int pxm_dwav_status(pxm_dwav_plan_t plan, int clear, pxm_stream_t stream);
 /* launch shapes (test / timing aid): (block, n) items, workgroups per chain of the harmonic-split and gamma launches */
 int pxm_dwav_plan_info(pxm_dwav_plan_t plan, int* nitems, int* split_blocks, int* gamma_blocks);
+
+/* Harmonic-space wavelet transforms (pys2let analysis_lm2lmn / synthesis_lmn2lm and their adjoints):
+ * inputs and outputs are spherical-harmonic coefficients.  f_lm [C][L*L] (ssht index l^2 + l + m, spin-s coefficients);
+ * X [C][ncoefs] = [scaling: bl_0^2 | j = J_min .. J_max: n = -(N-1), -(N-3), .., N-1: bl_j^2 each], every block
+ * ssht-indexed.
+ *   analysis   W^{j,n}_lm = sqrt(8 pi^2/(2l+1)) kappa_j(l) conj(s_ln) f_lm,   S_lm = kappa_0(l) f_lm
+ *   synthesis  f_lm = kappa_0(l) S_lm + sum_{j,n} sqrt((2l+1)/(8 pi^2)) kappa_j(l) s_ln W^{j,n}_lm
+ * and the two conjugate transposes.  Entries with l < max(|n|, |spin|) are zero after analysis and ignored by synthesis.
+ * N >= 1 at spin 0, N = 1 at any |spin| < L.  No SHT plan; nothing is allocated after creation; every call runs on the
+ * given stream (graph-capturable).  Outputs must not alias inputs. */
+int pxm_hwav_plan_create(int L, double B, int J_min, int N, int spin, int max_chains, unsigned flags, pxm_hwav_plan_t* plan);
+int pxm_hwav_plan_destroy(pxm_hwav_plan_t plan);
+int pxm_hwav_synthesis(pxm_hwav_plan_t plan, const void* X, void* flm, int C, pxm_stream_t stream);
+int pxm_hwav_synthesis_adjoint(pxm_hwav_plan_t plan, const void* flm, void* X, int C, pxm_stream_t stream);
+int pxm_hwav_analysis(pxm_hwav_plan_t plan, const void* flm, void* X, int C, pxm_stream_t stream);
+int pxm_hwav_analysis_adjoint(pxm_hwav_plan_t plan, const void* X, void* flm, int C, pxm_stream_t stream);
+/* host-only: number of coefficients of the harmonic layout, scaling block (bl_0^2) in *nscal_out */
+int64_t pxm_hwav_ncoefs(int L, double B, int J_min, int N, int64_t* nscal_out);
+/* no bounded waits: 0 for a valid plan */
+int pxm_hwav_status(pxm_hwav_plan_t plan, int clear, pxm_stream_t stream);
+/* One MYULA iteration of the synthesis setting with a harmonic plan, a measurement diagonal in (l, m) and a diagonal
+ * inverse covariance, in one kernel (one lane per (chain, lm)):
+ *   preds = k .* synthesis(X);  g = k .* invcov .* (preds - data);  X_out = MYULA update of X with the gradient
+ *   synthesis_adjoint(g) (soft threshold T / T_scalar, Philox noise keyed (seed, chain0 + c, coefficient, iter + *iter_dev)
+ *   as pxm_myula_step);  preds_out = k .* synthesis(X_out).
+ * kernel: null (identity measurement) or the weak-lensing kernel k_l [L*L], applied with l < 2 zeroed.  data [L*L]
+ * complex; invcov [L*L] real or complex (invcov_complex).  mode: PXM_MODE_REAL_NOISE or PXM_MODE_CPLX_NOISE, optionally
+ * OR PXM_NOISE_F64 (PXM_MODE_REAL_PAIRS is refused: harmonic coefficients are never real).  iter_dev may be null. */
+int pxm_hwav_myula_step(pxm_hwav_plan_t plan, const void* X, const void* data, const void* invcov, int invcov_complex,
+                        const double* kernel, const double* T, double T_scalar, double delta, double lmda, int mode,
+                        uint64_t seed, uint64_t chain0, uint64_t iter, const uint64_t* iter_dev, void* X_out,
+                        void* preds_out, int C, pxm_stream_t stream);
+/* launch shape (test / timing aid): items, workgroups per chain of the split launch, most items with a non-zero weight at
+ * one degree (the register count of the fused step) */
+int pxm_hwav_plan_info(pxm_hwav_plan_t plan, int* nitems, int* split_blocks, int* kact);
 
 /* Device-resident Philox iteration counter OF ONE PLAN (HIP-graph replay of the MYULA step): when registered,
  * the plan's fused steps use iteration = iter + *counter, read on the device at execution time, so a captured

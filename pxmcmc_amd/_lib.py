@@ -70,6 +70,19 @@ SIGNATURES = {
     "pxm_dwav_table_bytes": (c_i64, [c_vp]),
     "pxm_dwav_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_dwav_plan_info": (c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "pxm_hwav_plan_create": (c_int, [c_int, c_dbl, c_int, c_int, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),
+    "pxm_hwav_plan_destroy": (c_int, [c_vp]),
+    "pxm_hwav_synthesis": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_hwav_synthesis_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_hwav_analysis": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_hwav_analysis_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_hwav_ncoefs": (c_i64, [c_int, c_dbl, c_int, c_int, c_vp]),
+    "pxm_hwav_status": (c_int, [c_vp, c_int, c_vp]),
+    "pxm_hwav_plan_info": (c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "pxm_hwav_myula_step": (
+        c_int,
+        [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_int, c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_int, c_vp],
+    ),
     "pxm_wav_plan_create": (c_int, [c_int, c_dbl, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),
     "pxm_wav_plan_create_spin": (c_int, [c_int, c_dbl, c_int, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),
     "pxm_wav_plan_destroy": (c_int, [c_vp]),

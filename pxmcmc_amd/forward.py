@@ -130,7 +130,7 @@ class ForwardOperator:
         tr, ms = getattr(self, "transform", None), getattr(self, "measurement", None)
         if type(tr) is not SphericalWaveletTransform or type(ms) is not WeakLensing or tr.L != ms.L or tr.L < 3:
             return None
-        if tr.dirs != 1 or tr.spin != 0:  # (wl_attach is a WavPlan stage: axisymmetric, spin-0 images only)
+        if tr.dirs != 1 or tr.spin != 0 or tr.harmonic:  # (wl_attach is a WavPlan stage: axisymmetric, spin-0 images only)
             return None
         if not getattr(self, "fuse_weaklensing", True):
             return None

@@ -35,7 +35,7 @@ import torch
 from scipy.stats import laplace
 
 from . import ops
-from .measurements import Identity
+from .measurements import Identity, WeakLensingHarmonic
 from .prior import L1
 from .transforms import SphericalWaveletTransform
 
@@ -509,11 +509,37 @@ class MYULA(PxMCMC):
             and type(f).calc_gradg.__qualname__.startswith("ForwardOperator")
             and isinstance(getattr(f, "transform", None), SphericalWaveletTransform)
             and f.transform.dirs == 1  # (the fused steps are WavPlan's: axisymmetric only)
+            and not f.transform.harmonic  # (... and pixel space)
             and isinstance(getattr(f, "measurement", None), Identity)
             and f.measurement.ndata == f.measurement.npix
             and self._stock_prox
             and not self._own_step
         )
+
+    def _fusable_harmonic(self):
+        """the fused harmonic step (HarmWavPlan.myula_step) applies: synthesis, a harmonic SphericalWaveletTransform, a
+        measurement diagonal in (l, m) at its bandlimit -- exactly Identity(L^2, L^2) or WeakLensingHarmonic(L) -- a diagonal
+        inverse covariance, the stock prox and no subclass chain_step.  Returns the measurement kernel (None: identity), or
+        False."""
+        f = self.forward
+        tr, ms = getattr(f, "transform", None), getattr(f, "measurement", None)
+        if not (
+            getattr(f, "setting", None) == "synthesis"
+            and hasattr(getattr(f, "invcov", None), "diag")
+            and type(f).calc_gradg.__qualname__.startswith("ForwardOperator")
+            and type(f).forward.__qualname__.startswith("ForwardOperator")
+            and isinstance(tr, SphericalWaveletTransform)
+            and tr.harmonic
+            and self._stock_prox
+            and not self._own_step
+            and f.invcov.diag.numel() == tr.L ** 2
+        ):
+            return False
+        if type(ms) is Identity and ms.ndata == ms.npix == tr.L ** 2:
+            return None
+        if type(ms) is WeakLensingHarmonic and ms.L == tr.L:
+            return ms.kernel_dev
+        return False
 
     def _advance(self, X, preds, i, delta=None):
         """one MYULA update X -> X_prop (pxmcmc/mcmc.py:158-160), fused where the operators allow"""
@@ -542,11 +568,14 @@ class MYULA(PxMCMC):
 
     def _prepare(self):
         self._fused_wav = self._fusable_wavelet() and isinstance(self.delta, float)
+        kernel = self._fusable_harmonic() if isinstance(self.delta, float) else False
+        self._fused_harm = kernel is not False
+        self._harm_kernel = kernel if self._fused_harm else None
         self._fused_prox = self._stock_prox and not self._own_step
         # the calls of the reference's loop, one by one: host noise, a tensor delta or a subclass's chain_step (and,
         # without graph replay, the operators that have no fused step)
         self._eager_only = self.rng == "numpy" or not (
-            self._fused_wav or (self.use_graph and isinstance(self.delta, float) and not self._own_step))
+            self._fused_wav or self._fused_harm or (self.use_graph and isinstance(self.delta, float) and not self._own_step))
         self._it = 0
         self._pairs = False
 
@@ -601,6 +630,8 @@ class MYULA(PxMCMC):
             return self._engine_start_eager(X, preds, i0)
         if self._fused_wav:
             return self._engine_start_fused(X, preds, i0)
+        if self._fused_harm:
+            return self._engine_start_harmonic(X, preds, i0)
         f = self.forward
         delta, lmda = float(self.delta), self.lmda
 
@@ -653,6 +684,24 @@ class MYULA(PxMCMC):
 
             eng["one"] = one
         eng["reset"]()
+        return self._engine_ready(X, preds, i0, self.use_graph)
+
+    def _engine_start_harmonic(self, X, preds, i0):
+        """The fused harmonic step of HarmWavPlan: the whole iteration, preds of the new state included, in one kernel that
+        reads the iteration number from the engine's device counter"""
+        f = self.forward
+        plan = f.transform._plan
+        X = ops.as_device(X, torch.complex128).contiguous()
+        preds = ops.as_device(preds, torch.complex128)
+        eng = self._engine_new(X, preds, _Counter(i0), plan=plan)
+        data, d, T, delta, lmda, k = f.data_dev_c128, f.invcov.diag, self.prior.T_dev, float(self.delta), self.lmda, self._harm_kernel
+        kw = dict(noise_complex=bool(self.complex), seed=self.seed, chain0=self.chain_offset, noise64=self.noise64)
+
+        def one(src, dst):
+            plan.myula_step(src, data, d, k, T, delta, lmda, iter_dev=eng["cnt"].t, out=dst, preds_out=eng["P"], **kw)
+            eng["cnt"].add(1)
+
+        eng["one"] = one
         return self._engine_ready(X, preds, i0, self.use_graph)
 
     def _engine_start_eager(self, X, preds, i0):

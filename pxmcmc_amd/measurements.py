@@ -107,18 +107,35 @@ class WeakLensingHarmonic(Measurement):
             k[el * el : (el + 1) ** 2] = -1.0 * np.sqrt(((el + 2.0) * (el - 1.0)) / ((el + 1.0) * el))
         return k
 
-    def _mapping_dev(self, flm):
-        x, squeeze = ops._batched(ops.as_device(flm, torch.complex128))
+    def sks_estimate(self, glm):
+        """measurements.py:142-149: spherical Kaiser-Squires estimate (the usual start point of a sampler)."""
+        return self.harmonic_inverse_mapping(glm)
+
+    @property
+    def kernel_dev(self):
+        """the harmonic kernel k_l [L^2] on the device (float64)"""
         if self._kernel_dev is None:
             self._kernel_dev = ops.as_device(self.harmonic_kernel, torch.float64)
+        return self._kernel_dev
+
+    def _mapping_dev(self, flm, kernel=None):
+        x, squeeze = ops._batched(ops.as_device(flm, torch.complex128))
+        kernel = self.kernel_dev if kernel is None else kernel
         assert x.shape[1] == self.L ** 2
         out = torch.empty_like(x)
-        check(lib.pxm_wl_harmonic_mapping(ops._p(x), ops._p(self._kernel_dev), ops._p(out), x.shape[1], x.shape[0], ops._stream()))
+        check(lib.pxm_wl_harmonic_mapping(ops._p(x), ops._p(kernel), ops._p(out), x.shape[1], x.shape[0], ops._stream()))
         return out[0] if squeeze else out
 
     def harmonic_mapping(self, flm):
         """measurements.py:162-171: multiply by the kernel, zero the first four entries."""
         return to_like(self._mapping_dev(flm), flm)
+
+    def harmonic_inverse_mapping(self, flm):
+        """measurements.py:173-182: divide by the kernel, zero the first four entries (the mapping kernel with 1 / k_l:
+        every k_l with l >= 2 is non-zero)."""
+        if getattr(self, "_inv_kernel_dev", None) is None:
+            self._inv_kernel_dev = ops.as_device(1.0 / self.harmonic_kernel, torch.float64)
+        return to_like(self._mapping_dev(flm, self._inv_kernel_dev), flm)
 
 
 class WeakLensing(WeakLensingHarmonic):

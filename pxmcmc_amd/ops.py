@@ -784,6 +784,78 @@ class DirWavPlan(_Plan):
         return a.value, b.value, c.value
 
 
+class HarmWavPlan(_Plan):
+    """Harmonic-space scale-discretised wavelet transforms (replaces pys2let's analysis_lm2lmn / synthesis_lmn2lm and
+    their adjoints; include/pxmcmc_amd.h, pxm_hwav_*).  Inputs and outputs are spherical-harmonic coefficients: f_lm
+    [L*L] and the layout [scaling: bl_0^2 | j = J_min .. J_max: n = -(N-1), .., N-1: bl_j^2 each] (DESIGN.md section
+    13).  N > 1 at spin 0 only."""
+
+    def __init__(self, L, B, J_min, N=1, spin=0, max_chains=1):
+        require_gpu()
+        self.L, self.B, self.J_min, self.N, self.max_chains = int(L), float(B), int(J_min), int(N), int(max_chains)
+        self.spin = int(spin)
+        self.nlm = self.L * self.L
+        nscal = C.c_int64()
+        self.ncoefs = int(check(lib.pxm_hwav_ncoefs(self.L, self.B, self.J_min, self.N, C.byref(nscal))))
+        self.nscal = int(nscal.value)
+        super().__init__(lib.pxm_hwav_plan_create, (self.L, self.B, self.J_min, self.N, self.spin, self.max_chains, 0),
+                         lib.pxm_hwav_plan_destroy, lib.pxm_hwav_status,
+                         f"HarmWavPlan(L={self.L}, N={self.N}, spin={self.spin})")
+
+    def synthesis(self, X, out=None):
+        return self._run(lib.pxm_hwav_synthesis, X, self.ncoefs, self.nlm, out=out)
+
+    def synthesis_adjoint(self, flm):
+        return self._run(lib.pxm_hwav_synthesis_adjoint, flm, self.nlm, self.ncoefs)
+
+    def analysis(self, flm):
+        return self._run(lib.pxm_hwav_analysis, flm, self.nlm, self.ncoefs)
+
+    def analysis_adjoint(self, X):
+        return self._run(lib.pxm_hwav_analysis_adjoint, X, self.ncoefs, self.nlm)
+
+    def info(self):
+        """(items, split workgroups per chain, most items with a non-zero weight at one degree)"""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        check(lib.pxm_hwav_plan_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def myula_step(self, X, data, invcov, kernel, T, delta, lmda, noise_complex=False, seed=0, chain0=0, it=0, iter_dev=None,
+                   out=None, preds_out=None, noise64=False):
+        """One MYULA iteration of the synthesis setting with a measurement diagonal in (l, m) (``kernel``: None for the
+        identity, else WeakLensingHarmonic's k_l) and a diagonal inverse covariance; returns (X', forward(X')).  Noise:
+        the Philox stream of :func:`myula_step` at iteration ``it`` (+ ``iter_dev`` on the device)."""
+        x, squeeze = _batched(as_device(X, _CPLX))
+        if x.shape[1] != self.ncoefs or x.shape[0] > self.max_chains:
+            raise AssertionError("myula_step: shape mismatch")
+        d = as_device(data, _CPLX).reshape(-1)
+        ic = as_device(invcov).reshape(-1)
+        if d.numel() != self.nlm or ic.numel() != self.nlm:
+            raise ValueError("data / invcov length mismatch")
+        k = None
+        if kernel is not None:
+            k = as_device(kernel, _REAL).reshape(-1)
+            if k.numel() != self.nlm:
+                raise ValueError("kernel length mismatch")
+        Tv, Ts = _vecT(T, self.ncoefs, x.device)
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != _CPLX or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+            raise ValueError("out= buffer must be a distinct contiguous complex128 tensor of the state's shape")
+        if preds_out is None:
+            preds_out = torch.empty((x.shape[0], self.nlm), dtype=_CPLX, device=x.device)
+        elif preds_out.shape != (x.shape[0], self.nlm) or preds_out.dtype != _CPLX or not preds_out.is_contiguous():
+            raise ValueError("preds_out= buffer has the wrong shape / dtype / layout")
+        check(
+            lib.pxm_hwav_myula_step(
+                self._h, _p(x), _p(d), _p(ic), int(ic.is_complex()), _p(k), _p(Tv), Ts, float(delta), float(lmda),
+                int(bool(noise_complex)) | _nf(noise64), seed, chain0, it, _p(iter_dev), _p(out), _p(preds_out), x.shape[0],
+                _stream(),
+            )
+        )
+        return (out[0], preds_out[0]) if squeeze else (out, preds_out)
+
+
 # ---- device-resident iteration counter (HIP-graph replay) -----------------------------------
 class IterCounter:
     """A device int64 registered as the Philox iteration counter of ONE wavelet plan for the lifetime of the

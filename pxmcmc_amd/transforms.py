@@ -46,23 +46,22 @@ class IdentityTransform(Transform):
 
 class SphericalWaveletTransform(Transform):
     """
-    Spherical wavelet transforms (pxmcmc/transforms.py:59-166), pixel space, ``upsample=0``.  ``dirs = N > 1``:
-    directional wavelets; each wavelet block holds 2N - 1 orientation planes.  ``spin != 0``
-    (``dirs = 1`` only): images are spin-s MW maps, the coefficients keep the spin-0 layout.
+    Spherical wavelet transforms (pxmcmc/transforms.py:59-166), ``upsample=0``.  ``dirs = N > 1``: directional wavelets;
+    each wavelet block holds 2N - 1 orientation planes.  ``spin != 0`` (``dirs = 1`` only): images
+    are spin-s MW maps, the coefficients keep the spin-0 layout.  ``harmonic=True``: inputs and
+    outputs are spherical-harmonic coefficients, f_lm [L^2] and one ssht-indexed bl_j^2 block per (scale, n)
+    (pys2let's analysis_lm2lmn / synthesis_lmn2lm and their adjoints).
 
     :param int max_chains: largest chain batch the transform will be called with (extension)
     """
 
     def __init__(self, L, B, J_min, dirs=1, spin=0, harmonic=False, max_chains=1):
-        if harmonic:
-            # the harmonic variants are not in released pys2let either (reference tests/test_transforms.py:9-11)
-            raise NotImplementedError("harmonic=True is out of scope (SURVEY.md section 2, row 3)")
         if int(dirs) != dirs or dirs < 1:
             raise ValueError("dirs must be a positive integer")
         if int(spin) != spin:
             raise ValueError("spin must be an integer")
         if spin != 0 and dirs != 1:
-            raise NotImplementedError("spin wavelets are axisymmetric only (dirs = 1; DESIGN.md section 12)")
+            raise NotImplementedError("spin wavelets are axisymmetric only (dirs = 1; DESIGN.md sections 12, 13)")
         if abs(spin) >= L:
             raise ValueError("|spin| must be < L")
         spin = int(spin)
@@ -73,13 +72,17 @@ class SphericalWaveletTransform(Transform):
         self.nscales = self.J_max - self.J_min + 1
         self.dirs = dirs
         self.spin = spin
+        self.harmonic = bool(harmonic)
         self.params = {"B": B, "L": L, "J_min": J_min, "N": dirs, "spin": spin, "upsample": 0}
         self.max_chains = max_chains
         self._plan = self._make_plan(max_chains)
         self._get_ncoefs()
 
     def _make_plan(self, C):
-        """dirs = 1: the axisymmetric plan with the fused sampler steps; dirs > 1: the directional plan (SO(3) stages)"""
+        """harmonic: the harmonic-space plan; dirs = 1: the axisymmetric plan with the fused sampler steps; dirs > 1: the
+        directional plan (SO(3) stages)"""
+        if self.harmonic:
+            return ops.HarmWavPlan(self.L, self.B, self.J_min, int(self.dirs), spin=self.spin, max_chains=C)
         if self.dirs == 1:
             return ops.WavPlan(self.L, self.B, self.J_min, max_chains=C, spin=self.spin)
         return ops.DirWavPlan(self.L, self.B, self.J_min, int(self.dirs), max_chains=C)
@@ -91,7 +94,7 @@ class SphericalWaveletTransform(Transform):
             self._plan = self._make_plan(C)
 
     def forward(self, X):
-        """image -> wavelet coefficients (pys2let.analysis_px2wav, transforms.py:101-112)."""
+        """image (or f_lm) -> wavelet coefficients (pys2let.analysis_px2wav / analysis_lm2lmn, transforms.py:101-112)."""
         return to_like(self._plan.analysis(X), X)
 
     def inverse(self, X):
