@@ -107,6 +107,14 @@ def test_dirwav_four_ops_match_model(L, N, B, J_min):
     _four_ops_vs_model(L, B, J_min, N, 2, [0, 1], 1e-12)
 
 
+@pytest.mark.parametrize("N", [5, 6, 8, 12])
+@pytest.mark.parametrize("J_min", [1, 2])
+def test_dirwav_four_ops_match_model_gamma_variants(N, J_min):
+    """with N = 2, 3, 4 above and 7, 9 below: every instantiation of the gamma stage (N = 1 .. 8 unrolled, the generic one
+    beyond) runs against the model"""
+    _four_ops_vs_model(16, 2.0, J_min, N, 2, [0, 1], 1e-12)
+
+
 def test_dirwav_skipped_pairs_match_model():
     """L = 16, B = 2, J_min = 1, N = 5: the scales at bl_j = 2, 4 skip the pairs with |n| >= bl_j"""
     M = DirWavModel(16, 2.0, 1, 5)

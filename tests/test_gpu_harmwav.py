@@ -58,6 +58,31 @@ def test_four_ops_match_model(L, N, spin, C):
         assert _rel(got[list(rows)], ref) <= 1e-12, name
 
 
+@pytest.mark.parametrize("N", [1, 2, 5])
+@pytest.mark.parametrize("B,J_min", [(1.5, 1), (1.7, 2), (3.0, 1), (2.0, 0)])
+@pytest.mark.parametrize("L", [13, 33])
+def test_four_ops_match_model_other_tilings(L, B, J_min, N):
+    """non-dyadic B, J_min = 0 and odd L (a partial last workgroup), and per block: every (scale, n) block of the split
+    operators to 1e-12 of its own largest entry, so that the top scale cannot hide the others"""
+    from pxmcmc_amd import ops
+
+    C = 2
+    rng = np.random.default_rng(1000 * L + 100 * J_min + 10 * N + int(10 * B))
+    plan = ops.HarmWavPlan(L, B, J_min, N, max_chains=C)
+    M = _model(L, B, J_min, N)
+    assert (plan.ncoefs, plan.nscal) == (M.ncoefs, M.nscal)
+    X, f = _cplx(rng, C, M.ncoefs), _cplx(rng, C, L * L)
+    for name, arg in (("synthesis", X), ("synthesis_adjoint", f), ("analysis", f), ("analysis_adjoint", X)):
+        got = getattr(plan, name)(arg).cpu().numpy()
+        ref = np.stack([getattr(M, name)(arg[c]) for c in range(C)])
+        assert _rel(got, ref) <= 1e-12, name
+        if ref.shape[1] == M.ncoefs:
+            for i in range(len(M.blocks)):
+                a, b = M.offsets[i], M.offsets[i + 1]
+                scale = np.abs(ref[:, a:b]).max()
+                assert np.abs(got[:, a:b] - ref[:, a:b]).max() <= 1e-12 * scale, (name, i)
+
+
 def test_transform_interface():
     """numpy in -> numpy out, torch in -> torch out, 1-D or [C, n], sizes, chain growth, round trip"""
     import torch
@@ -216,17 +241,14 @@ def test_myula_numpy_rng_matches_numpy_sampler(wl):
         np.testing.assert_allclose(s.logPi[c], out["logPi"].real, rtol=1e-9)
 
 
-@pytest.mark.parametrize("wl", [False, True])
-@pytest.mark.parametrize("complex_", [False, True])
-def test_myula_fused_matches_generic_engine(wl, complex_):
-    """the fused harmonic step and the generic engine (reached through a measurement subclass) on one Philox stream, 50
-    iterations; and graph replay against eager stepping"""
+def _fused_vs_generic(wl, complex_, N, kact):
     from pxmcmc_amd.mcmc import MYULA, PxMCMCParams
 
     L, C = 16, 3
     runs = {}
     for name, subclass, use_graph in (("fused", False, True), ("fused_eager", False, False), ("generic", True, True)):
-        op, reg, data, lmda, mu, rng = _problem(wl, np.linspace(0.08, 0.12, L * L), C, L, subclass=subclass)
+        op, reg, data, lmda, mu, rng = _problem(wl, np.linspace(0.08, 0.12, L * L), C, L, N=N, subclass=subclass)
+        assert op.transform._plan.info()[2] == kact
         X0 = _cplx(rng, op.nparams) * 0.1
         p = PxMCMCParams(lmda=lmda, delta=5e-4, mu=mu, nsamples=5, nburn=9, ngap=10, verbosity=0, complex=complex_)
         s = MYULA(op, reg, p, nchains=C, seed=4, use_graph=use_graph)
@@ -240,6 +262,23 @@ def test_myula_fused_matches_generic_engine(wl, complex_):
     assert np.abs(f.chain - g.chain).max() < 1e-10 * np.abs(g.chain).max()
     np.testing.assert_allclose(f.logPi, g.logPi, rtol=1e-9)
     assert np.isfinite(f.chain).all()
+
+
+@pytest.mark.parametrize("wl", [False, True])
+@pytest.mark.parametrize("complex_", [False, True])
+def test_myula_fused_matches_generic_engine(wl, complex_):
+    """the fused harmonic step and the generic engine (reached through a measurement subclass) on one Philox stream, 50
+    iterations; and graph replay against eager stepping"""
+    _fused_vs_generic(wl, complex_, 1, 2)
+
+
+@pytest.mark.parametrize("wl", [False, True])
+@pytest.mark.parametrize("complex_", [False, True])
+@pytest.mark.parametrize("N,kact", [(2, 4), (5, 10), (9, 18)], ids=["N2-K5", "N5-K17", "N9-K0"])
+def test_myula_fused_matches_generic_engine_dirs(wl, complex_, N, kact):
+    """the same with dirs = N > 1: the samplers take the fused step for every N, and N selects the instantiation of its
+    kernel through kact, the most items with a non-zero weight at one degree (K = 5, 17 and the re-reading K = 0)"""
+    _fused_vs_generic(wl, complex_, N, kact)
 
 
 def test_myula_gates():
@@ -353,6 +392,15 @@ def test_refusals():
     rc = lib.pxm_hwav_myula_step(plan._h, vp(x.data_ptr()), vp(data.data_ptr()), vp(ic.data_ptr()), 0, None, None, 0.1, 1e-4,
                                  1e-3, 2, 0, 0, 0, None, vp(f.data_ptr()), vp(f.data_ptr()), 1, None)
     assert rc < 0 and b"mode must be 0 or 1" in lib.pxm_last_error()
+    step = lambda X, out, C_: lib.pxm_hwav_myula_step(plan._h, vp(X.data_ptr()), vp(data.data_ptr()), vp(ic.data_ptr()), 0, None,
+                                                      None, 0.1, 1e-4, 1e-3, 0, 0, 0, 0, None, vp(out.data_ptr()),
+                                                      vp(f.data_ptr()), C_, None)
+    y = torch.zeros_like(x)
+    assert step(x, y, 3) < 0 and b"pxm_hwav_myula_step: C outside [1, max_chains]" in lib.pxm_last_error()
+    assert step(x, x, 2) < 0 and b"X_out must not alias X" in lib.pxm_last_error()
+    assert step(x, y, 2) == 0
+    with pytest.raises(AssertionError, match="shape mismatch"):
+        plan.myula_step(x, data, ic, None, 0.1, 1e-4, 1e-3)
     with pytest.raises(ValueError, match="more chains"):
         plan.synthesis(x)
     with pytest.raises(ValueError, match="distinct"):
