@@ -20,9 +20,25 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pxmcmc_amd import ops  # noqa: E402
 from pxmcmc_amd.forward import SphericalWaveletTransformOperator  # noqa: E402
 from pxmcmc_amd.mcmc import MYULA, SKROCK, PxMALA, PxMCMCParams  # noqa: E402
+from pxmcmc_amd.optim import FISTA  # noqa: E402
 from pxmcmc_amd.prior import S2_Wavelets_L1  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
 from pxmcmc_amd.uncertainty import chain_to_images, credible_interval_range  # noqa: E402
+
+
+def map_start(forwardop, regulariser, params, L_g, start_point, tol=1e-3, max_iter=2000):
+    """FISTA on the samplers' posterior as the chain's start point.  The steps of FISTA shrink like 1 / k, so the run is
+    bounded: at most ``max_iter`` operator pairs, stopping at a relative step of ``tol`` (a start point, not a final
+    estimate).  1 / (L_g (1 + 1e-3)) is a valid step for the real-part operator FISTA uses with complex data as well."""
+    fista = FISTA(forwardop, regulariser, params, gamma=1 / (L_g * (1 + 1e-3)), tol=tol, max_iter=max_iter)
+    x = fista.run(start_point=start_point)
+    if fista._stock_prox:
+        print(f"MAP start: FISTA stopped after {int(fista.niter[0])} iterations (converged: {bool(fista.converged[0])}), "
+              f"objective {fista.objective_map[0]:.6e}")
+    else:  # the prior's own prox carries its own threshold: the fixed point of that iteration, not the posterior's MAP
+        print(f"start point: fixed point of the prior's own prox-gradient iteration (g + (lmda / gamma) f, not the MAP) after "
+              f"{int(fista.niter[0])} iterations (converged: {bool(fista.converged[0])})")
+    return x
 
 
 def main(argv=None):
@@ -39,6 +55,7 @@ def main(argv=None):
     ap.add_argument("--chains", type=int, default=1, help="independent chains batched on the GPU")
     ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
     ap.add_argument("--spin", type=int, default=0, help="spin S of the field (S != 0: a complex spin-S field, dirs = 1)")
+    ap.add_argument("--map-start", action="store_true", help="start the chain(s) at the MAP point found by FISTA first")
     ap.add_argument("--outdir", type=str, default=".")
     ap.add_argument("--jobid", type=str, default="0")
     args = ap.parse_args(argv)
@@ -70,15 +87,10 @@ def main(argv=None):
     forwardop = SphericalWaveletTransformOperator(data, args.sigma, setting, L, B, J_min, dirs=args.dirs, spin=spin,
                                                  max_chains=args.chains)
     lmda = 1e-6
-    # step size inside the MYULA bound 1 / (L_f + 1 / lmda), L_f = ||S||^2 / sigma^2 (power iteration)
-    import torch
-
-    x = torch.randn(forwardop.transform.ncoefs, dtype=torch.complex128).cuda()
-    for _ in range(20):
-        y = forwardop.transform.inverse_adjoint(forwardop.transform.inverse(x))
-        norm2 = float(torch.linalg.norm(y) / torch.linalg.norm(x))
-        x = y / torch.linalg.norm(y)
-    delta = 0.8 / (norm2 / args.sigma ** 2 + 1 / lmda)
+    # step size inside the MYULA bound 1 / (L_g + 1 / lmda), L_g = ||S||^2 / sigma^2 (power iteration on the operator)
+    L_g = forwardop.gradient_lipschitz(iters=50, tol=1e-3)  # (at most 50 operator pairs at start-up)
+    delta = 0.8 / (L_g + 1 / lmda)
+    print(f"L_g = {L_g:.6e}: MYULA step bound 1 / (L_g + 1 / lmda) = {1 / (L_g + 1 / lmda):.6e}, delta = {delta:.6e}")
     if args.algo == "skrock":  # SKROCK is stable up to (2 - 4 eta / 3) s^2 / L: the same margin, s^2 times the step
         delta *= args.s ** 2
 
@@ -90,8 +102,11 @@ def main(argv=None):
     print(f"Number of model parameters: {forwardop.nparams}")
     cls = {"myula": MYULA, "pxmala": PxMALA, "skrock": SKROCK}[args.algo]
     mcmc = cls(forwardop, regulariser, params, nchains=args.chains)
+    start_point = np.zeros(forwardop.nparams)
+    if args.map_start:
+        start_point = map_start(forwardop, regulariser, params, L_g, start_point.astype(complex) if spin else start_point)
     start = datetime.now()
-    mcmc.run(start_point=np.zeros(forwardop.nparams))
+    mcmc.run(start_point=start_point)
     elapsed = datetime.now() - start
 
     path = save_mcmc(mcmc, params, args.outdir, filename=f"{args.algo}_{setting}_{args.jobid}", L=L, B=B, J_min=J_min,

@@ -31,6 +31,7 @@ from pxmcmc_amd import ops  # noqa: E402
 from pxmcmc_amd.forward import ForwardOperator  # noqa: E402
 from pxmcmc_amd.mcmc import MYULA, SKROCK, PxMALA, PxMCMCParams  # noqa: E402
 from pxmcmc_amd.measurements import WeakLensing, WeakLensingHarmonic  # noqa: E402
+from pxmcmc_amd.optim import FISTA  # noqa: E402
 from pxmcmc_amd.prior import L1, S2_Wavelets_L1  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
 from pxmcmc_amd.transforms import SphericalWaveletTransform  # noqa: E402
@@ -67,6 +68,32 @@ def prepare_gammas(klm, L, wl, sigma=BEAM_SIGMA):
     return wl.forward(kappa_mw), kappa_mw.reshape(L, 2 * L - 1)
 
 
+def step_hint(forward_operator, params, args):
+    """print MYULA's step bound 1 / (L_g + 1 / lmda) beside --delta (SKROCK: s^2 times it); returns L_g"""
+    L_g = forward_operator.gradient_lipschitz(iters=50, tol=1e-3)  # (at most 50 operator pairs at start-up)
+    bound = 1 / (L_g + 1 / params.lmda)
+    print(f"L_g = {L_g:.6e}: step bound 1 / (L_g + 1 / lmda) = {bound:.6e} (--delta {args.delta:.6e}"
+          + (f", SKROCK with s = {args.s}: {bound * args.s ** 2:.6e})" if args.algo == "skrock" else ")"))
+    return L_g
+
+
+def map_start(forward_operator, prior, params, L_g, start_point=None, tol=1e-3, max_iter=2000):
+    """FISTA on the samplers' posterior as the chain's start point.  The shear data are complex with a real sig_d, so the
+    inverse covariance is complex (pxmcmc/forward.py:81-82) and FISTA takes its gradient on the operator with Re(invcov),
+    for which 1 / L_g of the full operator is a valid (smaller) step.  The steps of FISTA shrink like 1 / k, so the run is
+    bounded: at most ``max_iter`` operator pairs, stopping at a relative step of ``tol`` (a start point, not a final
+    estimate)."""
+    fista = FISTA(forward_operator, prior, params, gamma=1 / (L_g * (1 + 1e-3)), tol=tol, max_iter=max_iter)
+    x = fista.run(start_point=start_point)
+    if fista._stock_prox:
+        print(f"MAP start: FISTA stopped after {int(fista.niter[0])} iterations (converged: {bool(fista.converged[0])}), "
+              f"objective {fista.objective_map[0]:.6e}")
+    else:  # the prior's own prox carries its own threshold: the fixed point of that iteration, not the posterior's MAP
+        print(f"start point: fixed point of the prior's own prox-gradient iteration (g + (lmda / gamma) f, not the MAP) after "
+              f"{int(fista.niter[0])} iterations (converged: {bool(fista.converged[0])})")
+    return x
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--outdir", type=str, default=".")
@@ -84,6 +111,7 @@ def main(argv=None):
     ap.add_argument("--chains", type=int, default=1, help="independent chains batched on the GPU")
     ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--map-start", action="store_true", help="start the chain(s) at the MAP point found by FISTA first")
     ap.add_argument("--harmonic", action="store_true",
                     help="harmonic-space posterior: WeakLensingHarmonic + harmonic wavelets + L1, started from sks_estimate")
     args = ap.parse_args(argv)
@@ -106,6 +134,8 @@ def main(argv=None):
                            J_min=J_min, dirs=args.dirs)
     print(f"Number of data points: {gammas_truth.size}")
     print(f"Number of model parameters: {forward_operator.nparams}")
+    L_g = step_hint(forward_operator, params, args)
+    start_point = map_start(forward_operator, prior, params, L_g) if args.map_start else None
     if args.algo == "myula":
         mcmc = MYULA(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
     elif args.algo == "pxmala":
@@ -117,7 +147,7 @@ def main(argv=None):
 
     now = datetime.now()
     t0 = time.perf_counter()
-    mcmc.run()
+    mcmc.run(start_point=start_point)
     elapsed = time.perf_counter() - t0
     filename = f"{args.algo}_{setting}_{now.strftime('%d%m%y_%H%M%S')}_{args.jobid}"
     path = save_mcmc(mcmc, params, args.outdir, filename=filename, L=L, B=B, J_min=J_min, nparams=forward_operator.nparams,
@@ -152,6 +182,9 @@ def _main_harmonic(args, L, B, J_min, setting):
     prior = L1(setting, None, None, params.lmda * params.mu)
     X0 = transform.forward(measurement.sks_estimate(glm))
     print(f"harmonic set-up: {L * L} shear harmonics, {forward_operator.nparams} wavelet coefficients")
+    L_g = step_hint(forward_operator, params, args)
+    if args.map_start:
+        X0 = map_start(forward_operator, prior, params, L_g, start_point=X0)
     if args.algo == "myula":
         mcmc = MYULA(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
     elif args.algo == "pxmala":

@@ -353,6 +353,21 @@ int pxm_skrock_stage(const void* U, const void* proxf, const double* T, double T
                      const void* V, double a, double b, double c, double e, double r, const void* noise,
                      int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter, const uint64_t* iter_dev,
                      void* out, int64_t n, int C, int dtype, pxm_stream_t stream);
+/* One FISTA iteration on the samplers' posterior (Beck & Teboulle 2009), every array [C][n]:
+ *   V = Y - gamma gradg;  X_out = soft(V, T gamma / lmda) as pxm_myula_step forms it (T [n] shared by chains, or T_scalar)
+ *   -- or proxf when given (analysis setting / user prior: Y, gradg, T are then not read);
+ *   Y_out = X_out + beta (X_out - X_prev),  beta = beta_table[min(iter + *iter_dev, n_beta - 1)] read when the kernel runs
+ *   (iter_dev: caller-owned device iteration counter or NULL, as pxm_myula_step), so a HIP graph replays with the momentum
+ *   of its iteration.  sums [C][3] receives per chain sum |X_out - X_prev|^2, sum |X_out|^2 and sum T_i |X_out_i| (NaN with
+ *   proxf given), added in a fixed order that depends on n only: a chain's sums do not depend on its batch.
+ *   With n == 0 the sums are written as zeros (NaN for the third with proxf given).
+ * scratch: caller-owned, 3 * PXM_FISTA_SLICES_MAX * C doubles.  X_out and Y_out must not overlap an input or each other
+ * (only equal base pointers are detected and refused). */
+#define PXM_FISTA_SLICES_MAX 256
+int pxm_fista_step(const void* Y, const void* gradg, const void* proxf, const double* T, double T_scalar,
+                   const void* X_prev, double gamma, double lmda, const double* beta_table, int64_t n_beta,
+                   uint64_t iter, const uint64_t* iter_dev, void* X_out, void* Y_out, double* sums, double* scratch,
+                   int64_t n, int C, int dtype, pxm_stream_t stream);
 /* N(0,1) draws of the Philox4x32-10 stream keyed (seed, chain0+c, iter): out [C][n] (f64 or c128) */
 int pxm_randn(void* out, int64_t n, int C, int dtype, uint64_t seed, uint64_t chain0, uint64_t iter,
               pxm_stream_t stream);

@@ -115,6 +115,56 @@ class ForwardOperator:
             return self._gradg_analysis(preds)
         return self._gradg_synthesis(preds)
 
+    def _state_dtype(self):
+        """dtype of the state the operator acts on: complex128 for the wavelet transforms (their coefficients are complex),
+        complex data or a complex inverse covariance; float64 otherwise (the rule of the samplers' state)"""
+        if isinstance(getattr(self, "transform", None), SphericalWaveletTransform) or self.data_dev.is_complex():
+            return torch.complex128
+        inv = self.invcov
+        ic_complex = inv.is_complex if isinstance(inv, FullInverseCovariance) else inv.diag.is_complex()
+        return torch.complex128 if ic_complex else torch.float64
+
+    def gradient_lipschitz(self, iters=100, tol=1e-4, seed=0):
+        """Lipschitz constant ``L_g`` of the data term's gradient: the norm of the linear part ``A = Phi^H C^-1 Phi`` of
+        ``x -> calc_gradg(forward(x))``, by a power iteration on the device through the operator's own two calls (any
+        transform, measurement, setting and inverse covariance).  ``1 / L_g`` bounds the step of a proximal-gradient method
+        (:class:`pxmcmc_amd.optim.FISTA`), ``1 / (L_g + 1 / lmda)`` that of MYULA.
+
+        The estimates ``||A x_k|| / ||x_k||`` increase towards ``L_g`` from below, so ``L_g (1 + tol)`` is the safe value.
+        The iteration stops once the remaining gap is at most ``tol`` times the estimate on five consecutive iterations.  The
+        gap is extrapolated from the last two increments ``d_k``, ``d_{k-1}`` as ``2 d_k r / (1 - r)``, ``r = d_k / d_{k-1}``:
+        the geometric tail of an isolated largest eigenvalue, doubled because a spectrum that is dense below ``L_g`` closes
+        the gap like ``1 / k``, twice the geometric extrapolation.  A warning is issued when ``iters`` products (two operator
+        calls each) do not get there: the value returned is then a lower bound whose gap is unknown.  ``seed`` fixes the
+        start vector.  Returns a float."""
+        n = int(self.nparams)
+        dt = self._state_dtype()
+        gen = torch.Generator().manual_seed(int(seed))
+        x = ops.as_device(torch.randn(n, dtype=dt, generator=gen), dt)
+        A = lambda v: ops.as_device(self.calc_gradg(ops.as_device(self.forward(v))), dt)  # noqa: E731
+        g0 = A(torch.zeros_like(x))
+        norm = lambda v: float(ops.reduce_vdot(v, v)[0].real) ** 0.5  # noqa: E731
+        nx = norm(x)
+        ests, met = [], 0
+        for _ in range(int(iters)):
+            y = A(x / nx) - g0
+            ny = norm(y)
+            if ny == 0.0:
+                return 0.0
+            ests.append(ny)
+            if len(ests) >= 3:
+                d, d_prev = ests[-1] - ests[-2], ests[-2] - ests[-3]
+                r = d / d_prev if d_prev > 0 else 1.0
+                met = met + 1 if d <= 0.0 or (r < 1.0 and 2.0 * d * r / (1.0 - r) <= tol * ny) else 0
+                if met >= 5:
+                    break
+            x, nx = y, ny
+        else:
+            import warnings
+
+            warnings.warn(f"gradient_lipschitz: {iters} iterations did not reach tol = {tol:g}; the estimate is a lower bound")
+        return ests[-1]
+
     def _forward_analysis(self, X):
         return self.measurement.forward(X)
 

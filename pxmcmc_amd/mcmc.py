@@ -363,14 +363,17 @@ class PxMCMC:
             eng["graph"], eng["graph_long"] = graphs or (None, None)
         return eng
 
-    def _engine_start_generic(self, X, preds, i0, step, lazy, graph_ok):
+    def _engine_start_generic(self, X, preds, i0, step, lazy, graph_ok, reset=None):
         """The engine of the steps that run on the operators' own plans: ``step(eng, src, dst)`` per iteration on static
         buffers, the noise kernels reading the iteration number from a device counter (``eng["cnt"].t``).  With ``lazy``
-        the steps do not write P: forward(X) is formed where the state is observed."""
+        the steps do not write P: forward(X) is formed where the state is observed.  ``reset(eng)`` rebuilds whatever the
+        steps carry besides (XA, P) from the restored start state."""
         X = ops.as_device(X).contiguous()
         preds = ops.as_device(preds)
         eng = self._engine_new(X, preds, _Counter(i0))
         eng["one"] = lambda src, dst: step(eng, src, dst)
+        if reset is not None:
+            eng["reset"] = lambda: reset(eng)
         if lazy:
             eng["form_preds"] = lambda X: eng["P"].copy_(ops.as_device(self.forward.forward(X)))
         return self._engine_ready(X, preds, i0, graph_ok)

@@ -228,6 +228,63 @@ def skrock_stage(U, a, b=0.0, c=0.0, e=0.0, r=0.0, T=None, proxf=None, gradg=Non
     return out[0] if squeeze else out
 
 
+FISTA_SLICES_MAX = 256  # PXM_FISTA_SLICES_MAX: partial sums per chain of pxm_fista_step
+
+
+def fista_scratch(C_, dev):
+    """scratch of :func:`fista_step` for C_ chains (the stepping engine keeps one: no allocation per iteration)"""
+    return torch.empty(3 * FISTA_SLICES_MAX * int(C_), dtype=_REAL, device=dev)
+
+
+def fista_step(Y, gradg, X_prev, gamma, lmda, beta, T=None, proxf=None, it=0, iter_dev=None, out=None, sums=None, scratch=None):
+    """One FISTA iteration in one launch: ``X1 = soft(Y - gamma gradg, gamma T / lmda)`` -- or
+    ``proxf`` when given (the prior's own prox of ``Y - gamma gradg``; Y, gradg and T are then not read) -- and
+    ``Y1 = X1 + beta_k (X1 - X_prev)``.
+
+    ``beta``: the momentum table (float64 device vector, or a sequence); ``beta_k`` is entry ``it`` [+ ``*iter_dev``], read
+    when the kernel runs and clamped to the table's last entry.  ``out``: the pair of result buffers ``(X1, Y1)`` (neither
+    may alias an input).  Returns ``(X1, Y1, sums)`` with ``sums`` float64 [C, 3]: per chain ``sum |X1 - X_prev|^2``,
+    ``sum |X1|^2`` and ``sum T_i |X1_i|`` (NaN with ``proxf``)."""
+    x0, squeeze = _batched(as_device(X_prev))
+    given = proxf is not None
+    args = []
+    for t in ((proxf, None, None) if given else (None, Y, gradg)):
+        if t is None:
+            args.append(None)
+            continue
+        t, _ = _batched(as_device(t, x0.dtype))
+        if t.shape != x0.shape:
+            raise ValueError("fista_step: Y / gradg / proxf must have the state's shape")
+        args.append(t)
+    px, y, g = args
+    if not given and T is None:
+        raise ValueError("fista_step: the threshold T is needed unless proxf is given")
+    Tv, Ts = (None, 0.0) if given else _vecT(T, x0.shape[1], x0.device)
+    bt = beta if isinstance(beta, torch.Tensor) else as_device(np.atleast_1d(np.asarray(beta, dtype=float)), _REAL)
+    if bt.dtype != _REAL or bt.dim() != 1 or bt.numel() < 1 or not bt.is_contiguous() or bt.device != x0.device:
+        raise ValueError("fista_step: beta must be a non-empty contiguous float64 device vector")
+    C_ = x0.shape[0]
+    if out is None:
+        x1, y1 = torch.empty_like(x0), torch.empty_like(x0)
+    else:
+        x1, y1 = _out_like(out[0], x0), _out_like(out[1], x0)
+    if sums is None:
+        sums = torch.empty((C_, 3), dtype=_REAL, device=x0.device)
+    elif sums.shape != (C_, 3) or sums.dtype != _REAL or not sums.is_contiguous():
+        raise ValueError("fista_step: sums must be a contiguous float64 [C, 3] device array")
+    if scratch is None:
+        scratch = fista_scratch(C_, x0.device)
+    elif scratch.numel() < 3 * FISTA_SLICES_MAX * C_ or scratch.dtype != _REAL:
+        raise ValueError("fista_step: scratch is too small (fista_scratch)")
+    check(
+        lib.pxm_fista_step(
+            _p(y), _p(g), _p(px), _p(Tv), Ts, _p(x0), float(gamma), float(lmda), _p(bt), bt.numel(), int(it), _p(iter_dev),
+            _p(x1), _p(y1), _p(sums), _p(scratch), x0.shape[1], C_, _dt(x0), _stream()
+        )
+    )
+    return (x1[0], y1[0], sums) if squeeze else (x1, y1, sums)
+
+
 def randn(n, C_=1, complex_=False, seed=0, chain0=0, it=0, noise64=False):
     """N(0,1) draws of the device Philox stream keyed (seed, chain0 + c, it); noise64: Box-Muller in double precision"""
     out = torch.empty((C_, n), dtype=_CPLX if complex_ else _REAL, device=device())

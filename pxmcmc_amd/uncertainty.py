@@ -45,6 +45,25 @@ def credible_region_threshold(logpis, alpha=0.05):
     return np.quantile(logpis, 1 - alpha)
 
 
+def approx_credible_region_threshold(objective_map, ndim, alpha=0.05):
+    """Approximate threshold of the (1 - alpha) highest-posterior-density region of a log-concave posterior from its MAP
+    point alone, without a chain (Pereyra, "Maximum-a-posteriori estimation with Bayesian confidence regions", SIAM J.
+    Imaging Sci. 10(1), 2017, theorem 3.1): the region ``{x : F(x) <= F(x_map) + ndim (tau_alpha + 1)}`` with
+    ``tau_alpha = sqrt(16 log(3 / alpha) / ndim)`` contains the HPD region, for ``alpha`` in ``(4 exp(-ndim / 3), 1)``.
+
+    :param objective_map: the objective ``F = -log posterior`` at the MAP point (:attr:`pxmcmc_amd.optim.FISTA.objective_map`)
+    :param ndim: number of REAL dimensions of the state (``2 n`` for a complex state of n coefficients)
+    :raises ValueError: ``alpha`` outside the range of the bound
+    """
+    ndim = int(ndim)
+    if ndim < 1:
+        raise ValueError("ndim must be a positive number of real dimensions")
+    if not (4 * np.exp(-ndim / 3) < alpha < 1):
+        raise ValueError("alpha = %g is outside (4 exp(-ndim / 3), 1) = (%g, 1), the range of the bound" % (alpha, 4 * np.exp(-ndim / 3)))
+    tau = np.sqrt(16 * np.log(3 / alpha) / ndim)
+    return objective_map + ndim * (tau + 1)
+
+
 def in_credible_region(logpi, threshold):
     """pxmcmc/uncertainty.py:54-56"""
     return True if logpi <= threshold else False
