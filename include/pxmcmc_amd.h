@@ -305,7 +305,9 @@ int pxm_wav_ring_preds(pxm_wav_plan_t plan, void* preds, int C, pxm_stream_t str
  * (exact MW quadrature) -- so the harmonic kernel k_l is applied to the synthesised coefficients directly:
  *   pxm_wav_wl_attach  : spin-2 tables; pix2data [L(2L-1)] maps a pixel to its index in the masked data vector
  *                        (< 0 = masked; NULL = no mask, ndata = L(2L-1)); weight [ndata] = WeakLensing.inv_cov or
- *                        NULL.  Both stay caller-owned and must outlive the plan's use of them.
+ *                        NULL.  Both stay caller-owned and must outlive the plan's use of them.  A failed attach
+ *                        leaves the plan untouched and the call may be repeated; on a plan that has its attachment
+ *                        a further call only re-points pix2data / weight / ndata.
  *   pxm_wav_wl_forward : gamma [C][ndata] = WeakLensing.forward(transform.inverse(X))
  *   pxm_wav_wl_adjoint : X_out [C][ncoefs] = transform.inverse_adjoint(WeakLensing.adjoint(g)), g = gamma, or the
  *                        residual invcov .* (gamma - data) when data / invcov ([ndata]) are given (calc_gradg). */

@@ -83,7 +83,7 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
   constexpr int IT = (NV + NT - 1) / NT;                  // staging loads per thread per chunk
   const GemmTask t = tasks[bid];
   const int tid = threadIdx.x, lane = tid & 63;
-  if (t.n_rt == 0) return;  // padding entry of the XCD-queue order (plans.hip: upload_tasks)
+  if (t.n_rt == 0) return;  // padding entry of the XCD-queue order (tasklist.hip: order_tasks)
   const int xn = PK ? t.x_ncol : ncol, yn = PK ? t.y_ncol : ncol;  // doubles per operand / result row
 #ifdef PXM_GEMM_TRACE
   const unsigned long long trace_t0 = wall_clock64();

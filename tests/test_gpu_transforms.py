@@ -213,7 +213,7 @@ def test_table_cache_is_reference_counted_and_trimmable():
 
 
 def test_gemm_task_orders_are_bit_identical(monkeypatch):
-    """The ring-GEMM task lists are scheduled per regime (csrc/plans.hip upload_tasks): per-CU bins for launches that
+    """The ring-GEMM task lists are scheduled per regime (csrc/tasklist.hip order_tasks): per-CU bins for launches that
     are resident at once, per-XCD queues of operand-sharing units (padded with empty tasks) for long lists.  The
     order is a schedule only: every order gives bit-identical transforms, here through a wavelet plan (grouped
     lists over scales, Gram step) and a spin-2 plan (unpaired tables)."""

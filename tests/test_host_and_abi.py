@@ -229,14 +229,31 @@ def test_address_ranges_of_every_task_list_stay_inside_their_buffers(L):
 ])
 def test_address_range_check_refuses_short_buffers(spec, what, expect, monkeypatch):
     """negative control: with one class of buffers registered shorter than it is the check must fail, naming the access"""
+    _refuses_short_buffers((64, 2.0, 2, 0, 3), spec, what, expect, monkeypatch)
+
+
+def _refuses_short_buffers(shape, spec, what, expect, monkeypatch):
     lib = _lib().lib
-    assert lib.pxm_host_check_address_ranges(64, 2.0, 2, 0, 3, what) > 0
+    assert lib.pxm_host_check_address_ranges(*shape, what) > 0
     monkeypatch.setenv("PXM_RANGE_SELFTEST", spec)
-    assert lib.pxm_host_check_address_ranges(64, 2.0, 2, 0, 3, what) < 0
+    assert lib.pxm_host_check_address_ranges(*shape, what) < 0
     msg = lib.pxm_last_error().decode()
     assert expect in msg, msg
     monkeypatch.delenv("PXM_RANGE_SELFTEST")
-    assert lib.pxm_host_check_address_ranges(64, 2.0, 2, 0, 3, what) > 0  # and nothing of the failed plan lingers
+    assert lib.pxm_host_check_address_ranges(*shape, what) > 0  # and nothing of the failed plan lingers
+
+
+@pytest.mark.parametrize("spec,expect", [
+    ("twin ring array:64", "weak-lensing synthesis forward (twin scales)"),   # the last rows of the twin array missing
+    ("narrow ring arrays of the DFT group:256", "DFT group entry"),           # ... of the last member scale's narrow array
+    ("narrow class buffers:512", "weak-lensing forward-adjoint (twin scales)"),  # ... of the narrow H_L
+])
+def test_address_range_check_refuses_short_weaklensing_buffers(spec, expect, monkeypatch):
+    """The same negative control for a weak-lensing attach that fails AFTER it has allocated: L = 272, B = 2, one chain
+    takes the twin and narrow path (two top scales at band-limit 272 outside the DFT group, recursion stage wanted at
+    L >= 128), and each of these buffers is allocated behind the k_l vector (and the narrow spin-2 rings).  The failed attach
+    must release what it had built and leave nothing behind: the next, unshortened call succeeds."""
+    _refuses_short_buffers((272, 2.0, 2, 0, 1), spec, 7, expect, monkeypatch)
 
 
 def test_bench_tuned_iteration_window_rule():
