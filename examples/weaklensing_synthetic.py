@@ -94,6 +94,35 @@ def map_start(forward_operator, prior, params, L_g, start_point=None, tol=1e-3, 
     return x
 
 
+def build_sampler(args, forward_operator, prior, params, space):
+    """the sampler of --algo; with --summary the saved samples go into a device-resident summary of ``space`` ("image", or
+    "state" for the harmonic posterior, whose transform has no image) and "chain" leaves ``track``"""
+    if args.summary:
+        params.track = [t for t in params.track if t != "chain"]
+    kw = dict(nchains=args.chains, seed=args.seed, summary=space if args.summary else None)
+    if args.algo == "myula":
+        return MYULA(forward_operator, prior, params, **kw)
+    if args.algo == "pxmala":
+        return PxMALA(forward_operator, prior, params, tune_delta=True, **kw)
+    if args.algo == "skrock":
+        return SKROCK(forward_operator, prior, params, **kw)
+    raise ValueError("algo must be 'myula', 'pxmala' or 'skrock'")
+
+
+def summary_maps(args, mcmc, space, path):
+    """--summary: pooled mean and standard deviation of ``space`` over every chain, written beside the run; max R-hat"""
+    summ = mcmc.summary[space]
+    mean, std = summ.pooled_mean().cpu().numpy(), np.sqrt(summ.pooled_variance().cpu().numpy())
+    base = os.path.splitext(path)[0]
+    np.save(base + "_mean.npy", mean)
+    np.save(base + "_std.npy", std)
+    if args.chains > 1:
+        rmax, nundef = summ.max_rhat()
+        print(f"max R-hat over the {space} ({args.chains} chains): {rmax:.4f} ({nundef} components undefined)")
+    print(f"posterior mean and standard deviation of the {space}: {base}_mean.npy, {base}_std.npy")
+    return mean
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--outdir", type=str, default=".")
@@ -112,6 +141,8 @@ def main(argv=None):
     ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--map-start", action="store_true", help="start the chain(s) at the MAP point found by FISTA first")
+    ap.add_argument("--summary", action="store_true",
+                    help="accumulate the posterior mean / standard deviation / R-hat on the GPU instead of saving the chain")
     ap.add_argument("--harmonic", action="store_true",
                     help="harmonic-space posterior: WeakLensingHarmonic + harmonic wavelets + L1, started from sks_estimate")
     args = ap.parse_args(argv)
@@ -136,14 +167,7 @@ def main(argv=None):
     print(f"Number of model parameters: {forward_operator.nparams}")
     L_g = step_hint(forward_operator, params, args)
     start_point = map_start(forward_operator, prior, params, L_g) if args.map_start else None
-    if args.algo == "myula":
-        mcmc = MYULA(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
-    elif args.algo == "pxmala":
-        mcmc = PxMALA(forward_operator, prior, params, tune_delta=True, nchains=args.chains, seed=args.seed)
-    elif args.algo == "skrock":
-        mcmc = SKROCK(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
-    else:
-        raise ValueError("algo must be 'myula', 'pxmala' or 'skrock'")
+    mcmc = build_sampler(args, forward_operator, prior, params, "image")
 
     now = datetime.now()
     t0 = time.perf_counter()
@@ -153,8 +177,11 @@ def main(argv=None):
     path = save_mcmc(mcmc, params, args.outdir, filename=filename, L=L, B=B, J_min=J_min, nparams=forward_operator.nparams,
                      setting=setting, time=str(elapsed), chains=args.chains)
 
-    chain = mcmc.chain if args.chains == 1 else mcmc.chain[0]
-    kappa_mean = np.asarray(transform.inverse(chain.mean(axis=0))).real.reshape(L, 2 * L - 1)
+    if args.summary:
+        kappa_mean = summary_maps(args, mcmc, "image", path).real.reshape(L, 2 * L - 1)
+    else:
+        chain = mcmc.chain if args.chains == 1 else mcmc.chain[0]
+        kappa_mean = np.asarray(transform.inverse(chain.mean(axis=0))).real.reshape(L, 2 * L - 1)
     seen = mask.astype(bool)
     rel = np.linalg.norm((kappa_mean - kappa_truth.real)[seen]) / np.linalg.norm(kappa_truth.real[seen])
     niter = int(mcmc.niter)
@@ -185,14 +212,7 @@ def _main_harmonic(args, L, B, J_min, setting):
     L_g = step_hint(forward_operator, params, args)
     if args.map_start:
         X0 = map_start(forward_operator, prior, params, L_g, start_point=X0)
-    if args.algo == "myula":
-        mcmc = MYULA(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
-    elif args.algo == "pxmala":
-        mcmc = PxMALA(forward_operator, prior, params, tune_delta=True, nchains=args.chains, seed=args.seed)
-    elif args.algo == "skrock":
-        mcmc = SKROCK(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
-    else:
-        raise ValueError("algo must be 'myula', 'pxmala' or 'skrock'")
+    mcmc = build_sampler(args, forward_operator, prior, params, "state")
     now = datetime.now()
     t0 = time.perf_counter()
     mcmc.run(start_point=X0)
@@ -200,8 +220,11 @@ def _main_harmonic(args, L, B, J_min, setting):
     filename = f"{args.algo}_harmonic_{setting}_{now.strftime('%d%m%y_%H%M%S')}_{args.jobid}"
     path = save_mcmc(mcmc, params, args.outdir, filename=filename, L=L, B=B, J_min=J_min, nparams=forward_operator.nparams,
                      setting=setting, time=str(elapsed), chains=args.chains)
-    chain = mcmc.chain if args.chains == 1 else mcmc.chain[0]
-    klm_mean = np.asarray(transform.inverse(chain.mean(axis=0)))
+    if args.summary:
+        klm_mean = np.asarray(transform.inverse(summary_maps(args, mcmc, "state", path)))
+    else:
+        chain = mcmc.chain if args.chains == 1 else mcmc.chain[0]
+        klm_mean = np.asarray(transform.inverse(chain.mean(axis=0)))
     rel = np.linalg.norm(klm_mean[4:] - klm_truth[4:]) / np.linalg.norm(klm_truth[4:])
     niter = int(mcmc.niter)
     print(f"saved {path}; {niter} iterations x {args.chains} chain(s) in {elapsed:.2f} s = {elapsed / max(niter, 1) * 1e3:.3f} ms "

@@ -447,6 +447,35 @@ int pxm_select_copy_many(const int32_t* flag, int narrays, const void* const* sr
                          const int* esize, int C, pxm_stream_t stream);
 int pxm_counter_add(uint64_t* counter_dev, uint64_t inc, pxm_stream_t stream);
 
+/* ---- streaming posterior summaries --------------------------------------------------------
+ * pxm_moments_update replaces the chain-wide np.mean of experiments/earthtopography/plot.py:105-122 (and the same lines
+ * of the phasevel / weaklensing plot scripts) and the highest-posterior look-up of plot.py:75-76 (MAP_idx / MAP_X), which
+ * need every saved sample in host memory: one Welford step per chain, k = count[c] + 1; d = x - mean; mean += d / k;
+ * m2 += d (x - mean_new), in one pass over a [C][m] float64 batch.  x_stride 1: x is [C][m] float64; 2: x is [C][m]
+ * complex128 and its REAL parts are accumulated (a complex state accumulated per component is passed as float64
+ * [C][2 n]).  count int64 [C]; mean, m2 float64 [C][m]; mask int32 [C] or NULL (every chain): a masked-out chain's
+ * count, mean, m2 and best fields are not written.  Best sample (all three NULL: not tracked): logpi float64 with
+ * element stride logpi_stride (1, or 2 for the real parts of complex128 [C]); a masked-in chain with
+ * logpi[c] > best_logpi[c] copies x to best_x [C][m] (ties keep the first, NaN never wins; start best_logpi at -inf).
+ * Two launches on the given stream: the streaming pass, which only reads count and best_logpi, then one workgroup that
+ * advances them.  No allocation, no synchronisation: graph-capturable.  x, mean, m2 and best_x must be 16-byte aligned. */
+int pxm_moments_update(const double* x, int x_stride, int64_t* count, double* mean, double* m2, const int* mask,
+                       const double* logpi, int logpi_stride, double* best_logpi, double* best_x, int64_t m, int C,
+                       pxm_stream_t stream);
+/* doubles of caller-owned scratch pxm_moments_finalize needs for `stats` */
+int64_t pxm_moments_scratch_doubles(int64_t m);
+/* pxm_moments_finalize reduces the accumulators over chains, in chain order (deterministic), per element: pooled_mean [m]
+ * and pooled_var [m] (unbiased) over every sample of every chain with count > 0 by Chan's pairwise merge -- np.mean
+ * (plot.py:122) and the np.std maps of a run whose chains were concatenated -- and the Gelman-Rubin rhat [m] of the chains
+ * with count > 0, which the reference does not have.  With n their common count and C' their number:
+ * W = mean_c m2_c / (n - 1), B = n / (C' - 1) sum_c (mean_c - mean of means)^2, rhat = sqrt(((n - 1) / n W + B / n) / W).
+ * NaN where an output is undefined (no sample; variance of one sample; R-hat with C' < 2, n < 2 or W == 0).  stats [2]
+ * (optional; needs rhat and scratch): max rhat over the non-NaN elements (NaN if none) and the number of NaN elements, by
+ * a two-stage reduction.  Any output may be NULL.  With rhat requested the counts are read back (the call synchronises
+ * the stream) and chains with different counts are an error; the pooled moments alone take any counts. */
+int pxm_moments_finalize(const int64_t* count, const double* mean, const double* m2, int64_t m, int C, double* pooled_mean,
+                         double* pooled_var, double* rhat, double* stats, double* scratch, pxm_stream_t stream);
+
 /* ---- weak-lensing measurement helpers (pxmcmc/measurements.py:151-171, 242-304) --------- */
 /* out = flm .* kernel with entries [0,4) zeroed: harmonic_mapping (:162-171). kernel: [L*L] */
 int pxm_wl_harmonic_mapping(const void* flm, const double* kernel, void* out, int64_t n, int C,

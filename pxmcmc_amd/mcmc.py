@@ -22,7 +22,13 @@ Extensions (all optional, defaults reproduce the reference's one-chain behaviour
   fields); the fused wavelet path then carries two real chains per complex slot -- chain 2c in the real
   part, chain 2c+1 in the imaginary part -- through the complex-linear transforms and applies prox and
   noise per component (real-signal symmetry).  Same results, half the transform
-  work (default on; complex data, as in the reference-literal topography set-up, is never paired).
+  work (default on; complex data, as in the reference-literal topography set-up, is never paired);
+* ``summary``      -- ``None`` (default), ``"state"``, ``"image"`` or a tuple of both: accumulate every saved sample into a
+  device-resident :class:`uncertainty.PosteriorSummary` per space (per-chain mean and variance, highest-posterior sample,
+  R-hat across the batch; DESIGN.md section 15).  ``"state"`` is the sampled vector as ``chain`` would hold it;
+  ``"image"`` is ``transform.inverse`` of it in the synthesis setting and the state itself in the analysis setting.  After
+  ``run()`` the summaries are in ``self.summary[space]``.  With ``"chain"`` left out of ``track`` no state is copied to the
+  host during the run.
 
 SKROCK (pxmcmc/mcmc.py:292-383) follows the published recursion (Pereyra, Vargas-Mieles & Zygalakis 2020), which
 differs from the reference's literal code for s >= 2 (see :class:`SKROCK`); it takes the keywords above except
@@ -96,7 +102,7 @@ class PxMCMC:
     """
 
     def __init__(self, forward, prior, mcmcparams=PxMCMCParams(), nchains=1, rng="philox", seed=0, chain_offset=0,
-                 use_graph=True, ring_shortcut=True, real_pairs=True, noise_bits=64):
+                 use_graph=True, ring_shortcut=True, real_pairs=True, noise_bits=64, summary=None):
         self.forward = forward
         self.prior = prior
         for attr in mcmcparams.__dict__.keys():
@@ -120,10 +126,66 @@ class PxMCMC:
         for op in (getattr(forward, "transform", None), getattr(forward, "measurement", None)):
             if hasattr(op, "ensure_chains"):
                 op.ensure_chains(self.nchains)
+        self._summary_spaces = self._summary_arg(summary)
+        self.summary = {} if self._summary_spaces else None
+        self._summary_plan = None
         self._initialise_tracking_arrays()
 
     def run(self, start_point=None):
         raise NotImplementedError
+
+    # ---- streaming summaries of the saved samples (uncertainty.PosteriorSummary) --------------------------------------------
+    def _summary_arg(self, summary):
+        """``summary=`` -> tuple of spaces, validated against the operators"""
+        spaces = () if summary is None else ((summary,) if isinstance(summary, str) else tuple(summary))
+        for sp in spaces:
+            if sp not in ("state", "image"):
+                raise ValueError("summary must be None, 'state', 'image' or a tuple of both")
+        if "image" in spaces and getattr(self.forward, "setting", "synthesis") != "analysis":
+            tr = getattr(self.forward, "transform", None)
+            if tr is None or not hasattr(tr, "inverse"):
+                raise ValueError("summary='image' needs forward.transform.inverse in the synthesis setting")
+            if getattr(tr, "harmonic", False):
+                raise ValueError("summary='image': a harmonic transform maps to harmonic coefficients, not to an image")
+        return tuple(dict.fromkeys(spaces))
+
+    def _summary_image(self, tr, S):
+        """transform.inverse of a sample batch, on the device.  The fused wavelet steps carry ring state in the workspace of
+        the plan they run on between iterations: when that is the transform's own plan the synthesis runs on a plan of the
+        summary's own (same tables, its own workspace), made at the first save"""
+        eng = getattr(self, "_eng", None)
+        if eng is not None and eng["plan"] is not None and eng["plan"] is getattr(tr, "_plan", None):
+            if self._summary_plan is None:
+                self._summary_plan = tr._make_plan(self.nchains)
+            return self._summary_plan.synthesis(S)
+        return ops.as_device(tr.inverse(S))
+
+    def _summary_update(self, X_curr, logPi, chains):
+        """the samples being saved -> the summaries (created at the first save of a run, when shapes and device are known).
+        The state summary of a full save (MYULA, SKROCK) allocates and copies nothing.  A partial save (PxMALA's ``chains``)
+        uploads a [C] mask, at a point where that loop has just read the accept flags back; the image summary allocates the
+        images, and with ``params.complex = False`` the real-part copy of the state they are synthesised from."""
+        from .uncertainty import PosteriorSummary
+
+        X = ops.as_device(X_curr)
+        analysis = getattr(self.forward, "setting", "synthesis") == "analysis"
+        mask = None
+        if chains is not None:
+            mask = np.zeros(self.nchains, dtype=np.int32)
+            mask[list(chains)] = 1
+        for sp in self._summary_spaces:
+            if sp == "state" or analysis:
+                S, cplx = X, bool(self.complex)  # as ``chain`` keeps it: the real part unless params.complex
+            else:
+                tr = self.forward.transform
+                if X.is_complex() and not self.complex:  # the image of the sample ``chain`` keeps
+                    S = torch.complex(X.real, torch.zeros_like(X.real))
+                else:
+                    S = X
+                S, cplx = self._summary_image(tr, S), True
+            if sp not in self.summary:
+                self.summary[sp] = PosteriorSummary(self.nchains, S.shape[1], cplx)
+            self.summary[sp].update(S, logpi=ops.as_device(logPi), mask=mask)
 
     # ---- device-side pieces -----------------------------------------------------------
     def _state_dtype(self, start=None):
@@ -194,6 +256,8 @@ class PxMCMC:
     def _initial_sample(self, initial_sample=None):
         """pxmcmc/mcmc.py:97-111, returning GPU tensors [C, nparams], [C, ndata]."""
         C, N = self.nchains, self.forward.nparams
+        if self._summary_spaces:
+            self.summary = {}  # start of a run: its summaries begin empty
         if initial_sample is None:
             if self.rng == "numpy":
                 draw = lambda: np.stack([laplace.rvs(size=N) for _ in range(C)])
@@ -264,6 +328,8 @@ class PxMCMC:
             put(self.preds, curr_preds)
         if hasattr(self, "chain"):
             put(self.chain, X_curr)
+        if self._summary_spaces:
+            self._summary_update(X_curr, logPi, chains)
 
     # ---- device status -----------------------------------------------------------------
     def _device_plans(self):

@@ -334,6 +334,66 @@ def quantile_range(chain, alpha=0.05):
     return out
 
 
+def _moments_rows(X, C_, m):
+    """the sample batch of moments_update as (tensor, x_stride): float64 [C, m] (stride 1), or complex128 [C, m] whose real
+    parts are taken (stride 2); a complex state accumulated per component is passed as its float64 [C, 2 n] view"""
+    if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dim() == 2 and X.shape[0] == C_ and X.is_contiguous()
+            and X.dtype in (_REAL, _CPLX) and X.shape[1] == m and X.data_ptr() % 16 == 0):
+        raise TypeError("moments_update: X must be a contiguous 16-byte aligned float64 or complex128 [%d, %d] device tensor" % (C_, m))
+    return X, (2 if X.dtype == _CPLX else 1)
+
+
+def moments_update(X, count, mean, m2, mask=None, logpi=None, best_logpi=None, best_x=None):
+    """One Welford step per chain, in place on the device accumulators: ``count`` int64 [C], ``mean`` /
+    ``m2`` float64 [C, m]; ``X`` float64 [C, m], or complex128 [C, m] whose real parts are accumulated.  ``mask`` int32 [C]:
+    chains with a zero are left untouched.  With ``logpi`` (float64 or complex128 [C], real part), ``best_logpi`` [C] and
+    ``best_x`` [C, m], a chain whose logpi exceeds its best so far also copies its sample to ``best_x``.  No allocation, no
+    synchronisation: the call can be captured in a HIP graph."""
+    C_, m = mean.shape
+    x, xs = _moments_rows(X, C_, m)
+    for t, dt, shape in ((count, torch.int64, (C_,)), (mean, _REAL, (C_, m)), (m2, _REAL, (C_, m))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError("moments_update: count int64 [C], mean / m2 contiguous float64 [C, m] device tensors are expected")
+    if mask is not None and (mask.dtype != torch.int32 or tuple(mask.shape) != (C_,) or not mask.is_cuda):
+        raise TypeError("moments_update: mask must be an int32 [C] device tensor")
+    ls = 1
+    if logpi is not None:
+        if best_logpi is None or best_x is None:
+            raise ValueError("moments_update: logpi, best_logpi and best_x are given together")
+        if logpi.dtype not in (_REAL, _CPLX) or tuple(logpi.shape) != (C_,) or not logpi.is_contiguous() or not logpi.is_cuda:
+            raise TypeError("moments_update: logpi must be a contiguous float64 or complex128 [C] device tensor")
+        if best_logpi.dtype != _REAL or tuple(best_logpi.shape) != (C_,) or best_x.dtype != _REAL or tuple(best_x.shape) != (C_, m) \
+                or not best_x.is_contiguous():
+            raise TypeError("moments_update: best_logpi float64 [C] and best_x contiguous float64 [C, m] are expected")
+        ls = 2 if logpi.dtype == _CPLX else 1
+    elif best_logpi is not None or best_x is not None:
+        raise ValueError("moments_update: logpi, best_logpi and best_x are given together")
+    check(lib.pxm_moments_update(_p(x), xs, _p(count), _p(mean), _p(m2), _p(mask), _p(logpi), ls, _p(best_logpi), _p(best_x), m, C_,
+                                 _stream()))
+
+
+def moments_finalize(count, mean, m2, rhat=True):
+    """Reduce the accumulators of moments_update over chains (in chain order) -> (pooled_mean [m], pooled_var [m], rhat [m],
+    stats [2]) on the device: pooled moments over every sample of the chains with count > 0, Gelman-Rubin R-hat of those
+    chains, and stats = (max R-hat over the non-NaN elements, number of NaN elements).  ``rhat=False`` leaves the last two
+    out (None) and takes any counts; with R-hat requested, chains with different counts raise PxmError."""
+    if mean.dim() != 2:
+        raise TypeError("moments_finalize: mean must be a float64 [C, m] device tensor")
+    C_, m = mean.shape
+    for t, dt, shape in ((count, torch.int64, (C_,)), (mean, _REAL, (C_, m)), (m2, _REAL, (C_, m))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError("moments_finalize: count int64 [C], mean / m2 contiguous float64 [C, m] device tensors are expected")
+    pm = torch.empty(m, dtype=_REAL, device=mean.device)
+    pv = torch.empty_like(pm)
+    rh = st = scratch = None
+    if rhat:
+        rh = torch.empty_like(pm)
+        st = torch.empty(2, dtype=_REAL, device=mean.device)
+        scratch = torch.empty(int(lib.pxm_moments_scratch_doubles(m)), dtype=_REAL, device=mean.device)
+    check(lib.pxm_moments_finalize(_p(count), _p(mean), _p(m2), m, C_, _p(pm), _p(pv), _p(rh), _p(st), _p(scratch), _stream()))
+    return pm, pv, rh, st
+
+
 def reduce_l2(preds, data, invcov):
     """vdot(d, invcov d), d = data - preds (pxmcmc/mcmc.py:78-79) -> complex128 [C]."""
     p, _ = _batched(as_device(preds))

@@ -12,6 +12,8 @@ import os
 
 import numpy as np
 
+_SUMMARY_FIELDS = ("count", "mean", "m2", "best", "best_logpi")  # uncertainty.PosteriorSummary.to_host()
+
 _DATASETS = (
     ("logPi", "logposterior", None),
     ("preds", "predictions", None),
@@ -35,12 +37,23 @@ def _attr_value(v):
     return v
 
 
+def _summary_datasets(mcmc):
+    """[(name, array)] of a sampler run with ``summary=``: ``summary_<space>_{count,mean,m2,best,best_logpi}`` (the raw
+    accumulators, real-component layout; extension -- a run without a summary writes none of them)"""
+    out = []
+    for space, summ in (getattr(mcmc, "summary", None) or {}).items():
+        host = summ.to_host()
+        out += [(f"summary_{space}_{k}", host[k]) for k in _SUMMARY_FIELDS if k in host]
+    return out
+
+
 def save_mcmc(mcmc, params, outpath, filename="outputs", **kwargs):
     """
     Saves the MCMC run (pxmcmc/saving.py:5-36).  Any variable selected by the sampler's ``track`` option is a
     dataset; runtime parameters and ``**kwargs`` are attributes.  Returns the path written.
     """
     present = [(attr, name, dtype) for attr, name, dtype in _DATASETS if hasattr(mcmc, attr)]
+    summaries = _summary_datasets(mcmc)
     attrs = {k: getattr(params, k) for k in params.__dict__.keys()}
     attrs.update(kwargs)
     try:
@@ -55,6 +68,8 @@ def save_mcmc(mcmc, params, outpath, filename="outputs", **kwargs):
                     f.create_dataset(name, data=getattr(mcmc, attr))
                 else:
                     f.create_dataset(name, data=getattr(mcmc, attr), dtype=dtype)
+            for name, arr in summaries:
+                f.create_dataset(name, data=arr)
             for k, v in attrs.items():
                 f.attrs[k] = v
         return path
@@ -62,13 +77,27 @@ def save_mcmc(mcmc, params, outpath, filename="outputs", **kwargs):
     for attr, name, dtype in present:
         arr = np.asarray(getattr(mcmc, attr))
         data[name] = arr.astype(dtype) if dtype else arr
+    data.update(summaries)
     path = os.path.join(outpath, f"{filename}.npz")
     np.savez(path, __attrs__=np.array(json.dumps({k: _attr_value(v) for k, v in attrs.items()})), **data)
     return path
 
 
+def load_summaries(data):
+    """the ``summary_*`` datasets of a loaded run -> {space: host dict} as ``PosteriorSummary.to_host()`` returns them"""
+    out = {}
+    for name, arr in data.items():
+        if name.startswith("summary_"):
+            for k in sorted(_SUMMARY_FIELDS, key=len, reverse=True):  # ("best_logpi" before "best")
+                if name.endswith("_" + k):
+                    out.setdefault(name[len("summary_"):-len(k) - 1], {})[k] = arr
+                    break
+    return out
+
+
 def load_mcmc(path):
-    """Read a file written by :func:`save_mcmc` -> (datasets dict, attributes dict)."""
+    """Read a file written by :func:`save_mcmc` -> (datasets dict, attributes dict); ``load_summaries(datasets)`` groups the
+    ``summary_*`` datasets of a run with ``summary=`` by space."""
     if path.endswith(".npz"):
         with np.load(path, allow_pickle=False) as z:
             data = {k: z[k] for k in z.files if k != "__attrs__"}
