@@ -84,3 +84,20 @@ def randn_real(n, seed, chain, it, bits=32):
 def randn_complex(n, seed, chain, it, bits=32):
     z0, z1 = normal_pairs(seed, chain, np.arange(n, dtype=np.uint64), it, bits)
     return z0 + 1j * z1
+
+
+UNIFORM_INDEX = 0x8000000000000000
+
+
+def uniform(seed, chain, it):
+    """the Metropolis uniform of the PxMALA accept test (csrc/philox.h philox_uniform): key (seed, chain), counter
+    (index 2^63, iteration) -- off the noise stream, whose indices are element numbers -- and the first 53-bit draw of
+    the block, (a + 1/2) 2^-53 in (0, 1).  ``it`` is the iteration the kernel sees: its argument plus the device counter."""
+    m64 = (1 << 64) - 1
+    key = (int(seed) + int(chain) * 0x9E3779B97F4A7C15) & m64
+    it = int(it) & m64
+    ctr = np.array([UNIFORM_INDEX & 0xFFFFFFFF, UNIFORM_INDEX >> 32, it & 0xFFFFFFFF, it >> 32], dtype=np.uint32)
+    k = np.array([key & 0xFFFFFFFF, key >> 32], dtype=np.uint32)
+    r = philox4x32_10(ctr, k).astype(np.uint64)
+    a = int(((r[1] << np.uint64(32)) | r[0]) >> np.uint64(11))
+    return (a + 0.5) * 2.0 ** -53

@@ -518,14 +518,21 @@ def select_copy_many(flag, pairs):
     k = len(pairs)
     if not 1 <= k <= 4:
         raise ValueError("select_copy_many takes 1 to 4 array pairs")
-    srcs = (C.c_void_p * k)(*[p[0].data_ptr() for p in pairs])
-    dsts = (C.c_void_p * k)(*[p[1].data_ptr() for p in pairs])
-    ns = (C.c_int64 * k)(*[p[0][0].numel() if p[0].dim() == 2 else p[0].numel() for p in pairs])
-    es = (C.c_int * k)(*[p[0].element_size() for p in pairs])
+    C_ = flag.shape[0]
+    if flag.dim() != 1 or flag.dtype != torch.int32 or not flag.is_contiguous():
+        raise ValueError("select_copy_many: flag must be a contiguous int32 [C] array")
     for s_, d_ in pairs:
         if s_.shape != d_.shape or s_.dtype != d_.dtype or not s_.is_contiguous() or not d_.is_contiguous():
             raise ValueError("select_copy_many: shape / dtype / layout mismatch")
-    check(lib.pxm_select_copy_many(_p(flag), k, srcs, dsts, ns, es, flag.shape[0], _stream()))
+        # the kernel copies chain c's words [c * len, (c + 1) * len): the per-chain length is the array's size over C, so the
+        # leading axis must be the chain axis (one chain may come without it)
+        if C_ > 1 and (s_.dim() < 1 or s_.shape[0] != C_):
+            raise ValueError("select_copy_many: with %d chains every array must be [%d, ...], got %s" % (C_, C_, tuple(s_.shape)))
+    srcs = (C.c_void_p * k)(*[p[0].data_ptr() for p in pairs])
+    dsts = (C.c_void_p * k)(*[p[1].data_ptr() for p in pairs])
+    ns = (C.c_int64 * k)(*[p[0].numel() // C_ for p in pairs])
+    es = (C.c_int * k)(*[p[0].element_size() for p in pairs])
+    check(lib.pxm_select_copy_many(_p(flag), k, srcs, dsts, ns, es, C_, _stream()))
 
 
 def counter_add(counter, inc=1):
