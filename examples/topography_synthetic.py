@@ -9,6 +9,7 @@ experiments/earthtopography/main.py:72-185 on synthetic data (the ETOPO1 file ne
     python examples/topography_synthetic.py --L 32 --nsamples 50 --ngap 100 --chains 4 --outdir /tmp
 """
 import argparse
+import copy
 import os
 import sys
 from datetime import datetime
@@ -22,6 +23,7 @@ from pxmcmc_amd.forward import SphericalWaveletTransformOperator  # noqa: E402
 from pxmcmc_amd.mcmc import MYULA, SKROCK, PxMALA, PxMCMCParams  # noqa: E402
 from pxmcmc_amd.optim import FISTA  # noqa: E402
 from pxmcmc_amd.prior import S2_Wavelets_L1  # noqa: E402
+from pxmcmc_amd.sapg import SAPG  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
 from pxmcmc_amd.uncertainty import chain_to_images, credible_interval_range  # noqa: E402
 
@@ -41,6 +43,20 @@ def map_start(forwardop, regulariser, params, L_g, start_point, tol=1e-3, max_it
     return x
 
 
+def estimate_mu(forwardop, regulariser, params, delta_myula, args, start_point):
+    """--estimate-mu: SAPG (a MYULA chain whose threshold scale theta moves towards the marginal maximum-likelihood value,
+    DESIGN.md section 17) on the sampler's own operators first; returns the prior and the parameters with T and mu scaled by
+    theta_hat.  The chain takes MYULA's step whatever --algo is."""
+    p = copy.copy(params)
+    p.delta = float(delta_myula)
+    sapg = SAPG(forwardop, regulariser, p, nchains=args.chains, warmup=args.sapg_warmup, niter=args.sapg_iters,
+                burn=args.sapg_iters // 3)
+    theta_hat = sapg.run(start_point=start_point)
+    print(f"SAPG ({args.sapg_warmup} + {args.sapg_iters} iterations, graph replay: {sapg.used_graph}): theta_hat = "
+          f"{np.round(theta_hat, 6)}, mu_hat = {np.round(sapg.mu_hat, 6)} (mu given: {params.mu})")
+    return sapg.apply(regulariser, params)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--L", type=int, default=32, help="Angular bandlimit. Default 32.")
@@ -56,6 +72,10 @@ def main(argv=None):
     ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
     ap.add_argument("--spin", type=int, default=0, help="spin S of the field (S != 0: a complex spin-S field, dirs = 1)")
     ap.add_argument("--map-start", action="store_true", help="start the chain(s) at the MAP point found by FISTA first")
+    ap.add_argument("--estimate-mu", action="store_true",
+                    help="estimate the regularisation strength by SAPG first and sample with mu_hat = mu * theta_hat")
+    ap.add_argument("--sapg-warmup", type=int, default=100, help="--estimate-mu: MYULA iterations before theta moves")
+    ap.add_argument("--sapg-iters", type=int, default=600, help="--estimate-mu: iterations with a moving theta")
     ap.add_argument("--summary", action="store_true",
                     help="accumulate the posterior mean / standard deviation / R-hat on the GPU instead of saving the chain")
     ap.add_argument("--outdir", type=str, default=".")
@@ -91,7 +111,7 @@ def main(argv=None):
     lmda = 1e-6
     # step size inside the MYULA bound 1 / (L_g + 1 / lmda), L_g = ||S||^2 / sigma^2 (power iteration on the operator)
     L_g = forwardop.gradient_lipschitz(iters=50, tol=1e-3)  # (at most 50 operator pairs at start-up)
-    delta = 0.8 / (L_g + 1 / lmda)
+    delta = delta_myula = 0.8 / (L_g + 1 / lmda)
     print(f"L_g = {L_g:.6e}: MYULA step bound 1 / (L_g + 1 / lmda) = {1 / (L_g + 1 / lmda):.6e}, delta = {delta:.6e}")
     if args.algo == "skrock":  # SKROCK is stable up to (2 - 4 eta / 3) s^2 / L: the same margin, s^2 times the step
         delta *= args.s ** 2
@@ -105,8 +125,11 @@ def main(argv=None):
     print(f"Number of data points: {len(data)}")
     print(f"Number of model parameters: {forwardop.nparams}")
     cls = {"myula": MYULA, "pxmala": PxMALA, "skrock": SKROCK}[args.algo]
-    mcmc = cls(forwardop, regulariser, params, nchains=args.chains, summary="image" if args.summary else None)
     start_point = np.zeros(forwardop.nparams)
+    if args.estimate_mu:
+        regulariser, params = estimate_mu(forwardop, regulariser, params, delta_myula, args,
+                                          start_point.astype(complex) if spin else start_point)
+    mcmc = cls(forwardop, regulariser, params, nchains=args.chains, summary="image" if args.summary else None)
     if args.map_start:
         start_point = map_start(forwardop, regulariser, params, L_g, start_point.astype(complex) if spin else start_point)
     start = datetime.now()

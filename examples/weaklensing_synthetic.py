@@ -18,6 +18,7 @@ starts from the wavelet analysis of the Kaiser-Squires estimate (WeakLensingHarm
     python examples/weaklensing_synthetic.py --L 64 --algo pxmala --nsamples 20 --ngap 20 --nburn 100 --outdir /tmp
 """
 import argparse
+import copy
 import os
 import sys
 import time
@@ -33,6 +34,7 @@ from pxmcmc_amd.mcmc import MYULA, SKROCK, PxMALA, PxMCMCParams  # noqa: E402
 from pxmcmc_amd.measurements import WeakLensing, WeakLensingHarmonic  # noqa: E402
 from pxmcmc_amd.optim import FISTA  # noqa: E402
 from pxmcmc_amd.prior import L1, S2_Wavelets_L1  # noqa: E402
+from pxmcmc_amd.sapg import SAPG  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
 from pxmcmc_amd.transforms import SphericalWaveletTransform  # noqa: E402
 from pxmcmc_amd.utils import build_mask  # noqa: E402
@@ -94,6 +96,20 @@ def map_start(forward_operator, prior, params, L_g, start_point=None, tol=1e-3, 
     return x
 
 
+def estimate_mu(forward_operator, prior, params, L_g, args, start_point=None):
+    """--estimate-mu: SAPG (a MYULA chain whose threshold scale theta moves towards the marginal maximum-likelihood value,
+    DESIGN.md section 17) on the sampler's own operators first; returns the prior and the parameters with T and mu scaled by
+    theta_hat.  The chain takes --delta, or 0.8 of MYULA's bound when that is smaller."""
+    p = copy.copy(params)
+    p.delta = float(min(params.delta, 0.8 / (L_g + 1 / params.lmda)))
+    sapg = SAPG(forward_operator, prior, p, nchains=args.chains, warmup=args.sapg_warmup, niter=args.sapg_iters,
+                burn=args.sapg_iters // 3, seed=args.seed)
+    theta_hat = sapg.run(start_point=start_point)
+    print(f"SAPG ({args.sapg_warmup} + {args.sapg_iters} iterations at delta = {p.delta:.3e}, graph replay: {sapg.used_graph}): "
+          f"theta_hat = {np.round(theta_hat, 6)}, mu_hat = {np.round(sapg.mu_hat, 6)} (mu given: {params.mu})")
+    return sapg.apply(prior, params)
+
+
 def build_sampler(args, forward_operator, prior, params, space):
     """the sampler of --algo; with --summary the saved samples go into a device-resident summary of ``space`` ("image", or
     "state" for the harmonic posterior, whose transform has no image) and "chain" leaves ``track``"""
@@ -141,6 +157,10 @@ def main(argv=None):
     ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--map-start", action="store_true", help="start the chain(s) at the MAP point found by FISTA first")
+    ap.add_argument("--estimate-mu", action="store_true",
+                    help="estimate the regularisation strength by SAPG first and sample with mu_hat = mu * theta_hat")
+    ap.add_argument("--sapg-warmup", type=int, default=100, help="--estimate-mu: MYULA iterations before theta moves")
+    ap.add_argument("--sapg-iters", type=int, default=600, help="--estimate-mu: iterations with a moving theta")
     ap.add_argument("--summary", action="store_true",
                     help="accumulate the posterior mean / standard deviation / R-hat on the GPU instead of saving the chain")
     ap.add_argument("--harmonic", action="store_true",
@@ -166,6 +186,8 @@ def main(argv=None):
     print(f"Number of data points: {gammas_truth.size}")
     print(f"Number of model parameters: {forward_operator.nparams}")
     L_g = step_hint(forward_operator, params, args)
+    if args.estimate_mu:
+        prior, params = estimate_mu(forward_operator, prior, params, L_g, args)
     start_point = map_start(forward_operator, prior, params, L_g) if args.map_start else None
     mcmc = build_sampler(args, forward_operator, prior, params, "image")
 
@@ -210,6 +232,8 @@ def _main_harmonic(args, L, B, J_min, setting):
     X0 = transform.forward(measurement.sks_estimate(glm))
     print(f"harmonic set-up: {L * L} shear harmonics, {forward_operator.nparams} wavelet coefficients")
     L_g = step_hint(forward_operator, params, args)
+    if args.estimate_mu:
+        prior, params = estimate_mu(forward_operator, prior, params, L_g, args, start_point=X0)
     if args.map_start:
         X0 = map_start(forward_operator, prior, params, L_g, start_point=X0)
     mcmc = build_sampler(args, forward_operator, prior, params, "state")

@@ -42,7 +42,7 @@ typedef void* pxm_stream_t; /* hipStream_t */
 int pxm_version(void);
 /* Precision of the Box-Muller step of the Philox noise stream (pxmcmc/mcmc.py:193-195 draws fp64 randn).  Every
  * entry point that can draw noise takes the flag PXM_NOISE_F64, OR-ed into its `mode` (pxm_wav_*_step), `noise_complex`
- * (pxm_myula_step, pxm_chain_step, pxm_skrock_stage, pxm_pxmala_propose) or `dtype` (pxm_randn) argument:
+ * (pxm_myula_step, pxm_chain_step, pxm_skrock_stage, pxm_pxmala_propose, pxm_sapg_step) or `dtype` (pxm_randn) argument:
  *   absent   Box-Muller on the f32 transcendental units (v_log_f32 / v_sin_f32 / v_cos_f32 with the exact fp64 exponent:
  *            deviates ~1e-6 relative, tail to 8.5 sigma) -- the default, pxm_noise_bits() == 32;
  *   present  log / sqrt / sincos evaluated in double precision (branch-free polynomials, csrc/philox.h): deviates equal
@@ -370,6 +370,27 @@ int pxm_fista_step(const void* Y, const void* gradg, const void* proxf, const do
                    const void* X_prev, double gamma, double lmda, const double* beta_table, int64_t n_beta,
                    uint64_t iter, const uint64_t* iter_dev, void* X_out, void* Y_out, double* sums, double* scratch,
                    int64_t n, int C, int dtype, pxm_stream_t stream);
+/* One SAPG iteration (Vidal, De Bortoli, Pereyra & Durmus 2020): a MYULA step of every chain on the
+ * posterior whose prior is scaled by the chain's theta, then the move of theta towards the marginal maximum-likelihood
+ * value of the regularisation strength.  Every state array [C][n]; theta, eta [C] float64 on the device, updated in place.
+ *   thr_i = theta[c] T_i (rounded; T [n] shared by chains, or T_scalar);
+ *   X_out = (1 - delta/lmda) X + (delta/lmda) soft(X, thr) - delta gradg + sqrt(2 delta) w, the arithmetic and the noise of
+ *   pxm_myula_step (noise given, or the Philox stream keyed (seed, chain0 + c, element, iter + *iter_dev); noise_complex =
+ *   (0 | 1) | PXM_NOISE_F64; iter_dev: caller-owned device iteration counter or NULL);
+ *   G_c = (1 / lmda) sum_i T_i |X_out_i|, added in a fixed order that depends on n only (a chain's sum does not depend on its
+ *   batch); pool != 0: every chain takes the chain-order mean of the G_c;
+ *   eta[c] = min(max(eta[c] + rho (d - theta[c] G_c), eta_min), eta_max), rho = rho_table[min(iter + *iter_dev, n_rho - 1)]
+ *   read when the kernel runs;  theta[c] = exp(eta[c]);
+ *   trace [n_trace][C][3] (or NULL with n_trace 0): row iter + *iter_dev, when there is one, receives (theta, eta, G_c).
+ * d: the dimension of the state (the degree of the normaliser theta^-d of exp(-theta G)).  With n == 0 only the update runs,
+ * with G = 0.  scratch: caller-owned, (PXM_SAPG_SLICES_MAX + 1) * C doubles.  X_out, theta, eta, trace and scratch must not
+ * overlap an input or each other (only equal base pointers are detected and refused). */
+#define PXM_SAPG_SLICES_MAX 256
+int pxm_sapg_step(const void* X, const void* gradg, const double* T, double T_scalar, double delta, double lmda,
+                  const void* noise, int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter,
+                  const uint64_t* iter_dev, double* theta, double* eta, double d, const double* rho_table, int64_t n_rho,
+                  double eta_min, double eta_max, int pool, double* trace, int64_t n_trace, void* X_out, double* scratch,
+                  int64_t n, int C, int dtype, pxm_stream_t stream);
 /* N(0,1) draws of the Philox4x32-10 stream keyed (seed, chain0+c, iter): out [C][n] (f64 or c128) */
 int pxm_randn(void* out, int64_t n, int C, int dtype, uint64_t seed, uint64_t chain0, uint64_t iter,
               pxm_stream_t stream);

@@ -134,6 +134,11 @@ SIGNATURES = {
         [c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_dbl, c_dbl, c_vp, c_i64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int,
          c_vp],
     ),
+    "pxm_sapg_step": (
+        c_int,
+        [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i64, c_dbl, c_dbl,
+         c_int, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_vp],
+    ),
     "pxm_randn": (c_int, [c_vp, c_i64, c_int, c_int, c_u64, c_u64, c_u64, c_vp]),
     "pxm_box_muller": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "pxm_reduce_l1": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),

@@ -40,4 +40,41 @@ __device__ inline double2 chain_step_cplx(double2 X, double2 px, double2 g, doub
   return double2{chain_step_real(X.x, px.x, g.x, w.x, delta, lmda), chain_step_real(X.y, px.y, g.y, w.y, delta, lmda)};
 }
 
+// x * x + y * y with both products and the sum rounded (no fma contraction): numpy's re ** 2 + im ** 2
+__device__ __forceinline__ double abs2_plain(double x, double y) {
+#pragma clang fp contract(off)
+  return x * x + y * y;
+}
+
+// ---- the noise of the stepping kernels (pxm_myula_step, pxm_chain_step, pxm_randn, pxm_sapg_step): a given [C][n] array
+// or the Philox stream keyed (seed, chain0 + c, element, iter + *iter_dev)
+struct NoiseSrc {
+  const double* noise;
+  int noise_complex;
+  uint64_t seed, chain0, iter;
+  const uint64_t* iter_dev = nullptr;  // optional device-resident addend to iter (caller-owned counter: graph replay)
+  int f64 = 0;                         // Box-Muller step in double precision (flag PXM_NOISE_F64 of the entry point)
+};
+// noise_complex argument of the entry points = (0 | 1) | PXM_NOISE_F64 (include/pxmcmc_amd.h is not included here: its mode
+// macros would replace the enumerators of update.h; the callers assert that the two values agree)
+constexpr int NOISE_F64_FLAG = 16;
+static inline NoiseSrc make_noise_src(const void* noise, int noise_arg, uint64_t seed, uint64_t chain0, uint64_t iter,
+                                      const uint64_t* iter_dev = nullptr) {
+  return NoiseSrc{(const double*)noise, noise_arg & 1, seed, chain0, iter, iter_dev, (noise_arg & NOISE_F64_FLAG) ? 1 : 0};
+}
+
+template <bool CPLX>
+__device__ inline double2 draw_noise(const NoiseSrc& ns, int c, int64_t n, int64_t i) {
+  if (ns.noise) {
+    if (CPLX && ns.noise_complex) return reinterpret_cast<const double2*>(ns.noise)[(int64_t)c * n + i];
+    return double2{ns.noise[(int64_t)c * n + i], 0.0};
+  }
+  const uint64_t it = ns.iter + (ns.iter_dev ? *ns.iter_dev : 0);
+  if (CPLX && ns.noise_complex) {
+    NormalPair q = philox_normal_pair(ns.seed, ns.chain0 + c, (uint64_t)i, it, ns.f64);
+    return double2{q.z0, q.z1};
+  }
+  return double2{philox_normal_real(ns.seed, ns.chain0 + c, (uint64_t)i, it, ns.f64), 0.0};
+}
+
 }  // namespace pxm

@@ -9,6 +9,8 @@
 
 namespace pxm {
 
+static_assert(NOISE_F64_FLAG == PXM_NOISE_F64, "elem.h: the noise flag must be the public one");
+
 static inline dim3 ew_grid(int64_t n, int C) {
   int64_t bx = (n + 255) / 256;
   if (bx > 2048) bx = 2048;
@@ -47,33 +49,6 @@ __global__ void k_residual(const double* __restrict__ preds, const double* __res
       out[base + i] = invcov[i] * (preds[base + i] - data[i]);
     }
   }
-}
-
-struct NoiseSrc {
-  const double* noise;
-  int noise_complex;
-  uint64_t seed, chain0, iter;
-  const uint64_t* iter_dev = nullptr;  // optional device-resident addend to iter (caller-owned counter: graph replay)
-  int f64 = 0;                         // Box-Muller step in double precision (flag PXM_NOISE_F64 of the entry point)
-};
-// noise_complex argument of the entry points = (0 | 1) | PXM_NOISE_F64
-static inline NoiseSrc make_noise_src(const void* noise, int noise_arg, uint64_t seed, uint64_t chain0, uint64_t iter,
-                                      const uint64_t* iter_dev = nullptr) {
-  return NoiseSrc{(const double*)noise, noise_arg & 1, seed, chain0, iter, iter_dev, (noise_arg & PXM_NOISE_F64) ? 1 : 0};
-}
-
-template <bool CPLX>
-__device__ inline double2 draw_noise(const NoiseSrc& ns, int c, int64_t n, int64_t i) {
-  if (ns.noise) {
-    if (CPLX && ns.noise_complex) return reinterpret_cast<const double2*>(ns.noise)[(int64_t)c * n + i];
-    return double2{ns.noise[(int64_t)c * n + i], 0.0};
-  }
-  const uint64_t it = ns.iter + (ns.iter_dev ? *ns.iter_dev : 0);
-  if (CPLX && ns.noise_complex) {
-    NormalPair q = philox_normal_pair(ns.seed, ns.chain0 + c, (uint64_t)i, it, ns.f64);
-    return double2{q.z0, q.z1};
-  }
-  return double2{philox_normal_real(ns.seed, ns.chain0 + c, (uint64_t)i, it, ns.f64), 0.0};
 }
 
 // X_out = (1-d/l) X + (d/l) P - d g + sqrt(2d) w, with P = soft(X,T) (FUSED_PROX) or given

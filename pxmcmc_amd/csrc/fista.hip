@@ -24,9 +24,7 @@
 namespace pxm {
 
 // workgroups (slices) per chain: one per 256 elements up to PXM_FISTA_SLICES_MAX, grid-stride beyond
-static inline int fista_slices(int64_t n) {
-  return (int)std::min<int64_t>(PXM_FISTA_SLICES_MAX, std::max<int64_t>(1, (n + 255) / 256));
-}
+static inline int fista_slices(int64_t n) { return chain_slices(n, PXM_FISTA_SLICES_MAX); }
 
 struct FistaSums {
   double dx2, x2, tx;
@@ -47,12 +45,6 @@ __device__ __forceinline__ FistaSums fista_block_sum(FistaSums v) {
   if (threadIdx.x == 0)
     for (int w = 0; w < 4; ++w) tot.dx2 += part[w][0], tot.x2 += part[w][1], tot.tx += part[w][2];
   return tot;
-}
-
-// x * x + y * y with both products and the sum rounded (no fma contraction): numpy's re ** 2 + im ** 2
-__device__ __forceinline__ double abs2_plain(double x, double y) {
-#pragma clang fp contract(off)
-  return x * x + y * y;
 }
 
 // GIVEN: X_{k+1} is the array P (Y, G, T unused); else X_{k+1} = soft(Y - gamma G, tscale T_i), T_i = T[i] or Ts

@@ -285,6 +285,59 @@ def fista_step(Y, gradg, X_prev, gamma, lmda, beta, T=None, proxf=None, it=0, it
     return (x1[0], y1[0], sums) if squeeze else (x1, y1, sums)
 
 
+SAPG_SLICES_MAX = 256  # PXM_SAPG_SLICES_MAX: partial sums per chain of pxm_sapg_step
+
+
+def sapg_scratch(C_, dev):
+    """scratch of :func:`sapg_step` for C_ chains (the stepping engine keeps one: no allocation per iteration)"""
+    return torch.empty((SAPG_SLICES_MAX + 1) * int(C_), dtype=_REAL, device=dev)
+
+
+def sapg_step(X, gradg, T, delta, lmda, theta, eta, d, rho, eta_min, eta_max, pool=False, trace=None, noise=None,
+              noise_complex=False, seed=0, chain0=0, it=0, iter_dev=None, out=None, scratch=None, noise64=False):
+    """One SAPG iteration: the MYULA step of :func:`myula_step` with chain c's soft threshold scaled
+    by ``theta[c]``, read on the device, then ``eta[c] = clip(eta[c] + rho_k (d - theta[c] G_c))``, ``theta[c] = exp(eta[c])``
+    with ``G_c = (1 / lmda) sum_i T_i |X1_i|`` of the new state (``pool``: the chain mean of the ``G_c``).
+
+    ``theta``, ``eta``: contiguous float64 ``[C]`` device vectors, updated in place.  ``rho``: the step-size table (float64
+    device vector, or a sequence); ``rho_k`` is entry ``it`` [+ ``*iter_dev``], read when the kernel runs and clamped to the
+    table's last entry.  ``trace``: float64 ``[n_trace, C, 3]`` device array or None; row ``it`` [+ ``*iter_dev``], when there
+    is one, receives ``(theta, eta, G)``.  ``delta`` is a float (no per-chain step).  Returns ``(X1, theta, eta)``."""
+    x, squeeze = _batched(as_device(X))
+    g, _ = _batched(as_device(gradg, x.dtype))
+    if g.shape != x.shape:
+        raise ValueError("sapg_step: gradg shape mismatch")
+    if isinstance(delta, torch.Tensor):
+        raise ValueError("sapg_step: delta must be a float (no per-chain step sizes)")
+    C_, n = x.shape
+    Tv, Ts = _vecT(T, n, x.device)
+    w, wc = _noise_args(noise, x, noise_complex)
+    for name, v in (("theta", theta), ("eta", eta)):
+        if not isinstance(v, torch.Tensor) or v.shape != (C_,) or v.dtype != _REAL or not v.is_contiguous() or v.device != x.device:
+            raise ValueError(f"sapg_step: {name} must be a contiguous float64 [C] device vector")
+    rt = rho if isinstance(rho, torch.Tensor) else as_device(np.atleast_1d(np.asarray(rho, dtype=float)), _REAL)
+    if rt.dtype != _REAL or rt.dim() != 1 or rt.numel() < 1 or not rt.is_contiguous() or rt.device != x.device:
+        raise ValueError("sapg_step: rho must be a non-empty contiguous float64 device vector")
+    n_trace = 0
+    if trace is not None:
+        if trace.dim() != 3 or trace.shape[1:] != (C_, 3) or trace.dtype != _REAL or not trace.is_contiguous() or trace.device != x.device:
+            raise ValueError("sapg_step: trace must be a contiguous float64 [n_trace, C, 3] device array")
+        n_trace = trace.shape[0]
+    out = torch.empty_like(x) if out is None else _out_like(out, x)
+    if scratch is None:
+        scratch = sapg_scratch(C_, x.device)
+    elif scratch.numel() < (SAPG_SLICES_MAX + 1) * C_ or scratch.dtype != _REAL or not scratch.is_contiguous():
+        raise ValueError("sapg_step: scratch is too small (sapg_scratch)")
+    check(
+        lib.pxm_sapg_step(
+            _p(x), _p(g), _p(Tv), Ts, float(delta), float(lmda), _p(w), wc | _nf(noise64), seed, chain0, int(it), _p(iter_dev),
+            _p(theta), _p(eta), float(d), _p(rt), rt.numel(), float(eta_min), float(eta_max), int(bool(pool)),
+            _p(trace if n_trace else None), n_trace, _p(out), _p(scratch), n, C_, _dt(x), _stream()
+        )
+    )
+    return (out[0] if squeeze else out), theta, eta
+
+
 def randn(n, C_=1, complex_=False, seed=0, chain0=0, it=0, noise64=False):
     """N(0,1) draws of the device Philox stream keyed (seed, chain0 + c, it); noise64: Box-Muller in double precision"""
     out = torch.empty((C_, n), dtype=_CPLX if complex_ else _REAL, device=device())

@@ -1,0 +1,334 @@
+"""Host model of SAPG, the estimator of the regularisation strength (pxmcmc_amd/sapg.py, csrc/sapg.hip): the numpy
+restatement of one step and one update in the kernel's operation order, the extended-precision yardstick of the X update that
+tests/test_gpu_sapg.py holds the kernel to, and the statistical yardstick -- the closed-form marginal maximum-likelihood
+estimate of a Laplace / Gaussian denoising problem.
+
+    thr = fl(theta_c T);   X1 = (1 - delta/lmda) X + (delta/lmda) soft(X, thr) - delta g + sqrt(2 delta) w
+    G_c = (1 / lmda) sum_i T_i |X1_i|;   eta_c = clip(eta_c + rho (d - theta_c G_c));   theta_c = exp(eta_c)
+
+The numpy route uses ``oracle.pxmcmc_np.soft`` / ``chain_step``; nothing here runs the code under test except the step-size
+table, which is host arithmetic."""
+import numpy as np
+import pytest
+
+from oracle import pxmcmc_np
+
+EPS = 2.0 ** -52
+HAVE_LD = np.finfo(np.longdouble).eps < 1.1e-19  # x87 80-bit; otherwise mpmath at 40 digits, never a skip
+SLICES_MAX = 256  # PXM_SAPG_SLICES_MAX (test_scratch_size_constant_matches_the_header)
+
+# Largest error of the fp64 numpy route of the X update against the extended-precision model, over every element of
+# step_cases(), in units of 2^-52 S_e (test_numpy_route_against_extended_model measures it and holds it to this value).
+# Observed: 1.3914 (complex128), 1.2701 (float64).
+C0_MEASURED = 1.40
+
+# Largest relative deviation of the host SAPG loop's theta_hat from closed_form_mle on laplace_problem(), over the seeds
+# 0 ... 7 (test_host_sapg_finds_the_marginal_mle measures it and holds it to this value).  The deviation is MYULA's bias --
+# the chain samples the Moreau-Yosida smoothed posterior with a finite step -- not noise: every seed lands within 0.08 % of
+# the others.  Observed (MLE 4.7998): -1.057 %, -1.078 %, -1.046 %, -1.097 %, -1.093 %, -1.107 %, -1.119 %, -1.121 %; from
+# theta_0 = 25 (seed 0): -1.057 %.
+SAPG_REL_DEV = 0.0113
+
+
+# ---- numpy model ---------------------------------------------------------------------------------------------------------
+def sapg_step_np(X, g, T, theta, delta, lmda, w):
+    """the X update of C chains, fp64 numpy: X, g, w [C, n]; T a scalar or [n]; theta [C]"""
+    thr = np.asarray(theta, dtype=float)[:, None] * T  # rounded before the shrink
+    return pxmcmc_np.chain_step(X, pxmcmc_np.soft(X, thr), g, delta, lmda, w)
+
+
+def slices_of(n):
+    """workgroups per chain (common.h: chain_slices)"""
+    return int(min(SLICES_MAX, max(1, (n + 255) // 256)))
+
+
+def _tree64(v):
+    """lane 0 of the shuffle-down reduction of 64 lanes: offsets 32, 16, ..., 1 (last axis)"""
+    for off in (32, 16, 8, 4, 2, 1):
+        v = v[..., :off] + v[..., off:2 * off]
+    return v[..., 0]
+
+
+def sapg_sum_np(X1, T):
+    """sum_i T_i |X1_i| of one chain in the kernels' order: |z| = sqrt(re^2 + im^2) with every product and sum rounded; lane t
+    of slice b adds its elements b 256 + t + k 256 slices one after the other, the 64 lanes of a wave by the shuffle tree,
+    the four waves in order; then lane l of the update kernel adds the slices l, l + 64, ... and the tree joins the lanes"""
+    n = X1.shape[0]
+    term = np.broadcast_to(np.asarray(T, dtype=float), (n,)) * np.sqrt(np.real(X1) ** 2 + np.imag(X1) ** 2)
+    sl = slices_of(n)
+    passes = -(-n // (256 * sl))
+    padded = np.zeros(passes * sl * 256)
+    padded[:n] = term
+    lanes = np.zeros((sl, 256))
+    for k in range(passes):  # (adding the padding's +0.0 changes nothing: every term is >= 0)
+        lanes = lanes + padded[k * sl * 256:(k + 1) * sl * 256].reshape(sl, 256)
+    waves = _tree64(lanes.reshape(sl, 4, 64))
+    part = ((waves[:, 0] + waves[:, 1]) + waves[:, 2]) + waves[:, 3]
+    rows = -(-sl // 64)
+    padded = np.zeros(rows * 64)
+    padded[:sl] = part
+    acc = np.zeros(64)
+    for r in range(rows):
+        acc = acc + padded[r * 64:(r + 1) * 64]
+    return float(_tree64(acc))
+
+
+def sapg_update_np(S, theta, eta, d, rho, lmda, eta_min, eta_max, pool=False):
+    """one update from the per-chain sums S [C] -> (theta, eta, G), each operation rounded as written"""
+    G = np.asarray(S, dtype=float) / lmda
+    if pool:
+        s = 0.0
+        for gc in G:
+            s = s + gc
+        G = np.full_like(G, s / len(G))
+    eta = np.minimum(np.maximum(eta + rho * (d - theta * G), eta_min), eta_max)
+    return np.exp(eta), eta, G
+
+
+def rho_table(warmup, niter, ndim, scale=10.0, exponent=0.8):
+    return np.array([0.0] * warmup + [scale * j ** (-exponent) / ndim for j in range(1, niter + 1)])
+
+
+# ---- extended-precision model of the X update ----------------------------------------------------------------------------
+def sapg_step_ext(X, g, T, theta, delta, lmda, w):
+    """X1 in extended precision from the fp64 threshold fl(theta_c T_i), as (re, im) long double arrays (mpmath objects
+    without an 80-bit type)"""
+    thr64 = np.broadcast_to(np.asarray(theta, dtype=float)[:, None] * T, np.shape(X))
+    if HAVE_LD:
+        ld = np.longdouble
+        f = lambda a: np.asarray(a, dtype=np.float64).astype(ld)  # noqa: E731
+        xr, xi, gr, gi, wr, wi = f(np.real(X)), f(np.imag(X)), f(np.real(g)), f(np.imag(g)), f(np.real(w)), f(np.imag(w))
+        thr = f(thr64)
+        a = np.sqrt(xr * xr + xi * xi)
+        s = np.where(a > thr, (a - thr) / np.where(a > 0, a, 1), 0)
+        r, rt = ld(delta) / ld(lmda), np.sqrt(ld(2) * ld(delta))
+        one = lambda x, p, gg, ww: (1 - r) * x + r * p - ld(delta) * gg + rt * ww  # noqa: E731
+        return one(xr, xr * s, gr, wr), one(xi, xi * s, gi, wi)
+    import mpmath
+
+    mpmath.mp.dps = 40
+    m = mpmath.mpf
+    r, rt = m(delta) / m(lmda), mpmath.sqrt(2 * m(delta))
+    out = [[], []]
+    for x, gg, ww, t in zip(np.ravel(X), np.ravel(g), np.ravel(w), np.ravel(thr64)):
+        xr, xi = m(float(np.real(x))), m(float(np.imag(x)))
+        a = mpmath.sqrt(xr * xr + xi * xi)
+        s = (a - m(float(t))) / a if a > m(float(t)) else m(0)
+        for o, xx, g1, w1 in ((out[0], xr, np.real(gg), np.real(ww)), (out[1], xi, np.imag(gg), np.imag(ww))):
+            o.append((1 - r) * xx + r * xx * s - m(delta) * m(float(g1)) + rt * m(float(w1)))
+    return tuple(np.array(o, dtype=object).reshape(np.shape(X)) for o in out)
+
+
+def error_scale(X, g, T, theta, delta, lmda, w):
+    """S_e = (|1 - delta/lmda| + delta/lmda) |X_e| + (delta/lmda) theta_c T_e + delta |g_e| + sqrt(2 delta) |w_e|"""
+    r = delta / lmda
+    thr = np.asarray(theta, dtype=float)[:, None] * T
+    return (abs(1 - r) + r) * np.abs(X) + r * thr + delta * np.abs(g) + np.sqrt(2 * delta) * np.abs(w)
+
+
+def ratio_to_ext(got, ext, S):
+    """largest |got - ext| over the elements in units of 2^-52 S_e (complex: the modulus of the difference)"""
+    if HAVE_LD:
+        dr = np.array(np.real(got).astype(np.longdouble) - ext[0], dtype=float)
+        di = np.array(np.imag(got).astype(np.longdouble) - ext[1], dtype=float)
+    else:
+        dr = np.array([float(a - b) for a, b in zip(np.ravel(np.real(got)), np.ravel(ext[0]))])
+        di = np.array([float(a - b) for a, b in zip(np.ravel(np.imag(got)), np.ravel(ext[1]))])
+    return float(np.max(np.hypot(dr, di).reshape(-1) / (EPS * np.ravel(S))))
+
+
+THETAS = np.array([0.7, 1.0, 2.3])  # one per chain; 1.0 leaves the threshold as it is
+
+
+def step_inputs(n, C, cplx, vecT, seed):
+    """inputs of one step for C chains of n elements: T has zeros (no shrink) and entries above every |X| (the prox is zero);
+    thresholds on both sides of |X| are included (the branch of the shrink); theta differs per chain"""
+    rng = np.random.default_rng(seed)
+    draw = (lambda: rng.normal(size=(C, n)) + 1j * rng.normal(size=(C, n))) if cplx else (lambda: rng.normal(size=(C, n)))
+    X, g, w = draw(), draw() * 3.0, draw()
+    delta, lmda = 0.9e-2, 2.5e-2
+    if vecT:
+        T = np.abs(rng.normal(size=n)) * 0.8
+        T[::5] = 0.0
+        T[2::7] = 1e3
+    else:
+        T = 0.6
+    return X, g, T, THETAS[:C].copy(), delta, lmda, w
+
+
+def step_cases():
+    for cplx in (False, True):
+        for vecT in (False, True):
+            yield cplx, vecT, step_inputs(257, 3, cplx, vecT, seed=23 + 2 * cplx + vecT)
+
+
+# ---- the statistical yardstick -------------------------------------------------------------------------------------------
+def laplace_problem(n=1024, theta_star=5.0, sigma=0.05, seed=2020):
+    """y = x + sigma n with x_i ~ Laplace(1 / theta*): identity operators, lmda = sigma^2, T = lmda (so G(X) = sum |X_i| and
+    the prior is exp(-theta sum |x_i|)), delta = 0.98 / (1 / sigma^2 + 1 / lmda)"""
+    rng = np.random.default_rng(seed)
+    x = rng.laplace(scale=1.0 / theta_star, size=n)
+    y = x + sigma * rng.normal(size=n)
+    lmda = sigma ** 2
+    return dict(n=n, y=y, sigma=sigma, lmda=lmda, T=lmda, delta=0.98 / (1 / sigma ** 2 + 1 / lmda), warmup=200, niter=1500,
+                burn=500, theta0=1.0, theta_min=1e-3, theta_max=1e3)
+
+
+def _log_erfcx(z):
+    from scipy.special import erfc, erfcx
+
+    with np.errstate(over="ignore"):
+        return np.where(z < 0, np.log(erfc(np.minimum(z, 0))) + z * z, np.log(erfcx(np.maximum(z, 0))))
+
+
+def marginal_loglik(theta, y, sigma):
+    """log p(y | theta) up to a constant: per component
+    int (theta / 2) e^{-theta |x|} N(y - x; sigma^2) dx = (theta / 4) e^{-y^2 / 2 sigma^2} [erfcx(z-) + erfcx(z+)],
+    z-+ = (theta sigma^2 -+ y) / (sigma sqrt 2)"""
+    zm, zp = (theta * sigma ** 2 - y) / (sigma * np.sqrt(2)), (theta * sigma ** 2 + y) / (sigma * np.sqrt(2))
+    return float(np.sum(np.log(theta) + np.logaddexp(_log_erfcx(zm), _log_erfcx(zp))))
+
+
+def closed_form_mle(y, sigma, theta_min=1e-3, theta_max=1e3):
+    """the maximiser of the marginal likelihood over [theta_min, theta_max] (1-D, bounded in log theta)"""
+    from scipy.optimize import minimize_scalar
+
+    res = minimize_scalar(lambda e: -marginal_loglik(np.exp(e), y, sigma), bounds=(np.log(theta_min), np.log(theta_max)),
+                          method="bounded", options=dict(xatol=1e-10))
+    assert res.success
+    return float(np.exp(res.x))
+
+
+def sapg_np(prob, seed, theta0=None, vecT=False):
+    """the host SAPG loop on laplace_problem() for one chain, numpy noise -> (theta_hat, theta trace)"""
+    rng = np.random.default_rng([seed, 77])
+    y, sigma, lmda, delta, n = prob["y"], prob["sigma"], prob["lmda"], prob["delta"], prob["n"]
+    T = np.full(n, prob["T"]) if vecT else prob["T"]
+    rho = rho_table(prob["warmup"], prob["niter"], float(n))
+    lo, hi = np.log(prob["theta_min"]), np.log(prob["theta_max"])
+    eta = np.log(np.array([prob["theta0"] if theta0 is None else theta0], dtype=float))
+    theta = np.exp(eta)
+    X = y[None, :].copy()
+    trace = np.empty(len(rho))
+    for k in range(len(rho)):
+        g = (X - y) / sigma ** 2
+        X = sapg_step_np(X, g, T, theta, delta, lmda, rng.normal(size=(1, n)))
+        theta, eta, _ = sapg_update_np([sapg_sum_np(X[0], T)], theta, eta, float(n), rho[k], lmda, lo, hi)
+        trace[k] = theta[0]
+    return float(trace[prob["warmup"] + prob["burn"]:].mean()), trace
+
+
+# ---- tests ---------------------------------------------------------------------------------------------------------------
+def test_rho_table_matches_its_formula():
+    from pxmcmc_amd.sapg import sapg_rho_table
+
+    for warmup, niter, ndim, scale, expo in ((0, 1, 1.0, 10.0, 0.8), (200, 1500, 1024.0, 10.0, 0.8), (3, 7, 2 * 1140.0, 2.5, 0.6)):
+        got = sapg_rho_table(warmup, niter, ndim, scale, expo)
+        want = rho_table(warmup, niter, ndim, scale, expo)
+        assert got.shape == (warmup + niter,) and np.all(got[:warmup] == 0)
+        assert np.allclose(got, want, rtol=4 * EPS, atol=0)
+        assert got[warmup] == pytest.approx(scale / ndim, rel=2 * EPS) and np.all(np.diff(got[warmup:]) < 0)
+    with pytest.raises(ValueError):
+        sapg_rho_table(1, 0, 10.0)
+
+
+def test_scratch_size_constant_matches_the_header():
+    """ops sizes the kernel's scratch with its own copy of PXM_SAPG_SLICES_MAX: the two must not drift apart"""
+    import os
+    import re
+
+    from conftest import ROOT
+    from pxmcmc_amd import ops
+
+    header = open(os.path.join(ROOT, "include", "pxmcmc_amd.h")).read()
+    (value,) = re.findall(r"#define\s+PXM_SAPG_SLICES_MAX\s+(\d+)", header)
+    assert int(value) == ops.SAPG_SLICES_MAX == SLICES_MAX
+
+
+def test_fixed_order_sum_is_a_sum():
+    """the kernels' summation order against math.fsum: at most n additions of non-negative terms -> n 2^-52 relative; one
+    slice, two slices, and more elements than SLICES_MAX workgroups hold in one pass"""
+    import math
+
+    rng = np.random.default_rng(1)
+    for n in (1, 257, 65541):
+        X1 = rng.normal(size=n) + 1j * rng.normal(size=n)
+        T = np.abs(rng.normal(size=n))
+        want = math.fsum(T * np.sqrt(X1.real ** 2 + X1.imag ** 2))
+        assert abs(sapg_sum_np(X1, T) - want) <= n * EPS * want
+        assert sapg_sum_np(X1.real, 0.5) == pytest.approx(0.5 * np.abs(X1.real).sum(), rel=n * EPS)
+    assert [slices_of(n) for n in (0, 1, 256, 257, 65536, 65541)] == [1, 1, 1, 2, 256, 256]
+
+
+def test_update_is_the_projected_gradient_step():
+    """eta moves by rho (d - theta G) = rho theta (d / theta - G), the paper's projected update on the log scale; the clip
+    holds; pooling replaces every G by the chain mean"""
+    theta, eta = np.array([2.0, 0.5]), np.log(np.array([2.0, 0.5]))
+    S, lmda, d = np.array([3.0, 9.0]), 0.5, 10.0
+    th, e, G = sapg_update_np(S, theta, eta, d, 0.01, lmda, -5.0, 5.0)
+    assert np.array_equal(G, S / lmda)
+    assert np.allclose(e, eta + 0.01 * theta * (d / theta - G), rtol=4 * EPS) and np.allclose(th, np.exp(e), rtol=2 * EPS)
+    th, e, G = sapg_update_np(S, theta, eta, d, 0.01, lmda, -5.0, 5.0, pool=True)
+    assert np.array_equal(G, np.full(2, (S[0] / lmda + S[1] / lmda) / 2))
+    th, e, _ = sapg_update_np(S, theta, eta, d, 10.0, lmda, -0.25, 0.75)
+    assert set(e) <= {-0.25, 0.75} and np.array_equal(th, np.exp(e))
+    th, e, _ = sapg_update_np(S, theta, eta, d, 0.0, lmda, -5.0, 5.0)  # the warm-up: nothing moves
+    assert np.array_equal(e, eta)
+
+
+def test_numpy_route_against_extended_model():
+    """the yardstick of the GPU test: how far the fp64 numpy route of the X update is from the extended-precision model,
+    per element, in units of 2^-52 S_e -- measured here, pinned as C0_MEASURED"""
+    worst = {}
+    for cplx, vecT, inp in step_cases():
+        X, g, T, theta, delta, lmda, w = inp
+        X1 = sapg_step_np(*inp)
+        r = ratio_to_ext(X1, sapg_step_ext(*inp), error_scale(*inp))
+        worst[cplx] = max(worst.get(cplx, 0.0), r)
+        if vecT:  # the cases have what they are meant to have: the prox is zero under the large thresholds, X under T = 0
+            P = pxmcmc_np.soft(X, theta[:, None] * T)
+            assert np.all(P[:, 2::7] == 0) and np.allclose(P[:, 5::35], X[:, 5::35], rtol=4 * EPS, atol=0) and np.any((P != 0) & (P != X))
+    print("fp64 numpy route vs extended model, units of 2^-52 S_e:", worst)
+    assert max(worst.values()) <= C0_MEASURED
+    assert max(worst.values()) >= C0_MEASURED / 4  # the pinned value is the measured one, not a loose cap
+
+
+def test_closed_form_mle_is_the_maximiser():
+    """the 1-D maximiser against a brute-force scan of the likelihood, and against the truth within the spread a sample of
+    n = 1024 allows (the Fisher information of a noiseless Laplace sample is n / theta^2: 3 % at one sigma)"""
+    prob = laplace_problem()
+    y, sigma = prob["y"], prob["sigma"]
+    mle = closed_form_mle(y, sigma)
+    grid = np.exp(np.linspace(np.log(mle) - 0.2, np.log(mle) + 0.2, 401))
+    ll = np.array([marginal_loglik(t, y, sigma) for t in grid])
+    assert abs(grid[np.argmax(ll)] - mle) <= 1.5 * (grid[1] - grid[0])
+    assert marginal_loglik(mle, y, sigma) >= ll.max() - 1e-9 * abs(ll.max())
+    assert abs(mle - 5.0) <= 4 * 5.0 / np.sqrt(prob["n"])
+    # the erfcx form against direct quadrature of one component
+    from scipy.integrate import quad
+
+    for yi in (-0.8, 0.03, 2.5):
+        f = lambda x: 0.5 * 3.0 * np.exp(-3.0 * abs(x)) * np.exp(-(yi - x) ** 2 / (2 * sigma ** 2))  # noqa: E731
+        direct = quad(f, yi - 12 * sigma, yi + 12 * sigma, points=[0.0] if abs(yi) < 12 * sigma else None, epsabs=0, epsrel=1e-11)[0]
+        closed = np.exp(marginal_loglik(3.0, np.array([yi]), sigma) - yi ** 2 / (2 * sigma ** 2)) * sigma * np.sqrt(2 * np.pi) / 4
+        assert closed == pytest.approx(direct, rel=1e-9)
+
+
+def test_host_sapg_finds_the_marginal_mle():
+    """the host loop on laplace_problem() over 8 seeds (scalar and vector T alternate: the same arithmetic), from theta_0 = 1
+    and, once, from theta_0 = 25: the largest relative deviation from the closed-form MLE is SAPG_REL_DEV"""
+    prob = laplace_problem()
+    mle = closed_form_mle(prob["y"], prob["sigma"])
+    devs = []
+    for seed in range(8):
+        hat, trace = sapg_np(prob, seed, vecT=bool(seed & 1))
+        assert np.all(trace[:prob["warmup"]] == prob["theta0"])  # the warm-up leaves theta alone
+        devs.append((hat - mle) / mle)
+    print(f"MLE {mle:.4f}; relative deviations of theta_hat:", ", ".join(f"{100 * d:+.3f} %" for d in devs))
+    worst = max(abs(d) for d in devs)
+    assert worst <= SAPG_REL_DEV
+    assert worst >= SAPG_REL_DEV / 2  # the pinned value is the measured one, not a loose cap
+    assert max(devs) - min(devs) <= 2e-3  # bias, not noise
+    far, _ = sapg_np(prob, 0, theta0=25.0)
+    print(f"from theta_0 = 25: {100 * (far - mle) / mle:+.3f} %")
+    assert abs(far - mle) / mle <= SAPG_REL_DEV
