@@ -20,10 +20,17 @@ namespace pxm {
 
 // TAB_GRAM: (B^m)^T B^m, el <- el: the inverse transform followed by its adjoint in one contraction
 // (normal equations of the ring-space MYULA step)
-enum TableKind { TAB_INV = 0, TAB_FWD = 1, TAB_INV_ADJ = 2, TAB_FWD_ADJ = 3, TAB_GRAM = 4, TAB_KINDS = 5 };
+// TAB_GRAM_SPLIT: the same matrix for spin 0 and Rp % 32 == 0, stored without its structurally zero half.  For m >= 1
+// the entries G^m[l][l'] with l + l' odd vanish, so order m is kept as two half-size dense
+// matrices G_p[i][j] = G^m[2i + p][2j + p], p = 0 (even degrees) and 1 (odd degrees), each tiled like any other table
+// from kb_p = round_down(ceil((m - p) / 2), 16).  m = 0 has a real odd-parity part (the pole ring) and stays dense.
+// An order stays one dense block where the two halves would not be cheaper (gram_order_splits below): the halves cannot
+// go below one 16 x 16 tile, and each is a workgroup with a start-up and a drain of its own.
+enum TableKind { TAB_INV = 0, TAB_FWD = 1, TAB_INV_ADJ = 2, TAB_FWD_ADJ = 3, TAB_GRAM = 4, TAB_GRAM_SPLIT = 5, TAB_KINDS = 6 };
 inline bool kind_el_to_ring(int kind) { return kind == TAB_INV || kind == TAB_FWD_ADJ; }
-inline bool kind_rows_are_el(int kind) { return kind == TAB_FWD || kind == TAB_INV_ADJ || kind == TAB_GRAM; }
-inline bool kind_k_is_el(int kind) { return kind == TAB_INV || kind == TAB_FWD_ADJ || kind == TAB_GRAM; }
+inline bool kind_is_gram(int kind) { return kind == TAB_GRAM || kind == TAB_GRAM_SPLIT; }
+inline bool kind_rows_are_el(int kind) { return kind == TAB_FWD || kind == TAB_INV_ADJ || kind_is_gram(kind); }
+inline bool kind_k_is_el(int kind) { return kind == TAB_INV || kind == TAB_FWD_ADJ || kind_is_gram(kind); }
 
 // One workgroup's share of a per-m GEMM: up to 8 row tiles of 16 output rows.
 // Column slabs: slab 0 = +m, slab 1 = -m (spin 0 shares one table up to the sign (-1)^m).  A MERGED task
@@ -49,9 +56,10 @@ struct GemmTask {
   int m_unit;          // the order this task belongs to: m (paired tables: m >= 0 serves +-m) or m + L - 1
   int hd_stride;       // doubles between consecutive rows of the affine constants: 2 = the chain-less [m][row] complex
                        // array of the Gram step (whole 64-B segments per wave), ncol = columns 0, 1 of an H-layout array
-  int x_ncol, y_ncol;  // packed lists: doubles per row of THIS task's operand / result arrays (a narrow ring array of a
-                       // few-chain plan has 2 C or 4 columns per row instead of the plan's 16); the 16-columns-per-slab
-                       // kernels take the launch's ncol for both
+  int x_ncol, y_ncol;  // doubles per row of THIS task's operand / result arrays.  Read by the packed kernels (a narrow ring
+                       // array of a few-chain plan has 2 C or 4 columns per row instead of the plan's 16) and by the
+                       // two-operand kernels (the parity halves of the split Gram list step through an H-layout plane two
+                       // rows at a time: 2 ncol); the streaming 16-columns-per-slab kernels take the launch's ncol for both
 };
 
 // affine epilogue of the Gram launch: out = w * (ns * acc - hd[row]) as a complex product per chain
@@ -105,15 +113,33 @@ struct ShtTables {
   int L = 0, spin = 0, Rp = 0;
   bool paired = false;           // spin 0: only m >= 0 stored, -m served with sign (-1)^m
   int n_m = 0;                   // stored m count
-  double* d_tab[TAB_KINDS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t bytes[TAB_KINDS] = {0, 0, 0, 0, 0};
+  double* d_tab[TAB_KINDS] = {};
+  size_t bytes[TAB_KINDS] = {};
   std::vector<int64_t> m_off[TAB_KINDS];  // per stored-m offset (doubles) into d_tab[kind]
   std::vector<int> k_beg[TAB_KINDS];      // per stored-m contraction start (el->ring kinds) / first row tile*16 (ring->el)
+  // TAB_GRAM_SPLIT, orders stored as halves: the odd-degree half (m_off / k_beg above describe the even-degree half, in
+  // half-row units); odd_off < 0: the order is stored dense (m = 0, and the orders gram_order_splits turns down)
+  std::vector<int64_t> odd_off;
+  std::vector<int> odd_k_beg;
   int refs = 0;                           // plans holding this entry of the per-device cache
   int m_of(int i) const { return paired ? i : i - (L - 1); }
 };
 
-// builds (or returns cached) tables for (L, spin); kinds_mask selects which of the 4 to build.  The cache is
+// can the Gram matrix of these tables be stored split by degree parity (TAB_GRAM_SPLIT)?
+inline bool gram_can_split(const ShtTables& T) { return T.paired && T.Rp % 32 == 0; }
+// start-up and drain of a GEMM task, in contraction steps (the figure the XCD launch order balances with, tasklist.hip)
+constexpr int GEMM_TASK_FIXED_STEPS = 32;
+// first half-row of the parity-par half of order m, down to a tile: the first i with 2 i + par >= m
+inline int gram_half_k_beg(int m, int par) { return round_down((m - par + 1) / 2, 16); }
+// Is order m >= 1 cheaper as two halves than as one dense block?  Modelled work of a block of extent n from kb on: row
+// tiles x (contraction steps + the fixed cost of a task).  The halves win wherever they halve the block; they lose in
+// the last 16 orders (a one-tile block would become two) and where two tiles per half replace a 3 x 3 tile block.
+inline bool gram_order_splits(int Rp, int m) {
+  auto work = [](int n, int kb) { return (n - kb) / 16 * (n - kb + GEMM_TASK_FIXED_STEPS); };
+  return work(Rp / 2, gram_half_k_beg(m, 0)) + work(Rp / 2, gram_half_k_beg(m, 1)) < work(Rp, round_down(m, 16));
+}
+
+// builds (or returns cached) tables for (L, spin); kinds_mask selects which kinds to build.  The cache is
 // per device and shared by plans: a plan retains every entry it uses once and releases it at teardown;
 // tables_trim() frees the entries nobody holds (pxm_tables_trim).
 int get_tables(int L, int spin, unsigned kinds_mask, ShtTables** out);

@@ -84,7 +84,10 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
   const GemmTask t = tasks[bid];
   const int tid = threadIdx.x, lane = tid & 63;
   if (t.n_rt == 0) return;  // padding entry of the XCD-queue order (tasklist.hip: order_tasks)
-  const int xn = PK ? t.x_ncol : ncol, yn = PK ? t.y_ncol : ncol;  // doubles per operand / result row
+  // doubles per operand / result row: the task's own in the packed and the two-operand variants (narrow arrays; the parity
+  // halves of the split Gram list walk a plane two rows at a time), the launch's in the streaming variants (HOIST below:
+  // their register budget is tight)
+  const int xn = (PK || TWO) ? t.x_ncol : ncol, yn = (PK || TWO) ? t.y_ncol : ncol;
 #ifdef PXM_GEMM_TRACE
   const unsigned long long trace_t0 = wall_clock64();
   unsigned long long trace_t1 = 0, trace_t2 = 0;
@@ -295,7 +298,7 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
       const int slab = c / CT, cin = 16 * (c % CT), grp = slab >> 1;
       const double sgn = (slab & 1) ? t.sign1 : 1.0;
       const int rowb = t.row0 + 16 * (RT * wave + r) + kq;
-      double* yb = Y + t.y_off[slab] + col0 + cin + cl + (int64_t)rowb * ncol;
+      double* yb = Y + t.y_off[slab] + col0 + cin + cl + (int64_t)rowb * yn;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int row = rowb + 4 * q;
@@ -309,7 +312,7 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
           v = (cl & 1) ? (aff.wr * u + aff.wi * pu) : (aff.wr * u - aff.wi * pu);
           if (col0 + cin + cl >= aff.ncol_live) v = 0.0;  // padding chains stay at zero (they have no prox / damping)
         }
-        if (row >= t.row_lo[grp] && row < t.row_hi[grp]) yb[(int64_t)(4 * q) * ncol] = sgn * rsv[r][grp][q] * v;
+        if (row >= t.row_lo[grp] && row < t.row_hi[grp]) yb[(int64_t)(4 * q) * yn] = sgn * rsv[r][grp][q] * v;
       }
     }
   }
@@ -440,8 +443,10 @@ int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags,
     for (int col0 = 0; col0 < ncol; col0 += 32) {
       const int CT = (ncol - col0 >= 32) ? 2 : 1;
       for (int slab = 0; slab < nslab; ++slab) {
-        // operand staging: X + x_off[slab] + col0 + cin + (k_beg + kr + cs KC) ncol, cin < 16 CT, kr < KC, cs <= nch - 1
-        const int xn = t.x_ncol ? t.x_ncol : ncol, yn = t.y_ncol ? t.y_ncol : ncol;
+        // operand staging: X + x_off[slab] + col0 + cin + (k_beg + kr + cs KC) xn, cin < 16 CT, kr < KC, cs <= nch - 1
+        // (xn, yn: the task's own row pitch in the packed and two-operand kernels, the launch's ncol in the streaming
+        // ones -- upload_tasks holds the tasks of a streaming list to the launch's ncol)
+        const int xn = ((TWO || nslab == 4) && t.x_ncol) ? t.x_ncol : ncol, yn = ((TWO || nslab == 4) && t.y_ncol) ? t.y_ncol : ncol;
         const int wx = std::min(16 * CT, xn), wy = std::min(16 * CT, yn);  // (a narrow array has fewer than 16 columns per row)
         const int64_t lo = col0 + (int64_t)t.k_beg * xn, hi = col0 + wx - 1 + (int64_t)(t.k_end - 1) * xn;
         if (!ok(t.x_off[slab] + lo, t.x_off[slab] + hi)) return bad(ti, "operand staging", col0);
@@ -456,7 +461,7 @@ int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags,
           return bad(ti, "affine data term", col0);
         if (t.rs_off[slab >> 1] && !ok(t.rs_off[slab >> 1] + r_lo, t.rs_off[slab >> 1] + r_hi))
           return bad(ti, "per-row output scale", col0);
-        // stores: Y + y_off[slab] + col0 + cin + cl + row ncol for the owned rows inside [row_lo, row_hi)
+        // stores: Y + y_off[slab] + col0 + cin + cl + row yn for the owned rows inside [row_lo, row_hi)
         const int64_t s_lo = std::max<int64_t>(r_lo, t.row_lo[slab >> 1]), s_hi = std::min<int64_t>(r_hi, (int64_t)t.row_hi[slab >> 1] - 1);
         if (s_lo <= s_hi && !ok(t.y_off[slab] + col0 + s_lo * yn, t.y_off[slab] + col0 + wy - 1 + s_hi * yn))
           return bad(ti, "result rows", col0);
@@ -574,40 +579,70 @@ static void fill_side(GemmTask& g, int grp, const ShtTables& T, int kind, int m,
   (void)kind;
 }
 
-static void append_tasks_impl(const ShtTables& T, int kind, int ncol, const GemmSide& side,
-                              int64_t scratch_off, const double* ws_base, std::vector<GemmTask>& tasks) {
+// The tasks of one table block of order m: `tab` its tiled table, kb its start along the el dimension(s), n the extent of
+// its row and contraction dimensions.  par < 0: the block spans the order (n = Rp).  par = 0 / 1: a parity half of the
+// split Gram table (n = Rp / 2) -- an ordinary task on a strided view of the H-layout arrays: a plane [Rp][ncol] of one
+// order is also [Rp / 2][2 ncol], half-row r holding degree 2 r in columns 0 .. ncol - 1 and degree 2 r + 1 in columns
+// ncol .. 2 ncol - 1, so the half of parity par has row pitch 2 ncol and starts par * ncol into the plane; rows,
+// contraction steps and the row mask of the task count half-rows.  (Sides with a support cut or a row mask of their own
+// have no such view: the Gram step has neither.)
+static void append_block_tasks(const ShtTables& T, int kind, int ncol, const GemmSide& side, int64_t scratch_off,
+                               const double* ws_base, std::vector<GemmTask>& tasks, int m, const double* tab, int kb, int n,
+                               int par) {
   // el_lo: harmonic degrees below it carry no signal for the transform (compact support of a wavelet kernel): the
   // rows (ring->el kinds) or contraction steps (el->ring kinds) below it are skipped.
   const bool rows_el = kind_rows_are_el(kind), k_el = kind_k_is_el(kind);
-  const int Rp = T.Rp;
-  const int el_lo = side.el_lo;
-  const int lo16 = round_down(std::max(el_lo, 0), 16);
+  const int lo16 = round_down(std::max(side.el_lo, 0), 16);
   const int rpt = gemm_rows_per_task(ncol);  // row tiles per task
+  const int start = std::max(kb, lo16);
+  if (start >= n) return;
+  // table of this block: [row tiles from (rows_el ? kb : 0)][k chunks of 8 from (k_el ? kb : 0)]
+  const int64_t rt_stride = (int64_t)((k_el ? n - kb : n) / 8) * 128;
+  const int k_beg = k_el ? start : 0, k_end = n, row_beg = rows_el ? start : 0;
+  const int64_t tab_skip = (rows_el ? (int64_t)((start - kb) / 16) * rt_stride : 0) + (k_el ? (int64_t)((start - kb) / 8) * 128 : 0);
+  const int n_rt_total = (n - row_beg) / 16;
+  for (int rt = 0; rt < n_rt_total; rt += rpt) {
+    GemmTask g;
+    g.m_unit = T.paired ? m : m + T.L - 1;
+    g.tab_off = (tab + tab_skip + (int64_t)rt * rt_stride) - ws_base;
+    g.rt_stride = rt_stride;
+    for (int s = 0; s < 2; ++s) fill_side(g, s, T, kind, m, ncol, side, scratch_off, ws_base);  // (slab groups 0 and 1 alike)
+    g.nslab = T.paired ? 2 : 1;
+    g.k_beg = k_beg;
+    g.k_end = k_end;
+    g.row0 = row_beg + 16 * rt;
+    g.n_rt = std::min(rpt, n_rt_total - rt);
+    g.sign1 = kind_is_gram(kind) ? 1.0 : ((m & 1) ? -1.0 : 1.0);  // the Gram table is even in m
+    g.x_ncol = side.x_ncol ? side.x_ncol : ncol;
+    g.y_ncol = side.y_ncol ? side.y_ncol : ncol;
+    if (par >= 0) {
+      for (int s = 0; s < 4; ++s) {
+        g.x_off[s] += par * g.x_ncol;
+        g.y_off[s] += par * g.y_ncol;
+        if (g.x2_off[s]) g.x2_off[s] += par * g.x_ncol;
+        if (g.hd_off[s]) g.hd_off[s] += par * g.hd_stride;
+      }
+      g.x_ncol *= 2;
+      g.y_ncol *= 2;
+      g.hd_stride *= 2;
+      // written rows: the degrees l >= round_down(m, 16) the dense list writes, no others (kb can start lower)
+      for (int grp = 0; grp < 2; ++grp) g.row_lo[grp] = round_down(m, 16) / 2;
+    }
+    tasks.push_back(g);
+  }
+}
+
+static void append_tasks_impl(const ShtTables& T, int kind, int ncol, const GemmSide& side,
+                              int64_t scratch_off, const double* ws_base, std::vector<GemmTask>& tasks) {
   for (int i = 0; i < T.n_m; ++i) {
     const int m = T.m_of(i);
+    const double* tab = T.d_tab[kind] + T.m_off[kind][i];
     const int kb = T.k_beg[kind][i];  // table start of this m along its el dimension(s): multiple of 16
-    const int start = std::max(kb, lo16);
-    if (start >= Rp) continue;
-    // table of this m: [row tiles from (rows_el ? kb : 0)][k chunks of 8 from (k_el ? kb : 0)]
-    const int64_t rt_stride = (int64_t)((k_el ? Rp - kb : Rp) / 8) * 128;
-    const int k_beg = k_el ? start : 0, k_end = Rp, row_beg = rows_el ? start : 0;
-    const int64_t tab_skip = (rows_el ? (int64_t)((start - kb) / 16) * rt_stride : 0) + (k_el ? (int64_t)((start - kb) / 8) * 128 : 0);
-    const int n_rt_total = (Rp - row_beg) / 16;
-    for (int rt = 0; rt < n_rt_total; rt += rpt) {
-      GemmTask g;
-      g.m_unit = T.paired ? m : m + T.L - 1;
-      g.tab_off = (T.d_tab[kind] + T.m_off[kind][i] + tab_skip + (int64_t)rt * rt_stride) - ws_base;
-      g.rt_stride = rt_stride;
-      for (int s = 0; s < 2; ++s) fill_side(g, s, T, kind, m, ncol, side, scratch_off, ws_base);  // (slab groups 0 and 1 alike)
-      g.nslab = T.paired ? 2 : 1;
-      g.k_beg = k_beg;
-      g.k_end = k_end;
-      g.row0 = row_beg + 16 * rt;
-      g.n_rt = std::min(rpt, n_rt_total - rt);
-      g.sign1 = (kind == TAB_GRAM) ? 1.0 : ((m & 1) ? -1.0 : 1.0);  // the Gram table is even in m
-      g.x_ncol = side.x_ncol ? side.x_ncol : ncol;
-      g.y_ncol = side.y_ncol ? side.y_ncol : ncol;
-      tasks.push_back(g);
+    if (kind == TAB_GRAM_SPLIT && T.odd_off[i] >= 0) {  // even-degree half, odd-degree half
+      append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, tab, kb, T.Rp / 2, 0);
+      append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, T.d_tab[kind] + T.odd_off[i], T.odd_k_beg[i], T.Rp / 2, 1);
+    } else {
+      append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, tab, kb, T.Rp, -1);
     }
   }
 }
@@ -670,15 +705,20 @@ __global__ void k_build_gram(const double* __restrict__ Bd, double* __restrict__
   Gd[(int64_t)i * Rp * Rp + (int64_t)r * Rp + c] = acc;
 }
 
-// tiled[(rt, kk2, lane, h)] = D[row][k] (transposed = 0) or D[k][row] (transposed = 1), D = dense Rp x Rp
-__global__ void k_tile_table(const double* __restrict__ D, double* __restrict__ out, int Rp, int row_beg,
-                             int k_beg, int transposed) {
-  const int nk2 = (Rp - k_beg) / 8;
+// tiled[(rt, kk2, lane, h)] = D[row][k] (transposed = 0) or D[k][row] (transposed = 1), D = dense Rp x Rp.
+// par >= 0: the tiled matrix is the n = Rp / 2 parity half of D, entry [row][k] = D[2 row + par][2 k + par]
+__global__ void k_tile_table(const double* __restrict__ D, double* __restrict__ out, int Rp, int n, int row_beg,
+                             int k_beg, int transposed, int par) {
+  const int nk2 = (n - k_beg) / 8;
   const int rt = blockIdx.y;
   const int kk2 = blockIdx.x;
   const int lane = threadIdx.x >> 1, h = threadIdx.x & 1;
-  const int row = row_beg + 16 * rt + (lane & 15);
-  const int k = k_beg + 8 * kk2 + 4 * h + (lane >> 4);
+  int row = row_beg + 16 * rt + (lane & 15);
+  int k = k_beg + 8 * kk2 + 4 * h + (lane >> 4);
+  if (par >= 0) {
+    row = 2 * row + par;
+    k = 2 * k + par;
+  }
   const double v = transposed ? D[(int64_t)k * Rp + row] : D[(int64_t)row * Rp + k];
   out[((int64_t)rt * nk2 + kk2) * 128 + threadIdx.x] = v;
 }
@@ -686,7 +726,54 @@ __global__ void k_tile_table(const double* __restrict__ D, double* __restrict__ 
 static std::mutex g_tab_mutex;
 static std::map<std::pair<int, int>, ShtTables*> g_tab_cache;
 
+// TAB_GRAM_SPLIT: order 0 dense, the orders m >= 1 as their even-degree and odd-degree halves where that is the cheaper
+// form (sht_core.h), gathered from the dense Gram matrices d_G: the kept entries are the doubles the dense table holds
+static int build_gram_split(ShtTables& T, const double* d_G) {
+  const int kind = TAB_GRAM_SPLIT, Rp = T.Rp, Rh = Rp / 2;
+  PXM_REQUIRE(gram_can_split(T), "build_gram_split: the parity split needs spin-0 tables and Rp % 32 == 0");
+  T.m_off[kind].assign(T.n_m, 0);
+  T.k_beg[kind].assign(T.n_m, 0);
+  T.odd_off.assign(T.n_m, -1);
+  T.odd_k_beg.assign(T.n_m, 0);
+  int64_t total = 0;
+  for (int m = 0; m < T.n_m; ++m) {
+    if (m == 0 || !gram_order_splits(Rp, m)) {  // dense block, as in TAB_GRAM
+      const int kb = round_down(m, 16);
+      T.k_beg[kind][m] = kb;
+      T.m_off[kind][m] = total;
+      total += (int64_t)((Rp - kb) / 16) * ((Rp - kb) / 8) * 128;
+      continue;
+    }
+    for (int par = 0; par < 2; ++par) {
+      const int kb = gram_half_k_beg(m, par);
+      (par ? T.odd_k_beg[m] : T.k_beg[kind][m]) = kb;
+      (par ? T.odd_off[m] : T.m_off[kind][m]) = total;
+      total += (int64_t)((Rh - kb) / 16) * ((Rh - kb) / 8) * 128;
+    }
+  }
+  T.bytes[kind] = (size_t)total * sizeof(double);
+  if (int rc = dev_alloc(&T.d_tab[kind], T.bytes[kind], "ring table")) return rc;
+  if (dry_run()) return 0;  // layout only: no GPU to tile the tables on
+  for (int m = 0; m < T.n_m; ++m) {
+    const double* src = d_G + (int64_t)m * Rp * Rp;
+    if (T.odd_off[m] < 0) {
+      const int kb = T.k_beg[kind][m];
+      hipLaunchKernelGGL(k_tile_table, dim3((Rp - kb) / 8, (Rp - kb) / 16), dim3(128), 0, 0, src, T.d_tab[kind] + T.m_off[kind][m],
+                         Rp, Rp, kb, kb, 0, -1);
+      continue;
+    }
+    for (int par = 0; par < 2; ++par) {
+      const int kb = par ? T.odd_k_beg[m] : T.k_beg[kind][m];
+      hipLaunchKernelGGL(k_tile_table, dim3((Rh - kb) / 8, (Rh - kb) / 16), dim3(128), 0, 0, src,
+                         T.d_tab[kind] + (par ? T.odd_off[m] : T.m_off[kind][m]), Rp, Rh, kb, kb, 0, par);
+    }
+  }
+  PXM_HIP(hipGetLastError());
+  return 0;
+}
+
 static int build_kind(ShtTables& T, int kind, const double* d_B, const double* d_A, const double* d_G) {
+  if (kind == TAB_GRAM_SPLIT) return build_gram_split(T, d_G);
   const int Rp = T.Rp;
   const bool rows_el = kind_rows_are_el(kind), k_el = kind_k_is_el(kind);
   T.m_off[kind].resize(T.n_m);
@@ -716,8 +803,8 @@ static int build_kind(ShtTables& T, int kind, const double* d_B, const double* d
     const int row_beg = rows_el ? kb : 0, k_beg = k_el ? kb : 0;
     dim3 grid((Rp - k_beg) / 8, (Rp - row_beg) / 16), block(128);
     if (grid.x == 0 || grid.y == 0) continue;
-    hipLaunchKernelGGL(k_tile_table, grid, block, 0, 0, src, T.d_tab[kind] + T.m_off[kind][i], Rp, row_beg, k_beg,
-                       transposed);
+    hipLaunchKernelGGL(k_tile_table, grid, block, 0, 0, src, T.d_tab[kind] + T.m_off[kind][i], Rp, Rp, row_beg, k_beg,
+                       transposed, -1);
   }
   PXM_HIP(hipGetLastError());
   return 0;
@@ -774,7 +861,7 @@ int get_tables(int L, int spin, unsigned kinds_mask, ShtTables** out) {
       hipLaunchKernelGGL(k_build_fwd, grid, block, 0, 0, d_B, d_Q, d_A, Rp, L, 2.0 * M_PI / (2 * L - 1), m0, spin);
       PXM_HIP(hipGetLastError());
     }
-    if (missing & (1u << TAB_GRAM)) {
+    if (missing & ((1u << TAB_GRAM) | (1u << TAB_GRAM_SPLIT))) {
       PXM_HIP(hipMalloc(&d_G, dense * sizeof(double)));
       dim3 grid(Rp / 16, Rp / 16, T->n_m), block(16, 16);
       hipLaunchKernelGGL(k_build_gram, grid, block, 0, 0, d_B, d_G, Rp, L);

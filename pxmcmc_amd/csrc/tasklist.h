@@ -13,7 +13,8 @@ struct TaskList {
   std::vector<int> los;  // their support cuts el_lo (0 = none)
   double mfma_units = 0; // sum over tasks of row tiles x k-steps x slabs: MFMAs per column tile
   bool gram = false;     // Gram launch: the stored Gram tiles, TWO harmonic operand arrays read, one written, the data term
-  double gram_table_bytes = 0;  // bytes of the Gram table as stored (16-row / 16-k tiles from round_down(m, 16))
+  double gram_table_bytes = 0;  // bytes of the Gram table as stored (dense: 16-row / 16-k tiles from round_down(m, 16); or
+                                // the parity-split table of sht_core.h)
   int flags = 0;         // bit 0: tasks sum a second operand in while staging; bit 1: per-row operand scale (kernel variant)
   int pk = 0;            // packed column tile (few-chain plans, sht_gemm.hip: k_sht_gemm_pk): live columns per slab, 0 = off
   std::vector<char> tab_shared;  // packed lists: transform i streams its table together with transform i - 1 (one pass)

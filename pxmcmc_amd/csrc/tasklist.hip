@@ -92,7 +92,7 @@ static void order_bins(std::vector<GemmTask>& v, int64_t fixed) {
 }
 
 void order_tasks(std::vector<GemmTask>& v, const std::string& order) {
-  const int64_t fixed = order == "xcd" ? 32 : 0;
+  const int64_t fixed = order == "xcd" ? GEMM_TASK_FIXED_STEPS : 0;
   std::stable_sort(v.begin(), v.end(), [&](const GemmTask& a, const GemmTask& b) { return task_work(a, fixed) > task_work(b, fixed); });
   if (order == "xcd" && !v.empty()) order_xcd(v, fixed);
   else if (order == "bins" && (int)v.size() > 256) order_bins(v, fixed);  // (any other word, e.g. plain: descending)
@@ -121,6 +121,10 @@ int upload_tasks(std::vector<GemmTask> v, bool paired, TaskList* out, std::vecto
       if (t.x2_off[sl]) out->flags |= 1;
     if (t.ks_off[0] || t.ks_off[1]) out->flags |= 2;
   }
+  // only the packed and the two-operand kernels take a task's own row pitch (sht_gemm.hip: xn / yn)
+  if (!pk && !(out->flags & 1))
+    for (const GemmTask& t : v)
+      PXM_REQUIRE(t.n_rt == 0 || (t.x_ncol == ncol && t.y_ncol == ncol), "upload_tasks: a streaming list with a row pitch of its own");
   if (v.empty()) return 0;
   // address ranges of every load / store the launches of this list can form (sht_gemm.hip: check_gemm_task_ranges)
   if (int rc = check_gemm_task_ranges(v, out->nslab, out->flags, ncol, ws_base, name)) return rc;

@@ -238,17 +238,21 @@ static int wav_plan_create_impl(const char* who, int L, double B, int J_min, int
 int pxm::wav_make_gram_lists(pxm_wav_plan_s* p) {
   if (p->gram.d) return 0;
   int rc;
-  if ((rc = get_tables(p->L, p->spin, 1u << TAB_GRAM, &p->TL))) return rc;
+  // spin 0 and Rp % 32 == 0: the Gram table without its structurally zero half (sht_core.h: TAB_GRAM_SPLIT);
+  // PXM_GRAM_SPLIT=0 keeps the dense list (the cross-check and the A/B switch)
+  const char* split_env = getenv("PXM_GRAM_SPLIT");
+  const int kind = (gram_can_split(*p->TL) && !(split_env && atoi(split_env) == 0)) ? TAB_GRAM_SPLIT : TAB_GRAM;
+  if ((rc = get_tables(p->L, p->spin, 1u << kind, &p->TL))) return rc;
   wav_hold(p, p->TL);
   std::vector<GemmTask> v;
   GemmFuse fz;
   fz.x2_base = p->offHB;
   fz.hd_base = p->offHDc;
   fz.hd_stride = 2;
-  append_gemm_tasks(*p->TL, TAB_GRAM, p->ncol, p->offHA, p->L, p->Rp, p->offHL, p->L, p->Rp, nullptr, p->offS, p->ws, v, 0, fz);
+  append_gemm_tasks(*p->TL, kind, p->ncol, p->offHA, p->L, p->Rp, p->offHL, p->L, p->Rp, nullptr, p->offS, p->ws, v, 0, fz);
   if ((rc = upload_tasks(v, p->TL->paired, &p->gram, {p->L}, p->ncol, p->ws, "Gram step"))) return rc;
   p->gram.gram = true;
-  p->gram.gram_table_bytes = (double)p->TL->bytes[TAB_GRAM];
+  p->gram.gram_table_bytes = (double)p->TL->bytes[kind];
   return wav_level_list(p, TAB_INV_ADJ, p->offGD, p->offHD, GemmFuse(), &p->adj_invadj_D, "inverse-adjoint of the data rings");
 }
 
@@ -410,6 +414,24 @@ int64_t pxm_host_check_address_ranges(int L, double B, int J_min, int spin, int 
   tables_trim();  // the dry-run table entries (fake addresses) never outlive the call
   set_dry_run(false);
   return rc ? -1 : ranges_checked();
+}
+
+// Bytes of the Gram table the ring-space step of a wavelet plan (L, B, J_min) at `spin` streams per launch, as stored: the
+// parity-split table where it applies (spin 0, Rp % 32 == 0, PXM_GRAM_SPLIT not 0), the dense one otherwise.  Host-only: a
+// dry-run plan like the one above.
+int64_t pxm_host_gram_table_bytes(int L, double B, int J_min, int spin, int max_chains) {
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  PXM_REQUIRE(!capture_in_progress(), "pxm_host_gram_table_bytes: not during a stream capture");
+  set_dry_run(true);
+  pxm_wav_plan_t wp = nullptr;
+  int rc = pxm_wav_plan_create_spin(L, B, J_min, spin, max_chains, 0, &wp);
+  if (!rc) rc = wav_make_gram_lists(wp);
+  const int64_t bytes = rc ? -1 : (int64_t)wp->gram.gram_table_bytes;
+  if (wp) pxm_wav_plan_destroy(wp);
+  tables_trim();
+  set_dry_run(false);
+  return bytes;
 }
 
 }  // extern "C"
