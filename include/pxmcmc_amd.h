@@ -61,9 +61,10 @@ int pxm_noise_bits(void);
  * The same check runs at every real plan creation.  The dry-run switch is per thread (plans created concurrently on
  * other threads are real); not to be called during a stream capture. */
 int64_t pxm_host_check_address_ranges(int L, double B, int J_min, int spin, int max_chains, int what);
-/* Host-only: bytes of the Gram table, as stored, that the ring-space step of the wavelet plan (L, B, J_min) at `spin`
- * streams per launch -- the parity-split table for spin 0 and roundup(L, 16) % 32 == 0 unless PXM_GRAM_SPLIT=0 (read
- * when a plan's Gram lists are made), the dense one otherwise; < 0 on error. */
+/* Host-only: bytes of the Gram table, as stored, of the ring-space step of the wavelet plan (L, B, J_min) at `spin` -- the
+ * parity-split table for spin 0 and roundup(L, 16) % 32 == 0 unless PXM_GRAM_SPLIT=0 (read when a plan's Gram lists are
+ * made), the dense one otherwise; < 0 on error.  (Order 0 takes Rp^2 doubles in either split form; with its two halves --
+ * the default, PXM_GRAM_SPLIT=1 keeps it dense -- the launch streams the two diagonal blocks of them.) */
 int64_t pxm_host_gram_table_bytes(int L, double B, int J_min, int spin, int max_chains);
 const char* pxm_last_error(void);
 /* number of visible HIP devices (0 when none; never fails) */

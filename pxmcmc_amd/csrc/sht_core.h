@@ -26,9 +26,14 @@ namespace pxm {
 // from kb_p = round_down(ceil((m - p) / 2), 16).  m = 0 has a real odd-parity part (the pole ring) and stays dense.
 // An order stays one dense block where the two halves would not be cheaper (gram_order_splits below): the halves cannot
 // go below one 16 x 16 tile, and each is a workgroup with a start-up and a drain of its own.
-enum TableKind { TAB_INV = 0, TAB_FWD = 1, TAB_INV_ADJ = 2, TAB_FWD_ADJ = 3, TAB_GRAM = 4, TAB_GRAM_SPLIT = 5, TAB_KINDS = 6 };
+// TAB_GRAM_SPLIT0: TAB_GRAM_SPLIT with order 0 split as well.  The odd-parity part of G^0 is the pole ring alone and has
+// rank one: G^0[l][l'] = 1/2 b_l b_l' for l + l' odd, b_l = B^0[theta = pi][l].  Order 0 is stored as
+// the parity-permuted matrix [[ee, eo], [oe, oo]] (Rp^2 doubles, as before); its two half tasks stream the diagonal blocks
+// and add 1/2 b_row (b_other . x_other) in their epilogue (GemmTask::pole_n), the off-diagonal blocks are never read.
+enum TableKind { TAB_INV = 0, TAB_FWD = 1, TAB_INV_ADJ = 2, TAB_FWD_ADJ = 3, TAB_GRAM = 4, TAB_GRAM_SPLIT = 5, TAB_GRAM_SPLIT0 = 6, TAB_KINDS = 7 };
 inline bool kind_el_to_ring(int kind) { return kind == TAB_INV || kind == TAB_FWD_ADJ; }
-inline bool kind_is_gram(int kind) { return kind == TAB_GRAM || kind == TAB_GRAM_SPLIT; }
+inline bool kind_is_gram_split(int kind) { return kind == TAB_GRAM_SPLIT || kind == TAB_GRAM_SPLIT0; }
+inline bool kind_is_gram(int kind) { return kind == TAB_GRAM || kind_is_gram_split(kind); }
 inline bool kind_rows_are_el(int kind) { return kind == TAB_FWD || kind == TAB_INV_ADJ || kind_is_gram(kind); }
 inline bool kind_k_is_el(int kind) { return kind == TAB_INV || kind == TAB_FWD_ADJ || kind_is_gram(kind); }
 
@@ -60,6 +65,13 @@ struct GemmTask {
                        // array of a few-chain plan has 2 C or 4 columns per row instead of the plan's 16) and by the
                        // two-operand kernels (the parity halves of the split Gram list step through an H-layout plane two
                        // rows at a time: 2 ncol); the streaming 16-columns-per-slab kernels take the launch's ncol for both
+  // pole term of the order-0 halves of the split Gram list (TAB_GRAM_SPLIT0), pole_n = 0: none.  The task adds
+  // 1/2 b_own[row] * s[col] to its products, s[col] = sum over the pole_n half-rows r of the OTHER parity of
+  // b_other[r] * x[r][col], x being the staged operand (both class buffers) pole_dx doubles away from the task's own
+  int pole_n;          // half-rows of the other parity (Rp / 2)
+  int pole_dx;         // doubles from this half's operand to the other parity's: + ncol (even half) or - ncol (odd half)
+  int64_t pole_b_off;  // b of this half's degrees, indexed by half-row (relative to the workspace base, like tab_off)
+  int64_t pole_bo_off; // b of the other parity's degrees
 };
 
 // affine epilogue of the Gram launch: out = w * (ns * acc - hd[row]) as a complex product per chain
@@ -121,11 +133,13 @@ struct ShtTables {
   // half-row units); odd_off < 0: the order is stored dense (m = 0, and the orders gram_order_splits turns down)
   std::vector<int64_t> odd_off;
   std::vector<int> odd_k_beg;
+  // TAB_GRAM_SPLIT0: b_l = B^0[theta = pi][l] by parity, [Rp / 2 even degrees | Rp / 2 odd degrees], zero for l >= L
+  double* d_pole = nullptr;
   int refs = 0;                           // plans holding this entry of the per-device cache
   int m_of(int i) const { return paired ? i : i - (L - 1); }
 };
 
-// can the Gram matrix of these tables be stored split by degree parity (TAB_GRAM_SPLIT)?
+// can the Gram matrix of these tables be stored split by degree parity (TAB_GRAM_SPLIT, TAB_GRAM_SPLIT0)?
 inline bool gram_can_split(const ShtTables& T) { return T.paired && T.Rp % 32 == 0; }
 // start-up and drain of a GEMM task, in contraction steps (the figure the XCD launch order balances with, tasklist.hip)
 constexpr int GEMM_TASK_FIXED_STEPS = 32;

@@ -64,7 +64,9 @@ struct GemmGeom {
 // for up to two transforms (the two L-band-limited wavelet scales).  With one chain the unpacked launch spends two MFMA
 // column tiles per table fragment on 4 live columns and streams the 512-table once per scale; packed, one tile carries the
 // 8 live columns of both scales: half the table bytes and a quarter of the MFMAs.  Instantiated with CT = NSLAB = 1.
-template <int CT, int NSLAB, int NW, int RT, int NSET, bool TWO, bool SK, int PK = 0>
+// POLE: the launch has tasks with a pole term (GemmTask::pole_n, the order-0 halves of the split Gram list).  A variant of
+// its own, so that every other launch runs the code it ran before.
+template <int CT, int NSLAB, int NW, int RT, int NSET, bool TWO, bool SK, int PK = 0, bool POLE = false>
 __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks, const int bid,
                                               const double* __restrict__ X, double* __restrict__ Y, int ncol, int col0,
                                               const GemmAffine& aff, double (*xs)[KC][GemmGeom<CT, NSLAB>::PITCH]) {
@@ -270,6 +272,58 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
 #pragma unroll
       for (int q = 0; q < 4; ++q) rsv[r][g][q] = t.rs_off[g] ? (X + t.rs_off[g])[rowb + 4 * q] : 1.0;
   }
+  if constexpr (POLE) {
+    // Pole term of an order-0 half (task-uniform branch): acc[row][col] += 1/2 b_own[row] * s[col] with
+    // s[col] = sum_r b_other[r] * x_other[r][col] over the half-rows of the other parity.  Both slabs of order 0 stage
+    // the same operand, so s is formed once for the 16 CT columns of slab 0.  Fixed summation order: thread (row
+    // group rg, column pair cp) sums rows rg, rg + NRG, ...; a butterfly over the row groups of a wave; the eight
+    // waves through LDS in wave order.  The loads are issued with the epilogue operands above and share their latency.
+    if (t.pole_n) {
+      constexpr int W2 = 8 * CT;    // column pairs of one slab
+      constexpr int NRG = NT / W2;  // row groups of the workgroup
+      const int cp = tid % W2, rg = tid / W2;
+      const double* xo = X + t.x_off[0] + t.pole_dx + col0 + 2 * cp;
+      const double* xo2 = two ? X + t.x2_off[0] + t.pole_dx + col0 + 2 * cp : xo;
+      const double* bo = X + t.pole_bo_off;
+      double bown[RT][4];
+#pragma unroll
+      for (int r = 0; r < RT; ++r)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          bown[r][q] = (X + t.pole_b_off)[t.row0 + 16 * (r < n_my ? RT * wave + r : 0) + kq + 4 * q];
+      double2 part{0.0, 0.0};
+#pragma unroll 1  // (two rows per thread at L = 256; unrolled by two the variant takes 98 VGPRs instead of 78 and a CU holds two workgroups, not three)
+      for (int r = rg; r < t.pole_n; r += NRG) {
+        const double2 a = *reinterpret_cast<const double2*>(xo + (int64_t)r * xn);
+        const double2 a2 = *reinterpret_cast<const double2*>(xo2 + (int64_t)r * xn);
+        const double bv = bo[r];
+        const double2 v = stage_add(a, a2, two);
+        part.x += bv * v.x;
+        part.y += bv * v.y;
+      }
+#pragma unroll
+      for (int msk = W2; msk < 64; msk <<= 1) {
+        part.x += __shfl_xor(part.x, msk);
+        part.y += __shfl_xor(part.y, msk);
+      }
+      double* red = &xs[0][0][0];  // [NW][2 W2], over the operand buffers: nobody may still be reading the last chunk
+      __syncthreads();
+      if (lane < W2) *reinterpret_cast<double2*>(red + wave * 2 * W2 + 2 * lane) = part;
+      __syncthreads();
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        double sc = 0.0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) sc += red[w * 2 * W2 + 16 * ct + cl];
+#pragma unroll
+        for (int r = 0; r < RT; ++r)
+#pragma unroll
+          for (int sl = 0; sl < NSLAB; ++sl)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[r][sl * CT + ct][q] += 0.5 * bown[r][q] * sc;
+      }
+    }
+  }
   if constexpr (PK != 0) {
     // packed tile: this lane's column cl belongs to slab cl / PK (dead beyond the task's slabs), column cl % PK of its array
     const int slab = cl / PK, grp = slab >> 1;
@@ -338,13 +392,14 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
 #endif
 }
 
-template <int CT, int NSLAB, int NW, int RT, int NSET, bool TWO, bool SK>
+template <int CT, int NSLAB, int NW, int RT, int NSET, bool TWO, bool SK, bool POLE = false>
 __global__ __launch_bounds__(64 * NW) void k_sht_gemm(const GemmTask* __restrict__ tasks,
                                                       const double* __restrict__ X, double* __restrict__ Y,
                                                       int ncol, int col0, GemmAffine aff) {
   __shared__ double xs[2][KC][GemmGeom<CT, NSLAB>::PITCH];
+  static_assert(!POLE || 2 * KC * GemmGeom<CT, NSLAB>::PITCH >= NW * 16 * CT, "the pole reduction borrows the operand buffers");
   if (aff.bump && blockIdx.x == 0 && threadIdx.x == 0) *aff.bump += 1;  // Philox iteration counter of the ring-space step
-  sht_gemm_body<CT, NSLAB, NW, RT, NSET, TWO, SK>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs);
+  sht_gemm_body<CT, NSLAB, NW, RT, NSET, TWO, SK, 0, POLE>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs);
 }
 // packed column tile (few-chain plans): PK live columns per slab, up to 16 / PK slabs in the one tile
 template <int PK, int NW, int RT, int NSET, bool TWO, bool SK>
@@ -440,6 +495,16 @@ int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags,
     // lane < 64, two doubles each
     if (!ok(t.tab_off, t.tab_off + (int64_t)(t.n_rt - 1) * t.rt_stride + (int64_t)(2 * (nch - 1) + 1) * 128 + 127))
       return bad(ti, "ring-table stream", 0);
+    for (int col0 = 0; col0 < ncol && t.pole_n; col0 += 32) {
+      // pole term: b of the task's own rows (as the per-row scale: tiles 0 .. n_rt - 1), b of the other parity's pole_n
+      // half-rows, and the 16 CT columns of slab 0 of the other parity's operand(s), rows 0 .. pole_n - 1 at the task's pitch
+      const int CT = (ncol - col0 >= 32) ? 2 : 1;
+      if (!ok(t.pole_b_off + t.row0, t.pole_b_off + t.row0 + 16 * t.n_rt - 1)) return bad(ti, "pole column of the task's rows", col0);
+      if (!ok(t.pole_bo_off, t.pole_bo_off + t.pole_n - 1)) return bad(ti, "pole column of the other parity", col0);
+      const int64_t lo = t.pole_dx + col0, hi = t.pole_dx + col0 + 16 * CT - 1 + (int64_t)(t.pole_n - 1) * t.x_ncol;
+      if (!ok(t.x_off[0] + lo, t.x_off[0] + hi)) return bad(ti, "pole term operand", col0);
+      if (t.x2_off[0] && !ok(t.x2_off[0] + lo, t.x2_off[0] + hi)) return bad(ti, "pole term second operand", col0);
+    }
     for (int col0 = 0; col0 < ncol; col0 += 32) {
       const int CT = (ncol - col0 >= 32) ? 2 : 1;
       for (int slab = 0; slab < nslab; ++slab) {
@@ -479,7 +544,8 @@ int gemm_rows_per_task(int ncol) {
   return 8;
 }
 
-// flags: bit 0 = the list's tasks carry a second operand, bit 1 = a per-contraction-row operand scale
+// flags: bit 0 = the list's tasks carry a second operand, bit 1 = a per-contraction-row operand scale, bit 2 = a pole term
+// (the split Gram list with its order-0 halves: two operands, no scale, +-m pairs)
 int launch_gemm(const GemmTask* d_tasks, int n_tasks, int nslab, int flags, const double* X, double* Y, int ncol,
                 int col0, int ct, double alg_bytes, double flops, hipStream_t stream, const GemmAffine& aff, Profiler* prof) {
   if (n_tasks == 0) return 0;
@@ -500,7 +566,11 @@ int launch_gemm(const GemmTask* d_tasks, int n_tasks, int nslab, int flags, cons
     case 2: PXM_GEMM_L4(CT_, NS_, false, true); break;          \
     default: PXM_GEMM_L4(CT_, NS_, true, true); break;          \
   }
-  if (nslab == 2) {
+  if (flags & 4) {
+    PXM_REQUIRE(nslab == 2 && (flags & 3) == 1, "launch_gemm: a pole term outside the Gram list");
+    if (ct == 1) hipExtLaunchKernelGGL((k_sht_gemm<1, 2, 8, 1, 2, true, false, true>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff);
+    else hipExtLaunchKernelGGL((k_sht_gemm<2, 2, 8, 1, 2, true, false, true>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff);
+  } else if (nslab == 2) {
     if (ct == 1) { PXM_GEMM_L3(1, 2) } else { PXM_GEMM_L3(2, 2) }
   } else {
     if (ct == 1) { PXM_GEMM_L3(1, 1) } else { PXM_GEMM_L3(2, 1) }
@@ -588,7 +658,7 @@ static void fill_side(GemmTask& g, int grp, const ShtTables& T, int kind, int m,
 // have no such view: the Gram step has neither.)
 static void append_block_tasks(const ShtTables& T, int kind, int ncol, const GemmSide& side, int64_t scratch_off,
                                const double* ws_base, std::vector<GemmTask>& tasks, int m, const double* tab, int kb, int n,
-                               int par) {
+                               int par, int64_t rt_stride_stored = 0, const double* pole = nullptr) {
   // el_lo: harmonic degrees below it carry no signal for the transform (compact support of a wavelet kernel): the
   // rows (ring->el kinds) or contraction steps (el->ring kinds) below it are skipped.
   const bool rows_el = kind_rows_are_el(kind), k_el = kind_k_is_el(kind);
@@ -597,7 +667,8 @@ static void append_block_tasks(const ShtTables& T, int kind, int ncol, const Gem
   const int start = std::max(kb, lo16);
   if (start >= n) return;
   // table of this block: [row tiles from (rows_el ? kb : 0)][k chunks of 8 from (k_el ? kb : 0)]
-  const int64_t rt_stride = (int64_t)((k_el ? n - kb : n) / 8) * 128;
+  // (rt_stride_stored: the block is part of a wider stored matrix -- a diagonal block of the permuted order-0 table)
+  const int64_t rt_stride = rt_stride_stored ? rt_stride_stored : (int64_t)((k_el ? n - kb : n) / 8) * 128;
   const int k_beg = k_el ? start : 0, k_end = n, row_beg = rows_el ? start : 0;
   const int64_t tab_skip = (rows_el ? (int64_t)((start - kb) / 16) * rt_stride : 0) + (k_el ? (int64_t)((start - kb) / 8) * 128 : 0);
   const int n_rt_total = (n - row_beg) / 16;
@@ -615,6 +686,14 @@ static void append_block_tasks(const ShtTables& T, int kind, int ncol, const Gem
     g.sign1 = kind_is_gram(kind) ? 1.0 : ((m & 1) ? -1.0 : 1.0);  // the Gram table is even in m
     g.x_ncol = side.x_ncol ? side.x_ncol : ncol;
     g.y_ncol = side.y_ncol ? side.y_ncol : ncol;
+    g.pole_n = g.pole_dx = 0;
+    g.pole_b_off = g.pole_bo_off = 0;
+    if (pole) {  // order-0 half: pole = [n even degrees | n odd degrees] of b
+      g.pole_n = n;
+      g.pole_dx = par ? -g.x_ncol : g.x_ncol;
+      g.pole_b_off = (pole + par * n) - ws_base;
+      g.pole_bo_off = (pole + (1 - par) * n) - ws_base;
+    }
     if (par >= 0) {
       for (int s = 0; s < 4; ++s) {
         g.x_off[s] += par * g.x_ncol;
@@ -638,7 +717,12 @@ static void append_tasks_impl(const ShtTables& T, int kind, int ncol, const Gemm
     const int m = T.m_of(i);
     const double* tab = T.d_tab[kind] + T.m_off[kind][i];
     const int kb = T.k_beg[kind][i];  // table start of this m along its el dimension(s): multiple of 16
-    if (kind == TAB_GRAM_SPLIT && T.odd_off[i] >= 0) {  // even-degree half, odd-degree half
+    if (kind == TAB_GRAM_SPLIT0 && m == 0) {  // the diagonal blocks of [[ee, eo], [oe, oo]], each with its pole term
+      const int Rh = T.Rp / 2;
+      const int64_t rs = (int64_t)(T.Rp / 8) * 128;
+      append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, tab, 0, Rh, 0, rs, T.d_pole);
+      append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, tab + (Rh / 16) * rs + (int64_t)(Rh / 8) * 128, 0, Rh, 1, rs, T.d_pole);
+    } else if (kind_is_gram_split(kind) && T.odd_off[i] >= 0) {  // even-degree half, odd-degree half
       append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, tab, kb, T.Rp / 2, 0);
       append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, T.d_tab[kind] + T.odd_off[i], T.odd_k_beg[i], T.Rp / 2, 1);
     } else {
@@ -706,7 +790,8 @@ __global__ void k_build_gram(const double* __restrict__ Bd, double* __restrict__
 }
 
 // tiled[(rt, kk2, lane, h)] = D[row][k] (transposed = 0) or D[k][row] (transposed = 1), D = dense Rp x Rp.
-// par >= 0: the tiled matrix is the n = Rp / 2 parity half of D, entry [row][k] = D[2 row + par][2 k + par]
+// par = 0 / 1: the tiled matrix is the n = Rp / 2 parity half of D, entry [row][k] = D[2 row + par][2 k + par]
+// par = 2: the whole of D with rows and columns permuted by parity, even degrees first: [[ee, eo], [oe, oo]]
 __global__ void k_tile_table(const double* __restrict__ D, double* __restrict__ out, int Rp, int n, int row_beg,
                              int k_beg, int transposed, int par) {
   const int nk2 = (n - k_beg) / 8;
@@ -715,7 +800,10 @@ __global__ void k_tile_table(const double* __restrict__ D, double* __restrict__ 
   const int lane = threadIdx.x >> 1, h = threadIdx.x & 1;
   int row = row_beg + 16 * rt + (lane & 15);
   int k = k_beg + 8 * kk2 + 4 * h + (lane >> 4);
-  if (par >= 0) {
+  if (par == 2) {
+    row = row < n / 2 ? 2 * row : 2 * (row - n / 2) + 1;
+    k = k < n / 2 ? 2 * k : 2 * (k - n / 2) + 1;
+  } else if (par >= 0) {
     row = 2 * row + par;
     k = 2 * k + par;
   }
@@ -727,9 +815,10 @@ static std::mutex g_tab_mutex;
 static std::map<std::pair<int, int>, ShtTables*> g_tab_cache;
 
 // TAB_GRAM_SPLIT: order 0 dense, the orders m >= 1 as their even-degree and odd-degree halves where that is the cheaper
-// form (sht_core.h), gathered from the dense Gram matrices d_G: the kept entries are the doubles the dense table holds
-static int build_gram_split(ShtTables& T, const double* d_G) {
-  const int kind = TAB_GRAM_SPLIT, Rp = T.Rp, Rh = Rp / 2;
+// form (sht_core.h), gathered from the dense Gram matrices d_G: the kept entries are the doubles the dense table holds.
+// TAB_GRAM_SPLIT0: the same with order 0 permuted by parity (the same Rp^2 doubles in the same space) and the pole column b
+static int build_gram_split(ShtTables& T, int kind, const double* d_G) {
+  const int Rp = T.Rp, Rh = Rp / 2;
   PXM_REQUIRE(gram_can_split(T), "build_gram_split: the parity split needs spin-0 tables and Rp % 32 == 0");
   T.m_off[kind].assign(T.n_m, 0);
   T.k_beg[kind].assign(T.n_m, 0);
@@ -753,13 +842,22 @@ static int build_gram_split(ShtTables& T, const double* d_G) {
   }
   T.bytes[kind] = (size_t)total * sizeof(double);
   if (int rc = dev_alloc(&T.d_tab[kind], T.bytes[kind], "ring table")) return rc;
+  if (kind == TAB_GRAM_SPLIT0 && !T.d_pole) {
+    if (int rc = dev_alloc(&T.d_pole, (size_t)Rp * sizeof(double), "pole column of the order-0 Gram block")) return rc;
+    if (!dry_run()) {
+      std::vector<double> B0((size_t)Rp * Rp, 0.0), b(Rp, 0.0);
+      wigner_ring_table(T.L, 0, 0, B0.data(), Rp);  // the last ring is theta = pi
+      for (int l = 0; l < T.L; ++l) b[(l & 1) * Rh + l / 2] = B0[(size_t)(T.L - 1) * Rp + l];
+      if (int rc = dev_upload(T.d_pole, b.data(), b.size() * sizeof(double))) return rc;
+    }
+  }
   if (dry_run()) return 0;  // layout only: no GPU to tile the tables on
   for (int m = 0; m < T.n_m; ++m) {
     const double* src = d_G + (int64_t)m * Rp * Rp;
     if (T.odd_off[m] < 0) {
       const int kb = T.k_beg[kind][m];
       hipLaunchKernelGGL(k_tile_table, dim3((Rp - kb) / 8, (Rp - kb) / 16), dim3(128), 0, 0, src, T.d_tab[kind] + T.m_off[kind][m],
-                         Rp, Rp, kb, kb, 0, -1);
+                         Rp, Rp, kb, kb, 0, (kind == TAB_GRAM_SPLIT0 && m == 0) ? 2 : -1);
       continue;
     }
     for (int par = 0; par < 2; ++par) {
@@ -773,7 +871,7 @@ static int build_gram_split(ShtTables& T, const double* d_G) {
 }
 
 static int build_kind(ShtTables& T, int kind, const double* d_B, const double* d_A, const double* d_G) {
-  if (kind == TAB_GRAM_SPLIT) return build_gram_split(T, d_G);
+  if (kind_is_gram_split(kind)) return build_gram_split(T, kind, d_G);
   const int Rp = T.Rp;
   const bool rows_el = kind_rows_are_el(kind), k_el = kind_k_is_el(kind);
   T.m_off[kind].resize(T.n_m);
@@ -861,7 +959,7 @@ int get_tables(int L, int spin, unsigned kinds_mask, ShtTables** out) {
       hipLaunchKernelGGL(k_build_fwd, grid, block, 0, 0, d_B, d_Q, d_A, Rp, L, 2.0 * M_PI / (2 * L - 1), m0, spin);
       PXM_HIP(hipGetLastError());
     }
-    if (missing & ((1u << TAB_GRAM) | (1u << TAB_GRAM_SPLIT))) {
+    if (missing & ((1u << TAB_GRAM) | (1u << TAB_GRAM_SPLIT) | (1u << TAB_GRAM_SPLIT0))) {
       PXM_HIP(hipMalloc(&d_G, dense * sizeof(double)));
       dim3 grid(Rp / 16, Rp / 16, T->n_m), block(16, 16);
       hipLaunchKernelGGL(k_build_gram, grid, block, 0, 0, d_B, d_G, Rp, L);
@@ -904,6 +1002,7 @@ int64_t tables_trim() {
       if (T->d_tab[k]) deferred_free(T->d_tab[k]);
       freed += (int64_t)T->bytes[k];
     }
+    if (T->d_pole) deferred_free(T->d_pole);
     delete T;
     it = g_tab_cache.erase(it);
   }

@@ -15,7 +15,10 @@ struct TaskList {
   bool gram = false;     // Gram launch: the stored Gram tiles, TWO harmonic operand arrays read, one written, the data term
   double gram_table_bytes = 0;  // bytes of the Gram table as stored (dense: 16-row / 16-k tiles from round_down(m, 16); or
                                 // the parity-split table of sht_core.h)
-  int flags = 0;         // bit 0: tasks sum a second operand in while staging; bit 1: per-row operand scale (kernel variant)
+  bool gram_pole = false;        // the list has the order-0 halves with their pole term (TAB_GRAM_SPLIT0) ...
+  double gram_stream_bytes = 0;  // ... and streams this much of the stored table (the off-diagonal blocks of order 0 are not read)
+  int flags = 0;         // bit 0: tasks sum a second operand in while staging; bit 1: per-row operand scale; bit 2: pole term
+                         // (kernel variant)
   int pk = 0;            // packed column tile (few-chain plans, sht_gemm.hip: k_sht_gemm_pk): live columns per slab, 0 = off
   std::vector<char> tab_shared;  // packed lists: transform i streams its table together with transform i - 1 (one pass)
 };

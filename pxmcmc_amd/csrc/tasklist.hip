@@ -91,8 +91,14 @@ static void order_bins(std::vector<GemmTask>& v, int64_t fixed) {
   v.swap(ordered);
 }
 
+// fixed cost the orders balance with, in contraction steps.  The per-CU bins ran on work alone (0) until the longest chain of
+// the Gram list was halved; with it the headline iteration is 1.3 - 2.5 us shorter (docs/EXPERIMENTS.md, Round 8).  A
+// build-time knob for A/B runs.
+#ifndef PXM_BINS_FIXED_STEPS
+#define PXM_BINS_FIXED_STEPS GEMM_TASK_FIXED_STEPS
+#endif
 void order_tasks(std::vector<GemmTask>& v, const std::string& order) {
-  const int64_t fixed = order == "xcd" ? GEMM_TASK_FIXED_STEPS : 0;
+  const int64_t fixed = order == "xcd" ? GEMM_TASK_FIXED_STEPS : PXM_BINS_FIXED_STEPS;
   std::stable_sort(v.begin(), v.end(), [&](const GemmTask& a, const GemmTask& b) { return task_work(a, fixed) > task_work(b, fixed); });
   if (order == "xcd" && !v.empty()) order_xcd(v, fixed);
   else if (order == "bins" && (int)v.size() > 256) order_bins(v, fixed);  // (any other word, e.g. plain: descending)
@@ -120,6 +126,7 @@ int upload_tasks(std::vector<GemmTask> v, bool paired, TaskList* out, std::vecto
     for (int sl = 0; sl < 4; ++sl)
       if (t.x2_off[sl]) out->flags |= 1;
     if (t.ks_off[0] || t.ks_off[1]) out->flags |= 2;
+    if (t.pole_n) out->flags |= 4;
   }
   // only the packed and the two-operand kernels take a task's own row pitch (sht_gemm.hip: xn / yn)
   if (!pk && !(out->flags & 1))
@@ -138,7 +145,10 @@ double tasklist_bytes(const TaskList& tl, int cg) {
     const double Ld = tl.bls[i];
     // Gram launch: the table as stored; the operand is the sum of the TWO class buffers (both read), one result
     // array, (l, m) entries with l >= |m| only (16 B each: L^2 per array and chain slot), and the data term of chain 0
-    if (tl.gram) bytes += tl.gram_table_bytes + 3 * 16.0 * cg * Ld * Ld + 16.0 * Ld * Ld;
+    // (gram_stream_bytes: what the launch reads of the stored table, plus the operand rows and pole columns that the
+    // order-0 halves read for their pole term -- 2 L rows of both class buffers, 2 L entries of b twice)
+    if (tl.gram) bytes += (tl.gram_pole ? tl.gram_stream_bytes + 2 * 2 * 16.0 * cg * Ld + 2 * 2 * 8.0 * Ld : tl.gram_table_bytes) +
+                          3 * 16.0 * cg * Ld * Ld + 16.0 * Ld * Ld;
     else bytes += gemm_alg_bytes(tl.bls[i], tl.paired, cg, tl.los[i]);
     // a transform that rides on the previous one's pass over the table (packed pair: the support cut of the pass is the
     // smaller of the two, i.e. the previous entry's -- scales are listed coarse to fine)

@@ -238,10 +238,12 @@ static int wav_plan_create_impl(const char* who, int L, double B, int J_min, int
 int pxm::wav_make_gram_lists(pxm_wav_plan_s* p) {
   if (p->gram.d) return 0;
   int rc;
-  // spin 0 and Rp % 32 == 0: the Gram table without its structurally zero half (sht_core.h: TAB_GRAM_SPLIT);
-  // PXM_GRAM_SPLIT=0 keeps the dense list (the cross-check and the A/B switch)
+  // spin 0 and Rp % 32 == 0: the Gram table without its structurally zero half, order 0 included (sht_core.h:
+  // TAB_GRAM_SPLIT0).  The cross-check and A/B switches: PXM_GRAM_SPLIT=1 keeps order 0 dense (TAB_GRAM_SPLIT),
+  // PXM_GRAM_SPLIT=0 keeps the dense list
   const char* split_env = getenv("PXM_GRAM_SPLIT");
-  const int kind = (gram_can_split(*p->TL) && !(split_env && atoi(split_env) == 0)) ? TAB_GRAM_SPLIT : TAB_GRAM;
+  const int split = split_env ? atoi(split_env) : 2;
+  const int kind = (!gram_can_split(*p->TL) || split == 0) ? TAB_GRAM : (split == 1 ? TAB_GRAM_SPLIT : TAB_GRAM_SPLIT0);
   if ((rc = get_tables(p->L, p->spin, 1u << kind, &p->TL))) return rc;
   wav_hold(p, p->TL);
   std::vector<GemmTask> v;
@@ -253,6 +255,8 @@ int pxm::wav_make_gram_lists(pxm_wav_plan_s* p) {
   if ((rc = upload_tasks(v, p->TL->paired, &p->gram, {p->L}, p->ncol, p->ws, "Gram step"))) return rc;
   p->gram.gram = true;
   p->gram.gram_table_bytes = (double)p->TL->bytes[kind];
+  p->gram.gram_pole = kind == TAB_GRAM_SPLIT0;
+  p->gram.gram_stream_bytes = p->gram.gram_table_bytes - (p->gram.gram_pole ? 4.0 * p->Rp * p->Rp : 0.0);  // (two Rp/2 x Rp/2 blocks of doubles)
   return wav_level_list(p, TAB_INV_ADJ, p->offGD, p->offHD, GemmFuse(), &p->adj_invadj_D, "inverse-adjoint of the data rings");
 }
 
@@ -417,7 +421,8 @@ int64_t pxm_host_check_address_ranges(int L, double B, int J_min, int spin, int 
 }
 
 // Bytes of the Gram table the ring-space step of a wavelet plan (L, B, J_min) at `spin` streams per launch, as stored: the
-// parity-split table where it applies (spin 0, Rp % 32 == 0, PXM_GRAM_SPLIT not 0), the dense one otherwise.  Host-only: a
+// parity-split table where it applies (spin 0, Rp % 32 == 0, PXM_GRAM_SPLIT not 0; order 0 is stored whole in either split
+// form), the dense one otherwise.  Host-only: a
 // dry-run plan like the one above.
 int64_t pxm_host_gram_table_bytes(int L, double B, int J_min, int spin, int max_chains) {
   static std::mutex mu;

@@ -129,6 +129,10 @@ for (grid, gram), rows in launches:
     ends = (a[:, 3] - t0) / 100.0
     print(f"  last workgroup to finish: block {int(a[np.argmax(ends), 0])} with {int(nchs[np.argmax(ends)])} chunks, started at {start[np.argmax(ends)]:.1f} us, "
           f"ran {dur[np.argmax(ends)]:.1f} us; 90 % of the workgroups are done by {np.percentile(ends, 90):.1f} us")
+    print("  the eight workgroups that end the launch (block: chunks x row tiles, start -> end us): " + ", ".join(
+        f"{int(a[i, 0])}: {int(nchs[i])} x {int((a[i, 5] >> 16) & 0xffff)}, {start[i]:.1f} -> {ends[i]:.1f}" for i in np.argsort(ends)[::-1][:8]))
+    print("  end of the last workgroup per chunk count: " + ", ".join(
+        f"{nch}: {ends[nchs == nch].max():.1f}" for nch in sorted(set(nchs.tolist()), reverse=True)))
 
 m = int(h[1])
 q = h[8 + 8 * 8192:8 + 8 * 8192 + 8 * m].reshape(m, 8).astype(np.int64)
