@@ -58,6 +58,16 @@ struct GemmGeom {
   static constexpr int COLS = 16 * NCT;                       // staged operand columns
   static constexpr int PITCH = COLS + (COLS == 16 ? 0 : 16);  // doubles; PITCH*8 = 128 (mod 256)
 };
+// Epilogue operands of a task in LDS (the unpacked kernels): the distinct values its epilogue needs -- per output row the
+// complex data term of every slab, the output scale and, in the POLE variant, b of the row -- fetched once per workgroup at
+// task start, [hd: NSLAB][ROWS][2] [rs: ROWS] [b_own: ROWS] doubles, ROWS = 16 NW RT
+template <int NSLAB, int NW, int RT, bool POLE>
+struct GemmEpi {
+  static constexpr int ROWS = 16 * NW * RT;
+  static constexpr int NHD = 2 * NSLAB * ROWS;
+  static constexpr int RS_AT = NHD, B_AT = NHD + ROWS;
+  static constexpr int SIZE = NHD + ROWS + (POLE ? ROWS : 0);
+};
 // PK (packed columns, few-chain plans): 0 = off.  PK = 2 C in {2, 4}: ONE column tile whose 16 columns are up to 16 / PK
 // slabs of PK live columns each -- slab s = column / PK reads / writes columns col0 .. col0 + PK - 1 of ITS operand / result
 // array (x_off[s] / y_off[s]), slabs 2g, 2g + 1 being the +m / -m slabs of transform g of a task that streams one table
@@ -69,8 +79,11 @@ struct GemmGeom {
 template <int CT, int NSLAB, int NW, int RT, int NSET, bool TWO, bool SK, int PK = 0, bool POLE = false>
 __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks, const int bid,
                                               const double* __restrict__ X, double* __restrict__ Y, int ncol, int col0,
-                                              const GemmAffine& aff, double (*xs)[KC][GemmGeom<CT, NSLAB>::PITCH]) {
+                                              const GemmAffine& aff, double (*xs)[KC][GemmGeom<CT, NSLAB>::PITCH],
+                                              double* __restrict__ es) {
   constexpr int NCT = CT * NSLAB;
+  typedef GemmEpi<NSLAB, NW, RT, POLE> Epi;
+  constexpr bool EARLY = PK == 0;  // the epilogue operands go through es (the packed kernels load them after the loop)
   // all B-fragment LDS reads of a chunk ahead of its MFMAs (one LDS round trip per chunk instead of four): pays in the
   // Gram launch (1.5 workgroups per CU, nothing else to hide the latency: 22.3 -> 21.8 us), costs 6-10 VGPRs and with
   // them the eighth wave per SIMD in the streaming launches (32.0 -> 32.7 us) -- on for the two-operand variants only
@@ -183,6 +196,60 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
     }                                                                         \
   }
 
+  // ---- epilogue operands: none of them depends on the contraction, so their loads go out here, ahead of every load of
+  // the loop (its exact vmcnt counts keep holding: these are older), one value per thread instead of one per output
+  // element -- sixteen column lanes used to load the same scale, eight the same data term, in a memory round trip of
+  // its own after the last MFMA, with every workgroup of the launch at that point together.  The values wait in
+  // registers until iteration 1 has its operand and go to es there; that iteration's barrier publishes them.  As compiled,
+  // they have arrived long before: the wait for the per-thread slab offsets of the staging map (iteration 0, a
+  // vmcnt(0) ahead of the first table load) covers them, at a time when the memory system has nothing else to do.
+  // Without that wait (slab offsets selected from scalars, these loads in flight with the first table chunk) the three
+  // launches measured 0.6 - 0.8 us slower each (docs/EXPERIMENTS.md, round 9).
+  // Rows past the task's tiles re-read its row 0 (valid memory; nobody reads those entries).
+  constexpr int EIT = (Epi::NHD + NT - 1) / NT;
+  double e_hd[EIT], e_rs = 1.0;
+  if constexpr (EARLY) {
+#pragma unroll
+    for (int i = 0; i < EIT; ++i) {
+      const int e = (tid + NT * i) % Epi::NHD, sl = e / (2 * Epi::ROWS), rl = (e >> 1) % Epi::ROWS;
+      int64_t ho = t.hd_off[0];
+#pragma unroll
+      for (int s2 = 1; s2 < NSLAB; ++s2) ho = sl == s2 ? t.hd_off[s2] : ho;  // (a select, not a run-time index: see x_off above)
+      e_hd[i] = 0.0;
+      if (aff.on && ho) e_hd[i] = (X + ho)[(int64_t)(t.row0 + (rl < 16 * t.n_rt ? rl : 0)) * t.hd_stride + (e & 1)];
+    }
+    if (t.rs_off[0] && tid < Epi::ROWS) e_rs = (X + t.rs_off[0])[t.row0 + (tid < 16 * t.n_rt ? tid : 0)];
+  }
+  // Pole term of an order-0 half (task-uniform branch): acc[row][col] += 1/2 b_own[row] * s[col] with
+  // s[col] = sum_r b_other[r] * x_other[r][col] over the half-rows of the other parity.  Both slabs of order 0 stage
+  // the same operand, so s is formed once for the 16 CT columns of slab 0.  Fixed summation order: thread (row
+  // group rg, column pair cp) sums rows rg, rg + NRG, ...; a butterfly over the row groups of a wave; the eight
+  // waves through LDS in wave order.  The thread's own sum is formed HERE, before the loop -- the operand is what the
+  // previous launch wrote -- and b of the task's rows goes to es; the butterfly and the exchange need xs and follow the loop.
+  double2 part{0.0, 0.0};
+  if constexpr (POLE) {
+    if (t.pole_n) {
+      constexpr int W2 = 8 * CT;    // column pairs of one slab
+      constexpr int NRG = NT / W2;  // row groups of the workgroup
+      const int cp = tid % W2, rg = tid / W2;
+      const double* xo = X + t.x_off[0] + t.pole_dx + col0 + 2 * cp;
+      const double* xo2 = two ? X + t.x2_off[0] + t.pole_dx + col0 + 2 * cp : xo;
+      const double* bo = X + t.pole_bo_off;
+      double b_own = 0.0;  // (in flight with the operand rows below)
+      if (tid < Epi::ROWS) b_own = (X + t.pole_b_off)[t.row0 + (tid < 16 * t.n_rt ? tid : 0)];
+#pragma unroll 1  // (two rows per thread at L = 256)
+      for (int r = rg; r < t.pole_n; r += NRG) {
+        const double2 a = *reinterpret_cast<const double2*>(xo + (int64_t)r * xn);
+        const double2 a2 = *reinterpret_cast<const double2*>(xo2 + (int64_t)r * xn);
+        const double bv = bo[r];
+        const double2 v = stage_add(a, a2, two);
+        part.x += bv * v.x;
+        part.y += bv * v.y;
+      }
+      if (tid < Epi::ROWS) es[Epi::B_AT + tid] = b_own;
+    }
+  }
+
   d4 acc[RT][NCT];
 #pragma unroll
   for (int r = 0; r < RT; ++r)
@@ -219,6 +286,12 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
 #endif
       PXM_STAGE_STORE(us, buf)
       PXM_GEMM_CSTAMP(1)  // operand of this chunk arrived and went to LDS
+      if (EARLY && pv == 1 && it0 == 0) {  // iteration 1 (every task has it): the epilogue operands, loaded before the loop
+#pragma unroll
+        for (int i = 0; i < EIT; ++i)
+          if (tid + NT * i < Epi::NHD) es[tid + NT * i] = e_hd[i];
+        if (tid < Epi::ROWS) es[Epi::RS_AT + tid] = e_rs;
+      }
       PXM_STAGE_LOAD(us, it)
       PXM_TAB_LOAD(ut, it)
       __syncthreads();
@@ -254,53 +327,37 @@ __device__ __forceinline__ void sht_gemm_body(const GemmTask* __restrict__ tasks
 #endif
 
   // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg.
-  // Epilogue operands first -- the per-row data term of the Gram step and the per-row scale of the fused combine --
-  // ALL loads in flight together, then the arithmetic and the stores: one memory latency instead of one per output
-  // row (a per-workgroup timeline of the Gram launch showed 5-8 us of its 10-23 us in serial epilogue loads).
+  // Epilogue operands first -- the per-row data term of the Gram step and the per-row scale of the fused combine: LDS
+  // reads of what the task fetched at its start (packed kernels: global loads, ALL in flight together), then the
+  // arithmetic and the stores.
   constexpr int NGRP = PK ? 2 : 1;  // slab groups (transforms) per task: one, or up to two in packed lists
   double hdv[RT][NSLAB][4], rsv[RT][NGRP][4];
 #pragma unroll
   for (int r = 0; r < RT; ++r) {
-    const int rowb = t.row0 + 16 * (r < n_my ? RT * wave + r : 0) + kq;  // (a tile this wave does not own: the task's tile 0 -- valid rows, values discarded)
+    const int rl = 16 * (r < n_my ? RT * wave + r : 0) + kq;  // (a tile this wave does not own: the task's tile 0 -- valid rows, values discarded)
+    const int rowb = t.row0 + rl;
+    if constexpr (EARLY) {
 #pragma unroll
-    for (int sl = 0; sl < NSLAB; ++sl)
+      for (int sl = 0; sl < NSLAB; ++sl)
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        hdv[r][sl][q] = (aff.on && t.hd_off[sl]) ? (X + t.hd_off[sl])[(int64_t)(rowb + 4 * q) * t.hd_stride + (cl & 1)] : 0.0;
+        for (int q = 0; q < 4; ++q) hdv[r][sl][q] = es[2 * (sl * Epi::ROWS + rl + 4 * q) + (cl & 1)];
 #pragma unroll
-    for (int g = 0; g < NGRP; ++g)
+      for (int q = 0; q < 4; ++q) rsv[r][0][q] = es[Epi::RS_AT + rl + 4 * q];
+    } else {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) rsv[r][g][q] = t.rs_off[g] ? (X + t.rs_off[g])[rowb + 4 * q] : 1.0;
+      for (int g = 0; g < NGRP; ++g)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) rsv[r][g][q] = t.rs_off[g] ? (X + t.rs_off[g])[rowb + 4 * q] : 1.0;
+    }
   }
   if constexpr (POLE) {
-    // Pole term of an order-0 half (task-uniform branch): acc[row][col] += 1/2 b_own[row] * s[col] with
-    // s[col] = sum_r b_other[r] * x_other[r][col] over the half-rows of the other parity.  Both slabs of order 0 stage
-    // the same operand, so s is formed once for the 16 CT columns of slab 0.  Fixed summation order: thread (row
-    // group rg, column pair cp) sums rows rg, rg + NRG, ...; a butterfly over the row groups of a wave; the eight
-    // waves through LDS in wave order.  The loads are issued with the epilogue operands above and share their latency.
-    if (t.pole_n) {
+    if (t.pole_n) {  // the thread's sum `part` was formed before the loop
       constexpr int W2 = 8 * CT;    // column pairs of one slab
-      constexpr int NRG = NT / W2;  // row groups of the workgroup
-      const int cp = tid % W2, rg = tid / W2;
-      const double* xo = X + t.x_off[0] + t.pole_dx + col0 + 2 * cp;
-      const double* xo2 = two ? X + t.x2_off[0] + t.pole_dx + col0 + 2 * cp : xo;
-      const double* bo = X + t.pole_bo_off;
       double bown[RT][4];
 #pragma unroll
       for (int r = 0; r < RT; ++r)
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-          bown[r][q] = (X + t.pole_b_off)[t.row0 + 16 * (r < n_my ? RT * wave + r : 0) + kq + 4 * q];
-      double2 part{0.0, 0.0};
-#pragma unroll 1  // (two rows per thread at L = 256; unrolled by two the variant takes 98 VGPRs instead of 78 and a CU holds two workgroups, not three)
-      for (int r = rg; r < t.pole_n; r += NRG) {
-        const double2 a = *reinterpret_cast<const double2*>(xo + (int64_t)r * xn);
-        const double2 a2 = *reinterpret_cast<const double2*>(xo2 + (int64_t)r * xn);
-        const double bv = bo[r];
-        const double2 v = stage_add(a, a2, two);
-        part.x += bv * v.x;
-        part.y += bv * v.y;
-      }
+        for (int q = 0; q < 4; ++q) bown[r][q] = es[Epi::B_AT + 16 * (r < n_my ? RT * wave + r : 0) + kq + 4 * q];
 #pragma unroll
       for (int msk = W2; msk < 64; msk <<= 1) {
         part.x += __shfl_xor(part.x, msk);
@@ -397,16 +454,17 @@ __global__ __launch_bounds__(64 * NW) void k_sht_gemm(const GemmTask* __restrict
                                                       const double* __restrict__ X, double* __restrict__ Y,
                                                       int ncol, int col0, GemmAffine aff) {
   __shared__ double xs[2][KC][GemmGeom<CT, NSLAB>::PITCH];
+  __shared__ double es[GemmEpi<NSLAB, NW, RT, POLE>::SIZE];
   static_assert(!POLE || 2 * KC * GemmGeom<CT, NSLAB>::PITCH >= NW * 16 * CT, "the pole reduction borrows the operand buffers");
   if (aff.bump && blockIdx.x == 0 && threadIdx.x == 0) *aff.bump += 1;  // Philox iteration counter of the ring-space step
-  sht_gemm_body<CT, NSLAB, NW, RT, NSET, TWO, SK, 0, POLE>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs);
+  sht_gemm_body<CT, NSLAB, NW, RT, NSET, TWO, SK, 0, POLE>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs, es);
 }
 // packed column tile (few-chain plans): PK live columns per slab, up to 16 / PK slabs in the one tile
 template <int PK, int NW, int RT, int NSET, bool TWO, bool SK>
 __global__ __launch_bounds__(64 * NW) void k_sht_gemm_pk(const GemmTask* __restrict__ tasks, const double* __restrict__ X,
                                                          double* __restrict__ Y, int ncol, int col0, GemmAffine aff) {
   __shared__ double xs[2][KC][GemmGeom<1, 1>::PITCH];
-  sht_gemm_body<1, 1, NW, RT, NSET, TWO, SK, PK>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs);
+  sht_gemm_body<1, 1, NW, RT, NSET, TWO, SK, PK>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs, nullptr);
 }
 
 // ---- live profiler: event pairs around GEMM / grouped-DFT launches, owned by a plan ----------------
@@ -496,7 +554,7 @@ int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags,
     if (!ok(t.tab_off, t.tab_off + (int64_t)(t.n_rt - 1) * t.rt_stride + (int64_t)(2 * (nch - 1) + 1) * 128 + 127))
       return bad(ti, "ring-table stream", 0);
     for (int col0 = 0; col0 < ncol && t.pole_n; col0 += 32) {
-      // pole term: b of the task's own rows (as the per-row scale: tiles 0 .. n_rt - 1), b of the other parity's pole_n
+      // pole term: b of the task's own rows (one cooperative load at task start, as the per-row scale below), b of the other parity's pole_n
       // half-rows, and the 16 CT columns of slab 0 of the other parity's operand(s), rows 0 .. pole_n - 1 at the task's pitch
       const int CT = (ncol - col0 >= 32) ? 2 : 1;
       if (!ok(t.pole_b_off + t.row0, t.pole_b_off + t.row0 + 16 * t.n_rt - 1)) return bad(ti, "pole column of the task's rows", col0);
@@ -519,9 +577,12 @@ int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags,
         // per-k operand scale: X + ks_off[slab >> 1] + k_beg + kr + cs KC
         if (SK && t.ks_off[slab >> 1] && !ok(t.ks_off[slab >> 1] + t.k_beg, t.ks_off[slab >> 1] + t.k_end - 1))
           return bad(ti, "operand scale vector", col0);
-        // epilogue: rows row0 + 16 tile + kq + 4 q, tile <= n_rt - 1 (a tile the wave does not own: tile 0)
+        // epilogue operands.  Unpacked kernels: one cooperative load at task start, thread -> row row0 + rl of the task,
+        // rl < 16 n_rt (threads past the task's tiles re-read its row 0) -- every row of the task, contiguous.  Packed
+        // kernels: after the loop, rows row0 + 16 tile + kq + 4 q, tile <= n_rt - 1 (a tile the wave does not own: tile 0).
+        // The same range either way.
         const int64_t r_lo = t.row0, r_hi = t.row0 + 16 * t.n_rt - 1;
-        // affine constants: (X + hd_off[slab])[(row) hd_stride + (cl & 1)]
+        // affine constants: (X + hd_off[slab])[(row) hd_stride + {0, 1}]
         if (t.hd_off[slab] && !ok(t.hd_off[slab] + r_lo * t.hd_stride, t.hd_off[slab] + r_hi * t.hd_stride + 1))
           return bad(ti, "affine data term", col0);
         if (t.rs_off[slab >> 1] && !ok(t.rs_off[slab >> 1] + r_lo, t.rs_off[slab >> 1] + r_hi))
