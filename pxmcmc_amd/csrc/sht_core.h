@@ -1,4 +1,5 @@
-// Internal C++ interface of the SHT engine: ring tables, GEMM stage, DFT stage.
+// Internal C++ interface of the SHT engine: GEMM stage, DFT stage, layout repack (ring tables: sht_tables.h, task-list
+// construction: tasklist.h).
 //
 // Formulation.  Every MW transform is a phi-DFT stage and a
 // per-m "Legendre" stage that contracts a REAL table with complex data:
@@ -15,29 +16,15 @@
 //   G, H : [m_idx = m + L - 1][row][ncol]   ncol = 2*Cp doubles, Cp = roundup(C, 8)
 #pragma once
 #include "common.h"
+#include "profiler.h"
 
 namespace pxm {
 
-// TAB_GRAM: (B^m)^T B^m, el <- el: the inverse transform followed by its adjoint in one contraction
-// (normal equations of the ring-space MYULA step)
-// TAB_GRAM_SPLIT: the same matrix for spin 0 and Rp % 32 == 0, stored without its structurally zero half.  For m >= 1
-// the entries G^m[l][l'] with l + l' odd vanish, so order m is kept as two half-size dense
-// matrices G_p[i][j] = G^m[2i + p][2j + p], p = 0 (even degrees) and 1 (odd degrees), each tiled like any other table
-// from kb_p = round_down(ceil((m - p) / 2), 16).  m = 0 has a real odd-parity part (the pole ring) and stays dense.
-// An order stays one dense block where the two halves would not be cheaper (gram_order_splits below): the halves cannot
-// go below one 16 x 16 tile, and each is a workgroup with a start-up and a drain of its own.
-// TAB_GRAM_SPLIT0: TAB_GRAM_SPLIT with order 0 split as well.  The odd-parity part of G^0 is the pole ring alone and has
-// rank one: G^0[l][l'] = 1/2 b_l b_l' for l + l' odd, b_l = B^0[theta = pi][l].  Order 0 is stored as
-// the parity-permuted matrix [[ee, eo], [oe, oo]] (Rp^2 doubles, as before); its two half tasks stream the diagonal blocks
-// and add 1/2 b_row (b_other . x_other) in their epilogue (GemmTask::pole_n), the off-diagonal blocks are never read.
-enum TableKind { TAB_INV = 0, TAB_FWD = 1, TAB_INV_ADJ = 2, TAB_FWD_ADJ = 3, TAB_GRAM = 4, TAB_GRAM_SPLIT = 5, TAB_GRAM_SPLIT0 = 6, TAB_KINDS = 7 };
-inline bool kind_el_to_ring(int kind) { return kind == TAB_INV || kind == TAB_FWD_ADJ; }
-inline bool kind_is_gram_split(int kind) { return kind == TAB_GRAM_SPLIT || kind == TAB_GRAM_SPLIT0; }
-inline bool kind_is_gram(int kind) { return kind == TAB_GRAM || kind_is_gram_split(kind); }
-inline bool kind_rows_are_el(int kind) { return kind == TAB_FWD || kind == TAB_INV_ADJ || kind_is_gram(kind); }
-inline bool kind_k_is_el(int kind) { return kind == TAB_INV || kind == TAB_FWD_ADJ || kind_is_gram(kind); }
+// Row tiles of 16 output rows per task (= per workgroup): 8 waves x 1 row tile per wave.  (4 waves x 1 and 4 x 2 were
+// A/B variants until round 2: 26.1 us and slower for the Gram launch, operand staged twice as often.)
+constexpr int GEMM_TASK_ROW_TILES = 8;
 
-// One workgroup's share of a per-m GEMM: up to 8 row tiles of 16 output rows.
+// One workgroup's share of a per-m GEMM: up to GEMM_TASK_ROW_TILES row tiles of 16 output rows.
 // Column slabs: slab 0 = +m, slab 1 = -m (spin 0 shares one table up to the sign (-1)^m).  A MERGED task
 // (nslab = 4) streams the table once for TWO transforms at the same bandlimit (the two full-size wavelet
 // scales): slabs 2, 3 are the +m / -m slabs of the second transform; slabs 2g, 2g+1 form group g and share
@@ -55,7 +42,7 @@ struct GemmTask {
   int row_lo[2], row_hi[2];  // per group: only output rows in [row_lo, row_hi) are written
   int k_beg, k_end;    // contraction range, multiples of 16
   int row0;            // first output row of this task
-  int n_rt;            // row tiles in this task (1..8)
+  int n_rt;            // row tiles in this task (1..GEMM_TASK_ROW_TILES)
   int nslab;           // live slabs: 1 (all m stored) or 2 (+-m pair)
   double sign1;        // factor on the -m outputs ((-1)^m)
   int m_unit;          // the order this task belongs to: m (paired tables: m >= 0 serves +-m) or m + L - 1
@@ -82,111 +69,28 @@ struct GemmAffine {
   uint64_t* bump = nullptr;  // optional: workgroup 0 adds 1 to this counter before anything of this step reads it
 };
 
-// Live kernel timing of one plan (bench.py roofline leg): event pairs handed to hipExtLaunchKernelGGL, which
-// stamps them with the kernel's own start / end on the stream it runs on.  Owned by the plan -- no process state.
-struct Profiler {
-  struct Pool {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-    size_t used = 0;
-    double bytes = 0, flops = 0;
-    std::vector<double> launch_bytes;  // algorithmic bytes of every bracketed launch (launch classes of bench.py)
-    std::vector<int> launch_wgs;       // workgroups of every bracketed launch (the key rocprofv3 records join on)
-  };
-  bool on = false;
-  Pool gemm, dft;
-  void next(Pool& p, hipEvent_t* start, hipEvent_t* stop, double alg_bytes, double flops, int workgroups = 0) {
-    *start = *stop = nullptr;
-    if (!on || p.used >= p.ev.size()) return;
-    *start = p.ev[p.used].first;
-    *stop = p.ev[p.used].second;
-    p.bytes += alg_bytes;
-    p.flops += flops;
-    p.launch_bytes.push_back(alg_bytes);
-    p.launch_wgs.push_back(workgroups);
-    ++p.used;
-  }
-};
-int profiler_enable(Profiler* pr, int max_launches);  // 0 = off (events are released)
-int profiler_read(Profiler::Pool* p, double* ms, int64_t* launches, double* bytes, double* flops,
-                  double* per_launch_ms = nullptr, double* per_launch_bytes = nullptr, int64_t cap = 0,
-                  int32_t* per_launch_wgs = nullptr);
-void profiler_release(Profiler* pr);
-
-// extras of append_gemm_tasks for the fused wavelet combine
-struct GemmFuse {
-  int64_t x2_base = -1;           // second operand array (same L / Rp as x), -1 = none
-  const double* rscale = nullptr;  // per-output-row scale
-  int row_lo = 0, row_hi = 1 << 30;
-  int64_t hd_base = -1;            // array holding the affine constants, -1 = none ...
-  int hd_stride = 0;               // ... and its row stride in doubles (0: H layout, ncol doubles per row, chain 0)
-};
-
-struct ShtTables {
-  int L = 0, spin = 0, Rp = 0;
-  bool paired = false;           // spin 0: only m >= 0 stored, -m served with sign (-1)^m
-  int n_m = 0;                   // stored m count
-  double* d_tab[TAB_KINDS] = {};
-  size_t bytes[TAB_KINDS] = {};
-  std::vector<int64_t> m_off[TAB_KINDS];  // per stored-m offset (doubles) into d_tab[kind]
-  std::vector<int> k_beg[TAB_KINDS];      // per stored-m contraction start (el->ring kinds) / first row tile*16 (ring->el)
-  // TAB_GRAM_SPLIT, orders stored as halves: the odd-degree half (m_off / k_beg above describe the even-degree half, in
-  // half-row units); odd_off < 0: the order is stored dense (m = 0, and the orders gram_order_splits turns down)
-  std::vector<int64_t> odd_off;
-  std::vector<int> odd_k_beg;
-  // TAB_GRAM_SPLIT0: b_l = B^0[theta = pi][l] by parity, [Rp / 2 even degrees | Rp / 2 odd degrees], zero for l >= L
-  double* d_pole = nullptr;
-  int refs = 0;                           // plans holding this entry of the per-device cache
-  int m_of(int i) const { return paired ? i : i - (L - 1); }
-};
-
-// can the Gram matrix of these tables be stored split by degree parity (TAB_GRAM_SPLIT, TAB_GRAM_SPLIT0)?
-inline bool gram_can_split(const ShtTables& T) { return T.paired && T.Rp % 32 == 0; }
 // start-up and drain of a GEMM task, in contraction steps (the figure the XCD launch order balances with, tasklist.hip)
 constexpr int GEMM_TASK_FIXED_STEPS = 32;
-// first half-row of the parity-par half of order m, down to a tile: the first i with 2 i + par >= m
-inline int gram_half_k_beg(int m, int par) { return round_down((m - par + 1) / 2, 16); }
-// Is order m >= 1 cheaper as two halves than as one dense block?  Modelled work of a block of extent n from kb on: row
-// tiles x (contraction steps + the fixed cost of a task).  The halves win wherever they halve the block; they lose in
-// the last 16 orders (a one-tile block would become two) and where two tiles per half replace a 3 x 3 tile block.
-inline bool gram_order_splits(int Rp, int m) {
-  auto work = [](int n, int kb) { return (n - kb) / 16 * (n - kb + GEMM_TASK_FIXED_STEPS); };
-  return work(Rp / 2, gram_half_k_beg(m, 0)) + work(Rp / 2, gram_half_k_beg(m, 1)) < work(Rp, round_down(m, 16));
-}
 
-// builds (or returns cached) tables for (L, spin); kinds_mask selects which kinds to build.  The cache is
-// per device and shared by plans: a plan retains every entry it uses once and releases it at teardown;
-// tables_trim() frees the entries nobody holds (pxm_tables_trim).
-int get_tables(int L, int spin, unsigned kinds_mask, ShtTables** out);
-void retain_tables(ShtTables* T);
-void release_tables(ShtTables* T);
-int64_t tables_trim();  // returns the bytes released
-
-// Append the tasks of one transform's GEMM stage.  x_base / y_base are offsets (doubles) of the
-// [2L-1][Rp][ncol] operand / output arrays inside the workspace; x rows may belong to a larger
-// array (x_Rp, x_L give the operand array's row padding and bandlimit for the m_idx mapping).
-void append_gemm_tasks(const ShtTables& T, int kind, int ncol, int64_t x_base, int x_L, int x_Rp,
-                       int64_t y_base, int y_L, int y_Rp, const double* kscale, int64_t scratch_off,
-                       const double* ws_base, std::vector<GemmTask>& tasks, int el_lo = 0,
-                       const GemmFuse& fuse = GemmFuse());
-// the same for TWO transforms that share the table T (same bandlimit): one pass over the table, 4 slabs
-struct GemmSide {
-  int64_t x_base, y_base;
-  int x_L, x_Rp, y_L, y_Rp;
-  const double* kscale;
-  int el_lo;
-  GemmFuse fuse;
-  int x_ncol = 0, y_ncol = 0;  // 0 = the launch's ncol
+// what the tasks of a list carry, i.e. the kernel variant its launches take (TaskList::flags)
+enum GemmListFlag {
+  GEMM_LIST_TWO = 1,    // a second operand, summed in while staging
+  GEMM_LIST_SCALE = 2,  // a per-contraction-row operand scale
+  GEMM_LIST_POLE = 4,   // a pole term (the split Gram list with its order-0 halves: two operands, no scale, +-m pairs)
 };
 
-void append_gemm_tasks_packed(const ShtTables& T, int kind, int ncol, const GemmSide& side_a, const GemmSide* side_b,
-                              int64_t scratch_off, const double* ws_base, std::vector<GemmTask>& tasks);
+// Column groups of an unpacked list: one launch per 32 columns (two column tiles of 16) while 32 remain, one tile after
+constexpr int GEMM_GROUP_COLS = 32;
+inline int gemm_group_tiles(int ncol, int col0) { return (ncol - col0 >= GEMM_GROUP_COLS) ? 2 : 1; }
+
+// packed launch (pk = live columns per slab: 2 or 4); flags: GemmListFlag bits
 int launch_gemm_packed(const GemmTask* d_tasks, int n_tasks, int pk, int flags, const double* X, double* Y, int ncol, int col0,
                        double alg_bytes, double flops, hipStream_t stream, Profiler* prof = nullptr);
 
 // launch: tasks on device; X/Y = workspace base; col0 = first column of this chain group, ct = column
 // tiles (1 or 2) of the group
 // alg_bytes: algorithmic bytes of this launch (table once + operand + result), for the live profiler
-// nslab: 1 (unpaired) or 2 (+-m pairs)
+// nslab: 1 (unpaired) or 2 (+-m pairs); flags: GemmListFlag bits
 int launch_gemm(const GemmTask* d_tasks, int n_tasks, int nslab, int flags, const double* X, double* Y, int ncol,
                 int col0, int ct, double alg_bytes, double flops, hipStream_t stream,
                 const GemmAffine& aff = GemmAffine(), Profiler* prof = nullptr);
@@ -219,10 +123,9 @@ inline double gemm_alg_bytes(int L, bool paired, int C, int el_lo = 0) {
   return 8.0 * L * tab_entries + 16.0 * C * (lm_entries + (double)L * (2 * L - 1));
 }
 
-int gemm_rows_per_task(int ncol);
-// host model of every address k_sht_gemm forms for a task list (sht_gemm.hip); < 0 + error text when a range leaves
-// its allocation
-int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags, int ncol, const double* ws_base,
+// host model of every address k_sht_gemm / k_sht_gemm_pk (pk != 0) forms for a task list (sht_gemm.hip); < 0 + error
+// text when a range leaves its allocation
+int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int pk, int flags, int ncol, const double* ws_base,
                            const char* list_name);
 
 // ---- DFT stage ---------------------------------------------------------------

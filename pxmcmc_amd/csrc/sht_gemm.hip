@@ -1,5 +1,6 @@
 // Legendre ("ring") stage of the MW transforms: per-m real-table x complex-batch GEMMs on
-// v_mfma_f64_16x16x4_f64, plus the device-side construction of the tiled ring tables.
+// v_mfma_f64_16x16x4_f64, the host model of the addresses the kernel forms, and the launchers.  (The tables are built in
+// sht_tables.hip, the task lists in tasklist.hip.)
 //
 // Table layout: for every stored m and every tile of 16 output rows the
 // contraction index runs in chunks of 8; one chunk is 128 doubles = [lane(64)][2], where
@@ -13,9 +14,7 @@
 
 #include <hip/hip_ext.h>
 
-#include <cstdlib>
-#include <map>
-#include <mutex>
+#include <algorithm>
 
 namespace pxm {
 
@@ -467,60 +466,6 @@ __global__ __launch_bounds__(64 * NW) void k_sht_gemm_pk(const GemmTask* __restr
   sht_gemm_body<1, 1, NW, RT, NSET, TWO, SK, PK>(tasks, blockIdx.x, X, Y, ncol, col0, aff, xs, nullptr);
 }
 
-// ---- live profiler: event pairs around GEMM / grouped-DFT launches, owned by a plan ----------------
-int profiler_enable(Profiler* pr, int max_launches) {
-  profiler_release(pr);
-  if (max_launches <= 0) return 0;
-  for (Profiler::Pool* p : {&pr->gemm, &pr->dft}) {
-    p->ev.resize((size_t)max_launches);
-    for (auto& e : p->ev) {
-      e.first = e.second = nullptr;
-      PXM_HIP(hipEventCreate(&e.first));
-      PXM_HIP(hipEventCreate(&e.second));
-    }
-  }
-  pr->on = true;
-  return 0;
-}
-void profiler_release(Profiler* pr) {
-  pr->on = false;
-  for (Profiler::Pool* p : {&pr->gemm, &pr->dft}) {
-    for (auto& e : p->ev) {
-      deferred_event_destroy(e.first);
-      deferred_event_destroy(e.second);
-    }
-    p->ev.clear();
-    p->used = 0;
-    p->bytes = p->flops = 0;
-    p->launch_bytes.clear();
-    p->launch_wgs.clear();
-  }
-}
-int profiler_read(Profiler::Pool* p, double* ms, int64_t* launches, double* bytes, double* flops, double* per_launch_ms,
-                  double* per_launch_bytes, int64_t cap, int32_t* per_launch_wgs) {
-  double tot = 0;
-  for (size_t i = 0; i < p->used; ++i) {
-    PXM_HIP(hipEventSynchronize(p->ev[i].second));
-    float t = 0;
-    PXM_HIP(hipEventElapsedTime(&t, p->ev[i].first, p->ev[i].second));
-    tot += t;
-    if ((int64_t)i < cap) {
-      if (per_launch_ms) per_launch_ms[i] = t;
-      if (per_launch_bytes) per_launch_bytes[i] = p->launch_bytes[i];
-      if (per_launch_wgs) per_launch_wgs[i] = p->launch_wgs[i];
-    }
-  }
-  if (ms) *ms = tot;
-  if (launches) *launches = (int64_t)p->used;
-  if (bytes) *bytes = p->bytes;
-  if (flops) *flops = p->flops;
-  p->used = 0;
-  p->bytes = p->flops = 0;
-  p->launch_bytes.clear();
-  p->launch_wgs.clear();
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------
 // Host model of the addresses k_sht_gemm forms.  KEEP IN STEP WITH THE KERNEL ABOVE: every global load and store of
 // the kernel has one line here, including the loads whose values are discarded (clamped chunk indices past the end
@@ -530,7 +475,7 @@ int profiler_read(Profiler::Pool* p, double* ms, int64_t* launches, double* byte
 // check of address RANGES does, without a GPU.  For every task and every column group run_tasks can launch, each
 // range must lie inside ONE registered device allocation (common.h: dev_alloc / dev_range_ok).
 // ---------------------------------------------------------------------------------------
-int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags, int ncol, const double* ws_base,
+int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int pk, int flags, int ncol, const double* ws_base,
                            const char* list_name) {
   int64_t n = 0;
   std::string why;
@@ -544,7 +489,7 @@ int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags,
     ++n;
     return lo <= hi && dev_range_ok(ws_base + lo, ws_base + hi + 1, &why);
   };
-  const bool TWO = flags & 1, SK = flags & 2;
+  const bool TWO = flags & GEMM_LIST_TWO, SK = flags & GEMM_LIST_SCALE;
   for (size_t ti = 0; ti < v.size(); ++ti) {
     const GemmTask& t = v[ti];
     if (t.n_rt == 0) continue;  // padding entry: the workgroup exits before forming any address
@@ -553,23 +498,23 @@ int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags,
     // lane < 64, two doubles each
     if (!ok(t.tab_off, t.tab_off + (int64_t)(t.n_rt - 1) * t.rt_stride + (int64_t)(2 * (nch - 1) + 1) * 128 + 127))
       return bad(ti, "ring-table stream", 0);
-    for (int col0 = 0; col0 < ncol && t.pole_n; col0 += 32) {
+    for (int col0 = 0; col0 < ncol && t.pole_n; col0 += GEMM_GROUP_COLS) {
       // pole term: b of the task's own rows (one cooperative load at task start, as the per-row scale below), b of the other parity's pole_n
       // half-rows, and the 16 CT columns of slab 0 of the other parity's operand(s), rows 0 .. pole_n - 1 at the task's pitch
-      const int CT = (ncol - col0 >= 32) ? 2 : 1;
+      const int CT = gemm_group_tiles(ncol, col0);
       if (!ok(t.pole_b_off + t.row0, t.pole_b_off + t.row0 + 16 * t.n_rt - 1)) return bad(ti, "pole column of the task's rows", col0);
       if (!ok(t.pole_bo_off, t.pole_bo_off + t.pole_n - 1)) return bad(ti, "pole column of the other parity", col0);
       const int64_t lo = t.pole_dx + col0, hi = t.pole_dx + col0 + 16 * CT - 1 + (int64_t)(t.pole_n - 1) * t.x_ncol;
       if (!ok(t.x_off[0] + lo, t.x_off[0] + hi)) return bad(ti, "pole term operand", col0);
       if (t.x2_off[0] && !ok(t.x2_off[0] + lo, t.x2_off[0] + hi)) return bad(ti, "pole term second operand", col0);
     }
-    for (int col0 = 0; col0 < ncol; col0 += 32) {
-      const int CT = (ncol - col0 >= 32) ? 2 : 1;
+    for (int col0 = 0; col0 < ncol; col0 += GEMM_GROUP_COLS) {
+      const int CT = gemm_group_tiles(ncol, col0);
       for (int slab = 0; slab < nslab; ++slab) {
         // operand staging: X + x_off[slab] + col0 + cin + (k_beg + kr + cs KC) xn, cin < 16 CT, kr < KC, cs <= nch - 1
         // (xn, yn: the task's own row pitch in the packed and two-operand kernels, the launch's ncol in the streaming
         // ones -- upload_tasks holds the tasks of a streaming list to the launch's ncol)
-        const int xn = ((TWO || nslab == 4) && t.x_ncol) ? t.x_ncol : ncol, yn = ((TWO || nslab == 4) && t.y_ncol) ? t.y_ncol : ncol;
+        const int xn = ((TWO || pk) && t.x_ncol) ? t.x_ncol : ncol, yn = ((TWO || pk) && t.y_ncol) ? t.y_ncol : ncol;
         const int wx = std::min(16 * CT, xn), wy = std::min(16 * CT, yn);  // (a narrow array has fewer than 16 columns per row)
         const int64_t lo = col0 + (int64_t)t.k_beg * xn, hi = col0 + wx - 1 + (int64_t)(t.k_end - 1) * xn;
         if (!ok(t.x_off[slab] + lo, t.x_off[slab] + hi)) return bad(ti, "operand staging", col0);
@@ -598,46 +543,53 @@ int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int flags,
   return 0;
 }
 
-// GEMM workgroup geometry: 8 waves x 1 row tile per wave (a task covers 8 row tiles).  (4 waves x 1 and 4 x 2 were
-// A/B variants until round 2: 26.1 us and slower for the Gram launch, operand staged twice as often.)
-int gemm_rows_per_task(int ncol) {
-  (void)ncol;
-  return 8;
+// ---------------------------------------------------------------------------------------
+// Launchers.  Workgroup geometry: NW waves x RT row tiles per wave cover the row tiles of a task (sht_core.h).
+// ---------------------------------------------------------------------------------------
+constexpr int NW = 8, RT = 1;
+static_assert(NW * RT == GEMM_TASK_ROW_TILES, "a workgroup covers the row tiles of one task");
+
+// calls f(two, sk): the flags GEMM_LIST_TWO / GEMM_LIST_SCALE of a list as std::bool_constant, i.e. the TWO / SK kernel variant
+template <class F>
+static void with_gemm_variant(int flags, F f) {
+  switch (flags & (GEMM_LIST_TWO | GEMM_LIST_SCALE)) {
+    case 0: f(std::false_type(), std::false_type()); break;
+    case GEMM_LIST_TWO: f(std::true_type(), std::false_type()); break;
+    case GEMM_LIST_SCALE: f(std::false_type(), std::true_type()); break;
+    default: f(std::true_type(), std::true_type()); break;
+  }
 }
 
-// flags: bit 0 = the list's tasks carry a second operand, bit 1 = a per-contraction-row operand scale, bit 2 = a pole term
-// (the split Gram list with its order-0 halves: two operands, no scale, +-m pairs)
+// flags: GemmListFlag bits of the list
 int launch_gemm(const GemmTask* d_tasks, int n_tasks, int nslab, int flags, const double* X, double* Y, int ncol,
                 int col0, int ct, double alg_bytes, double flops, hipStream_t stream, const GemmAffine& aff, Profiler* prof) {
   if (n_tasks == 0) return 0;
   PXM_REQUIRE(nslab == 1 || nslab == 2, "launch_gemm: nslab must be 1 (unpaired tables) or 2 (+-m pairs)");
-  dim3 grid(n_tasks), block(512);
+  dim3 grid(n_tasks), block(64 * NW);
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (prof) prof->next(prof->gemm, &ev0, &ev1, alg_bytes, flops, n_tasks);
   // look-ahead NSET = 2 (one chunk ahead) on every launch: occupancy hides the load latency (60 VGPR at 16 columns,
   // 4 workgroups per CU); 3 / 4 sets measured 10-15 % slower on the grouped launches, and 4 % / 16 % slower on the
   // Gram launch too (its short tasks re-read their last chunk in the deeper prologue, its long chains are not what
   // bounds it)
-#define PXM_GEMM_L4(CT_, NS_, TWO_, SK_) \
-  hipExtLaunchKernelGGL((k_sht_gemm<CT_, NS_, 8, 1, 2, TWO_, SK_>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff)
-#define PXM_GEMM_L3(CT_, NS_)                                   \
-  switch (flags & 3) {                                          \
-    case 0: PXM_GEMM_L4(CT_, NS_, false, false); break;         \
-    case 1: PXM_GEMM_L4(CT_, NS_, true, false); break;          \
-    case 2: PXM_GEMM_L4(CT_, NS_, false, true); break;          \
-    default: PXM_GEMM_L4(CT_, NS_, true, true); break;          \
-  }
-  if (flags & 4) {
-    PXM_REQUIRE(nslab == 2 && (flags & 3) == 1, "launch_gemm: a pole term outside the Gram list");
-    if (ct == 1) hipExtLaunchKernelGGL((k_sht_gemm<1, 2, 8, 1, 2, true, false, true>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff);
-    else hipExtLaunchKernelGGL((k_sht_gemm<2, 2, 8, 1, 2, true, false, true>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff);
-  } else if (nslab == 2) {
-    if (ct == 1) { PXM_GEMM_L3(1, 2) } else { PXM_GEMM_L3(2, 2) }
+  constexpr int NSET = 2;
+  auto go = [&](auto kernel) { hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff); };
+  if (flags & GEMM_LIST_POLE) {
+    PXM_REQUIRE(nslab == 2 && (flags & (GEMM_LIST_TWO | GEMM_LIST_SCALE)) == GEMM_LIST_TWO, "launch_gemm: a pole term outside the Gram list");
+    if (ct == 1) go(k_sht_gemm<1, 2, NW, RT, NSET, true, false, true>);
+    else go(k_sht_gemm<2, 2, NW, RT, NSET, true, false, true>);
   } else {
-    if (ct == 1) { PXM_GEMM_L3(1, 1) } else { PXM_GEMM_L3(2, 1) }
+    with_gemm_variant(flags, [&](auto two, auto sk) {
+      constexpr bool TWO = decltype(two)::value, SK = decltype(sk)::value;
+      if (nslab == 2) {
+        if (ct == 1) go(k_sht_gemm<1, 2, NW, RT, NSET, TWO, SK>);
+        else go(k_sht_gemm<2, 2, NW, RT, NSET, TWO, SK>);
+      } else {
+        if (ct == 1) go(k_sht_gemm<1, 1, NW, RT, NSET, TWO, SK>);
+        else go(k_sht_gemm<2, 1, NW, RT, NSET, TWO, SK>);
+      }
+    });
   }
-#undef PXM_GEMM_L3
-#undef PXM_GEMM_L4
   PXM_HIP(hipGetLastError());
   return 0;
 }
@@ -647,428 +599,22 @@ int launch_gemm_packed(const GemmTask* d_tasks, int n_tasks, int pk, int flags, 
                        double alg_bytes, double flops, hipStream_t stream, Profiler* prof) {
   if (n_tasks == 0) return 0;
   PXM_REQUIRE(pk == 2 || pk == 4, "launch_gemm_packed: 2 or 4 live columns per slab");
-  dim3 grid(n_tasks), block(512);
+  dim3 grid(n_tasks), block(64 * NW);
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (prof) prof->next(prof->gemm, &ev0, &ev1, alg_bytes, flops, n_tasks);
   GemmAffine aff;
   // look-ahead NSET = 3 (two chunks ahead).  The packed launches carry a quarter of the MFMA work per table byte of the
   // 16-columns-per-slab ones and 44 - 54 VGPRs: with one chunk of look-ahead their waves spent half their cycles in
   // s_waitcnt (SQ_WAIT_INST_ANY 425 M of 825 M wave-cycles, 2.5 TB/s)
-#define PXM_PK_L(PK_, TWO_, SK_) \
-  hipExtLaunchKernelGGL((k_sht_gemm_pk<PK_, 8, 1, 3, TWO_, SK_>), grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff)
-#define PXM_PK_N(PK_)                                     \
-  switch (flags & 3) {                                    \
-    case 0: PXM_PK_L(PK_, false, false); break;           \
-    case 1: PXM_PK_L(PK_, true, false); break;            \
-    case 2: PXM_PK_L(PK_, false, true); break;            \
-    default: PXM_PK_L(PK_, true, true); break;            \
-  }
-  if (pk == 2) { PXM_PK_N(2) } else { PXM_PK_N(4) }
-#undef PXM_PK_N
-#undef PXM_PK_L
+  constexpr int NSET = 3;
+  with_gemm_variant(flags, [&](auto two, auto sk) {
+    constexpr bool TWO = decltype(two)::value, SK = decltype(sk)::value;
+    auto go = [&](auto kernel) { hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, ev0, ev1, 0, d_tasks, X, Y, ncol, col0, aff); };
+    if (pk == 2) go(k_sht_gemm_pk<2, NW, RT, NSET, TWO, SK>);
+    else go(k_sht_gemm_pk<4, NW, RT, NSET, TWO, SK>);
+  });
   PXM_HIP(hipGetLastError());
   return 0;
-}
-
-// ---------------------------------------------------------------------------------------
-// Task lists
-// ---------------------------------------------------------------------------------------
-// slabs 2g, 2g+1 of task g <- one transform (side): operand / output slab offsets for +m / -m, scales, row mask
-static void fill_side(GemmTask& g, int grp, const ShtTables& T, int kind, int m, int ncol, const GemmSide& sd,
-                      int64_t scratch_off, const double* ws_base) {
-  const int s0 = 2 * grp, s1 = 2 * grp + 1;
-  const int xn = sd.x_ncol ? sd.x_ncol : ncol, yn = sd.y_ncol ? sd.y_ncol : ncol;  // doubles per row of the two arrays
-  g.x_off[s0] = sd.x_base + (int64_t)(m + sd.x_L - 1) * sd.x_Rp * xn;
-  g.y_off[s0] = sd.y_base + (int64_t)(m + sd.y_L - 1) * sd.y_Rp * yn;
-  if (T.paired) {
-    if (m == 0) {
-      g.x_off[s1] = g.x_off[s0];
-      g.y_off[s1] = scratch_off;
-    } else {
-      g.x_off[s1] = sd.x_base + (int64_t)(-m + sd.x_L - 1) * sd.x_Rp * xn;
-      g.y_off[s1] = sd.y_base + (int64_t)(-m + sd.y_L - 1) * sd.y_Rp * yn;
-    }
-  } else {
-    g.x_off[s1] = g.x_off[s0];
-    g.y_off[s1] = g.y_off[s0];
-  }
-  g.ks_off[grp] = sd.kscale ? (sd.kscale - ws_base) : 0;
-  g.rs_off[grp] = sd.fuse.rscale ? (sd.fuse.rscale - ws_base) : 0;
-  g.row_lo[grp] = sd.fuse.row_lo;
-  g.row_hi[grp] = sd.fuse.row_hi;
-  g.x2_off[s0] = g.x2_off[s1] = 0;
-  if (sd.fuse.x2_base >= 0) {
-    g.x2_off[s0] = sd.fuse.x2_base + (int64_t)(m + sd.x_L - 1) * sd.x_Rp * xn;
-    g.x2_off[s1] = (T.paired && m != 0) ? sd.fuse.x2_base + (int64_t)(-m + sd.x_L - 1) * sd.x_Rp * xn : g.x2_off[s0];
-  }
-  g.hd_off[s0] = g.hd_off[s1] = 0;
-  g.hd_stride = sd.fuse.hd_stride > 0 ? sd.fuse.hd_stride : ncol;
-  if (sd.fuse.hd_base >= 0) {
-    g.hd_off[s0] = sd.fuse.hd_base + (int64_t)(m + sd.y_L - 1) * sd.y_Rp * g.hd_stride;
-    g.hd_off[s1] = (T.paired && m != 0) ? sd.fuse.hd_base + (int64_t)(-m + sd.y_L - 1) * sd.y_Rp * g.hd_stride : g.hd_off[s0];
-  }
-  (void)kind;
-}
-
-// The tasks of one table block of order m: `tab` its tiled table, kb its start along the el dimension(s), n the extent of
-// its row and contraction dimensions.  par < 0: the block spans the order (n = Rp).  par = 0 / 1: a parity half of the
-// split Gram table (n = Rp / 2) -- an ordinary task on a strided view of the H-layout arrays: a plane [Rp][ncol] of one
-// order is also [Rp / 2][2 ncol], half-row r holding degree 2 r in columns 0 .. ncol - 1 and degree 2 r + 1 in columns
-// ncol .. 2 ncol - 1, so the half of parity par has row pitch 2 ncol and starts par * ncol into the plane; rows,
-// contraction steps and the row mask of the task count half-rows.  (Sides with a support cut or a row mask of their own
-// have no such view: the Gram step has neither.)
-static void append_block_tasks(const ShtTables& T, int kind, int ncol, const GemmSide& side, int64_t scratch_off,
-                               const double* ws_base, std::vector<GemmTask>& tasks, int m, const double* tab, int kb, int n,
-                               int par, int64_t rt_stride_stored = 0, const double* pole = nullptr) {
-  // el_lo: harmonic degrees below it carry no signal for the transform (compact support of a wavelet kernel): the
-  // rows (ring->el kinds) or contraction steps (el->ring kinds) below it are skipped.
-  const bool rows_el = kind_rows_are_el(kind), k_el = kind_k_is_el(kind);
-  const int lo16 = round_down(std::max(side.el_lo, 0), 16);
-  const int rpt = gemm_rows_per_task(ncol);  // row tiles per task
-  const int start = std::max(kb, lo16);
-  if (start >= n) return;
-  // table of this block: [row tiles from (rows_el ? kb : 0)][k chunks of 8 from (k_el ? kb : 0)]
-  // (rt_stride_stored: the block is part of a wider stored matrix -- a diagonal block of the permuted order-0 table)
-  const int64_t rt_stride = rt_stride_stored ? rt_stride_stored : (int64_t)((k_el ? n - kb : n) / 8) * 128;
-  const int k_beg = k_el ? start : 0, k_end = n, row_beg = rows_el ? start : 0;
-  const int64_t tab_skip = (rows_el ? (int64_t)((start - kb) / 16) * rt_stride : 0) + (k_el ? (int64_t)((start - kb) / 8) * 128 : 0);
-  const int n_rt_total = (n - row_beg) / 16;
-  for (int rt = 0; rt < n_rt_total; rt += rpt) {
-    GemmTask g;
-    g.m_unit = T.paired ? m : m + T.L - 1;
-    g.tab_off = (tab + tab_skip + (int64_t)rt * rt_stride) - ws_base;
-    g.rt_stride = rt_stride;
-    for (int s = 0; s < 2; ++s) fill_side(g, s, T, kind, m, ncol, side, scratch_off, ws_base);  // (slab groups 0 and 1 alike)
-    g.nslab = T.paired ? 2 : 1;
-    g.k_beg = k_beg;
-    g.k_end = k_end;
-    g.row0 = row_beg + 16 * rt;
-    g.n_rt = std::min(rpt, n_rt_total - rt);
-    g.sign1 = kind_is_gram(kind) ? 1.0 : ((m & 1) ? -1.0 : 1.0);  // the Gram table is even in m
-    g.x_ncol = side.x_ncol ? side.x_ncol : ncol;
-    g.y_ncol = side.y_ncol ? side.y_ncol : ncol;
-    g.pole_n = g.pole_dx = 0;
-    g.pole_b_off = g.pole_bo_off = 0;
-    if (pole) {  // order-0 half: pole = [n even degrees | n odd degrees] of b
-      g.pole_n = n;
-      g.pole_dx = par ? -g.x_ncol : g.x_ncol;
-      g.pole_b_off = (pole + par * n) - ws_base;
-      g.pole_bo_off = (pole + (1 - par) * n) - ws_base;
-    }
-    if (par >= 0) {
-      for (int s = 0; s < 4; ++s) {
-        g.x_off[s] += par * g.x_ncol;
-        g.y_off[s] += par * g.y_ncol;
-        if (g.x2_off[s]) g.x2_off[s] += par * g.x_ncol;
-        if (g.hd_off[s]) g.hd_off[s] += par * g.hd_stride;
-      }
-      g.x_ncol *= 2;
-      g.y_ncol *= 2;
-      g.hd_stride *= 2;
-      // written rows: the degrees l >= round_down(m, 16) the dense list writes, no others (kb can start lower)
-      for (int grp = 0; grp < 2; ++grp) g.row_lo[grp] = round_down(m, 16) / 2;
-    }
-    tasks.push_back(g);
-  }
-}
-
-static void append_tasks_impl(const ShtTables& T, int kind, int ncol, const GemmSide& side,
-                              int64_t scratch_off, const double* ws_base, std::vector<GemmTask>& tasks) {
-  for (int i = 0; i < T.n_m; ++i) {
-    const int m = T.m_of(i);
-    const double* tab = T.d_tab[kind] + T.m_off[kind][i];
-    const int kb = T.k_beg[kind][i];  // table start of this m along its el dimension(s): multiple of 16
-    if (kind == TAB_GRAM_SPLIT0 && m == 0) {  // the diagonal blocks of [[ee, eo], [oe, oo]], each with its pole term
-      const int Rh = T.Rp / 2;
-      const int64_t rs = (int64_t)(T.Rp / 8) * 128;
-      append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, tab, 0, Rh, 0, rs, T.d_pole);
-      append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, tab + (Rh / 16) * rs + (int64_t)(Rh / 8) * 128, 0, Rh, 1, rs, T.d_pole);
-    } else if (kind_is_gram_split(kind) && T.odd_off[i] >= 0) {  // even-degree half, odd-degree half
-      append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, tab, kb, T.Rp / 2, 0);
-      append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, T.d_tab[kind] + T.odd_off[i], T.odd_k_beg[i], T.Rp / 2, 1);
-    } else {
-      append_block_tasks(T, kind, ncol, side, scratch_off, ws_base, tasks, m, tab, kb, T.Rp, -1);
-    }
-  }
-}
-
-// Packed lists: the tasks of one transform (side_b == nullptr) or of TWO transforms at the same bandlimit that stream the table
-// once (slabs 0, 1 = +-m of side_a, slabs 2, 3 = +-m of side_b).  The support cut of a pair is the smaller of the two: the
-// row masks (ring->el kinds) / zero scale rows (el->ring kinds) of the transform with the narrower support do the rest.
-void append_gemm_tasks_packed(const ShtTables& T, int kind, int ncol, const GemmSide& side_a, const GemmSide* side_b,
-                              int64_t scratch_off, const double* ws_base, std::vector<GemmTask>& tasks) {
-  GemmSide sa = side_a;
-  if (side_b) sa.el_lo = std::min(side_a.el_lo, side_b->el_lo);
-  const size_t first = tasks.size();
-  append_tasks_impl(T, kind, ncol, sa, scratch_off, ws_base, tasks);
-  for (size_t i = first; i < tasks.size(); ++i) {
-    GemmTask& g = tasks[i];
-    const int m = T.paired ? g.m_unit : g.m_unit - (T.L - 1);
-    fill_side(g, 0, T, kind, m, ncol, side_a, scratch_off, ws_base);
-    fill_side(g, 1, T, kind, m, ncol, side_b ? *side_b : side_a, scratch_off, ws_base);
-    g.nslab = side_b ? 4 : 2;
-    g.x_ncol = side_a.x_ncol ? side_a.x_ncol : ncol;  // (the two transforms of a pair share the strides of their arrays)
-    g.y_ncol = side_a.y_ncol ? side_a.y_ncol : ncol;
-    if (!T.paired) {  // all m stored: one slab per transform -- slabs 0 (a) and 1 (b); the kernel's group index is slab >> 1,
-      // so an unpaired packed list carries ONE transform per task
-      g.nslab = 1;
-    }
-  }
-}
-
-void append_gemm_tasks(const ShtTables& T, int kind, int ncol, int64_t x_base, int x_L, int x_Rp,
-                       int64_t y_base, int y_L, int y_Rp, const double* kscale, int64_t scratch_off,
-                       const double* ws_base, std::vector<GemmTask>& tasks, int el_lo, const GemmFuse& fuse) {
-  const GemmSide sd{x_base, y_base, x_L, x_Rp, y_L, y_Rp, kscale, el_lo, fuse};
-  append_tasks_impl(T, kind, ncol, sd, scratch_off, ws_base, tasks);
-}
-
-// ---------------------------------------------------------------------------------------
-// Table construction (setup time)
-// ---------------------------------------------------------------------------------------
-// Ad[i][el][t] = scale * sum_t' Bd[i][t'][el] * Q[par(i)][t'][t]
-__global__ void k_build_fwd(const double* __restrict__ Bd, const double* __restrict__ Qd, double* __restrict__ Ad,
-                            int Rp, int L, double scale, int m0, int spin) {
-  const int i = blockIdx.z;
-  const int el = blockIdx.x * 16 + threadIdx.x, t = blockIdx.y * 16 + threadIdx.y;
-  const int m = m0 + i;
-  const int par = ((m + spin) & 1) ? 1 : 0;  // index 0 = even parity (+1), 1 = odd (-1)
-  const double* B = Bd + (int64_t)i * Rp * Rp;
-  const double* Q = Qd + (int64_t)par * Rp * Rp;
-  double acc = 0;
-  for (int tp = 0; tp < L; ++tp) acc += B[(int64_t)tp * Rp + el] * Q[(int64_t)tp * Rp + t];
-  Ad[(int64_t)i * Rp * Rp + (int64_t)el * Rp + t] = scale * acc;
-}
-
-// Gd[i][r][c] = sum_t Bd[i][t][r] * Bd[i][t][c]   (the per-m Gram matrix of the inverse transform)
-__global__ void k_build_gram(const double* __restrict__ Bd, double* __restrict__ Gd, int Rp, int L) {
-  const int i = blockIdx.z;
-  const int r = blockIdx.x * 16 + threadIdx.x, c = blockIdx.y * 16 + threadIdx.y;
-  const double* B = Bd + (int64_t)i * Rp * Rp;
-  double acc = 0;
-  for (int t = 0; t < L; ++t) acc += B[(int64_t)t * Rp + r] * B[(int64_t)t * Rp + c];
-  Gd[(int64_t)i * Rp * Rp + (int64_t)r * Rp + c] = acc;
-}
-
-// tiled[(rt, kk2, lane, h)] = D[row][k] (transposed = 0) or D[k][row] (transposed = 1), D = dense Rp x Rp.
-// par = 0 / 1: the tiled matrix is the n = Rp / 2 parity half of D, entry [row][k] = D[2 row + par][2 k + par]
-// par = 2: the whole of D with rows and columns permuted by parity, even degrees first: [[ee, eo], [oe, oo]]
-__global__ void k_tile_table(const double* __restrict__ D, double* __restrict__ out, int Rp, int n, int row_beg,
-                             int k_beg, int transposed, int par) {
-  const int nk2 = (n - k_beg) / 8;
-  const int rt = blockIdx.y;
-  const int kk2 = blockIdx.x;
-  const int lane = threadIdx.x >> 1, h = threadIdx.x & 1;
-  int row = row_beg + 16 * rt + (lane & 15);
-  int k = k_beg + 8 * kk2 + 4 * h + (lane >> 4);
-  if (par == 2) {
-    row = row < n / 2 ? 2 * row : 2 * (row - n / 2) + 1;
-    k = k < n / 2 ? 2 * k : 2 * (k - n / 2) + 1;
-  } else if (par >= 0) {
-    row = 2 * row + par;
-    k = 2 * k + par;
-  }
-  const double v = transposed ? D[(int64_t)k * Rp + row] : D[(int64_t)row * Rp + k];
-  out[((int64_t)rt * nk2 + kk2) * 128 + threadIdx.x] = v;
-}
-
-static std::mutex g_tab_mutex;
-static std::map<std::pair<int, int>, ShtTables*> g_tab_cache;
-
-// TAB_GRAM_SPLIT: order 0 dense, the orders m >= 1 as their even-degree and odd-degree halves where that is the cheaper
-// form (sht_core.h), gathered from the dense Gram matrices d_G: the kept entries are the doubles the dense table holds.
-// TAB_GRAM_SPLIT0: the same with order 0 permuted by parity (the same Rp^2 doubles in the same space) and the pole column b
-static int build_gram_split(ShtTables& T, int kind, const double* d_G) {
-  const int Rp = T.Rp, Rh = Rp / 2;
-  PXM_REQUIRE(gram_can_split(T), "build_gram_split: the parity split needs spin-0 tables and Rp % 32 == 0");
-  T.m_off[kind].assign(T.n_m, 0);
-  T.k_beg[kind].assign(T.n_m, 0);
-  T.odd_off.assign(T.n_m, -1);
-  T.odd_k_beg.assign(T.n_m, 0);
-  int64_t total = 0;
-  for (int m = 0; m < T.n_m; ++m) {
-    if (m == 0 || !gram_order_splits(Rp, m)) {  // dense block, as in TAB_GRAM
-      const int kb = round_down(m, 16);
-      T.k_beg[kind][m] = kb;
-      T.m_off[kind][m] = total;
-      total += (int64_t)((Rp - kb) / 16) * ((Rp - kb) / 8) * 128;
-      continue;
-    }
-    for (int par = 0; par < 2; ++par) {
-      const int kb = gram_half_k_beg(m, par);
-      (par ? T.odd_k_beg[m] : T.k_beg[kind][m]) = kb;
-      (par ? T.odd_off[m] : T.m_off[kind][m]) = total;
-      total += (int64_t)((Rh - kb) / 16) * ((Rh - kb) / 8) * 128;
-    }
-  }
-  T.bytes[kind] = (size_t)total * sizeof(double);
-  if (int rc = dev_alloc(&T.d_tab[kind], T.bytes[kind], "ring table")) return rc;
-  if (kind == TAB_GRAM_SPLIT0 && !T.d_pole) {
-    if (int rc = dev_alloc(&T.d_pole, (size_t)Rp * sizeof(double), "pole column of the order-0 Gram block")) return rc;
-    if (!dry_run()) {
-      std::vector<double> B0((size_t)Rp * Rp, 0.0), b(Rp, 0.0);
-      wigner_ring_table(T.L, 0, 0, B0.data(), Rp);  // the last ring is theta = pi
-      for (int l = 0; l < T.L; ++l) b[(l & 1) * Rh + l / 2] = B0[(size_t)(T.L - 1) * Rp + l];
-      if (int rc = dev_upload(T.d_pole, b.data(), b.size() * sizeof(double))) return rc;
-    }
-  }
-  if (dry_run()) return 0;  // layout only: no GPU to tile the tables on
-  for (int m = 0; m < T.n_m; ++m) {
-    const double* src = d_G + (int64_t)m * Rp * Rp;
-    if (T.odd_off[m] < 0) {
-      const int kb = T.k_beg[kind][m];
-      hipLaunchKernelGGL(k_tile_table, dim3((Rp - kb) / 8, (Rp - kb) / 16), dim3(128), 0, 0, src, T.d_tab[kind] + T.m_off[kind][m],
-                         Rp, Rp, kb, kb, 0, (kind == TAB_GRAM_SPLIT0 && m == 0) ? 2 : -1);
-      continue;
-    }
-    for (int par = 0; par < 2; ++par) {
-      const int kb = par ? T.odd_k_beg[m] : T.k_beg[kind][m];
-      hipLaunchKernelGGL(k_tile_table, dim3((Rh - kb) / 8, (Rh - kb) / 16), dim3(128), 0, 0, src,
-                         T.d_tab[kind] + (par ? T.odd_off[m] : T.m_off[kind][m]), Rp, Rh, kb, kb, 0, par);
-    }
-  }
-  PXM_HIP(hipGetLastError());
-  return 0;
-}
-
-static int build_kind(ShtTables& T, int kind, const double* d_B, const double* d_A, const double* d_G) {
-  if (kind_is_gram_split(kind)) return build_gram_split(T, kind, d_G);
-  const int Rp = T.Rp;
-  const bool rows_el = kind_rows_are_el(kind), k_el = kind_k_is_el(kind);
-  T.m_off[kind].resize(T.n_m);
-  T.k_beg[kind].resize(T.n_m);
-  int64_t total = 0;
-  for (int i = 0; i < T.n_m; ++i) {
-    const int elmin = std::max(std::abs(T.m_of(i)), std::abs(T.spin));
-    const int kb = round_down(elmin, 16);  // contraction runs in 16-k chunks, output row tiles are 16 rows
-    T.k_beg[kind][i] = kb;
-    T.m_off[kind][i] = total;
-    total += (int64_t)((rows_el ? Rp - kb : Rp) / 16) * ((k_el ? Rp - kb : Rp) / 8) * 128;
-  }
-  T.bytes[kind] = (size_t)total * sizeof(double);
-  if (int rc = dev_alloc(&T.d_tab[kind], T.bytes[kind], "ring table")) return rc;
-  if (dry_run()) return 0;  // layout only: no GPU to tile the tables on
-  for (int i = 0; i < T.n_m; ++i) {
-    const int kb = T.k_beg[kind][i];
-    const double* src;
-    int transposed;
-    // dense arrays: B[t][el], A[el][t], G[el][el].  el->ring kinds want D[row = t][k = el].
-    if (kind == TAB_INV) { src = d_B; transposed = 0; }
-    else if (kind == TAB_FWD_ADJ) { src = d_A; transposed = 1; }
-    else if (kind == TAB_FWD) { src = d_A; transposed = 0; }
-    else if (kind == TAB_INV_ADJ) { src = d_B; transposed = 1; }
-    else { src = d_G; transposed = 0; }
-    src += (int64_t)i * Rp * Rp;
-    const int row_beg = rows_el ? kb : 0, k_beg = k_el ? kb : 0;
-    dim3 grid((Rp - k_beg) / 8, (Rp - row_beg) / 16), block(128);
-    if (grid.x == 0 || grid.y == 0) continue;
-    hipLaunchKernelGGL(k_tile_table, grid, block, 0, 0, src, T.d_tab[kind] + T.m_off[kind][i], Rp, Rp, row_beg, k_beg,
-                       transposed, -1);
-  }
-  PXM_HIP(hipGetLastError());
-  return 0;
-}
-
-int get_tables(int L, int spin, unsigned kinds_mask, ShtTables** out) {
-  std::lock_guard<std::mutex> lock(g_tab_mutex);
-  int dev = 15;  // (dry-run entries -- fake addresses -- live under a device id no node has: never handed to a real plan)
-  if (!dry_run()) {
-    PXM_HIP(hipGetDevice(&dev));
-    PXM_REQUIRE(dev >= 0 && dev < 15, "get_tables: device index outside [0, 15)");
-  }
-  auto key = std::make_pair(L * 16 + dev, spin);
-  ShtTables* T = nullptr;
-  auto it = g_tab_cache.find(key);
-  if (it != g_tab_cache.end()) T = it->second;
-  else {
-    T = new ShtTables();
-    T->L = L;
-    T->spin = spin;
-    T->Rp = round_up(L, 16);
-    T->paired = (spin == 0);
-    T->n_m = T->paired ? L : 2 * L - 1;
-    g_tab_cache[key] = T;
-  }
-  unsigned missing = 0;
-  for (int k = 0; k < TAB_KINDS; ++k)
-    if ((kinds_mask >> k & 1u) && !T->d_tab[k]) missing |= 1u << k;
-  if (missing && dry_run()) {
-    for (int k = 0; k < TAB_KINDS; ++k)
-      if (missing >> k & 1u) {
-        int rc = build_kind(*T, k, nullptr, nullptr, nullptr);
-        if (rc) return rc;
-      }
-  } else if (missing) {
-    const int Rp = T->Rp;
-    const size_t dense = (size_t)T->n_m * Rp * Rp;
-    std::vector<double> hB(dense, 0.0);
-    const int m0 = T->paired ? 0 : -(L - 1);
-    for (int i = 0; i < T->n_m; ++i) wigner_ring_table(L, spin, m0 + i, hB.data() + (size_t)i * Rp * Rp, Rp);
-    double *d_B = nullptr, *d_A = nullptr, *d_Q = nullptr, *d_G = nullptr;
-    PXM_HIP(hipMalloc(&d_B, dense * sizeof(double)));
-    PXM_HIP(hipMemcpy(d_B, hB.data(), dense * sizeof(double), hipMemcpyHostToDevice));
-    hB.clear();
-    hB.shrink_to_fit();
-    if (missing & ((1u << TAB_FWD) | (1u << TAB_FWD_ADJ))) {
-      std::vector<double> hQ((size_t)2 * Rp * Rp, 0.0);
-      quadrature_gram(L, +1, hQ.data(), Rp);
-      quadrature_gram(L, -1, hQ.data() + (size_t)Rp * Rp, Rp);
-      PXM_HIP(hipMalloc(&d_Q, hQ.size() * sizeof(double)));
-      PXM_HIP(hipMemcpy(d_Q, hQ.data(), hQ.size() * sizeof(double), hipMemcpyHostToDevice));
-      PXM_HIP(hipMalloc(&d_A, dense * sizeof(double)));
-      dim3 grid(Rp / 16, Rp / 16, T->n_m), block(16, 16);
-      hipLaunchKernelGGL(k_build_fwd, grid, block, 0, 0, d_B, d_Q, d_A, Rp, L, 2.0 * M_PI / (2 * L - 1), m0, spin);
-      PXM_HIP(hipGetLastError());
-    }
-    if (missing & ((1u << TAB_GRAM) | (1u << TAB_GRAM_SPLIT) | (1u << TAB_GRAM_SPLIT0))) {
-      PXM_HIP(hipMalloc(&d_G, dense * sizeof(double)));
-      dim3 grid(Rp / 16, Rp / 16, T->n_m), block(16, 16);
-      hipLaunchKernelGGL(k_build_gram, grid, block, 0, 0, d_B, d_G, Rp, L);
-      PXM_HIP(hipGetLastError());
-    }
-    for (int k = 0; k < TAB_KINDS; ++k)
-      if (missing >> k & 1u) {
-        int rc = build_kind(*T, k, d_B, d_A, d_G);
-        if (rc) return rc;
-      }
-    PXM_HIP(hipDeviceSynchronize());
-    PXM_HIP(hipFree(d_B));
-    if (d_A) PXM_HIP(hipFree(d_A));
-    if (d_Q) PXM_HIP(hipFree(d_Q));
-    if (d_G) PXM_HIP(hipFree(d_G));
-  }
-  *out = T;
-  return 0;
-}
-
-void retain_tables(ShtTables* T) {
-  std::lock_guard<std::mutex> lock(g_tab_mutex);
-  if (T) ++T->refs;
-}
-void release_tables(ShtTables* T) {
-  std::lock_guard<std::mutex> lock(g_tab_mutex);
-  if (T && T->refs > 0) --T->refs;
-}
-int64_t tables_trim() {
-  std::lock_guard<std::mutex> lock(g_tab_mutex);
-  int64_t freed = 0;
-  for (auto it = g_tab_cache.begin(); it != g_tab_cache.end();) {
-    ShtTables* T = it->second;
-    // (a dry-run pass only drops its own entries -- device id 15 -- and leaves the real cache alone)
-    if (T->refs > 0 || (dry_run() && it->first.first % 16 != 15)) {
-      ++it;
-      continue;
-    }
-    for (int k = 0; k < TAB_KINDS; ++k) {
-      if (T->d_tab[k]) deferred_free(T->d_tab[k]);
-      freed += (int64_t)T->bytes[k];
-    }
-    if (T->d_pole) deferred_free(T->d_pole);
-    delete T;
-    it = g_tab_cache.erase(it);
-  }
-  drain_deferred();
-  return freed;
 }
 
 }  // namespace pxm

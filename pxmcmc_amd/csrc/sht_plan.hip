@@ -52,8 +52,8 @@ int pxm_sht_plan_create(int L, int spin, int max_chains, unsigned flags, pxm_sht
   for (int k = 0; k < 4; ++k) {
     std::vector<GemmTask> v;
     const bool e2r = kind_el_to_ring(k);
-    append_gemm_tasks(*p->T, k, p->ncol, e2r ? p->offH : p->offG, L, p->Rp, e2r ? p->offG : p->offH, L, p->Rp, nullptr,
-                      p->offS, p->ws, v);
+    const GemmSide side{e2r ? p->offH : p->offG, e2r ? p->offG : p->offH, L, p->Rp, L, p->Rp, nullptr, 0, GemmFuse()};
+    append_gemm_tasks(*p->T, k, p->ncol, side, p->offS, p->ws, v);
     if ((rc = upload_tasks(v, p->T->paired, &p->tl[k], {L}, p->ncol, p->ws, "SHT stage"))) return rc;
   }
   if (rec_wanted(L, spin, max_chains) && (rc = rec_tables_create(L, spin, max_chains, p->Rp, p->ncol, &p->rec))) return rc;

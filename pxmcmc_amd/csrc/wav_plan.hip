@@ -89,7 +89,7 @@ int pxm::wav_packed_lists(const pxm_wav_plan_s* p, int which, int kind, const Wl
 // one L-level stage (spin 0 pairs +-m on one table, spin s != 0 stores every m: unpaired lists, one slab per task)
 static int wav_level_list(pxm_wav_plan_s* p, int kind, int64_t x, int64_t y, const GemmFuse& fuse, TaskList* tl, const char* name) {
   std::vector<GemmTask> v;
-  append_gemm_tasks(*p->TL, kind, p->ncol, x, p->L, p->Rp, y, p->L, p->Rp, nullptr, p->offS, p->ws, v, 0, fuse);
+  append_gemm_tasks(*p->TL, kind, p->ncol, GemmSide{x, y, p->L, p->Rp, p->L, p->Rp, nullptr, 0, fuse}, p->offS, p->ws, v);
   return upload_tasks(v, p->TL->paired, tl, {p->L}, p->ncol, p->ws, name);
 }
 
@@ -185,9 +185,7 @@ static int wav_plan_create_impl(const char* who, int L, double B, int J_min, int
   std::vector<GemmTask>* lists[4] = {&v_syn_fwd, &v_adj_fwdadj, &v_ana_inv, &v_anadj_invadj};
   for (int s = 0; s < p->nsc; ++s) {
     for (int w = 0; w < 4; ++w) {
-      const GemmSide g = wav_side(p, s, w);
-      append_gemm_tasks(*p->T[s], kinds[w], p->ncol, g.x_base, g.x_L, g.x_Rp, g.y_base, g.y_L, g.y_Rp, g.kscale, p->offS,
-                        p->ws, *lists[w], g.el_lo, g.fuse);
+      append_gemm_tasks(*p->T[s], kinds[w], p->ncol, wav_side(p, s, w), p->offS, p->ws, *lists[w]);
     }
     p->table_bytes[0] += p->T[s]->bytes[TAB_FWD];
     p->table_bytes[1] += p->T[s]->bytes[TAB_FWD_ADJ];
@@ -238,7 +236,7 @@ static int wav_plan_create_impl(const char* who, int L, double B, int J_min, int
 int pxm::wav_make_gram_lists(pxm_wav_plan_s* p) {
   if (p->gram.d) return 0;
   int rc;
-  // spin 0 and Rp % 32 == 0: the Gram table without its structurally zero half, order 0 included (sht_core.h:
+  // spin 0 and Rp % 32 == 0: the Gram table without its structurally zero half, order 0 included (sht_tables.h:
   // TAB_GRAM_SPLIT0).  The cross-check and A/B switches: PXM_GRAM_SPLIT=1 keeps order 0 dense (TAB_GRAM_SPLIT),
   // PXM_GRAM_SPLIT=0 keeps the dense list
   const char* split_env = getenv("PXM_GRAM_SPLIT");
@@ -251,12 +249,9 @@ int pxm::wav_make_gram_lists(pxm_wav_plan_s* p) {
   fz.x2_base = p->offHB;
   fz.hd_base = p->offHDc;
   fz.hd_stride = 2;
-  append_gemm_tasks(*p->TL, kind, p->ncol, p->offHA, p->L, p->Rp, p->offHL, p->L, p->Rp, nullptr, p->offS, p->ws, v, 0, fz);
+  append_gemm_tasks(*p->TL, kind, p->ncol, GemmSide{p->offHA, p->offHL, p->L, p->Rp, p->L, p->Rp, nullptr, 0, fz}, p->offS, p->ws, v);
   if ((rc = upload_tasks(v, p->TL->paired, &p->gram, {p->L}, p->ncol, p->ws, "Gram step"))) return rc;
-  p->gram.gram = true;
-  p->gram.gram_table_bytes = (double)p->TL->bytes[kind];
-  p->gram.gram_pole = kind == TAB_GRAM_SPLIT0;
-  p->gram.gram_stream_bytes = p->gram.gram_table_bytes - (p->gram.gram_pole ? 4.0 * p->Rp * p->Rp : 0.0);  // (two Rp/2 x Rp/2 blocks of doubles)
+  tasklist_set_gram(&p->gram, *p->TL, kind);
   return wav_level_list(p, TAB_INV_ADJ, p->offGD, p->offHD, GemmFuse(), &p->adj_invadj_D, "inverse-adjoint of the data rings");
 }
 

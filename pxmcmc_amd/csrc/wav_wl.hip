@@ -65,12 +65,12 @@ static int wl_build(const pxm_wav_plan_s* p, WlAttach* w) {
     std::vector<GemmTask> v;
     GemmFuse sum2;
     sum2.x2_base = p->offHB;
-    append_gemm_tasks(*w->T2, TAB_INV, p->ncol, p->offHA, p->L, p->Rp, p->offG2, p->L, p->Rp, w->d_wlk, p->offS, p->ws, v, 0, sum2);
+    append_gemm_tasks(*w->T2, TAB_INV, p->ncol, GemmSide{p->offHA, p->offG2, p->L, p->Rp, p->L, p->Rp, w->d_wlk, 0, sum2}, p->offS, p->ws, v);
     if ((rc = upload_tasks(v, false, &w->inv, {p->L}, p->ncol, p->ws, "weak-lensing spin-2 inverse"))) return rc;
     v.clear();
     GemmFuse rs;
     rs.rscale = w->d_wlk;
-    append_gemm_tasks(*w->T2, TAB_INV_ADJ, p->ncol, p->offG2, p->L, p->Rp, p->offHL, p->L, p->Rp, nullptr, p->offS, p->ws, v, 0, rs);
+    append_gemm_tasks(*w->T2, TAB_INV_ADJ, p->ncol, GemmSide{p->offG2, p->offHL, p->L, p->Rp, p->L, p->Rp, nullptr, 0, rs}, p->offS, p->ws, v);
     if ((rc = upload_tasks(v, false, &w->invadj, {p->L}, p->ncol, p->ws, "weak-lensing spin-2 inverse-adjoint"))) return rc;
   }
   if (w->twin_s < 0) return 0;

@@ -1,4 +1,4 @@
-"""The ring-space MYULA step on the Gram list with order 0 split as well (csrc/sht_core.h: TAB_GRAM_SPLIT0: two half tasks
+"""The ring-space MYULA step on the Gram list with order 0 split as well (csrc/sht_tables.h: TAB_GRAM_SPLIT0: two half tasks
 on the parity-permuted order-0 block plus the rank-one pole term) against the list with order 0 dense (PXM_GRAM_SPLIT=1),
 the dense list (PXM_GRAM_SPLIT=0) and the oracle's literal loop, on the inputs of tests/test_gpu_gram_split.py.
 

@@ -1,4 +1,4 @@
-"""The ring-space MYULA step on the parity-split Gram list (csrc/sht_core.h: TAB_GRAM_SPLIT) against the oracle's literal
+"""The ring-space MYULA step on the parity-split Gram list (csrc/sht_tables.h: TAB_GRAM_SPLIT) against the oracle's literal
 loop and against the dense list (PXM_GRAM_SPLIT=0) on the same inputs.
 
 Shapes: L = 32 (one k-chunk pair per half, kb_p = 0 throughout), L = 64 (kb_p steps from 0 to 16 at m = 31 .. 33,

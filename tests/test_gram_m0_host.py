@@ -1,4 +1,4 @@
-"""CPU-side checks of the order-0 halves of the split Gram list (csrc/sht_core.h: TAB_GRAM_SPLIT0): the rank-one
+"""CPU-side checks of the order-0 halves of the split Gram list (csrc/sht_tables.h: TAB_GRAM_SPLIT0): the rank-one
 cross-parity part of the oracle's order-0 Gram block that the pole term rests on, a numpy model of the two half
 products plus the pole term, and the address ranges of the three Gram lists (dry-run plans)."""
 import functools

@@ -1,4 +1,4 @@
-"""CPU-side checks of the parity-split Gram table (csrc/sht_core.h: TAB_GRAM_SPLIT): the structure of the oracle's Gram
+"""CPU-side checks of the parity-split Gram table (csrc/sht_tables.h: TAB_GRAM_SPLIT): the structure of the oracle's Gram
 matrix that the split rests on, the address ranges of the split and dense Gram lists (dry-run plans), the stored size."""
 import functools
 
