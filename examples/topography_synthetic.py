@@ -7,6 +7,10 @@ experiments/earthtopography/main.py:72-185 on synthetic data (the ETOPO1 file ne
     -> credible-interval maps of the saved samples.
 
     python examples/topography_synthetic.py --L 32 --nsamples 50 --ngap 100 --chains 4 --outdir /tmp
+
+Both routes write the 95 % credible-interval map of chain 0 as ``*_ci.npy``.  ``--summary image --summary-alpha A`` keeps no
+chain and writes the (1 - A) map from the streaming summary of the images instead: at A = 0.05, the alpha of the chain route,
+the two files are equal.
 """
 import argparse
 import copy
@@ -76,11 +80,15 @@ def main(argv=None):
                     help="estimate the regularisation strength by SAPG first and sample with mu_hat = mu * theta_hat")
     ap.add_argument("--sapg-warmup", type=int, default=100, help="--estimate-mu: MYULA iterations before theta moves")
     ap.add_argument("--sapg-iters", type=int, default=600, help="--estimate-mu: iterations with a moving theta")
-    ap.add_argument("--summary", action="store_true",
+    ap.add_argument("--summary", nargs="?", const="image", default=None, choices=("image",),
                     help="accumulate the posterior mean / standard deviation / R-hat on the GPU instead of saving the chain")
+    ap.add_argument("--summary-alpha", type=float, default=None,
+                    help="with --summary: also keep the per-pixel tails that give the (1 - alpha) credible-interval map exactly")
     ap.add_argument("--outdir", type=str, default=".")
     ap.add_argument("--jobid", type=str, default="0")
     args = ap.parse_args(argv)
+    if args.summary_alpha is not None and not args.summary:
+        ap.error("--summary-alpha needs --summary")
 
     L, B, J_min, setting = args.L, 1.5, 2, args.setting  # B, J_min as in main.py:72-74
 
@@ -129,7 +137,7 @@ def main(argv=None):
     if args.estimate_mu:
         regulariser, params = estimate_mu(forwardop, regulariser, params, delta_myula, args,
                                           start_point.astype(complex) if spin else start_point)
-    mcmc = cls(forwardop, regulariser, params, nchains=args.chains, summary="image" if args.summary else None)
+    mcmc = cls(forwardop, regulariser, params, nchains=args.chains, summary=args.summary, summary_alpha=args.summary_alpha)
     if args.map_start:
         start_point = map_start(forwardop, regulariser, params, L_g, start_point.astype(complex) if spin else start_point)
     start = datetime.now()
@@ -139,12 +147,12 @@ def main(argv=None):
     path = save_mcmc(mcmc, params, args.outdir, filename=f"{args.algo}_{setting}_{args.jobid}", L=L, B=B, J_min=J_min,
                      sigma=args.sigma, nparams=forwardop.nparams, setting=setting, time=str(elapsed), chains=args.chains,
                      **({"spin": spin} if spin else {}))
+    base = os.path.join(args.outdir, f"{args.algo}_{setting}_{args.jobid}")
     if args.summary:
         summ = mcmc.summary["image"]
         mean, std = summ.pooled_mean().cpu().numpy(), np.sqrt(summ.pooled_variance().cpu().numpy())
         if spin == 0:
             mean = mean.real
-        base = os.path.join(args.outdir, f"{args.algo}_{setting}_{args.jobid}")
         np.save(base + "_mean.npy", mean)
         np.save(base + "_std.npy", std)
         if args.chains > 1:
@@ -153,12 +161,20 @@ def main(argv=None):
         rel = np.sqrt(np.mean(np.abs(mean - truth) ** 2)) / np.sqrt(np.mean(np.abs(truth) ** 2))
         print(f"saved {path} and {base}_mean.npy / _std.npy; {mcmc.niter} iterations x {args.chains} chain(s) in {elapsed}; "
               f"posterior-mean error {rel:.3f} (noise {args.sigma:.3f}); median posterior std {np.median(std):.3f}")
-        return path, rel, std  # (no chain, so no quantile map: the third item is the posterior standard deviation)
+        if args.summary_alpha is None:
+            return path, rel, std  # (no chain and no tails, so no quantile map: the third item is the posterior standard deviation)
+        # the map the chain route below writes (chain 0, real part), from the tails the summary kept instead of a chain
+        ci = summ.credible_interval_range()[0].cpu().numpy().real
+        np.save(base + "_ci.npy", ci)
+        print(f"{base}_ci.npy: median {100 * (1 - args.summary_alpha):g}% CI width {np.median(ci):.3f} "
+              f"({summ.tail_bytes() / 2 ** 20:.1f} MiB of tails)")
+        return path, rel, ci
     chain = mcmc.chain if args.chains == 1 else mcmc.chain[0]
     images = chain_to_images(chain, forwardop.transform)  # every saved sample mapped to the sphere
     if spin == 0:
         images = images.real
     ci = credible_interval_range(images.real)  # (spin S: of the real part, e.g. Q of Q + iU)
+    np.save(base + "_ci.npy", ci)
     mean = images.mean(axis=0)
     rel = np.sqrt(np.mean(np.abs(mean - truth) ** 2)) / np.sqrt(np.mean(np.abs(truth) ** 2))
     print(f"saved {path}; {mcmc.niter} iterations x {args.chains} chain(s) in {elapsed}; "

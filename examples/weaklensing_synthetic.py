@@ -115,7 +115,7 @@ def build_sampler(args, forward_operator, prior, params, space):
     "state" for the harmonic posterior, whose transform has no image) and "chain" leaves ``track``"""
     if args.summary:
         params.track = [t for t in params.track if t != "chain"]
-    kw = dict(nchains=args.chains, seed=args.seed, summary=space if args.summary else None)
+    kw = dict(nchains=args.chains, seed=args.seed, summary=space if args.summary else None, summary_alpha=args.summary_alpha)
     if args.algo == "myula":
         return MYULA(forward_operator, prior, params, **kw)
     if args.algo == "pxmala":
@@ -126,7 +126,8 @@ def build_sampler(args, forward_operator, prior, params, space):
 
 
 def summary_maps(args, mcmc, space, path):
-    """--summary: pooled mean and standard deviation of ``space`` over every chain, written beside the run; max R-hat"""
+    """--summary: pooled mean and standard deviation of ``space`` over every chain, written beside the run; max R-hat; with
+    --summary-alpha the (1 - alpha) credible-interval map of chain 0 (per real component), from the tails the summary kept"""
     summ = mcmc.summary[space]
     mean, std = summ.pooled_mean().cpu().numpy(), np.sqrt(summ.pooled_variance().cpu().numpy())
     base = os.path.splitext(path)[0]
@@ -136,6 +137,10 @@ def summary_maps(args, mcmc, space, path):
         rmax, nundef = summ.max_rhat()
         print(f"max R-hat over the {space} ({args.chains} chains): {rmax:.4f} ({nundef} components undefined)")
     print(f"posterior mean and standard deviation of the {space}: {base}_mean.npy, {base}_std.npy")
+    if args.summary_alpha is not None:
+        ci = summ.credible_interval_range()[0].cpu().numpy()
+        np.save(base + "_ci.npy", ci)
+        print(f"{100 * (1 - args.summary_alpha):g}% credible-interval map of the {space} (chain 0): {base}_ci.npy")
     return mean
 
 
@@ -161,11 +166,18 @@ def main(argv=None):
                     help="estimate the regularisation strength by SAPG first and sample with mu_hat = mu * theta_hat")
     ap.add_argument("--sapg-warmup", type=int, default=100, help="--estimate-mu: MYULA iterations before theta moves")
     ap.add_argument("--sapg-iters", type=int, default=600, help="--estimate-mu: iterations with a moving theta")
-    ap.add_argument("--summary", action="store_true",
-                    help="accumulate the posterior mean / standard deviation / R-hat on the GPU instead of saving the chain")
+    ap.add_argument("--summary", nargs="?", const=True, default=None, choices=("image", "state"),
+                    help="accumulate the posterior mean / standard deviation / R-hat on the GPU instead of saving the chain: "
+                         "of the image, or with --harmonic of the state (the value may be left out; the other one is an error)")
+    ap.add_argument("--summary-alpha", type=float, default=None,
+                    help="with --summary: also keep the per-element tails that give the (1 - alpha) credible-interval map exactly")
     ap.add_argument("--harmonic", action="store_true",
                     help="harmonic-space posterior: WeakLensingHarmonic + harmonic wavelets + L1, started from sks_estimate")
     args = ap.parse_args(argv)
+    if args.summary_alpha is not None and not args.summary:
+        ap.error("--summary-alpha needs --summary")
+    if args.summary not in (None, True, "state" if args.harmonic else "image"):
+        ap.error("--summary %s: the summary is of the %s" % (args.summary, "state with --harmonic" if args.harmonic else "image without --harmonic"))
 
     L, B, J_min, setting = args.L, 2, 2, args.setting  # main.py:85-88
     if args.harmonic:

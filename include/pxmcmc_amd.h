@@ -502,6 +502,37 @@ int64_t pxm_moments_scratch_doubles(int64_t m);
 int pxm_moments_finalize(const int64_t* count, const double* mean, const double* m2, int64_t m, int C, double* pooled_mean,
                          double* pooled_var, double* rhat, double* stats, double* scratch, pxm_stream_t stream);
 
+/* ---- exact streaming credible intervals -----------------------------------------------------
+ * Replace np.quantile(chain, (alpha / 2, 1 - alpha / 2), axis=0) of credible_interval_range (pxmcmc/uncertainty.py:7-16),
+ * which needs every saved sample, by the k smallest and the k largest samples per chain and element, kept on the device.
+ * With N the number of saves declared before the run and (i, g) = split(q, n) the arithmetic of pxm_quantile_range,
+ * k = min(N, max(i_lo(N) + 2, N - i_hi(N))) slots per tail hold the order statistics numpy's linear quantile needs at
+ * every sample count n <= N and every alpha' <= alpha.  State, caller-owned: lo, hi float64 [C][k][m] (slot-major; each a
+ * binary heap over its slots, ordered by the 64-bit key of pxm_quantile_range, slot 0 the threshold: the largest of lo,
+ * the smallest of hi), thr_lo, thr_hi float64 [C][m], copies of the thresholds, and stage float64 [C][B][m], a ring of
+ * the last saves: they are merged into the heaps B at a time, which touches each cache line of a tail once per B saves.
+ * No initialisation is needed.  pxm_tails_buffer_doubles: doubles of each of lo and hi; pxm_tails_stage_doubles: doubles
+ * of stage (-1: bad arguments or overflow). */
+int64_t pxm_tails_buffer_doubles(int64_t m, int C, int64_t k);
+int64_t pxm_tails_stage_doubles(int64_t m, int C);
+/* One save: x as for pxm_moments_update (x_stride 1: float64 [C][m]; 2: the real parts of complex128 [C][m]).  count int64
+ * [C] is the number of samples BEFORE this one and is only read: queue the call before the pxm_moments_update of the same
+ * sample, which advances it.  count[c] < k: the sample goes to slot count[c] of both heaps.  Later it goes to row
+ * (count[c] - k) % B of the ring, and the save that fills the ring merges it: a sample between the two thresholds costs
+ * no store, one beyond a threshold replaces it and sifts down.  A masked-out chain (mask int32 [C], NULL: every chain)
+ * and a chain with count[c] >= nsamples are not touched.  One launch, no allocation, no synchronisation:
+ * graph-capturable.  x, thr_lo and thr_hi must be 16-byte aligned. */
+int pxm_tails_update(const double* x, int x_stride, const int64_t* count, double* lo, double* hi, double* thr_lo, double* thr_hi,
+                     double* stage, const int* mask, int64_t m, int C, int64_t k, int64_t nsamples, pxm_stream_t stream);
+/* Read-out after the run: q_lo, q_hi float64 [C][m], numpy's linear quantiles at alpha / 2 and 1 - alpha / 2 of the
+ * count[c] samples of every chain and element, bit for bit (exact order statistics of each tail together with the rows
+ * of the ring not merged yet, by radix select, numpy's lerp); NaN for a chain without samples.  Nothing is written to the
+ * state.  alpha may be any value whose order statistics lie inside the tails (every alpha up to the one k was sized for).
+ * The counts are read back (the call synchronises the stream); an alpha the tails do not cover, or a chain with
+ * count[c] > nsamples, is an error. */
+int pxm_tails_quantiles(const int64_t* count, const double* lo, const double* hi, const double* stage, int64_t m, int C, int64_t k,
+                        int64_t nsamples, double alpha, double* q_lo, double* q_hi, pxm_stream_t stream);
+
 /* ---- weak-lensing measurement helpers (pxmcmc/measurements.py:151-171, 242-304) --------- */
 /* out = flm .* kernel with entries [0,4) zeroed: harmonic_mapping (:162-171). kernel: [L*L] */
 int pxm_wl_harmonic_mapping(const void* flm, const double* kernel, void* out, int64_t n, int C,

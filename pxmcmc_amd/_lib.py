@@ -55,6 +55,10 @@ SIGNATURES = {
     "pxm_moments_update": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_vp]),
     "pxm_moments_scratch_doubles": (c_i64, [c_i64]),
     "pxm_moments_finalize": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pxm_tails_buffer_doubles": (c_i64, [c_i64, c_int, c_i64]),
+    "pxm_tails_stage_doubles": (c_i64, [c_i64, c_int]),
+    "pxm_tails_update": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_i64, c_vp]),
+    "pxm_tails_quantiles": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_i64, c_dbl, c_vp, c_vp, c_vp]),
     "pxm_sht_uses_recursion": (c_int, [c_vp]),
     "pxm_rec_reduce_selftest": (c_int, [c_vp]),
     "pxm_sht_plan_create": (c_int, [c_int, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),

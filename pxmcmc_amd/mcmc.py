@@ -28,7 +28,11 @@ Extensions (all optional, defaults reproduce the reference's one-chain behaviour
   R-hat across the batch; DESIGN.md section 15).  ``"state"`` is the sampled vector as ``chain`` would hold it;
   ``"image"`` is ``transform.inverse`` of it in the synthesis setting and the state itself in the analysis setting.  After
   ``run()`` the summaries are in ``self.summary[space]``.  With ``"chain"`` left out of ``track`` no state is copied to the
-  host during the run.
+  host during the run;
+* ``summary_alpha`` -- ``None`` (default) or alpha in (0, 1]; needs ``summary``.  The summaries also keep the
+  ``tail_capacity(alpha, nsamples)`` smallest and largest saved samples of every element, and
+  ``self.summary[space].credible_interval_range()`` then gives, per chain, the (1 - alpha) credible-interval map the
+  reference computes from the saved chain (pxmcmc/uncertainty.py:7-16), exactly.
 
 SKROCK (pxmcmc/mcmc.py:292-383) follows the published recursion (Pereyra, Vargas-Mieles & Zygalakis 2020), which
 differs from the reference's literal code for s >= 2 (see :class:`SKROCK`); it takes the keywords above except
@@ -102,7 +106,7 @@ class PxMCMC:
     """
 
     def __init__(self, forward, prior, mcmcparams=PxMCMCParams(), nchains=1, rng="philox", seed=0, chain_offset=0,
-                 use_graph=True, ring_shortcut=True, real_pairs=True, noise_bits=64, summary=None):
+                 use_graph=True, ring_shortcut=True, real_pairs=True, noise_bits=64, summary=None, summary_alpha=None):
         self.forward = forward
         self.prior = prior
         for attr in mcmcparams.__dict__.keys():
@@ -129,6 +133,13 @@ class PxMCMC:
         self._summary_spaces = self._summary_arg(summary)
         self.summary = {} if self._summary_spaces else None
         self._summary_plan = None
+        if summary_alpha is not None:
+            from .uncertainty import tail_capacity
+
+            if not self._summary_spaces:
+                raise ValueError("summary_alpha needs summary: the tails are part of the streaming summaries")
+            tail_capacity(summary_alpha, self.nsamples)  # (validates alpha and nsamples)
+        self.summary_alpha = None if summary_alpha is None else float(summary_alpha)
         self._initialise_tracking_arrays()
 
     def run(self, start_point=None):
@@ -184,7 +195,7 @@ class PxMCMC:
                     S = X
                 S, cplx = self._summary_image(tr, S), True
             if sp not in self.summary:
-                self.summary[sp] = PosteriorSummary(self.nchains, S.shape[1], cplx)
+                self.summary[sp] = PosteriorSummary(self.nchains, S.shape[1], cplx, alpha=self.summary_alpha, nsamples=self.nsamples)
             self.summary[sp].update(S, logpi=ops.as_device(logPi), mask=mask)
 
     # ---- device-side pieces -----------------------------------------------------------

@@ -447,6 +447,55 @@ def moments_finalize(count, mean, m2, rhat=True):
     return pm, pv, rh, st
 
 
+def _tails_state(fn, lo, hi, thr_lo, thr_hi, stage, count):
+    """argument checks of the tails entry points -> (C, k, m)"""
+    if not (isinstance(lo, torch.Tensor) and lo.dim() == 3):
+        raise TypeError("%s: lo must be a float64 [C, k, m] device tensor" % fn)
+    C_, k, m = lo.shape
+    for t, dt, shape in ((count, torch.int64, (C_,)), (lo, _REAL, (C_, k, m)), (hi, _REAL, (C_, k, m)), (thr_lo, _REAL, (C_, m)),
+                         (thr_hi, _REAL, (C_, m)), (stage, _REAL, (C_, tails_stage_depth(), m))):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError("%s: count int64 [C], lo / hi contiguous float64 [C, k, m], thr_lo / thr_hi contiguous float64 [C, m] "
+                            "and stage contiguous float64 [C, %d, m] device tensors are expected" % (fn, tails_stage_depth()))
+    if int(lib.pxm_tails_buffer_doubles(m, C_, k)) != lo.numel():
+        raise ValueError("%s: bad tail shape [%d, %d, %d]" % (fn, C_, k, m))
+    return C_, k, m
+
+
+def tails_stage_depth():
+    """B: the saves ``tails_update`` stages in its ring ``stage`` float64 [C, B, m] between two merges into the heaps"""
+    return int(lib.pxm_tails_stage_doubles(1, 1))
+
+
+def tails_update(X, count, lo, hi, thr_lo, thr_hi, stage, nsamples, mask=None):
+    """One save into the per-element tail heaps, in place: ``lo`` / ``hi`` float64 [C, k, m] keep the k
+    smallest / largest samples, ``thr_lo`` / ``thr_hi`` [C, m] their thresholds, ``stage`` [C, B, m] (:func:`tails_stage_depth`)
+    the saves not merged into them yet; ``X`` as for :func:`moments_update`.  ``count``
+    int64 [C] is the number of samples before this one and is not written: call this before the ``moments_update`` of the same
+    sample.  ``nsamples`` is the number of saves k was sized for (:func:`pxmcmc_amd.uncertainty.tail_capacity`); a chain
+    that has reached it, or that ``mask`` (int32 [C]) switches off, is left untouched.  No allocation, no synchronisation:
+    the call can be captured in a HIP graph."""
+    C_, k, m = _tails_state("tails_update", lo, hi, thr_lo, thr_hi, stage, count)
+    x, xs = _moments_rows(X, C_, m)
+    if mask is not None and (mask.dtype != torch.int32 or tuple(mask.shape) != (C_,) or not mask.is_cuda or not mask.is_contiguous()):
+        raise TypeError("tails_update: mask must be a contiguous int32 [C] device tensor")
+    check(lib.pxm_tails_update(_p(x), xs, _p(count), _p(lo), _p(hi), _p(thr_lo), _p(thr_hi), _p(stage), _p(mask), m, C_, k, int(nsamples),
+                               _stream()))
+
+
+def tails_quantiles(count, lo, hi, stage, nsamples, alpha):
+    """Read-out of the tail heaps of :func:`tails_update` -> (q_lo, q_hi) float64 [C, m] on the device: numpy's linear
+    quantiles at ``alpha / 2`` and ``1 - alpha / 2`` of every chain's samples (NaN for a chain without any).  Raises PxmError
+    when the tails do not hold the order statistics ``alpha`` needs, or a chain saw more than ``nsamples`` saves."""
+    C_, k, m = _tails_state("tails_quantiles", lo, hi, None, None, stage, count)
+    q_lo = torch.empty((C_, m), dtype=_REAL, device=lo.device)
+    q_hi = torch.empty_like(q_lo)
+    check(lib.pxm_tails_quantiles(_p(count), _p(lo), _p(hi), _p(stage), m, C_, k, int(nsamples), float(alpha), _p(q_lo), _p(q_hi), _stream()))
+    return q_lo, q_hi
+
+
 def reduce_l2(preds, data, invcov):
     """vdot(d, invcov d), d = data - preds (pxmcmc/mcmc.py:78-79) -> complex128 [C]."""
     p, _ = _batched(as_device(preds))

@@ -13,6 +13,7 @@ import os
 import numpy as np
 
 _SUMMARY_FIELDS = ("count", "mean", "m2", "best", "best_logpi")  # uncertainty.PosteriorSummary.to_host()
+_TAIL_FIELDS = ("q_lo", "q_hi")  # ... of a summary built with alpha (its ``alpha`` becomes the attribute summary_alpha)
 
 _DATASETS = (
     ("logPi", "logposterior", None),
@@ -39,12 +40,16 @@ def _attr_value(v):
 
 def _summary_datasets(mcmc):
     """[(name, array)] of a sampler run with ``summary=``: ``summary_<space>_{count,mean,m2,best,best_logpi}`` (the raw
-    accumulators, real-component layout; extension -- a run without a summary writes none of them)"""
-    out = []
+    accumulators, real-component layout; extension -- a run without a summary writes none of them), and with
+    ``summary_alpha`` the quantile maps ``summary_<space>_{q_lo,q_hi}``; {"summary_alpha": alpha} then, else {}.  A summary
+    whose tails cannot be read out (``PosteriorSummary.to_host`` warns) is written without the maps and the attribute."""
+    out, attrs = [], {}
     for space, summ in (getattr(mcmc, "summary", None) or {}).items():
         host = summ.to_host()
-        out += [(f"summary_{space}_{k}", host[k]) for k in _SUMMARY_FIELDS if k in host]
-    return out
+        out += [(f"summary_{space}_{k}", host[k]) for k in _SUMMARY_FIELDS + _TAIL_FIELDS if k in host]
+        if "alpha" in host:
+            attrs["summary_alpha"] = float(host["alpha"])
+    return out, attrs
 
 
 def save_mcmc(mcmc, params, outpath, filename="outputs", **kwargs):
@@ -53,8 +58,9 @@ def save_mcmc(mcmc, params, outpath, filename="outputs", **kwargs):
     dataset; runtime parameters and ``**kwargs`` are attributes.  Returns the path written.
     """
     present = [(attr, name, dtype) for attr, name, dtype in _DATASETS if hasattr(mcmc, attr)]
-    summaries = _summary_datasets(mcmc)
+    summaries, summary_attrs = _summary_datasets(mcmc)
     attrs = {k: getattr(params, k) for k in params.__dict__.keys()}
+    attrs.update(summary_attrs)
     attrs.update(kwargs)
     try:
         import h5py
@@ -83,15 +89,20 @@ def save_mcmc(mcmc, params, outpath, filename="outputs", **kwargs):
     return path
 
 
-def load_summaries(data):
-    """the ``summary_*`` datasets of a loaded run -> {space: host dict} as ``PosteriorSummary.to_host()`` returns them"""
+def load_summaries(data, attrs=None):
+    """the ``summary_*`` datasets of a loaded run -> {space: host dict} as ``PosteriorSummary.to_host()`` returns them;
+    with the run's attributes, a space that carries ``q_lo`` / ``q_hi`` also gets its ``alpha``"""
     out = {}
     for name, arr in data.items():
         if name.startswith("summary_"):
-            for k in sorted(_SUMMARY_FIELDS, key=len, reverse=True):  # ("best_logpi" before "best")
+            for k in sorted(_SUMMARY_FIELDS + _TAIL_FIELDS, key=len, reverse=True):  # ("best_logpi" before "best")
                 if name.endswith("_" + k):
                     out.setdefault(name[len("summary_"):-len(k) - 1], {})[k] = arr
                     break
+    if attrs is not None and "summary_alpha" in attrs:
+        for host in out.values():
+            if "q_lo" in host:
+                host["alpha"] = np.float64(attrs["summary_alpha"])
     return out
 
 

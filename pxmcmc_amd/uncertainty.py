@@ -7,8 +7,13 @@ by sample (experiments/earthtopography/plot.py:105-115).
 Streaming summaries: :class:`PosteriorSummary` accumulates per-chain moments and the
 highest-posterior sample on the device while a sampler runs (``summary=`` of the samplers), so the posterior mean, the
 standard-deviation map, the "MAP_X" sample (plot.py:75-76, 122) and R-hat across the chain batch need no saved chain;
-:func:`moments_np`, :func:`pooled_np` and :func:`rhat_np` state the same quantities in numpy.
+:func:`moments_np`, :func:`pooled_np` and :func:`rhat_np` state the same quantities in numpy.  With ``alpha=`` it also keeps
+the k smallest and k largest samples of every element (:func:`tail_capacity`), from which ``credible_interval_range()``
+gives the numbers of :func:`credible_interval_range` on each chain's saved samples, exactly; :func:`tails_update_np` and
+:func:`tails_quantiles_np` state that in numpy.
 """
+import warnings
+
 import numpy as np
 import torch
 
@@ -163,6 +168,96 @@ def rhat_np(count, mean, m2):
     return np.where(W != 0.0, r, np.nan)
 
 
+# ---- exact streaming credible intervals: per-element tails ---------------------------------------------
+def _quantile_split(q, n):
+    """numpy.quantile, method "linear", on n samples: (i, g), the lower order statistic and the interpolation weight -- the
+    fp64 arithmetic of ``pxm_quantile_range``"""
+    vi = float(q) * float(n - 1)
+    fl = min(np.floor(vi), float(n - 1))
+    return int(fl), vi - fl
+
+
+def tail_capacity(alpha, nsamples):
+    """k(alpha, N): slots per tail so that the k smallest and the k largest of n samples hold the two pairs of order
+    statistics ``np.quantile(x, (alpha' / 2, 1 - alpha' / 2))`` interpolates between, for every n <= N = ``nsamples`` and
+    every alpha' <= alpha: ``min(N, max(i_lo(N) + 2, N - i_hi(N)))``."""
+    alpha, N = float(alpha), int(nsamples)
+    if not (0.0 < alpha <= 1.0):
+        raise ValueError("alpha must lie in (0, 1]")
+    if N < 1:
+        raise ValueError("nsamples must be at least 1")
+    i_lo, _ = _quantile_split(alpha / 2, N)
+    i_hi, _ = _quantile_split(1 - alpha / 2, N)
+    return min(N, max(i_lo + 2, N - i_hi))
+
+
+def _qkey(x):
+    """the order-preserving uint64 key of ``qkey()`` (csrc/qkey.h): NaN, +-inf and +-0 in the order the device selects by"""
+    u = np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+    return np.where(u >> np.uint64(63) != 0, ~u, u | np.uint64(1 << 63))
+
+
+def tails_update_np(x, count, lo, hi, nsamples):
+    """the numpy statement of one ``pxm_tails_update`` on ONE chain, in place: ``x`` [m] the sample, ``count`` the number of
+    samples before it, ``lo`` / ``hi`` [k, m] the k smallest / largest so far (in no particular slot order; the device keeps
+    heaps, and the last saves in a ring until it merges them: this states which samples the read-out sees, not where they lie).  ``count < k``: slot ``count`` of both; later a sample below the largest of ``lo`` (above the smallest of ``hi``)
+    replaces it; ``count >= nsamples``: nothing.  ``count`` is the caller's to advance."""
+    x = np.asarray(x, dtype=np.float64)
+    k, m = lo.shape
+    count = int(count)
+    if count >= int(nsamples):
+        return
+    if count < k:
+        lo[count] = x
+        hi[count] = x
+        return
+    kx, cols = _qkey(x), np.arange(m)
+    klo = _qkey(lo)
+    s = klo.argmax(axis=0)
+    ins = kx < klo[s, cols]
+    lo[s[ins], cols[ins]] = x[ins]
+    khi = _qkey(hi)
+    s = khi.argmin(axis=0)
+    ins = kx > khi[s, cols]
+    hi[s[ins], cols[ins]] = x[ins]
+
+
+def _np_lerp(a, b, t):
+    """numpy/lib/_function_base_impl.py: _lerp, elementwise"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = b - a
+        return np.where(t >= 0.5, b - d * (1.0 - t), a + d * t)
+
+
+def tails_quantiles_np(count, lo, hi, alpha, nsamples=None):
+    """the numpy statement of ``pxm_tails_quantiles``: ``count`` [C], ``lo`` / ``hi`` [C, k, m] -> (q_lo, q_hi) [C, m], the
+    linear quantiles at ``alpha / 2`` and ``1 - alpha / 2`` of every chain's ``count[c]`` samples from its two tails (NaN for
+    a chain without samples).  ``ValueError`` when an order statistic lies outside the tails, or a count exceeds
+    ``nsamples`` (the number of saves the tails were sized for, when given)."""
+    count = np.asarray(count, dtype=np.int64).reshape(-1)
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    if lo.ndim != 3 or lo.shape != hi.shape or lo.shape[0] != count.shape[0]:
+        raise ValueError("count [C] and lo / hi [C, k, m] are expected")
+    if not (0.0 <= alpha <= 1.0):
+        raise ValueError("alpha must lie in [0, 1]")
+    C, k, m = lo.shape
+    q_lo, q_hi = np.full((C, m), np.nan), np.full((C, m), np.nan)
+    for c, n in enumerate(int(v) for v in count):
+        if nsamples is not None and n > int(nsamples):
+            raise ValueError("chain %d holds %d samples, the tails were sized for %d" % (c, n, nsamples))
+        if n == 0:
+            continue
+        ns = min(k, n)
+        for q, tail, out, shift in ((alpha / 2, lo[c, :ns], q_lo, 0), (1 - alpha / 2, hi[c, :ns], q_hi, n - ns)):
+            i, g = _quantile_split(q, n)
+            top = min(i + 1, n - 1)
+            if i - shift < 0 or top - shift >= ns:
+                raise ValueError("alpha = %g at %d samples needs order statistics %d and %d, outside tails of %d slots" % (alpha, n, i, top, k))
+            srt = np.take_along_axis(tail, np.argsort(_qkey(tail), axis=0, kind="stable"), axis=0)
+            out[c] = _np_lerp(srt[i - shift], srt[top - shift], g)
+    return q_lo, q_hi
+
+
 class PosteriorSummary:
     """Device accumulators of a chain batch: per chain the sample count, the running mean and the sum of squared deviations
     of every parameter (Welford's recurrence, ``pxm_moments_update``), and the sample of highest log posterior seen so far.
@@ -175,6 +270,14 @@ class PosteriorSummary:
         components, re / im interleaved).  ``False``: the real parts of the samples are accumulated (``m = nparams``), as the
         samplers' real ``chain`` array keeps them.
     :param best: track the highest-posterior sample (``update`` then needs ``logpi``)
+    :param alpha: also keep, per chain and real component, the ``k = tail_capacity(alpha, nsamples)`` smallest and largest
+        samples (``pxm_tails_update``), from which :meth:`credible_interval` reads the (1 - alpha') interval of every
+        alpha' <= alpha exactly.  ``None``: no tails
+    :param nsamples: the number of ``update`` calls the run will make per chain (needed with ``alpha``); a chain updated more
+        often keeps its first ``nsamples`` samples in the tails and :meth:`credible_interval` then raises
+
+    Intervals are per chain.  A pooled interval over the chain batch is deliberately not offered: exact pooling needs k
+    proportional to the pooled sample count, which costs as much as the chain.
 
     Complex states come back complex: ``mean`` as ``re + i im``, ``variance`` as ``var_re + var_im`` (``E |x - mean|^2``),
     ``best_sample`` as stored.  ``rhat()`` is per REAL component, shape ``[m]`` (``[2 nparams]`` for a complex state: a
@@ -183,12 +286,20 @@ class PosteriorSummary:
     """
 
     FIELDS = ("count", "mean", "m2", "best", "best_logpi")
+    TAIL_FIELDS = ("alpha", "q_lo", "q_hi")  # ``to_host()`` of a summary built with ``alpha``
 
-    def __init__(self, nchains, nparams, complex_, best=True, device=None):
+    def __init__(self, nchains, nparams, complex_, best=True, device=None, alpha=None, nsamples=None):
         self.nchains, self.nparams, self.complex = int(nchains), int(nparams), bool(complex_)
         if self.nchains < 1 or self.nparams < 1:
             raise ValueError("PosteriorSummary needs nchains >= 1 and nparams >= 1")
         self.m = self.nparams * (2 if self.complex else 1)
+        self.alpha = self.tail_slots = self._lo = self._hi = self._thr_lo = self._thr_hi = self._stage = None
+        self.nsamples = None if nsamples is None else int(nsamples)
+        if alpha is not None:
+            if nsamples is None:
+                raise ValueError("PosteriorSummary: alpha needs nsamples, the number of updates the tails are sized for")
+            self.tail_slots = tail_capacity(alpha, nsamples)
+            self.alpha = float(alpha)
         dev = ops.device() if device is None else device
         C, m = self.nchains, self.m
         self._count = torch.zeros(C, dtype=torch.int64, device=dev)
@@ -197,13 +308,19 @@ class PosteriorSummary:
         self.best = bool(best)
         self._best_x = torch.zeros((C, m), dtype=torch.float64, device=dev) if self.best else None
         self._best_logpi = torch.full((C,), -np.inf, dtype=torch.float64, device=dev) if self.best else None
+        if self.alpha is not None:
+            self._lo = torch.zeros((C, self.tail_slots, m), dtype=torch.float64, device=dev)
+            self._hi = torch.zeros_like(self._lo)
+            self._stage = torch.zeros((C, ops.tails_stage_depth(), m), dtype=torch.float64, device=dev)
+            self._thr_lo = torch.zeros((C, m), dtype=torch.float64, device=dev)
+            self._thr_hi = torch.zeros_like(self._thr_lo)
 
     # ---- accumulation -----------------------------------------------------------------------------------------------
     def update(self, X, logpi=None, mask=None):
         """add one sample per chain: ``X`` [C, nparams] on the device (complex128, or float64 when ``complex_`` is False),
         ``logpi`` [C] its log posterior (float64 or complex128: the real part; needed with ``best``), ``mask`` an int32 [C]
         device tensor or a sequence of chain flags -- chains with a zero keep their accumulators untouched.  One fused pass
-        and one small launch on the current stream.  With contiguous device tensors for ``X``, ``logpi`` and ``mask`` nothing is
+        and one small launch on the current stream, behind the tails pass of a summary built with ``alpha``.  With contiguous device tensors for ``X``, ``logpi`` and ``mask`` nothing is
         allocated or copied (the form a captured graph takes); a host ``mask`` or ``logpi`` is uploaded first (a small
         synchronous copy), and a non-contiguous ``X`` is copied."""
         X = ops.as_device(X) if not (isinstance(X, torch.Tensor) and X.is_cuda) else X
@@ -225,6 +342,8 @@ class PosteriorSummary:
             logpi = None
         if mask is not None and not (isinstance(mask, torch.Tensor) and mask.is_cuda):
             mask = torch.as_tensor(np.asarray(mask) != 0, dtype=torch.int32).to(self._mean.device)
+        if self.alpha is not None:  # reads the counts the moments pass is about to advance
+            ops.tails_update(X, self._count, self._lo, self._hi, self._thr_lo, self._thr_hi, self._stage, self.nsamples, mask=mask)
         ops.moments_update(X, self._count, self._mean, self._m2, mask=mask, logpi=logpi, best_logpi=self._best_logpi,
                            best_x=self._best_x)
 
@@ -284,22 +403,71 @@ class PosteriorSummary:
             raise ValueError("this summary was built with best=False")
         return self._best_logpi
 
+    # ---- credible intervals from the tails ----------------------------------------------------------------------------
+    def _tail_quantiles(self, alpha):
+        if self.alpha is None:
+            raise ValueError("this summary was built without alpha: it keeps no tails")
+        alpha = self.alpha if alpha is None else float(alpha)
+        if not (0.0 < alpha <= self.alpha):
+            raise ValueError("alpha = %g: the tails were sized for alpha = %g and give any alpha in (0, %g]" % (alpha, self.alpha, self.alpha))
+        return ops.tails_quantiles(self._count, self._lo, self._hi, self._stage, self.nsamples, alpha)
+
+    def credible_interval(self, alpha=None):
+        """(q_lo, q_hi) [C, nparams] (device): per chain, ``np.quantile(samples, (alpha / 2, 1 - alpha / 2), axis=0)`` of the
+        samples accumulated so far, bit for bit; NaN for a chain without samples.  Per real component: for a complex state
+        the real (imaginary) parts of the complex results are the quantiles of the real (imaginary) parts.  ``alpha``
+        defaults to the constructed one and may be any smaller value; a larger one raises ``ValueError``, a chain updated
+        more than ``nsamples`` times ``PxmError``.  Per chain only: there is no pooled interval over the batch."""
+        q_lo, q_hi = self._tail_quantiles(alpha)
+        return self._cplx(q_lo), self._cplx(q_hi)
+
+    def credible_interval_range(self, alpha=None):
+        """``q_hi - q_lo`` of :meth:`credible_interval`, [C, nparams] (device): per chain the numbers
+        :func:`credible_interval_range` gives on that chain's saved samples"""
+        q_lo, q_hi = self._tail_quantiles(alpha)
+        return self._cplx(q_hi - q_lo)
+
+    def tail_bytes(self):
+        """device bytes of the tail heaps, their thresholds and the ring of staged saves: ``(2 k + 2 + B) * 8 * C * m`` with
+        ``B = ops.tails_stage_depth()`` (0 without ``alpha``)"""
+        return 0 if self.alpha is None else (2 * self.tail_slots + 2 + ops.tails_stage_depth()) * 8 * self.nchains * self.m
+
     # ---- host side --------------------------------------------------------------------------------------------------
     def to_host(self):
         """plain dict of numpy arrays: ``count`` int64 [C], ``mean`` / ``m2`` float64 [C, m] in the real-component layout
-        and, with ``best``, ``best`` [C, nparams] (complex for a complex state) and ``best_logpi`` [C]"""
+        and, with ``best``, ``best`` [C, nparams] (complex for a complex state) and ``best_logpi`` [C]; a summary built with
+        ``alpha`` adds ``alpha`` (float64 scalar) and its quantiles ``q_lo`` / ``q_hi`` [C, m] in the real-component layout.
+        Where the tails cannot be read out (a chain updated more than ``nsamples`` times: ``PxmError`` from
+        :meth:`credible_interval`) these three are left out with a ``RuntimeWarning``, so that the moments and the best
+        sample of the run can still be saved."""
         out = {"count": self._count.cpu().numpy(), "mean": self._mean.cpu().numpy(), "m2": self._m2.cpu().numpy()}
         if self.best:
             out["best"] = self.best_sample().cpu().numpy()
             out["best_logpi"] = self._best_logpi.cpu().numpy()
+        if self.alpha is not None:
+            try:
+                q_lo, q_hi = self._tail_quantiles(None)
+            except ops.PxmError as e:
+                warnings.warn("PosteriorSummary.to_host: no credible intervals (%s)" % e, RuntimeWarning, stacklevel=2)
+            else:
+                out.update(alpha=np.float64(self.alpha), q_lo=q_lo.cpu().numpy(), q_hi=q_hi.cpu().numpy())
         return out
 
     @staticmethod
     def merge(dicts):
         """concatenate the chains of several ``to_host()`` dicts (one per rank, in rank order) -> one such dict;
-        ``rhat_np(d["count"], d["mean"], d["m2"])`` of the result is R-hat over all the chains of a multi-rank run"""
+        ``rhat_np(d["count"], d["mean"], d["m2"])`` of the result is R-hat over all the chains of a multi-rank run.  When
+        every dict carries the ``TAIL_FIELDS``, with one common ``alpha``, so does the result: the intervals stay per chain
+        (exact pooling over chains would need tails as long as the pooled chain)"""
         dicts = list(dicts)
         if not dicts:
             raise ValueError("merge: no summaries")
         keys = [k for k in PosteriorSummary.FIELDS if all(k in d for d in dicts)]
-        return {k: np.concatenate([np.asarray(d[k]) for d in dicts], axis=0) for k in keys}
+        out = {k: np.concatenate([np.asarray(d[k]) for d in dicts], axis=0) for k in keys}
+        if all(k in d for d in dicts for k in PosteriorSummary.TAIL_FIELDS):
+            alphas = {float(d["alpha"]) for d in dicts}
+            if len(alphas) != 1:
+                raise ValueError("merge: the summaries were built with different alpha: %s" % sorted(alphas))
+            out["alpha"] = np.float64(alphas.pop())
+            out.update({k: np.concatenate([np.asarray(d[k]) for d in dicts], axis=0) for k in ("q_lo", "q_hi")})
+        return out

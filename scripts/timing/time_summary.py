@@ -11,8 +11,21 @@ Cost of one streaming-summary update at the benchmark siz
   realparts   the route of a sampler with params.complex = False (the benchmark configuration): the real parts of the
               complex128 state (x_stride 2), m = 305 060 per chain, 48 * C * n bytes (about 234 MB), warm and cold.
   iteration   one replayed MYULA iteration (fused ring-space step, two real chains per slot), same regions.
+  tails       the exact credible intervals of a run of N = 1000 saves at alpha = 0.05 (k = 26 slots per tail), for the real
+              parts (m = 305 060 per chain) and for the complex state (m = 610 120), fresh standard-normal samples:
+                fill      one pxm_tails_update in the fill phase (count = k / 2), cold;
+                steady    pxm_tails_update at the end of the run, a fresh sample each time, cold: one save that stages its
+                          sample in the ring and one that merges the full ring into the heaps; a steady-state save is
+                          (15 staging + 1 merging) / 16 of them (B = 16), beside the cold pxm_moments_update of the same
+                          layout; algorithmic traffic x + two thresholds = 24 B per element, reported against 8 TB/s;
+                readout   one pxm_tails_quantiles (host-timed: it synchronises);
+                run       the N saves (device events around every pxm_tails_update, summed) plus the read-out, against
+                parent    the route without tails for the same map: one row copy into a device-resident [N, C m] chain
+                          per save (events, summed) plus pxm_quantile_range of it at the end (held a ring of rows and four
+                          chains at a time, see time_tails: same bytes, bounded device memory).
+              A run with tails must not take longer than the route without them: the script exits with an error if one does.
 
-    python scripts/timing/time_summary.py [--out FILE.json]
+    python scripts/timing/time_summary.py [--out FILE.json] [--sections moments,tails,iteration]
 """
 import argparse
 import contextlib
@@ -31,11 +44,13 @@ from pxmcmc_amd import ops  # noqa: E402
 from pxmcmc_amd.forward import SphericalWaveletTransformOperator  # noqa: E402
 from pxmcmc_amd.mcmc import MYULA, PxMCMCParams  # noqa: E402
 from pxmcmc_amd.prior import S2_Wavelets_L1  # noqa: E402
-from pxmcmc_amd.uncertainty import PosteriorSummary  # noqa: E402
+from pxmcmc_amd.uncertainty import PosteriorSummary, tail_capacity  # noqa: E402
 
 L, B, J_MIN, C = 256, 2.0, 2, 16
 HBM_RATE = 8e12  # bytes/s
 LMDA, DELTA = 1e-6, 1e-7
+TAIL_N, TAIL_ALPHA = 1000, 0.05
+PARENT_RING, PARENT_BLOCK = 64, 4  # rows of the copy ring, chains per select of the route without tails (device memory bound)
 
 
 def regions_ms(fn, calls=20, regions=5):
@@ -53,12 +68,15 @@ def regions_ms(fn, calls=20, regions=5):
     return statistics.median(times), times
 
 
-def cold_ms(fn, regions=5):
-    """median device time of one call whose operands are not in the last-level cache: a 512 MiB copy runs before each"""
+def cold_ms(fn, regions=5, prep=None):
+    """median device time of one call whose operands are not in the last-level cache: a 512 MiB copy runs before each
+    (and after ``prep``, which readies the call's input)"""
     src = torch.empty(512 << 20, dtype=torch.uint8, device=ops.device())
     dst = torch.empty_like(src)
     times = []
     for _ in range(regions + 1):
+        if prep is not None:
+            prep()
         dst.copy_(src)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
@@ -70,10 +88,119 @@ def cold_ms(fn, regions=5):
     return statistics.median(times[1:]), times[1:]
 
 
+def summed_events_ms(steps, fn):
+    """sum over ``steps`` calls fn(i, before, after) of the device time between the two events fn records"""
+    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    for i, (a, b) in enumerate(pairs):
+        fn(i, a, b)
+    torch.cuda.synchronize()
+    return sum(a.elapsed_time(b) for a, b in pairs)
+
+
+def time_tails(X, cplx):
+    """the ``tails`` block of the module docstring for one layout: ``cplx`` the complex state per component (m = 2 n), else
+    the real parts of X (x_stride 2, m = n)"""
+    C_, n = X.shape
+    m = 2 * n if cplx else n
+    N, alpha = TAIL_N, TAIL_ALPHA
+    k = tail_capacity(alpha, N)
+    B_ = ops.tails_stage_depth()
+    dev = X.device
+    rows = (lambda: torch.view_as_real(X).reshape(C_, m)) if cplx else (lambda: X)  # what the entry points are handed
+    alg = 24 * C_ * m
+    out = {"m": m, "k": k, "N": N, "alpha": alpha, "tail_bytes": (2 * k + 2 + B_) * 8 * C_ * m, "chain_bytes": N * 8 * C_ * m,
+           "algorithmic_bytes": alg}
+    rate = lambda ms: {"ms": ms, "fraction_of_8TBps": alg / (ms * 1e-3) / HBM_RATE}  # noqa: E731
+
+    s = PosteriorSummary(C_, n, cplx, best=False)
+    med, times = cold_ms(lambda: s.update(X), prep=X.normal_)
+    out["moments_cold"] = dict(rate(med), regions_ms=times)
+
+    count = torch.zeros(C_, dtype=torch.int64, device=dev)
+    lo = torch.zeros((C_, k, m), dtype=torch.float64, device=dev)
+    hi, thr_lo = torch.zeros_like(lo), torch.zeros((C_, m), dtype=torch.float64, device=dev)
+    thr_hi = torch.zeros_like(thr_lo)
+    stage = torch.zeros((C_, B_, m), dtype=torch.float64, device=dev)
+    save = lambda: ops.tails_update(rows(), count, lo, hi, thr_lo, thr_hi, stage, N)  # noqa: E731
+    for _ in range(k // 2):
+        X.normal_()
+        save()
+        count += 1
+    med, times = cold_ms(save, prep=X.normal_)  # (count stays: every call refills slot k / 2)
+    out["fill_cold"] = dict(rate(med), regions_ms=times)
+
+    def one_save(i, a, b):
+        X.normal_()
+        a.record()
+        save()
+        b.record()
+        count.add_(1)
+
+    count.zero_()  # the run from its start (the fill phase never reads a slot it has not written in this run)
+    run_ms = summed_events_ms(N, one_save)
+    assert count.tolist() == [N] * C_
+    t0 = time.perf_counter()
+    q_lo, q_hi = ops.tails_quantiles(count, lo, hi, stage, N, alpha)
+    torch.cuda.synchronize()
+    readout_ms = (time.perf_counter() - t0) * 1e3
+    out["saves_ms"], out["readout_ms"], out["run_ms"] = run_ms, readout_ms, run_ms + readout_ms
+    last_merge = k + (N - k) // B_ * B_ - 1  # the last save of the run that fills the ring
+    count.fill_(last_merge - 1)
+    med_s, times = cold_ms(save, prep=X.normal_)
+    out["stage_cold"] = {"ms": med_s, "regions_ms": times}
+    count.fill_(last_merge)
+    med_m, times = cold_ms(save, prep=X.normal_)  # (the ring holds fresh samples of the calls before)
+    out["merge_cold"] = {"ms": med_m, "regions_ms": times}
+    med = ((B_ - 1) * med_s + med_m) / B_
+    out["steady_cold"] = rate(med)
+    out["steady_over_moments"] = med / out["moments_cold"]["ms"]
+    tails_range = (q_hi - q_lo)[0, :4096].clone()
+    del lo, hi, thr_lo, thr_hi, stage, q_lo, q_hi, s
+
+    torch.cuda.empty_cache()
+
+    # The route without tails: a row copy into a device-resident chain per save, pxm_quantile_range at the end.  The whole
+    # chain is N * 8 * C * m bytes (39 / 78 GB); to bound device memory the N copies go, at their full size, into a ring of
+    # PARENT_RING rows (far larger than the last-level cache, so every row is written to HBM as in the chain), and the select
+    # runs on the columns of PARENT_BLOCK chains at a time, on fresh samples -- the same bytes and sweeps as on the whole chain.
+    ring = torch.empty((PARENT_RING, C_ * m), dtype=torch.float64, device=dev)
+    src = (lambda: torch.view_as_real(X).reshape(C_, m)) if cplx else (lambda: X.real)  # (a strided view: one copy kernel)
+
+    def one_copy(i, a, b):
+        X.normal_()
+        a.record()
+        ring[i % PARENT_RING].view(C_, m).copy_(src())
+        b.record()
+
+    copies_ms = summed_events_ms(N, one_copy)
+    del ring
+    torch.cuda.empty_cache()
+    assert C_ % PARENT_BLOCK == 0
+    chain = torch.empty((N, PARENT_BLOCK * m), dtype=torch.float64, device=dev)
+    select_ms = 0.0
+    for _ in range(C_ // PARENT_BLOCK):
+        chain.normal_()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rng = ops.quantile_range(chain, alpha)
+        torch.cuda.synchronize()
+        select_ms += (time.perf_counter() - t0) * 1e3
+    out["parent"] = {"copies_ms": copies_ms, "select_ms": select_ms, "run_ms": copies_ms + select_ms,
+                     "select_block_bytes": chain.numel() * 8}
+    out["run_over_parent"] = out["run_ms"] / out["parent"]["run_ms"]
+    # (different samples in the two routes: only the scale of the two maps is compared)
+    out["median_range"] = {"tails": float(tails_range.median()), "parent": float(rng[:4096].median())}
+    del chain
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sections", default="moments,tails,iteration")
     a = ap.parse_args()
+    sections = set(a.sections.split(","))
     data = np.random.default_rng(0).normal(size=L * (2 * L - 1))
     op = SphericalWaveletTransformOperator(data, 0.05, "synthesis", L, B, J_MIN, max_chains=C)
     reg = S2_Wavelets_L1("synthesis", None, None, LMDA, L=L, B=B, J_min=J_MIN)
@@ -85,7 +212,7 @@ def main():
     logpi = torch.randn(C, dtype=torch.float64, device=dev)
     nbytes = 5 * 8 * C * 2 * n
     res["algorithmic_bytes"] = nbytes
-    for name, best in (("update", False), ("update_best", True)):
+    for name, best in (("update", False), ("update_best", True)) if "moments" in sections else ():
         s = PosteriorSummary(C, n, True, best=best)
         med, times = regions_ms(lambda: s.update(X, logpi=logpi if best else None))
         res[name] = {"ms": med, "regions_ms": times, "TBps": nbytes / (med * 1e-3) / 1e12,
@@ -99,30 +226,40 @@ def main():
     nbytes_re = 48 * C * n
     res["algorithmic_bytes_realparts"] = nbytes_re
     s = PosteriorSummary(C, n, False, best=True)
-    for name, timer in (("update_realparts_best", regions_ms), ("update_realparts_best_cold", cold_ms)):
+    for name, timer in (("update_realparts_best", regions_ms), ("update_realparts_best_cold", cold_ms)) if "moments" in sections else ():
         med, times = timer(lambda: s.update(X, logpi=logpi))
         res[name] = {"ms": med, "regions_ms": times, "TBps": nbytes_re / (med * 1e-3) / 1e12,
                      "fraction_of_8TBps": nbytes_re / (med * 1e-3) / HBM_RATE}
 
-    p = PxMCMCParams(lmda=LMDA, delta=DELTA, nsamples=1, nburn=0, ngap=1, verbosity=0)
-    my = MYULA(op, reg, p, nchains=C, seed=1)
-    my._prepare()
-    with contextlib.redirect_stdout(io.StringIO()):
-        X0, preds = my._initial_sample(np.zeros(n))
-    if my._pairs_ok(X0):
-        my._pairs_start()
-    my._engine_start(X0, preds, 0)
-    assert my._eng["graph"] is not None, my._eng["graph_error"]
-    med, times = regions_ms(lambda: my._engine_advance(16), calls=4)
-    my._engine_stop()
-    res["myula_iteration"] = {"ms": med / 16, "regions_ms": [t / 16 for t in times]}
-    res["update_over_iteration"] = {k: res[k]["ms"] / res["myula_iteration"]["ms"]
-                                    for k in ("update_best", "update_best_cold", "update_realparts_best", "update_realparts_best_cold")}
+    del s
+    if "tails" in sections:
+        res["tails_realparts"] = time_tails(X, False)
+        res["tails_complex"] = time_tails(X, True)
+
+    if "iteration" in sections:
+        p = PxMCMCParams(lmda=LMDA, delta=DELTA, nsamples=1, nburn=0, ngap=1, verbosity=0)
+        my = MYULA(op, reg, p, nchains=C, seed=1)
+        my._prepare()
+        with contextlib.redirect_stdout(io.StringIO()):
+            X0, preds = my._initial_sample(np.zeros(n))
+        if my._pairs_ok(X0):
+            my._pairs_start()
+        my._engine_start(X0, preds, 0)
+        assert my._eng["graph"] is not None, my._eng["graph_error"]
+        med, times = regions_ms(lambda: my._engine_advance(16), calls=4)
+        my._engine_stop()
+        res["myula_iteration"] = {"ms": med / 16, "regions_ms": [t / 16 for t in times]}
+        res["update_over_iteration"] = {k: res[k]["ms"] / res["myula_iteration"]["ms"]
+                                        for k in ("update_best", "update_best_cold", "update_realparts_best", "update_realparts_best_cold")
+                                        if k in res}
     print(json.dumps(res, indent=1), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
+    slower = {k: v["run_over_parent"] for k, v in res.items() if isinstance(v, dict) and v.get("run_over_parent", 0) > 1}
+    if slower:  # the acceptance condition of DESIGN.md section 15
+        sys.exit("a run with tails takes longer than the route without them: %s" % slower)
 
 
 if __name__ == "__main__":
