@@ -80,13 +80,6 @@ inline int allow_dynamic_lds(std::atomic<uint64_t>& done, std::initializer_list<
   return 0;
 }
 
-// workgroups (slices) per chain of the stepping kernels that leave per-chain sums (fista.hip, sapg.hip): one per 256
-// elements up to `most`, grid-stride beyond.  A function of n only, so a chain's sums do not depend on its batch.
-inline int chain_slices(int64_t n, int most) {
-  const int64_t s = (n + 255) / 256;
-  return (int)(s < 1 ? 1 : (s > most ? most : s));
-}
-
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline int round_down(int x, int m) { return x / m * m; }
 

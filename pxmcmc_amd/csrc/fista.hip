@@ -17,6 +17,7 @@
 #include "../../include/pxmcmc_amd.h"
 #include "common.h"
 #include "elem.h"
+#include "reduce.h"
 
 #include <algorithm>
 #include <cmath>
@@ -29,23 +30,6 @@ static inline int fista_slices(int64_t n) { return chain_slices(n, PXM_FISTA_SLI
 struct FistaSums {
   double dx2, x2, tx;
 };
-
-// sum over the workgroup in a fixed order: lanes by shuffle, then the waves one after the other; valid in thread 0
-__device__ __forceinline__ FistaSums fista_block_sum(FistaSums v) {
-  __shared__ double part[4][3];
-  for (int off = 32; off > 0; off >>= 1) {
-    v.dx2 += __shfl_down(v.dx2, off);
-    v.x2 += __shfl_down(v.x2, off);
-    v.tx += __shfl_down(v.tx, off);
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) part[wave][0] = v.dx2, part[wave][1] = v.x2, part[wave][2] = v.tx;
-  __syncthreads();
-  FistaSums tot{0.0, 0.0, 0.0};
-  if (threadIdx.x == 0)
-    for (int w = 0; w < 4; ++w) tot.dx2 += part[w][0], tot.x2 += part[w][1], tot.tx += part[w][2];
-  return tot;
-}
 
 // GIVEN: X_{k+1} is the array P (Y, G, T unused); else X_{k+1} = soft(Y - gamma G, tscale T_i), T_i = T[i] or Ts
 template <bool CPLX, bool GIVEN>
@@ -91,28 +75,20 @@ __global__ __launch_bounds__(256) void k_fista_step(const double* __restrict__ Y
       if constexpr (!GIVEN) acc.tx += (T ? T[i] : Ts) * fabs(x1);
     }
   }
-  const FistaSums tot = fista_block_sum(acc);
+  block_sum<4>(acc.dx2, acc.x2, acc.tx);
   if (threadIdx.x == 0) {
     double* p = part + ((int64_t)c * gridDim.x + blockIdx.x) * 3;
-    p[0] = tot.dx2, p[1] = tot.x2, p[2] = tot.tx;
+    p[0] = acc.dx2, p[1] = acc.x2, p[2] = acc.tx;
   }
 }
 
-// sums[c][0..2] = the chain's partials added in a fixed order (lane l takes slices l, l + 64, ..., then the lanes by
-// shuffle); the third sum is NaN when the launch did not form it (given prox)
+// sums[c][0..2] = the chain's partials added in the fixed order (reduce.h: slice_sum); the third sum is NaN when the launch
+// did not form it (given prox)
 __global__ __launch_bounds__(64) void k_fista_finish(const double* __restrict__ part, int slices, int has_f,
                                                      double* __restrict__ sums) {
   const int c = blockIdx.x;
-  FistaSums v{0.0, 0.0, 0.0};
-  for (int sl = threadIdx.x; sl < slices; sl += 64) {
-    const double* p = part + ((int64_t)c * slices + sl) * 3;
-    v.dx2 += p[0], v.x2 += p[1], v.tx += p[2];
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    v.dx2 += __shfl_down(v.dx2, off);
-    v.x2 += __shfl_down(v.x2, off);
-    v.tx += __shfl_down(v.tx, off);
-  }
+  FistaSums v;
+  slice_sum<3>(part + (int64_t)c * slices * 3, slices, threadIdx.x, v.dx2, v.x2, v.tx);
   if (threadIdx.x == 0) {
     sums[c * 3 + 0] = v.dx2;
     sums[c * 3 + 1] = v.x2;

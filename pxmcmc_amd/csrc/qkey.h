@@ -1,4 +1,4 @@
-// The total order on doubles that the quantile kernels select by (elementwise.hip: k_quantile_range; tails.hip), and numpy's
+// The total order on doubles that the quantile kernels select by (tails.hip: k_quantile_range, k_tails_quantiles), and numpy's
 // interpolation between two order statistics.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -10,7 +10,7 @@
 //
 // with the update arithmetic (elem.h: soft_*, chain_step_*) and the noise (elem.h: draw_noise) of pxm_myula_step.  Every
 // workgroup also writes one partial of sum_i T_i |X1_i| (plain products and sums, no contraction); the number of workgroups
-// per chain depends on n only (common.h: chain_slices), so a chain's sum does not depend on its batch.  A pure stream like
+// per chain depends on n only (reduce.h: chain_slices), so a chain's sum does not depend on its batch.  A pure stream like
 // k_fista_step: 16-byte accesses per complex128 element, one element per lane and pass, no LDS beyond the 32 bytes of the
 // workgroup sum, no atomics.
 //
@@ -25,25 +25,13 @@
 #include "../../include/pxmcmc_amd.h"
 #include "common.h"
 #include "elem.h"
+#include "reduce.h"
 
 #include <cmath>
 
 namespace pxm {
 
 static_assert(NOISE_F64_FLAG == PXM_NOISE_F64, "elem.h: the noise flag must be the public one");
-
-// sum over the workgroup in a fixed order: lanes by shuffle, then the waves one after the other; valid in thread 0
-__device__ __forceinline__ double sapg_block_sum(double v) {
-  __shared__ double part[4];
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) part[wave] = v;
-  __syncthreads();
-  double tot = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < 4; ++w) tot += part[w];
-  return tot;
-}
 
 // NZ selects the noise at compile time, so that draw_noise's run-time switches fold away and with them the scalar registers
 // of the paths not taken (with all of them in one kernel the complex128 form runs out of scalar registers):
@@ -87,8 +75,8 @@ __global__ __launch_bounds__(256) void k_sapg_step(const double* __restrict__ X,
       acc += t * fabs(x1);
     }
   }
-  const double tot = sapg_block_sum(acc);
-  if (threadIdx.x == 0) part[(int64_t)c * gridDim.x + blockIdx.x] = tot;
+  block_sum<4>(acc);
+  if (threadIdx.x == 0) part[(int64_t)c * gridDim.x + blockIdx.x] = acc;
 }
 
 struct SapgUpdate {
@@ -100,8 +88,8 @@ struct SapgUpdate {
   int pool;
 };
 
-// part [C][slices] -> gsum [C] (wave w adds the chains w, w + 16, ...: lane l takes slices l, l + 64, ..., then the lanes
-// by shuffle), then one thread per chain moves eta and theta
+// part [C][slices] -> gsum [C] (wave w adds the chains w, w + 16, ... in the fixed order, reduce.h: slice_sum), then one
+// thread per chain moves eta and theta
 __global__ __launch_bounds__(1024) void k_sapg_update(const double* __restrict__ part, int slices, int C, SapgUpdate u,
                                                       double* __restrict__ gsum, double* __restrict__ theta,
                                                       double* __restrict__ eta, double* __restrict__ trace) {
@@ -109,9 +97,8 @@ __global__ __launch_bounds__(1024) void k_sapg_update(const double* __restrict__
   __shared__ double pooled;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nwave = blockDim.x >> 6;
   for (int c = wave; c < C; c += nwave) {
-    double v = 0.0;
-    for (int sl = lane; sl < slices; sl += 64) v += part[(int64_t)c * slices + sl];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    double v;
+    slice_sum<1>(part + (int64_t)c * slices, slices, lane, v);
     if (lane == 0) gsum[c] = v / u.lmda;
   }
   __syncthreads();

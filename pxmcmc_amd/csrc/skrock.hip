@@ -36,7 +36,7 @@ struct SkCoef {
   double a, b, c, e, r;
 };
 
-// the noise of pxm_myula_step (elementwise.hip: draw_noise), element i of chain c
+// the noise of pxm_myula_step (elem.h: draw_noise), element i of chain c
 template <bool CPLX>
 __device__ __forceinline__ double2 sk_noise(const SkNoise& ns, int c, int64_t n, int64_t i) {
   if (ns.noise) {

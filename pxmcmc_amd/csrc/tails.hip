@@ -8,7 +8,8 @@
 // largest, ordered by qkey().  The root (slot 0) is the tail's threshold, the value a new sample has to beat; thr_lo /
 // thr_hi [C][m] mirror the roots in the layout of the sample.  A sample beyond a threshold replaces the root and sifts down:
 // two reads per level, log2 k levels, in place of a rescan of the k slots.  Saves are staged in a ring of TAIL_STAGE rows
-// per chain and merged into the heaps when it is full (k_tails_update says why).
+// per chain and merged into the heaps when it is full (k_tails_update says why).  After them: the same select on a whole
+// chain that is resident on the device (k_quantile_range).
 #include "common.h"
 #include "qkey.h"
 
@@ -188,6 +189,23 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 
 using namespace pxm;
 
+// ---- quantile credible-interval range of a chain resident on the device (pxmcmc/uncertainty.py:7-16) ------------------------
+// out[j] = Q(1 - alpha/2) - Q(alpha/2) of column j of chain[ns][np] (numpy's default "linear" quantile: virtual index q (ns - 1),
+// the two order statistics around it, numpy's lerp).  One thread per column -- adjacent threads read adjacent columns, every
+// pass over the samples is a fully coalesced sweep of the chain -- and the radix select of qkey.h, both quantiles in the same
+// sweep: 33 sweeps of the chain.  (Outside the namespace, as it always was: the kernel's name is an exported symbol.)
+__global__ __launch_bounds__(256) void k_quantile_range(const double* __restrict__ chain, int64_t ns, int64_t np, int64_t ld,
+                                                        int64_t i_lo, double g_lo, int64_t i_hi, double g_hi, double* __restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= np) return;
+  const int64_t idx[2] = {i_lo, i_hi};
+  const double g[2] = {g_lo, g_hi};
+  double v[2];
+  const double* col = chain + j;
+  select_quantiles<2>([=](int64_t s_) { return col[s_ * ld]; }, ns, idx, g, v);
+  out[j] = v[1] - v[0];
+}
+
 extern "C" {
 
 int64_t pxm_tails_buffer_doubles(int64_t m, int C, int64_t k) {
@@ -270,6 +288,21 @@ int pxm_tails_quantiles(const int64_t* count, const double* lo, const double* hi
                        stage + (int64_t)c * TAIL_STAGE * m, m, r.ns, r.np, r.r_lo, r.g_lo, r.r_hi, r.g_hi, q_lo + (int64_t)c * m, q_hi + (int64_t)c * m);
     PXM_HIP(hipGetLastError());
   }
+  return 0;
+}
+
+int pxm_quantile_range(const double* chain, int64_t nsamples, int64_t nparams, int64_t ld, double alpha, double* out,
+                       pxm_stream_t stream) {
+  PXM_REQUIRE(chain && out, "pxm_quantile_range: null buffer");
+  PXM_REQUIRE(nsamples >= 1 && nparams >= 1 && ld >= nparams, "pxm_quantile_range: bad shape");
+  PXM_REQUIRE(alpha >= 0.0 && alpha <= 1.0, "pxm_quantile_range: alpha must lie in [0, 1]");
+  int64_t i_lo, i_hi;
+  double g_lo, g_hi;
+  quantile_split(alpha / 2, nsamples, &i_lo, &g_lo);
+  quantile_split(1 - alpha / 2, nsamples, &i_hi, &g_hi);
+  hipLaunchKernelGGL(k_quantile_range, dim3((unsigned)((nparams + 255) / 256)), dim3(256), 0, (hipStream_t)stream, chain, nsamples,
+                     nparams, ld, i_lo, g_lo, i_hi, g_hi, out);
+  PXM_HIP(hipGetLastError());
   return 0;
 }
 

@@ -1,5 +1,5 @@
-"""The PxMALA iteration kernels on the GPU (csrc/elementwise.hip: k_pxmala_propose, k_pxmala_tail_partial, k_pxmala_accept2 /
-accept3, k_select_copy_many, philox_uniform) against the extended-precision model of tests/test_pxmala_host.py: every
+"""The PxMALA iteration kernels on the GPU (csrc/pxmala.hip: k_pxmala_propose, k_pxmala_tail_partial, k_pxmala_accept2 /
+accept3; csrc/elementwise.hip: k_select_copy_many; philox_uniform) against the extended-precision model of tests/test_pxmala_host.py: every
 element of the proposal, every sum, the stored log transition terms, the Metropolis decision at a known distance from the
 model's log acceptance ratio, the delta adaptation with its clamps, the trace ring, the device counter, the uniform stream
 and the conditional copy.  Every buffer is allocated for more chains than are used and prefilled with NaN or a sentinel;

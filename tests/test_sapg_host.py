@@ -38,7 +38,7 @@ def sapg_step_np(X, g, T, theta, delta, lmda, w):
 
 
 def slices_of(n):
-    """workgroups per chain (common.h: chain_slices)"""
+    """workgroups per chain (reduce.h: chain_slices)"""
     return int(min(SLICES_MAX, max(1, (n + 255) // 256)))
 
 
