@@ -84,11 +84,16 @@ def main(argv=None):
                     help="accumulate the posterior mean / standard deviation / R-hat on the GPU instead of saving the chain")
     ap.add_argument("--summary-alpha", type=float, default=None,
                     help="with --summary: also keep the per-pixel tails that give the (1 - alpha) credible-interval map exactly")
+    ap.add_argument("--summary-ess", type=int, default=None, metavar="K",
+                    help="with --summary: also accumulate the autocovariances at lags below K (even, 2..64) and print the "
+                         "effective sample size and the standard error of the mean map")
     ap.add_argument("--outdir", type=str, default=".")
     ap.add_argument("--jobid", type=str, default="0")
     args = ap.parse_args(argv)
     if args.summary_alpha is not None and not args.summary:
         ap.error("--summary-alpha needs --summary")
+    if args.summary_ess is not None and not args.summary:
+        ap.error("--summary-ess needs --summary")
 
     L, B, J_min, setting = args.L, 1.5, 2, args.setting  # B, J_min as in main.py:72-74
 
@@ -137,7 +142,8 @@ def main(argv=None):
     if args.estimate_mu:
         regulariser, params = estimate_mu(forwardop, regulariser, params, delta_myula, args,
                                           start_point.astype(complex) if spin else start_point)
-    mcmc = cls(forwardop, regulariser, params, nchains=args.chains, summary=args.summary, summary_alpha=args.summary_alpha)
+    mcmc = cls(forwardop, regulariser, params, nchains=args.chains, summary=args.summary, summary_alpha=args.summary_alpha,
+               summary_ess=args.summary_ess)
     if args.map_start:
         start_point = map_start(forwardop, regulariser, params, L_g, start_point.astype(complex) if spin else start_point)
     start = datetime.now()
@@ -158,6 +164,8 @@ def main(argv=None):
         if args.chains > 1:
             rmax, nundef = summ.max_rhat()
             print(f"max R-hat over the image ({args.chains} chains): {rmax:.4f} ({nundef} components undefined)")
+        if args.summary_ess is not None:
+            print(summ.ess_report("image"))
         rel = np.sqrt(np.mean(np.abs(mean - truth) ** 2)) / np.sqrt(np.mean(np.abs(truth) ** 2))
         print(f"saved {path} and {base}_mean.npy / _std.npy; {mcmc.niter} iterations x {args.chains} chain(s) in {elapsed}; "
               f"posterior-mean error {rel:.3f} (noise {args.sigma:.3f}); median posterior std {np.median(std):.3f}")

@@ -115,7 +115,8 @@ def build_sampler(args, forward_operator, prior, params, space):
     "state" for the harmonic posterior, whose transform has no image) and "chain" leaves ``track``"""
     if args.summary:
         params.track = [t for t in params.track if t != "chain"]
-    kw = dict(nchains=args.chains, seed=args.seed, summary=space if args.summary else None, summary_alpha=args.summary_alpha)
+    kw = dict(nchains=args.chains, seed=args.seed, summary=space if args.summary else None, summary_alpha=args.summary_alpha,
+              summary_ess=args.summary_ess)
     if args.algo == "myula":
         return MYULA(forward_operator, prior, params, **kw)
     if args.algo == "pxmala":
@@ -136,6 +137,8 @@ def summary_maps(args, mcmc, space, path):
     if args.chains > 1:
         rmax, nundef = summ.max_rhat()
         print(f"max R-hat over the {space} ({args.chains} chains): {rmax:.4f} ({nundef} components undefined)")
+    if args.summary_ess is not None:
+        print(summ.ess_report(space))
     print(f"posterior mean and standard deviation of the {space}: {base}_mean.npy, {base}_std.npy")
     if args.summary_alpha is not None:
         ci = summ.credible_interval_range()[0].cpu().numpy()
@@ -171,11 +174,16 @@ def main(argv=None):
                          "of the image, or with --harmonic of the state (the value may be left out; the other one is an error)")
     ap.add_argument("--summary-alpha", type=float, default=None,
                     help="with --summary: also keep the per-element tails that give the (1 - alpha) credible-interval map exactly")
+    ap.add_argument("--summary-ess", type=int, default=None, metavar="K",
+                    help="with --summary: also accumulate the autocovariances at lags below K (even, 2..64) and print the "
+                         "effective sample size and the standard error of the mean map")
     ap.add_argument("--harmonic", action="store_true",
                     help="harmonic-space posterior: WeakLensingHarmonic + harmonic wavelets + L1, started from sks_estimate")
     args = ap.parse_args(argv)
     if args.summary_alpha is not None and not args.summary:
         ap.error("--summary-alpha needs --summary")
+    if args.summary_ess is not None and not args.summary:
+        ap.error("--summary-ess needs --summary")
     if args.summary not in (None, True, "state" if args.harmonic else "image"):
         ap.error("--summary %s: the summary is of the %s" % (args.summary, "state with --harmonic" if args.harmonic else "image without --harmonic"))
 

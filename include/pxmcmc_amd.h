@@ -533,6 +533,43 @@ int pxm_tails_update(const double* x, int x_stride, const int64_t* count, double
 int pxm_tails_quantiles(const int64_t* count, const double* lo, const double* hi, const double* stage, int64_t m, int C, int64_t k,
                         int64_t nsamples, double alpha, double* q_lo, double* q_hi, pxm_stream_t stream);
 
+/* ---- streaming effective sample size -------------------------------------------------------
+ * The lagged autocovariances of every chain and element at lags 0 ... K - 1 (K even, 2 <= K <= 64), accumulated at the
+ * save points, without the chain.  With x_0 ... x_{n-1} the saves of a chain, p = x_0 and y_t = x_t - p, the caller-owned
+ * float64 state is acc [C][K][m] (acc_l = sum_{t >= l} y_t y_{t-l}) and tot [C][m] (sum_t y_t), both summed in save order
+ * with every product and sum rounded on its own, head [C][K][m], the first K saves as they came (row 0 is the pivot), and
+ * ring [C][K - 1 + B][m], save t at row t mod (K - 1 + B), B = pxm_acov_stage_depth().  acc and tot cover the complete
+ * blocks of B saves; the saves after them wait in the ring.  No initialisation is needed: the first block starts from zero.
+ * pxm_acov_state_doubles: doubles of each of acc and head; pxm_acov_ring_doubles: doubles of ring; pxm_acov_scratch_doubles:
+ * doubles of the scratch pxm_acov_ess needs for `stats` (-1: bad arguments or overflow). */
+int pxm_acov_stage_depth(void);
+int64_t pxm_acov_state_doubles(int64_t m, int C, int K);
+int64_t pxm_acov_ring_doubles(int64_t m, int C, int K);
+int64_t pxm_acov_scratch_doubles(int64_t m);
+/* One save: x as for pxm_moments_update (x_stride 1: float64 [C][m]; 2: the real parts of complex128 [C][m]).  count int64
+ * [C] is the number of samples BEFORE this one and is only read: queue the call before the pxm_moments_update of the same
+ * sample, which advances it.  The sample is copied to row count[c] mod (K - 1 + B) of the ring (and to row count[c] of head
+ * while count[c] < K); the save with count[c] mod B == B - 1 also folds its block into acc and tot.  Every chain has its own
+ * phase.  A masked-out chain (mask int32 [C], NULL: every chain) is not touched.  One launch, no allocation, no
+ * synchronisation: graph-capturable. */
+int pxm_acov_update(const double* x, int x_stride, const int64_t* count, double* acc, double* tot, double* head, double* ring,
+                    const int* mask, int64_t m, int C, int K, pxm_stream_t stream);
+/* Read-out; writes nothing to the state and folds the count[c] mod B saves that wait in the ring on the fly, in the order
+ * a merge would.  Per chain, d = tot / n, head_l (tail_l) the sum of the first (last) l of the y_t:
+ * gamma_l = (acc_l - d ((tot - head_l) + (tot - tail_l)) + (n - l) d^2) / n, rho_l = gamma_l / gamma_0, Geyer's initial
+ * monotone sequence over P_k = rho_2k + rho_2k+1 for 2 k + 1 < min(K, n) (stop at the first P_k that is not positive,
+ * else P_k <- min(P_k, P_k-1)), tau = -1 + 2 sum P_k, ess [C][m] = min(n / tau, n log10 n) (the cap where tau <= 0) and
+ * ess_lag int32 [C][m], the even lag of the stop, 2 floor(min(K, n) / 2) when the sequence never stopped (the estimate is
+ * then truncated: an upper bound).  NaN and -1 for n < 4 or a gamma_0 that is not positive and finite.  ess_pooled [m] and
+ * mcse [m] (optional): over the C' chains with samples, W = mean_c n / (n - 1) gamma_0,c, var+ = (n - 1) / n W + the
+ * variance of the chain means p_c + d_c, rho_l = 1 - (W - mean_c n / (n - 1) gamma_l,c) / var+, the same sum,
+ * ess_pooled = min(C' n / tau, C' n log10(C' n)), mcse = sqrt(var+ / ess_pooled); they make the call read the counts back
+ * (it synchronises the stream), and chains with different counts are then an error.  stats [3] (optional, needs scratch):
+ * the minimum of ess over its non-NaN values (NaN if none), its NaN count and its truncated count. */
+int pxm_acov_ess(const int64_t* count, const double* acc, const double* tot, const double* head, const double* ring, int64_t m, int C,
+                 int K, double* ess, int* ess_lag, double* ess_pooled, double* mcse, double* stats, double* scratch,
+                 pxm_stream_t stream);
+
 /* ---- weak-lensing measurement helpers (pxmcmc/measurements.py:151-171, 242-304) --------- */
 /* out = flm .* kernel with entries [0,4) zeroed: harmonic_mapping (:162-171). kernel: [L*L] */
 int pxm_wl_harmonic_mapping(const void* flm, const double* kernel, void* out, int64_t n, int C,

@@ -59,6 +59,12 @@ SIGNATURES = {
     "pxm_tails_stage_doubles": (c_i64, [c_i64, c_int]),
     "pxm_tails_update": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_i64, c_vp]),
     "pxm_tails_quantiles": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_i64, c_dbl, c_vp, c_vp, c_vp]),
+    "pxm_acov_stage_depth": (c_int, []),
+    "pxm_acov_state_doubles": (c_i64, [c_i64, c_int, c_int]),
+    "pxm_acov_ring_doubles": (c_i64, [c_i64, c_int, c_int]),
+    "pxm_acov_scratch_doubles": (c_i64, [c_i64]),
+    "pxm_acov_update": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_acov_ess": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pxm_sht_uses_recursion": (c_int, [c_vp]),
     "pxm_rec_reduce_selftest": (c_int, [c_vp]),
     "pxm_sht_plan_create": (c_int, [c_int, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),

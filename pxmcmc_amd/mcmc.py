@@ -32,7 +32,11 @@ Extensions (all optional, defaults reproduce the reference's one-chain behaviour
 * ``summary_alpha`` -- ``None`` (default) or alpha in (0, 1]; needs ``summary``.  The summaries also keep the
   ``tail_capacity(alpha, nsamples)`` smallest and largest saved samples of every element, and
   ``self.summary[space].credible_interval_range()`` then gives, per chain, the (1 - alpha) credible-interval map the
-  reference computes from the saved chain (pxmcmc/uncertainty.py:7-16), exactly.
+  reference computes from the saved chain (pxmcmc/uncertainty.py:7-16), exactly;
+* ``summary_ess``  -- ``None`` (default) or K, even with 2 <= K <= 64; needs ``summary``.  The summaries also accumulate the
+  lagged products of the saved samples at lags below K, and ``self.summary[space].ess()`` then gives the effective sample
+  size of every chain and element, ``ess_pooled()`` that of the chain batch and ``mcse()`` the standard error of
+  ``pooled_mean()``.  Where ``ess_lag()`` reaches K the value is truncated, an upper bound: raise K or ``ngap``.
 
 SKROCK (pxmcmc/mcmc.py:292-383) follows the published recursion (Pereyra, Vargas-Mieles & Zygalakis 2020), which
 differs from the reference's literal code for s >= 2 (see :class:`SKROCK`); it takes the keywords above except
@@ -106,7 +110,8 @@ class PxMCMC:
     """
 
     def __init__(self, forward, prior, mcmcparams=PxMCMCParams(), nchains=1, rng="philox", seed=0, chain_offset=0,
-                 use_graph=True, ring_shortcut=True, real_pairs=True, noise_bits=64, summary=None, summary_alpha=None):
+                 use_graph=True, ring_shortcut=True, real_pairs=True, noise_bits=64, summary=None, summary_alpha=None,
+                 summary_ess=None):
         self.forward = forward
         self.prior = prior
         for attr in mcmcparams.__dict__.keys():
@@ -140,6 +145,13 @@ class PxMCMC:
                 raise ValueError("summary_alpha needs summary: the tails are part of the streaming summaries")
             tail_capacity(summary_alpha, self.nsamples)  # (validates alpha and nsamples)
         self.summary_alpha = None if summary_alpha is None else float(summary_alpha)
+        if summary_ess is not None:
+            from .uncertainty import _ess_lags
+
+            if not self._summary_spaces:
+                raise ValueError("summary_ess needs summary: the lagged products are part of the streaming summaries")
+            summary_ess = _ess_lags(summary_ess)
+        self.summary_ess = summary_ess
         self._initialise_tracking_arrays()
 
     def run(self, start_point=None):
@@ -195,7 +207,8 @@ class PxMCMC:
                     S = X
                 S, cplx = self._summary_image(tr, S), True
             if sp not in self.summary:
-                self.summary[sp] = PosteriorSummary(self.nchains, S.shape[1], cplx, alpha=self.summary_alpha, nsamples=self.nsamples)
+                self.summary[sp] = PosteriorSummary(self.nchains, S.shape[1], cplx, alpha=self.summary_alpha, nsamples=self.nsamples,
+                                                    ess_lags=self.summary_ess)
             self.summary[sp].update(S, logpi=ops.as_device(logPi), mask=mask)
 
     # ---- device-side pieces -----------------------------------------------------------

@@ -496,6 +496,65 @@ def tails_quantiles(count, lo, hi, stage, nsamples, alpha):
     return q_lo, q_hi
 
 
+def acov_stage_depth():
+    """B: the saves ``acov_update`` keeps in its ring between two merges into ``acc`` and ``tot``; the ring has
+    ``K - 1 + B`` rows"""
+    return int(lib.pxm_acov_stage_depth())
+
+
+def _acov_state(fn, acc, tot, head, ring, count):
+    """argument checks of the autocovariance entry points -> (C, K, m)"""
+    if not (isinstance(acc, torch.Tensor) and acc.dim() == 3):
+        raise TypeError("%s: acc must be a float64 [C, K, m] device tensor" % fn)
+    C_, K, m = acc.shape
+    if K < 2 or K > 64 or K % 2:
+        raise ValueError("%s: K must be even with 2 <= K <= 64, got %d" % (fn, K))
+    R = K - 1 + acov_stage_depth()
+    for t, dt, shape in ((count, torch.int64, (C_,)), (acc, _REAL, (C_, K, m)), (tot, _REAL, (C_, m)), (head, _REAL, (C_, K, m)),
+                         (ring, _REAL, (C_, R, m))):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError("%s: count int64 [C], acc / head contiguous float64 [C, K, m], tot contiguous float64 [C, m] and ring "
+                            "contiguous float64 [C, K - 1 + %d, m] device tensors are expected" % (fn, acov_stage_depth()))
+    if int(lib.pxm_acov_state_doubles(m, C_, K)) != acc.numel() or int(lib.pxm_acov_ring_doubles(m, C_, K)) != ring.numel():
+        raise ValueError("%s: bad state shape [%d, %d, %d]" % (fn, C_, K, m))
+    return C_, K, m
+
+
+def acov_update(X, count, acc, tot, head, ring, mask=None):
+    """One save into the lagged-product accumulators of the streaming effective sample size, in place:
+    ``acc`` / ``head`` float64 [C, K, m], ``tot`` [C, m], ``ring`` [C, K - 1 + B, m] (:func:`acov_stage_depth`); ``X`` as for
+    :func:`moments_update`.  ``count`` int64 [C] is the number of samples before this one and is not written: call this
+    before the ``moments_update`` of the same sample.  A chain that ``mask`` (int32 [C]) switches off is left untouched.  The
+    state needs no initialisation.  No allocation, no synchronisation: the call can be captured in a HIP graph."""
+    C_, K, m = _acov_state("acov_update", acc, tot, head, ring, count)
+    x, xs = _moments_rows(X, C_, m)
+    if mask is not None and (mask.dtype != torch.int32 or tuple(mask.shape) != (C_,) or not mask.is_cuda or not mask.is_contiguous()):
+        raise TypeError("acov_update: mask must be a contiguous int32 [C] device tensor")
+    check(lib.pxm_acov_update(_p(x), xs, _p(count), _p(acc), _p(tot), _p(head), _p(ring), _p(mask), m, C_, K, _stream()))
+
+
+def acov_ess(count, acc, tot, head, ring, pooled=True):
+    """Read-out of the accumulators of :func:`acov_update` -> (ess float64 [C, m], ess_lag int32 [C, m], ess_pooled [m], mcse
+    [m], stats [3]) on the device: the effective sample size of every chain and element by Geyer's initial monotone sequence
+    over the K lags, the even lag at which the sequence stopped (``2 * (min(K, n) // 2)``: it never did, the estimate is
+    truncated), the effective sample size pooled over the chains with samples and the Monte-Carlo standard error of their
+    pooled mean, and stats = (min ESS over the non-NaN values, NaN count, truncated count) of ``ess``.  Nothing is written to
+    the state.  ``pooled=False`` leaves ``ess_pooled`` and ``mcse`` out (None) and takes any counts; with them, chains with
+    different counts raise PxmError."""
+    C_, K, m = _acov_state("acov_ess", acc, tot, head, ring, count)
+    ess = torch.empty((C_, m), dtype=_REAL, device=acc.device)
+    lag = torch.empty((C_, m), dtype=torch.int32, device=acc.device)
+    ep = se = None
+    if pooled:
+        ep = torch.empty(m, dtype=_REAL, device=acc.device)
+        se = torch.empty_like(ep)
+    st = torch.empty(3, dtype=_REAL, device=acc.device)
+    scratch = torch.empty(int(lib.pxm_acov_scratch_doubles(m)), dtype=_REAL, device=acc.device)
+    check(lib.pxm_acov_ess(_p(count), _p(acc), _p(tot), _p(head), _p(ring), m, C_, K, _p(ess), _p(lag), _p(ep), _p(se), _p(st),
+                           _p(scratch), _stream()))
+    return ess, lag, ep, se, st
+
+
 def reduce_l2(preds, data, invcov):
     """vdot(d, invcov d), d = data - preds (pxmcmc/mcmc.py:78-79) -> complex128 [C]."""
     p, _ = _batched(as_device(preds))

@@ -14,6 +14,7 @@ import numpy as np
 
 _SUMMARY_FIELDS = ("count", "mean", "m2", "best", "best_logpi")  # uncertainty.PosteriorSummary.to_host()
 _TAIL_FIELDS = ("q_lo", "q_hi")  # ... of a summary built with alpha (its ``alpha`` becomes the attribute summary_alpha)
+_ESS_FIELDS = ("ess", "ess_lag")  # ... of a summary built with ess_lags (which becomes the attribute summary_ess_lags)
 
 _DATASETS = (
     ("logPi", "logposterior", None),
@@ -42,13 +43,16 @@ def _summary_datasets(mcmc):
     """[(name, array)] of a sampler run with ``summary=``: ``summary_<space>_{count,mean,m2,best,best_logpi}`` (the raw
     accumulators, real-component layout; extension -- a run without a summary writes none of them), and with
     ``summary_alpha`` the quantile maps ``summary_<space>_{q_lo,q_hi}``; {"summary_alpha": alpha} then, else {}.  A summary
-    whose tails cannot be read out (``PosteriorSummary.to_host`` warns) is written without the maps and the attribute."""
+    whose tails cannot be read out (``PosteriorSummary.to_host`` warns) is written without the maps and the attribute.  With
+    ``summary_ess`` the per-chain effective sample sizes ``summary_<space>_{ess,ess_lag}`` and {"summary_ess_lags": K}."""
     out, attrs = [], {}
     for space, summ in (getattr(mcmc, "summary", None) or {}).items():
         host = summ.to_host()
-        out += [(f"summary_{space}_{k}", host[k]) for k in _SUMMARY_FIELDS + _TAIL_FIELDS if k in host]
+        out += [(f"summary_{space}_{k}", host[k]) for k in _SUMMARY_FIELDS + _TAIL_FIELDS + _ESS_FIELDS if k in host]
         if "alpha" in host:
             attrs["summary_alpha"] = float(host["alpha"])
+        if "ess_lags" in host:
+            attrs["summary_ess_lags"] = int(host["ess_lags"])
     return out, attrs
 
 
@@ -91,11 +95,12 @@ def save_mcmc(mcmc, params, outpath, filename="outputs", **kwargs):
 
 def load_summaries(data, attrs=None):
     """the ``summary_*`` datasets of a loaded run -> {space: host dict} as ``PosteriorSummary.to_host()`` returns them;
-    with the run's attributes, a space that carries ``q_lo`` / ``q_hi`` also gets its ``alpha``"""
+    with the run's attributes, a space that carries ``q_lo`` / ``q_hi`` also gets its ``alpha`` and one that carries ``ess``
+    its ``ess_lags``"""
     out = {}
     for name, arr in data.items():
         if name.startswith("summary_"):
-            for k in sorted(_SUMMARY_FIELDS + _TAIL_FIELDS, key=len, reverse=True):  # ("best_logpi" before "best")
+            for k in sorted(_SUMMARY_FIELDS + _TAIL_FIELDS + _ESS_FIELDS, key=len, reverse=True):  # ("best_logpi" before "best")
                 if name.endswith("_" + k):
                     out.setdefault(name[len("summary_"):-len(k) - 1], {})[k] = arr
                     break
@@ -103,6 +108,10 @@ def load_summaries(data, attrs=None):
         for host in out.values():
             if "q_lo" in host:
                 host["alpha"] = np.float64(attrs["summary_alpha"])
+    if attrs is not None and "summary_ess_lags" in attrs:
+        for host in out.values():
+            if "ess" in host:
+                host["ess_lags"] = np.int64(attrs["summary_ess_lags"])
     return out
 
 

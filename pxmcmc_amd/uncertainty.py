@@ -10,7 +10,9 @@ standard-deviation map, the "MAP_X" sample (plot.py:75-76, 122) and R-hat across
 :func:`moments_np`, :func:`pooled_np` and :func:`rhat_np` state the same quantities in numpy.  With ``alpha=`` it also keeps
 the k smallest and k largest samples of every element (:func:`tail_capacity`), from which ``credible_interval_range()``
 gives the numbers of :func:`credible_interval_range` on each chain's saved samples, exactly; :func:`tails_update_np` and
-:func:`tails_quantiles_np` state that in numpy.
+:func:`tails_quantiles_np` state that in numpy.  With ``ess_lags=`` it accumulates the lagged products of the saved samples,
+from which ``ess()``, ``ess_pooled()`` and ``mcse()`` give the effective sample size and the standard error of the pooled
+mean; :func:`acov_update_np`, :func:`ess_np` and :func:`ess_pooled_np` state that in numpy, :func:`autocov_np` the definition.
 """
 import warnings
 
@@ -258,6 +260,154 @@ def tails_quantiles_np(count, lo, hi, alpha, nsamples=None):
     return q_lo, q_hi
 
 
+# ---- streaming effective sample size: lagged products --------------------------------------------------
+def _ess_lags(K):
+    K = int(K)
+    if K < 2 or K > 64 or K % 2:
+        raise ValueError("ess_lags must be even with 2 <= K <= 64, got %d" % K)
+    return K
+
+
+def acov_update_np(x, count, acc, tot, head, last):
+    """the numpy statement of one ``pxm_acov_update`` on ONE chain, in place, by the recurrence without staging: ``x`` [m] the
+    sample, ``count`` = n the number of samples before it, ``acc`` [K, m] the lagged products ``acc_l = sum_{t >= l} y_t
+    y_{t-l}`` of ``y_t = x_t - x_0``, ``tot`` [m] their sum, ``head`` [K, m] the first K samples, ``last`` [K, m] the latest
+    ones (sample t in row ``t % K``).  Every product and every sum is rounded on its own, in save order; the first sample
+    zeroes ``acc`` and ``tot``, so the state needs no initialisation.  (The device adds the same terms in the same order, a
+    block of saves at a time: its ``acc`` and ``tot`` equal these after every complete block.)  ``count`` is the caller's to
+    advance."""
+    x = np.asarray(x, dtype=np.float64)
+    K, n = acc.shape[0], int(count)
+    if n == 0:
+        acc[:] = 0.0
+        tot[:] = 0.0
+    if n < K:
+        head[n] = x
+    last[n % K] = x
+    p = head[0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        y = x - p
+        tot[:] = tot + y
+        for l in range(min(n, K - 1) + 1):
+            acc[l] = acc[l] + y * (last[(n - l) % K] - p)
+
+
+def _geyer_np(rho, N):
+    """Geyer's initial monotone sequence over ``P_k = rho[2 k] + rho[2 k + 1]``, elementwise over the columns of ``rho``
+    [lmax, m] -> (ess [m], ess_lag [m]): stop at the first P_k that is not positive (a NaN included), otherwise ``P_k <-
+    min(P_k, P_{k-1})``; ``tau = -1 + 2 sum P_k``; ``ess = min(N / tau, N log10 N)``, the cap where ``tau <= 0``;
+    ``ess_lag`` the even lag of the stop, ``2 * (lmax // 2)`` where the sequence never stopped"""
+    lmax, m = rho.shape
+    total, prev = np.zeros(m), np.full(m, np.inf)
+    lag = np.full(m, -1, dtype=np.int32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for k in range(lmax // 2):
+            P = rho[2 * k] + rho[2 * k + 1]
+            going = lag < 0
+            lag[going & ~(P > 0.0)] = 2 * k
+            add = lag < 0
+            prev = np.where(add, np.minimum(P, prev), prev)
+            total = np.where(add, total + prev, total)
+        lag[lag < 0] = 2 * (lmax // 2)
+        tau, cap = -1.0 + 2.0 * total, N * np.log10(N)
+        return np.where(tau > 0.0, np.minimum(N / tau, cap), cap), lag
+
+
+def acov_gamma_np(count, acc, tot, head, last):
+    """the biased autocovariances about the chain's own mean of ONE chain from its accumulators -> (gamma [min(K, n), m],
+    mean [m]): with ``d = tot / n``, ``head_l`` (``tail_l``) the sum of the first (last) l of the ``y_t``::
+
+        gamma_l = (acc_l - d ((tot - head_l) + (tot - tail_l)) + (n - l) d^2) / n,    mean = x_0 + d
+
+    in the order of operations of ``k_acov_ess``"""
+    n, K = int(count), acc.shape[0]
+    lmax, p = min(K, n), head[0]
+    nd = float(n)
+    g = np.empty((lmax, acc.shape[1]))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        d = tot / nd
+        dd = d * d
+        hc, tc = np.zeros_like(d), np.zeros_like(d)
+        for l in range(lmax):
+            g[l] = ((acc[l] - d * ((tot - hc) + (tot - tc))) + float(n - l) * dd) / nd
+            hc = hc + (head[l] - p)
+            tc = tc + (last[(n - 1 - l) % K] - p)
+        return g, p + d
+
+
+def ess_np(count, acc, tot, head, last):
+    """the numpy statement of the per-chain part of ``pxm_acov_ess``: ``count`` [C], ``acc`` / ``head`` / ``last`` [C, K, m]
+    and ``tot`` [C, m] as :func:`acov_update_np` leaves them -> (ess float64 [C, m], ess_lag int32 [C, m]).  NaN and -1 for a
+    chain with fewer than 4 samples and where ``gamma_0`` is not positive and finite."""
+    count = np.asarray(count, dtype=np.int64).reshape(-1)
+    C, K, m = np.shape(acc)
+    ess, lag = np.full((C, m), np.nan), np.full((C, m), -1, dtype=np.int32)
+    for c, n in enumerate(int(v) for v in count):
+        if n < 4:
+            continue
+        g, _ = acov_gamma_np(n, acc[c], tot[c], head[c], last[c])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ok = (g[0] > 0.0) & (g[0] < np.inf)
+            e, la = _geyer_np(g / g[0], float(n))
+        ess[c], lag[c] = np.where(ok, e, np.nan), np.where(ok, la, -1)
+    return ess, lag
+
+
+def ess_pooled_np(count, acc, tot, head, last):
+    """the numpy statement of the pooled part of ``pxm_acov_ess`` -> (ess_pooled [m], mcse [m]) over the C' chains with
+    ``count > 0``, which must share one count n (``ValueError`` otherwise), after Vehtari et al. 2021 without rank
+    normalisation::
+
+        W = mean_c n / (n - 1) gamma_0,c;   var+ = (n - 1) / n W + sum_c (mean_c - mean of means)^2 / (C' - 1)
+        rho_l = 1 - (W - mean_c n / (n - 1) gamma_l,c) / var+;   ess_pooled = min(C' n / tau, C' n log10(C' n))
+
+    with Geyer's sum for tau, and ``mcse = sqrt(var+ / ess_pooled)``, the standard error of the pooled mean.  NaN for n < 4,
+    where a chain has no positive finite ``gamma_0`` and where ``var+`` is not positive and finite."""
+    count = np.asarray(count, dtype=np.int64).reshape(-1)
+    C, K, m = np.shape(acc)
+    on = np.flatnonzero(count > 0)
+    nan = np.full(m, np.nan)
+    if on.size >= 2 and count[on].min() != count[on].max():
+        raise ValueError("ess_pooled_np: the pooled ESS needs one common sample count, the chains hold between %d and %d samples"
+                         % (count[on].min(), count[on].max()))
+    if on.size == 0 or count[on[0]] < 4:
+        return nan, nan.copy()
+    n = int(count[on[0]])
+    nd, cp, lmax = float(n), float(on.size), min(K, n)
+    f = nd / (nd - 1.0)
+    G, sm, means, bad = np.zeros((lmax, m)), np.zeros(m), [], np.zeros(m, dtype=bool)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for c in on:
+            g, mean = acov_gamma_np(n, acc[c], tot[c], head[c], last[c])
+            bad |= ~((g[0] > 0.0) & (g[0] < np.inf))
+            G = G + f * g
+            sm = sm + mean
+            means.append(mean)
+        mbar, W = sm / cp, G[0] / cp
+        ssq = np.zeros(m)
+        for mean in means:
+            dm = mean - mbar
+            ssq = ssq + dm * dm
+        varp = (nd - 1.0) / nd * W
+        if on.size > 1:
+            varp = varp + ssq / (cp - 1.0)
+        ok = ~bad & (varp > 0.0) & (varp < np.inf)
+        e, _ = _geyer_np(1.0 - (W - G / cp) / varp, cp * nd)
+        e = np.where(ok, e, np.nan)
+        return e, np.sqrt(varp / e)
+
+
+def autocov_np(chain, K):
+    """the biased autocovariances of ONE chain [n, m] at lags 0 ... min(K, n) - 1 by their definition, in long double on the
+    pivot-shifted samples: ``gamma_l = sum_{t >= l} (y_t - ybar) (y_{t-l} - ybar) / n`` with ``y_t = x_t - x_0`` -> long double
+    [min(K, n), m].  The error model of the accumulators is measured against this."""
+    x = _components(chain)
+    n = x.shape[0]
+    y = x.astype(np.longdouble) - x[0].astype(np.longdouble)
+    z = y - y.sum(axis=0) / np.longdouble(n)
+    return np.stack([(z[l:] * z[:n - l]).sum(axis=0) / np.longdouble(n) for l in range(min(int(K), n))])
+
+
 class PosteriorSummary:
     """Device accumulators of a chain batch: per chain the sample count, the running mean and the sum of squared deviations
     of every parameter (Welford's recurrence, ``pxm_moments_update``), and the sample of highest log posterior seen so far.
@@ -275,6 +425,9 @@ class PosteriorSummary:
         alpha' <= alpha exactly.  ``None``: no tails
     :param nsamples: the number of ``update`` calls the run will make per chain (needed with ``alpha``); a chain updated more
         often keeps its first ``nsamples`` samples in the tails and :meth:`credible_interval` then raises
+    :param ess_lags: K, even with 2 <= K <= 64: also accumulate, per chain and real component, the lagged products of the
+        samples at lags below K (``pxm_acov_update``), from which :meth:`ess`, :meth:`ess_pooled` and :meth:`mcse` are read.
+        ``None``: none
 
     Intervals are per chain.  A pooled interval over the chain batch is deliberately not offered: exact pooling needs k
     proportional to the pooled sample count, which costs as much as the chain.
@@ -287,8 +440,9 @@ class PosteriorSummary:
 
     FIELDS = ("count", "mean", "m2", "best", "best_logpi")
     TAIL_FIELDS = ("alpha", "q_lo", "q_hi")  # ``to_host()`` of a summary built with ``alpha``
+    ESS_FIELDS = ("ess_lags", "ess", "ess_lag")  # ... of a summary built with ``ess_lags``
 
-    def __init__(self, nchains, nparams, complex_, best=True, device=None, alpha=None, nsamples=None):
+    def __init__(self, nchains, nparams, complex_, best=True, device=None, alpha=None, nsamples=None, ess_lags=None):
         self.nchains, self.nparams, self.complex = int(nchains), int(nparams), bool(complex_)
         if self.nchains < 1 or self.nparams < 1:
             raise ValueError("PosteriorSummary needs nchains >= 1 and nparams >= 1")
@@ -300,6 +454,8 @@ class PosteriorSummary:
                 raise ValueError("PosteriorSummary: alpha needs nsamples, the number of updates the tails are sized for")
             self.tail_slots = tail_capacity(alpha, nsamples)
             self.alpha = float(alpha)
+        self.ess_lags = None if ess_lags is None else _ess_lags(ess_lags)
+        self._acc = self._tot = self._head = self._ring = None
         dev = ops.device() if device is None else device
         C, m = self.nchains, self.m
         self._count = torch.zeros(C, dtype=torch.int64, device=dev)
@@ -314,13 +470,20 @@ class PosteriorSummary:
             self._stage = torch.zeros((C, ops.tails_stage_depth(), m), dtype=torch.float64, device=dev)
             self._thr_lo = torch.zeros((C, m), dtype=torch.float64, device=dev)
             self._thr_hi = torch.zeros_like(self._thr_lo)
+        if self.ess_lags is not None:  # (pxm_acov_update needs no initialisation)
+            K = self.ess_lags
+            self._acc = torch.empty((C, K, m), dtype=torch.float64, device=dev)
+            self._head = torch.empty_like(self._acc)
+            self._tot = torch.empty((C, m), dtype=torch.float64, device=dev)
+            self._ring = torch.empty((C, K - 1 + ops.acov_stage_depth(), m), dtype=torch.float64, device=dev)
 
     # ---- accumulation -----------------------------------------------------------------------------------------------
     def update(self, X, logpi=None, mask=None):
         """add one sample per chain: ``X`` [C, nparams] on the device (complex128, or float64 when ``complex_`` is False),
         ``logpi`` [C] its log posterior (float64 or complex128: the real part; needed with ``best``), ``mask`` an int32 [C]
         device tensor or a sequence of chain flags -- chains with a zero keep their accumulators untouched.  One fused pass
-        and one small launch on the current stream, behind the tails pass of a summary built with ``alpha``.  With contiguous device tensors for ``X``, ``logpi`` and ``mask`` nothing is
+        and one small launch on the current stream, behind the lagged-product pass of a summary built with ``ess_lags`` and the
+        tails pass of one built with ``alpha``.  With contiguous device tensors for ``X``, ``logpi`` and ``mask`` nothing is
         allocated or copied (the form a captured graph takes); a host ``mask`` or ``logpi`` is uploaded first (a small
         synchronous copy), and a non-contiguous ``X`` is copied."""
         X = ops.as_device(X) if not (isinstance(X, torch.Tensor) and X.is_cuda) else X
@@ -342,7 +505,9 @@ class PosteriorSummary:
             logpi = None
         if mask is not None and not (isinstance(mask, torch.Tensor) and mask.is_cuda):
             mask = torch.as_tensor(np.asarray(mask) != 0, dtype=torch.int32).to(self._mean.device)
-        if self.alpha is not None:  # reads the counts the moments pass is about to advance
+        if self.ess_lags is not None:  # reads the counts the moments pass is about to advance
+            ops.acov_update(X, self._count, self._acc, self._tot, self._head, self._ring, mask=mask)
+        if self.alpha is not None:  # (so does this)
             ops.tails_update(X, self._count, self._lo, self._hi, self._thr_lo, self._thr_hi, self._stage, self.nsamples, mask=mask)
         ops.moments_update(X, self._count, self._mean, self._m2, mask=mask, logpi=logpi, best_logpi=self._best_logpi,
                            best_x=self._best_x)
@@ -432,11 +597,81 @@ class PosteriorSummary:
         ``B = ops.tails_stage_depth()`` (0 without ``alpha``)"""
         return 0 if self.alpha is None else (2 * self.tail_slots + 2 + ops.tails_stage_depth()) * 8 * self.nchains * self.m
 
+    # ---- effective sample size from the lagged products ------------------------------------------------------------------
+    def _ess(self, pooled):
+        if self.ess_lags is None:
+            raise ValueError("this summary was built without ess_lags: it keeps no lagged products")
+        return ops.acov_ess(self._count, self._acc, self._tot, self._head, self._ring, pooled=pooled)
+
+    def ess_readout(self, pooled=True):
+        """ONE read-out of the lagged products -> dict of device tensors ``ess`` [C, m], ``ess_lag`` int32 [C, m],
+        ``ess_pooled`` [m], ``mcse`` [m] and ``stats`` [3] (min ESS over the defined values, undefined count, truncated
+        count), all in the real-component layout.  ``pooled=False`` leaves ``ess_pooled`` and ``mcse`` out and takes chains
+        of any counts; with them, differing counts raise PxmError.  :meth:`ess`, :meth:`ess_lag`, :meth:`ess_pooled`,
+        :meth:`mcse` and :meth:`ess_stats` each make such a read-out of their own: take several results from this call."""
+        ess, lag, ep, se, st = self._ess(pooled)
+        out = {"ess": ess, "ess_lag": lag, "stats": st}
+        if pooled:
+            out.update(ess_pooled=ep, mcse=se)
+        return out
+
+    def ess_report(self, what="state"):
+        """one line for a log, from one read-out: smallest and median per-chain ESS over ``what``, the fraction of truncated
+        values and the largest Monte-Carlo standard error of the pooled mean (left out, with the reason, when the chains hold
+        different counts)"""
+        try:
+            r, why = self.ess_readout(True), ""
+        except ops.PxmError:
+            r, why = self.ess_readout(False), "; no pooled MCSE: the chains stopped at different counts"
+        lo, nundef, ntrunc = (float(v) for v in r["stats"].cpu().numpy())
+        defined = r["ess"].numel() - int(nundef)
+        if not defined:
+            return f"ESS of the {what}: undefined everywhere (fewer than 4 samples per chain, or nothing moved)"
+        line = (f"ESS per chain over the {what} (lags below {self.ess_lags}): min {lo:.1f}, "
+                f"median {float(r['ess'][~r['ess'].isnan()].median()):.1f}; {ntrunc / defined:.1%} truncated "
+                f"(upper bounds: use more lags or a larger ngap)")
+        if "mcse" in r:
+            se = r["mcse"][~r["mcse"].isnan()]
+            why = f"; max MCSE of the pooled mean {float(se.max()):.3e}" if se.numel() else "; MCSE undefined"
+        return line + why
+
+    def ess(self):
+        """effective sample size per chain and real component, [C, m] (device): Geyer's initial monotone sequence over the
+        autocorrelations at lags below ``ess_lags``; NaN for a chain with fewer than 4 samples and for a component that
+        never moved.  Where :meth:`ess_lag` equals ``2 * (min(ess_lags, n) // 2)`` the sequence did not end within the lags
+        kept and the value is an upper bound: use more lags, or a larger ``ngap``."""
+        return self._ess(False)[0]
+
+    def ess_lag(self):
+        """the even lag at which the sequence of :meth:`ess` stopped, int32 [C, m] (device; -1 where ess is NaN)"""
+        return self._ess(False)[1]
+
+    def ess_pooled(self):
+        """effective sample size of the whole chain batch per real component, [m] (device), after Vehtari et al. 2021 without
+        rank normalisation; raises PxmError when the chains' counts differ.  Over several ranks no pooled value is offered:
+        sum the per-chain values where R-hat is close to 1."""
+        return self._ess(True)[2]
+
+    def mcse(self):
+        """Monte-Carlo standard error of :meth:`pooled_mean` per real component, [m] (device): ``sqrt(var+ / ess_pooled)``"""
+        return self._ess(True)[3]
+
+    def ess_stats(self):
+        """(smallest per-chain ESS over the values that are defined, number that are not, number that are truncated)"""
+        st = self._ess(False)[4].cpu().numpy()
+        return float(st[0]), int(st[1]), int(st[2])
+
+    def ess_bytes(self):
+        """device bytes of the lagged products, the first saves and the ring: ``(3 K + B) * 8 * C * m`` with
+        ``B = ops.acov_stage_depth()`` (0 without ``ess_lags``)"""
+        return 0 if self.ess_lags is None else (3 * self.ess_lags + ops.acov_stage_depth()) * 8 * self.nchains * self.m
+
     # ---- host side --------------------------------------------------------------------------------------------------
     def to_host(self):
         """plain dict of numpy arrays: ``count`` int64 [C], ``mean`` / ``m2`` float64 [C, m] in the real-component layout
         and, with ``best``, ``best`` [C, nparams] (complex for a complex state) and ``best_logpi`` [C]; a summary built with
-        ``alpha`` adds ``alpha`` (float64 scalar) and its quantiles ``q_lo`` / ``q_hi`` [C, m] in the real-component layout.
+        ``alpha`` adds ``alpha`` (float64 scalar) and its quantiles ``q_lo`` / ``q_hi`` [C, m] in the real-component layout,
+        one built with ``ess_lags`` adds ``ess_lags`` (int64 scalar), ``ess`` float64 [C, m] and ``ess_lag`` int32 [C, m].
         Where the tails cannot be read out (a chain updated more than ``nsamples`` times: ``PxmError`` from
         :meth:`credible_interval`) these three are left out with a ``RuntimeWarning``, so that the moments and the best
         sample of the run can still be saved."""
@@ -451,6 +686,9 @@ class PosteriorSummary:
                 warnings.warn("PosteriorSummary.to_host: no credible intervals (%s)" % e, RuntimeWarning, stacklevel=2)
             else:
                 out.update(alpha=np.float64(self.alpha), q_lo=q_lo.cpu().numpy(), q_hi=q_hi.cpu().numpy())
+        if self.ess_lags is not None:
+            ess, lag = self._ess(False)[:2]
+            out.update(ess_lags=np.int64(self.ess_lags), ess=ess.cpu().numpy(), ess_lag=lag.cpu().numpy())
         return out
 
     @staticmethod
@@ -458,7 +696,9 @@ class PosteriorSummary:
         """concatenate the chains of several ``to_host()`` dicts (one per rank, in rank order) -> one such dict;
         ``rhat_np(d["count"], d["mean"], d["m2"])`` of the result is R-hat over all the chains of a multi-rank run.  When
         every dict carries the ``TAIL_FIELDS``, with one common ``alpha``, so does the result: the intervals stay per chain
-        (exact pooling over chains would need tails as long as the pooled chain)"""
+        (exact pooling over chains would need tails as long as the pooled chain).  Likewise the ``ESS_FIELDS`` when every
+        dict carries them with one ``ess_lags``: per-chain values; a pooled ESS over ranks is not offered -- sum the per-chain
+        values where R-hat is close to 1"""
         dicts = list(dicts)
         if not dicts:
             raise ValueError("merge: no summaries")
@@ -470,4 +710,7 @@ class PosteriorSummary:
                 raise ValueError("merge: the summaries were built with different alpha: %s" % sorted(alphas))
             out["alpha"] = np.float64(alphas.pop())
             out.update({k: np.concatenate([np.asarray(d[k]) for d in dicts], axis=0) for k in ("q_lo", "q_hi")})
+        if all(k in d for d in dicts for k in PosteriorSummary.ESS_FIELDS) and len({int(d["ess_lags"]) for d in dicts}) == 1:
+            out["ess_lags"] = np.int64(dicts[0]["ess_lags"])
+            out.update({k: np.concatenate([np.asarray(d[k]) for d in dicts], axis=0) for k in ("ess", "ess_lag")})
         return out

@@ -24,8 +24,18 @@ Cost of one streaming-summary update at the benchmark siz
                           per save (events, summed) plus pxm_quantile_range of it at the end (held a ring of rows and four
                           chains at a time, see time_tails: same bytes, bounded device memory).
               A run with tails must not take longer than the route without them: the script exits with an error if one does.
+  ess         the streaming effective sample size of a run of N = 1000 saves at K = 32 lags, same two layouts and samples:
+                steady    pxm_acov_update at the end of the run, cold: one save that only copies its row into the ring and
+                          one that also merges its block of B = 16 into the lagged products; a steady-state save is
+                          (15 + 1) / 16 of them, beside the cold pxm_moments_update of the same layout;
+                readout   one pxm_acov_ess with the pooled outputs (host-timed: it synchronises);
+                run       the N saves (device events around every pxm_acov_update, summed) plus the read-out, against
+                parent    the route without the feature: one row copy per save into a device-resident chain (as for the
+                          tails) plus, at the end, the same K lagged sums of the mean-centred chain with torch, four chains
+                          at a time.
+              The same acceptance condition as for the tails.
 
-    python scripts/timing/time_summary.py [--out FILE.json] [--sections moments,tails,iteration]
+    python scripts/timing/time_summary.py [--out FILE.json] [--sections moments,tails,ess,iteration]
 """
 import argparse
 import contextlib
@@ -50,6 +60,7 @@ L, B, J_MIN, C = 256, 2.0, 2, 16
 HBM_RATE = 8e12  # bytes/s
 LMDA, DELTA = 1e-6, 1e-7
 TAIL_N, TAIL_ALPHA = 1000, 0.05
+ESS_N, ESS_LAGS = 1000, 32
 PARENT_RING, PARENT_BLOCK = 64, 4  # rows of the copy ring, chains per select of the route without tails (device memory bound)
 
 
@@ -195,10 +206,97 @@ def time_tails(X, cplx):
     return out
 
 
+def time_ess(X, cplx):
+    """the ``ess`` block of the module docstring for one layout (``cplx`` as for time_tails)"""
+    C_, n = X.shape
+    m = 2 * n if cplx else n
+    N, K = ESS_N, ESS_LAGS
+    B_ = ops.acov_stage_depth()
+    dev = X.device
+    rows = (lambda: torch.view_as_real(X).reshape(C_, m)) if cplx else (lambda: X)
+    out = {"m": m, "K": K, "N": N, "ess_bytes": (3 * K + B_) * 8 * C_ * m, "chain_bytes": N * 8 * C_ * m}
+
+    s = PosteriorSummary(C_, n, cplx, best=False)
+    med, times = cold_ms(lambda: s.update(X), prep=X.normal_)
+    out["moments_cold"] = {"ms": med, "regions_ms": times}
+    del s
+
+    count = torch.zeros(C_, dtype=torch.int64, device=dev)
+    acc = torch.empty((C_, K, m), dtype=torch.float64, device=dev)
+    head, tot = torch.empty_like(acc), torch.empty((C_, m), dtype=torch.float64, device=dev)
+    ring = torch.empty((C_, K - 1 + B_, m), dtype=torch.float64, device=dev)
+    save = lambda: ops.acov_update(rows(), count, acc, tot, head, ring)  # noqa: E731
+
+    def one_save(i, a, b):
+        X.normal_()
+        a.record()
+        save()
+        b.record()
+        count.add_(1)
+
+    run_ms = summed_events_ms(N, one_save)
+    assert count.tolist() == [N] * C_
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ess, lag, pooled, mcse, stats = ops.acov_ess(count, acc, tot, head, ring)
+    torch.cuda.synchronize()
+    readout_ms = (time.perf_counter() - t0) * 1e3
+    out["saves_ms"], out["readout_ms"], out["run_ms"] = run_ms, readout_ms, run_ms + readout_ms
+    st = stats.cpu().numpy()
+    out["ess"] = {"min": float(st[0]), "median": float(ess.median()), "nan": int(st[1]), "truncated": int(st[2]),
+                  "pooled_median": float(pooled.median()), "mcse_max": float(mcse.max())}
+    last_merge = N // B_ * B_ - 1  # the last save of the run that completes a block
+    count.fill_(last_merge - 1)
+    med_s, times = cold_ms(save, prep=X.normal_)
+    out["stage_cold"] = {"ms": med_s, "regions_ms": times}
+    count.fill_(last_merge)
+    med_m, times = cold_ms(save, prep=X.normal_)
+    out["merge_cold"] = {"ms": med_m, "regions_ms": times}
+    med = ((B_ - 1) * med_s + med_m) / B_
+    out["steady_cold"] = {"ms": med}
+    out["steady_over_moments"] = med / out["moments_cold"]["ms"]
+    del acc, head, tot, ring, ess, lag, pooled, mcse
+    torch.cuda.empty_cache()
+
+    # The route without the feature: the row copies of time_tails, then the K lagged sums of the mean-centred chain with
+    # torch, on the columns of PARENT_BLOCK chains at a time (fresh samples: the same bytes and sweeps as on the whole chain).
+    copy_ring = torch.empty((PARENT_RING, C_ * m), dtype=torch.float64, device=dev)
+    src = (lambda: torch.view_as_real(X).reshape(C_, m)) if cplx else (lambda: X.real)
+
+    def one_copy(i, a, b):
+        X.normal_()
+        a.record()
+        copy_ring[i % PARENT_RING].view(C_, m).copy_(src())
+        b.record()
+
+    copies_ms = summed_events_ms(N, one_copy)
+    del copy_ring
+    torch.cuda.empty_cache()
+    assert C_ % PARENT_BLOCK == 0
+    chain = torch.empty((N, PARENT_BLOCK * m), dtype=torch.float64, device=dev)
+    gamma = torch.empty((K, PARENT_BLOCK * m), dtype=torch.float64, device=dev)
+    sums_ms = 0.0
+    for _ in range(C_ // PARENT_BLOCK):
+        chain.normal_()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        chain -= chain.mean(dim=0)
+        for l in range(K):
+            torch.sum(chain[l:] * chain[: N - l], dim=0, out=gamma[l])
+        gamma /= N
+        torch.cuda.synchronize()
+        sums_ms += (time.perf_counter() - t0) * 1e3
+    out["parent"] = {"copies_ms": copies_ms, "lagged_sums_ms": sums_ms, "run_ms": copies_ms + sums_ms, "block_bytes": chain.numel() * 8}
+    out["run_over_parent"] = out["run_ms"] / out["parent"]["run_ms"]
+    del chain, gamma
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--sections", default="moments,tails,iteration")
+    ap.add_argument("--sections", default="moments,tails,ess,iteration")
     a = ap.parse_args()
     sections = set(a.sections.split(","))
     data = np.random.default_rng(0).normal(size=L * (2 * L - 1))
@@ -235,6 +333,9 @@ def main():
     if "tails" in sections:
         res["tails_realparts"] = time_tails(X, False)
         res["tails_complex"] = time_tails(X, True)
+    if "ess" in sections:
+        res["ess_realparts"] = time_ess(X, False)
+        res["ess_complex"] = time_ess(X, True)
 
     if "iteration" in sections:
         p = PxMCMCParams(lmda=LMDA, delta=DELTA, nsamples=1, nburn=0, ngap=1, verbosity=0)
@@ -259,7 +360,7 @@ def main():
             json.dump(res, f, indent=1)
     slower = {k: v["run_over_parent"] for k, v in res.items() if isinstance(v, dict) and v.get("run_over_parent", 0) > 1}
     if slower:  # the acceptance condition of DESIGN.md section 15
-        sys.exit("a run with tails takes longer than the route without them: %s" % slower)
+        sys.exit("a streaming run takes longer than the route without it: %s" % slower)
 
 
 if __name__ == "__main__":
