@@ -15,12 +15,7 @@
 // a block does so once per ACOV_STAGE saves.  The first block starts its sums from zero instead of reading them, so the
 // state needs no initialisation.  The read-out folds the saves of the incomplete last block on the fly, in the order a merge
 // would use, and writes nothing to the state.
-#include "common.h"
-
-#include <cmath>
-#include <limits>
-#include <string>
-#include <vector>
+#include "summary.h"
 
 #include "../../include/pxmcmc_amd.h"
 
@@ -31,7 +26,6 @@ constexpr int ACOV_STAGE = 16;         // B: saves of a block
 constexpr int ACOV_MAX_LAGS = 64;      // largest K
 constexpr int ACOV_MAX_BLOCKS = 4096;  // per chain; the rest of a row is covered by the grid-stride loop
 constexpr int ESS_THREADS = 64;        // lanes of a read-out workgroup
-constexpr int ACOV_FIN_BLOCKS = 1024;  // partial (min ESS, NaN count, truncated count) triples of the read-out
 
 __device__ __forceinline__ double acov_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
@@ -155,14 +149,15 @@ __device__ __forceinline__ double acov_total(const double* __restrict__ tr, cons
 // The read-out, one lane per element, chains in index order.  Per chain: d = tot / n, gamma_l = (acc_l - d ((tot - head_l) +
 // (tot - tail_l)) + (n - l) d^2) / n with head_l (tail_l) the sum of the first (last) l of the y_t, rho_l = gamma_l /
 // gamma_0, Geyer's sum, ess [C][m] and ess_lag [C][m] (NaN and -1 for n < 4 or a gamma_0 that is not positive and finite).
-// Pooled (ess_pooled non-null; the host has checked that the n_part chains with samples share the count n_common):
+// Pooled (ess_pooled non-null; the host has read the counts and checked that the n_part >= 1 chains with samples share the
+// count n_common, 0 when no chain has any):
 // G_l = sum_c n / (n - 1) gamma_l,c in the registers of the lane, W = G_0 / C', var+ = (n - 1) / n W + sum_c (mean_c -
 // mean of means)^2 / (C' - 1) with mean_c = p_c + d_c, rho_l = 1 - (W - G_l / C') / var+, the same Geyer sum,
 // ESS = min(C' n / tau, C' n log10(C' n)) and mcse = sqrt(var+ / ESS).  Every product and sum is rounded on its own:
 // uncertainty.ess_np / ess_pooled_np state the same sequence of operations.  Each workgroup leaves (min ESS over its non-NaN
-// values, NaN count, truncated count) of the per-chain values in part[3 b].  The lag loops run to K at run time and the
-// G_l are indexed by the lag, so they live in LDS, one column per lane (a register array indexed so would go to scratch
-// memory); the workgroup is one wave to keep that at 32 KiB.
+// values, NaN count, truncated count) of the per-chain values in part[3 b] (summary.h).  The lag loops run to K at run time
+// and the G_l are indexed by the lag, so they live in LDS, one column per lane (a register array indexed so would go to
+// scratch memory); the workgroup is one wave to keep that at 32 KiB.
 __global__ __launch_bounds__(ESS_THREADS) void k_acov_ess(const int64_t* __restrict__ count, const double* __restrict__ acc,
                                                            const double* __restrict__ tot, const double* __restrict__ head,
                                                            const double* __restrict__ ring, int64_t m, int C, int K,
@@ -267,69 +262,10 @@ __global__ __launch_bounds__(ESS_THREADS) void k_acov_ess(const int64_t* __restr
     ess_pooled[e] = vp;
     if (mcse) mcse[e] = se;
   }
-  if (!part) return;
-  __shared__ double s_min[ESS_THREADS], s_nan[ESS_THREADS], s_tr[ESS_THREADS];
-  s_min[threadIdx.x] = emin;
-  s_nan[threadIdx.x] = nnan;
-  s_tr[threadIdx.x] = ntrunc;
-  __syncthreads();
-  for (int w = ESS_THREADS / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      s_min[threadIdx.x] = fmin(s_min[threadIdx.x], s_min[threadIdx.x + w]);
-      s_nan[threadIdx.x] += s_nan[threadIdx.x + w];
-      s_tr[threadIdx.x] += s_tr[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    part[3 * blockIdx.x] = s_min[0];
-    part[3 * blockIdx.x + 1] = s_nan[0];
-    part[3 * blockIdx.x + 2] = s_tr[0];
-  }
-}
-
-// second stage: stats = (min ESS over the non-NaN values, or NaN when there is none; NaN count; truncated count)
-__global__ __launch_bounds__(ACOV_THREADS) void k_acov_stats(const double* __restrict__ part, int nblocks,
-                                                             double* __restrict__ stats) {
-  __shared__ double s_min[ACOV_THREADS], s_nan[ACOV_THREADS], s_tr[ACOV_THREADS];
-  double emin = INFINITY, nnan = 0.0, ntrunc = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += ACOV_THREADS) {
-    emin = fmin(emin, part[3 * b]);
-    nnan += part[3 * b + 1];
-    ntrunc += part[3 * b + 2];
-  }
-  s_min[threadIdx.x] = emin;
-  s_nan[threadIdx.x] = nnan;
-  s_tr[threadIdx.x] = ntrunc;
-  __syncthreads();
-  for (int w = ACOV_THREADS / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      s_min[threadIdx.x] = fmin(s_min[threadIdx.x], s_min[threadIdx.x + w]);
-      s_nan[threadIdx.x] += s_nan[threadIdx.x + w];
-      s_tr[threadIdx.x] += s_tr[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    stats[0] = s_min[0] == INFINITY ? acov_nan() : s_min[0];
-    stats[1] = s_nan[0];
-    stats[2] = s_tr[0];
-  }
-}
-
-static inline int acov_fin_blocks(int64_t m) {
-  const int64_t b = (m + ESS_THREADS - 1) / ESS_THREADS;
-  return (int)(b < ACOV_FIN_BLOCKS ? b : ACOV_FIN_BLOCKS);
+  if (part) stats_partial<false, ESS_THREADS / 64>(part, emin, nnan, ntrunc);
 }
 
 static inline bool acov_lags_ok(int64_t K) { return K >= 2 && K <= ACOV_MAX_LAGS && K % 2 == 0; }
-
-// doubles of C chains of `rows` rows of m elements, -1 on overflow
-static inline int64_t acov_doubles(int64_t m, int C, int64_t rows) {
-  if (m < 1 || C < 1 || rows < 1) return -1;
-  if (rows > INT64_MAX / m || rows * m > INT64_MAX / 8 / C) return -1;
-  return (int64_t)C * rows * m;
-}
 
 }  // namespace pxm
 
@@ -339,25 +275,20 @@ extern "C" {
 
 int pxm_acov_stage_depth(void) { return ACOV_STAGE; }
 
-int64_t pxm_acov_state_doubles(int64_t m, int C, int K) { return acov_lags_ok(K) ? acov_doubles(m, C, K) : -1; }
+int64_t pxm_acov_state_doubles(int64_t m, int C, int K) { return acov_lags_ok(K) ? rows_doubles(m, C, K) : -1; }
 
-int64_t pxm_acov_ring_doubles(int64_t m, int C, int K) { return acov_lags_ok(K) ? acov_doubles(m, C, K - 1 + ACOV_STAGE) : -1; }
+int64_t pxm_acov_ring_doubles(int64_t m, int C, int K) { return acov_lags_ok(K) ? rows_doubles(m, C, K - 1 + ACOV_STAGE) : -1; }
 
-int64_t pxm_acov_scratch_doubles(int64_t m) { return m >= 1 ? 3 * (int64_t)acov_fin_blocks(m) : -1; }
+int64_t pxm_acov_scratch_doubles(int64_t m) { return stats_scratch_doubles(m, ESS_THREADS, 3); }
 
 int pxm_acov_update(const double* x, int x_stride, const int64_t* count, double* acc, double* tot, double* head, double* ring,
                     const int* mask, int64_t m, int C, int K, pxm_stream_t stream) {
-  PXM_REQUIRE(C >= 1 && C <= 65535, "pxm_acov_update: need 1 <= C <= 65535");
-  PXM_REQUIRE(m >= 1, "pxm_acov_update: need m >= 1");
+  hipStream_t st = (hipStream_t)stream;
+  if (save_check("pxm_acov_update", m, C, x_stride, st)) return -1;
   PXM_REQUIRE(acov_lags_ok(K), "pxm_acov_update: K must be even with 2 <= K <= 64");
   PXM_REQUIRE(pxm_acov_ring_doubles(m, C, K) > 0, "pxm_acov_update: C (K - 1 + B) m overflows");
   PXM_REQUIRE(x && count && acc && tot && head && ring, "pxm_acov_update: null buffer");
-  PXM_REQUIRE(x_stride == 1 || x_stride == 2, "pxm_acov_update: x_stride must be 1 (float64) or 2 (real parts of complex128)");
-  hipStream_t st = (hipStream_t)stream;
-  note_stream(st);
-  int64_t nb = (m + ACOV_THREADS - 1) / ACOV_THREADS;  // one element per lane, 8-byte coalesced accesses
-  nb = nb > ACOV_MAX_BLOCKS ? ACOV_MAX_BLOCKS : nb;
-  const dim3 grid((unsigned)nb, (unsigned)C);
+  const dim3 grid = rows_grid(m, ACOV_THREADS, ACOV_MAX_BLOCKS, C);  // 8-byte coalesced accesses
   const int64_t ldx = m * x_stride;
 #define ACOV_LAUNCH(KMAX) \
   hipLaunchKernelGGL((k_acov_update<KMAX>), grid, dim3(ACOV_THREADS), 0, st, x, ldx, x_stride, count, acc, tot, head, ring, mask, m, K)
@@ -382,32 +313,17 @@ int pxm_acov_ess(const int64_t* count, const double* acc, const double* tot, con
   PXM_REQUIRE(!stats || scratch, "pxm_acov_ess: stats needs scratch");
   hipStream_t st = (hipStream_t)stream;
   note_stream(st);
-  int64_t n_common = 0;
-  int n_part = 0;
-  if (ess_pooled) {  // the pooled estimate is over chains of one length: read the counts back (a post-run call, it synchronises)
-    std::vector<int64_t> h(C);
-    PXM_HIP(hipMemcpyAsync(h.data(), count, sizeof(int64_t) * C, hipMemcpyDeviceToHost, st));
-    PXM_HIP(hipStreamSynchronize(st));
-    int64_t lo = std::numeric_limits<int64_t>::max(), hi = 0;
-    for (int64_t v : h)
-      if (v > 0) {
-        ++n_part;
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
-      }
-    if (n_part >= 2 && lo != hi) {
-      set_error("pxm_acov_ess: the pooled ESS needs one common sample count, the chains hold between " + std::to_string(lo) + " and " +
-                std::to_string(hi) + " samples (the per-chain values do not: call without ess_pooled)");
-      return -1;
-    }
-    if (n_part >= 1) n_common = lo;
-  }
-  const int nb = acov_fin_blocks(m);
-  hipLaunchKernelGGL(k_acov_ess, dim3(nb), dim3(ESS_THREADS), 0, st, count, acc, tot, head, ring, m, C, K, n_common, n_part, ess, ess_lag,
+  Counts k;  // the pooled estimate is over chains of one length
+  if (ess_pooled && (read_counts(count, C, st, k) ||
+                     require_common_count(k, "pxm_acov_ess: the pooled ESS", "the per-chain values do not: call without ess_pooled")))
+    return -1;
+  const int64_t n_common = k.n_part >= 1 ? k.lo : 0;
+  const int nb = stats_blocks(m, ESS_THREADS);
+  hipLaunchKernelGGL(k_acov_ess, dim3(nb), dim3(ESS_THREADS), 0, st, count, acc, tot, head, ring, m, C, K, n_common, k.n_part, ess, ess_lag,
                      ess_pooled, mcse, stats ? scratch : nullptr);
   PXM_HIP(hipGetLastError());
   if (stats) {
-    hipLaunchKernelGGL(k_acov_stats, dim3(1), dim3(ACOV_THREADS), 0, st, scratch, nb, stats);
+    hipLaunchKernelGGL((k_summary_stats<false, 2>), dim3(1), dim3(STATS_THREADS), 0, st, scratch, nb, stats);
     PXM_HIP(hipGetLastError());
   }
   return 0;

@@ -2,11 +2,7 @@
 // [C, m] float64 batch, accumulated on the device at the samplers' save points, and their reduction over chains (pooled
 // moments, Gelman-Rubin R-hat).  Replaces the np.mean / np.std over a saved chain and the argmax(logposterior) look-up of the
 // reference's plot scripts, which need the whole chain in host memory.
-#include "common.h"
-
-#include <cmath>
-#include <limits>
-#include <vector>
+#include "summary.h"
 
 #include "../../include/pxmcmc_amd.h"
 
@@ -15,7 +11,6 @@ namespace pxm {
 constexpr int MOM_THREADS = 256;
 constexpr int MOM_UNROLL = 4;         // independent 16-byte loads in flight per array and lane
 constexpr int MOM_MAX_BLOCKS = 2048;  // per chain; the rest of a row is covered by the grid-stride loop
-constexpr int FIN_MAX_BLOCKS = 1024;  // partial (max R-hat, NaN count) pairs of the finalize launch
 
 // elements j, j + 1 of the sample: XS = 1 a dense float64 row (j even relative to a 16-byte boundary), XS = 2 the real
 // parts of a complex128 row (every element its own aligned 16-byte load)
@@ -128,7 +123,9 @@ __global__ __launch_bounds__(MOM_THREADS) void k_moments_advance(int64_t* __rest
 // Reduction over chains, one lane per element, chains in index order (deterministic).  Pooled moments by Chan's pairwise
 // merge over the chains with count > 0; R-hat over those chains when they share one count n_common >= 2 (n_common = 0:
 // undefined, NaN).  Every product and sum is rounded on its own (no contraction): uncertainty.rhat_np states the same
-// sequence of operations.  Each workgroup leaves (max R-hat over its non-NaN elements, its NaN count) in part[2 b].
+// sequence of operations.  n_common and n_part come from the host, which has read the counts: n_common = the common count
+// when n_part >= 2 chains take part and it is >= 2, else 0.  Each workgroup leaves (max R-hat over its non-NaN elements, its
+// NaN count) in part[2 b] (summary.h).
 __global__ __launch_bounds__(MOM_THREADS) void k_moments_finalize(const int64_t* __restrict__ count,
                                                                   const double* __restrict__ mean,
                                                                   const double* __restrict__ m2, int C, int64_t m,
@@ -178,55 +175,8 @@ __global__ __launch_bounds__(MOM_THREADS) void k_moments_finalize(const int64_t*
       else rmax = fmax(rmax, r);
     }
   }
-  if (!part) return;
-  __shared__ double s_max[MOM_THREADS], s_nan[MOM_THREADS];
-  s_max[threadIdx.x] = rmax;
-  s_nan[threadIdx.x] = nnan;
-  __syncthreads();
-  for (int w = MOM_THREADS / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      s_max[threadIdx.x] = fmax(s_max[threadIdx.x], s_max[threadIdx.x + w]);
-      s_nan[threadIdx.x] += s_nan[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = s_max[0];
-    part[2 * blockIdx.x + 1] = s_nan[0];
-  }
+  if (part) stats_partial<true, MOM_THREADS / 64>(part, rmax, nnan);
 }
-
-// second stage: stats = (max R-hat over the non-NaN elements, or NaN when there is none; number of NaN elements)
-__global__ __launch_bounds__(MOM_THREADS) void k_moments_stats(const double* __restrict__ part, int nblocks,
-                                                               double* __restrict__ stats) {
-  __shared__ double s_max[MOM_THREADS], s_nan[MOM_THREADS];
-  double rmax = -INFINITY, nnan = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += MOM_THREADS) {
-    rmax = fmax(rmax, part[2 * b]);
-    nnan += part[2 * b + 1];
-  }
-  s_max[threadIdx.x] = rmax;
-  s_nan[threadIdx.x] = nnan;
-  __syncthreads();
-  for (int w = MOM_THREADS / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      s_max[threadIdx.x] = fmax(s_max[threadIdx.x], s_max[threadIdx.x + w]);
-      s_nan[threadIdx.x] += s_nan[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    stats[0] = s_max[0] == -INFINITY ? __longlong_as_double(0x7ff8000000000000ll) : s_max[0];
-    stats[1] = s_nan[0];
-  }
-}
-
-static inline int fin_blocks(int64_t m) {
-  const int64_t b = (m + MOM_THREADS - 1) / MOM_THREADS;
-  return (int)(b < FIN_MAX_BLOCKS ? b : FIN_MAX_BLOCKS);
-}
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace pxm
 
@@ -234,22 +184,19 @@ using namespace pxm;
 
 extern "C" {
 
-int64_t pxm_moments_scratch_doubles(int64_t m) { return m >= 1 ? 2 * (int64_t)fin_blocks(m) : -1; }
+int64_t pxm_moments_scratch_doubles(int64_t m) { return stats_scratch_doubles(m, MOM_THREADS, 2); }
 
 int pxm_moments_update(const double* x, int x_stride, int64_t* count, double* mean, double* m2, const int* mask,
                        const double* logpi, int logpi_stride, double* best_logpi, double* best_x, int64_t m, int C,
                        pxm_stream_t stream) {
-  PXM_REQUIRE(C >= 1 && C <= 65535, "pxm_moments_update: need 1 <= C <= 65535");
-  PXM_REQUIRE(m >= 1, "pxm_moments_update: need m >= 1");
+  hipStream_t st = (hipStream_t)stream;
+  if (save_check("pxm_moments_update", m, C, x_stride, st)) return -1;
   PXM_REQUIRE(x && count && mean && m2, "pxm_moments_update: null buffer");
-  PXM_REQUIRE(x_stride == 1 || x_stride == 2, "pxm_moments_update: x_stride must be 1 (float64) or 2 (real parts of complex128)");
   const bool best = logpi || best_logpi || best_x;
   PXM_REQUIRE(!best || (logpi && best_logpi && best_x), "pxm_moments_update: logpi, best_logpi and best_x are given together");
   PXM_REQUIRE(!best || logpi_stride == 1 || logpi_stride == 2, "pxm_moments_update: logpi_stride must be 1 or 2");
   PXM_REQUIRE(aligned16(x) && aligned16(mean) && aligned16(m2) && aligned16(best_x),
               "pxm_moments_update: x, mean, m2 and best_x must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  note_stream(st);
   const int64_t per = (int64_t)MOM_THREADS * MOM_UNROLL;
   // whole unrolled passes only (floor): every lane runs the 4-deep body for the bulk of a row and the first lanes take what
   // is left (fewer than 4 strides) one pair at a time; rows shorter than one pass run on a single workgroup
@@ -283,32 +230,17 @@ int pxm_moments_finalize(const int64_t* count, const double* mean, const double*
   PXM_REQUIRE(!stats || (rhat && scratch), "pxm_moments_finalize: stats needs rhat and scratch");
   hipStream_t st = (hipStream_t)stream;
   note_stream(st);
-  int64_t n_common = 0;
-  int n_part = 0;
-  if (rhat) {  // the counts decide whether R-hat is defined: read them back (a post-run call, it synchronises the stream)
-    std::vector<int64_t> h(C);
-    PXM_HIP(hipMemcpyAsync(h.data(), count, sizeof(int64_t) * C, hipMemcpyDeviceToHost, st));
-    PXM_HIP(hipStreamSynchronize(st));
-    int64_t lo = std::numeric_limits<int64_t>::max(), hi = 0;
-    for (int64_t v : h)
-      if (v > 0) {
-        ++n_part;
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
-      }
-    if (n_part >= 2 && lo != hi) {
-      set_error("pxm_moments_finalize: R-hat needs one common sample count, the chains hold between " + std::to_string(lo) +
-                " and " + std::to_string(hi) + " samples (the pooled moments do not: call without rhat)");
-      return -1;
-    }
-    if (n_part >= 2 && lo >= 2) n_common = lo;
-  }
-  const int nb = fin_blocks(m);
-  hipLaunchKernelGGL(k_moments_finalize, dim3(nb), dim3(MOM_THREADS), 0, st, count, mean, m2, C, m, n_common, n_part, pooled_mean,
+  Counts k;  // they decide whether R-hat is defined
+  if (rhat && (read_counts(count, C, st, k) ||
+               require_common_count(k, "pxm_moments_finalize: R-hat", "the pooled moments do not: call without rhat")))
+    return -1;
+  const int64_t n_common = k.n_part >= 2 && k.lo >= 2 ? k.lo : 0;
+  const int nb = stats_blocks(m, MOM_THREADS);
+  hipLaunchKernelGGL(k_moments_finalize, dim3(nb), dim3(MOM_THREADS), 0, st, count, mean, m2, C, m, n_common, k.n_part, pooled_mean,
                      pooled_var, rhat, stats ? scratch : nullptr);
   PXM_HIP(hipGetLastError());
   if (stats) {
-    hipLaunchKernelGGL(k_moments_stats, dim3(1), dim3(MOM_THREADS), 0, st, scratch, nb, stats);
+    hipLaunchKernelGGL((k_summary_stats<true, 1>), dim3(1), dim3(STATS_THREADS), 0, st, scratch, nb, stats);
     PXM_HIP(hipGetLastError());
   }
   return 0;

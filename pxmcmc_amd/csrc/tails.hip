@@ -10,12 +10,8 @@
 // two reads per level, log2 k levels, in place of a rescan of the k slots.  Saves are staged in a ring of TAIL_STAGE rows
 // per chain and merged into the heaps when it is full (k_tails_update says why).  After them: the same select on a whole
 // chain that is resident on the device (k_quantile_range).
-#include "common.h"
 #include "qkey.h"
-
-#include <cmath>
-#include <string>
-#include <vector>
+#include "summary.h"
 
 #include "../../include/pxmcmc_amd.h"
 
@@ -183,8 +179,6 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tails_quantiles(const double* 
   q_hi[j] = v[0];
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace pxm
 
 using namespace pxm;
@@ -208,28 +202,19 @@ __global__ __launch_bounds__(256) void k_quantile_range(const double* __restrict
 
 extern "C" {
 
-int64_t pxm_tails_buffer_doubles(int64_t m, int C, int64_t k) {
-  if (m < 1 || C < 1 || k < 1) return -1;
-  if (k > INT64_MAX / m || k * m > INT64_MAX / 8 / C) return -1;
-  return (int64_t)C * k * m;
-}
+int64_t pxm_tails_buffer_doubles(int64_t m, int C, int64_t k) { return rows_doubles(m, C, k); }
 
 int64_t pxm_tails_stage_doubles(int64_t m, int C) { return pxm_tails_buffer_doubles(m, C, TAIL_STAGE); }
 
 int pxm_tails_update(const double* x, int x_stride, const int64_t* count, double* lo, double* hi, double* thr_lo, double* thr_hi,
                      double* stage, const int* mask, int64_t m, int C, int64_t k, int64_t nsamples, pxm_stream_t stream) {
-  PXM_REQUIRE(C >= 1 && C <= 65535, "pxm_tails_update: need 1 <= C <= 65535");
-  PXM_REQUIRE(m >= 1, "pxm_tails_update: need m >= 1");
+  hipStream_t st = (hipStream_t)stream;
+  if (save_check("pxm_tails_update", m, C, x_stride, st)) return -1;
   PXM_REQUIRE(k >= 1 && k <= nsamples, "pxm_tails_update: need 1 <= k <= nsamples");
   PXM_REQUIRE(pxm_tails_buffer_doubles(m, C, k) > 0 && pxm_tails_stage_doubles(m, C) > 0, "pxm_tails_update: C k m overflows");
   PXM_REQUIRE(x && count && lo && hi && thr_lo && thr_hi && stage, "pxm_tails_update: null buffer");
-  PXM_REQUIRE(x_stride == 1 || x_stride == 2, "pxm_tails_update: x_stride must be 1 (float64) or 2 (real parts of complex128)");
   PXM_REQUIRE(aligned16(x) && aligned16(thr_lo) && aligned16(thr_hi), "pxm_tails_update: x, thr_lo and thr_hi must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  note_stream(st);
-  int64_t nb = (m + TAIL_THREADS - 1) / TAIL_THREADS;  // one element per lane, 8-byte coalesced accesses
-  nb = nb > TAIL_MAX_BLOCKS ? TAIL_MAX_BLOCKS : nb;
-  const dim3 grid((unsigned)nb, (unsigned)C);
+  const dim3 grid = rows_grid(m, TAIL_THREADS, TAIL_MAX_BLOCKS, C);  // 8-byte coalesced accesses
   const int64_t ldx = m * x_stride;
   if (x_stride == 1)
     hipLaunchKernelGGL((k_tails_update<1>), grid, dim3(TAIL_THREADS), 0, st, x, ldx, count, lo, hi, thr_lo, thr_hi, stage, mask, m, k, nsamples);
@@ -249,16 +234,15 @@ int pxm_tails_quantiles(const int64_t* count, const double* lo, const double* hi
   PXM_REQUIRE(alpha >= 0.0 && alpha <= 1.0, "pxm_tails_quantiles: alpha must lie in [0, 1]");
   hipStream_t st = (hipStream_t)stream;
   note_stream(st);
-  std::vector<int64_t> h(C);  // a post-run call: the counts decide the ranks, read them back (synchronises the stream)
-  PXM_HIP(hipMemcpyAsync(h.data(), count, sizeof(int64_t) * C, hipMemcpyDeviceToHost, st));
-  PXM_HIP(hipStreamSynchronize(st));
+  Counts counts;  // they decide the ranks
+  if (read_counts(count, C, st, counts)) return -1;
   struct Ranks {
     int64_t ns, np, r_lo, r_hi;  // filled slots of a tail, rows of the ring not merged yet, ranks in the two together
     double g_lo, g_hi;
   };
   std::vector<Ranks> ranks(C);
   for (int c = 0; c < C; ++c) {
-    const int64_t n = h[c];
+    const int64_t n = counts.n[c];
     if (n < 0 || n > nsamples) {
       set_error("pxm_tails_quantiles: chain " + std::to_string(c) + " holds " + std::to_string(n) + " samples, the tails were sized for " +
                 std::to_string(nsamples) + " (the saves beyond were not recorded)");

@@ -387,12 +387,26 @@ def quantile_range(chain, alpha=0.05):
     return out
 
 
-def _moments_rows(X, C_, m):
-    """the sample batch of moments_update as (tensor, x_stride): float64 [C, m] (stride 1), or complex128 [C, m] whose real
-    parts are taken (stride 2); a complex state accumulated per component is passed as its float64 [C, 2 n] view"""
+def _dev_tensors(fn, what, *specs):
+    """every (tensor, dtype, shape) of ``specs`` is a contiguous device tensor of that dtype and shape, or ``fn`` raises a
+    TypeError that says ``what`` is expected"""
+    for t, dt, shape in specs:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError("%s: %s" % (fn, what))
+
+
+def _mask_arg(fn, mask, C_):
+    """the optional ``mask`` of the update entry points"""
+    if mask is not None:
+        _dev_tensors(fn, "mask must be a contiguous int32 [C] device tensor", (mask, torch.int32, (C_,)))
+
+
+def _moments_rows(fn, X, C_, m):
+    """the sample batch of the update entry points as (tensor, x_stride): float64 [C, m] (stride 1), or complex128 [C, m] whose
+    real parts are taken (stride 2); a complex state accumulated per component is passed as its float64 [C, 2 n] view"""
     if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dim() == 2 and X.shape[0] == C_ and X.is_contiguous()
             and X.dtype in (_REAL, _CPLX) and X.shape[1] == m and X.data_ptr() % 16 == 0):
-        raise TypeError("moments_update: X must be a contiguous 16-byte aligned float64 or complex128 [%d, %d] device tensor" % (C_, m))
+        raise TypeError("%s: X must be a contiguous 16-byte aligned float64 or complex128 [%d, %d] device tensor" % (fn, C_, m))
     return X, (2 if X.dtype == _CPLX else 1)
 
 
@@ -403,21 +417,18 @@ def moments_update(X, count, mean, m2, mask=None, logpi=None, best_logpi=None, b
     ``best_x`` [C, m], a chain whose logpi exceeds its best so far also copies its sample to ``best_x``.  No allocation, no
     synchronisation: the call can be captured in a HIP graph."""
     C_, m = mean.shape
-    x, xs = _moments_rows(X, C_, m)
-    for t, dt, shape in ((count, torch.int64, (C_,)), (mean, _REAL, (C_, m)), (m2, _REAL, (C_, m))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
-            raise TypeError("moments_update: count int64 [C], mean / m2 contiguous float64 [C, m] device tensors are expected")
-    if mask is not None and (mask.dtype != torch.int32 or tuple(mask.shape) != (C_,) or not mask.is_cuda):
-        raise TypeError("moments_update: mask must be an int32 [C] device tensor")
+    x, xs = _moments_rows("moments_update", X, C_, m)
+    _dev_tensors("moments_update", "count int64 [C], mean / m2 contiguous float64 [C, m] device tensors are expected",
+                 (count, torch.int64, (C_,)), (mean, _REAL, (C_, m)), (m2, _REAL, (C_, m)))
+    _mask_arg("moments_update", mask, C_)
     ls = 1
     if logpi is not None:
         if best_logpi is None or best_x is None:
             raise ValueError("moments_update: logpi, best_logpi and best_x are given together")
         if logpi.dtype not in (_REAL, _CPLX) or tuple(logpi.shape) != (C_,) or not logpi.is_contiguous() or not logpi.is_cuda:
             raise TypeError("moments_update: logpi must be a contiguous float64 or complex128 [C] device tensor")
-        if best_logpi.dtype != _REAL or tuple(best_logpi.shape) != (C_,) or best_x.dtype != _REAL or tuple(best_x.shape) != (C_, m) \
-                or not best_x.is_contiguous():
-            raise TypeError("moments_update: best_logpi float64 [C] and best_x contiguous float64 [C, m] are expected")
+        _dev_tensors("moments_update", "best_logpi float64 [C] and best_x contiguous float64 [C, m] are expected",
+                     (best_logpi, _REAL, (C_,)), (best_x, _REAL, (C_, m)))
         ls = 2 if logpi.dtype == _CPLX else 1
     elif best_logpi is not None or best_x is not None:
         raise ValueError("moments_update: logpi, best_logpi and best_x are given together")
@@ -433,9 +444,8 @@ def moments_finalize(count, mean, m2, rhat=True):
     if mean.dim() != 2:
         raise TypeError("moments_finalize: mean must be a float64 [C, m] device tensor")
     C_, m = mean.shape
-    for t, dt, shape in ((count, torch.int64, (C_,)), (mean, _REAL, (C_, m)), (m2, _REAL, (C_, m))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
-            raise TypeError("moments_finalize: count int64 [C], mean / m2 contiguous float64 [C, m] device tensors are expected")
+    _dev_tensors("moments_finalize", "count int64 [C], mean / m2 contiguous float64 [C, m] device tensors are expected",
+                 (count, torch.int64, (C_,)), (mean, _REAL, (C_, m)), (m2, _REAL, (C_, m)))
     pm = torch.empty(m, dtype=_REAL, device=mean.device)
     pv = torch.empty_like(pm)
     rh = st = scratch = None
@@ -452,13 +462,11 @@ def _tails_state(fn, lo, hi, thr_lo, thr_hi, stage, count):
     if not (isinstance(lo, torch.Tensor) and lo.dim() == 3):
         raise TypeError("%s: lo must be a float64 [C, k, m] device tensor" % fn)
     C_, k, m = lo.shape
-    for t, dt, shape in ((count, torch.int64, (C_,)), (lo, _REAL, (C_, k, m)), (hi, _REAL, (C_, k, m)), (thr_lo, _REAL, (C_, m)),
-                         (thr_hi, _REAL, (C_, m)), (stage, _REAL, (C_, tails_stage_depth(), m))):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
-            raise TypeError("%s: count int64 [C], lo / hi contiguous float64 [C, k, m], thr_lo / thr_hi contiguous float64 [C, m] "
-                            "and stage contiguous float64 [C, %d, m] device tensors are expected" % (fn, tails_stage_depth()))
+    B = tails_stage_depth()
+    _dev_tensors(fn, "count int64 [C], lo / hi contiguous float64 [C, k, m], thr_lo / thr_hi contiguous float64 [C, m] and stage "
+                 "contiguous float64 [C, %d, m] device tensors are expected" % B,
+                 (count, torch.int64, (C_,)), (lo, _REAL, (C_, k, m)), (hi, _REAL, (C_, k, m)), (stage, _REAL, (C_, B, m)),
+                 *((t, _REAL, (C_, m)) for t in (thr_lo, thr_hi) if t is not None))  # (the read-out has no thresholds)
     if int(lib.pxm_tails_buffer_doubles(m, C_, k)) != lo.numel():
         raise ValueError("%s: bad tail shape [%d, %d, %d]" % (fn, C_, k, m))
     return C_, k, m
@@ -478,9 +486,8 @@ def tails_update(X, count, lo, hi, thr_lo, thr_hi, stage, nsamples, mask=None):
     that has reached it, or that ``mask`` (int32 [C]) switches off, is left untouched.  No allocation, no synchronisation:
     the call can be captured in a HIP graph."""
     C_, k, m = _tails_state("tails_update", lo, hi, thr_lo, thr_hi, stage, count)
-    x, xs = _moments_rows(X, C_, m)
-    if mask is not None and (mask.dtype != torch.int32 or tuple(mask.shape) != (C_,) or not mask.is_cuda or not mask.is_contiguous()):
-        raise TypeError("tails_update: mask must be a contiguous int32 [C] device tensor")
+    x, xs = _moments_rows("tails_update", X, C_, m)
+    _mask_arg("tails_update", mask, C_)
     check(lib.pxm_tails_update(_p(x), xs, _p(count), _p(lo), _p(hi), _p(thr_lo), _p(thr_hi), _p(stage), _p(mask), m, C_, k, int(nsamples),
                                _stream()))
 
@@ -509,12 +516,11 @@ def _acov_state(fn, acc, tot, head, ring, count):
     C_, K, m = acc.shape
     if K < 2 or K > 64 or K % 2:
         raise ValueError("%s: K must be even with 2 <= K <= 64, got %d" % (fn, K))
-    R = K - 1 + acov_stage_depth()
-    for t, dt, shape in ((count, torch.int64, (C_,)), (acc, _REAL, (C_, K, m)), (tot, _REAL, (C_, m)), (head, _REAL, (C_, K, m)),
-                         (ring, _REAL, (C_, R, m))):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
-            raise TypeError("%s: count int64 [C], acc / head contiguous float64 [C, K, m], tot contiguous float64 [C, m] and ring "
-                            "contiguous float64 [C, K - 1 + %d, m] device tensors are expected" % (fn, acov_stage_depth()))
+    B = acov_stage_depth()
+    _dev_tensors(fn, "count int64 [C], acc / head contiguous float64 [C, K, m], tot contiguous float64 [C, m] and ring contiguous "
+                 "float64 [C, K - 1 + %d, m] device tensors are expected" % B,
+                 (count, torch.int64, (C_,)), (acc, _REAL, (C_, K, m)), (tot, _REAL, (C_, m)), (head, _REAL, (C_, K, m)),
+                 (ring, _REAL, (C_, K - 1 + B, m)))
     if int(lib.pxm_acov_state_doubles(m, C_, K)) != acc.numel() or int(lib.pxm_acov_ring_doubles(m, C_, K)) != ring.numel():
         raise ValueError("%s: bad state shape [%d, %d, %d]" % (fn, C_, K, m))
     return C_, K, m
@@ -527,9 +533,8 @@ def acov_update(X, count, acc, tot, head, ring, mask=None):
     before the ``moments_update`` of the same sample.  A chain that ``mask`` (int32 [C]) switches off is left untouched.  The
     state needs no initialisation.  No allocation, no synchronisation: the call can be captured in a HIP graph."""
     C_, K, m = _acov_state("acov_update", acc, tot, head, ring, count)
-    x, xs = _moments_rows(X, C_, m)
-    if mask is not None and (mask.dtype != torch.int32 or tuple(mask.shape) != (C_,) or not mask.is_cuda or not mask.is_contiguous()):
-        raise TypeError("acov_update: mask must be a contiguous int32 [C] device tensor")
+    x, xs = _moments_rows("acov_update", X, C_, m)
+    _mask_arg("acov_update", mask, C_)
     check(lib.pxm_acov_update(_p(x), xs, _p(count), _p(acc), _p(tot), _p(head), _p(ring), _p(mask), m, C_, K, _stream()))
 
 

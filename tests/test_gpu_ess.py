@@ -181,6 +181,54 @@ def test_acov_kernels_elementwise(m, C, mode):
         _sweep_case(m, C, K, mode)
 
 
+@pytest.mark.parametrize("m", [16385, 65601])
+def test_read_out_stats_over_many_workgroups(m):
+    """the two-stage reduction of the read-out's stats beyond m = 8193 (129 workgroups of 64 lanes): m = 16385 is 257
+    partials, a second trip of the second stage's loop; m = 65601 is one element beyond the 1024 workgroups of the cap, a
+    second trip of the element loop.  Constant columns give a NaN count above zero; with and without the pooled outputs; the
+    minimum is also that of the kernel's own ess array, exactly"""
+    C, K, T = 2, 2, 5
+    x = _columns(T, C, m, seed=m)
+    t = _Acov(C, m, K)
+    model = _Model(C, m, K)
+    for i in range(T):
+        t.update(x[i])
+        model.push_all(x[i])
+    for pooled in (True, False):
+        _check_read_out(t, model, ("stats", m, pooled), pooled=pooled)
+        ess, _, _, _, st = t.read(pooled)
+        assert 0 < st[1] == np.isnan(ess).sum() < ess.size and st[0] == np.nanmin(ess), (m, pooled, st)
+
+
+def test_update_entry_points_name_themselves_in_a_type_error():
+    """a sample batch that is not contiguous or not 16-byte aligned, and a strided mask, are refused in the name of the entry
+    point that was called"""
+    import torch
+
+    from pxmcmc_amd import ops
+    from test_gpu_tails import _Tails
+
+    C, m = 2, 6
+    wide = torch.zeros((C, 2 * m + 2), dtype=torch.float64, device="cuda")
+    strided = wide[:, : 2 * m : 2]
+    off = wide.reshape(-1)[1 : 1 + C * m].view(C, m)
+    good = torch.zeros((C, m), dtype=torch.float64, device="cuda")
+    mask = torch.ones(2 * C, dtype=torch.int32, device="cuda")[::2]
+    assert not strided.is_contiguous() and off.is_contiguous() and off.data_ptr() % 16 == 8 and not mask.is_contiguous()
+    a = _Acov(C, m, 4)
+    acov = lambda X, **kw: ops.acov_update(X, a.count[:C], a.acc[:C], a.tot[:C], a.head[:C], a.ring[:C], **kw)  # noqa: E731
+    tl = _Tails(C, m, 0.5, 10)
+    tails = lambda X, **kw: ops.tails_update(X, tl.count[:C], tl.lo[:C], tl.hi[:C], tl.thr_lo[:C], tl.thr_hi[:C], tl.stage[:C], tl.N, **kw)  # noqa: E731
+    mom = lambda X, **kw: ops.moments_update(X, a.count[:C], good.clone(), good.clone(), **kw)  # noqa: E731
+    for name, call in (("acov_update", acov), ("tails_update", tails), ("moments_update", mom)):
+        for X in (strided, off):
+            with pytest.raises(TypeError, match="^%s: X must be" % name):
+                call(X)
+        with pytest.raises(TypeError, match="^%s: mask must be" % name):
+            call(good, mask=mask)
+    assert a.count[:C].tolist() == [0, 0]
+
+
 def test_read_out_leaves_the_run_as_it_was():
     """a run with a read-out after every save against the uninterrupted run: state and final read-out bit for bit"""
     import torch

@@ -257,10 +257,12 @@ def _filled(C, m, n, cplx=False, seed=0):
     return s
 
 
-@pytest.mark.parametrize("C,m,n", [(4, 257, 6), (2, 1, 2), (3, 70001, 3)])
+@pytest.mark.parametrize("C,m,n", [(4, 257, 6), (2, 1, 2), (3, 70001, 3), (2, 65537, 3), (2, 262401, 3)])
 def test_finalize_against_numpy(C, m, n):
     """pooled mean / variance and R-hat against pooled_np / rhat_np on the same accumulators (rtol 1e-13); max R-hat and the
-    NaN count exact against numpy on the kernel's own R-hat array (70001 elements: more than one workgroup per stage)"""
+    NaN count exact against numpy on the kernel's own R-hat array (70001 elements: more than one workgroup per stage; 65537:
+    257 partials, a second trip of the second stage's loop; 262401: one element beyond the 1024 workgroups of the cap, a
+    second trip of the element loop)"""
     from pxmcmc_amd import ops
     from pxmcmc_amd.uncertainty import pooled_np, rhat_np
 

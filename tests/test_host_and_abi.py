@@ -48,6 +48,27 @@ def test_bad_arguments_set_error():
     assert L.lib.pxm_wav_bandlimits(256, 2.0, 2, buf, 2) < 0  # capacity too small
 
 
+def test_summary_updates_name_themselves_when_they_refuse_the_sample_batch(monkeypatch):
+    """tails_update and acov_update share the check of X with moments_update; the TypeError of a batch that is not
+    contiguous, or not 16-byte aligned, names the entry point that was called.  (Host tensors: the checks of the state
+    buffers, which need device tensors, are stepped over; X is refused before the library is called.)"""
+    import torch
+
+    from pxmcmc_amd import ops
+
+    C, k, m = 2, 3, 6
+    monkeypatch.setattr(ops, "_tails_state", lambda *a: (C, k, m))
+    monkeypatch.setattr(ops, "_acov_state", lambda *a: (C, k, m))
+    wide = torch.zeros((C, 2 * m + 2), dtype=torch.float64)
+    strided, off = wide[:, : 2 * m : 2], wide.reshape(-1)[1 : 1 + C * m].view(C, m)
+    assert not strided.is_contiguous() and off.is_contiguous() and off.data_ptr() % 16 == 8
+    for X in (strided, off):
+        with pytest.raises(TypeError, match="^tails_update: X must be a contiguous 16-byte aligned"):
+            ops.tails_update(X, None, None, None, None, None, None, 10)
+        with pytest.raises(TypeError, match="^acov_update: X must be a contiguous 16-byte aligned"):
+            ops.acov_update(X, None, None, None, None, None)
+
+
 @pytest.mark.parametrize("spin", [0, 2, -2])
 def test_host_ring_tables_match_oracle(spin):
     from oracle import ssht
