@@ -841,9 +841,86 @@ class MYULA(PxMCMC):
         return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
 
 
+class _PxmalaState:
+    """Static device buffers of one PxMALA run (``PxMALA._start_state``); a route allocates what it uses.  All routes: the
+    current state ``X preds gradg proxf logpi L2 prior delta``, overwritten per chain where ``accept`` [C] is set, the
+    iteration counter ``cnt`` and the two rings of ``_TraceChunks`` that the accept kernels write.  Proposal buffers:
+    ``X_prop lt_cp prior_p`` (proposal, q(X'|X), prior(X')) and the stock prior's threshold and weights ``T w_prior`` on
+    the fused and separate routes, ``proxf_prop`` on the separate route, ``lt_pc L2_p`` (q(X|X'), L2(X')) and the two
+    scratches of partial sums on the fused route; the plugin route's proposal is whatever tensors the user's operators
+    return."""
+
+    def __init__(self, start, C, dev, route, traces, prior):
+        self.X, self.preds, self.gradg, self.proxf, self.logpi, self.L2, self.prior, self.delta = start
+        self.accept = torch.zeros(C, dtype=torch.int32, device=dev)
+        self.cnt = _Counter(0)  # device-resident iteration number (graph replay)
+        self.acc_trace, self.delta_trace = traces.acc_buf, traces.delta_buf
+        if route != "plugin":
+            self.T, self.w_prior = prior.T_dev, getattr(prior, "_weights_dev", None)  # (the proposal kernel applies the prox)
+            self.X_prop = torch.empty_like(self.X)
+            self.lt_cp = torch.empty(C, dtype=torch.complex128, device=dev)
+            self.prior_p = torch.empty(C, dtype=torch.float64, device=dev)
+        if route == "separate":
+            self.proxf_prop = torch.empty_like(self.X)
+        if route == "fused":
+            self.lt_pc = torch.empty(C, dtype=torch.complex128, device=dev)
+            self.L2_p = torch.empty(C, dtype=torch.complex128, device=dev)
+            self.prop_scratch = ops.pxmala_propose_scratch(C, dev)
+            self.fin_scratch = torch.empty(2 * ops.reduce_scratch_doubles(C), dtype=torch.float64, device=dev)
+
+    def current(self):
+        """what an iteration carries over to the next: the tensors a graph capture snapshots and restores"""
+        return (self.X, self.preds, self.gradg, self.proxf, self.logpi, self.L2, self.prior, self.delta)
+
+
+class _TraceChunks:
+    """Acceptance flag and delta of every iteration and chain.  The accept kernels write row ``i % depth`` of two
+    ``[depth, C]`` device rings; ``after(i)`` reads both back when iteration i filled the last row (the only host
+    synchronisation of the traces during a run), ``result`` reads the rows of the last, partial chunk."""
+
+    def __init__(self, depth, C, dev):
+        self.depth = depth
+        self.acc_buf = torch.zeros((depth, C), dtype=torch.int32, device=dev)
+        self.delta_buf = torch.zeros((depth, C), dtype=torch.float64, device=dev)
+        self._acc, self._delta = [], []
+        self._accepted0 = 0  # accepted proposals of chain 0 in the chunks read back
+
+    def _read(self, rows):
+        self._acc.append(self.acc_buf[:rows].cpu().numpy().copy())
+        self._delta.append(self.delta_buf[:rows].cpu().numpy().copy())
+
+    def after(self, i):
+        if i % self.depth == self.depth - 1:
+            self._read(self.depth)
+            self._accepted0 += int(self._acc[-1][:, 0].sum())
+
+    def accepted0(self, i):
+        """accepted proposals of chain 0 in iterations 0..i (progress line; reads the rows not yet flushed)"""
+        k = i % self.depth
+        pending = 0 if k == self.depth - 1 else int(self.acc_buf[: k + 1, 0].sum().item())
+        return self._accepted0 + pending
+
+    def result(self, niter, delta0, tune_delta):
+        """(acceptance_trace, deltas_trace) of ``niter`` iterations as the reference keeps them: lists for one chain,
+        ``[niter, C]`` / ``[1 + niter, C]`` arrays otherwise; deltas start with delta0 and grow only with tune_delta"""
+        C = self.acc_buf.shape[1]
+        if niter % self.depth:
+            self._read(niter % self.depth)
+        acc = np.concatenate(self._acc) if self._acc else np.zeros((0, C), dtype=np.int32)
+        deltas = np.concatenate([np.full((1, C), delta0)] + (self._delta if tune_delta else []))
+        if C == 1:
+            return [int(v) for v in acc[:, 0]], [float(v) for v in deltas[:, 0]]
+        return acc, deltas
+
+
 class PxMALA(MYULA):
     """
     PxMALA = MYULA proposal + Metropolis-Hastings acceptance (pxmcmc/mcmc.py:204-289).
+
+    One iteration is a fixed sequence of device operations on the static buffers of a ``_PxmalaState``, by the route
+    chosen once per run (``_route``): ``_iteration_fused`` or ``_iteration_separate`` (the library's own prior), or
+    ``_iteration_plugin`` (a user-supplied prior or ``chain_step``).  ``run`` keeps the schedule: a chain saves on an
+    accepted candidate.
 
     :param bool tune_delta: tune ``delta`` towards an acceptance probability of 0.5
     """
@@ -870,180 +947,174 @@ class PxMALA(MYULA):
         self.transitions_trace = []
         self.proposals_trace = []
 
+    # ---- the run's device state and its route ---------------------------------------------------------------------------
+    def _route(self):
+        """which of the ``_iteration_*`` methods steps this run.  Stock prior (library L1 / S2 soft threshold + weighted L1
+        norm): the proposal kernel applies it.  With a diagonal inverse covariance too, the totals of the proposal pass are
+        deferred and everything between the proposal's gradient and the conditional copy is two launches
+        (pxm_pxmala_finish) instead of seven; the sums are added in the same order either way (``fuse_tail = False``: the
+        separate calls, bit-identical)."""
+        stock = self._fused_prox and type(self.prior).prior is L1.prior
+        if not stock:
+            return "plugin"
+        return "fused" if self.fuse_tail and not hasattr(self.forward.invcov, "matvec") else "separate"
+
+    def _start_state(self, start_point, route, traces):
+        C, dev = self.nchains, ops.device()
+        X, preds = self._initial_sample(start_point)
+        dt = X.dtype
+        X = X.contiguous()
+        preds = ops.as_device(preds).clone()
+        gradg = ops.as_device(self.forward.calc_gradg(preds), dt).clone()
+        proxf = ops.as_device(self.prior.proxf(X), dt).clone()
+        logpi, L2, prior = self._logpi_dev(X, preds)
+        logpi, L2 = logpi.to(torch.complex128).contiguous(), L2.to(torch.complex128).contiguous()
+        prior = prior.to(torch.float64).contiguous()
+        delta = torch.full((C,), float(self.delta), dtype=torch.float64, device=dev)
+        return _PxmalaState((X, preds, gradg, proxf, logpi, L2, prior, delta), C, dev, route, traces, self.prior)
+
+    # ---- one iteration: three routes, one signature; Philox / adaptation use iteration number i_host + *counter ---------
+    def _philox_kw(self, i_host):
+        return dict(seed=self.seed, chain0=self.chain_offset, it=i_host)
+
+    def _draw_noise(self, st):  # (``rng="numpy"``: the reference's stream, normals before uniforms)
+        return self._host_noise(st.X) if self.rng == "numpy" else None
+
+    def _draw_uniforms(self):
+        return np.array([np.random.rand() for _ in range(self.nchains)]) if self.rng == "numpy" else None
+
+    def _proposal_model(self, Xp, dt):
+        """forward model and gradient of the proposal (pxmcmc/mcmc.py:232-233)"""
+        pp = ops.as_device(self.forward.forward(Xp))
+        return pp, ops.as_device(self.forward.calc_gradg(pp), dt)
+
+    def _iteration_fused(self, st, i_host, counter, bump=None):
+        """stock prior, fused tail: no prox arrays at all -- soft(X, T) is formed where it is needed; with ``bump`` the
+        counter advances inside pxm_pxmala_finish"""
+        kw = self._philox_kw(i_host)
+        ops.pxmala_propose(st.X, None, st.gradg, st.T, st.w_prior, st.delta, self.lmda, st.X_prop, None, None, None,
+                           noise=self._draw_noise(st), noise_complex=bool(self.complex), iter_dev=counter,
+                           noise64=self.noise64, scratch=st.prop_scratch, **kw)
+        Xp = st.X_prop
+        pp, gp = self._proposal_model(Xp, st.X.dtype)
+        p_, data_, ic_ = self._l2_inputs(pp)
+        ops.pxmala_finish(Xp, st.X, None, gp.contiguous(), p_, data_, ic_, st.prop_scratch, self.mu, self.lmda, st.logpi,
+                          st.L2, st.prior, st.accept, st.delta, self.tune_delta, st.lt_pc, st.lt_cp, st.prior_p, st.L2_p,
+                          st.fin_scratch, u=self._draw_uniforms(), iter_dev=counter, acc_trace=st.acc_trace,
+                          delta_trace=st.delta_trace, bump=bump, T=st.T if st.T is not None else 0.0, **kw)
+        self._last_transitions = (st.lt_cp, st.lt_pc)
+        self._last_proposal = (st.prior_p, st.L2_p)
+        ops.select_copy_many(st.accept, [(Xp, st.X), (pp.to(st.preds.dtype), st.preds), (gp, st.gradg)])
+
+    def _iteration_separate(self, st, i_host, counter, bump=None):
+        """stock prior, separate calls: proposal + prox + forward transition + prior in one pass, then the tail"""
+        kw = self._philox_kw(i_host)
+        ops.pxmala_propose(st.X, st.proxf, st.gradg, st.T, st.w_prior, st.delta, self.lmda, st.X_prop, st.proxf_prop,
+                           st.lt_cp, st.prior_p, noise=self._draw_noise(st), noise_complex=bool(self.complex),
+                           iter_dev=counter, noise64=self.noise64, scratch=None, **kw)
+        self._tail_separate(st, counter, kw, st.X_prop, st.proxf_prop, st.lt_cp, st.prior_p)
+        if bump is not None:
+            st.cnt.add(1)
+
+    def _iteration_plugin(self, st, i_host, counter, bump=None):
+        """user-supplied prior / chain_step: the reference's own sequence of calls (pxmcmc/mcmc.py:231-242)"""
+        dt, kw = st.X.dtype, self._philox_kw(i_host)
+        noise = self._draw_noise(st)  # (drawn whoever steps: the stream does not depend on the route)
+        if not self._own_step:
+            Xp = ops.chain_step(st.X, st.proxf, st.gradg, st.delta, self.lmda, noise=noise,
+                                noise_complex=bool(self.complex), noise64=self.noise64, **kw)
+        else:
+            Xp = ops.as_device(self.chain_step(st.X, st.proxf, st.gradg), dt)
+        pxp = ops.as_device(self.prior.proxf(Xp), dt)
+        ltc = ops.logtransition(st.X, Xp, st.proxf, st.gradg, st.delta, self.lmda)
+        prp = self.prior.prior(Xp)
+        if not isinstance(prp, torch.Tensor):
+            prp = torch.as_tensor(np.atleast_1d(np.asarray(prp, dtype=float)), device=ops.device())
+        self._tail_separate(st, counter, kw, Xp, pxp, ltc, prp.to(torch.float64).contiguous())
+
+    def _tail_separate(self, st, counter, kw, Xp, pxp, ltc, prp):
+        """from the proposal's forward model to the conditional copy of the accepted states, one call per step"""
+        pp, gp = self._proposal_model(Xp, st.X.dtype)
+        L2p = self._l2_dev(pp)
+        ltp = ops.logtransition(Xp, st.X, pxp, gp, st.delta, self.lmda)
+        self._last_transitions = (ltc, ltp)  # q(X'|X), q(X|X') of this iteration (pxmcmc/mcmc.py:240-241)
+        self._last_proposal = (prp, L2p)
+        ops.pxmala_accept(ltp, ltc, prp, L2p, self.mu, st.logpi, st.L2, st.prior, st.accept, st.delta, self.tune_delta,
+                          self.lmda, u=self._draw_uniforms(), iter_dev=counter, acc_trace=st.acc_trace,
+                          delta_trace=st.delta_trace, **kw)
+        ops.select_copy_many(st.accept, [(Xp, st.X), (pp.to(st.preds.dtype), st.preds), (gp, st.gradg), (pxp, st.proxf)])
+
+    def _capture(self, st, route, iteration):
+        """HIP graph of one iteration reading the device counter, which it advances itself (device Philox stream and stock
+        prior only; any operator that synchronises or cannot be captured falls back to eager stepping -- same results)"""
+        self.graph_error = None
+        graph = None
+        if self.use_graph and self.rng != "numpy" and route != "plugin":
+            snap = [t.clone() for t in st.current()]
+
+            def restore():
+                for t, s_ in zip(st.current(), snap):
+                    t.copy_(s_)
+
+            graphs, self.graph_error = self._engine_capture(
+                lambda: iteration(st, 0, st.cnt.t), restore, [lambda: iteration(st, 0, st.cnt.t, bump=st.cnt.t)])
+            graph = graphs[0] if graphs else None
+            st.cnt.set(0)
+        self.used_graph = graph is not None
+        return graph
+
     def run(self, start_point=None):
         """Run the algorithm (pxmcmc/mcmc.py:218-275); every chain carries its own delta and accept flag.
 
-        One iteration is a fixed sequence of device operations on static buffers -- proposal + prox + forward
-        transition + prior in one pass (pxm_pxmala_propose), forward model, gradient, L2, reverse transition,
-        Metropolis test / delta adaptation / traces on the device (pxm_pxmala_accept), one conditional copy of the
-        accepted states -- and, with the device Philox stream, is replayed from a captured HIP graph between
-        observable events (save candidates, progress prints, trace flushes)."""
+        Prepare, build the state, choose the route, capture, loop, publish.  With the device Philox stream the iteration is
+        replayed from a captured HIP graph; the loop synchronises with the device on save candidates (the accept flags),
+        laps, progress prints and full trace chunks only."""
         self._prepare()
         self.laps = []
         self._fused_wav = False  # PxMALA needs gradg and proxf of the proposal separately
         C = self.nchains
-        dev = ops.device()
-        acc_chunks, delta_chunks = [], []
-        acc_buf = torch.zeros((self._CHUNK, C), dtype=torch.int32, device=dev)
-        delta_buf = torch.zeros((self._CHUNK, C), dtype=torch.float64, device=dev)
-        delta_dev = torch.full((C,), float(self.delta), dtype=torch.float64, device=dev)
+        traces = _TraceChunks(self._CHUNK, C, ops.device())
         delta0 = float(self.delta)
-        j = np.zeros(C, dtype=int)
-        X_curr, curr_preds = self._initial_sample(start_point)
-        dt = X_curr.dtype
-        X_curr = X_curr.contiguous()
-        curr_preds = ops.as_device(curr_preds).clone()
-        gradg_curr = ops.as_device(self.forward.calc_gradg(curr_preds), dt).clone()
-        proxf_curr = ops.as_device(self.prior.proxf(X_curr), dt).clone()
-        logpiXc, L2Xc, priorXc = self._logpi_dev(X_curr, curr_preds)
-        logpiXc, L2Xc = logpiXc.to(torch.complex128).contiguous(), L2Xc.to(torch.complex128).contiguous()
-        priorXc = priorXc.to(torch.float64).contiguous()
-        # stock prior (library L1 / S2 soft threshold + weighted L1 norm): the fused proposal kernel applies
-        stock = self._fused_prox and type(self.prior).prior is L1.prior
-        T_dev = self.prior.T_dev if stock else None
-        w_prior = getattr(self.prior, "_weights_dev", None) if stock else None
-        X_prop, proxf_prop = torch.empty_like(X_curr), torch.empty_like(X_curr)
-        lt_cp = torch.empty(C, dtype=torch.complex128, device=dev)
-        prior_p = torch.empty(C, dtype=torch.float64, device=dev)
-        accept = torch.zeros(C, dtype=torch.int32, device=dev)
-        it_dev = torch.zeros(1, dtype=torch.int64, device=dev)  # device-resident iteration number (graph replay)
-        host_rng = self.rng == "numpy"
-
-        # stock prior + diagonal inverse covariance: the totals of the proposal pass are deferred and everything between
-        # the proposal's gradient and the conditional copy is two launches (pxm_pxmala_finish) instead of seven; the sums
-        # are added in the same order either way (``fuse_tail = False``: the separate calls, bit-identical)
-        fused_tail = bool(stock and self.fuse_tail and not hasattr(self.forward.invcov, "matvec"))
-        if fused_tail:
-            prop_scratch = ops.pxmala_propose_scratch(C, dev)
-            fin_scratch = torch.empty(2 * ops.reduce_scratch_doubles(C), dtype=torch.float64, device=dev)
-            lt_pc = torch.empty(C, dtype=torch.complex128, device=dev)
-            L2_p = torch.empty(C, dtype=torch.complex128, device=dev)
-
-        def iteration(i_host, counter, bump=None):
-            """one PxMALA iteration; Philox / adaptation use iteration number i_host + *counter"""
-            kw = dict(seed=self.seed, chain0=self.chain_offset, it=i_host)
-            noise = self._host_noise(X_curr) if host_rng else None
-            if stock:
-                # (fused tail: no prox arrays at all -- soft(X, T) is formed where it is needed)
-                ops.pxmala_propose(X_curr, None if fused_tail else proxf_curr, gradg_curr, T_dev, w_prior, delta_dev, self.lmda,
-                                   X_prop, None if fused_tail else proxf_prop,
-                                   None if fused_tail else lt_cp, None if fused_tail else prior_p, noise=noise,
-                                   noise_complex=bool(self.complex), iter_dev=counter, noise64=self.noise64,
-                                   scratch=prop_scratch if fused_tail else None, **kw)
-                Xp, pxp, ltc, prp = X_prop, proxf_prop, lt_cp, prior_p
-            else:  # user-supplied prior / chain_step: the reference's own sequence of calls (mcmc.py:231-242)
-                if not self._own_step:
-                    Xp = ops.chain_step(X_curr, proxf_curr, gradg_curr, delta_dev, self.lmda, noise=noise,
-                                        noise_complex=bool(self.complex), noise64=self.noise64, **kw)
-                else:
-                    Xp = ops.as_device(self.chain_step(X_curr, proxf_curr, gradg_curr), dt)
-                pxp = ops.as_device(self.prior.proxf(Xp), dt)
-                ltc = ops.logtransition(X_curr, Xp, proxf_curr, gradg_curr, delta_dev, self.lmda)
-                prp = self.prior.prior(Xp)
-                if not isinstance(prp, torch.Tensor):
-                    prp = torch.as_tensor(np.atleast_1d(np.asarray(prp, dtype=float)), device=dev)
-                prp = prp.to(torch.float64).contiguous()
-            pp = ops.as_device(self.forward.forward(Xp))
-            gp = ops.as_device(self.forward.calc_gradg(pp), dt)
-            if fused_tail:
-                p_, data_, ic_ = self._l2_inputs(pp)
-                u = np.array([np.random.rand() for _ in range(C)]) if host_rng else None
-                ops.pxmala_finish(Xp, X_curr, None, gp.contiguous(), p_, data_, ic_, prop_scratch, self.mu, self.lmda, logpiXc,
-                                  L2Xc, priorXc, accept, delta_dev, self.tune_delta, lt_pc, lt_cp, prior_p, L2_p, fin_scratch,
-                                  u=u, iter_dev=counter, acc_trace=acc_buf, delta_trace=delta_buf, bump=bump,
-                                  T=T_dev if T_dev is not None else 0.0, **kw)
-                self._last_transitions = (lt_cp, lt_pc)
-                self._last_proposal = (prior_p, L2_p)
-                ops.select_copy_many(accept, [(Xp, X_curr), (pp.to(curr_preds.dtype), curr_preds), (gp, gradg_curr)])
-                return
-            L2p = self._l2_dev(pp)
-            ltp = ops.logtransition(Xp, X_curr, pxp, gp, delta_dev, self.lmda)
-            self._last_transitions = (ltc, ltp)  # q(X'|X), q(X|X') of this iteration (pxmcmc/mcmc.py:240-241)
-            self._last_proposal = (prp, L2p)
-            u = np.array([np.random.rand() for _ in range(C)]) if host_rng else None
-            ops.pxmala_accept(ltp, ltc, prp, L2p, self.mu, logpiXc, L2Xc, priorXc, accept, delta_dev, self.tune_delta,
-                              self.lmda, u=u, iter_dev=counter, acc_trace=acc_buf, delta_trace=delta_buf, **kw)
-            ops.select_copy_many(accept, [(Xp, X_curr), (pp.to(curr_preds.dtype), curr_preds), (gp, gradg_curr), (pxp, proxf_curr)])
-
-        # HIP graph of one iteration (device Philox stream only; any operator that synchronises or cannot be
-        # captured falls back to eager stepping -- same results)
-        graph = None
-        self.graph_error = None
-        if self.use_graph and not host_rng and stock:
-            state = (X_curr, curr_preds, gradg_curr, proxf_curr, logpiXc, L2Xc, priorXc, delta_dev)
-            snap = [t.clone() for t in state]
-
-            def restore():
-                for t, s_ in zip(state, snap):
-                    t.copy_(s_)
-
-            def body():
-                if fused_tail:
-                    iteration(0, it_dev, bump=it_dev)  # (the counter advances inside pxm_pxmala_finish)
-                else:
-                    iteration(0, it_dev)
-                    ops.counter_add(it_dev, 1)
-
-            graphs, self.graph_error = self._engine_capture(lambda: iteration(0, it_dev), restore, [body])
-            graph = graphs[0] if graphs else None
-            it_dev.zero_()
-        self.used_graph = graph is not None
+        route = self._route()
+        st = self._start_state(start_point, route, traces)
+        iteration = getattr(self, "_iteration_" + route)
+        graph = self._capture(st, route, iteration)
 
         i = 0
-        n_acc = 0
+        j = np.zeros(C, dtype=int)
         torch.cuda.synchronize()
         t_loop = time.perf_counter()  # (loop_seconds: the iterations alone, without set-up and graph capture)
         while j.min() < self.nsamples and (self.max_iter is None or i < self.max_iter):
             if graph is not None:
                 graph.replay()
             else:
-                iteration(i, None)
+                iteration(st, i, None)
             if self.track_transitions:  # observation only (synchronises): both calc_logtransition values per iteration
                 self.transitions_trace.append(tuple(t.cpu().numpy().copy() for t in self._last_transitions))
                 self.proposals_trace.append(tuple(t.cpu().numpy().copy() for t in self._last_proposal))
-            k = i % self._CHUNK
-            if k == self._CHUNK - 1:
-                acc_chunks.append(acc_buf.cpu().numpy().copy())
-                delta_chunks.append(delta_buf.cpu().numpy().copy())
-                n_acc += int(acc_chunks[-1][:, 0].sum())  # running count of chain 0 (progress print)
-
-            gap_it = i >= self.nburn and (self.ngap == 0 or (i - self.nburn) % self.ngap == 0)
-            if gap_it:
-                acc_h = accept.cpu().numpy()  # the only per-iteration host sync, on save candidates only
+            traces.after(i)
+            if i >= self.nburn and (self.ngap == 0 or (i - self.nburn) % self.ngap == 0):
+                acc_h = st.accept.cpu().numpy()  # the only per-iteration host sync, on save candidates only
                 chains = [c for c in range(C) if acc_h[c] and j[c] < self.nsamples]
                 if chains:
                     self._check_device_status()
-                    self._tracking(j[chains] if C > 1 else int(j[0]), X_curr, curr_preds, logpiXc, L2Xc, priorXc,
+                    self._tracking(j[chains] if C > 1 else int(j[0]), st.X, st.preds, st.logpi, st.L2, st.prior,
                                    chains=chains if C > 1 else None)
                     j[chains] += 1
             if self.lap_every > 0 and (i + 1) % self.lap_every == 0:
                 torch.cuda.synchronize()
                 self.laps.append((i + 1, time.perf_counter() - t_loop))
             if self.verbosity > 0 and (i + 1) % self.verbosity == 0:
-                pending = 0 if k == self._CHUNK - 1 else int(acc_buf[: k + 1, 0].sum().item())  # rows not yet flushed
-                rate = (n_acc + pending) / (i + 1)
-                self._print_progress(
-                    int(j[0]) - 1, float(logpiXc[0].real), L2=float(L2Xc[0].real), prior=float(priorXc[0]), acceptanceRate=rate
-                )
+                self._print_progress(int(j[0]) - 1, float(st.logpi[0].real), L2=float(st.L2[0].real), prior=float(st.prior[0]),
+                                     acceptanceRate=traces.accepted0(i) / (i + 1))
             i += 1
         torch.cuda.synchronize()
         self.loop_seconds = time.perf_counter() - t_loop
-        k = i % self._CHUNK
-        if k:
-            acc_chunks.append(acc_buf[:k].cpu().numpy().copy())
-            delta_chunks.append(delta_buf[:k].cpu().numpy().copy())
-        acc_all = np.concatenate(acc_chunks) if acc_chunks else np.zeros((0, C), dtype=np.int32)
-        del_all = np.concatenate([np.full((1, C), delta0)] + (delta_chunks if self.tune_delta else []))
-        if C == 1:
-            self.acceptance_trace = [int(v) for v in acc_all[:, 0]]
-            self.deltas_trace = [float(v) for v in del_all[:, 0]]
-        else:
-            self.acceptance_trace = acc_all
-            self.deltas_trace = del_all
-        self.delta = float(delta_dev[0].item())
-        self.delta_dev = delta_dev
+        self.acceptance_trace, self.deltas_trace = traces.result(i, delta0, self.tune_delta)
+        self.delta = float(st.delta[0].item())
+        self.delta_dev = st.delta
         self._check_device_status()
-        self.X_curr, self.curr_preds, self.niter = X_curr, curr_preds, i
+        self.X_curr, self.curr_preds, self.niter = st.X, st.preds, i
         # rows of chain / logPi / ... beyond nsaved[c] were never written (zeros): a ``max_iter`` stop says so
         self.nsaved = j.copy() if C > 1 else int(j[0])
         self.stopped_early = bool(j.min() < self.nsamples)
