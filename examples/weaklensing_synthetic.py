@@ -37,6 +37,7 @@ from pxmcmc_amd.prior import L1, S2_Wavelets_L1  # noqa: E402
 from pxmcmc_amd.sapg import SAPG  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
 from pxmcmc_amd.transforms import SphericalWaveletTransform  # noqa: E402
+from pxmcmc_amd.uncertainty import local_credible_intervals, superpixel_regions  # noqa: E402
 from pxmcmc_amd.utils import build_mask  # noqa: E402
 
 BEAM_SIGMA = np.radians(50 / 60)  # 50 arcmin (experiments/weaklensing/main.py:35)
@@ -94,6 +95,19 @@ def map_start(forward_operator, prior, params, L_g, start_point=None, tol=1e-3, 
         print(f"start point: fixed point of the prior's own prox-gradient iteration (g + (lmda / gamma) f, not the MAP) after "
               f"{int(fista.niter[0])} iterations (converged: {bool(fista.converged[0])})")
     return x
+
+
+def local_ci_maps(forward_operator, prior, params, x_map, L, size, base):
+    """--local-ci SIZE: the local credible intervals of the MAP convergence on superpixels of SIZE x SIZE samples (DESIGN.md
+    section 14b), at the approximate 95 % HPD level; writes the lower / upper / range maps"""
+    lci = local_credible_intervals(forward_operator, prior, params, x_map, superpixel_regions(L, size))
+    ok = lci.status == 0
+    for name in ("lower", "upper", "range"):
+        np.save(f"{base}_lci_{name}.npy", lci.to_map(getattr(lci, name)))
+    print(f"local credible intervals: {ok.sum()} of {ok.size} superpixels of {size} x {size} samples have an interval at the "
+          f"level {lci.threshold:.6e}; median range {np.median(lci.range[ok]) if ok.any() else float('nan'):.4f}; "
+          f"maps in {base}_lci_lower.npy / _upper.npy / _range.npy")
+    return lci
 
 
 def estimate_mu(forward_operator, prior, params, L_g, args, start_point=None):
@@ -165,6 +179,9 @@ def main(argv=None):
     ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--map-start", action="store_true", help="start the chain(s) at the MAP point found by FISTA first")
+    ap.add_argument("--local-ci", type=int, default=None, metavar="SIZE",
+                    help="with --map-start: local credible intervals of the MAP point on superpixels of SIZE x SIZE samples "
+                         "(pixel-space posterior only)")
     ap.add_argument("--estimate-mu", action="store_true",
                     help="estimate the regularisation strength by SAPG first and sample with mu_hat = mu * theta_hat")
     ap.add_argument("--sapg-warmup", type=int, default=100, help="--estimate-mu: MYULA iterations before theta moves")
@@ -184,6 +201,8 @@ def main(argv=None):
         ap.error("--summary-alpha needs --summary")
     if args.summary_ess is not None and not args.summary:
         ap.error("--summary-ess needs --summary")
+    if args.local_ci is not None and (not args.map_start or args.harmonic):
+        ap.error("--local-ci needs --map-start and the pixel-space posterior (no --harmonic)")
     if args.summary not in (None, True, "state" if args.harmonic else "image"):
         ap.error("--summary %s: the summary is of the %s" % (args.summary, "state with --harmonic" if args.harmonic else "image without --harmonic"))
 
@@ -209,6 +228,9 @@ def main(argv=None):
     if args.estimate_mu:
         prior, params = estimate_mu(forward_operator, prior, params, L_g, args)
     start_point = map_start(forward_operator, prior, params, L_g) if args.map_start else None
+    if args.local_ci is not None:
+        local_ci_maps(forward_operator, prior, params, start_point, L, args.local_ci,
+                      os.path.join(args.outdir, f"{args.algo}_{setting}_{args.jobid}"))
     mcmc = build_sampler(args, forward_operator, prior, params, "image")
 
     now = datetime.now()

@@ -396,6 +396,43 @@ int pxm_sapg_step(const void* X, const void* gradg, const double* T, double T_sc
                   const uint64_t* iter_dev, double* theta, double* eta, double d, const double* rho_table, int64_t n_rho,
                   double eta_min, double eta_max, int pool, double* trace, int64_t n_trace, void* X_out, double* scratch,
                   int64_t n, int C, int dtype, pxm_stream_t stream);
+/* Local credible intervals from the MAP point (Cai, Pereyra & McEwen 2018).  Slot c of a batch is one
+ * region of the image; along the surrogate X(xi) = a_c + xi b_c (xi real) the objective of pxm_fista_step's posterior is
+ *   F_c(xi) = q0 + q1 xi + q2 xi^2 + (1 / lmda) sum_k T_k |a_ck + xi b_ck|,
+ * convex in xi, and the interval of the slot is {xi : F_c(xi) <= gamma_c}.  a, b [C][n] (f64 or c128), T [n] shared by the
+ * slots or T_scalar.  Every sum is added in a fixed order that depends on the vector length only: a slot's numbers do not
+ * depend on its batch.  scratch: caller-owned, pxm_lci_scratch_doubles(n, C) doubles, n the longer of the vectors summed.
+ *
+ * pxm_lci_data_terms: quad[c] = (q0, q1, q2) = (1/2 sum w |r|^2, sum w Re(conj(r) s), 1/2 sum w |s|^2) with r = preds_a[c] -
+ *   data and s = preds_b[c] (the predictions of a_c and b_c, [C][ndata]; data [ndata] of the same dtype and w [ndata], real,
+ *   are shared by the slots).
+ * pxm_lci_eval: P[c][j] = sum_k T_k |a_ck + xi[c][j] b_ck| for the PXM_LCI_POINTS values xi[c][.], in one pass over a, b, T,
+ *   the modulus formed from (a_re + xi b_re, a_im + xi b_im); P[c][32] = sum T|a_c|, P[c][33] = sum T|b_c|  (P [C][34]).
+ * pxm_lci_search: the whole search, enqueued on the stream: an initialisation kernel, then `rounds` times (pxm_lci_eval's
+ *   two kernels, a refinement kernel).  `rounds` (1 ... PXM_LCI_ROUNDS_MAX) is fixed here, on the host; no device loop has
+ *   a trip count that depends on data, and nothing waits.  gamma [C] on the device.  Outer bracket: the roots of the
+ *   quadratic = gamma (q2 > 0; F >= the quadratic), or |xi| <= (lmda (gamma - q0) + S_a) / (S_b - lmda |q1|) (q2 == 0 and
+ *   a positive denominator; found in the first round; q1 = 0 whenever s = 0).  While no point has F <= gamma the 32 points span the bracket and the bracket becomes the
+ *   smallest point with its two neighbours; from then on each end has a bracket of its own, cut by 16 interior points per
+ *   round.  The brackets shrink by at least 2/31 per round (1/17 once split).
+ *   out[c] = (lower, upper, width of the lower end's bracket, of the upper end's, smallest F seen, its xi, outer bracket
+ *   lo, hi): lower and upper are the inner points of the final brackets, where F <= gamma was evaluated.  status[c]: 0, or
+ *   PXM_LCI_EMPTY (no point with F <= gamma was found: negative discriminant -- NaN ends --, or still none after the last
+ *   round -- lower, upper are then the bracket of the minimiser), PXM_LCI_UNCONSTRAINED (b = 0 and s = 0 with F <= gamma, or q2 == 0
+ *   with |q1| >= S_b / lmda, F not coercive: -inf, +inf), PXM_LCI_NONFINITE (a non-finite input, whatever else holds: NaN). */
+#define PXM_LCI_POINTS 32
+#define PXM_LCI_ROUNDS_MAX 64
+#define PXM_LCI_EMPTY 1
+#define PXM_LCI_UNCONSTRAINED 2
+#define PXM_LCI_NONFINITE 4
+int64_t pxm_lci_scratch_doubles(int64_t n, int C);
+int pxm_lci_data_terms(const void* preds_a, const void* preds_b, const void* data, const double* w, double* quad,
+                       double* scratch, int64_t ndata, int C, int dtype, pxm_stream_t stream);
+int pxm_lci_eval(const void* a, const void* b, const double* T, double T_scalar, const double* xi, double* P,
+                 double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream);
+int pxm_lci_search(const void* a, const void* b, const double* T, double T_scalar, const double* quad, double lmda,
+                   const double* gamma, int rounds, double* out, int* status, double* scratch, int64_t n, int C, int dtype,
+                   pxm_stream_t stream);
 /* N(0,1) draws of the Philox4x32-10 stream keyed (seed, chain0+c, iter): out [C][n] (f64 or c128) */
 int pxm_randn(void* out, int64_t n, int C, int dtype, uint64_t seed, uint64_t chain0, uint64_t iter,
               pxm_stream_t stream);

@@ -13,6 +13,10 @@ gives the numbers of :func:`credible_interval_range` on each chain's saved sampl
 :func:`tails_quantiles_np` state that in numpy.  With ``ess_lags=`` it accumulates the lagged products of the saved samples,
 from which ``ess()``, ``ess_pooled()`` and ``mcse()`` give the effective sample size and the standard error of the pooled
 mean; :func:`acov_update_np`, :func:`ess_np` and :func:`ess_pooled_np` state that in numpy, :func:`autocov_np` the definition.
+
+Local credible intervals: :func:`local_credible_intervals` turns the MAP point and the level of
+:func:`approx_credible_region_threshold` into an error bar per region of the image (:func:`superpixel_regions`), searched on
+the device; :func:`lci_terms_np`, :func:`lci_eval_np` and :func:`lci_search_np` state its sums and its search in numpy.
 """
 import warnings
 
@@ -714,3 +718,319 @@ class PosteriorSummary:
             out["ess_lags"] = np.int64(dicts[0]["ess_lags"])
             out.update({k: np.concatenate([np.asarray(d[k]) for d in dicts], axis=0) for k in ("ess", "ess_lag")})
         return out
+
+
+# ---- local credible intervals from the MAP point ------------------------------------------------------
+LCI_POINTS = 32  # values of xi per pass (PXM_LCI_POINTS)
+LCI_OK, LCI_EMPTY, LCI_UNCONSTRAINED, LCI_NONFINITE = 0, 1, 2, 4  # status of a region: 0, or these bits
+
+
+def lci_shrink_factor(rounds, q2_positive=True):
+    """the guaranteed bound on (width of a final bracket) / (width of the outer bracket) after ``rounds`` rounds: every round
+    cuts the bracket to at most 2/31 of itself (joint: the smallest of 32 points and its two neighbours; the round that finds
+    the run: 1/31; split: 1/17).  With ``q2 == 0`` the first round goes into the outer bracket, which needs ``S_a``, ``S_b``."""
+    return (2.0 / 31.0) ** (int(rounds) - (0 if q2_positive else 1))
+
+
+def lci_sum_depth(n):
+    """the longest chain of additions in a fixed-order sum of ``pxm_lci_eval`` / ``pxm_lci_data_terms`` over n terms (the
+    error model of DESIGN.md section 14b): the terms a lane adds one after the other (one workgroup of 256 lanes per 1024
+    terms up to 512 workgroups, grid-stride beyond), the 6 levels of the wave tree, the 4 waves of the workgroup, then the
+    slices a lane of the finishing wave adds and its tree"""
+    n = int(n)
+    slices = min(512, max(1, -(-n // 1024)))
+    return -(-n // (slices * 256)) + 6 + 4 + -(-slices // 64) + 6
+
+
+def superpixel_regions(L, size):
+    """int32 labels [L, 2L - 1] of the MW grid cut into superpixels of ``size`` rings x ``size`` phi-samples, numbered row
+    by row; the last block of a row of blocks, and the last row of blocks, are smaller when ``size`` does not divide"""
+    L, size = int(L), int(size)
+    if L < 1 or size < 1:
+        raise ValueError("superpixel_regions needs L >= 1 and size >= 1")
+    t, p = np.arange(L) // size, np.arange(2 * L - 1) // size
+    return (t[:, None] * (p[-1] + 1) + p[None, :]).astype(np.int32)
+
+
+def lci_terms_np(a, b, r, s, w, T):
+    """the long-double statement of the sums of one region: ``(q, S_a, S_b)`` with ``q = (1/2 sum w |r|^2, sum w Re(conj(r)
+    s), 1/2 sum w |s|^2)``, ``S_a = sum T |a|``, ``S_b = sum T |b|``.  ``a``, ``b`` [n] and ``r``, ``s`` [ndata] real or
+    complex, ``w`` [ndata] real, ``T`` [n] or a scalar."""
+    ld = np.longdouble
+
+    def parts(v):
+        v = np.asarray(v)
+        return v.real.astype(ld), (v.imag.astype(ld) if np.iscomplexobj(v) else np.zeros(v.shape, dtype=ld))
+
+    (ar, ai), (br, bi), (rr, ri), (sr, si) = parts(a), parts(b), parts(r), parts(s)
+    w, T = np.asarray(w, dtype=np.float64).astype(ld), np.broadcast_to(np.asarray(T, dtype=np.float64), ar.shape).astype(ld)
+    half = ld(0.5)
+    q = np.array([half * (w * (rr * rr + ri * ri)).sum(), (w * (rr * sr + ri * si)).sum(), half * (w * (sr * sr + si * si)).sum()],
+                 dtype=ld)
+    return q, (T * np.sqrt(ar * ar + ai * ai)).sum(), (T * np.sqrt(br * br + bi * bi)).sum()
+
+
+def lci_eval_np(a, b, T, xi):
+    """the long-double statement of ``pxm_lci_eval`` for one region: ``P_j = sum_k T_k |a_k + xi_j b_k|`` -> long double
+    [len(xi)], the modulus from ``(a_re + xi b_re, a_im + xi b_im)``"""
+    ld = np.longdouble
+    a, b = np.asarray(a), np.asarray(b)
+    xi = np.atleast_1d(np.asarray(xi, dtype=np.float64)).astype(ld)[:, None]
+    T = np.broadcast_to(np.asarray(T, dtype=np.float64), a.shape).astype(ld)
+    re = a.real.astype(ld) + xi * b.real.astype(ld)
+    if np.iscomplexobj(a) or np.iscomplexobj(b):
+        im = a.imag.astype(ld) + xi * b.imag.astype(ld)
+        return (T * np.sqrt(re * re + im * im)).sum(axis=1)
+    return (T * np.abs(re)).sum(axis=1)
+
+
+def lci_search_np(q, a, b, T, lmda, gamma, rounds=10):
+    """the numpy statement of ``pxm_lci_search`` for one region, the same bracket / joint / split rules in float64 (the sums
+    are numpy's, so the numbers agree with the device's to rounding, not bit for bit).  ``q`` = (q0, q1, q2).  Returns a
+    dict: ``lower``, ``upper`` (the inner points of the final brackets: F <= gamma was evaluated there), ``width_lower``,
+    ``width_upper``, ``f_min`` and ``xi_min`` (the smallest F seen), ``outer`` (lo, hi) and ``status``."""
+    q0, q1, q2 = (float(v) for v in q)
+    lmda, gamma = float(lmda), float(gamma)
+    a, b = np.asarray(a), np.asarray(b)
+    cplx = np.iscomplexobj(a) or np.iscomplexobj(b)
+    T = np.broadcast_to(np.asarray(T, dtype=np.float64), a.shape)
+    nan, inf = float("nan"), float("inf")
+
+    def P(xi):
+        with np.errstate(invalid="ignore", over="ignore"):
+            re = a.real + np.asarray(xi)[:, None] * b.real
+            if not cplx:
+                return (T * np.abs(re)).sum(axis=1)
+            im = a.imag + np.asarray(xi)[:, None] * b.imag
+            return (T * np.sqrt(re * re + im * im)).sum(axis=1)
+
+    def result(status, lower, upper, wlo, whi, fmin, ximin, outer):
+        if status & LCI_NONFINITE:
+            lower = upper = fmin = ximin = nan
+        return dict(lower=lower, upper=upper, width_lower=wlo, width_upper=whi, f_min=fmin, xi_min=ximin, outer=outer, status=status)
+
+    Sa, Sb = float(P([0.0])[0]), float((T * np.abs(b)).sum())
+    fmin, ximin, outer = inf, nan, (nan, nan)
+    if not np.all(np.isfinite([q0, q1, q2, gamma, Sa, Sb])):
+        return result(LCI_NONFINITE, nan, nan, nan, nan, nan, nan, outer)
+    left = int(rounds)
+    if q2 > 0.0:
+        cc = q0 - gamma
+        disc = q1 * q1 - 4.0 * q2 * cc
+        if disc < 0.0:
+            return result(LCI_EMPTY, nan, nan, nan, nan, fmin, ximin, outer)
+        t = -0.5 * (q1 + np.copysign(np.sqrt(disc), q1))
+        r1, r2 = (0.0, 0.0) if t == 0.0 else (t / q2, cc / t)
+        lo, hi = min(r1, r2), max(r1, r2)
+    else:  # the first round of the device goes into this bracket
+        left -= 1
+        fmin, ximin = q0 + Sa / lmda, 0.0
+        D = Sb - lmda * abs(q1)  # F >= q0 - |q1| |xi| + (|xi| S_b - S_a) / lmda  (q1 = 0 whenever s = 0)
+        if not D > 0.0:
+            if q1 != 0.0 or fmin <= gamma:
+                return result(LCI_UNCONSTRAINED, -inf, inf, 0.0, 0.0, fmin, ximin, outer)
+            return result(LCI_EMPTY, nan, nan, nan, nan, fmin, ximin, outer)
+        R = (lmda * (gamma - q0) + Sa) / D
+        if R < 0.0:
+            return result(LCI_EMPTY, nan, nan, nan, nan, fmin, ximin, outer)
+        lo, hi = -R, R
+    outer = (lo, hi)
+    split, lo_in, hi_in = False, nan, nan
+    n, h = LCI_POINTS, LCI_POINTS // 2
+    for _ in range(left):
+        if not split:
+            x = np.minimum(lo + (hi - lo) * np.arange(n) / (n - 1.0), hi)
+            x[-1] = hi
+        else:
+            f = np.arange(1.0, h + 1)
+            x = np.concatenate([np.minimum(lo + (lo_in - lo) * f / (h + 1.0), lo_in), np.minimum(hi_in + (hi - hi_in) * f / (h + 1.0), hi)])
+        Pv = P(x)
+        if not np.all(np.isfinite(Pv)):
+            return result(LCI_NONFINITE, nan, nan, nan, nan, nan, nan, outer)
+        F = ((q2 * x + q1) * x + q0) + Pv / lmda
+        jm = int(np.argmin(F))
+        if F[jm] < fmin:
+            fmin, ximin = float(F[jm]), float(x[jm])
+        inside = np.flatnonzero(F <= gamma)
+        if not split:
+            if inside.size:
+                j0, j1 = int(inside[0]), int(inside[-1])
+                lo, lo_in, hi_in, hi = x[max(j0 - 1, 0)], x[j0], x[j1], x[min(j1 + 1, n - 1)]
+                split = True
+            else:
+                lo, hi = x[max(jm - 1, 0)], x[min(jm + 1, n - 1)]
+        else:
+            low, up = inside[inside < h], inside[inside >= h]
+            if low.size:
+                j0 = int(low[0])
+                lo, lo_in = (x[j0 - 1] if j0 > 0 else lo), x[j0]
+            else:
+                lo = x[h - 1]
+            if up.size:
+                j1 = int(up[-1])
+                hi, hi_in = (x[j1 + 1] if j1 < n - 1 else hi), x[j1]
+            else:
+                hi = x[h]
+    if not split:
+        return result(LCI_EMPTY, float(lo), float(hi), float(hi - lo), float(hi - lo), fmin, ximin, outer)
+    return result(LCI_OK, float(lo_in), float(hi_in), float(lo_in - lo), float(hi - hi_in), fmin, ximin, outer)
+
+
+def _lci_check_setup(forward, prior):
+    """the scope of the construction: synthesis setting, stock L1 prior, pixel-space transform, diagonal inverse covariance"""
+    from .mcmc import _is_stock_l1
+
+    if getattr(forward, "setting", None) != "synthesis":
+        raise ValueError("local credible intervals are defined in the synthesis setting (the surrogate lives in coefficient space)")
+    if not _is_stock_l1(prior):
+        raise ValueError("local credible intervals need the stock synthesis L1 prior: the objective is formed from prior.T")
+    tr = getattr(forward, "transform", None)
+    if tr is None or not hasattr(tr, "forward") or not hasattr(tr, "inverse"):
+        raise ValueError("local credible intervals need forward.transform with forward and inverse")
+    if getattr(tr, "harmonic", False):
+        raise ValueError("local credible intervals need a pixel-space transform: with harmonic=True there is no image to cut into regions")
+    if hasattr(forward.invcov, "matvec"):
+        raise ValueError("local credible intervals need a diagonal inverse covariance; a full covariance matrix is not supported")
+
+
+def _lci_weights(forward):
+    """w: the real diagonal inverse covariance of ``optim.gradient_operator(forward)``, float64 [ndata] on the device"""
+    from .optim import gradient_operator
+
+    diag = gradient_operator(forward).invcov.diag
+    return (diag.real if diag.is_complex() else diag).to(torch.float64).contiguous()
+
+
+def _lci_preds(forward, X):
+    """forward.forward of a [C, N] batch with the data in the dtype of the residual -> (preds [C, ndata], data [ndata])"""
+    p = ops.as_device(forward.forward(X))
+    dt = forward._resid_dtype(p) if hasattr(forward, "_resid_dtype") else p.dtype
+    return p.to(dt).contiguous(), forward.data_dev.to(dt).contiguous()
+
+
+def map_objective(forward, prior, params, X):
+    """``F(X) = 1/2 sum w |forward(X) - data|^2 + (1 / lmda) sum T |X|`` per chain -> float64 [C] on the device (``[1]`` for a
+    1-D ``X``), from the reductions the samplers use.  Defined through ``prior.T`` as :mod:`pxmcmc_amd.optim` explains, with
+    ``w = Re(invcov)``: the objective FISTA minimises, so at ``FISTA.X_map`` it equals ``FISTA.objective_map`` up to the
+    rounding of the prior sum.  Synthesis setting, stock L1 prior, diagonal inverse covariance."""
+    _lci_check_setup(forward, prior)
+    x, _ = ops._batched(ops.as_device(X))
+    p, d = _lci_preds(forward, x)
+    w = _lci_weights(forward)
+    l2 = ops.reduce_l2(p, d, w.to(p.dtype) if p.is_complex() else w)
+    T = prior.T_dev
+    l1 = ops.reduce_l1(x) * T if isinstance(T, float) else ops.reduce_l1(x, T)
+    return 0.5 * l2.real + l1 / float(params.lmda)
+
+
+class LocalCredibleIntervals:
+    """the result of :func:`local_credible_intervals`: one entry per region of ``lower``, ``upper``, ``range`` (= upper -
+    lower), ``map_value``, ``width`` (the larger of the two final bracket widths: each end is known to that), ``f_min``,
+    ``xi_min``, ``status`` (numpy arrays ``[nregions]``), ``outer`` (``[nregions, 2]``: the outer bracket the search started
+    from, so ``width <= lci_shrink_factor(rounds) * (outer[:, 1] - outer[:, 0])``), the ``threshold`` used and the ``labels``"""
+
+    FIELDS = ("lower", "upper", "range", "map_value", "width", "f_min", "xi_min", "status", "outer")
+
+    def __init__(self, labels, threshold, **fields):
+        self.labels, self.threshold = labels, threshold
+        for k in self.FIELDS:
+            setattr(self, k, fields[k])
+
+    def to_map(self, values=None):
+        """paint one value per region (default: ``range``) back onto the pixels, in the shape of the label array; NaN where
+        the label is -1"""
+        values = np.asarray(self.range if values is None else values, dtype=np.float64)
+        if values.shape != self.lower.shape:
+            raise ValueError("to_map: one value per region is expected")
+        out = np.full(self.labels.shape, np.nan)
+        on = self.labels >= 0
+        out[on] = values[self.labels[on]]
+        return out
+
+
+def local_credible_intervals(forward, prior, params, X_map, regions, threshold=None, alpha=0.05, rounds=10, batch=None):
+    """Local credible intervals of Cai, Pereyra & McEwen (2018) from the MAP point, searched on the device (DESIGN.md section
+    14b).  For every region with indicator image ``zeta`` the surrogate ``X(xi) = X_map + A[(xi - x_map) zeta]`` (``A =
+    transform.forward``, ``x_map = transform.inverse(X_map)``) sets the region of the band-limited image to the constant xi;
+    the interval is ``{xi : F(X(xi)) <= threshold}``, F the objective of :func:`map_objective`.  **xi is real**: for a complex
+    image (a spin field, complex data) the region is set to the real constant xi, its imaginary part to zero.
+
+    :param X_map: the MAP point, ``[N]`` (``FISTA.run``'s result for one chain)
+    :param regions: int labels over the pixels (any shape with ``npix`` entries, e.g. :func:`superpixel_regions`); -1: in no
+        region; the labels in use must be 0 ... nregions - 1, an unused one raises
+    :param threshold: the level gamma; ``None``: :func:`approx_credible_region_threshold` of ``map_objective(X_map)`` with
+        ``ndim = forward.nparams`` real dimensions, twice that with ``params.complex`` (the dimension the samplers started
+        from this point move in)
+    :param rounds: search rounds; every end is then known to ``lci_shrink_factor(rounds)`` of the outer bracket
+    :param batch: regions per pass; ``None``: the chain capacity of the operators (``transform.max_chains``).  The operators
+        are grown to it (``ensure_chains``); the last batch may be smaller
+
+    Per batch: two ``transform.forward`` calls (``b = A zeta``, ``A (x_map zeta)``), two ``forward.forward`` calls and the
+    three ``lci_*`` launches sequences; one read-back at the end.  Returns :class:`LocalCredibleIntervals`."""
+    _lci_check_setup(forward, prior)
+    tr = forward.transform
+    X = ops.as_device(X_map)
+    if X.dim() == 2 and X.shape[0] == 1:
+        X = X[0]
+    if X.dim() != 1 or X.shape[0] != int(forward.nparams):
+        raise ValueError("local_credible_intervals: X_map must be one MAP point [nparams]")
+    cplx_state = torch.complex128
+    if batch is None:
+        batch = int(getattr(tr, "max_chains", 1))
+    batch = int(batch)
+    if batch < 1 or int(rounds) < 1:
+        raise ValueError("local_credible_intervals needs batch >= 1 and rounds >= 1")
+    for op in (tr, getattr(forward, "measurement", None)):
+        if hasattr(op, "ensure_chains"):
+            op.ensure_chains(batch)
+    X = X.to(cplx_state).contiguous()
+    x_map = ops.as_device(tr.inverse(X[None]))[0]
+    labels = np.asarray(regions)
+    if not np.issubdtype(labels.dtype, np.integer) or labels.size != x_map.shape[0]:
+        raise ValueError("local_credible_intervals: regions must be an integer label per pixel (%d pixels)" % x_map.shape[0])
+    if labels.min() < -1 or labels.max() < 0:
+        raise ValueError("local_credible_intervals: labels are -1 (no region) or 0 ... nregions - 1, with at least one region")
+    nreg = int(labels.max()) + 1
+    counts = np.bincount(labels[labels >= 0].ravel(), minlength=nreg)
+    if (counts == 0).any():
+        raise ValueError("local_credible_intervals: region %d has no pixel" % int(np.flatnonzero(counts == 0)[0]))
+    dev = X.device
+    lab = torch.from_numpy(labels.reshape(-1).astype(np.int64)).to(dev)
+    lmda = float(params.lmda)
+    T = prior.T_dev
+    w = _lci_weights(forward)
+    if threshold is None:
+        ndim = int(forward.nparams) * (2 if getattr(params, "complex", False) else 1)
+        gamma1 = approx_credible_region_threshold(map_objective(forward, prior, params, X), ndim, alpha)  # (a device tensor)
+    else:
+        gamma1 = torch.full((1,), float(threshold), dtype=torch.float64, device=dev)
+    gamma = gamma1.expand(batch).contiguous()
+    out = torch.empty((nreg, 8), dtype=torch.float64, device=dev)
+    status = torch.empty(nreg, dtype=torch.int32, device=dev)
+    quad = torch.empty((batch, 3), dtype=torch.float64, device=dev)
+    ndata = int(forward.data_dev.numel())
+    scratch = ops.lci_scratch(max(int(X.shape[0]), ndata), batch, dev)
+    ids = torch.arange(batch, device=dev)
+    for r0 in range(0, nreg, batch):
+        Cb = min(batch, nreg - r0)
+        zeta = (lab[None, :] == (r0 + ids[:Cb, None])).to(cplx_state)
+        b = ops.as_device(tr.forward(zeta), cplx_state)
+        a = X[None] - ops.as_device(tr.forward(zeta * x_map[None]), cplx_state)
+        pa, d = _lci_preds(forward, a)
+        pb, _ = _lci_preds(forward, b)
+        ops.lci_data_terms(pa, pb, d, w, out=quad[:Cb], scratch=scratch)
+        ops.lci_search(a, b, T, quad[:Cb], lmda, gamma[:Cb], rounds=rounds, out=out[r0 : r0 + Cb], status=status[r0 : r0 + Cb],
+                       scratch=scratch)
+    # the one read-back: the results, and the MAP image for the plain mean over every region (summed on the host in pixel
+    # order: a device scatter-add would add in an order that changes from call to call)
+    flat = torch.cat([out.reshape(-1), status.to(torch.float64), gamma1.reshape(-1)[:1], x_map.real.to(torch.float64)]).cpu().numpy()
+    host = flat[: 8 * nreg].reshape(nreg, 8)
+    stat, thr, img = flat[8 * nreg : 9 * nreg].astype(np.int32), float(flat[9 * nreg]), flat[9 * nreg + 1 :]
+    on = labels.reshape(-1) >= 0
+    means = np.bincount(labels.reshape(-1)[on], weights=img[on], minlength=nreg) / counts
+    lower, upper = host[:, 0], host[:, 1]
+    with np.errstate(invalid="ignore"):
+        rng = upper - lower
+    return LocalCredibleIntervals(labels, thr, lower=lower, upper=upper, range=rng, map_value=means,
+                                  width=np.fmax(host[:, 2], host[:, 3]), f_min=host[:, 4], xi_min=host[:, 5], status=stat,
+                                  outer=host[:, 6:8].copy())
