@@ -59,6 +59,12 @@ inline int dev_alloc(T** p, size_t bytes, const char* what) {
   return dev_alloc_bytes(reinterpret_cast<void**>(p), bytes, what);
 }
 int dev_upload(void* dst, const void* src, size_t bytes);  // host -> device copy (skipped in dry-run mode)
+// a host table on the device: allocates *d for v and copies v into it (P: T, or void where the header hides the type)
+template <class P, class T>
+inline int dev_table(P** d, const std::vector<T>& v, const char* what) {
+  if (int rc = dev_alloc(d, v.size() * sizeof(T), what)) return rc;
+  return dev_upload(*d, v.data(), v.size() * sizeof(T));
+}
 int dev_zero(void* p, size_t bytes);
 // [lo, hi) in bytes lies inside one registered allocation?  On failure *msg names the nearest allocation.
 bool dev_range_ok(const void* lo, const void* hi, std::string* msg);

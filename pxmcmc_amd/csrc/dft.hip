@@ -164,12 +164,9 @@ int make_dft_plan(int L, DftPlan* p) {
   int th = R * b.M / 2;
   p->threads = th < 64 ? 64 : (th > 1024 ? 1024 : th);
   int rc;
-  if ((rc = dev_alloc(&p->d_chirp, b.chirp.size() * sizeof(double), "Bluestein chirp"))) return rc;
-  if ((rc = dev_alloc(&p->d_bhat, b.bhat.size() * sizeof(double), "Bluestein filter spectrum"))) return rc;
-  if ((rc = dev_alloc(&p->d_tw, b.tw.size() * sizeof(double), "radix-2 twiddles"))) return rc;
-  if ((rc = dev_upload(p->d_chirp, b.chirp.data(), b.chirp.size() * sizeof(double)))) return rc;
-  if ((rc = dev_upload(p->d_bhat, b.bhat.data(), b.bhat.size() * sizeof(double)))) return rc;
-  if ((rc = dev_upload(p->d_tw, b.tw.data(), b.tw.size() * sizeof(double)))) return rc;
+  if ((rc = dev_table(&p->d_chirp, b.chirp, "Bluestein chirp"))) return rc;
+  if ((rc = dev_table(&p->d_bhat, b.bhat, "Bluestein filter spectrum"))) return rc;
+  if ((rc = dev_table(&p->d_tw, b.tw, "radix-2 twiddles"))) return rc;
   static std::atomic<uint64_t> lds_done{0};
   return allow_dynamic_lds(lds_done, {reinterpret_cast<const void*>(k_px2ring), reinterpret_cast<const void*>(k_ring2px)});
 }

@@ -878,8 +878,7 @@ int pair_make_tables(int n, bool pfa, PairTables* t) {
     pfa511_host_tables(reinterpret_cast<uint16_t*>(h.data() + o_pfa + PFA_TAB_GAT), h.data() + o_pfa + PFA_TAB_B2);
   }
   t->pfa_off = (int)o_pfa;
-  if (int rc = dev_alloc(&t->d_all, h.size() * sizeof(double), "phi-DFT tables (8 points per lane)")) return rc;
-  if (int rc = dev_upload(t->d_all, h.data(), h.size() * sizeof(double))) return rc;
+  if (int rc = dev_table(&t->d_all, h, "phi-DFT tables (8 points per lane)")) return rc;
   t->r0 = r0;
   t->cE = t->d_all + o_cE;
   t->cO = t->d_all + o_cO;
@@ -1057,8 +1056,7 @@ int dft_group_create(const std::vector<const DftPlan*>& plans, const std::vector
   out->n = (int)v.size();
   out->all = v.size() == plans.size();
   out->blocks = b0;
-  if (int rc = dev_alloc(&out->d, v.size() * sizeof(Dft5Group), "DFT group entries")) return rc;
-  if (int rc = dev_upload(out->d, v.data(), v.size() * sizeof(Dft5Group))) return rc;
+  if (int rc = dev_table(&out->d, v, "DFT group entries")) return rc;
   static std::atomic<uint64_t> lds_done{0};
   return allow_dynamic_lds(lds_done, {reinterpret_cast<const void*>(k_ring2px_group5<true, false>), reinterpret_cast<const void*>(k_ring2px_group5<true, true>),
                                       reinterpret_cast<const void*>(k_ring2px_group5<false, false>), reinterpret_cast<const void*>(k_ring2px_group5<false, true>),
@@ -1147,8 +1145,7 @@ int quad_make_tables(int n, QuadTables* t) {
   for (int w = 0; w < 4; ++w)
     for (int k0 = 0; k0 < 8; ++k0)
       for (int lane = 0; lane < 64; ++lane) put(bhat[4 * ((lane >> 3) + 8 * (lane & 7) + 64 * k0) + w]);
-  if (int rc = dev_alloc(&t->d_all, h.size() * sizeof(double), "phi-DFT tables (four waves per ring)")) return rc;
-  if (int rc = dev_upload(t->d_all, h.data(), h.size() * sizeof(double))) return rc;
+  if (int rc = dev_table(&t->d_all, h, "phi-DFT tables (four waves per ring)")) return rc;
   t->cA = t->d_all + o[0];
   t->cB = t->d_all + o[1];
   t->dA = t->d_all + o[2];

@@ -1,0 +1,122 @@
+// The harmonic split / merge stage (harm_stage.h): its two kernels, their launches, and the host tables of its weights.
+#include "../../include/pxmcmc_amd.h"
+#include "elem.h"
+#include "harm_stage.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace pxm {
+
+__device__ __forceinline__ double2 dw_w(double2 w, bool cj) { return cj ? double2{w.x, -w.y} : w; }
+
+// out_d[c][lm] = w_d(l) f[c][lm]  (w or conj(w)), for every item d and lm < bl_d^2 (out_d[c] at a_off + c cstride)
+__global__ __launch_bounds__(DW_THREADS) void k_dw_split(const double2* __restrict__ flm, double2* __restrict__ harm,
+                                                         const DwItem* __restrict__ items, int nitems,
+                                                         const double2* __restrict__ W, int cj, int L) {
+  const int d = dw_find(items, nitems, blockIdx.x);
+  const DwItem it = items[d];
+  const int lm = (blockIdx.x - it.blk0) * DW_THREADS + threadIdx.x;
+  const int nlm = it.bl * it.bl;
+  if (lm >= nlm) return;
+  const int c = blockIdx.y;
+  const double2 w = dw_w(W[it.w_off + dw_el(lm)], cj);
+  harm[it.a_off + (int64_t)c * it.cstride + lm] = cmul(w, flm[(int64_t)c * L * L + lm]);
+}
+
+// f[c][lm] = sum_d [l < bl_d] w_d(l) b_d[c][lm]
+__global__ __launch_bounds__(DW_THREADS) void k_dw_merge(const double2* __restrict__ harm, double2* __restrict__ flm,
+                                                         const DwItem* __restrict__ items, int nitems,
+                                                         const double2* __restrict__ W, int cj, int L) {
+  const int lm = blockIdx.x * DW_THREADS + threadIdx.x;
+  if (lm >= L * L) return;
+  const int c = blockIdx.y;
+  const int el = dw_el(lm);
+  double2 acc{0.0, 0.0};
+  for (int d = 0; d < nitems; ++d) {
+    const DwItem it = items[d];
+    if (el >= it.bl) continue;
+    const double2 w = dw_w(W[it.w_off + el], cj);
+    const double2 b = harm[it.a_off + (int64_t)c * it.cstride + lm];
+    acc = cadd(acc, cmul(w, b));
+  }
+  flm[(int64_t)c * L * L + lm] = acc;
+}
+
+int harm_split(const HarmStage& s, const double2* flm, double2* harm, int weights, int cj, int C, hipStream_t st) {
+  hipLaunchKernelGGL(k_dw_split, dim3(s.split_blocks, C), dim3(DW_THREADS), 0, st, flm, harm, s.d_items, s.nitems,
+                     weights ? s.d_ws : s.d_wa, cj, s.L);
+  PXM_HIP(hipGetLastError());
+  return 0;
+}
+
+int harm_merge(const HarmStage& s, const double2* harm, double2* flm, int weights, int cj, int C, hipStream_t st) {
+  hipLaunchKernelGGL(k_dw_merge, dim3((s.L * s.L + DW_THREADS - 1) / DW_THREADS, C), dim3(DW_THREADS), 0, st, harm, flm,
+                     s.d_items, s.nitems, weights ? s.d_ws : s.d_wa, cj, s.L);
+  PXM_HIP(hipGetLastError());
+  return 0;
+}
+
+void harm_release(HarmStage* s) {
+  for (void* q : {(void*)s->d_items, (void*)s->d_wa, (void*)s->d_ws}) deferred_free(q);
+}
+
+int harm_create_check(const char* who, const void* plan, int L, double B, int J_min, int N, int spin, int max_chains) {
+  const std::string fn(who);
+  PXM_REQUIRE(plan, fn + ": null plan pointer");
+  PXM_REQUIRE(L >= 2 && B > 1.0 && J_min >= 0, fn + ": bad (L, B, J_min)");
+  PXM_REQUIRE(N >= 1 && N <= L, fn + ": need 1 <= N <= L");
+  PXM_REQUIRE(std::abs(spin) < L, fn + ": |spin| must be < L");
+  PXM_REQUIRE(spin == 0 || N == 1, fn + ": spin != 0 needs N = 1 (spin directional wavelets are not supported)");
+  PXM_REQUIRE(max_chains >= 1 && max_chains <= 65535, fn + ": max_chains outside [1, 65535]");
+  PXM_REQUIRE(J_min <= j_max(L, B), fn + ": J_min > J_max");
+  PXM_REQUIRE(pxm_device_count() > 0, fn + ": no HIP device visible (the HIP path is the only path)");
+  return 0;
+}
+
+// directionality component s_lm [L*L]: nu sqrt(2^-g C(g, (g - m)/2)), m = -g, -g + 2, .., g,
+// g = gamma_l = the largest integer <= min(N - 1, l) with the parity of N - 1; nu = 1 (N odd), i (N even)
+static std::vector<double2> dir_component(int L, int N) {
+  std::vector<double2> s((size_t)L * L, double2{0.0, 0.0});
+  for (int el = 0; el < L; ++el) {
+    int g = std::min(N - 1, el);
+    if ((N - 1 - g) % 2) --g;
+    if (g < 0) continue;
+    for (int m = -g; m <= g; m += 2) {
+      // C(g, k) 2^-g through lgamma: exact enough for g < 1000 (the values are O(1) and below)
+      const int k = (g - m) / 2;
+      const double v = std::sqrt(std::exp(std::lgamma(g + 1.0) - std::lgamma(k + 1.0) - std::lgamma(g - k + 1.0) - g * std::log(2.0)));
+      s[(size_t)el * el + el + m] = (N % 2) ? double2{v, 0.0} : double2{0.0, v};
+    }
+  }
+  return s;
+}
+
+DwTiling::DwTiling(int L_, double B, int J_min_, int N, int spin_) : L(L_), J_min(J_min_), spin(spin_), s(dir_component(L_, N)) {
+  tiling_axisym(L, B, J_min, k0, kap);
+}
+
+void DwTiling::rows(int b, int n, bool harmonic, std::vector<double2>& wa, std::vector<double2>& ws) const {
+  const double ca = 1.0 / std::sqrt(2.0 * M_PI), cs = std::sqrt(2.0 * M_PI);
+  const double sgn = (!harmonic && (n % 2)) ? -1.0 : 1.0;
+  for (int el = 0; el < L; ++el) {
+    if (el < std::abs(spin)) {
+      wa.push_back({0.0, 0.0});
+      ws.push_back({0.0, 0.0});
+      continue;
+    }
+    if (!b) {
+      wa.push_back({k0[el], 0.0});
+      ws.push_back({k0[el], 0.0});
+      continue;
+    }
+    const double kj = kap[(size_t)(J_min + b - 1) * L + el];
+    const double2 sv = std::abs(n) <= el ? s[(size_t)el * el + el + n] : double2{0.0, 0.0};
+    const double fa = harmonic ? std::sqrt(8.0 * M_PI * M_PI / (2 * el + 1)) : ca;
+    const double fs = harmonic ? std::sqrt((2 * el + 1) / (8.0 * M_PI * M_PI)) : cs;
+    wa.push_back({sgn * kj * sv.x * fa, -sgn * kj * sv.y * fa});
+    ws.push_back({sgn * kj * sv.x * fs, sgn * kj * sv.y * fs});
+  }
+}
+
+}  // namespace pxm

@@ -547,21 +547,14 @@ int rec_tables_create(int L, int spin, int C, int Rp, int ncol, RecTables** out,
   }
   T->n_units = (int)units.size() / 2;
   int rc;
-  if ((rc = dev_alloc(&T->d_coefN, cN.size() * sizeof(double), "recursion coefficients (north)"))) return rc;
-  if ((rc = dev_alloc(&T->d_coefS, cS.size() * sizeof(double), "recursion coefficients (south)"))) return rc;
-  if ((rc = dev_alloc(&T->d_g, g.size() * sizeof(double), "recursion normalisation g"))) return rc;
-  if ((rc = dev_alloc(&T->d_seed, seed.size() * sizeof(double), "recursion seeds"))) return rc;
-  if ((rc = dev_alloc(&T->d_zeta, zeta.size() * sizeof(double), "ring pole distances"))) return rc;
-  if ((rc = dev_alloc(&T->d_units, units.size() * sizeof(int), "recursion units"))) return rc;
-  if ((rc = dev_alloc(&T->d_wdesc, wdesc.size() * sizeof(int), "recursion wave descriptors"))) return rc;
+  if ((rc = dev_table(&T->d_coefN, cN, "recursion coefficients (north)"))) return rc;
+  if ((rc = dev_table(&T->d_coefS, cS, "recursion coefficients (south)"))) return rc;
+  if ((rc = dev_table(&T->d_g, g, "recursion normalisation g"))) return rc;
+  if ((rc = dev_table(&T->d_seed, seed, "recursion seeds"))) return rc;
+  if ((rc = dev_table(&T->d_zeta, zeta, "ring pole distances"))) return rc;
+  if ((rc = dev_table(&T->d_units, units, "recursion units"))) return rc;
+  if ((rc = dev_table(&T->d_wdesc, wdesc, "recursion wave descriptors"))) return rc;
   if ((rc = dev_alloc(&T->d_hs, nl * T->NC * 2 * sizeof(double), "recursion packed operand"))) return rc;
-  if ((rc = dev_upload(T->d_coefN, cN.data(), cN.size() * sizeof(double)))) return rc;
-  if ((rc = dev_upload(T->d_coefS, cS.data(), cS.size() * sizeof(double)))) return rc;
-  if ((rc = dev_upload(T->d_g, g.data(), g.size() * sizeof(double)))) return rc;
-  if ((rc = dev_upload(T->d_seed, seed.data(), seed.size() * sizeof(double)))) return rc;
-  if ((rc = dev_upload(T->d_zeta, zeta.data(), zeta.size() * sizeof(double)))) return rc;
-  if ((rc = dev_upload(T->d_units, units.data(), units.size() * sizeof(int)))) return rc;
-  if ((rc = dev_upload(T->d_wdesc, wdesc.data(), wdesc.size() * sizeof(int)))) return rc;
   if ((rc = dev_zero(T->d_hs, nl * T->NC * 2 * sizeof(double)))) return rc;
   T->bytes = (cN.size() + cS.size() + g.size() + seed.size() + zeta.size()) * sizeof(double);
   *out = guard.release();

@@ -24,38 +24,17 @@
 
 namespace pxm {
 
-struct SkNoise {
-  const double* noise;        // given [C][n] array (real, or complex when cplx) or null: Philox
-  int cplx;                   // complex noise (params.complex): randn + 1j randn
-  int f64;                    // Box-Muller step in double precision (PXM_NOISE_F64)
-  uint64_t seed, chain0, iter;
-  const uint64_t* iter_dev;   // device addend to iter, read when the kernel runs (graph replay), or null
-};
+static_assert(NOISE_F64_FLAG == PXM_NOISE_F64, "elem.h: the noise flag must be the public one");
 
 struct SkCoef {
   double a, b, c, e, r;
 };
 
-// the noise of pxm_myula_step (elem.h: draw_noise), element i of chain c
-template <bool CPLX>
-__device__ __forceinline__ double2 sk_noise(const SkNoise& ns, int c, int64_t n, int64_t i) {
-  if (ns.noise) {
-    if (CPLX && ns.cplx) return reinterpret_cast<const double2*>(ns.noise)[(int64_t)c * n + i];
-    return double2{ns.noise[(int64_t)c * n + i], 0.0};
-  }
-  const uint64_t it = ns.iter + (ns.iter_dev ? *ns.iter_dev : 0);
-  if (CPLX && ns.cplx) {
-    const NormalPair q = philox_normal_pair(ns.seed, ns.chain0 + c, (uint64_t)i, it, ns.f64);
-    return double2{q.z0, q.z1};
-  }
-  return double2{philox_normal_real(ns.seed, ns.chain0 + c, (uint64_t)i, it, ns.f64), 0.0};
-}
-
 // PM: 0 no prox term, 1 P = soft(U, T), 2 P given.  HAS_G / HAS_V: gradient / second state present.  NOISE: r Z term.
 template <bool CPLX, int PM, bool HAS_G, bool HAS_V, bool NOISE>
 __global__ __launch_bounds__(256) void k_skrock_stage(const double* __restrict__ U, const double* __restrict__ P,
                                                       const double* __restrict__ T, double Ts, const double* __restrict__ G,
-                                                      const double* __restrict__ V, SkCoef k, SkNoise ns,
+                                                      const double* __restrict__ V, SkCoef k, NoiseSrc ns,
                                                       double* __restrict__ out, int64_t n) {
   const int c = blockIdx.y;
   const int64_t base = (int64_t)c * n;
@@ -76,7 +55,7 @@ __global__ __launch_bounds__(256) void k_skrock_stage(const double* __restrict__
         acc = double2{fma(k.e, v.x, acc.x), fma(k.e, v.y, acc.y)};
       }
       if constexpr (NOISE) {
-        const double2 z = sk_noise<true>(ns, c, n, i);
+        const double2 z = draw_noise<true>(ns, c, n, i);
         acc = double2{fma(k.r, z.x, acc.x), fma(k.r, z.y, acc.y)};
       }
       reinterpret_cast<double2*>(out)[base + i] = acc;
@@ -86,7 +65,7 @@ __global__ __launch_bounds__(256) void k_skrock_stage(const double* __restrict__
       if constexpr (PM != 0) acc = fma(k.b, PM == 1 ? soft_real(u, T ? T[i] : Ts) : P[base + i], acc);
       if constexpr (HAS_G) acc = fma(k.c, G[base + i], acc);
       if constexpr (HAS_V) acc = fma(k.e, V[base + i], acc);
-      if constexpr (NOISE) acc = fma(k.r, sk_noise<false>(ns, c, n, i).x, acc);
+      if constexpr (NOISE) acc = fma(k.r, draw_noise<false>(ns, c, n, i).x, acc);
       out[base + i] = acc;
     }
   }
@@ -101,7 +80,7 @@ static inline dim3 sk_grid(int64_t n, int C) {
 
 template <bool CPLX, int PM, bool HAS_G, bool HAS_V>
 static void sk_launch_noise(bool noise, dim3 g, hipStream_t st, const double* U, const double* P, const double* T, double Ts,
-                            const double* G, const double* V, SkCoef k, const SkNoise& ns, double* out, int64_t n) {
+                            const double* G, const double* V, SkCoef k, const NoiseSrc& ns, double* out, int64_t n) {
   if (noise)
     hipLaunchKernelGGL((k_skrock_stage<CPLX, PM, HAS_G, HAS_V, true>), g, dim3(256), 0, st, U, P, T, Ts, G, V, k, ns, out, n);
   else
@@ -110,7 +89,7 @@ static void sk_launch_noise(bool noise, dim3 g, hipStream_t st, const double* U,
 
 template <bool CPLX, int PM>
 static void sk_launch_gv(bool noise, dim3 g, hipStream_t st, const double* U, const double* P, const double* T, double Ts,
-                         const double* G, const double* V, SkCoef k, const SkNoise& ns, double* out, int64_t n) {
+                         const double* G, const double* V, SkCoef k, const NoiseSrc& ns, double* out, int64_t n) {
   if (G && V) sk_launch_noise<CPLX, PM, true, true>(noise, g, st, U, P, T, Ts, G, V, k, ns, out, n);
   else if (G) sk_launch_noise<CPLX, PM, true, false>(noise, g, st, U, P, T, Ts, G, V, k, ns, out, n);
   else if (V) sk_launch_noise<CPLX, PM, false, true>(noise, g, st, U, P, T, Ts, G, V, k, ns, out, n);
@@ -119,7 +98,7 @@ static void sk_launch_gv(bool noise, dim3 g, hipStream_t st, const double* U, co
 
 template <bool CPLX>
 static void sk_launch(int pm, bool noise, dim3 g, hipStream_t st, const double* U, const double* P, const double* T, double Ts,
-                      const double* G, const double* V, SkCoef k, const SkNoise& ns, double* out, int64_t n) {
+                      const double* G, const double* V, SkCoef k, const NoiseSrc& ns, double* out, int64_t n) {
   if (pm == 0) sk_launch_gv<CPLX, 0>(noise, g, st, U, P, T, Ts, G, V, k, ns, out, n);
   else if (pm == 1) sk_launch_gv<CPLX, 1>(noise, g, st, U, P, T, Ts, G, V, k, ns, out, n);
   else sk_launch_gv<CPLX, 2>(noise, g, st, U, P, T, Ts, G, V, k, ns, out, n);
@@ -143,7 +122,7 @@ int pxm_skrock_stage(const void* U, const void* proxf, const double* T, double T
   if (int rc = check_noise_arg("pxm_skrock_stage", noise_complex, dtype)) return rc;
   const int pm = b == 0.0 ? 0 : (proxf ? 2 : 1);
   const bool nz = r != 0.0;
-  const SkNoise ns{(const double*)noise, noise_complex & 1, (noise_complex & PXM_NOISE_F64) ? 1 : 0, seed, chain0, iter, iter_dev};
+  const NoiseSrc ns = make_noise_src(noise, noise_complex, seed, chain0, iter, iter_dev);
   const SkCoef k{a, b, c, e, r};
   const dim3 g = sk_grid(n, C);
   hipStream_t st = (hipStream_t)stream;

@@ -279,8 +279,7 @@ int upload_tasks(std::vector<GemmTask> v, bool paired, TaskList* out, std::vecto
   if (v.empty()) return 0;
   // address ranges of every load / store the launches of this list can form (sht_gemm.hip: check_gemm_task_ranges)
   if (int rc = check_gemm_task_ranges(v, out->nslab, pk, out->flags, ncol, ws_base, name)) return rc;
-  if (int rc = dev_alloc(&out->d, v.size() * sizeof(GemmTask), "GEMM task list")) return rc;
-  return dev_upload(out->d, v.data(), v.size() * sizeof(GemmTask));
+  return dev_table(&out->d, v, "GEMM task list");
 }
 
 double tasklist_bytes(const TaskList& tl, int cg) {

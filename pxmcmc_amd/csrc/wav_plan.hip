@@ -168,10 +168,8 @@ static int wav_plan_create_impl(const char* who, int L, double B, int J_min, int
       kc_syn[(size_t)s * p->Rp + el] = (s == 0) ? k : cs * k;
       kc_ana[(size_t)s * p->Rp + el] = (s == 0) ? k : ca * k;
     }
-  if ((rc = dev_alloc(&p->d_kc_syn, kc_syn.size() * sizeof(double), "synthesis kernel rows c kappa [nsc][Rp]"))) return rc;
-  if ((rc = dev_alloc(&p->d_kc_ana, kc_ana.size() * sizeof(double), "analysis kernel rows c kappa [nsc][Rp]"))) return rc;
-  if ((rc = dev_upload(p->d_kc_syn, kc_syn.data(), kc_syn.size() * sizeof(double)))) return rc;
-  if ((rc = dev_upload(p->d_kc_ana, kc_ana.data(), kc_ana.size() * sizeof(double)))) return rc;
+  if ((rc = dev_table(&p->d_kc_syn, kc_syn, "synthesis kernel rows c kappa [nsc][Rp]"))) return rc;
+  if ((rc = dev_table(&p->d_kc_ana, kc_ana, "analysis kernel rows c kappa [nsc][Rp]"))) return rc;
   // support cut per scale: first degree with a non-zero kernel (compact support of kappa_j).  The rows / contraction
   // steps below it are skipped, and it is the row mask of the fused combine (class buffers are shared by scales with
   // disjoint supports).

@@ -35,8 +35,7 @@ static int wl_build(const pxm_wav_plan_s* p, WlAttach* w) {
   int rc;
   std::vector<double> k((size_t)p->Rp, 0.0);
   for (int el = 2; el < p->L; ++el) k[el] = -std::sqrt(((el + 2.0) * (el - 1.0)) / ((el + 1.0) * el));
-  if ((rc = dev_alloc(&w->d_wlk, k.size() * sizeof(double), "weak-lensing harmonic kernel k_l [Rp]"))) return rc;
-  if ((rc = dev_upload(w->d_wlk, k.data(), k.size() * sizeof(double)))) return rc;
+  if ((rc = dev_table(&w->d_wlk, k, "weak-lensing harmonic kernel k_l [Rp]"))) return rc;
   // one chain, two top scales of equal bandlimit outside the DFT group (L = 512, B = 2: scales 8 and 9): twin ring array
   if (p->pk == 2 && p->Cmax == 1)
     for (int s = 0; s + 1 < p->nsc && w->twin_s < 0; ++s)

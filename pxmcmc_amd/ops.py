@@ -908,9 +908,53 @@ class ShtPlan(_Plan):
         return int(check(lib.pxm_sht_uses_recursion(self._h)))
 
 
-class WavPlan(_Plan):
+def _update_out(out, x):
+    """the ``out=`` buffer of a fused step: fresh, or a distinct tensor of the state's shape"""
+    if out is None:
+        return torch.empty_like(x)
+    if out.shape != x.shape or out.dtype != _CPLX or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+        raise ValueError("out= buffer must be a distinct contiguous complex128 tensor of the state's shape")
+    return out
+
+
+def _preds_out(preds_out, x, n):
+    """the ``preds_out=`` buffer of a fused step: fresh, or [chains of x][n]"""
+    if preds_out is None:
+        return torch.empty((x.shape[0], n), dtype=_CPLX, device=x.device)
+    if preds_out.shape != (x.shape[0], n) or preds_out.dtype != _CPLX or not preds_out.is_contiguous():
+        raise ValueError("preds_out= buffer has the wrong shape / dtype / layout")
+    return preds_out
+
+
+class _WaveletPlan(_Plan):
+    """The four transforms of a wavelet plan: the entry points ``pxm_<_abi>_*`` between coefficient vectors [ncoefs] and
+    images whose length is the attribute named by ``_image`` (``npix`` pixels, or ``nlm`` harmonic coefficients)."""
+
+    def _fn(self, name):
+        return getattr(lib, f"pxm_{self._abi}_{name}")
+
+    @property
+    def _nimg(self):
+        return getattr(self, self._image)
+
+    def synthesis(self, X, out=None):
+        return self._run(self._fn("synthesis"), X, self.ncoefs, self._nimg, out=out)
+
+    def synthesis_adjoint(self, f):
+        return self._run(self._fn("synthesis_adjoint"), f, self._nimg, self.ncoefs)
+
+    def analysis(self, f):
+        return self._run(self._fn("analysis"), f, self._nimg, self.ncoefs)
+
+    def analysis_adjoint(self, X):
+        return self._run(self._fn("analysis_adjoint"), X, self.ncoefs, self._nimg)
+
+
+class WavPlan(_WaveletPlan):
     """Axisymmetric scale-discretised wavelet transforms (replaces the pys2let calls).  ``spin``: spin of the images;
     the coefficients are spin-0 functions in the same layout whatever it is."""
+
+    _abi, _image = "wav", "npix"
 
     def __init__(self, L, B, J_min, max_chains=1, spin=0):
         require_gpu()
@@ -923,28 +967,12 @@ class WavPlan(_Plan):
         super().__init__(lib.pxm_wav_plan_create_spin, (self.L, self.B, self.J_min, self.spin, self.max_chains, 0),
                          lib.pxm_wav_plan_destroy, lib.pxm_wav_status, f"WavPlan(L={self.L}, spin={self.spin})")
 
-    def synthesis(self, X, out=None):
-        return self._run(lib.pxm_wav_synthesis, X, self.ncoefs, self.npix, out=out)
-
-    def synthesis_adjoint(self, f):
-        return self._run(lib.pxm_wav_synthesis_adjoint, f, self.npix, self.ncoefs)
-
-    def analysis(self, f):
-        return self._run(lib.pxm_wav_analysis, f, self.npix, self.ncoefs)
-
-    def analysis_adjoint(self, X):
-        return self._run(lib.pxm_wav_analysis_adjoint, X, self.ncoefs, self.npix)
-
     def _update_args(self, x, T, noise, noise_complex, pairs, out):
         """the MYULA-update arguments of the fused steps: thresholds, noise (``pairs``: two real chains per complex slot,
         PXM_MODE_REAL_PAIRS) and the result buffer (fresh, or a distinct tensor of the state's shape)"""
         Tv, Ts = _vecT(T, self.ncoefs, x.device)
         w, wc = _pair_noise_args(noise, x) if pairs else _noise_args(noise, x, noise_complex)
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != _CPLX or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
-            raise ValueError("out= buffer must be a distinct contiguous complex128 tensor of the state's shape")
-        return Tv, Ts, w, wc, out
+        return Tv, Ts, w, wc, _update_out(out, x)
 
     def gradg_step(self, X, preds, data, invcov, T, delta, lmda, noise=None, noise_complex=False, seed=0, chain0=0, it=0, out=None,
                    pairs=False, noise64=False):
@@ -991,10 +1019,7 @@ class WavPlan(_Plan):
             raise AssertionError("image_step: shape mismatch")
         d, ic = self._image_args(data, invcov)
         Tv, Ts, w, wc, out = self._update_args(x, T, noise, noise_complex, pairs, out)
-        if preds_out is None:
-            preds_out = torch.empty((x.shape[0], self.npix), dtype=_CPLX, device=x.device)
-        elif preds_out.shape != (x.shape[0], self.npix) or preds_out.dtype != _CPLX or not preds_out.is_contiguous():
-            raise ValueError("preds_out= buffer has the wrong shape / dtype / layout")
+        preds_out = _preds_out(preds_out, x, self.npix)
         check(
             lib.pxm_wav_image_step(
                 self._h, _p(x), _p(d), _p(ic), int(ic.is_complex()), _p(Tv), Ts, float(delta), float(lmda),
@@ -1118,10 +1143,12 @@ class WavPlan(_Plan):
         return (ms.value, nl.value, nb.value, nf.value), (dms.value, dnl.value, dnb.value)
 
 
-class DirWavPlan(_Plan):
+class DirWavPlan(_WaveletPlan):
     """Directional (N = dirs >= 1) scale-discretised wavelet transforms, spin 0 (replaces the pys2let calls with N > 1;
     include/pxmcmc_amd.h, pxm_dwav_*).  Layout [scaling | j = J_min .. J_max], block j = 2N - 1 orientation planes of
     the MW grid at bl_j.  With N = 1 it computes what :class:`WavPlan` computes (without WavPlan's fused sampler steps)."""
+
+    _abi, _image = "dwav", "npix"
 
     def __init__(self, L, B, J_min, N, max_chains=1):
         require_gpu()
@@ -1132,18 +1159,6 @@ class DirWavPlan(_Plan):
         self.nscal = int(nscal.value)
         super().__init__(lib.pxm_dwav_plan_create, (self.L, self.B, self.J_min, self.N, self.max_chains, 0),
                          lib.pxm_dwav_plan_destroy, lib.pxm_dwav_status, f"DirWavPlan(L={self.L}, N={self.N})")
-
-    def synthesis(self, X, out=None):
-        return self._run(lib.pxm_dwav_synthesis, X, self.ncoefs, self.npix, out=out)
-
-    def synthesis_adjoint(self, f):
-        return self._run(lib.pxm_dwav_synthesis_adjoint, f, self.npix, self.ncoefs)
-
-    def analysis(self, f):
-        return self._run(lib.pxm_dwav_analysis, f, self.npix, self.ncoefs)
-
-    def analysis_adjoint(self, X):
-        return self._run(lib.pxm_dwav_analysis_adjoint, X, self.ncoefs, self.npix)
 
     def table_bytes(self):
         """device bytes of the tables the plan reads (inner Wigner tables + its own weights and phases)"""
@@ -1156,11 +1171,13 @@ class DirWavPlan(_Plan):
         return a.value, b.value, c.value
 
 
-class HarmWavPlan(_Plan):
+class HarmWavPlan(_WaveletPlan):
     """Harmonic-space scale-discretised wavelet transforms (replaces pys2let's analysis_lm2lmn / synthesis_lmn2lm and
     their adjoints; include/pxmcmc_amd.h, pxm_hwav_*).  Inputs and outputs are spherical-harmonic coefficients: f_lm
     [L*L] and the layout [scaling: bl_0^2 | j = J_min .. J_max: n = -(N-1), .., N-1: bl_j^2 each] (DESIGN.md section
     13).  N > 1 at spin 0 only."""
+
+    _abi, _image = "hwav", "nlm"
 
     def __init__(self, L, B, J_min, N=1, spin=0, max_chains=1):
         require_gpu()
@@ -1173,18 +1190,6 @@ class HarmWavPlan(_Plan):
         super().__init__(lib.pxm_hwav_plan_create, (self.L, self.B, self.J_min, self.N, self.spin, self.max_chains, 0),
                          lib.pxm_hwav_plan_destroy, lib.pxm_hwav_status,
                          f"HarmWavPlan(L={self.L}, N={self.N}, spin={self.spin})")
-
-    def synthesis(self, X, out=None):
-        return self._run(lib.pxm_hwav_synthesis, X, self.ncoefs, self.nlm, out=out)
-
-    def synthesis_adjoint(self, flm):
-        return self._run(lib.pxm_hwav_synthesis_adjoint, flm, self.nlm, self.ncoefs)
-
-    def analysis(self, flm):
-        return self._run(lib.pxm_hwav_analysis, flm, self.nlm, self.ncoefs)
-
-    def analysis_adjoint(self, X):
-        return self._run(lib.pxm_hwav_analysis_adjoint, X, self.ncoefs, self.nlm)
 
     def info(self):
         """(items, split workgroups per chain, most items with a non-zero weight at one degree)"""
@@ -1210,14 +1215,7 @@ class HarmWavPlan(_Plan):
             if k.numel() != self.nlm:
                 raise ValueError("kernel length mismatch")
         Tv, Ts = _vecT(T, self.ncoefs, x.device)
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != _CPLX or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
-            raise ValueError("out= buffer must be a distinct contiguous complex128 tensor of the state's shape")
-        if preds_out is None:
-            preds_out = torch.empty((x.shape[0], self.nlm), dtype=_CPLX, device=x.device)
-        elif preds_out.shape != (x.shape[0], self.nlm) or preds_out.dtype != _CPLX or not preds_out.is_contiguous():
-            raise ValueError("preds_out= buffer has the wrong shape / dtype / layout")
+        out, preds_out = _update_out(out, x), _preds_out(preds_out, x, self.nlm)
         check(
             lib.pxm_hwav_myula_step(
                 self._h, _p(x), _p(d), _p(ic), int(ic.is_complex()), _p(k), _p(Tv), Ts, float(delta), float(lmda),

@@ -126,6 +126,33 @@ def test_dirwav_four_ops_match_model_L256_16chains():
     _four_ops_vs_model(256, 2.0, 2, 4, 16, [0, 15], 1e-11)
 
 
+def test_dirwav_refusals_leave_plan_usable():
+    """every transform entry point refuses too many chains and a null input on the host, in its own name, and the plan
+    computes the same afterwards"""
+    import ctypes
+
+    import torch
+
+    from pxmcmc_amd import ops
+    from pxmcmc_amd._lib import lib
+
+    L = 8
+    plan = ops.DirWavPlan(L, 2.0, 1, 2, max_chains=2)
+    X0 = _cplx(np.random.default_rng(5), 2, plan.ncoefs)
+    before = plan.synthesis(X0).clone()
+    x = torch.zeros((3, plan.ncoefs), dtype=torch.complex128, device="cuda")
+    f = torch.zeros((3, plan.npix), dtype=torch.complex128, device="cuda")
+    vp = ctypes.c_void_p
+    for name, out in (("synthesis", f), ("synthesis_adjoint", x), ("analysis", x), ("analysis_adjoint", f)):
+        fn = getattr(lib, "pxm_dwav_" + name)
+        src = x if out is f else f
+        assert fn(plan._h, vp(src.data_ptr()), vp(out.data_ptr()), 3, None) < 0
+        assert b"pxm_dwav_" + name.encode() + b": C outside [1, max_chains]" in lib.pxm_last_error()
+        assert fn(plan._h, None, vp(out.data_ptr()), 1, None) < 0
+        assert b"pxm_dwav_" + name.encode() + b": null argument" in lib.pxm_last_error()
+    assert torch.equal(plan.synthesis(X0), before)
+
+
 # ---- operator properties -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("L,B,J_min,N", [(16, 2.0, 1, 2), (32, 1.5, 2, 3), (32, 2.0, 2, 4), (64, 2.0, 2, 7), (24, 2.0, 1, 9)])
 def test_dirwav_properties(L, B, J_min, N):
