@@ -80,20 +80,21 @@ def step_hint(forward_operator, params, args):
     return L_g
 
 
-def map_start(forward_operator, prior, params, L_g, start_point=None, tol=1e-3, max_iter=2000):
+def map_start(forward_operator, prior, params, L_g, start_point=None, tol=1e-3, max_iter=2000, restart=None):
     """FISTA on the samplers' posterior as the chain's start point.  The shear data are complex with a real sig_d, so the
     inverse covariance is complex (pxmcmc/forward.py:81-82) and FISTA takes its gradient on the operator with Re(invcov),
     for which 1 / L_g of the full operator is a valid (smaller) step.  The steps of FISTA shrink like 1 / k, so the run is
     bounded: at most ``max_iter`` operator pairs, stopping at a relative step of ``tol`` (a start point, not a final
-    estimate)."""
-    fista = FISTA(forward_operator, prior, params, gamma=1 / (L_g * (1 + 1e-3)), tol=tol, max_iter=max_iter)
+    estimate; ``restart="gradient"``, --map-restart, removes that tail)."""
+    fista = FISTA(forward_operator, prior, params, gamma=1 / (L_g * (1 + 1e-3)), tol=tol, max_iter=max_iter, restart=restart)
     x = fista.run(start_point=start_point)
+    its = f"{int(fista.niter[0])} iterations" + (f", {int(fista.nrestarts[0])} restarts" if restart else "")
     if fista._stock_prox:
-        print(f"MAP start: FISTA stopped after {int(fista.niter[0])} iterations (converged: {bool(fista.converged[0])}), "
+        print(f"MAP start: FISTA stopped after {its} (converged: {bool(fista.converged[0])}), "
               f"objective {fista.objective_map[0]:.6e}")
     else:  # the prior's own prox carries its own threshold: the fixed point of that iteration, not the posterior's MAP
         print(f"start point: fixed point of the prior's own prox-gradient iteration (g + (lmda / gamma) f, not the MAP) after "
-              f"{int(fista.niter[0])} iterations (converged: {bool(fista.converged[0])})")
+              f"{its} (converged: {bool(fista.converged[0])})")
     return x
 
 
@@ -179,6 +180,8 @@ def main(argv=None):
     ap.add_argument("--dirs", type=int, default=1, help="wavelet directions N (1: axisymmetric; > 1: directional)")
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--map-start", action="store_true", help="start the chain(s) at the MAP point found by FISTA first")
+    ap.add_argument("--map-restart", action="store_true",
+                    help="with --map-start: FISTA with adaptive (gradient) restart, decided per chain on the device")
     ap.add_argument("--local-ci", type=int, default=None, metavar="SIZE",
                     help="with --map-start: local credible intervals of the MAP point on superpixels of SIZE x SIZE samples "
                          "(pixel-space posterior only)")
@@ -201,6 +204,8 @@ def main(argv=None):
         ap.error("--summary-alpha needs --summary")
     if args.summary_ess is not None and not args.summary:
         ap.error("--summary-ess needs --summary")
+    if args.map_restart and not args.map_start:
+        ap.error("--map-restart needs --map-start")
     if args.local_ci is not None and (not args.map_start or args.harmonic):
         ap.error("--local-ci needs --map-start and the pixel-space posterior (no --harmonic)")
     if args.summary not in (None, True, "state" if args.harmonic else "image"):
@@ -227,7 +232,7 @@ def main(argv=None):
     L_g = step_hint(forward_operator, params, args)
     if args.estimate_mu:
         prior, params = estimate_mu(forward_operator, prior, params, L_g, args)
-    start_point = map_start(forward_operator, prior, params, L_g) if args.map_start else None
+    start_point = map_start(forward_operator, prior, params, L_g, restart="gradient" if args.map_restart else None) if args.map_start else None
     if args.local_ci is not None:
         local_ci_maps(forward_operator, prior, params, start_point, L, args.local_ci,
                       os.path.join(args.outdir, f"{args.algo}_{setting}_{args.jobid}"))
@@ -277,7 +282,7 @@ def _main_harmonic(args, L, B, J_min, setting):
     if args.estimate_mu:
         prior, params = estimate_mu(forward_operator, prior, params, L_g, args, start_point=X0)
     if args.map_start:
-        X0 = map_start(forward_operator, prior, params, L_g, start_point=X0)
+        X0 = map_start(forward_operator, prior, params, L_g, start_point=X0, restart="gradient" if args.map_restart else None)
     mcmc = build_sampler(args, forward_operator, prior, params, "state")
     now = datetime.now()
     t0 = time.perf_counter()

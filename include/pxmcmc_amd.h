@@ -375,6 +375,23 @@ int pxm_fista_step(const void* Y, const void* gradg, const void* proxf, const do
                    const void* X_prev, double gamma, double lmda, const double* beta_table, int64_t n_beta,
                    uint64_t iter, const uint64_t* iter_dev, void* X_out, void* Y_out, double* sums, double* scratch,
                    int64_t n, int C, int dtype, pxm_stream_t stream);
+/* pxm_fista_step with adaptive (gradient) restart decided per chain on the device (O'Donoghue & Candes 2015; DESIGN.md
+ * section 14).  The arguments and the arithmetic of X_out, Y_out and the first three sums are those of pxm_fista_step, except:
+ *   beta = beta_table[min(momentum_index[c], n_beta - 1)]: momentum_index [C] is the chain's own index on the device, read
+ *   by the step and then updated by the finishing kernel;
+ *   sums is [C][4]: the three sums of pxm_fista_step, then r_c = sum_i Re conj(Y_i - X_out_i) (X_out_i - X_prev_i), its
+ *   terms (y.re - x.re) d.re + (y.im - x.im) d.im formed without contraction and added in the same fixed order;
+ *   after the step: restart_on != 0 and r_c > 0 (false for 0 and for NaN) -> momentum_index[c] = 0 and, with restarts [C]
+ *   given (NULL: not counted), restarts[c] += 1; otherwise momentum_index[c] += 1.  Y_out keeps the momentum of the step that
+ *   decided: the reset acts on the following step, which runs with beta_table[0].
+ *   Y is needed with proxf given too (r_c reads it); gradg and T are still not read then.
+ *   With n == 0 the sums are zeros (NaN for the third with proxf given) and the indices advance.
+ * scratch: caller-owned, 4 * PXM_FISTA_SLICES_MAX * C doubles.  momentum_index, restarts and sums must be different arrays.
+ * No atomics and no host read: a HIP graph replays it. */
+int pxm_fista_step_restart(const void* Y, const void* gradg, const void* proxf, const double* T, double T_scalar,
+                           const void* X_prev, double gamma, double lmda, const double* beta_table, int64_t n_beta,
+                           uint64_t* momentum_index, uint64_t* restarts, int restart_on, void* X_out, void* Y_out,
+                           double* sums, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream);
 /* One SAPG iteration (Vidal, De Bortoli, Pereyra & Durmus 2020): a MYULA step of every chain on the
  * posterior whose prior is scaled by the chain's theta, then the move of theta towards the marginal maximum-likelihood
  * value of the regularisation strength.  Every state array [C][n]; theta, eta [C] float64 on the device, updated in place.

@@ -236,6 +236,48 @@ def fista_scratch(C_, dev):
     return torch.empty(3 * FISTA_SLICES_MAX * int(C_), dtype=_REAL, device=dev)
 
 
+def fista_restart_scratch(C_, dev):
+    """scratch of :func:`fista_step_restart` for C_ chains: four partial sums per slice and chain"""
+    return torch.empty(4 * FISTA_SLICES_MAX * int(C_), dtype=_REAL, device=dev)
+
+
+def _fista_args(name, nsums, Y, gradg, X_prev, beta, T, proxf, y_with_proxf, out, sums, scratch):
+    """the arguments the two FISTA steps share, checked -> (x0, squeeze, y, g, px, Tv, Ts, bt, x1, y1, sums, scratch);
+    ``y_with_proxf``: Y is passed on next to a given proxf (the restarted step reads it)"""
+    x0, squeeze = _batched(as_device(X_prev))
+    given = proxf is not None
+    args = []
+    for t in ((proxf, Y if y_with_proxf else None, None) if given else (None, Y, gradg)):
+        if t is None:
+            args.append(None)
+            continue
+        t, _ = _batched(as_device(t, x0.dtype))
+        if t.shape != x0.shape:
+            raise ValueError(f"{name}: Y / gradg / proxf must have the state's shape")
+        args.append(t)
+    px, y, g = args
+    if not given and T is None:
+        raise ValueError(f"{name}: the threshold T is needed unless proxf is given")
+    Tv, Ts = (None, 0.0) if given else _vecT(T, x0.shape[1], x0.device)
+    bt = beta if isinstance(beta, torch.Tensor) else as_device(np.atleast_1d(np.asarray(beta, dtype=float)), _REAL)
+    if bt.dtype != _REAL or bt.dim() != 1 or bt.numel() < 1 or not bt.is_contiguous() or bt.device != x0.device:
+        raise ValueError(f"{name}: beta must be a non-empty contiguous float64 device vector")
+    C_ = x0.shape[0]
+    if out is None:
+        x1, y1 = torch.empty_like(x0), torch.empty_like(x0)
+    else:
+        x1, y1 = _out_like(out[0], x0), _out_like(out[1], x0)
+    if sums is None:
+        sums = torch.empty((C_, nsums), dtype=_REAL, device=x0.device)
+    elif sums.shape != (C_, nsums) or sums.dtype != _REAL or not sums.is_contiguous():
+        raise ValueError(f"{name}: sums must be a contiguous float64 [C, {nsums}] device array")
+    if scratch is None:
+        scratch = torch.empty(nsums * FISTA_SLICES_MAX * C_, dtype=_REAL, device=x0.device)
+    elif scratch.numel() < nsums * FISTA_SLICES_MAX * C_ or scratch.dtype != _REAL:
+        raise ValueError(f"{name}: scratch is too small")
+    return x0, squeeze, y, g, px, Tv, Ts, bt, x1, y1, sums, scratch
+
+
 def fista_step(Y, gradg, X_prev, gamma, lmda, beta, T=None, proxf=None, it=0, iter_dev=None, out=None, sums=None, scratch=None):
     """One FISTA iteration in one launch: ``X1 = soft(Y - gamma gradg, gamma T / lmda)`` -- or
     ``proxf`` when given (the prior's own prox of ``Y - gamma gradg``; Y, gradg and T are then not read) -- and
@@ -244,42 +286,46 @@ def fista_step(Y, gradg, X_prev, gamma, lmda, beta, T=None, proxf=None, it=0, it
     ``beta``: the momentum table (float64 device vector, or a sequence); ``beta_k`` is entry ``it`` [+ ``*iter_dev``], read
     when the kernel runs and clamped to the table's last entry.  ``out``: the pair of result buffers ``(X1, Y1)`` (neither
     may alias an input).  Returns ``(X1, Y1, sums)`` with ``sums`` float64 [C, 3]: per chain ``sum |X1 - X_prev|^2``,
-    ``sum |X1|^2`` and ``sum T_i |X1_i|`` (NaN with ``proxf``)."""
-    x0, squeeze = _batched(as_device(X_prev))
-    given = proxf is not None
-    args = []
-    for t in ((proxf, None, None) if given else (None, Y, gradg)):
-        if t is None:
-            args.append(None)
-            continue
-        t, _ = _batched(as_device(t, x0.dtype))
-        if t.shape != x0.shape:
-            raise ValueError("fista_step: Y / gradg / proxf must have the state's shape")
-        args.append(t)
-    px, y, g = args
-    if not given and T is None:
-        raise ValueError("fista_step: the threshold T is needed unless proxf is given")
-    Tv, Ts = (None, 0.0) if given else _vecT(T, x0.shape[1], x0.device)
-    bt = beta if isinstance(beta, torch.Tensor) else as_device(np.atleast_1d(np.asarray(beta, dtype=float)), _REAL)
-    if bt.dtype != _REAL or bt.dim() != 1 or bt.numel() < 1 or not bt.is_contiguous() or bt.device != x0.device:
-        raise ValueError("fista_step: beta must be a non-empty contiguous float64 device vector")
-    C_ = x0.shape[0]
-    if out is None:
-        x1, y1 = torch.empty_like(x0), torch.empty_like(x0)
-    else:
-        x1, y1 = _out_like(out[0], x0), _out_like(out[1], x0)
-    if sums is None:
-        sums = torch.empty((C_, 3), dtype=_REAL, device=x0.device)
-    elif sums.shape != (C_, 3) or sums.dtype != _REAL or not sums.is_contiguous():
-        raise ValueError("fista_step: sums must be a contiguous float64 [C, 3] device array")
-    if scratch is None:
-        scratch = fista_scratch(C_, x0.device)
-    elif scratch.numel() < 3 * FISTA_SLICES_MAX * C_ or scratch.dtype != _REAL:
-        raise ValueError("fista_step: scratch is too small (fista_scratch)")
+    ``sum |X1|^2`` and ``sum T_i |X1_i|`` (NaN with ``proxf``).  ``scratch``: :func:`fista_scratch`."""
+    x0, squeeze, y, g, px, Tv, Ts, bt, x1, y1, sums, scratch = _fista_args("fista_step", 3, Y, gradg, X_prev, beta, T, proxf, False,
+                                                                          out, sums, scratch)
     check(
         lib.pxm_fista_step(
             _p(y), _p(g), _p(px), _p(Tv), Ts, _p(x0), float(gamma), float(lmda), _p(bt), bt.numel(), int(it), _p(iter_dev),
-            _p(x1), _p(y1), _p(sums), _p(scratch), x0.shape[1], C_, _dt(x0), _stream()
+            _p(x1), _p(y1), _p(sums), _p(scratch), x0.shape[1], x0.shape[0], _dt(x0), _stream()
+        )
+    )
+    return (x1[0], y1[0], sums) if squeeze else (x1, y1, sums)
+
+
+def _index_arg(name, what, t, C_, dev):
+    """a per-chain 64-bit device counter (torch.int64, or torch.uint64: the library reads it as uint64_t)"""
+    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype not in (torch.int64, torch.uint64) or t.shape != (C_,)
+                          or not t.is_contiguous() or t.device != dev):
+        raise ValueError(f"{name}: {what} must be a contiguous 64-bit integer [C] device vector")
+    return t
+
+
+def fista_step_restart(Y, gradg, X_prev, gamma, lmda, beta, momentum_index, T=None, proxf=None, restarts=None, restart=True,
+                       out=None, sums=None, scratch=None):
+    """:func:`fista_step` with adaptive (gradient) restart decided per chain on the device.
+
+    ``momentum_index`` ([C] 64-bit integer device vector): chain c steps with ``beta[min(momentum_index[c], len - 1)]``.
+    ``sums`` is float64 [C, 4]: the three sums of :func:`fista_step`, then ``r_c = sum Re conj(Y - X1) (X1 - X_prev)``.
+    After the step the device sets ``momentum_index[c] = 0`` and adds one to ``restarts[c]`` (optional [C] vector) where
+    ``restart`` and ``r_c > 0``, and adds one to ``momentum_index[c]`` everywhere else; ``Y1`` keeps the momentum of this
+    step.  ``Y`` is needed with ``proxf`` too (``r_c`` reads it).  A missing ``momentum_index`` is reported by the library.
+    ``scratch``: :func:`fista_restart_scratch`.  Returns ``(X1, Y1, sums)``."""
+    name = "fista_step_restart"
+    x0, squeeze, y, g, px, Tv, Ts, bt, x1, y1, sums, scratch = _fista_args(name, 4, Y, gradg, X_prev, beta, T, proxf, True, out,
+                                                                          sums, scratch)
+    C_ = x0.shape[0]
+    mi = _index_arg(name, "momentum_index", momentum_index, C_, x0.device)
+    rs = _index_arg(name, "restarts", restarts, C_, x0.device)
+    check(
+        lib.pxm_fista_step_restart(
+            _p(y), _p(g), _p(px), _p(Tv), Ts, _p(x0), float(gamma), float(lmda), _p(bt), bt.numel(), _p(mi), _p(rs),
+            int(bool(restart)), _p(x1), _p(y1), _p(sums), _p(scratch), x0.shape[1], C_, _dt(x0), _stream()
         )
     )
     return (x1[0], y1[0], sums) if squeeze else (x1, y1, sums)

@@ -8,8 +8,8 @@ threshold: f is the potential whose prox MYULA's drift applies, so the estimator
 sample.  The objective is defined through ``T``, not through ``prior.prior``: ``S2_Wavelets_L1_Power_Weights.prior`` applies
 its weights twice, and the estimator minimises the function its prox belongs to.
 
-One iteration is one fused HIP launch (``pxm_fista_step``) around the two operator calls, replayed from a captured HIP graph
-by the samplers' stepping engine.
+One iteration is one fused HIP launch (``pxm_fista_step``, or ``pxm_fista_step_restart`` with adaptive restart) around the two
+operator calls, replayed from a captured HIP graph by the samplers' stepping engine.
 """
 import copy
 import warnings
@@ -74,6 +74,11 @@ class FISTA(PxMCMC):
         a redundant frame) while the fixed-point residual is far smaller: ``last_steps`` bounds the latter
     :param check_every: iterations between two checks; between checks the iterations are replayed from the captured graph
     :param use_graph: replay from a captured HIP graph (``False``: the same launches one by one, same results)
+    :param restart: ``None``, or ``"gradient"``: adaptive restart (O'Donoghue & Candes 2015), which removes the ``1 / k`` tail.
+        Every chain has its own momentum index ``k_c`` on the device and steps with ``beta_{k_c}``; the step also forms
+        ``r_c = sum Re conj(Y_k - X_{k+1}) (X_{k+1} - X_k)``, and ``r_c > 0`` sets ``k_c = 0`` (otherwise ``k_c + 1``).  The
+        decision is taken on the device after the pass that wrote ``Y_{k+1}``, which keeps its momentum: the reset acts on
+        the following step (``beta_0 = 0``, so ``Y_{k+2} = X_{k+2}``), from where the sequence is a fresh FISTA run
 
     A prior other than the stock synthesis L1 (analysis setting, user prior) is applied through its own ``proxf(V)``, whose
     threshold is the prior's (the prox of ``lmda f``): the iteration then minimises ``g + (lmda / gamma) f``, which is not
@@ -88,15 +93,21 @@ class FISTA(PxMCMC):
     ``preds_map`` (device arrays), ``objective_map`` (``[C]``), ``used_graph`` and ``last_steps`` (``[C, 2]``: the lengths
     ``||X_K - X_{K-1}||`` and ``||X_{K-1} - X_{K-2}||`` of the last two steps, which bound the fixed-point residual of the
     returned point: ``||X_K - P(X_K)|| <= ||X_K - X_{K-1}|| + beta ||X_{K-1} - X_{K-2}||`` for the nonexpansive step map P).
+    With ``restart``: also ``restarts`` (``[nchecks, C]``, restarts so far at each check) and ``nrestarts`` (``[C]``).
     """
 
     lipschitz_tol = 1e-4
 
     def __init__(self, forward, prior, mcmcparams=PxMCMCParams(), nchains=1, gamma=None, momentum=True, max_iter=10000,
-                 tol=1e-4, check_every=10, use_graph=True):
+                 tol=1e-4, check_every=10, use_graph=True, restart=None):
         super().__init__(forward, prior, mcmcparams, nchains=nchains, use_graph=use_graph)
         if int(max_iter) < 1 or int(check_every) < 1:
             raise ValueError("FISTA needs max_iter >= 1 and check_every >= 1")
+        if restart not in (None, "gradient"):
+            raise ValueError('FISTA: restart is None or "gradient"')
+        if restart and not momentum:
+            raise ValueError("FISTA: restart needs momentum (forward-backward has none to reset)")
+        self.restart = restart
         self.gradient_op = gradient_operator(forward)
         if not self._stock_prox:
             warnings.warn("FISTA: the prior is not the stock synthesis L1, so its own proxf (the prox of lmda f) is applied: the "
@@ -117,30 +128,47 @@ class FISTA(PxMCMC):
 
     def _engine_start(self, X, preds, i0):
         """static state (XA, XB, P) plus the extrapolated point in YA / YB -- Y of the state in XA lives in YA, of XB in YB --
-        the per-chain sums and the momentum table on the device; the kernel reads beta_k at the engine's device counter"""
+        the per-chain sums and the momentum table on the device; the kernel reads beta_k at the engine's device counter, or,
+        with restart, at the chain's own momentum index, which the step itself advances or resets"""
         self._engine_stop()
         X = ops.as_device(X).contiguous()
         f, gamma, lmda = self.gradient_op, self.gamma, self.lmda
         YA, YB, V = X.clone(), torch.empty_like(X), torch.empty_like(X)
         beta = ops.as_device(self.beta, torch.float64)
         # sums of the step that wrote XA in _sums[0], of the step that wrote XB in _sums[1]: the last two steps' sums
-        self._sums = torch.zeros((2, X.shape[0], 3), dtype=torch.float64, device=X.device)
-        scratch = ops.fista_scratch(X.shape[0], X.device)
+        C, restart = X.shape[0], self.restart is not None
+        self._sums = torch.zeros((2, C, 4 if restart else 3), dtype=torch.float64, device=X.device)
+        scratch = (ops.fista_restart_scratch if restart else ops.fista_scratch)(C, X.device)
         T = self.prior.T_dev if self._stock_prox else None
+        # restart: the chains' momentum indices and restart counts (the library reads them as uint64)
+        self._momentum_index = torch.zeros(C, dtype=torch.int64, device=X.device) if restart else None
+        self._restarts = torch.zeros(C, dtype=torch.int64, device=X.device) if restart else None
 
         def step(eng, src, dst):
             Y, Y_next = (YA, YB) if src is eng["XA"] else (YB, YA)
             g = ops.as_device(f.calc_gradg(ops.as_device(f.forward(Y))), src.dtype)
-            kw = dict(iter_dev=eng["cnt"].t, out=(dst, Y_next), sums=self._sums[0 if dst is eng["XA"] else 1], scratch=scratch)
+            kw = dict(out=(dst, Y_next), sums=self._sums[0 if dst is eng["XA"] else 1], scratch=scratch)
             if self._stock_prox:
-                ops.fista_step(Y, g, src, gamma, lmda, beta, T=T, **kw)
+                kw["T"] = T
             else:
                 ops.skrock_stage(Y, 1.0, c=-gamma, gradg=g, out=V)  # V = Y - gamma gradg
-                ops.fista_step(None, None, src, gamma, lmda, beta, proxf=ops.as_device(self.prior.proxf(V), src.dtype), **kw)
+                kw["proxf"] = ops.as_device(self.prior.proxf(V), src.dtype)
+            if restart:  # Y is passed next to a given proxf too: the restart sum reads it
+                ops.fista_step_restart(Y, g, src, gamma, lmda, beta, self._momentum_index, restarts=self._restarts, **kw)
+            elif self._stock_prox:
+                ops.fista_step(Y, g, src, gamma, lmda, beta, iter_dev=eng["cnt"].t, **kw)
+            else:
+                ops.fista_step(None, None, src, gamma, lmda, beta, iter_dev=eng["cnt"].t, **kw)
             eng["cnt"].add(1)
 
-        return self._engine_start_generic(X, preds, i0, step, lazy=True, graph_ok=self.use_graph,
-                                          reset=lambda eng: (YA.copy_(eng["XA"]), self._sums.zero_()))
+        def reset(eng):
+            YA.copy_(eng["XA"])
+            self._sums.zero_()
+            if restart:
+                self._momentum_index.zero_()
+                self._restarts.zero_()
+
+        return self._engine_start_generic(X, preds, i0, step, lazy=True, graph_ok=self.use_graph, reset=reset)
 
     def run(self, start_point=None):
         """Iterate from ``start_point`` (``[N]``, or ``[C, N]`` with one row per chain; ``None``: zero) until every chain meets
@@ -153,6 +181,7 @@ class FISTA(PxMCMC):
         X, preds = self._initial_sample(start_point)
         self._engine_start(X, preds, 0)
         traces = {k: [] for k in ("objective", "data_term", "prior_term", "rel_change")}
+        restarts = []
         self.checks = []
         niter = np.zeros(C, dtype=int)
         met = np.zeros(C, dtype=bool)
@@ -177,6 +206,8 @@ class FISTA(PxMCMC):
                 self.checks.append(i)
                 for key, v in zip(traces, (data_term + prior_term, data_term, prior_term, rel)):
                     traces[key].append(np.array(v, dtype=float))
+                if self.restart:
+                    restarts.append(self._restarts.cpu().numpy().copy())
                 if met.all():
                     break
             self.X_map, self.preds_map = X.clone(), preds.clone()
@@ -188,6 +219,9 @@ class FISTA(PxMCMC):
         for key, rows in traces.items():
             setattr(self, key, np.stack(rows))
         self.niter, self.converged = niter, met
+        if self.restart:
+            self.restarts = np.stack(restarts)
+            self.nrestarts = self.restarts[-1]
         self.objective_map = self.objective[-1]
         out = self.X_map if C > 1 else self.X_map[0]
         return out.clone() if as_torch else out.cpu().numpy()
