@@ -194,8 +194,23 @@ class PxmError(RuntimeError):
     pass
 
 
-NOISE_F64 = 16  # PXM_NOISE_F64: OR-ed into the mode / noise_complex / dtype argument of the noise-drawing entry points
-STATUS_PAIR_SYNC = 2  # bit of pxm_wav_status / pxm_sht_status (bit 0 is unused)
+# The integer ``#define PXM_<NAME>`` of include/pxmcmc_amd.h: each is mirrored once, here, as the module attribute <NAME>
+# (tests/test_host_and_abi.py compares the block with the header in both directions).
+CONSTANTS = dict(
+    NOISE_F64=16,  # OR-ed into the mode / noise_complex / dtype argument of the noise-drawing entry points
+    STATUS_PAIR_SYNC=2,  # bit of pxm_wav_status / pxm_sht_status (bit 0 is unused)
+    MODE_REAL_NOISE=0,  # `mode` of the fused pxm_wav_*_step: real noise,
+    MODE_CPLX_NOISE=1,  # complex noise,
+    MODE_REAL_PAIRS=2,  # two real chains per complex slot
+    FISTA_SLICES_MAX=256,  # partial sums per chain of pxm_fista_step
+    SAPG_SLICES_MAX=256,  # partial sums per chain of pxm_sapg_step
+    LCI_POINTS=32,  # values of xi per slot and pass of pxm_lci_eval
+    LCI_ROUNDS_MAX=64,  # most passes of pxm_lci_search
+    LCI_EMPTY=1,  # bits of the status of pxm_lci_search (0: ok)
+    LCI_UNCONSTRAINED=2,
+    LCI_NONFINITE=4,
+)
+globals().update(CONSTANTS)
 
 
 def _load():

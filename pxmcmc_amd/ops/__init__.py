@@ -1,0 +1,28 @@
+"""
+Thin tensor-level wrappers over the C-ABI: torch supplies device memory and the stream,
+every operation is a hand-written HIP kernel behind ``include/pxmcmc_amd.h``.
+
+Conventions: arrays are ``[C, n]`` (chain batch first) or ``[n]`` (one chain); dtype is
+float64 or complex128; outputs are fresh tensors (the reference never mutates inputs,
+SURVEY.md section 8b).
+
+One module per concern, as the kernel files are: ``steps`` (elementwise.hip, skrock.hip, fista.hip, sapg.hip), ``reduce``
+(reduce.hip), ``pxmala`` (pxmala.hip), ``summary`` (moments.hip, tails.hip, acov.hip), ``lci`` (lci.hip), ``sparse``
+(spmv.hip), ``plans`` (the plan sources), ``host`` (tables.cpp, host_api.cpp); ``_args`` holds what they do to their arguments
+and the checks they share.  Callers use the names below as ``ops.<name>``.
+"""
+# flake8: noqa: F401  (every import below is a re-export)
+from .._lib import (FISTA_SLICES_MAX, LCI_EMPTY, LCI_NONFINITE, LCI_POINTS, LCI_UNCONSTRAINED, SAPG_SLICES_MAX, PxmError, check,
+                    require_gpu)
+from ._args import _batched, _p, _stream, as_device, device
+from .host import j_max, mw_ring_weights, noise_bits, tiling_axisym, wav_bandlimits
+from .lci import lci_data_terms, lci_eval, lci_scratch, lci_search
+from .plans import (DirWavPlan, HarmWavPlan, IterCounter, ShtPlan, WavPlan, _Plan, capture_scope, live_plans, raise_on_status,
+                    tables_trim)
+from .pxmala import logtransition, pxmala_accept, pxmala_finish, pxmala_propose, pxmala_propose_scratch
+from .reduce import quantile_range, reduce_l1, reduce_l2, reduce_scratch_doubles, reduce_vdot
+from .sparse import CsrMatrix
+from .steps import (box_muller, chain_step, counter_add, fista_restart_scratch, fista_scratch, fista_step, fista_step_restart,
+                    myula_step, randn, residual_grad, sapg_scratch, sapg_step, select_copy_many, skrock_stage, soft)
+from .summary import (acov_ess, acov_stage_depth, acov_update, moments_finalize, moments_update, tails_quantiles,
+                      tails_stage_depth, tails_update)

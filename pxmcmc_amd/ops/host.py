@@ -1,0 +1,37 @@
+"""Host-side set-up helpers: no GPU needed (csrc/tables.cpp, host_api.cpp)."""
+import ctypes as C
+
+import numpy as np
+
+from .._lib import check, lib
+
+
+def j_max(L, B):
+    return int(check(lib.pxm_j_max(int(L), float(B))))
+
+
+def wav_bandlimits(L, B, J_min):
+    buf = (C.c_int * 64)()
+    n = check(lib.pxm_wav_bandlimits(int(L), float(B), int(J_min), buf, 64))
+    return [int(buf[i]) for i in range(n)]
+
+
+def tiling_axisym(L, B, J_min):
+    J = j_max(L, B)
+    k0 = np.zeros(L)
+    k = np.zeros((J + 1, L))
+    check(lib.pxm_tiling_axisym(int(L), float(B), int(J_min), k0.ctypes.data, k.ctypes.data))
+    return k0, k
+
+
+def mw_ring_weights(L):
+    q = np.zeros(L)
+    check(lib.pxm_mw_ring_weights(int(L), q.ctypes.data))
+    return q
+
+
+def noise_bits():
+    """32: the precision of the Box-Muller step of the device noise stream WITHOUT the flag (the samplers of mcmc.py pass
+    the flag by default: ``noise_bits=64``); every noise-drawing call takes
+    ``noise64=True`` for the double-precision evaluation (PXM_NOISE_F64, include/pxmcmc_amd.h)"""
+    return int(lib.pxm_noise_bits())

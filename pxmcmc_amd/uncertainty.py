@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._lib import LCI_EMPTY, LCI_NONFINITE, LCI_POINTS, LCI_UNCONSTRAINED
 from .utils import _multires_bandlimits, mw_size
 
 
@@ -721,8 +722,7 @@ class PosteriorSummary:
 
 
 # ---- local credible intervals from the MAP point ------------------------------------------------------
-LCI_POINTS = 32  # values of xi per pass (PXM_LCI_POINTS)
-LCI_OK, LCI_EMPTY, LCI_UNCONSTRAINED, LCI_NONFINITE = 0, 1, 2, 4  # status of a region: 0, or these bits
+LCI_OK = 0  # status of a region: 0, or the LCI_* bits (these and LCI_POINTS, the values of xi per pass: the header's, from _lib)
 
 
 def lci_shrink_factor(rounds, q2_positive=True):

@@ -240,16 +240,3 @@ def test_numpy_route_against_extended_model():
     print("fp64 numpy route vs extended model, units of 2^-52 S_e:", worst)
     assert max(worst.values()) <= C0_MEASURED
     assert max(worst.values()) >= C0_MEASURED / 4  # the pinned value is the measured one, not a loose cap
-
-
-def test_scratch_size_constant_matches_the_header():
-    """ops sizes the kernel's scratch with its own copy of PXM_FISTA_SLICES_MAX: the two must not drift apart"""
-    import os
-    import re
-
-    from conftest import ROOT
-    from pxmcmc_amd import ops
-
-    header = open(os.path.join(ROOT, "include", "pxmcmc_amd.h")).read()
-    (value,) = re.findall(r"#define\s+PXM_FISTA_SLICES_MAX\s+(\d+)", header)
-    assert int(value) == ops.FISTA_SLICES_MAX

@@ -11,9 +11,6 @@ Per chain, with momentum index k_c (from 0) and restart count R_c:
 
 The decision is known only after the pass that wrote Y1, so Y1 keeps its momentum and the reset acts on the following step,
 which runs with beta_0 = 0."""
-import os
-import re
-
 import numpy as np
 import pytest
 
@@ -131,14 +128,3 @@ def test_decision_is_false_for_zero_and_nan():
     for r in (0.0, -0.0, float("nan"), -1.0):
         assert not (r > 0)
     assert 2.0 ** -1000 > 0
-
-
-def test_entry_point_is_declared_and_listed():
-    from conftest import ROOT
-    from pxmcmc_amd import _lib
-
-    header = open(os.path.join(ROOT, "include", "pxmcmc_amd.h")).read()
-    assert re.search(r"\bint\s+pxm_fista_step_restart\s*\(", header)
-    restype, argtypes = _lib.SIGNATURES["pxm_fista_step_restart"]
-    (decl,) = re.findall(r"\bint\s+pxm_fista_step_restart\s*\(([^;]*)\)\s*;", header)
-    assert len(argtypes) == len(decl.split(","))

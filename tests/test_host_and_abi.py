@@ -16,16 +16,63 @@ def _lib():
     return _lib
 
 
+def _header():
+    return open(os.path.join(ROOT, "include", "pxmcmc_amd.h")).read()
+
+
+_SCALARS = {"int": ctypes.c_int, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+            "unsigned": ctypes.c_uint}
+
+
+def _ctype_of(decl, is_return=False):
+    """ctypes type of one parameter (or return type) of a header declaration"""
+    words = re.findall(r"\w+|\*", decl)
+    if not is_return:
+        words = words[:-1]  # the parameter's name
+    words = [w for w in words if w != "const"]
+    if words[-1] == "*":
+        if is_return:
+            assert words == ["char", "*"], decl
+            return ctypes.c_char_p
+        if re.fullmatch(r"pxm_\w+_plan_t", words[0]):
+            return ctypes.POINTER(ctypes.c_void_p)  # the out-parameter of a plan's create call
+        return ctypes.c_void_p
+    (word,) = words
+    if re.fullmatch(r"pxm_\w+_plan_t|pxm_stream_t", word):
+        return ctypes.c_void_p
+    return _SCALARS[word]
+
+
 def test_library_exports_every_declared_symbol():
+    """every ``ret pxm_name(args);`` of the header has its entry in ``_lib.SIGNATURES`` with the same return and argument
+    types, the table has no other entry, and the library exports each name"""
     L = _lib()
-    header = open(os.path.join(ROOT, "include", "pxmcmc_amd.h")).read()
-    declared = set(re.findall(r"\b(pxm_[a-z0-9_]+)\s*\(", header))
+    header = re.sub(r"/\*.*?\*/|//[^\n]*", " ", _header(), flags=re.S)
+    declared = {}
+    for ret, name, args in re.findall(r"\b((?:const\s+)?\w+\s*\*?)\s*\b(pxm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header):
+        args = [] if args.strip() in ("", "void") else [_ctype_of(a) for a in args.split(",")]
+        assert name not in declared, name
+        declared[name] = (_ctype_of(ret, is_return=True), args)
     assert declared, "no declarations found"
-    assert declared == set(L.SIGNATURES), declared ^ set(L.SIGNATURES)
+    assert set(re.findall(r"\b(pxm_[a-z0-9_]+)\s*\(", header)) == set(declared)  # the pattern misses no declaration
+    assert set(declared) == set(L.SIGNATURES), set(declared) ^ set(L.SIGNATURES)
+    wrong = {name: (sig, L.SIGNATURES[name]) for name, sig in declared.items() if tuple(L.SIGNATURES[name]) != sig}
+    assert not wrong, wrong
     raw = ctypes.CDLL(L.LIB_PATH)
     for name in declared:
         assert hasattr(raw, name), name
     assert L.lib.pxm_version() >= 100
+
+
+def test_header_constants_have_one_mirror_each():
+    """every integer ``#define PXM_<NAME> <n>`` of the header equals ``_lib.CONSTANTS[<NAME>]`` and the module attribute of
+    that name, and the mirror block names nothing else"""
+    L = _lib()
+    defines = {name: int(value) for name, value in re.findall(r"^\s*#\s*define\s+PXM_(\w+)\s+(-?\d+)\s*$", _header(), flags=re.M)}
+    assert len(defines) >= 12
+    assert defines == L.CONSTANTS, set(defines.items()) ^ set(L.CONSTANTS.items())
+    for name, value in defines.items():
+        assert getattr(L, name) == value, name
 
 
 def test_no_gpu_fails_loudly(have_gpu):
@@ -57,8 +104,8 @@ def test_summary_updates_name_themselves_when_they_refuse_the_sample_batch(monke
     from pxmcmc_amd import ops
 
     C, k, m = 2, 3, 6
-    monkeypatch.setattr(ops, "_tails_state", lambda *a: (C, k, m))
-    monkeypatch.setattr(ops, "_acov_state", lambda *a: (C, k, m))
+    monkeypatch.setattr(ops.summary, "_tails_state", lambda *a: (C, k, m))
+    monkeypatch.setattr(ops.summary, "_acov_state", lambda *a: (C, k, m))
     wide = torch.zeros((C, 2 * m + 2), dtype=torch.float64)
     strided, off = wide[:, : 2 * m : 2], wide.reshape(-1)[1 : 1 + C * m].view(C, m)
     assert not strided.is_contiguous() and off.is_contiguous() and off.data_ptr() % 16 == 8
