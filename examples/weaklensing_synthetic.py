@@ -38,7 +38,7 @@ from pxmcmc_amd.sapg import SAPG  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
 from pxmcmc_amd.transforms import SphericalWaveletTransform  # noqa: E402
 from pxmcmc_amd.uncertainty import local_credible_intervals, superpixel_regions  # noqa: E402
-from pxmcmc_amd.utils import build_mask  # noqa: E402
+from pxmcmc_amd.utils import _multires_bandlimits, build_mask  # noqa: E402
 
 BEAM_SIGMA = np.radians(50 / 60)  # 50 arcmin (experiments/weaklensing/main.py:35)
 
@@ -118,11 +118,26 @@ def estimate_mu(forward_operator, prior, params, L_g, args, start_point=None):
     p = copy.copy(params)
     p.delta = float(min(params.delta, 0.8 / (L_g + 1 / params.lmda)))
     sapg = SAPG(forward_operator, prior, p, nchains=args.chains, warmup=args.sapg_warmup, niter=args.sapg_iters,
-                burn=args.sapg_iters // 3, seed=args.seed)
+                burn=args.sapg_iters // 3, seed=args.seed, groups="scale" if args.estimate_mu_per_scale else None)
     theta_hat = sapg.run(start_point=start_point)
-    print(f"SAPG ({args.sapg_warmup} + {args.sapg_iters} iterations at delta = {p.delta:.3e}, graph replay: {sapg.used_graph}): "
-          f"theta_hat = {np.round(theta_hat, 6)}, mu_hat = {np.round(sapg.mu_hat, 6)} (mu given: {params.mu})")
+    if args.estimate_mu_per_scale:
+        print(f"SAPG per scale ({args.sapg_warmup} + {args.sapg_iters} iterations at delta = {p.delta:.3e}, graph replay: "
+              f"{sapg.used_graph}), mu given: {params.mu}")
+        print_theta_per_scale(sapg, forward_operator.transform)
+    else:
+        print(f"SAPG ({args.sapg_warmup} + {args.sapg_iters} iterations at delta = {p.delta:.3e}, graph replay: {sapg.used_graph}): "
+              f"theta_hat = {np.round(theta_hat, 6)}, mu_hat = {np.round(sapg.mu_hat, 6)} (mu given: {params.mu})")
     return sapg.apply(prior, params)
+
+
+def print_theta_per_scale(sapg, transform):
+    """--estimate-mu-per-scale: one line per block [scaling | j = J_min ... J_max] with its bandlimit, its size and the chain
+    mean of theta_hat (what SAPG.apply scales the block's thresholds by)"""
+    bls = _multires_bandlimits(transform.L, transform.B, transform.J_min)
+    names = ["scaling"] + [f"j = {j}" for j in range(transform.J_min, transform.J_max + 1)]
+    hat = np.asarray(sapg.theta_hat).reshape(-1, len(names)).mean(axis=0)
+    for name, bl, size, th in zip(names, bls, np.diff(sapg.group_bounds), hat):
+        print(f"  {name:>8}: bandlimit {int(bl):4d}, {int(size):8d} coefficients, theta_hat = {th:.6g}")
 
 
 def build_sampler(args, forward_operator, prior, params, space):
@@ -187,6 +202,9 @@ def main(argv=None):
                          "(pixel-space posterior only)")
     ap.add_argument("--estimate-mu", action="store_true",
                     help="estimate the regularisation strength by SAPG first and sample with mu_hat = mu * theta_hat")
+    ap.add_argument("--estimate-mu-per-scale", action="store_true",
+                    help="--estimate-mu with one theta per wavelet scale (SAPG groups='scale'): prints theta_hat per scale and "
+                         "samples with every scale's thresholds and weights scaled by its own theta_hat")
     ap.add_argument("--sapg-warmup", type=int, default=100, help="--estimate-mu: MYULA iterations before theta moves")
     ap.add_argument("--sapg-iters", type=int, default=600, help="--estimate-mu: iterations with a moving theta")
     ap.add_argument("--summary", nargs="?", const=True, default=None, choices=("image", "state"),
@@ -200,6 +218,7 @@ def main(argv=None):
     ap.add_argument("--harmonic", action="store_true",
                     help="harmonic-space posterior: WeakLensingHarmonic + harmonic wavelets + L1, started from sks_estimate")
     args = ap.parse_args(argv)
+    args.estimate_mu = args.estimate_mu or args.estimate_mu_per_scale
     if args.summary_alpha is not None and not args.summary:
         ap.error("--summary-alpha needs --summary")
     if args.summary_ess is not None and not args.summary:

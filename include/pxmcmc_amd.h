@@ -413,6 +413,28 @@ int pxm_sapg_step(const void* X, const void* gradg, const double* T, double T_sc
                   const uint64_t* iter_dev, double* theta, double* eta, double d, const double* rho_table, int64_t n_rho,
                   double eta_min, double eta_max, int pool, double* trace, int64_t n_trace, void* X_out, double* scratch,
                   int64_t n, int C, int dtype, pxm_stream_t stream);
+/* pxm_sapg_step with one theta per chain and per group of the state ("One theta per group"): the prior
+ * is sum_k theta_k G_k(X), G_k(X) = (1 / lmda) sum_{b_k <= i < b_k+1} T_i |X_i| on K contiguous, non-empty blocks -- the scales
+ * of a wavelet prior.  bounds: HOST array of the K + 1 offsets 0 = b_0 < b_1 < ... < b_K = n, 1 <= K <= PXM_SAPG_GROUPS_MAX,
+ * read during the call only (the kernels receive them by value).  theta, eta [C][K] float64 on the device, updated in place.
+ *   thr_i = theta[c][k(i)] T_i (rounded), k(i) the group of element i;  X_out as pxm_sapg_step's, the noise keyed by the
+ *   element's index i in the whole state: X_out is pxm_myula_step on T'_i = theta[c][k(i)] T_i;
+ *   G[c][k] = (1 / lmda) sum over group k of T_i |X_out_i|, added in the order pxm_sapg_step adds a state of b_k+1 - b_k
+ *   elements: it depends on the group's length only, not on the batch or the other groups;  pool != 0: every chain takes the
+ *   chain-order mean of the G[c][k], group by group;
+ *   eta[c][k] = min(max(eta[c][k] + rho[j][k] (d[k] - theta[c][k] G[c][k]), eta_min), eta_max), j = min(iter + *iter_dev,
+ *   n_rho - 1);  theta[c][k] = exp(eta[c][k]);
+ *   trace [n_trace][C][K][3] (or NULL with n_trace 0): row iter + *iter_dev, when there is one, receives (theta, eta, G).
+ * d [K] (the dimensions of the groups) and rho_table [n_rho][K]: float64 on the device.  n == 0 is refused: a group cannot be
+ * empty.  With K == 1 the results are pxm_sapg_step's with d = d[0], bit for bit.
+ * scratch: caller-owned, (PXM_SAPG_SLICES_MAX + 1) * K * C doubles.  Aliasing rules as for pxm_sapg_step; no allocation, copy
+ * or host read per call: a HIP graph replays it. */
+#define PXM_SAPG_GROUPS_MAX 32
+int pxm_sapg_step_groups(const void* X, const void* gradg, const double* T, double T_scalar, double delta, double lmda,
+                         const void* noise, int noise_complex, uint64_t seed, uint64_t chain0, uint64_t iter,
+                         const uint64_t* iter_dev, double* theta, double* eta, const int64_t* bounds, int K, const double* d,
+                         const double* rho_table, int64_t n_rho, double eta_min, double eta_max, int pool, double* trace,
+                         int64_t n_trace, void* X_out, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream);
 /* Local credible intervals from the MAP point (Cai, Pereyra & McEwen 2018).  Slot c of a batch is one
  * region of the image; along the surrogate X(xi) = a_c + xi b_c (xi real) the objective of pxm_fista_step's posterior is
  *   F_c(xi) = q0 + q1 xi + q2 xi^2 + (1 / lmda) sum_k T_k |a_ck + xi b_ck|,

@@ -159,6 +159,11 @@ SIGNATURES = {
         [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i64, c_dbl, c_dbl,
          c_int, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_vp],
     ),
+    "pxm_sapg_step_groups": (
+        c_int,
+        [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64,
+         c_dbl, c_dbl, c_int, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_vp],
+    ),
     "pxm_randn": (c_int, [c_vp, c_i64, c_int, c_int, c_u64, c_u64, c_u64, c_vp]),
     "pxm_box_muller": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "pxm_reduce_l1": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
@@ -203,7 +208,8 @@ CONSTANTS = dict(
     MODE_CPLX_NOISE=1,  # complex noise,
     MODE_REAL_PAIRS=2,  # two real chains per complex slot
     FISTA_SLICES_MAX=256,  # partial sums per chain of pxm_fista_step
-    SAPG_SLICES_MAX=256,  # partial sums per chain of pxm_sapg_step
+    SAPG_SLICES_MAX=256,  # partial sums per chain of pxm_sapg_step (per chain and group of pxm_sapg_step_groups)
+    SAPG_GROUPS_MAX=32,  # most groups of pxm_sapg_step_groups
     LCI_POINTS=32,  # values of xi per slot and pass of pxm_lci_eval
     LCI_ROUNDS_MAX=64,  # most passes of pxm_lci_search
     LCI_EMPTY=1,  # bits of the status of pxm_lci_search (0: ok)

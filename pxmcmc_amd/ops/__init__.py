@@ -12,8 +12,8 @@ One module per concern, as the kernel files are: ``steps`` (elementwise.hip, skr
 and the checks they share.  Callers use the names below as ``ops.<name>``.
 """
 # flake8: noqa: F401  (every import below is a re-export)
-from .._lib import (FISTA_SLICES_MAX, LCI_EMPTY, LCI_NONFINITE, LCI_POINTS, LCI_UNCONSTRAINED, SAPG_SLICES_MAX, PxmError, check,
-                    require_gpu)
+from .._lib import (FISTA_SLICES_MAX, LCI_EMPTY, LCI_NONFINITE, LCI_POINTS, LCI_UNCONSTRAINED, SAPG_GROUPS_MAX, SAPG_SLICES_MAX,
+                    PxmError, check, require_gpu)
 from ._args import _batched, _p, _stream, as_device, device
 from .host import j_max, mw_ring_weights, noise_bits, tiling_axisym, wav_bandlimits
 from .lci import lci_data_terms, lci_eval, lci_scratch, lci_search
@@ -23,6 +23,7 @@ from .pxmala import logtransition, pxmala_accept, pxmala_finish, pxmala_propose,
 from .reduce import quantile_range, reduce_l1, reduce_l2, reduce_scratch_doubles, reduce_vdot
 from .sparse import CsrMatrix
 from .steps import (box_muller, chain_step, counter_add, fista_restart_scratch, fista_scratch, fista_step, fista_step_restart,
-                    myula_step, randn, residual_grad, sapg_scratch, sapg_step, select_copy_many, skrock_stage, soft)
+                    myula_step, randn, residual_grad, sapg_group_bounds, sapg_groups_scratch, sapg_scratch, sapg_step,
+                    sapg_step_groups, select_copy_many, skrock_stage, soft)
 from .summary import (acov_ess, acov_stage_depth, acov_update, moments_finalize, moments_update, tails_quantiles,
                       tails_stage_depth, tails_update)

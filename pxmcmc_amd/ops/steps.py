@@ -1,9 +1,10 @@
 """The elementwise steps of the samplers and optimisers (csrc/elementwise.hip, skrock.hip, fista.hip, sapg.hip)."""
 import ctypes as C
 
+import numpy as np
 import torch
 
-from .._lib import FISTA_SLICES_MAX, SAPG_SLICES_MAX, check, lib
+from .._lib import FISTA_SLICES_MAX, SAPG_GROUPS_MAX, SAPG_SLICES_MAX, check, lib
 from ._args import (_CPLX, _REAL, _batched, _chain_vector, _companion, _data_invcov, _delta_args, _dt, _nf, _noise_group, _p,
                     _result, _scratch, _state_out, _stream, _table, _vecT, as_device, device)
 
@@ -203,6 +204,78 @@ def sapg_step(X, gradg, T, delta, lmda, theta, eta, d, rho, eta_min, eta_max, po
             _p(x), _p(g), _p(Tv), Ts, float(delta), float(lmda), *noise_group,
             _p(theta), _p(eta), float(d), _p(rt), rt.numel(), float(eta_min), float(eta_max), int(bool(pool)),
             _p(trace if n_trace else None), n_trace, _p(out), _p(scratch), n, C_, _dt(x), _stream()
+        )
+    )
+    return (out[0] if squeeze else out), theta, eta
+
+
+def sapg_groups_scratch(C_, K, dev):
+    """scratch of :func:`sapg_step_groups` for C_ chains of K groups"""
+    return _scratch(None, (SAPG_SLICES_MAX + 1) * int(K) * int(C_), dev)
+
+
+def sapg_group_bounds(bounds, n, name="sapg_step_groups"):
+    """the offsets ``0 = b_0 < b_1 < ... < b_K = n`` of K contiguous, non-empty groups (any integer sequence), checked by the
+    rule of the C-ABI -> int64 numpy array of K + 1"""
+    try:
+        b = np.asarray(bounds)
+        if b.dtype.kind not in "iu":
+            raise TypeError
+        b = b.astype(np.int64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: bounds must be a sequence of integers") from None
+    if b.ndim != 1 or not 2 <= b.size <= SAPG_GROUPS_MAX + 1:
+        raise ValueError(f"{name}: bounds must hold K + 1 offsets, 1 <= K <= {SAPG_GROUPS_MAX}")
+    if b[0] != 0 or b[-1] != n or np.any(np.diff(b) <= 0):
+        raise ValueError(f"{name}: bounds must increase strictly from 0 to n = {n} (no empty group)")
+    return b
+
+
+def sapg_step_groups(X, gradg, T, delta, lmda, theta, eta, bounds, d, rho, eta_min, eta_max, pool=False, trace=None, noise=None,
+                     noise_complex=False, seed=0, chain0=0, it=0, iter_dev=None, out=None, scratch=None, noise64=False):
+    """:func:`sapg_step` with one theta per chain and per group: the elements ``bounds[k] <= i <
+    bounds[k + 1]`` of chain c are shrunk at ``theta[c, k] T_i``; ``G[c, k] = (1 / lmda) sum T_i |X1_i|`` over the group;
+    ``eta[c, k] = clip(eta[c, k] + rho[j, k] (d[k] - theta[c, k] G[c, k]))``, ``theta = exp(eta)`` (``pool``: the chain mean of
+    ``G[:, k]``, group by group).
+
+    ``bounds``: K + 1 integers increasing strictly from 0 to n.  ``theta``, ``eta``: contiguous float64 ``[C, K]`` device
+    arrays, updated in place.  ``d``: the groups' dimensions, float64 ``[K]`` device vector (or a sequence).  ``rho``: float64
+    ``[n_rho, K]`` device table (or a nested sequence); row ``j = it`` [+ ``*iter_dev``], clamped to the last.  ``trace``:
+    float64 ``[n_trace, C, K, 3]`` device array or None; row j receives ``(theta, eta, G)``.  ``scratch``:
+    :func:`sapg_groups_scratch`.  Returns ``(X1, theta, eta)``."""
+    x, squeeze = _batched(as_device(X))
+    g = _companion(gradg, x, "sapg_step_groups: gradg shape mismatch")
+    if isinstance(delta, torch.Tensor):
+        raise ValueError("sapg_step_groups: delta must be a float (no per-chain step sizes)")
+    C_, n = x.shape
+    b = sapg_group_bounds(bounds, n)
+    K = b.size - 1
+    Tv, Ts = _vecT(T, n, x.device)
+    w, noise_group = _noise_group(noise, x, noise_complex, noise64, seed, chain0, int(it), iter_dev)
+    f64 = lambda t, shape: (isinstance(t, torch.Tensor) and t.dtype == _REAL and tuple(t.shape) == shape  # noqa: E731
+                            and t.is_contiguous() and t.device == x.device)
+    for name, v in (("theta", theta), ("eta", eta)):
+        if not f64(v, (C_, K)):
+            raise ValueError(f"sapg_step_groups: {name} must be a contiguous float64 [C, K] device array")
+    dv = d if isinstance(d, torch.Tensor) else as_device(np.atleast_1d(np.asarray(d, dtype=float)), _REAL)
+    if not f64(dv, (K,)):
+        raise ValueError("sapg_step_groups: d must be a contiguous float64 [K] device vector")
+    rt = rho if isinstance(rho, torch.Tensor) else as_device(np.asarray(rho, dtype=float), _REAL)
+    if rt.dim() != 2 or rt.shape[0] < 1 or not f64(rt, (rt.shape[0], K)):
+        raise ValueError("sapg_step_groups: rho must be a non-empty contiguous float64 [n_rho, K] device table")
+    n_trace = 0
+    if trace is not None:
+        if not (isinstance(trace, torch.Tensor) and trace.dim() == 4 and f64(trace, (trace.shape[0], C_, K, 3))):
+            raise ValueError("sapg_step_groups: trace must be a contiguous float64 [n_trace, C, K, 3] device array")
+        n_trace = trace.shape[0]
+    out = torch.empty_like(x) if out is None else _state_out(out, x)
+    scratch = _scratch(scratch, (SAPG_SLICES_MAX + 1) * K * C_, x.device,
+                       "sapg_step_groups: scratch is too small (sapg_groups_scratch)")
+    check(
+        lib.pxm_sapg_step_groups(
+            _p(x), _p(g), _p(Tv), Ts, float(delta), float(lmda), *noise_group,
+            _p(theta), _p(eta), b.ctypes.data_as(C.c_void_p), K, _p(dv), _p(rt), rt.shape[0], float(eta_min), float(eta_max),
+            int(bool(pool)), _p(trace if n_trace else None), n_trace, _p(out), _p(scratch), n, C_, _dt(x), _stream()
         )
     )
     return (out[0] if squeeze else out), theta, eta

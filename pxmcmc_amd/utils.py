@@ -54,6 +54,19 @@ def _multires_bandlimits(L, B, J_min, dirs=1, spin=0):
     return np.array([int(np.nonzero(r)[0].max()) + 1 for r in rows], dtype=int)
 
 
+def wavelet_scale_bounds(L, B, J_min, dirs=1, spin=0, harmonic=False):
+    """[ext] the offsets of the blocks ``[scaling | j = J_min ... J_max]`` in the coefficient vector of
+    ``SphericalWaveletTransform(L, B, J_min, dirs, spin, harmonic)``: K + 1 integers from 0 to ``ncoefs``.  A block of
+    bandlimit bl_j holds ``mw_size(bl_j)`` samples per plane in pixel space and ``bl_j ** 2`` harmonic coefficients per plane
+    with ``harmonic``; the scaling block is one plane, a wavelet scale ``2 * dirs - 1`` orientation planes in pixel space (the
+    rule of ``S2_Wavelets_L1.map_weights``) and ``dirs`` blocks, one per n, in harmonic space; a spin
+    keeps the spin-0 layout.  The groups of ``SAPG(groups="scale")``."""
+    bls = _multires_bandlimits(L, B, J_min, dirs, spin)
+    planes = [1] + [int(dirs) if harmonic else 2 * int(dirs) - 1] * (len(bls) - 1)
+    sizes = [(int(bl) ** 2 if harmonic else mw_size(int(bl))) * k for bl, k in zip(bls, planes)]
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
 def dir_component(L, N):
     """[ext] the directionality component s_lm [L*L] of s2let's directional wavelets:
     ``nu sqrt(2^-g C(g, (g - m)/2))`` for m = -g, -g + 2, .., g with g = gamma_l the largest integer <= min(N - 1, l) of

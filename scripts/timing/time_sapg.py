@@ -1,9 +1,11 @@
 """SAPG at the configs[2] size (L = 256, B = 2, J_min = 2, 16 chains), beside MYULA in the same run.
 
-  python scripts/timing/time_sapg.py [--out FILE]   pxm_sapg_step (step kernel + update kernel) and pxm_myula_step alone on the
-                                                    same arrays: device time from events around back-to-back calls, the two
+  python scripts/timing/time_sapg.py [--out FILE]   pxm_sapg_step (step kernel + update kernel), pxm_sapg_step_groups with one
+                                                    theta per wavelet scale and pxm_myula_step alone on the same arrays: device
+                                                    time from events around back-to-back calls, the three
                                                     taken in turn over 7 rounds (median, min, max), and the HBM rate on the
-                                                    algorithmic bytes; a replayed SAPG iteration and a replayed MYULA iteration
+                                                    algorithmic bytes; a replayed SAPG iteration without and with
+                                                    groups="scale" and a replayed MYULA iteration
                                                     on the operators' own plans (the generic engine SAPG runs on: the fused
                                                     wavelet step is switched off for the comparison), median of 5
                                                     device-synchronised regions after warm-up
@@ -26,6 +28,7 @@ from pxmcmc_amd.forward import SphericalWaveletTransformOperator  # noqa: E402
 from pxmcmc_amd.mcmc import MYULA, PxMCMCParams  # noqa: E402
 from pxmcmc_amd.prior import S2_Wavelets_L1  # noqa: E402
 from pxmcmc_amd.sapg import SAPG  # noqa: E402
+from pxmcmc_amd.utils import wavelet_scale_bounds  # noqa: E402
 
 L, B, J_MIN, C = 256, 2.0, 2, 16
 COPY_RATE = 6.29e12  # measured float4 copy rate of the MI355X, bytes/s
@@ -85,9 +88,17 @@ def main():
     theta, eta = torch.ones(C, dtype=torch.float64, device=dev), torch.zeros(C, dtype=torch.float64, device=dev)
     rho = ops.as_device(np.zeros(8), torch.float64)
     scratch = ops.sapg_scratch(C, dev)
+    bounds = wavelet_scale_bounds(L, B, J_MIN)
+    K = len(bounds) - 1
+    res["config"]["groups"] = {"K": K, "bounds": bounds.tolist()}
+    theta_g, eta_g = torch.ones((C, K), dtype=torch.float64, device=dev), torch.zeros((C, K), dtype=torch.float64, device=dev)
+    rho_g, d_g = ops.as_device(np.zeros((8, K)), torch.float64), ops.as_device(2.0 * np.diff(bounds), torch.float64)
+    scratch_g = ops.sapg_groups_scratch(C, K, dev)
     calls = {
         "sapg_step": lambda: ops.sapg_step(X, G, T, DELTA, LMDA, theta, eta, float(n), rho, -7.0, 7.0, iter_dev=it, out=out,
                                            scratch=scratch, noise64=True),
+        "sapg_step_groups": lambda: ops.sapg_step_groups(X, G, T, DELTA, LMDA, theta_g, eta_g, bounds, d_g, rho_g, -7.0, 7.0,
+                                                         iter_dev=it, out=out, scratch=scratch_g, noise64=True),
         "myula_step": lambda: ops.myula_step(X, G, T, DELTA, LMDA, iter_dev=it, out=out, noise64=True),
     }
     for fn in calls.values():
@@ -103,18 +114,23 @@ def main():
     res["TBps"] = {k: nbytes / (statistics.median(v) * 1e-6) / 1e12 for k, v in rounds.items()}
     res["fraction_of_copy_rate"] = {k: res["TBps"][k] * 1e12 / COPY_RATE for k in rounds}
     res["sapg_over_myula"] = statistics.median(rounds["sapg_step"]) / statistics.median(rounds["myula_step"])
+    res["groups_over_sapg"] = statistics.median(rounds["sapg_step_groups"]) / statistics.median(rounds["sapg_step"])
 
     # replayed iterations on the generic engine
     p = PxMCMCParams(lmda=LMDA, delta=DELTA, nsamples=1, nburn=0, ngap=1, verbosity=0)
     s = SAPG(op, reg, p, nchains=C, warmup=64, niter=4096, burn=0, seed=1)
     med_s, all_s = iteration_ms(started(s, op))
     s._engine_stop()
+    sg = SAPG(op, reg, p, nchains=C, warmup=64, niter=4096, burn=0, seed=1, groups="scale")
+    med_g, all_g = iteration_ms(started(sg, op))
+    sg._engine_stop()
     m = MYULA(op, reg, p, nchains=C, seed=1)
     m._prepare()
     m._fused_wav = False  # the operators' own plans, as SAPG steps
     med_m, all_m = iteration_ms(started(m, op))
     m._engine_stop()
-    res["iteration_ms"] = {"sapg": med_s, "sapg_regions": all_s, "myula_generic": med_m, "myula_generic_regions": all_m,
+    res["iteration_ms"] = {"sapg": med_s, "sapg_regions": all_s, "sapg_groups": med_g, "sapg_groups_regions": all_g,
+                           "sapg_groups_over_sapg": med_g / med_s, "myula_generic": med_m, "myula_generic_regions": all_m,
                            "sapg_over_myula_generic": med_s / med_m}
     print(json.dumps(res, indent=1), flush=True)
     if a.out:
