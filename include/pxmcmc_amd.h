@@ -103,6 +103,10 @@ int pxm_host_sht_tables(int L, int spin, int m, double* Binv, double* Afwd);
  * double precision on a per-ring scaled state; host emulation, operation for operation): what pyssht.inverse /
  * inverse_adjoint (pxmcmc/measurements.py:225,237) multiply by when a plan takes the recursion path */
 int pxm_host_rec_table(int L, int spin, int m, double* Brec);
+/* the launch geometry the recursion kernels of a plan (L, spin, C chains) would take, PXM_REC_R included: out[4] = {ring
+ * blocks per wavefront R, complex columns per stored order NC, wavefronts per workgroup, LDS bytes of the ring -> el
+ * kernel}; -1 (pxm_last_error) when the size has none and the plan stays on the ring tables.  No GPU needed. */
+int pxm_host_rec_geometry(int L, int spin, int C, int* out);
 /* tables of the exact-length phi-DFT unit for ring length 511 = 7 x 73 (csrc/dft_pfa.h; the phi stage of
  * pys2let.synthesis_wav2px / synthesis_adjoint_px2wav at bandlimit 256, pxmcmc/transforms.py:126,138): idx[(64 + 80) * 8]
  * uint16 gather / scatter offsets, b2[8 * 9 * 2] the spectrum of Rader's filter; for the CPU test against

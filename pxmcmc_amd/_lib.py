@@ -50,6 +50,7 @@ SIGNATURES = {
     "pxm_mw_ring_weights": (c_int, [c_int, c_vp]),
     "pxm_host_sht_tables": (c_int, [c_int, c_int, c_int, c_vp, c_vp]),
     "pxm_host_rec_table": (c_int, [c_int, c_int, c_int, c_vp]),
+    "pxm_host_rec_geometry": (c_int, [c_int, c_int, c_int, c_vp]),
     "pxm_host_pfa511_tables": (c_int, [c_vp, c_vp]),
     "pxm_quantile_range": (c_int, [c_vp, c_i64, c_i64, c_i64, c_dbl, c_vp, c_vp]),
     "pxm_moments_update": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_vp]),

@@ -286,3 +286,21 @@ int pxm_host_rec_table(int L, int spin, int m, double* Brec) {
 }
 
 }  // extern "C"
+namespace pxm {
+bool rec_geometry(int L, int spin, int C, int* R, int* NW, size_t* lds);  // sht_rec.hip
+}
+extern "C" {
+int pxm_host_rec_geometry(int L, int spin, int C, int* out) {
+  PXM_REQUIRE(out, "pxm_host_rec_geometry: null output");
+  PXM_REQUIRE(L >= 1 && C >= 1, "pxm_host_rec_geometry: need L >= 1 and C >= 1");
+  int R = 0, NW = 0;
+  size_t lds = 0;
+  PXM_REQUIRE(pxm::rec_geometry(L, spin, C, &R, &NW, &lds), "pxm_host_rec_geometry: no geometry for this size (rec_geometry)");
+  out[0] = R;
+  out[1] = spin == 0 ? 2 * C : C;
+  out[2] = NW;
+  out[3] = (int)lds;
+  return 0;
+}
+
+}  // extern "C"

@@ -429,6 +429,14 @@ bool rec_geometry(int L, int spin, int C, int* R_out, int* NW_out, size_t* lds_o
   const int n_units_est = spin == 0 ? (L + 1) / 2 : L;
   int R = 4;
   while (R > 1 && (int64_t)n_units_est * ((nb + R - 1) / R) < 2048) R >>= 1;
+  // PXM_REC_R=1|2|4 (read where PXM_REC is, at plan creation): that value is the only candidate, under the same limits,
+  // and any other value has no geometry -- the tests run every (R, NC) instantiation of the kernels at sizes that take seconds
+  const char* e = std::getenv("PXM_REC_R");
+  const bool forced = e && *e;
+  if (forced) {
+    R = std::atoi(e);
+    if (R != 1 && R != 2 && R != 4) return false;
+  }
   for (;; R <<= 1) {
     // waves: runs of up to R consecutive blocks of one hemisphere (block b is northern when its centre ring is)
     int nw = 0;
@@ -446,7 +454,7 @@ bool rec_geometry(int L, int spin, int C, int* R_out, int* NW_out, size_t* lds_o
       *lds_out = lds;
       return true;
     }
-    if (R >= 4) return false;
+    if (R >= 4 || forced) return false;
   }
 }
 

@@ -30,6 +30,15 @@ def mw_ring_weights(L):
     return q
 
 
+def rec_geometry(L, spin, chains):
+    """(R, NC, waves, lds_bytes) of the table-free ring stage (csrc/sht_rec.hip) for a plan of this size, honouring
+    PXM_REC_R, or None where the size has no geometry and the plan keeps its ring tables"""
+    out = (C.c_int * 4)()
+    if lib.pxm_host_rec_geometry(int(L), int(spin), int(chains), out) < 0:
+        return None
+    return tuple(int(v) for v in out)
+
+
 def noise_bits():
     """32: the precision of the Box-Muller step of the device noise stream WITHOUT the flag (the samplers of mcmc.py pass
     the flag by default: ``noise_bits=64``); every noise-drawing call takes
