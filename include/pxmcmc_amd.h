@@ -36,6 +36,7 @@ typedef struct pxm_sht_plan_s* pxm_sht_plan_t;
 typedef struct pxm_wav_plan_s* pxm_wav_plan_t;
 typedef struct pxm_dwav_plan_s* pxm_dwav_plan_t;
 typedef struct pxm_hwav_plan_s* pxm_hwav_plan_t;
+typedef struct pxm_dft_plan_s* pxm_dft_plan_t;
 typedef void* pxm_stream_t; /* hipStream_t */
 
 /* ---- library ------------------------------------------------------------ */
@@ -56,7 +57,8 @@ int pxm_noise_bits(void);
 /* Host-only (no GPU) check that every global address a launch of the plans' GEMM task lists and DFT groups can form
  * -- including the clamped / aliased loads whose values are discarded -- lies inside its buffer.  Builds the plans
  * named by `what` (1: SHT plan (L, spin); 2: wavelet plan (L, B, J_min) + Gram lists; 4: + weak-lensing lists; 8: the
- * wavelet plan of bit 2 at `spin` instead of spin 0, without weak-lensing lists unless spin == 0) in
+ * wavelet plan of bit 2 at `spin` instead of spin 0, without weak-lensing lists unless spin == 0; 16: the phi-DFT plan
+ * (L, max_chains), which has no ranges to count: 0 when it can be created) in
  * dry-run mode and returns the number of address ranges verified, < 0 on a violation (pxm_last_error names the task).
  * The same check runs at every real plan creation.  The dry-run switch is per thread (plans created concurrently on
  * other threads are real); not to be called during a stream capture. */
@@ -112,6 +114,13 @@ int pxm_host_rec_geometry(int L, int spin, int C, int* out);
  * uint16 gather / scatter offsets, b2[8 * 9 * 2] the spectrum of Rader's filter; for the CPU test against
  * scripts/dev/proto_pfa511.py */
 int pxm_host_pfa511_tables(uint16_t* idx, double* b2);
+/* what the phi-DFT stage of a plan at bandlimit L (ring length n = 2L-1) runs on, PXM_DFT_NO_W and PXM_DFT_PFA included:
+ * out[6] = {unit (0 radix-2, 1 pair, 2 quad), length M of the Bluestein transform, chains per workgroup (radix-2: R; quad: 2,
+ * and 1 for a single chain) or rings per workgroup (pair: 8 / r0 with M = 128 r0; 2 for the exact-length body), threads per
+ * workgroup, LDS bytes per workgroup, 1 when n = 511 takes the exact-length body}.  It is the function every plan's creation
+ * calls.  -1 (pxm_last_error names L, M and the bytes) where the unit needs more LDS than a CU has: L >= 1025, which every
+ * plan constructor refuses with the same text.  No GPU needed. */
+int pxm_host_dft_geometry(int L, int* out);
 
 /* ---- spin spherical-harmonic transforms on the MW grid ---------------------- */
 /* replaces pyssht.forward / inverse / inverse_adjoint / forward_adjoint
@@ -132,6 +141,23 @@ int pxm_sht_inverse_adjoint(pxm_sht_plan_t plan, const void* f, void* flm, int C
 int pxm_sht_forward_adjoint(pxm_sht_plan_t plan, const void* flm, void* f, int C, pxm_stream_t stream);
 /* bytes of Legendre/Wigner ring table one transform launch streams (roofline accounting) */
 int64_t pxm_sht_table_bytes(pxm_sht_plan_t plan, int op /*0 inv,1 fwd,2 inv_adj,3 fwd_adj*/);
+
+/* ---- the phi-DFT stage on its own ---------------------------------------------------------------------------------
+ * The stage of every transform above between the image and the rings (the FFTs over phi inside pyssht.forward / inverse,
+ * pxmcmc/measurements.py:223,225), as a plan without ring tables, task lists or workspace: the same unit selection
+ * (pxm_host_dft_geometry; PXM_DFT_NO_W and PXM_DFT_PFA are read at creation) and the same launches as an SHT plan at L.
+ *   f : [C][L][2L-1] c128, the image of a chain
+ *   G : [2L-1][Rp][Cp] c128, caller-owned, 16-byte aligned: order m = -(L-1) .. L-1, ring t, chain c, with
+ *       Rp = roundup(L, 16) rows and Cp = roundup(max_chains, 8) columns (the internal ring layout, not repacked)
+ *   pxm_dft_px2ring  G[m][t][c] = sum_p f[c][t][p] exp(-i m phi_p), phi_p = 2 pi p / (2L-1); for t < L every column is written:
+ *                    c >= C with zeros; rows t >= L are left as they are
+ *   pxm_dft_ring2px  f[c][t][p] = sum_m G[m][t][c] exp(+i m phi_p); rows t >= L and columns c >= C of G never enter a result
+ * pxm_dft_status reads the plan's status word as pxm_sht_status does. */
+int pxm_dft_plan_create(int L, int max_chains, pxm_dft_plan_t* plan);
+int pxm_dft_plan_destroy(pxm_dft_plan_t plan);
+int pxm_dft_px2ring(pxm_dft_plan_t plan, const void* f, void* G, int C, pxm_stream_t stream);
+int pxm_dft_ring2px(pxm_dft_plan_t plan, const void* G, void* f, int C, pxm_stream_t stream);
+int pxm_dft_status(pxm_dft_plan_t plan, int clear, pxm_stream_t stream);
 
 /* ---- scale-discretised wavelet transform (N=1, upsample=0) -------------------- */
 /* replaces pys2let.synthesis_wav2px / synthesis_adjoint_px2wav / analysis_px2wav /

@@ -52,6 +52,7 @@ SIGNATURES = {
     "pxm_host_rec_table": (c_int, [c_int, c_int, c_int, c_vp]),
     "pxm_host_rec_geometry": (c_int, [c_int, c_int, c_int, c_vp]),
     "pxm_host_pfa511_tables": (c_int, [c_vp, c_vp]),
+    "pxm_host_dft_geometry": (c_int, [c_int, c_vp]),
     "pxm_quantile_range": (c_int, [c_vp, c_i64, c_i64, c_i64, c_dbl, c_vp, c_vp]),
     "pxm_moments_update": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_vp]),
     "pxm_moments_scratch_doubles": (c_i64, [c_i64]),
@@ -75,6 +76,11 @@ SIGNATURES = {
     "pxm_sht_inverse_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
     "pxm_sht_forward_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
     "pxm_sht_table_bytes": (c_i64, [c_vp, c_int]),
+    "pxm_dft_plan_create": (c_int, [c_int, c_int, C.POINTER(c_vp)]),
+    "pxm_dft_plan_destroy": (c_int, [c_vp]),
+    "pxm_dft_px2ring": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_dft_ring2px": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_dft_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_dwav_plan_create": (c_int, [c_int, c_dbl, c_int, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),
     "pxm_dwav_plan_destroy": (c_int, [c_vp]),
     "pxm_dwav_synthesis": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),

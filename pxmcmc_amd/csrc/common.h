@@ -108,7 +108,8 @@ struct BluesteinTables {
   std::vector<double> bhat;   // [M][2]   FFT_M(conj chirp filter) / M, bit-reversed order
   std::vector<double> tw;     // [M/2][2] exp(-2 pi i k / M)
 };
-BluesteinTables make_bluestein(int n, int M_force = 0);  // M_force: a power of two >= 2n-1, 0 = smallest
+int bluestein_size(int n);  // the smallest power of two >= max(16, 2n-1): the transform length of the radix-2 unit
+BluesteinTables make_bluestein(int n, int M_force = 0);  // M_force: a power of two >= 2n-1, 0 = bluestein_size(n)
 // the table math all three Bluestein units of the phi-DFT stage share, in long double: the chirp c_j, j < n, and
 // FFT_M(h) / M of the chirp filter h_j = conj(c_|j|) (j mod M), in bit-reversed or natural order
 void bluestein_chirp_spectrum(int n, int M, bool natural, std::vector<std::complex<long double>>& chirp,

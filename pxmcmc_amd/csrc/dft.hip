@@ -135,34 +135,59 @@ __global__ void k_ring2px(DftArgs a, const double* __restrict__ G, int ncol, PxO
   }
 }
 
-int make_dft_plan(int L, DftPlan* p) {
-  p->L = L;
-  p->n = 2 * L - 1;
-  p->Rp = round_up(L, 16);
+int dft_geometry(int L, DftGeometry* g) {
+  PXM_REQUIRE(L >= 1 && L <= (1 << 28), "dft_geometry: need 1 <= L <= 2^28");
+  const int n = 2 * L - 1;
   // PXM_DFT_NO_W=1: the radix-2 unit for every size; PXM_DFT_PFA=0: the pair unit's Bluestein body for n = 511 as well
   const bool radix2_only = getenv("PXM_DFT_NO_W") != nullptr;
   const char* pfa_env = getenv("PXM_DFT_PFA");
-  const bool pfa = !(pfa_env && atoi(pfa_env) == 0);
-  if (!radix2_only && pair_r0(p->n)) {
-    p->unit = DFT_PAIR;
+  *g = DftGeometry();
+  g->pfa = !(pfa_env && atoi(pfa_env) == 0);
+  if (!radix2_only && pair_r0(n)) {
+    g->unit = DFT_PAIR;
+    g->M = 128 * pair_r0(n);
+    pair_workgroup(n, g->pfa, &g->per_wg, &g->threads, &g->lds, &g->exact);
+  } else if (!radix2_only && n <= 1023) {
+    g->unit = DFT_QUAD;
+    g->M = 2048;
+    quad_workgroup(&g->per_wg, &g->threads, &g->lds);
+  } else {
+    g->unit = DFT_RADIX2;
+    g->M = bluestein_size(n);
+    // chains per workgroup: as many as fit in ~128 KB of LDS, at most 8 (128-B ring-layout segments)
+    int R = 8;
+    while (R > 1 && (size_t)R * g->M * 16 > 128 * 1024) R >>= 1;
+    g->per_wg = R;
+    g->lds = ((size_t)R * g->M + g->M / 2) * 16;
+    const int64_t th = (int64_t)R * g->M / 2;
+    g->threads = th < 64 ? 64 : (th > 1024 ? 1024 : (int)th);
+  }
+  // (one chain of M = 8192 points and its twiddles: no smaller R to fall back to)
+  PXM_REQUIRE(g->lds <= DFT_LDS_MAX, "phi-DFT stage: no unit for bandlimit L = " + std::to_string(L) + ": the radix-2 unit at M = " +
+                                         std::to_string(g->M) + " needs " + std::to_string(g->lds) + " B of LDS per workgroup, a CU has " +
+                                         std::to_string(DFT_LDS_MAX) + " (the largest bandlimit is L = 1024)");
+  return 0;
+}
+
+int make_dft_plan(int L, DftPlan* p) {
+  DftGeometry g;
+  if (int rc = dft_geometry(L, &g)) return rc;
+  p->L = L;
+  p->n = 2 * L - 1;
+  p->Rp = round_up(L, 16);
+  p->unit = g.unit;
+  if (g.unit == DFT_PAIR) {
     if (const char* e = getenv("PXM_DEBUG_PAIR_SYNC_LIMIT")) p->spin_limit = (unsigned)std::max(0, atoi(e));
-    return pair_make_tables(p->n, pfa, &p->pair);
+    return pair_make_tables(p->n, g.pfa, &p->pair);
   }
-  if (!radix2_only && p->n <= 1023) {
-    p->unit = DFT_QUAD;
-    return quad_make_tables(p->n, &p->quad);
-  }
-  p->unit = DFT_RADIX2;
-  BluesteinTables b = make_bluestein(p->n);
+  if (g.unit == DFT_QUAD) return quad_make_tables(p->n, &p->quad);
+  BluesteinTables b = make_bluestein(p->n, g.M);
+  PXM_REQUIRE(b.M == g.M, "make_dft_plan: the Bluestein tables disagree with dft_geometry");
   p->M = b.M;
   p->logM = b.logM;
-  // chains per workgroup: as many as fit in ~128 KB of LDS, at most 8 (128-B ring-layout segments)
-  int R = 8;
-  while (R > 1 && (size_t)R * b.M * 16 > 128 * 1024) R >>= 1;
-  p->R = R;
-  p->lds = ((size_t)R * b.M + b.M / 2) * 16;
-  int th = R * b.M / 2;
-  p->threads = th < 64 ? 64 : (th > 1024 ? 1024 : th);
+  p->R = g.per_wg;
+  p->lds = g.lds;
+  p->threads = g.threads;
   int rc;
   if ((rc = dev_table(&p->d_chirp, b.chirp, "Bluestein chirp"))) return rc;
   if ((rc = dev_table(&p->d_bhat, b.bhat, "Bluestein filter spectrum"))) return rc;

@@ -1,0 +1,81 @@
+// The phi-DFT stage as a plan of its own (one DftPlan and a status word: no ring tables, no task lists, no workspace) and
+// the host report of the unit selection.  The entry points run the launches an SHT plan at the same bandlimit runs, on
+// the caller's ring array.
+#include "plan_common.h"
+
+#include <memory>
+
+using namespace pxm;
+
+struct pxm_dft_plan_s {
+  int L = 0, Cmax = 0, Cp = 0, ncol = 0, Rp = 0;
+  DftPlan dft;
+  unsigned* d_status = nullptr;  // device status word of this plan (pxm_dft_status)
+};
+
+extern "C" {
+
+int pxm_host_dft_geometry(int L, int* out) {
+  PXM_REQUIRE(out, "pxm_host_dft_geometry: null output");
+  PXM_REQUIRE(L >= 1, "pxm_host_dft_geometry: need L >= 1");
+  DftGeometry g;
+  if (int rc = dft_geometry(L, &g)) return rc;
+  out[0] = g.unit == DFT_RADIX2 ? 0 : (g.unit == DFT_PAIR ? 1 : 2);
+  out[1] = g.M;
+  out[2] = g.per_wg;
+  out[3] = g.threads;
+  out[4] = (int)g.lds;
+  out[5] = g.exact ? 1 : 0;
+  return 0;
+}
+
+int pxm_dft_plan_create(int L, int max_chains, pxm_dft_plan_t* plan) {
+  PXM_REQUIRE(plan, "pxm_dft_plan_create: null plan pointer");
+  PXM_REQUIRE(L >= 1, "pxm_dft_plan_create: Bandlimit must be greater than 0");
+  PXM_REQUIRE(max_chains >= 1, "pxm_dft_plan_create: max_chains must be >= 1");
+  PXM_REQUIRE(dry_run() || pxm_device_count() > 0, "pxm_dft_plan_create: no HIP device visible (the HIP path is the only path)");
+  drain_deferred();
+  std::unique_ptr<pxm_dft_plan_s, int (*)(pxm_dft_plan_t)> guard(new pxm_dft_plan_s(), pxm_dft_plan_destroy);
+  pxm_dft_plan_s* p = guard.get();
+  p->L = L;
+  p->Cmax = max_chains;
+  p->Cp = round_up(max_chains, 8);
+  p->ncol = 2 * p->Cp;
+  p->Rp = round_up(L, 16);
+  int rc;
+  if ((rc = make_dft_plan(L, &p->dft))) return rc;
+  if ((rc = status_alloc(&p->d_status))) return rc;
+  p->dft.d_status = p->d_status;
+  *plan = guard.release();
+  return 0;
+}
+
+int pxm_dft_plan_destroy(pxm_dft_plan_t p) {
+  if (!p) return 0;
+  free_dft_plan(&p->dft);
+  deferred_free(p->d_status);
+  delete p;
+  drain_deferred();  // (a no-op while a stream capture is in progress: freed at the next safe point)
+  return 0;
+}
+
+int pxm_dft_px2ring(pxm_dft_plan_t p, const void* f, void* G, int C, pxm_stream_t s) {
+  if (int rc = plan_check(p, f, G, C, "pxm_dft_px2ring")) return rc;
+  PXM_REQUIRE(((uintptr_t)G & 15) == 0, "pxm_dft_px2ring: the ring array must be 16-byte aligned");
+  note_stream((hipStream_t)s);
+  return launch_px2ring(p->dft, image_in(p->L, f), (double*)G, p->ncol, C, (hipStream_t)s);
+}
+
+int pxm_dft_ring2px(pxm_dft_plan_t p, const void* G, void* f, int C, pxm_stream_t s) {
+  if (int rc = plan_check(p, G, f, C, "pxm_dft_ring2px")) return rc;
+  PXM_REQUIRE(((uintptr_t)G & 15) == 0, "pxm_dft_ring2px: the ring array must be 16-byte aligned");
+  note_stream((hipStream_t)s);
+  return launch_ring2px(p->dft, (const double*)G, p->ncol, image_out(p->L, f), C, (hipStream_t)s);
+}
+
+int pxm_dft_status(pxm_dft_plan_t p, int clear, pxm_stream_t stream) {
+  PXM_REQUIRE(p, "pxm_dft_status: null plan");
+  return status_read(p->d_status, (hipStream_t)stream, clear);
+}
+
+}  // extern "C"

@@ -902,6 +902,13 @@ static_assert((size_t)512 * D5_RMAX * 16 <= (size_t)2 * D5_RMAX * D5_PLANE * 16,
 // slots) + the filter spectrum, the fp64 Box-Muller tables and the group counters: 81 056 B
 static_assert(((size_t)8 * PFA_PLANE + 72 + NOISE_LOG_N + 256 + 1) * 16 <= D5_LDS, "PFA workgroup LDS");
 
+void pair_workgroup(int n, bool pfa, int* rings, int* threads, size_t* lds, bool* exact) {
+  *exact = n == PFA_N && pfa;
+  *rings = *exact ? 2 : 8 / pair_r0(n);  // (pair_ring_blocks on ring arrays of whole lines)
+  *threads = 128 * D5_RMAX;
+  *lds = D5_LDS;
+}
+
 static Dft5Args pair_args(const DftPlan& p) {
   const PairTables& t = p.pair;
   auto c = [](const double* x) { return reinterpret_cast<const double2*>(x); };
@@ -1170,6 +1177,11 @@ static int quad_attr() {
                                   reinterpret_cast<const void*>(k_ring2px6<false, 1>), reinterpret_cast<const void*>(k_ring2px6<true, 1>)});
 }
 static int quad_chains_per_wg(int C) { return C == 1 ? 1 : 2; }
+void quad_workgroup(int* chains, int* threads, size_t* lds) {
+  *chains = quad_chains_per_wg(2);
+  *threads = 256 * *chains;
+  *lds = quad_lds(*chains);
+}
 int quad_px2ring(const DftPlan& p, const PxIn& in, double* G, int ncol, int C, hipStream_t st) {
   if (int rc = quad_attr()) return rc;
   const int R = quad_chains_per_wg(C);

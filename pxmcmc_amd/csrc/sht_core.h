@@ -133,8 +133,8 @@ int check_gemm_task_ranges(const std::vector<GemmTask>& v, int nslab, int pk, in
 //   DFT_PAIR   n <= 511: eight points per lane, a pair of waves per ring set (dft_wave.hip); n = 511 on eight-slot lines
 //              runs the exact-length body (dft_pfa.h) unless PXM_DFT_PFA=0
 //   DFT_QUAD   511 < n <= 1023: four waves per ring, eight points per lane (dft_wave.hip)
-//   DFT_RADIX2 every larger n, and every n with PXM_DFT_NO_W=1: the radix-2 in-LDS unit (dft.hip; an independent
-//              implementation, the cross-check of the other two)
+//   DFT_RADIX2 1023 < n <= 2047, and every n <= 2047 with PXM_DFT_NO_W=1: the radix-2 in-LDS unit (dft.hip; an independent
+//              implementation, the cross-check of the other two).  Longer rings (L >= 1025) have no unit: dft_geometry
 enum DftUnit { DFT_RADIX2, DFT_PAIR, DFT_QUAD };
 
 // device tables of the pair unit: one allocation, typed views into it
@@ -167,6 +167,22 @@ struct DftPlan {
 };
 // bit of a plan's status word (pxm_wav_status / pxm_sht_status); bit 0 is unused
 enum { PXM_STATUS_PAIR_SYNC_BIT = 2 };
+
+// What a plan at bandlimit L runs its rings on: the one selection rule, read by make_dft_plan and reported by
+// pxm_host_dft_geometry.  Honours PXM_DFT_NO_W and PXM_DFT_PFA.
+struct DftGeometry {
+  DftUnit unit = DFT_RADIX2;
+  int M = 0;        // length of the Bluestein transform (the exact-length body runs beside the M = 1024 tables of n = 511)
+  int per_wg = 0;   // radix-2, quad: chains per workgroup (R; the quad unit takes 1 for a single chain); pair: rings per ring
+                    // set, 8 / r0 (a ring pair for the exact-length body)
+  int threads = 0;  // threads per workgroup
+  size_t lds = 0;   // dynamic LDS per workgroup, bytes
+  bool exact = false;  // n = 511 runs the exact-length body (dft_pfa.h)
+  bool pfa = true;     // PXM_DFT_PFA is not 0
+};
+constexpr size_t DFT_LDS_MAX = 160 * 1024;  // what allow_dynamic_lds permits: the LDS of a CU
+// < 0 with the error text (L, M and the byte count) where the selected geometry needs more than DFT_LDS_MAX: L >= 1025
+int dft_geometry(int L, DftGeometry* g);
 
 int make_dft_plan(int L, DftPlan* p);
 void free_dft_plan(DftPlan* p);

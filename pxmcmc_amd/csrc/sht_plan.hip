@@ -36,6 +36,10 @@ int pxm_sht_plan_create(int L, int spin, int max_chains, unsigned flags, pxm_sht
   p->Cp = round_up(max_chains, 8);
   p->ncol = 2 * p->Cp;
   p->Rp = round_up(L, 16);
+  {  // a bandlimit the phi-DFT stage has no unit for is refused before the ring tables are built
+    DftGeometry g;
+    if (int rc = dft_geometry(L, &g)) return rc;
+  }
   int rc = get_tables(L, spin, 0xF, &p->T);
   if (rc) { p->T = nullptr; return rc; }
   retain_tables(p->T);

@@ -309,11 +309,16 @@ void bluestein_chirp_spectrum(int n, int M, bool natural, std::vector<std::compl
   }
 }
 
+int bluestein_size(int n) {
+  int M = 16;
+  while (M < 2 * (int64_t)n - 1) M <<= 1;
+  return M;
+}
+
 BluesteinTables make_bluestein(int n, int M_force) {
   BluesteinTables b;
   b.n = n;
-  int M = 16;
-  while (M < 2 * n - 1) M <<= 1;
+  int M = bluestein_size(n);
   if (M_force > M) M = M_force;
   b.M = M;
   b.logM = 0;

@@ -124,6 +124,10 @@ static int wav_plan_create_impl(const char* who, int L, double B, int J_min, int
   }
   p->ncoefs = off;
   int rc;
+  {  // a bandlimit the phi-DFT stage has no unit for is refused before any table is built (no scale has longer rings)
+    DftGeometry g;
+    if ((rc = dft_geometry(L, &g))) return rc;
+  }
   if ((rc = status_alloc(&p->d_status))) return rc;
   // tables: every scale needs the forward pair (synthesis: FWD, its adjoint: FWD_ADJ) and, for the
   // analysis setting, the inverse pair at its own bandlimit (spin 0); L needs all four, at the plan's spin.
@@ -407,6 +411,11 @@ int64_t pxm_host_check_address_ranges(int L, double B, int J_min, int spin, int 
     if (!rc) rc = wav_make_gram_lists(wp);
     if (!rc && (what & 4) && L >= 3 && wspin == 0) rc = pxm_wav_wl_attach(wp, nullptr, nullptr, (int64_t)L * (2 * L - 1));
     if (wp) pxm_wav_plan_destroy(wp);
+  }
+  if (!rc && (what & 16)) {
+    pxm_dft_plan_t dp = nullptr;
+    rc = pxm_dft_plan_create(L, max_chains, &dp);
+    if (dp) pxm_dft_plan_destroy(dp);
   }
   tables_trim();  // the dry-run table entries (fake addresses) never outlive the call
   set_dry_run(false);

@@ -39,6 +39,19 @@ def rec_geometry(L, spin, chains):
     return tuple(int(v) for v in out)
 
 
+DFT_UNITS = ("radix2", "pair", "quad")  # out[0] of pxm_host_dft_geometry
+
+
+def dft_geometry(L):
+    """(unit, M, per_workgroup, threads, lds_bytes, exact) of the phi-DFT stage (csrc/dft.hip: dft_geometry) of a plan at
+    bandlimit L, honouring PXM_DFT_NO_W and PXM_DFT_PFA: ``unit`` one of DFT_UNITS, ``per_workgroup`` chains (radix2, quad)
+    or rings (pair) per workgroup, ``exact`` whether the 511-point rings take the exact-length body.  Raises PxmError
+    where the stage has no unit for the size (L >= 1025), in the words every plan constructor refuses it with."""
+    out = (C.c_int * 6)()
+    check(lib.pxm_host_dft_geometry(int(L), out))
+    return (DFT_UNITS[out[0]], int(out[1]), int(out[2]), int(out[3]), int(out[4]), bool(out[5]))
+
+
 def noise_bits():
     """32: the precision of the Box-Muller step of the device noise stream WITHOUT the flag (the samplers of mcmc.py pass
     the flag by default: ``noise_bits=64``); every noise-drawing call takes

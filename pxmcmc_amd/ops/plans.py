@@ -1,6 +1,6 @@
-"""The transform plans -- spherical-harmonic, axisymmetric, directional and harmonic-space wavelets -- with the fused sampler
-steps of the wavelet plan, the live-plan registry, the device iteration counter and the capture scope (csrc/sht_plan.hip,
-wav_plan.hip, wav_ops.hip, wav_wl.hip, dirwav.hip, harmwav.hip)."""
+"""The transform plans -- spherical-harmonic, the phi-DFT stage alone, axisymmetric, directional and harmonic-space wavelets --
+with the fused sampler steps of the wavelet plan, the live-plan registry, the device iteration counter and the capture scope
+(csrc/sht_plan.hip, dft_plan.hip, wav_plan.hip, wav_ops.hip, wav_wl.hip, dirwav.hip, harmwav.hip)."""
 import ctypes as C
 import threading
 import weakref
@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .._lib import STATUS_PAIR_SYNC, PxmError, check, lib, require_gpu
-from ._args import (_CPLX, _REAL, _batched, _data_invcov, _nf, _noise_args, _p, _pair_noise_args, _result, _stream, _vecT, as_device,
+from ._args import (_CPLX, _REAL, _batched, _data_invcov, _dev_tensors, _nf, _noise_args, _p, _pair_noise_args, _result, _stream, _vecT, as_device,
                     device)
 
 
@@ -107,6 +107,67 @@ class ShtPlan(_Plan):
         """0, or 16 * ring blocks per wavefront + complex columns per order when inverse / inverse_adjoint take the
         table-free recursion kernels (csrc/sht_rec.hip) instead of the ring-table GEMM"""
         return int(check(lib.pxm_sht_uses_recursion(self._h)))
+
+
+class DftPlan(_Plan):
+    """The phi-DFT stage of the transforms on its own (include/pxmcmc_amd.h, pxm_dft_*): the rings <-> pixels launches of
+    an SHT plan at bandlimit L without its ring tables.  Images are [C, L, 2L-1]; ``rings`` / ``pixels`` speak [C, L, 2L-1]
+    (chain, ring t, order m = -(L-1) .. L-1) and permute with torch; ``rings_raw`` / ``pixels_raw`` work on the internal
+    ring array [2L-1, Rp, Cp] (``ring_array``), padding rows and columns included."""
+
+    def __init__(self, L, max_chains=1):
+        require_gpu()
+        self.L, self.max_chains = int(L), int(max_chains)
+        self.n = 2 * self.L - 1
+        self.Rp, self.Cp = -(-self.L // 16) * 16, -(-self.max_chains // 8) * 8
+        super().__init__(lib.pxm_dft_plan_create, (self.L, self.max_chains), lib.pxm_dft_plan_destroy, lib.pxm_dft_status,
+                         f"DftPlan(L={self.L})")
+
+    def ring_array(self):
+        """a zeroed ring array in the internal layout [2L-1, Rp, Cp]"""
+        return torch.zeros((self.n, self.Rp, self.Cp), dtype=_CPLX, device=device())
+
+    def _image(self, f, who):
+        f = as_device(f, _CPLX)
+        if f.dim() != 3 or tuple(f.shape[1:]) != (self.L, self.n):
+            raise ValueError(f"{who}: the image must be [C, {self.L}, {self.n}]")
+        if f.shape[0] > self.max_chains:
+            raise ValueError("more chains than the plan was created for")
+        return f
+
+    def _ring_array(self, G, who):
+        _dev_tensors(who, f"G must be a contiguous complex128 [{self.n}, {self.Rp}, {self.Cp}] device tensor",
+                     (G, _CPLX, (self.n, self.Rp, self.Cp)))
+        return G
+
+    def rings_raw(self, f, G):
+        """G[m + L - 1, t, c] = sum_p f[c, t, p] exp(-i m phi_p) for t < L, in place: columns c >= C are zeroed, rows
+        t >= L are left as they are; returns G"""
+        f, G = self._image(f, "rings_raw"), self._ring_array(G, "rings_raw")
+        check(lib.pxm_dft_px2ring(self._h, _p(f), _p(G), f.shape[0], _stream()))
+        return G
+
+    def pixels_raw(self, G, C_, out=None):
+        """f[c, t, p] = sum_m G[m + L - 1, t, c] exp(+i m phi_p) for the chains c < C_ -> [C_, L, 2L-1]"""
+        G = self._ring_array(G, "pixels_raw")
+        if not 1 <= int(C_) <= self.max_chains:
+            raise ValueError("more chains than the plan was created for")
+        out = _result(out, (int(C_), self.L, self.n), _CPLX, G.device, "out= buffer has the wrong shape / dtype / layout")
+        check(lib.pxm_dft_ring2px(self._h, _p(G), _p(out), int(C_), _stream()))
+        return out
+
+    def rings(self, f):
+        """[C, L, 2L-1] image -> [C, L, 2L-1] rings (chain, ring, order)"""
+        f = self._image(f, "rings")
+        G = self.rings_raw(f, self.ring_array())
+        return G[:, :self.L, :f.shape[0]].permute(2, 1, 0).contiguous()
+
+    def pixels(self, G):
+        """[C, L, 2L-1] rings (chain, ring, order) -> [C, L, 2L-1] image"""
+        g = self._image(G, "pixels")  # (the same shape)
+        raw = self.ring_array()
+        raw[:, :self.L, :g.shape[0]] = g.permute(2, 1, 0)
+        return self.pixels_raw(raw, g.shape[0])
 
 
 def _update_out(out, x):

@@ -17,7 +17,8 @@ def g():
     import scipy.sparse as sp
     import torch
 
-    from pxmcmc_amd import ops
+    from pxmcmc_amd import _lib, ops
+    from pxmcmc_amd.ops import _p
 
     dev = ops.device()
     g = SimpleNamespace(ops=ops, torch=torch, dev=dev)
@@ -43,6 +44,9 @@ def g():
     g.wav = ops.WavPlan(16, 2, 2, max_chains=C)
     g.wav.wl_attach(None, None, g.wav.npix)
     g.hwav = ops.HarmWavPlan(16, 2, 2, max_chains=C)
+    g.dft = ops.DftPlan(8, max_chains=C)  # images [c, 8, 15], ring array [15, 16, 8]
+    g.G = g.dft.ring_array()
+    g.dft_abi = lambda name, a, b, n: ops.check(getattr(_lib.lib, name)(g.dft._h, _p(a), _p(b), n, None))
     g.X = g.c(C, g.wav.ncoefs)
     g.img, g.w_img = g.c(g.wav.npix), g.r(g.wav.npix)
     g.XH = g.c(C, g.hwav.ncoefs)
@@ -231,6 +235,29 @@ ROWS = [
     ("plan-length", lambda g: g.sht.inverse(g.c(5)), A, r"^expected length 64, got 5"),
     ("plan-chains", lambda g: g.sht.inverse(g.c(C + 1, 64)), V, r"^more chains than the plan was created for"),
     ("plan-out", lambda g: g.wav.synthesis(g.X, out=g.c(C, 3)), V, r"^out= buffer has the wrong shape / dtype / layout"),
+    ("dft-image-shape", lambda g: g.dft.rings(g.c(C, 8, 16)), V, r"^rings: the image must be \[C, 8, 15\]"),
+    ("dft-image-flat", lambda g: g.dft.rings_raw(g.c(C, 8 * 15), g.G), V, r"^rings_raw: the image must be \[C, 8, 15\]"),
+    ("dft-rings-shape", lambda g: g.dft.pixels(g.c(C, 9, 15)), V, r"^pixels: the image must be \[C, 8, 15\]"),
+    ("dft-image-chains", lambda g: g.dft.rings(g.c(C + 1, 8, 15)), V, r"^more chains than the plan was created for"),
+    ("dft-pixels_raw-chains", lambda g: g.dft.pixels_raw(g.G, C + 1), V, r"^more chains than the plan was created for"),
+    ("dft-pixels_raw-no-chain", lambda g: g.dft.pixels_raw(g.G, 0), V, r"^more chains than the plan was created for"),
+    ("dft-G-none", lambda g: g.dft.rings_raw(g.c(C, 8, 15), None), T_,
+     r"^rings_raw: G must be a contiguous complex128 \[15, 16, 8\] device tensor"),
+    ("dft-G-dtype", lambda g: g.dft.rings_raw(g.c(C, 8, 15), g.r(15, 16, 8)), T_,
+     r"^rings_raw: G must be a contiguous complex128 \[15, 16, 8\] device tensor"),
+    ("dft-G-shape", lambda g: g.dft.pixels_raw(g.c(15, 8, 8), C), T_,
+     r"^pixels_raw: G must be a contiguous complex128 \[15, 16, 8\] device tensor"),
+    ("dft-G-strided", lambda g: g.dft.pixels_raw(g.c(15, 16, 16)[:, :, ::2], C), T_,
+     r"^pixels_raw: G must be a contiguous complex128 \[15, 16, 8\] device tensor"),
+    ("dft-G-host", lambda g: g.dft.rings_raw(g.c(C, 8, 15), g.G.cpu()), T_,
+     r"^rings_raw: G must be a contiguous complex128 \[15, 16, 8\] device tensor"),
+    ("dft-pixels_raw-out", lambda g: g.dft.pixels_raw(g.G, C, out=g.c(C, 8, 16)), V, r"^out= buffer has the wrong shape / dtype / layout"),
+    ("dft-abi-null-image", lambda g: g.dft_abi("pxm_dft_px2ring", None, g.G, C), "PxmError", r"^pxm_dft_px2ring: null argument"),
+    ("dft-abi-null-rings", lambda g: g.dft_abi("pxm_dft_ring2px", None, g.c(C, 8, 15), C), "PxmError", r"^pxm_dft_ring2px: null argument"),
+    ("dft-abi-chains", lambda g: g.dft_abi("pxm_dft_px2ring", g.c(C, 8, 15), g.G, C + 1), "PxmError",
+     r"^pxm_dft_px2ring: C outside \[1, max_chains\]"),
+    ("dft-abi-unaligned", lambda g: g.dft_abi("pxm_dft_ring2px", g.r(2 * g.G.numel() + 2)[1:], g.c(C, 8, 15), C), "PxmError",
+     r"^pxm_dft_ring2px: the ring array must be 16-byte aligned"),
     ("gradg_step-shape", lambda g: g.wav.gradg_step(g.c(C, g.wav.ncoefs + 1), g.c(C, g.wav.npix), g.img, g.w_img, **_step_args(g)), A,
      r"^gradg_step: shape mismatch"),
     ("gradg_step-data", lambda g: g.wav.gradg_step(g.X, g.c(C, g.wav.npix), g.c(g.wav.npix + 1), g.w_img, **_step_args(g)), V,

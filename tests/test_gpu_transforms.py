@@ -240,11 +240,13 @@ def test_gemm_task_orders_are_bit_identical(monkeypatch):
             assert torch.equal(torch.view_as_real(a) if a.is_complex() else a, torch.view_as_real(b) if b.is_complex() else b), order
 
 
-@pytest.mark.parametrize("L,B", [(20, 2), (28, 1.5), (64, 2)])
+@pytest.mark.parametrize("L,B", [(20, 2), (28, 1.5), (64, 2), (130, 2)])
 def test_grouped_plain_dft_launches_match_per_scale_launches(L, B, monkeypatch):
     """The blocks <-> rings transforms of every member scale run in one grid each (k_px2ring_group5,
     k_ring2px_group5<false>); PXM_NO_PLAIN_DFT_GROUP=1 keeps one launch per scale.  Same bodies, same numbers: all four
-    wavelet operators agree bit for bit, for a full and a partly filled chain batch."""
+    wavelet operators agree bit for bit, for a full and a partly filled chain batch.  (130, 2): band-limits 4 .. 128 and
+    130, so one grid holds the r0 = 1, 2, 4 and 8 bodies; the per-scale launches are the ones test_gpu_dft.py holds to the
+    long-double model, which the grouped bodies inherit through this identity."""
     import torch
 
     from pxmcmc_amd import ops
