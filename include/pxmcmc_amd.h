@@ -37,6 +37,7 @@ typedef struct pxm_wav_plan_s* pxm_wav_plan_t;
 typedef struct pxm_dwav_plan_s* pxm_dwav_plan_t;
 typedef struct pxm_hwav_plan_s* pxm_hwav_plan_t;
 typedef struct pxm_dft_plan_s* pxm_dft_plan_t;
+typedef struct pxm_gemm_plan_s* pxm_gemm_plan_t;
 typedef void* pxm_stream_t; /* hipStream_t */
 
 /* ---- library ------------------------------------------------------------ */
@@ -158,6 +159,48 @@ int pxm_dft_plan_destroy(pxm_dft_plan_t plan);
 int pxm_dft_px2ring(pxm_dft_plan_t plan, const void* f, void* G, int C, pxm_stream_t stream);
 int pxm_dft_ring2px(pxm_dft_plan_t plan, const void* G, void* f, int C, pxm_stream_t stream);
 int pxm_dft_status(pxm_dft_plan_t plan, int clear, pxm_stream_t stream);
+
+/* ---- the ring-GEMM stage on its own -------------------------------------------------------------------------------
+ * The Legendre stage of every transform above (csrc/sht_gemm.hip) as a plan without DFT stage, wavelet kernels or samplers:
+ * ring tables from the shared cache, one workspace and ONE task list, built, ordered (PXM_GEMM_ORDER is read at creation),
+ * range-checked, uploaded and launched by the code every other plan uses.  How the test suite holds each kernel variant to
+ * a long-double model of the contraction ("Error model and tests of the ring GEMM").
+ * A list is n_sides sides appended in order (pk = 0), or one side / a pair of sides sharing a table in packed form (pk = 2,
+ * 4: live columns per slab; 2 * max_chains <= pk).  Side i is sides[PXM_GEMM_SIDE_INTS * i + ..]:
+ *   0 table kind (0 inverse, 1 forward, 2 inverse adjoint, 3 forward adjoint, 4 Gram, 5 parity-split Gram, 6 the same with
+ *     order 0 split and its pole term)            1 bandlimit of the tables and the ring side
+ *   2 bandlimit of the harmonic-side array, 0 = the same     3 second operand   4 per-k operand scale   5 per-row result scale
+ *   6, 7 row mask [row_lo, row_hi), row_hi <= 0 = none       8 support cut el_lo    9 data term (complex per row, stride 2)
+ *   10, 11 doubles per row of the operand / result array, 0 = 2 * roundup(max_chains, 8) (packed lists only)
+ *   12, 13 index of the earlier side whose operand(s) / result and data term this side shares, -1 = arrays of its own
+ *   14, 15 zero
+ * Arrays are [2 L' - 1][roundup(L', 16)][doubles per row] at the bandlimit L' of their side of the table.
+ * pxm_gemm_plan_report writes min(cap, n) of its n int64 words to out and returns n:
+ *   what 0: {ncol, sides, tasks, list flags (1 second operand, 2 scale, 4 pole), kernel slabs, pk, workspace doubles, offset and
+ *           doubles of the scratch row block, offset of the 8-byte counter, max_chains, +-m pairs, 0 x 4}, then 16 per side:
+ *           offsets of operand, second operand, result, k scale, row scale, data term (-1 = none), then L', rows, doubles
+ *           per row of the operand and of the result array, doubles of both, doubles of the tiled table and of the pole column
+ *   what 1: 16 per task in launch order, padding entries (n_rt = 0) included: {m_unit, row0, n_rt, k_beg, k_end, pole_n, nslab,
+ *           side, parity half (-1 none), row_lo, row_hi of slab group 0 and of group 1, sign1, second side of a packed pair
+ *           (-1 none), order m}
+ *   what 2: the tiled table of `side` (layout: top of csrc/sht_gemm.hip): {stored orders, Rp, +-m pairs, doubles, doubles of
+ *           the pole column, L, spin, kind, then per stored order: m, m_off, k_beg, odd_off (-1: stored dense), odd_k_beg}
+ * pxm_host_gemm_plan_report: the same report of a plan created in dry-run mode (no GPU; address ranges checked as at every
+ * creation), < 0 where the creation refuses.
+ * pxm_gemm_plan_write / _read copy n doubles device-to-device into / out of the workspace at `offset` (refused outside it);
+ * pxm_gemm_plan_table_read copies the first n doubles of the tiled table (which = 0) or the pole column (1) of a side.
+ * pxm_gemm_plan_run launches the list once for C chains over every column group with a live chain; affine != 0: the epilogue
+ * out = w (ns acc - data term) with w = wr + i wi per chain, columns >= 2 C zero; bump != 0: the counter advances by one. */
+#define PXM_GEMM_SIDE_INTS 16
+int pxm_gemm_plan_create(int spin, int max_chains, int pk, const int* sides, int n_sides, pxm_gemm_plan_t* plan);
+int pxm_gemm_plan_destroy(pxm_gemm_plan_t plan);
+int64_t pxm_gemm_plan_report(pxm_gemm_plan_t plan, int what, int side, int64_t* out, int64_t cap);
+int64_t pxm_host_gemm_plan_report(int spin, int max_chains, int pk, const int* sides, int n_sides, int what, int side,
+                                  int64_t* out, int64_t cap);
+int pxm_gemm_plan_write(pxm_gemm_plan_t plan, int64_t offset, const double* src, int64_t n, pxm_stream_t stream);
+int pxm_gemm_plan_read(pxm_gemm_plan_t plan, int64_t offset, double* dst, int64_t n, pxm_stream_t stream);
+int pxm_gemm_plan_table_read(pxm_gemm_plan_t plan, int side, int which, double* dst, int64_t n, pxm_stream_t stream);
+int pxm_gemm_plan_run(pxm_gemm_plan_t plan, int C, int affine, double ns, double wr, double wi, int bump, pxm_stream_t stream);
 
 /* ---- scale-discretised wavelet transform (N=1, upsample=0) -------------------- */
 /* replaces pys2let.synthesis_wav2px / synthesis_adjoint_px2wav / analysis_px2wav /

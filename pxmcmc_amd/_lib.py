@@ -81,6 +81,14 @@ SIGNATURES = {
     "pxm_dft_px2ring": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
     "pxm_dft_ring2px": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
     "pxm_dft_status": (c_int, [c_vp, c_int, c_vp]),
+    "pxm_gemm_plan_create": (c_int, [c_int, c_int, c_int, c_vp, c_int, C.POINTER(c_vp)]),
+    "pxm_gemm_plan_destroy": (c_int, [c_vp]),
+    "pxm_gemm_plan_report": (c_i64, [c_vp, c_int, c_int, c_vp, c_i64]),
+    "pxm_host_gemm_plan_report": (c_i64, [c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64]),
+    "pxm_gemm_plan_write": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "pxm_gemm_plan_read": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "pxm_gemm_plan_table_read": (c_int, [c_vp, c_int, c_int, c_vp, c_i64, c_vp]),
+    "pxm_gemm_plan_run": (c_int, [c_vp, c_int, c_int, c_dbl, c_dbl, c_dbl, c_int, c_vp]),
     "pxm_dwav_plan_create": (c_int, [c_int, c_dbl, c_int, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),
     "pxm_dwav_plan_destroy": (c_int, [c_vp]),
     "pxm_dwav_synthesis": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
@@ -222,6 +230,7 @@ CONSTANTS = dict(
     LCI_EMPTY=1,  # bits of the status of pxm_lci_search (0: ok)
     LCI_UNCONSTRAINED=2,
     LCI_NONFINITE=4,
+    GEMM_SIDE_INTS=16,  # ints per side of pxm_gemm_plan_create
 )
 globals().update(CONSTANTS)
 

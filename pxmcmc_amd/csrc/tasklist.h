@@ -53,8 +53,10 @@ struct TaskList {
 // launch order of a list: "xcd" (one queue per XCD), "bins" (one bin per CU) or anything else (descending work)
 void order_tasks(std::vector<GemmTask>& v, const std::string& order);
 // orders the tasks (PXM_GEMM_ORDER or by size), checks every address range their launches can form and uploads them
+// (ordered: where given, receives the list in launch order, padding entries included -- what the GEMM-only plan reports)
 int upload_tasks(std::vector<GemmTask> v, bool paired, TaskList* out, std::vector<int> bls, int ncol, const double* ws_base,
-                 const char* name, std::vector<int> los = {}, int pk = 0, std::vector<char> tab_shared = {});
+                 const char* name, std::vector<int> los = {}, int pk = 0, std::vector<char> tab_shared = {},
+                 std::vector<GemmTask>* ordered = nullptr);
 // algorithmic bytes of one launch of a list for cg live chain slots
 double tasklist_bytes(const TaskList& tl, int cg);
 // marks an uploaded list as the Gram launch of table T.d_tab[kind]: the four gram* fields tasklist_bytes accounts with

@@ -249,7 +249,7 @@ void order_tasks(std::vector<GemmTask>& v, const std::string& order) {
 }
 
 int upload_tasks(std::vector<GemmTask> v, bool paired, TaskList* out, std::vector<int> bls, int ncol, const double* ws_base,
-                 const char* name, std::vector<int> los, int pk, std::vector<char> tab_shared) {
+                 const char* name, std::vector<int> los, int pk, std::vector<char> tab_shared, std::vector<GemmTask>* ordered) {
   tab_shared.resize(bls.size(), 0);
   los.resize(bls.size(), 0);
   out->pk = pk;
@@ -258,6 +258,7 @@ int upload_tasks(std::vector<GemmTask> v, bool paired, TaskList* out, std::vecto
   out->los = los;
   const char* order_env = getenv("PXM_GEMM_ORDER");  // xcd | bins | plain forces one order
   order_tasks(v, order_env ? order_env : (v.size() > 2048 ? "xcd" : "bins"));
+  if (ordered) *ordered = v;
   out->n = (int)v.size();
   out->paired = paired;
   out->nslab = pk ? 4 : (paired ? 2 : 1);

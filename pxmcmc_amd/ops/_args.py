@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .._lib import MODE_REAL_PAIRS, NOISE_F64, require_gpu
+from .._lib import GEMM_SIDE_INTS, MODE_REAL_PAIRS, NOISE_F64, require_gpu
 
 _CPLX, _REAL = torch.complex128, torch.float64
 
@@ -139,6 +139,35 @@ def _dev_tensors(fn, what, *specs):
     for t, dt, shape in specs:
         if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
             raise TypeError("%s: %s" % (fn, what))
+
+
+# ---- the sides of a GEMM-only plan ----------------------------------------------------------------------------------------------
+GEMM_KINDS = ("inv", "fwd", "inv_adj", "fwd_adj", "gram", "gram_split", "gram_split0")  # TableKind of csrc/sht_tables.h
+_GEMM_SIDE_KEYS = ("kind", "bl", "L", "two", "ks", "rs", "rows", "el_lo", "hd", "x_ncol", "y_ncol", "x_share", "y_share")
+
+
+def _gemm_sides(sides, max_chains, pk):
+    """the sides of ``GemmPlan`` / ``gemm_plan_geometry`` (dicts with ``kind`` and ``bl`` and any of the other keys of
+    include/pxmcmc_amd.h, pxm_gemm_plan_create) -> the int array of the C-ABI, GEMM_SIDE_INTS per side"""
+    if not isinstance(sides, (list, tuple)) or not sides or not all(isinstance(s, dict) for s in sides):
+        raise TypeError("GemmPlan: sides must be a non-empty list of dicts")
+    if int(pk) not in (0, 2, 4):
+        raise ValueError("GemmPlan: pk must be 0, 2 or 4")
+    if int(max_chains) < 1 or (pk and 2 * int(max_chains) > pk):
+        raise ValueError("GemmPlan: max_chains must be >= 1, and at most pk / 2 in a packed list")
+    out = (C.c_int * (GEMM_SIDE_INTS * len(sides)))()
+    for i, s in enumerate(sides):
+        unknown = set(s) - set(_GEMM_SIDE_KEYS)
+        if unknown or "kind" not in s or "bl" not in s:
+            raise ValueError(f"GemmPlan: side {i} needs kind and bl and knows {', '.join(_GEMM_SIDE_KEYS)}")
+        kind = GEMM_KINDS.index(s["kind"]) if s["kind"] in GEMM_KINDS else s["kind"]
+        if not isinstance(kind, int) or not 0 <= kind < len(GEMM_KINDS):
+            raise ValueError(f"GemmPlan: side {i}: kind must be one of {', '.join(GEMM_KINDS)}")
+        lo, hi = s.get("rows") or (0, 0)
+        row = (kind, s["bl"], s.get("L", 0), bool(s.get("two")), bool(s.get("ks")), bool(s.get("rs")), lo, hi, s.get("el_lo", 0),
+               bool(s.get("hd")), s.get("x_ncol", 0), s.get("y_ncol", 0), s.get("x_share", -1), s.get("y_share", -1), 0, 0)
+        out[GEMM_SIDE_INTS * i:GEMM_SIDE_INTS * (i + 1)] = [int(v) for v in row]
+    return out
 
 
 # ---- step size and noise -------------------------------------------------------------------------------------------------------

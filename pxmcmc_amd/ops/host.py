@@ -57,3 +57,47 @@ def noise_bits():
     the flag by default: ``noise_bits=64``); every noise-drawing call takes
     ``noise64=True`` for the double-precision evaluation (PXM_NOISE_F64, include/pxmcmc_amd.h)"""
     return int(lib.pxm_noise_bits())
+
+
+# ---- reports of a GEMM-only plan (include/pxmcmc_amd.h: pxm_gemm_plan_report) ------------------------------------------------------
+GEMM_TASK_FIELDS = ("m_unit", "row0", "n_rt", "k_beg", "k_end", "pole_n", "nslab", "side", "par", "row_lo", "row_hi", "row_lo1",
+                    "row_hi1", "sign1", "side_b", "m")
+_GEMM_HEAD = ("ncol", "n_sides", "n_tasks", "flags", "nslab", "pk", "ws_doubles", "off_scratch", "scratch_doubles", "off_counter",
+              "max_chains", "paired")
+_GEMM_SIDE = ("off_x", "off_x2", "off_y", "off_ks", "off_rs", "off_hd", "xL", "xRp", "xn", "yL", "yRp", "yn", "n_x", "n_y", "n_tab",
+              "n_pole")
+_GEMM_TABLE = ("n_m", "Rp", "paired", "n_tab", "n_pole", "L", "spin", "kind")
+
+
+def _gemm_words(call, what, side):
+    """the int64 words of report ``what``: ``call(what, side, out, cap)`` is asked for the size, then for the words"""
+    n = check(call(what, side, None, 0))
+    out = (C.c_int64 * max(int(n), 1))()
+    check(call(what, side, out, n))
+    return np.array(out[:n], dtype=np.int64)
+
+
+def gemm_report(call, n_sides):
+    """the three reports of a GEMM-only plan as ``{layout, sides, tasks, tables}``: ``layout`` the header words by name,
+    ``sides`` one dict per side, ``tasks`` the [n, 16] list in launch order (columns GEMM_TASK_FIELDS), ``tables`` per side
+    the bookkeeping of its tiled table with ``orders`` [n_m, 5] = (m, m_off, k_beg, odd_off, odd_k_beg)"""
+    w = _gemm_words(call, 0, 0)
+    rep = {"layout": dict(zip(_GEMM_HEAD, (int(v) for v in w[:16]))),
+           "sides": [dict(zip(_GEMM_SIDE, (int(v) for v in w[16 + 16 * i:32 + 16 * i]))) for i in range(n_sides)],
+           "tasks": _gemm_words(call, 1, 0).reshape(-1, len(GEMM_TASK_FIELDS)), "tables": []}
+    for i in range(n_sides):
+        t = _gemm_words(call, 2, i)
+        tab = dict(zip(_GEMM_TABLE, (int(v) for v in t[:8])))
+        tab["orders"] = t[8:].reshape(-1, 5)
+        rep["tables"].append(tab)
+    return rep
+
+
+def gemm_plan_geometry(sides, spin=0, max_chains=8, pk=0):
+    """``gemm_report`` of the GEMM-only plan ``ops.GemmPlan(sides, spin, max_chains, pk)`` built in dry-run mode: the real task
+    builders, launch order (PXM_GEMM_ORDER) and address-range check, no GPU.  Raises PxmError where the creation refuses."""
+    from ._args import _gemm_sides
+
+    desc = _gemm_sides(sides, max_chains, pk)
+    return gemm_report(lambda what, side, out, cap: lib.pxm_host_gemm_plan_report(int(spin), int(max_chains), int(pk), desc, len(sides),
+                                                                                  what, side, out, cap), len(sides))

@@ -1,6 +1,6 @@
-"""The transform plans -- spherical-harmonic, the phi-DFT stage alone, axisymmetric, directional and harmonic-space wavelets --
+"""The transform plans -- spherical-harmonic, the phi-DFT stage alone, the ring-GEMM stage alone, axisymmetric, directional and harmonic-space wavelets --
 with the fused sampler steps of the wavelet plan, the live-plan registry, the device iteration counter and the capture scope
-(csrc/sht_plan.hip, dft_plan.hip, wav_plan.hip, wav_ops.hip, wav_wl.hip, dirwav.hip, harmwav.hip)."""
+(csrc/sht_plan.hip, dft_plan.hip, gemm_plan.hip, wav_plan.hip, wav_ops.hip, wav_wl.hip, dirwav.hip, harmwav.hip)."""
 import ctypes as C
 import threading
 import weakref
@@ -9,7 +9,8 @@ import numpy as np
 import torch
 
 from .._lib import STATUS_PAIR_SYNC, PxmError, check, lib, require_gpu
-from ._args import (_CPLX, _REAL, _batched, _data_invcov, _dev_tensors, _nf, _noise_args, _p, _pair_noise_args, _result, _stream, _vecT, as_device,
+from .host import gemm_report
+from ._args import (_CPLX, _REAL, _batched, _data_invcov, _dev_tensors, _gemm_sides, _nf, _noise_args, _p, _pair_noise_args, _result, _stream, _vecT, as_device,
                     device)
 
 
@@ -168,6 +169,70 @@ class DftPlan(_Plan):
         raw = self.ring_array()
         raw[:, :self.L, :g.shape[0]] = g.permute(2, 1, 0)
         return self.pixels_raw(raw, g.shape[0])
+
+
+class GemmPlan(_Plan):
+    """The ring-GEMM stage of the transforms on its own (include/pxmcmc_amd.h, pxm_gemm_plan_*): ring tables, a workspace and
+    ONE task list made of ``sides`` (dicts: ``kind`` one of ops.GEMM_KINDS, ``bl``, and optionally ``L`` the bandlimit of
+    the harmonic-side array, ``two``, ``ks``, ``rs``, ``rows`` = (row_lo, row_hi), ``el_lo``, ``hd``, ``x_ncol``, ``y_ncol``,
+    ``x_share``, ``y_share``), appended in order or, with ``pk`` 2 / 4, as one packed side or pair.  ``layout``, ``sides``,
+    ``tasks`` and ``tables`` are ops.gemm_report of the plan; the caller fills the arrays with ``write``, runs the list and
+    reads results, scratch block and counter back with ``read``."""
+
+    def __init__(self, sides, spin=0, max_chains=8, pk=0):
+        require_gpu()
+        desc = _gemm_sides(sides, max_chains, pk)
+        self.spin, self.max_chains, self.pk, self.n_sides = int(spin), int(max_chains), int(pk), len(sides)
+        super().__init__(lib.pxm_gemm_plan_create, (self.spin, self.max_chains, self.pk, desc, self.n_sides), lib.pxm_gemm_plan_destroy,
+                         None, f"GemmPlan(spin={self.spin}, sides={self.n_sides}, pk={self.pk})")
+        rep = gemm_report(lambda what, side, out, cap: lib.pxm_gemm_plan_report(self._h, what, side, out, cap), self.n_sides)
+        self.layout, self.sides, self.tasks, self.tables = rep["layout"], rep["sides"], rep["tasks"], rep["tables"]
+
+    def status(self, clear=False):
+        """0: the GEMM kernels have no bounded wait"""
+        return 0
+
+    def write(self, offset, src):
+        """copies the float64 device tensor ``src`` into the workspace at ``offset`` (doubles)"""
+        _dev_tensors("GemmPlan.write", "src must be a contiguous float64 device tensor", (src, _REAL, tuple(getattr(src, "shape", ()))))
+        check(lib.pxm_gemm_plan_write(self._h, int(offset), _p(src), src.numel(), _stream()))
+
+    def read(self, offset, n):
+        """``n`` doubles of the workspace from ``offset`` on -> a fresh device tensor"""
+        if int(n) < 0:
+            raise ValueError("GemmPlan.read: negative length")
+        out = torch.empty(int(n), dtype=_REAL, device=device())
+        check(lib.pxm_gemm_plan_read(self._h, int(offset), _p(out), int(n), _stream()))
+        return out
+
+    def _table(self, side, which, n):
+        if not 0 <= int(side) < self.n_sides:
+            raise ValueError("GemmPlan: no such side")
+        out = torch.empty(n, dtype=_REAL, device=device())
+        if n:
+            check(lib.pxm_gemm_plan_table_read(self._h, int(side), which, _p(out), n, _stream()))
+        return out
+
+    def table(self, side=0):
+        """the tiled table of a side as the kernel streams it (layout: top of csrc/sht_gemm.hip; ``tables[side]``)"""
+        return self._table(side, 0, self.tables[side]["n_tab"] if 0 <= int(side) < self.n_sides else 0)
+
+    def pole(self, side=0):
+        """the pole column b of a gram_split0 side, [Rp / 2 even degrees | Rp / 2 odd degrees] (empty for other kinds)"""
+        return self._table(side, 1, self.tables[side]["n_pole"] if 0 <= int(side) < self.n_sides else 0)
+
+    def run(self, C_, affine=None, bump=False):
+        """launches the list once for ``C_`` chains; ``affine`` = (ns, w): the epilogue out = w (ns acc - data term);
+        ``bump``: the counter at ``layout['off_counter']`` advances by one"""
+        if not 1 <= int(C_) <= self.max_chains:
+            raise ValueError("more chains than the plan was created for")
+        ns, w = (0.0, 0.0) if affine is None else affine
+        w = complex(w)
+        check(lib.pxm_gemm_plan_run(self._h, int(C_), int(affine is not None), float(ns), w.real, w.imag, int(bool(bump)), _stream()))
+
+    def counter(self):
+        """the value of the 8-byte counter"""
+        return int(self.read(self.layout["off_counter"], 1).view(torch.int64).item())
 
 
 def _update_out(out, x):

@@ -47,6 +47,9 @@ def g():
     g.dft = ops.DftPlan(8, max_chains=C)  # images [c, 8, 15], ring array [15, 16, 8]
     g.G = g.dft.ring_array()
     g.dft_abi = lambda name, a, b, n: ops.check(getattr(_lib.lib, name)(g.dft._h, _p(a), _p(b), n, None))
+    g.gemm = ops.GemmPlan([dict(kind="inv", bl=8)], max_chains=C)  # workspace: counter block, operand, result, scratch rows
+    g.gemm_pk = ops.GemmPlan([dict(kind="fwd", bl=8)], max_chains=1, pk=2)
+    g.gemm_abi = lambda name, *a: ops.check(getattr(_lib.lib, name)(*a))
     g.X = g.c(C, g.wav.ncoefs)
     g.img, g.w_img = g.c(g.wav.npix), g.r(g.wav.npix)
     g.XH = g.c(C, g.hwav.ncoefs)
@@ -258,6 +261,45 @@ ROWS = [
      r"^pxm_dft_px2ring: C outside \[1, max_chains\]"),
     ("dft-abi-unaligned", lambda g: g.dft_abi("pxm_dft_ring2px", g.r(2 * g.G.numel() + 2)[1:], g.c(C, 8, 15), C), "PxmError",
      r"^pxm_dft_ring2px: the ring array must be 16-byte aligned"),
+    ("gemm-sides-type", lambda g: g.ops.GemmPlan(dict(kind="inv", bl=8)), T_, r"^GemmPlan: sides must be a non-empty list of dicts"),
+    ("gemm-sides-empty", lambda g: g.ops.GemmPlan([]), T_, r"^GemmPlan: sides must be a non-empty list of dicts"),
+    ("gemm-side-key", lambda g: g.ops.GemmPlan([dict(kind="inv", bl=8, scale=True)]), V, r"^GemmPlan: side 0 needs kind and bl and knows"),
+    ("gemm-side-kind", lambda g: g.ops.GemmPlan([dict(kind="legendre", bl=8)]), V, r"^GemmPlan: side 0: kind must be one of inv, fwd"),
+    ("gemm-pk", lambda g: g.ops.GemmPlan([dict(kind="fwd", bl=8)], max_chains=1, pk=3), V, r"^GemmPlan: pk must be 0, 2 or 4"),
+    ("gemm-pk-chains", lambda g: g.ops.GemmPlan([dict(kind="fwd", bl=8)], max_chains=2, pk=2), V,
+     r"^GemmPlan: max_chains must be >= 1, and at most pk / 2 in a packed list"),
+    ("gemm-pitch-unpacked", lambda g: g.ops.GemmPlan([dict(kind="fwd", bl=8, x_ncol=4)]), "PxmError",
+     r"^pxm_gemm_plan_create: a row pitch of its own needs a packed list"),
+    ("gemm-pair-tables", lambda g: g.ops.GemmPlan([dict(kind="fwd", bl=8), dict(kind="fwd", bl=16)], max_chains=1, pk=2), "PxmError",
+     r"^pxm_gemm_plan_create: the two sides of a packed pair share one table"),
+    ("gemm-share-later", lambda g: g.ops.GemmPlan([dict(kind="fwd", bl=8, y_share=0)]), "PxmError",
+     r"^pxm_gemm_plan_create: a side shares arrays of an earlier side only"),
+    ("gemm-split-Rp", lambda g: g.ops.GemmPlan([dict(kind="gram_split", bl=8, two=True)]), "PxmError",
+     r"^build_gram_split: the parity split needs spin-0 tables and Rp % 32 == 0"),
+    ("gemm-pole-streaming", lambda g: g.ops.GemmPlan([dict(kind="gram_split0", bl=32)]), "PxmError",
+     r"^upload_tasks: a streaming list with a row pitch of its own"),
+    ("gemm-pole-scale", lambda g: g.ops.GemmPlan([dict(kind="gram_split0", bl=32, two=True, ks=True)]).run(1), "PxmError",
+     r"^launch_gemm: a pole term outside the Gram list"),
+    ("gemm-write-dtype", lambda g: g.gemm.write(16, g.c(4)), T_, r"^GemmPlan.write: src must be a contiguous float64 device tensor"),
+    ("gemm-write-host", lambda g: g.gemm.write(16, g.r(4).cpu()), T_, r"^GemmPlan.write: src must be a contiguous float64 device tensor"),
+    ("gemm-write-past", lambda g: g.gemm.write(g.gemm.layout["ws_doubles"] - 3, g.r(4)), "PxmError",
+     r"^pxm_gemm_plan_write: range outside the workspace"),
+    ("gemm-write-negative", lambda g: g.gemm.write(-1, g.r(4)), "PxmError", r"^pxm_gemm_plan_write: range outside the workspace"),
+    ("gemm-read-past", lambda g: g.gemm.read(g.gemm.layout["ws_doubles"], 1), "PxmError",
+     r"^pxm_gemm_plan_read: range outside the workspace"),
+    ("gemm-read-negative", lambda g: g.gemm.read(0, -1), V, r"^GemmPlan.read: negative length"),
+    ("gemm-table-side", lambda g: g.gemm.table(1), V, r"^GemmPlan: no such side"),
+    ("gemm-run-chains", lambda g: g.gemm.run(C + 1), V, r"^more chains than the plan was created for"),
+    ("gemm-run-packed-affine", lambda g: g.gemm_pk.run(1, affine=(1.0, 1.0)), "PxmError",
+     r"^pxm_gemm_plan_run: the packed kernels have no affine epilogue and no counter"),
+    ("gemm-abi-null-plan", lambda g: g.gemm_abi("pxm_gemm_plan_run", None, 1, 0, 0.0, 0.0, 0.0, 0, None), "PxmError",
+     r"^pxm_gemm_plan_run: null plan"),
+    ("gemm-abi-chains", lambda g: g.gemm_abi("pxm_gemm_plan_run", g.gemm._h, C + 1, 0, 0.0, 0.0, 0.0, 0, None), "PxmError",
+     r"^pxm_gemm_plan_run: C outside \[1, max_chains\]"),
+    ("gemm-abi-table-more", lambda g: g.gemm_abi("pxm_gemm_plan_table_read", g.gemm._h, 0, 1, g.r(4).data_ptr(), 4, None), "PxmError",
+     r"^pxm_gemm_plan_table_read: more doubles than the table has"),
+    ("gemm-abi-report-what", lambda g: g.gemm_abi("pxm_gemm_plan_report", g.gemm._h, 3, 0, None, 0), "PxmError",
+     r"^pxm_gemm_plan_report: what must be 0"),
     ("gradg_step-shape", lambda g: g.wav.gradg_step(g.c(C, g.wav.ncoefs + 1), g.c(C, g.wav.npix), g.img, g.w_img, **_step_args(g)), A,
      r"^gradg_step: shape mismatch"),
     ("gradg_step-data", lambda g: g.wav.gradg_step(g.X, g.c(C, g.wav.npix), g.c(g.wav.npix + 1), g.w_img, **_step_args(g)), V,
