@@ -122,6 +122,14 @@ int pxm_host_pfa511_tables(uint16_t* idx, double* b2);
  * calls.  -1 (pxm_last_error names L, M and the bytes) where the unit needs more LDS than a CU has: L >= 1025, which every
  * plan constructor refuses with the same text.  No GPU needed. */
 int pxm_host_dft_geometry(int L, int* out);
+/* whether a fused rings -> X' -> rings launch of the phi-DFT stage is the STOCK MYULA update, which the pair unit runs on
+ * kernels that hold the update's mode at compile time (csrc/sht_core.h: dft_step_is_stock -- the predicate the launchers
+ * call): fields = which optional operands the launch carries, bit 0 the state X (fused update), 1 the threshold vector T,
+ * 2 injected noise, 3 the device-resident iteration addend, 4 / 5 residual data / inverse covariance, 6 / 7 gather index /
+ * weight; mode one of PXM_MODE_*; chain0 the id of the first chain.  1: stock -- X, T and the addend present, none of the
+ * others, PXM_MODE_REAL_PAIRS and an even chain0; 0 otherwise.  PXM_DFT_STOCK=0 at plan creation keeps every launch on the
+ * generic kernels.  No GPU needed. */
+int pxm_host_dft_step_is_stock(unsigned fields, int mode, uint64_t chain0);
 
 /* ---- spin spherical-harmonic transforms on the MW grid ---------------------- */
 /* replaces pyssht.forward / inverse / inverse_adjoint / forward_adjoint
@@ -299,6 +307,9 @@ int pxm_wav_status(pxm_wav_plan_t plan, int clear, pxm_stream_t stream);
 int pxm_sht_status(pxm_sht_plan_t plan, int clear, pxm_stream_t stream);
 /* scales whose 511-point rings the fused rings -> X' -> rings launch takes through the exact-length phi-DFT unit (0: Bluestein) */
 int pxm_wav_exact_dft_scales(pxm_wav_plan_t plan);
+/* 1 when that launch runs stock MYULA updates (pxm_host_dft_step_is_stock) on the STOCK kernel instantiation; 0 with
+ * PXM_DFT_STOCK=0 at plan creation or without a grouped launch: every update on the generic kernels */
+int pxm_wav_dft_stock(pxm_wav_plan_t plan);
 
 /* Live kernel timing of one plan (bench.py roofline leg).  pxm_wav_profile_enable(plan, n) with n > 0 creates
  * n event pairs per kernel class; while enabled every SHT ring-GEMM launch and every grouped phi-DFT launch of

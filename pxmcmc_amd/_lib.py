@@ -35,6 +35,7 @@ SIGNATURES = {
     "pxm_wav_release_iter_counter": (c_int, [c_vp, c_vp]),
     "pxm_wav_iter_counter_add": (c_int, [c_vp, c_u64, c_vp]),
     "pxm_wav_exact_dft_scales": (c_int, [c_vp]),
+    "pxm_wav_dft_stock": (c_int, [c_vp]),
     "pxm_wav_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_sht_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_wav_profile_enable": (c_int, [c_vp, c_int]),
@@ -53,6 +54,7 @@ SIGNATURES = {
     "pxm_host_rec_geometry": (c_int, [c_int, c_int, c_int, c_vp]),
     "pxm_host_pfa511_tables": (c_int, [c_vp, c_vp]),
     "pxm_host_dft_geometry": (c_int, [c_int, c_vp]),
+    "pxm_host_dft_step_is_stock": (c_int, [C.c_uint, c_int, c_u64]),
     "pxm_quantile_range": (c_int, [c_vp, c_i64, c_i64, c_i64, c_dbl, c_vp, c_vp]),
     "pxm_moments_update": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_vp]),
     "pxm_moments_scratch_doubles": (c_i64, [c_i64]),

@@ -176,6 +176,7 @@ int make_dft_plan(int L, DftPlan* p) {
   p->n = 2 * L - 1;
   p->Rp = round_up(L, 16);
   p->unit = g.unit;
+  if (const char* e = getenv("PXM_DFT_STOCK")) p->stock = atoi(e) != 0;
   if (g.unit == DFT_PAIR) {
     if (const char* e = getenv("PXM_DEBUG_PAIR_SYNC_LIMIT")) p->spin_limit = (unsigned)std::max(0, atoi(e));
     return pair_make_tables(p->n, g.pfa, &p->pair);

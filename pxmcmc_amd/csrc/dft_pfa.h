@@ -182,9 +182,12 @@ static_assert(4 * PFA_STAGE_S <= 4 * PFA_PLANE, "a ring group's stage fits in it
 // bxw: workgroup index along the rings; the workgroup takes the ring pairs bxw * passes + ps, ps < passes, one after the
 // other (passes = 2: half as many workgroups -- with one such workgroup per CU the latency-bound workgroups of the small
 // scales are resident from the start of the launch instead of forming a second round).
-template <bool RING_OUT, bool N64>
+// STOCK: the launch is the stock MYULA update (dft_step_is_stock, sht_core.h; fp64 noise): its epilogue is
+// px_stock_update4 (update.h) and none of the mode fields of PxOut is read.
+template <bool RING_OUT, bool N64, bool STOCK = false>
 __device__ __forceinline__ void ring2px_body_pfa(const Dft5Args& a, const PfaTabs& pt, double* __restrict__ G, int ncol,
                                                  const PxOut& out, int C, int bxw, int by, int passes, double2* lds5) {
+  static_assert(!STOCK || (RING_OUT && N64), "the stock instantiation is the fused step with the fp64 noise stream");
   if ((by << 2) >= C) return;
 #ifdef PXM_D5_TRACE
   unsigned long long d5_stamp[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -234,7 +237,7 @@ __device__ __forceinline__ void ring2px_body_pfa(const Dft5Args& a, const PfaTab
     // fp64 noise: LDS copies of the two Box-Muller tables (129 + 256 entries behind the filter spectrum); behind them the two
     // group counters: 81 056 B per workgroup
 #if !defined(PXM_NOISE_F64_POLY)
-    if (N64 && out.X && !out.noise && tid < NOISE_LOG_N + 256)  // (385 entries, 512 threads)
+    if (N64 && (STOCK || (out.X && !out.noise)) && tid < NOISE_LOG_N + 256)  // (385 entries, 512 threads)
       B2l[72 + tid] = tid < NOISE_LOG_N ? reinterpret_cast<const double2*>(&NOISE_LOG_TAB[0][0])[tid]
                                         : reinterpret_cast<const double2*>(&NOISE_SINCOS_TAB[0][0])[tid - NOISE_LOG_N];
 #endif
@@ -287,10 +290,25 @@ __device__ __forceinline__ void ring2px_body_pfa(const Dft5Args& a, const PfaTab
   const int64_t e0 = out.ring0 + (int64_t)t * n + lane;  // the lane's first element; p advances by 64
   const int64_t ce0 = (int64_t)ch * out.chain_stride + e0;
   const bool last_ok = lane < 63;                        // element lane + 448 exists
-  const uint64_t it_eff = out.iter + (out.iter_dev ? *out.iter_dev : 0);
+  const uint64_t it_eff = out.iter + ((STOCK || out.iter_dev) ? *out.iter_dev : 0);
   const int ch_s = __builtin_amdgcn_readfirstlane(ch);
 #pragma unroll
   for (int g0 = 0; g0 < 8; g0 += 4) {
+    if constexpr (STOCK) {
+      // the stock update (update.h), plane -> X' -> plane four elements at a time
+      double2* park = plane + lane + 64 * g0;
+      if (act) {
+        const bool ok[4] = {true, true, true, g0 + 3 < 7 || last_ok};  // (lane 63, p = 7: slot 511, never an element)
+        px_stock_update4<64>(out, ok, e0 + 64 * g0, ce0 + 64 * g0, -lane - 64 * g0, ch_s, it_eff, park, logt, sct);
+      } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) park[64 * u] = double2{0.0, 0.0};  // padding chains / rings: their rings are kept at zero
+      }
+#ifdef PXM_D5_TRACE
+      if (g0 == 0) PXM_D5_STAMP(3) else PXM_D5_STAMP(4)
+#endif
+      continue;
+    }
     double2 x[4];
     // (lane 63, p = 7: slot 511, never an element.  In the update branch the four elements stay in the plane until the noise
     // has been drawn: 16 registers fewer across the fp64 Box-Muller)

@@ -15,6 +15,25 @@ struct pxm_dft_plan_s {
 
 extern "C" {
 
+int pxm_host_dft_step_is_stock(unsigned fields, int mode, uint64_t chain0) {
+  PXM_REQUIRE((fields & ~0xffu) == 0, "pxm_host_dft_step_is_stock: fields has eight bits");
+  static const double some = 0;  // (the predicate asks only whether a pointer is set)
+  static const uint64_t some_u = 0;
+  static const int32_t some_i = 0;
+  PxOut o;
+  o.X = (fields & 1) ? &some : nullptr;
+  o.T = (fields & 2) ? &some : nullptr;
+  o.noise = (fields & 4) ? &some : nullptr;
+  o.iter_dev = (fields & 8) ? &some_u : nullptr;
+  o.rdata = (fields & 16) ? &some : nullptr;
+  o.rinvcov = (fields & 32) ? &some : nullptr;
+  o.gidx = (fields & 64) ? &some_i : nullptr;
+  o.gw = (fields & 128) ? &some : nullptr;
+  o.mode = mode;
+  o.chain0 = chain0;
+  return dft_step_is_stock(o) ? 1 : 0;
+}
+
 int pxm_host_dft_geometry(int L, int* out) {
   PXM_REQUIRE(out, "pxm_host_dft_geometry: null output");
   PXM_REQUIRE(L >= 1, "pxm_host_dft_geometry: need L >= 1");

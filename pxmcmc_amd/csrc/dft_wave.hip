@@ -104,6 +104,19 @@ __device__ __forceinline__ void d5_exchange_fill(double2 (&x)[8], double2* plane
   }
 }
 
+// the same where the wave's own (updated) elements already stand in exchange region SLOT of its plane (STOCK epilogue)
+template <int SLOT>
+__device__ __forceinline__ void d5_exchange_fill_parked(double2 (&x)[8], const double2* plane, const double2* pplane, int lane, int half,
+                                                        unsigned* pcnt, unsigned& epoch, const D5Sync& sy) {
+  d5_pair_sync(pcnt, epoch += 2, lane, sy);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const double2 o = pplane[256 * SLOT + 64 * u + lane], own = plane[256 * SLOT + 64 * u + lane];
+    x[u] = d5_sel(half, o, own);
+    x[4 + u] = d5_sel(half, own, o);
+  }
+}
+
 // ---- workgroup geometry ---------------------------------------------------------------------------------------
 // Two waves per ring set: wave = 2 * unit + half; unit u = chain u of the workgroup; lane -> ring rho of the unit.  stage: the rings of the workgroup in [ring][k][chain] order (16-B x R
 // segments per m in the ring arrays); the chain slot is rotated with k so that the lanes' strided reads
@@ -229,7 +242,9 @@ __device__ unsigned long long* g_dft_trace = nullptr;
 #endif
 // N64: the Philox stream's Box-Muller step in double precision (PxOut::noise64; a kernel instantiation of its own: the
 // fp64 evaluation holds ~40 registers and the update epilogue sits at the 128-VGPR budget of four waves per SIMD)
-template <int R0, bool RING_OUT, bool N64>
+// STOCK: the launch is the stock MYULA update (dft_step_is_stock, sht_core.h; fp64 noise): its epilogue is px_stock_update4
+// (update.h) on elements parked in the wave's plane, and none of the mode fields of PxOut is read
+template <int R0, bool RING_OUT, bool N64, bool STOCK = false>
 __device__ __forceinline__ void ring2px_body5(const Dft5Args& a, double* __restrict__ G, int ncol, const PxOut& out, int C,
                                               int bx, int by, double2* lds5) {
   // chain groups without a live chain do nothing (see run_tasks / GemmAffine::ncol_live: nothing iterates on them)
@@ -287,7 +302,22 @@ __device__ __forceinline__ void ring2px_body5(const Dft5Args& a, double* __restr
   const bool act = ch < C && tv;
   const int64_t e0 = out.ring0 + (int64_t)t * n + jb + (int64_t)(8 * R0) * pb;  // the wave's first element; u advances by 8 r0
   const int64_t ce0 = (int64_t)ch * out.chain_stride + e0;
-  if (act && out.X) {  // fused prox + MYULA update (pxmcmc/mcmc.py:185-201, prior.py:49-50)
+  if constexpr (STOCK) {
+    static_assert(RING_OUT && N64, "the stock instantiation is the fused step with the fp64 noise stream");
+    // The wave's four elements wait in exchange region 1 of its OWN plane -- dead since the transform, and where
+    // d5_exchange_fill<1> would put the updated elements for the partner anyway -- while the noise is drawn: the operand
+    // loads can then go first and fly across the Philox rounds (as in the exact-length body) without 16 more live registers.
+    double2* park = plane + 256 + lane;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) park[64 * u] = act ? x[u] : double2{0.0, 0.0};
+    if (act) {
+      bool ok[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) ok[u] = jb + 8 * R0 * (pb + u) < n;
+      px_stock_update4<8 * R0>(out, ok, e0, ce0, -(jb + 8 * R0 * pb), __builtin_amdgcn_readfirstlane(ch), out.iter + *out.iter_dev, park,
+                               reinterpret_cast<const double2*>(&NOISE_LOG_TAB[0][0]), reinterpret_cast<const double2*>(&NOISE_SINCOS_TAB[0][0]));
+    }
+  } else if (act && out.X) {  // fused prox + MYULA update (pxmcmc/mcmc.py:185-201, prior.py:49-50)
     const uint64_t it_eff = out.iter + (out.iter_dev ? *out.iter_dev : 0);
     // (the chain slot is the same for every lane of a wave: as a scalar, the Philox key -- seed + chain * odd constant,
     // a 64-bit multiply -- is computed once on the scalar unit instead of per lane and per element)
@@ -391,7 +421,8 @@ __device__ __forceinline__ void ring2px_body5(const Dft5Args& a, double* __restr
   if (!RING_OUT) return;
   PXM_D5_STAMP(2)  // prox + update + noise done
   // ---- forward transform of the updated ring
-  d5_exchange_fill<1>(x, plane, pplane, lane, half, pcnt, epoch, sy);  // both waves of the ring set need all 8 elements
+  if constexpr (STOCK) d5_exchange_fill_parked<1>(x, plane, pplane, lane, half, pcnt, epoch, sy);  // (its own elements stand there already)
+  else d5_exchange_fill<1>(x, plane, pplane, lane, half, pcnt, epoch, sy);  // both waves of the ring set need all 8 elements
   d5_pair_sync(pcnt, epoch += 2, lane, sy);        // ... and every exchange read is done before the planes are reused
   PXM_D5_TRANSFORM(0)
   PXM_D5_STAMP(3)  // forward transform done
@@ -428,7 +459,7 @@ __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_px2ring5(Dft5Args a, PxIn 
   px2ring_body5<R0>(a, in, G, ncol, C, blockIdx.x, blockIdx.y, lds5);
 }
 
-template <int R0, bool RING_OUT, bool N64>
+template <int R0, bool RING_OUT, bool N64, bool STOCK = false>
 __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_ring2px5(Dft5Args a, double* __restrict__ G, int ncol,
                                                                                  PxOut out, int C) {
   extern __shared__ double2 lds5[];
@@ -436,11 +467,11 @@ __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_ring2px5(Dft5Args a, doubl
     if (a.pfa && ncol >= 8) {
       const PfaTabs pt{reinterpret_cast<const uint16_t*>(a.pfa + PFA_TAB_GAT), reinterpret_cast<const uint16_t*>(a.pfa + PFA_TAB_KIDX),
                        reinterpret_cast<const double2*>(a.pfa + PFA_TAB_B2)};
-      ring2px_body_pfa<RING_OUT, N64>(a, pt, G, ncol, out, C, blockIdx.x, blockIdx.y, 1, lds5);
+      ring2px_body_pfa<RING_OUT, N64, STOCK>(a, pt, G, ncol, out, C, blockIdx.x, blockIdx.y, 1, lds5);
       return;
     }
   }
-  ring2px_body5<R0, RING_OUT, N64>(a, G, ncol, out, C, blockIdx.x, blockIdx.y, lds5);
+  ring2px_body5<R0, RING_OUT, N64, STOCK>(a, G, ncol, out, C, blockIdx.x, blockIdx.y, lds5);
 }
 
 // block id -> (scale entry, bx, by).  XCD-aware order inside a scale: the chain groups (by) of one ring set share
@@ -488,7 +519,7 @@ extern "C" int pxm_debug_set_dft_trace(unsigned long long* buf) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_dft_trace), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
 }
 #endif
-template <bool RING_OUT, bool N64>
+template <bool RING_OUT, bool N64, bool STOCK = false>
 __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_ring2px_group5(const Dft5Group* __restrict__ ents, int nent,
                                                                                        double* __restrict__ ws, int ncol, PxOut out,
                                                                                        int C) {
@@ -504,14 +535,14 @@ __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_ring2px_group5(const Dft5G
                      reinterpret_cast<const double2*>(pb + PFA_TAB_B2)};
     // (pfa_passes = 2: half as many workgroups, each taking two ring pairs in turn -- with one such workgroup per CU the
     // latency-bound workgroups of the small scales are resident from the start instead of forming a second round)
-    ring2px_body_pfa<RING_OUT, N64>(a, pt, G, ncol, out, C, bx, by, g.pfa_passes, lds5);
+    ring2px_body_pfa<RING_OUT, N64, STOCK>(a, pt, G, ncol, out, C, bx, by, g.pfa_passes, lds5);
   }
   switch (g.r0) {
     case 9: break;  // (done above)
-    case 8: ring2px_body5<8, RING_OUT, N64>(a, G, ncol, out, C, bx, by, lds5); break;
-    case 4: ring2px_body5<4, RING_OUT, N64>(a, G, ncol, out, C, bx, by, lds5); break;
-    case 2: ring2px_body5<2, RING_OUT, N64>(a, G, ncol, out, C, bx, by, lds5); break;
-    default: ring2px_body5<1, RING_OUT, N64>(a, G, ncol, out, C, bx, by, lds5); break;
+    case 8: ring2px_body5<8, RING_OUT, N64, STOCK>(a, G, ncol, out, C, bx, by, lds5); break;
+    case 4: ring2px_body5<4, RING_OUT, N64, STOCK>(a, G, ncol, out, C, bx, by, lds5); break;
+    case 2: ring2px_body5<2, RING_OUT, N64, STOCK>(a, G, ncol, out, C, bx, by, lds5); break;
+    default: ring2px_body5<1, RING_OUT, N64, STOCK>(a, G, ncol, out, C, bx, by, lds5); break;
   }
 #ifdef PXM_D5_TRACE
   if (threadIdx.x == 0 && g_dft_trace) {
@@ -921,7 +952,8 @@ static int pair_attr() {
   static std::atomic<uint64_t> done{0};
   return allow_dynamic_lds(done, {reinterpret_cast<const void*>(k_px2ring5<R0>), reinterpret_cast<const void*>(k_ring2px5<R0, false, false>),
                                   reinterpret_cast<const void*>(k_ring2px5<R0, true, false>), reinterpret_cast<const void*>(k_ring2px5<R0, false, true>),
-                                  reinterpret_cast<const void*>(k_ring2px5<R0, true, true>)});
+                                  reinterpret_cast<const void*>(k_ring2px5<R0, true, true>),
+                                  reinterpret_cast<const void*>(k_ring2px5<R0, true, true, true>)});
 }
 
 // ring sets (workgroups) along the rings: one ring set of 8 / r0 rings each, or a ring pair of the exact-length unit
@@ -950,7 +982,9 @@ static int pair_ring2px_r(const DftPlan& p, const double* G, int ncol, const PxO
   // (the fp64-noise instantiations only where the launch draws Philox noise in double precision)
   const bool n64 = out.X && !out.noise && out.noise64;
   if (ring_out) {
-    if (n64) hipLaunchKernelGGL((k_ring2px5<R0, true, true>), grid, block, D5_LDS, st, da, Gw, ncol, out, C);
+    // (the stock update of the fp64 stream on the instantiation that holds its mode at compile time)
+    if (n64 && p.stock && dft_step_is_stock(out)) hipLaunchKernelGGL((k_ring2px5<R0, true, true, true>), grid, block, D5_LDS, st, da, Gw, ncol, out, C);
+    else if (n64) hipLaunchKernelGGL((k_ring2px5<R0, true, true>), grid, block, D5_LDS, st, da, Gw, ncol, out, C);
     else hipLaunchKernelGGL((k_ring2px5<R0, true, false>), grid, block, D5_LDS, st, da, Gw, ncol, out, C);
   } else {
     if (n64) hipLaunchKernelGGL((k_ring2px5<R0, false, true>), grid, block, D5_LDS, st, da, Gw, ncol, out, C);
@@ -1063,9 +1097,11 @@ int dft_group_create(const std::vector<const DftPlan*>& plans, const std::vector
   out->n = (int)v.size();
   out->all = v.size() == plans.size();
   out->blocks = b0;
+  out->stock = plans[order[0]]->stock;  // (PXM_DFT_STOCK, read by make_dft_plan: the same for every scale of a plan)
   if (int rc = dev_table(&out->d, v, "DFT group entries")) return rc;
   static std::atomic<uint64_t> lds_done{0};
   return allow_dynamic_lds(lds_done, {reinterpret_cast<const void*>(k_ring2px_group5<true, false>), reinterpret_cast<const void*>(k_ring2px_group5<true, true>),
+                                      reinterpret_cast<const void*>(k_ring2px_group5<true, true, true>),
                                       reinterpret_cast<const void*>(k_ring2px_group5<false, false>), reinterpret_cast<const void*>(k_ring2px_group5<false, true>),
                                       reinterpret_cast<const void*>(k_px2ring_group5)});
 }
@@ -1085,7 +1121,10 @@ int dft_group_launch(const DftGroupList& g, double* ws, int ncol, const PxOut& o
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (prof) prof->next(prof->dft, &ev0, &ev1, bytes, 0.0);
   const Dft5Group* ents = reinterpret_cast<const Dft5Group*>(g.d);
-  if (out.X && !out.noise && out.noise64)
+  if (g.stock && out.noise64 && dft_step_is_stock(out))  // the stock update: its mode is part of the instantiation
+    hipExtLaunchKernelGGL((k_ring2px_group5<true, true, true>), dim3(g.blocks), dim3(128 * D5_RMAX), D5_LDS, st, ev0, ev1, 0,
+                          ents, g.n, ws, ncol, out, C);
+  else if (out.X && !out.noise && out.noise64)
     hipExtLaunchKernelGGL((k_ring2px_group5<true, true>), dim3(g.blocks), dim3(128 * D5_RMAX), D5_LDS, st, ev0, ev1, 0,
                           ents, g.n, ws, ncol, out, C);
   else

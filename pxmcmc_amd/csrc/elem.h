@@ -36,6 +36,11 @@ __device__ inline double chain_step_real(double X, double px, double g, double w
   const double r = delta / lmda;
   return (1 - r) * X + r * px - delta * g + sqrt(2 * delta) * w;
 }
+// the same step with its two chain-independent factors r = d / l and s = sqrt(2 d) formed by the caller, once for all its
+// elements (the division and the square root are ~25 fp64 operations): the same operations on X, px, g and w in the same order
+__device__ __forceinline__ double chain_step_real_rs(double X, double px, double g, double w, double delta, double r, double s) {
+  return (1 - r) * X + r * px - delta * g + s * w;
+}
 __device__ inline double2 chain_step_cplx(double2 X, double2 px, double2 g, double2 w, double delta, double lmda) {
   return double2{chain_step_real(X.x, px.x, g.x, w.x, delta, lmda), chain_step_real(X.y, px.y, g.y, w.y, delta, lmda)};
 }

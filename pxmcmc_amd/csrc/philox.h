@@ -167,6 +167,69 @@ __device__ inline NormalPair box_muller_f64_tab(double u1, double u2, const doub
   const double S = cs.y + fma(cs.x, sa, cs.y * cm1);
   return NormalPair{g * C, g * S};
 }
+// The same evaluation in two halves -- operation for operation, so the deviates are the same bits (tests/test_gpu_dft_stock.py
+// holds the kernels that use it to the ones that call box_muller_f64_tab): what depends on the uniforms alone up to the two
+// table look-ups, and the arithmetic on what they return.  A kernel that draws several elements per lane may issue the
+// look-ups of its next element before the arithmetic of the current one.
+struct BoxMullerLook {
+  double m;        // mantissa of u1, [0.5, 1)
+  int ex;          // exponent of u1
+  double a;        // angle residual, |a| <= pi / 256
+  double2 lt, cs;  // {rc_j, 2 ln rc_j} and {cos, sin}(2 pi k / 256)
+};
+__device__ inline BoxMullerLook box_muller_f64_tab_look(double u1, double u2, const double2* logt, const double2* sct) {
+  BoxMullerLook L;
+  L.ex = __builtin_amdgcn_frexp_exp(u1);
+  L.m = __builtin_amdgcn_frexp_mant(u1);  // [0.5, 1)
+  const int j = min(max((int)__builtin_rint(L.m * 256.0), NOISE_LOG_J0), 256);  // (clamped: see box_muller_f64_tab)
+  L.lt = logt[j - NOISE_LOG_J0];
+  const double t = 256.0 * u2;
+  const double k = __builtin_rint(t);
+  L.a = (t - k) * 0.024543692606170259675;  // 2 pi / 256
+  L.cs = sct[(int)k & 255];
+  return L;
+}
+// PIN: the addend constants of the fused multiply-adds (they need a vector register each; 0.5 and 1 are inline operands)
+// are formed where they are used.  Inside a loop around a kernel body the compiler otherwise hoists them in front of the
+// loop and, at the 128-register budget of the fused phi-DFT kernels, spills them there.  Same values: same deviates.
+template <bool PIN>
+__device__ __forceinline__ double box_muller_const(double c) {
+  if constexpr (PIN) asm volatile("" : "+s"(c));
+  return c;
+}
+template <bool PIN>
+__device__ inline NormalPair box_muller_f64_tab_finish(const BoxMullerLook& L) {
+  const double m = L.m;
+  const double2 lt = L.lt;
+  const double r = fma(m, lt.x, -1.0);
+  double p = 1.0 / 7.0;
+  p = fma(p, r, box_muller_const<PIN>(-1.0 / 6.0));
+  p = fma(p, r, box_muller_const<PIN>(1.0 / 5.0));
+  p = fma(p, r, box_muller_const<PIN>(-0.25));
+  p = fma(p, r, box_muller_const<PIN>(1.0 / 3.0));
+  p = fma(p, r, -0.5);
+  p = fma(p, r, 1.0);
+  p *= r;  // log1p(r)
+  const double e = (double)L.ex;
+  // -2 ln u1 = -2 e ln 2 + 2 ln rc - 2 log1p(r)   (ln 2 split so that e * hi is exact for |e| <= 54)
+  double x = fma(-2.0, p, fma(e, -2.0 * 0.693147180369123816490, fma(e, -2.0 * 1.90821492927058770002e-10, lt.y)));
+  x = fmax(x, 1e-300);  // u1 == 1.0: x = -0.0 (see box_muller_f64_poly)
+  double h = __builtin_amdgcn_rsq(x);
+  double g = x * h;
+  h *= 0.5;
+  const double rr = fma(-h, g, 0.5);
+  g = fma(g, rr, g);
+  g = fma(fma(-g, g, x), h, g);  // sqrt(x)
+  const double a = L.a;
+  const double2 cs = L.cs;
+  const double a2 = a * a;
+  const double q = fma(fma(a2, -1.0 / 5040.0, box_muller_const<PIN>(1.0 / 120.0)), a2, box_muller_const<PIN>(-1.0 / 6.0));
+  const double sa = fma(a * a2, q, a);                                                              // sin a
+  const double cm1 = fma(fma(a2, -1.0 / 720.0, box_muller_const<PIN>(1.0 / 24.0)), a2, -0.5) * a2;  // cos a - 1
+  const double C = cs.x + fma(-cs.y, sa, cs.x * cm1);
+  const double S = cs.y + fma(cs.x, sa, cs.y * cm1);
+  return NormalPair{g * C, g * S};
+}
 __device__ inline NormalPair box_muller_f64_tab(double u1, double u2) {
   return box_muller_f64_tab(u1, u2, reinterpret_cast<const double2*>(&NOISE_LOG_TAB[0][0]), reinterpret_cast<const double2*>(&NOISE_SINCOS_TAB[0][0]));
 }
@@ -208,6 +271,17 @@ __device__ inline NormalPair normal_pair_from_bits_tabs(const uint4 c, const dou
   const uint64_t a = (((uint64_t)c.y << 32) | c.x) >> 11;
   const uint64_t b = (((uint64_t)c.w << 32) | c.z) >> 11;
   return box_muller_f64_tab(((double)a + 0.5) * 0x1.0p-53, ((double)b + 0.5) * 0x1.0p-53, logt, sct);
+}
+// ... and that step in its two halves (box_muller_f64_tab_look / _finish)
+__device__ inline BoxMullerLook normal_look_from_bits(const uint4 c, const double2* logt, const double2* sct) {
+  const uint64_t a = (((uint64_t)c.y << 32) | c.x) >> 11;
+  const uint64_t b = (((uint64_t)c.w << 32) | c.z) >> 11;
+  return box_muller_f64_tab_look(((double)a + 0.5) * 0x1.0p-53, ((double)b + 0.5) * 0x1.0p-53, logt, sct);
+}
+__device__ inline NormalPair normal_pair_from_bits_poly(const uint4 c) {  // (-DPXM_NOISE_F64_POLY builds)
+  const uint64_t a = (((uint64_t)c.y << 32) | c.x) >> 11;
+  const uint64_t b = (((uint64_t)c.w << 32) | c.z) >> 11;
+  return box_muller_f64_poly(((double)a + 0.5) * 0x1.0p-53, ((double)b + 0.5) * 0x1.0p-53);
 }
 // the fp64 form with the caller's copies of the Box-Muller tables (same deviates, bit for bit)
 __device__ inline NormalPair philox_normal_pair_tabs(uint64_t seed, uint64_t chain, uint64_t index, uint64_t iter, const double2* logt,

@@ -164,6 +164,9 @@ struct DftPlan {
   // of the wave-pair wait of the pair unit (PXM_DEBUG_PAIR_SYNC_LIMIT, read at plan creation: 0 forces an expiry)
   unsigned* d_status = nullptr;
   unsigned spin_limit = 1u << 18;
+  // the fused step's stock launches (dft_step_is_stock) take the STOCK kernel instantiations; PXM_DFT_STOCK=0 at plan
+  // creation keeps the generic ones (A/B runs, the identity test)
+  bool stock = true;
 };
 // bit of a plan's status word (pxm_wav_status / pxm_sht_status); bit 0 is unused
 enum { PXM_STATUS_PAIR_SYNC_BIT = 2 };
@@ -225,6 +228,15 @@ struct PxOut {  // ring2px output: plain image, or the fused MYULA update of a c
   const double* gw = nullptr;
 };
 
+// The stock MYULA update of the fused rings -> X' -> rings step: state and thresholds in place (X, vector T), Philox noise,
+// two real chains per slot from an even first chain (one Philox pair per slot), the device-resident iteration addend of
+// graph replay, and neither residual nor gather.  The fused launchers of the pair unit (dft_wave.hip) run such a launch on
+// kernel instantiations that hold all of this as compile-time facts (template parameter STOCK); every other launch takes
+// the generic instantiations.  mode 2: PXM_MODE_REAL_PAIRS (update.h).
+inline bool dft_step_is_stock(const PxOut& o) {
+  return o.X && o.T && !o.noise && o.mode == 2 && !(o.chain0 & 1) && o.iter_dev && !o.rdata && !o.rinvcov && !o.gidx && !o.gw;
+}
+
 // grouped launches of a wavelet plan's member scales (dft_wave.hip): one grid for every scale on the pair unit
 struct DftGroupList {
   void* d = nullptr;  // device array of per-scale descriptors
@@ -234,6 +246,7 @@ struct DftGroupList {
   int64_t ring_end = 0; // largest ring0 + L n over the entries: the launches require it <= chain_stride
   std::vector<char> member;  // per scale: its rings <-> pixels launches are part of this group
   bool all = false;          // every scale is a member (needed by the fused rings -> X' -> rings step)
+  bool stock = true;         // stock launches take the STOCK instantiation (PXM_DFT_STOCK is not 0 at creation)
 };
 int dft_group_create(const std::vector<const DftPlan*>& plans, const std::vector<int64_t>& g_off,
                      const std::vector<int64_t>& ring0, int ncol, const double* ws_base,

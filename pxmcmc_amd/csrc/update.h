@@ -212,4 +212,74 @@ __device__ __forceinline__ double2 px_update(const PxOut& o, double2 x, double T
   return chain_step_cplx(x, px, g, w, o.delta, o.lmda);
 }
 
+// ---- the stock update as compile-time facts (dft_step_is_stock, sht_core.h) -----------------------------------------
+// Kernels instantiated with STOCK read none of the mode fields of PxOut: the update is the real-pair one, the noise of a
+// slot is ONE Philox pair of the real stream (even first chain).
+static_assert(PXM_MODE_REAL_PAIRS == 2, "dft_step_is_stock (sht_core.h) names the real-pair mode by its value");
+
+// a double that is the same in every lane, as a scalar
+__device__ __forceinline__ double px_uniform(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+// The STOCK epilogue of the pair unit's fused bodies: prox + MYULA update of FOUR elements of a lane, two real chains per
+// slot with one Philox pair of the fp64 stream per slot.  The elements (ring values, not yet conjugated) stand in LDS at
+// park[64 u]; the updated elements go to out.f and back to park[64 u].  Element u is e0 + ES u of the plan's coefficient
+// vector (ce0: the same inside the chain's state); ok[u] false: no element -- a zero is parked and the operand loads re-read
+// element e0 + zoff (the ring's element 0), dropped.
+//   * The operand loads go first and the Philox bits of the four elements -- independent integer chains -- are formed
+//     while they are in flight.
+//   * The fp64 Box-Muller step then runs on TWO elements at a time (their operations interleave: the look-ups and the
+//     dependent chains of one hide behind the other), and the two are FINISHED -- update, stores -- before the next two
+//     start: the deviates of finished elements are never held beside the registers of the evaluation.
+//   * d / l and sqrt(2 d) of the step are formed once per call, as scalars: behind the per-element branches the compiler
+//     forms them again for every element (a division and a square root, ~25 fp64 operations).
+// Every element sees the operations of px_update / px_noise_philox_t<true> in their order: the same bits
+// (tests/test_gpu_dft_stock.py).  logt / sct: the Box-Muller tables (philox.h), the global ones or a kernel's LDS copies.
+template <int ES>
+__device__ __forceinline__ void px_stock_update4(const PxOut& out, const bool (&ok)[4], int64_t e0, int64_t ce0, int zoff, int ch_s,
+                                                 uint64_t it, double2* park, const double2* logt, const double2* sct) {
+  const double delta = out.delta, r_dl = px_uniform(out.delta / out.lmda), s_2d = px_uniform(sqrt(2 * out.delta));
+  double2 xs[4];
+  double Ts[4];
+  int eo[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) eo[u] = ok[u] ? ES * u : zoff;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) xs[u] = reinterpret_cast<const double2*>(out.X)[ce0 + eo[u]];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) Ts[u] = out.T[e0 + eo[u]];
+  __builtin_amdgcn_sched_barrier(0);
+  uint4 pbits[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) pbits[u] = philox_bits(out.seed + PXM_PAIR_TWEAK, (out.chain0 >> 1) + ch_s, (uint64_t)(e0 + ES * u), it);
+  __builtin_amdgcn_sched_barrier(0);
+  auto finish_elem = [&](int u, const NormalPair& q) {
+    double2 xn{0.0, 0.0};
+    if (ok[u]) {
+      const double2 xv = park[64 * u];
+      xn = double2{chain_step_real_rs(xs[u].x, soft_real(xs[u].x, Ts[u]), xv.x, q.z0, delta, r_dl, s_2d),
+                   chain_step_real_rs(xs[u].y, soft_real(xs[u].y, Ts[u]), -xv.y, q.z1, delta, r_dl, s_2d)};
+      reinterpret_cast<double2*>(out.f)[ce0 + ES * u] = xn;
+    }
+    park[64 * u] = xn;
+  };
+#pragma unroll
+  for (int u = 0; u < 4; u += 2) {
+#if defined(PXM_NOISE_F64_POLY)
+    (void)logt, (void)sct;
+    const NormalPair qa = normal_pair_from_bits_poly(pbits[u]), qb = normal_pair_from_bits_poly(pbits[u + 1]);
+#else
+    const BoxMullerLook la = normal_look_from_bits(pbits[u], logt, sct), lb = normal_look_from_bits(pbits[u + 1], logt, sct);
+    const NormalPair qa = box_muller_f64_tab_finish<true>(la), qb = box_muller_f64_tab_finish<true>(lb);
+#endif
+    __builtin_amdgcn_sched_barrier(0);
+    finish_elem(u, qa);
+    finish_elem(u + 1, qb);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 }  // namespace pxm

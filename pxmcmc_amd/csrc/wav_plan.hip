@@ -374,6 +374,13 @@ int pxm_wav_exact_dft_scales(pxm_wav_plan_t p) {
   return p->dft_group.d ? p->dft_group.n_pfa : 0;
 }
 
+// 1 when the grouped fused launch of this plan takes the STOCK kernel instantiation for stock updates (sht_core.h:
+// dft_step_is_stock), 0 when the launch is not grouped or PXM_DFT_STOCK=0 at creation
+int pxm_wav_dft_stock(pxm_wav_plan_t p) {
+  PXM_REQUIRE(p, "pxm_wav_dft_stock: null plan");
+  return (p->dft_group.d && p->dft_group.stock) ? 1 : 0;
+}
+
 int64_t pxm_wav_table_bytes(pxm_wav_plan_t p, int op) {
   if (!p || op < 0 || op > 1) return -1;
   return p->table_bytes[op];

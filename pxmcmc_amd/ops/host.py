@@ -52,6 +52,19 @@ def dft_geometry(L):
     return (DFT_UNITS[out[0]], int(out[1]), int(out[2]), int(out[3]), int(out[4]), bool(out[5]))
 
 
+DFT_STEP_FIELDS = ("X", "T", "noise", "iter_dev", "rdata", "rinvcov", "gidx", "gw")  # bits of pxm_host_dft_step_is_stock
+
+
+def dft_step_is_stock(fields, mode, chain0):
+    """whether a fused rings -> X' -> rings launch that carries the optional operands named in ``fields`` (names of
+    DFT_STEP_FIELDS) with update mode ``mode`` (PXM_MODE_*) and first chain ``chain0`` is the stock MYULA update, which the
+    pair unit of the phi-DFT stage runs on its STOCK kernel instantiations (csrc/sht_core.h: dft_step_is_stock)"""
+    bits = 0
+    for f in fields:
+        bits |= 1 << DFT_STEP_FIELDS.index(f)
+    return bool(check(lib.pxm_host_dft_step_is_stock(bits, int(mode), int(chain0))))
+
+
 def noise_bits():
     """32: the precision of the Box-Muller step of the device noise stream WITHOUT the flag (the samplers of mcmc.py pass
     the flag by default: ``noise_bits=64``); every noise-drawing call takes

@@ -381,6 +381,11 @@ class WavPlan(_WaveletPlan):
         """scales whose 511-point rings the fused step transforms with the exact-length unit (csrc/dft_pfa.h); 0 = Bluestein"""
         return int(check(lib.pxm_wav_exact_dft_scales(self._h)))
 
+    def dft_stock(self):
+        """whether the fused step runs stock MYULA updates (ops.dft_step_is_stock) on the STOCK kernel instantiation of the
+        phi-DFT stage; False with PXM_DFT_STOCK=0 at creation"""
+        return bool(check(lib.pxm_wav_dft_stock(self._h)))
+
     # ---- weak-lensing measurement fused with the synthesis (pxm_wav_wl_*) ----
     def wl_attach(self, pix2data, weight, ndata):
         """pix2data: int32 [npix] pixel -> index in the masked data vector (< 0 masked) or None; weight: float64
