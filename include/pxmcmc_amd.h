@@ -161,11 +161,28 @@ int64_t pxm_sht_table_bytes(pxm_sht_plan_t plan, int op /*0 inv,1 fwd,2 inv_adj,
  *   pxm_dft_px2ring  G[m][t][c] = sum_p f[c][t][p] exp(-i m phi_p), phi_p = 2 pi p / (2L-1); for t < L every column is written:
  *                    c >= C with zeros; rows t >= L are left as they are
  *   pxm_dft_ring2px  f[c][t][p] = sum_m G[m][t][c] exp(+i m phi_p); rows t >= L and columns c >= C of G never enter a result
- * pxm_dft_status reads the plan's status word as pxm_sht_status does. */
+ * pxm_dft_status reads the plan's status word as pxm_sht_status does.
+ * The _ex pair runs the same launches with the pixel side and the ring array a weak-lensing or wavelet plan gives them:
+ *   G      : [2L-1][Rp][ncol / 2] c128 with ncol one of 2, 4, 6, 8 or a multiple of 16 doubles per row, C <= ncol / 2
+ *   f      : [C][chain_stride] c128; the image of a chain is its elements [ring0, ring0 + L (2L-1))
+ *   data, invcov (px2ring only, together): G <- rings of invcov .* (f - data); [chain_stride] each, read at the image's
+ *            own offsets, invcov real or (invcov_complex) complex
+ *   gidx   : int32 [L (2L-1)], pixel -> entry of the data vector, < 0 masked; then f (and data, invcov) are data-space
+ *            arrays with chain_stride == ndata >= 1 and ring0 == 0: px2ring reads pixel e from entry gidx[e] (masked: zero),
+ *            ring2px writes pixel e to entry gidx[e] (masked: dropped; entries no pixel maps to are left as they are).
+ *            Every entry must be < ndata: the caller's duty (ops.DftPlan checks it on the device)
+ *   gw     : float64 [ndata] weight of the entry a pixel maps to, or null (needs gidx)
+ * Every other combination is refused before a launch. */
 int pxm_dft_plan_create(int L, int max_chains, pxm_dft_plan_t* plan);
 int pxm_dft_plan_destroy(pxm_dft_plan_t plan);
 int pxm_dft_px2ring(pxm_dft_plan_t plan, const void* f, void* G, int C, pxm_stream_t stream);
 int pxm_dft_ring2px(pxm_dft_plan_t plan, const void* G, void* f, int C, pxm_stream_t stream);
+int pxm_dft_px2ring_ex(pxm_dft_plan_t plan, const void* f, int64_t chain_stride, int64_t ring0, const void* data, const void* invcov,
+                       int invcov_complex, const int32_t* gidx, const double* gw, int64_t ndata, void* G, int ncol, int C,
+                       pxm_stream_t stream);
+int pxm_dft_ring2px_ex(pxm_dft_plan_t plan, const void* G, int ncol, void* f, int64_t chain_stride, int64_t ring0, const void* data,
+                       const void* invcov, int invcov_complex, const int32_t* gidx, const double* gw, int64_t ndata, int C,
+                       pxm_stream_t stream);
 int pxm_dft_status(pxm_dft_plan_t plan, int clear, pxm_stream_t stream);
 
 /* ---- the ring-GEMM stage on its own -------------------------------------------------------------------------------

@@ -82,6 +82,8 @@ SIGNATURES = {
     "pxm_dft_plan_destroy": (c_int, [c_vp]),
     "pxm_dft_px2ring": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
     "pxm_dft_ring2px": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_dft_px2ring_ex": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp]),
+    "pxm_dft_ring2px_ex": (c_int, [c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_vp]),
     "pxm_dft_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_gemm_plan_create": (c_int, [c_int, c_int, c_int, c_vp, c_int, C.POINTER(c_vp)]),
     "pxm_gemm_plan_destroy": (c_int, [c_vp]),

@@ -1,6 +1,7 @@
 // The phi-DFT stage as a plan of its own (one DftPlan and a status word: no ring tables, no task lists, no workspace) and
 // the host report of the unit selection.  The entry points run the launches an SHT plan at the same bandlimit runs, on
-// the caller's ring array.
+// the caller's ring array; the _ex pair runs the same launches with the pixel side (residual, pixel -> data map, an image
+// inside a longer chain) and the ring array's column count a weak-lensing or wavelet plan gives them.
 #include "plan_common.h"
 
 #include <memory>
@@ -90,6 +91,60 @@ int pxm_dft_ring2px(pxm_dft_plan_t p, const void* G, void* f, int C, pxm_stream_
   PXM_REQUIRE(((uintptr_t)G & 15) == 0, "pxm_dft_ring2px: the ring array must be 16-byte aligned");
   note_stream((hipStream_t)s);
   return launch_ring2px(p->dft, (const double*)G, p->ncol, image_out(p->L, f), C, (hipStream_t)s);
+}
+
+}  // extern "C"
+
+// The pixel side of the _ex entry points and the launch's column count: every refusal, before any launch.  to_rings: the
+// call is pxm_dft_px2ring_ex (the residual is fused into the reads of that direction only).
+static int px_side_check(pxm_dft_plan_t p, const void* G, int ncol, int C, int64_t chain_stride, int64_t ring0, const void* data,
+                         const void* invcov, const int32_t* gidx, const double* gw, int64_t ndata, bool to_rings, const std::string& who) {
+  PXM_REQUIRE(ncol == 2 || ncol == 4 || ncol == 6 || ncol == 8 || (ncol >= 16 && ncol % 16 == 0),
+              who + ": ncol must be 2, 4, 6, 8 or a multiple of 16 (the ring arrays the plans make)");
+  PXM_REQUIRE(C <= ncol / 2, who + ": C chains need ncol >= 2 C");
+  PXM_REQUIRE(((uintptr_t)G & 15) == 0, who + ": the ring array must be 16-byte aligned");
+  PXM_REQUIRE((data == nullptr) == (invcov == nullptr), who + ": data and invcov come together");
+  PXM_REQUIRE(to_rings || !data, who + ": the residual (data, invcov) is fused into pixels -> rings only");
+  PXM_REQUIRE(gidx || !gw, who + ": a weight gw needs the pixel -> data map gidx");
+  const int64_t P = (int64_t)p->L * (2 * p->L - 1);
+  if (gidx) {
+    PXM_REQUIRE(ring0 == 0, who + ": a pixel -> data map needs ring0 == 0");
+    PXM_REQUIRE(ndata >= 1, who + ": a pixel -> data map needs ndata >= 1");
+    PXM_REQUIRE(chain_stride == ndata, who + ": with a pixel -> data map the chains are ndata apart");
+  } else {
+    PXM_REQUIRE(ring0 >= 0, who + ": ring0 must be >= 0");
+    PXM_REQUIRE(ring0 <= chain_stride && P <= chain_stride - ring0, who + ": the image [ring0, ring0 + L (2L-1)) must lie inside a chain");
+  }
+  return 0;
+}
+
+extern "C" {
+
+int pxm_dft_px2ring_ex(pxm_dft_plan_t p, const void* f, int64_t chain_stride, int64_t ring0, const void* data, const void* invcov,
+                       int invcov_complex, const int32_t* gidx, const double* gw, int64_t ndata, void* G, int ncol, int C, pxm_stream_t s) {
+  if (int rc = plan_check(p, f, G, C, "pxm_dft_px2ring_ex")) return rc;
+  if (int rc = px_side_check(p, G, ncol, C, chain_stride, ring0, data, invcov, gidx, gw, ndata, true, "pxm_dft_px2ring_ex")) return rc;
+  PxIn in = image_in(p->L, f, data, invcov, invcov_complex);
+  in.chain_stride = chain_stride;
+  in.ring0 = ring0;
+  in.gidx = gidx;
+  in.gw = gw;
+  note_stream((hipStream_t)s);
+  return launch_px2ring(p->dft, in, (double*)G, ncol, C, (hipStream_t)s);
+}
+
+int pxm_dft_ring2px_ex(pxm_dft_plan_t p, const void* G, int ncol, void* f, int64_t chain_stride, int64_t ring0, const void* data,
+                       const void* invcov, int invcov_complex, const int32_t* gidx, const double* gw, int64_t ndata, int C, pxm_stream_t s) {
+  (void)invcov_complex;
+  if (int rc = plan_check(p, G, f, C, "pxm_dft_ring2px_ex")) return rc;
+  if (int rc = px_side_check(p, G, ncol, C, chain_stride, ring0, data, invcov, gidx, gw, ndata, false, "pxm_dft_ring2px_ex")) return rc;
+  PxOut out = image_out(p->L, f);
+  out.chain_stride = chain_stride;
+  out.ring0 = ring0;
+  out.gidx = gidx;
+  out.gw = gw;
+  note_stream((hipStream_t)s);
+  return launch_ring2px(p->dft, (const double*)G, ncol, out, C, (hipStream_t)s);
 }
 
 int pxm_dft_status(pxm_dft_plan_t p, int clear, pxm_stream_t stream) {

@@ -89,6 +89,20 @@ def _data_invcov(data, invcov, n, dtype, preds=None):
     return d, ic
 
 
+def _pixel_map(gidx, npix, ndata, length_msg, range_msg):
+    """a pixel -> data map (an entry < 0: masked pixel) -> contiguous int32 [npix] on the GPU whose every entry is < ndata.
+    The range is checked here, on the device (one max() reduction, one synchronisation): the kernels index the data vector
+    with the entries and the C-ABI cannot see them."""
+    if not isinstance(gidx, torch.Tensor):
+        gidx = torch.from_numpy(np.ascontiguousarray(np.asarray(gidx)))
+    if gidx.numel() != npix:
+        raise ValueError(length_msg)
+    gidx = gidx.to(device=device()).reshape(-1)
+    if npix and int(gidx.max()) >= int(ndata):  # (in the caller's integer type: before the narrowing to int32 can wrap it)
+        raise ValueError(range_msg)
+    return gidx.to(dtype=torch.int32).contiguous()
+
+
 def _chain_vector(t, C_, dev, dtypes, msg, optional=False):
     """a per-chain device vector the kernel reads or updates in place: contiguous [C] of one of ``dtypes`` on ``dev``"""
     if t is None and optional:

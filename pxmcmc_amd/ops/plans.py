@@ -10,8 +10,8 @@ import torch
 
 from .._lib import STATUS_PAIR_SYNC, PxmError, check, lib, require_gpu
 from .host import gemm_report
-from ._args import (_CPLX, _REAL, _batched, _data_invcov, _dev_tensors, _gemm_sides, _nf, _noise_args, _p, _pair_noise_args, _result, _stream, _vecT, as_device,
-                    device)
+from ._args import (_CPLX, _REAL, _batched, _data_invcov, _dev_tensors, _gemm_sides, _nf, _noise_args, _p, _pair_noise_args, _pixel_map, _result, _stream,
+                    _vecT, as_device, device)
 
 
 def raise_on_status(status, what):
@@ -114,7 +114,9 @@ class DftPlan(_Plan):
     """The phi-DFT stage of the transforms on its own (include/pxmcmc_amd.h, pxm_dft_*): the rings <-> pixels launches of
     an SHT plan at bandlimit L without its ring tables.  Images are [C, L, 2L-1]; ``rings`` / ``pixels`` speak [C, L, 2L-1]
     (chain, ring t, order m = -(L-1) .. L-1) and permute with torch; ``rings_raw`` / ``pixels_raw`` work on the internal
-    ring array [2L-1, Rp, Cp] (``ring_array``), padding rows and columns included."""
+    ring array [2L-1, Rp, Cp] (``ring_array``), padding rows and columns included; ``rings_raw_ex`` / ``pixels_raw_ex`` run
+    the same launches with the pixel side (residual, pixel -> data map and weight, an image inside a longer chain) and the
+    narrow ring arrays a weak-lensing or wavelet plan gives them."""
 
     def __init__(self, L, max_chains=1):
         require_gpu()
@@ -155,6 +157,49 @@ class DftPlan(_Plan):
             raise ValueError("more chains than the plan was created for")
         out = _result(out, (int(C_), self.L, self.n), _CPLX, G.device, "out= buffer has the wrong shape / dtype / layout")
         check(lib.pxm_dft_ring2px(self._h, _p(G), _p(out), int(C_), _stream()))
+        return out
+
+    # ---- the same launches with the pixel side and the ring arrays of the weak-lensing and wavelet plans (pxm_dft_*_ex) ----
+    def _px_side(self, who, f, G, gidx, gw, data=None, invcov=None):
+        """the arguments of an _ex launch.  f: contiguous complex128 [C, chain_stride] device tensor (with ``gidx``: data
+        space, chain_stride = ndata); G: contiguous complex128 [2L-1, Rp, ncol / 2] device tensor; ``gidx``: pixel -> entry
+        of a chain (< 0: masked), every entry checked on the device to be < ndata; ``gw``, ``data``, ``invcov``: one entry
+        per element of a chain.  -> (ncol, data, invcov, gidx, gw)"""
+        cols = G.shape[2] if isinstance(G, torch.Tensor) and G.dim() == 3 else 0
+        _dev_tensors(who, f"G must be a contiguous complex128 [{self.n}, {self.Rp}, ncol / 2] device tensor", (G, _CPLX, (self.n, self.Rp, cols)))
+        chains, stride = tuple(f.shape) if isinstance(f, torch.Tensor) and f.dim() == 2 else (0, 0)
+        _dev_tensors(who, "the pixel side must be a contiguous complex128 [C, chain_stride] device tensor", (f, _CPLX, (chains, stride)))
+        if not 1 <= f.shape[0] <= self.max_chains:
+            raise ValueError("more chains than the plan was created for")
+        if (data is None) != (invcov is None):
+            raise ValueError(f"{who}: data and invcov come together")
+        if data is not None:
+            data, invcov = _data_invcov(data, invcov, stride, _CPLX, preds=f)
+        if gidx is not None:
+            gidx = _pixel_map(gidx, self.L * self.n, stride, f"{who}: gidx must have one entry per pixel", f"{who}: gidx holds an index >= ndata")
+        if gw is not None:
+            gw = as_device(gw, _REAL).reshape(-1)
+            if gw.numel() != stride:
+                raise ValueError(f"{who}: gw must have one entry per datum")
+        return 2 * cols, data, invcov, gidx, gw
+
+    def rings_raw_ex(self, f, G, *, ring0=0, data=None, invcov=None, gidx=None, gw=None):
+        """``rings_raw`` of the image at the elements [ring0, ring0 + L (2L-1)) of every chain of ``f`` [C, chain_stride], or
+        with ``gidx`` of the image whose pixel e is entry gidx[e] of a chain of the data-space ``f`` [C, ndata] (masked:
+        zero) times gw[gidx[e]]; with ``data`` / ``invcov`` (one entry per element of a chain) of invcov .* (f - data).  G:
+        [2L-1, Rp, ncol / 2] with ncol = 2, 4, 6, 8 or a multiple of 16; returns G"""
+        ncol, d, ic, gi, w = self._px_side("rings_raw_ex", f, G, gidx, gw, data, invcov)
+        check(lib.pxm_dft_px2ring_ex(self._h, _p(f), f.shape[1], int(ring0), _p(d), _p(ic), int(ic.is_complex()) if ic is not None else 0,
+                                     _p(gi), _p(w), f.shape[1] if gi is not None else 0, _p(G), ncol, f.shape[0], _stream()))
+        return G
+
+    def pixels_raw_ex(self, G, out, *, ring0=0, gidx=None, gw=None):
+        """``pixels_raw`` of the chains c < C into the elements [ring0, ring0 + L (2L-1)) of every chain of ``out``
+        [C, chain_stride], or with ``gidx`` pixel e into entry gidx[e] of a chain of the data-space ``out`` [C, ndata], times
+        gw[gidx[e]] (masked pixels are dropped); every other element of ``out`` is left as it is; returns out"""
+        ncol, _, _, gi, w = self._px_side("pixels_raw_ex", out, G, gidx, gw)
+        check(lib.pxm_dft_ring2px_ex(self._h, _p(G), ncol, _p(out), out.shape[1], int(ring0), None, None, 0, _p(gi), _p(w),
+                                     out.shape[1] if gi is not None else 0, out.shape[0], _stream()))
         return out
 
     def rings(self, f):
@@ -391,9 +436,8 @@ class WavPlan(_WaveletPlan):
         """pix2data: int32 [npix] pixel -> index in the masked data vector (< 0 masked) or None; weight: float64
         [ndata] (WeakLensing.inv_cov) or None.  The plan keeps the tensors alive."""
         if pix2data is not None:
-            pix2data = pix2data.to(device=device(), dtype=torch.int32).contiguous()
-            if pix2data.numel() != self.npix:
-                raise ValueError("pix2data must have one entry per pixel")
+            pix2data = _pixel_map(pix2data, self.npix, ndata, "pix2data must have one entry per pixel",
+                                  "wl_attach: pix2data holds an index >= ndata")
         if weight is not None:
             weight = as_device(weight, _REAL).reshape(-1)
             if weight.numel() != int(ndata):

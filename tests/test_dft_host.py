@@ -160,6 +160,107 @@ def dense(seed, *shape):
     return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
 
 
+# ---- the pixel side of the stage (tests/test_gpu_dft_px.py): masks, pixel -> data maps and integer-exact residual inputs ---------
+# one case per kernel body, at the smallest L where the body's edge cases exist
+PX_CASES = [("pair1", 5, {}), ("pair2", 35, {}), ("pair4", 67, {}), ("pair8", 129, {}), ("exact", 256, {}),
+            ("pair8", 256, {"PXM_DFT_PFA": "0"}), ("quad", 257, {}), ("quad", 300, {}), ("radix2", 9, NO_W), ("radix2", 513, {})]
+assert all(c in CASES for c in PX_CASES)
+PX_EXTRA = 7  # entries of the longer data vector that no pixel maps to
+
+
+@functools.lru_cache(maxsize=None)
+def px_mask(L):
+    """keep[t, p]: about 30 % of the pixels masked; ring 0 entirely masked (so is the image's first pixel: the entry a masked
+    element re-reads is not its own), ring L - 1 entirely kept, ring 1 masked at its first pixel and kept at its last, ring 2
+    the reverse"""
+    n = 2 * L - 1
+    keep = np.random.default_rng(9000 + L).random((L, n)) >= 0.3
+    keep[0, :], keep[L - 1, :] = False, True
+    keep[1, 0], keep[1, n - 1] = False, True
+    keep[2, 0], keep[2, n - 1] = True, False
+    keep.setflags(write=False)
+    return keep
+
+
+@functools.lru_cache(maxsize=None)
+def px_index_map(L, extra):
+    """(gidx int32 [L (2L-1)], ndata): the kept pixels onto [0, ndata) injectively through a random permutation -- not the
+    monotone map of a mask --, masked pixels -1; ndata = kept pixels + extra, so `extra` entries stay unreferenced"""
+    keep = px_mask(L).reshape(-1)
+    ndata = int(keep.sum()) + extra
+    gidx = np.full(keep.size, -1, dtype=np.int32)
+    gidx[keep] = np.random.default_rng(9100 + 8 * L + extra).permutation(ndata)[:int(keep.sum())]
+    gidx.setflags(write=False)
+    return gidx, ndata
+
+
+def px_integer_inputs(seed, C, N):
+    """f [C, N], data [N], invcov [N] complex and gw [N] real with integer components: f, data in [-2^10, 2^10], invcov in
+    [-2^8, 2^8] without a zero component, gw in {1, 2, 3, 5, 8}.  |f - data| <= 2^11 per component, a component of
+    invcov (f - data) is a sum of two products <= 2^19, times gw <= 2^23: every intermediate is an integer below 2^24, exact in
+    float64 in any order and with or without a fused multiply-add."""
+    rng = np.random.default_rng(seed)
+    ints = lambda lo, hi, *shape: rng.integers(lo, hi + 1, size=shape).astype(float)
+    nz = lambda *shape: ints(1, 256, *shape) * rng.choice([-1.0, 1.0], size=shape)
+    f = ints(-1024, 1024, C, N) + 1j * ints(-1024, 1024, C, N)
+    data = ints(-1024, 1024, N) + 1j * ints(-1024, 1024, N)
+    invcov = nz(N) + 1j * nz(N)
+    gw = rng.choice([1.0, 2.0, 3.0, 5.0, 8.0], size=N)
+    return f, data, invcov, gw
+
+
+PX_CHAINS = 5
+
+
+def px_integer_inputs_of(L, extra):
+    """the integer inputs of the pixel-side tests at bandlimit L: in pixel space (extra None) or in the data space of
+    px_index_map(L, extra)"""
+    N = L * (2 * L - 1) if extra is None else px_index_map(L, extra)[1]
+    return px_integer_inputs(9200 + 16 * L + (0 if extra is None else 1 + extra), PX_CHAINS, N)
+
+
+@pytest.mark.parametrize("case", PX_CASES, ids=case_id)
+def test_integer_residual_inputs_are_exact_in_float64(case):
+    """What the bit comparison of the complex residual rests on: for the inputs of every L of the pixel-side tests, pixel
+    space and both data vectors, gw (invcov (f - data)) evaluated in float64 equals the evaluation in Python integers, with
+    every intermediate below 2^24 -- so no order of the products and no contraction can change a bit."""
+    _, L, _ = case
+    for extra in (None, 0, PX_EXTRA):
+        f, data, invcov, gw = px_integer_inputs_of(L, extra)
+        assert f.shape == (PX_CHAINS, L * (2 * L - 1) if extra is None else px_index_map(L, extra)[1])
+        for a in (f, data, invcov):
+            assert (a.real == np.rint(a.real)).all() and (a.imag == np.rint(a.imag)).all()
+        assert (invcov.real != 0).all() and (invcov.imag != 0).all() and set(np.unique(gw)) <= {1.0, 2.0, 3.0, 5.0, 8.0}
+        assert max(np.abs(f.real).max(), np.abs(f.imag).max(), np.abs(data.real).max(), np.abs(data.imag).max()) <= 2 ** 10
+        assert max(np.abs(invcov.real).max(), np.abs(invcov.imag).max()) <= 2 ** 8
+        got = gw * (invcov * (f - data))  # float64, every chain
+
+        def evaluate(as_int):
+            fr, fi, dr, di = as_int(f.real), as_int(f.imag), as_int(data.real), as_int(data.imag)
+            wr, wi, g = as_int(invcov.real), as_int(invcov.imag), as_int(gw)
+            rr, ri = fr - dr, fi - di
+            terms = [wr * rr, wi * ri, wr * ri, wi * rr]
+            want = [g * (terms[0] - terms[1]), g * (terms[2] + terms[3])]
+            assert max(int(np.abs(t).max()) for t in terms + want) < 2 ** 24
+            assert (as_int(got.real) == want[0]).all() and (as_int(got.imag) == want[1]).all(), (case_id(case), extra)
+
+        evaluate(lambda a: a.astype(np.int64))  # every chain, in 64-bit integers (nothing near their range)
+        evaluate(lambda a: np.array([int(v) for v in a[..., :4096].reshape(-1)], dtype=object).reshape(a[..., :4096].shape))  # Python integers
+
+
+def test_pixel_masks_have_their_edge_cases():
+    for _, L, _ in PX_CASES:
+        keep, n = px_mask(L), 2 * L - 1
+        assert not keep[0].any() and keep[L - 1].all() and (L < 35 or 0.65 <= keep.mean() <= 0.75)
+        assert (keep[1, 0], keep[1, n - 1], keep[2, 0], keep[2, n - 1]) == (False, True, True, False)
+        for extra in (0, PX_EXTRA):
+            gidx, ndata = px_index_map(L, extra)
+            live = gidx[keep.reshape(-1)]
+            assert ndata == keep.sum() + extra and (gidx[~keep.reshape(-1)] == -1).all()
+            assert live.min() >= 0 and live.max() < ndata and len(np.unique(live)) == len(live)  # injective, in range
+            assert (np.diff(live) < 0).any()  # not the monotone map
+
+
 # ---- the model against numpy and the oracle ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [1, 3, 17, 63, 129, 511, 1025])
 def test_dft_ld_equals_numpy_fft(n):

@@ -269,6 +269,17 @@ def test_nine_chains(case, monkeypatch, impulse_model):
 
 
 # ---- check 6: round trip and adjointness, one case per unit ----------------------------------------------------------------------------
+def round_trip_taus(case, f, g):
+    """(tau_f, tau_i) of test_round_trip_and_dot: 4 eps x the model's measured ratio per direction, on the first rings of
+    chain 0 of the image f and of the rings g (both [C, L, 2L-1]); shared with tests/test_gpu_dft_px.py"""
+    L = case[1]
+    n, M, bins = 2 * L - 1, model_M(case), _order_index(L)
+    k = min(L, 8)  # rows that measure the model's ratio: the first rings of chain 0
+    xg = np.zeros((k, n), dtype=complex)
+    xg[:, bins] = g[0, :k]
+    return 4 * EPS * model_ratio(f[0, :k], M, -1), 4 * EPS * model_ratio(xg, M, +1)
+
+
 @pytest.mark.parametrize("case", ONE_PER_UNIT, ids=case_id)
 def test_round_trip_and_dot(case, monkeypatch):
     """pixels(rings(f)) = n f and <rings(f), g> = <f, pixels(g)>.  Bounds from check 3: with tau = 4 ratio eps per
@@ -276,14 +287,10 @@ def test_round_trip_and_dot(case, monkeypatch):
     n tau_f ||f||_2, and the way back adds tau_i ||rings||_2 = tau_i sqrt(n) ||f||_2: n (tau_f + tau_i) ||f||_2 bounds both.
     The dot products differ by at most sum over rings of tau_f ||f||_2 ||g||_1 + tau_i ||g||_2 ||f||_1."""
     unit, L, _ = case
-    n, M, bins, C = 2 * L - 1, model_M(case), _order_index(L), 3
+    n, C = 2 * L - 1, 3
     plan, _ = _plan(monkeypatch, case, 5)
     f, g = dense(7000 + L, C, L, n), dense(8000 + L, C, L, n)
-    k = min(L, 8)  # rows that measure the model's ratio: the first rings of chain 0
-    xg = np.zeros((k, n), dtype=complex)
-    xg[:, bins] = g[0, :k]
-    tau_f = 4 * EPS * model_ratio(f[0, :k], M, -1)
-    tau_i = 4 * EPS * model_ratio(xg, M, +1)
+    tau_f, tau_i = round_trip_taus(case, f, g)
     rings = plan.rings(f)
     back = _cpu(plan.pixels(rings))
     nf = np.linalg.norm(f, axis=-1)

@@ -47,6 +47,7 @@ def g():
     g.dft = ops.DftPlan(8, max_chains=C)  # images [c, 8, 15], ring array [15, 16, 8]
     g.G = g.dft.ring_array()
     g.dft_abi = lambda name, a, b, n: ops.check(getattr(_lib.lib, name)(g.dft._h, _p(a), _p(b), n, None))
+    g.lib, g.p = _lib.lib, _p
     g.gemm = ops.GemmPlan([dict(kind="inv", bl=8)], max_chains=C)  # workspace: counter block, operand, result, scratch rows
     g.gemm_pk = ops.GemmPlan([dict(kind="fwd", bl=8)], max_chains=1, pk=2)
     g.gemm_abi = lambda name, *a: ops.check(getattr(_lib.lib, name)(*a))
@@ -98,6 +99,24 @@ def _finish(g, **kw):
 
 def _step_args(g):
     return dict(T=0.1, delta=0.1, lmda=1.0)
+
+
+DFT_P = 8 * 15  # pixels of an image of g.dft
+
+
+def _dft_ex(g, to_rings=True, **kw):
+    """pxm_dft_px2ring_ex / pxm_dft_ring2px_ex on g.dft with arguments that are in order but for ``kw``"""
+    a = dict(f=g.c(C, DFT_P), chain_stride=DFT_P, ring0=0, data=None, invcov=None, gidx=None, gw=None, ndata=0, G=g.G, ncol=16, C=C)
+    a.update(kw)
+    p = g.p
+    px = (a["chain_stride"], a["ring0"], p(a["data"]), p(a["invcov"]), 0, p(a["gidx"]), p(a["gw"]), a["ndata"])
+    if to_rings:
+        return g.ops.check(g.lib.pxm_dft_px2ring_ex(g.dft._h, p(a["f"]), *px, p(a["G"]), a["ncol"], a["C"], None))
+    return g.ops.check(g.lib.pxm_dft_ring2px_ex(g.dft._h, p(a["G"]), a["ncol"], p(a["f"]), *px, a["C"], None))
+
+
+def _gidx(g, value=0, n=DFT_P):
+    return g.i(n, dtype=g.torch.int32) + value
 
 
 V, T_, A = ValueError, TypeError, AssertionError
@@ -261,6 +280,55 @@ ROWS = [
      r"^pxm_dft_px2ring: C outside \[1, max_chains\]"),
     ("dft-abi-unaligned", lambda g: g.dft_abi("pxm_dft_ring2px", g.r(2 * g.G.numel() + 2)[1:], g.c(C, 8, 15), C), "PxmError",
      r"^pxm_dft_ring2px: the ring array must be 16-byte aligned"),
+    # the _ex entry points: every refusal of the pixel side and the column count, decided before a launch
+    ("dft-ex-ncol", lambda g: _dft_ex(g, ncol=10), "PxmError", r"^pxm_dft_px2ring_ex: ncol must be 2, 4, 6, 8 or a multiple of 16"),
+    ("dft-ex-ncol-ring2px", lambda g: _dft_ex(g, False, ncol=24), "PxmError",
+     r"^pxm_dft_ring2px_ex: ncol must be 2, 4, 6, 8 or a multiple of 16"),
+    ("dft-ex-chains-ncol", lambda g: _dft_ex(g, ncol=2), "PxmError", r"^pxm_dft_px2ring_ex: C chains need ncol >= 2 C"),
+    ("dft-ex-chains", lambda g: _dft_ex(g, C=C + 1), "PxmError", r"^pxm_dft_px2ring_ex: C outside \[1, max_chains\]"),
+    ("dft-ex-null", lambda g: _dft_ex(g, False, f=None), "PxmError", r"^pxm_dft_ring2px_ex: null argument"),
+    ("dft-ex-unaligned", lambda g: _dft_ex(g, G=g.r(2 * g.G.numel() + 2)[1:]), "PxmError",
+     r"^pxm_dft_px2ring_ex: the ring array must be 16-byte aligned"),
+    ("dft-ex-data-alone", lambda g: _dft_ex(g, data=g.c(DFT_P)), "PxmError", r"^pxm_dft_px2ring_ex: data and invcov come together"),
+    ("dft-ex-invcov-alone", lambda g: _dft_ex(g, invcov=g.r(DFT_P)), "PxmError", r"^pxm_dft_px2ring_ex: data and invcov come together"),
+    ("dft-ex-ring2px-residual", lambda g: _dft_ex(g, False, data=g.c(DFT_P), invcov=g.r(DFT_P)), "PxmError",
+     r"^pxm_dft_ring2px_ex: the residual \(data, invcov\) is fused into pixels -> rings only"),
+    ("dft-ex-gw-alone", lambda g: _dft_ex(g, gw=g.r(DFT_P)), "PxmError",
+     r"^pxm_dft_px2ring_ex: a weight gw needs the pixel -> data map gidx"),
+    ("dft-ex-gidx-ring0", lambda g: _dft_ex(g, False, gidx=_gidx(g), ndata=DFT_P, ring0=1), "PxmError",
+     r"^pxm_dft_ring2px_ex: a pixel -> data map needs ring0 == 0"),
+    ("dft-ex-gidx-ndata", lambda g: _dft_ex(g, gidx=_gidx(g, -1), ndata=0, chain_stride=0), "PxmError",
+     r"^pxm_dft_px2ring_ex: a pixel -> data map needs ndata >= 1"),
+    ("dft-ex-gidx-stride", lambda g: _dft_ex(g, gidx=_gidx(g), ndata=100), "PxmError",
+     r"^pxm_dft_px2ring_ex: with a pixel -> data map the chains are ndata apart"),
+    ("dft-ex-ring0-negative", lambda g: _dft_ex(g, ring0=-1), "PxmError", r"^pxm_dft_px2ring_ex: ring0 must be >= 0"),
+    ("dft-ex-ring0-past", lambda g: _dft_ex(g, f=g.c(C, DFT_P + 4), chain_stride=DFT_P + 4, ring0=5), "PxmError",
+     r"^pxm_dft_px2ring_ex: the image \[ring0, ring0 \+ L \(2L-1\)\) must lie inside a chain"),
+    ("dft-ex-stride-short", lambda g: _dft_ex(g, False, chain_stride=DFT_P - 1), "PxmError",
+     r"^pxm_dft_ring2px_ex: the image \[ring0, ring0 \+ L \(2L-1\)\) must lie inside a chain"),
+    ("dft-rings_raw_ex-gidx-range", lambda g: g.dft.rings_raw_ex(g.c(C, 100), g.G, gidx=_gidx(g, 100)), V,
+     r"^rings_raw_ex: gidx holds an index >= ndata"),
+    ("dft-pixels_raw_ex-gidx-range", lambda g: g.dft.pixels_raw_ex(g.G, g.c(C, 100), gidx=g.i(DFT_P) + 2 ** 32 + 5), V,
+     r"^pixels_raw_ex: gidx holds an index >= ndata"),
+    ("dft-rings_raw_ex-gidx-length", lambda g: g.dft.rings_raw_ex(g.c(C, 100), g.G, gidx=_gidx(g, 0, DFT_P + 1)), V,
+     r"^rings_raw_ex: gidx must have one entry per pixel"),
+    ("dft-rings_raw_ex-gw-length", lambda g: g.dft.rings_raw_ex(g.c(C, 100), g.G, gidx=_gidx(g), gw=g.r(99)), V,
+     r"^rings_raw_ex: gw must have one entry per datum"),
+    ("dft-rings_raw_ex-gw-alone", lambda g: g.dft.rings_raw_ex(g.c(C, DFT_P), g.G, gw=g.r(DFT_P)), "PxmError",
+     r"^pxm_dft_px2ring_ex: a weight gw needs the pixel -> data map gidx"),
+    ("dft-rings_raw_ex-data-alone", lambda g: g.dft.rings_raw_ex(g.c(C, DFT_P), g.G, data=g.c(DFT_P)), V,
+     r"^rings_raw_ex: data and invcov come together"),
+    ("dft-rings_raw_ex-data-length", lambda g: g.dft.rings_raw_ex(g.c(C, DFT_P), g.G, data=g.c(DFT_P + 1), invcov=g.r(DFT_P)), V,
+     r"^data / invcov length mismatch"),
+    ("dft-rings_raw_ex-image", lambda g: g.dft.rings_raw_ex(g.c(C, 8, 15), g.G), T_,
+     r"^rings_raw_ex: the pixel side must be a contiguous complex128 \[C, chain_stride\] device tensor"),
+    ("dft-rings_raw_ex-chains", lambda g: g.dft.rings_raw_ex(g.c(C + 1, DFT_P), g.G), V, r"^more chains than the plan was created for"),
+    ("dft-pixels_raw_ex-G-rows", lambda g: g.dft.pixels_raw_ex(g.c(15, 8, 4), g.c(C, DFT_P)), T_,
+     r"^pixels_raw_ex: G must be a contiguous complex128 \[15, 16, ncol / 2\] device tensor"),
+    ("dft-pixels_raw_ex-ncol", lambda g: g.dft.pixels_raw_ex(g.c(15, 16, 5), g.c(C, DFT_P)), "PxmError",
+     r"^pxm_dft_ring2px_ex: ncol must be 2, 4, 6, 8 or a multiple of 16"),
+    ("dft-pixels_raw_ex-ring0", lambda g: g.dft.pixels_raw_ex(g.G, g.c(C, DFT_P + 4), ring0=5), "PxmError",
+     r"^pxm_dft_ring2px_ex: the image \[ring0, ring0 \+ L \(2L-1\)\) must lie inside a chain"),
     ("gemm-sides-type", lambda g: g.ops.GemmPlan(dict(kind="inv", bl=8)), T_, r"^GemmPlan: sides must be a non-empty list of dicts"),
     ("gemm-sides-empty", lambda g: g.ops.GemmPlan([]), T_, r"^GemmPlan: sides must be a non-empty list of dicts"),
     ("gemm-side-key", lambda g: g.ops.GemmPlan([dict(kind="inv", bl=8, scale=True)]), V, r"^GemmPlan: side 0 needs kind and bl and knows"),
@@ -323,6 +391,8 @@ ROWS = [
      r"^injected noise must have the state's shape"),
     ("wl_attach-pix2data", lambda g: g.wav.wl_attach(g.i(g.wav.npix + 1, dtype=g.torch.int32), None, g.wav.npix), V,
      r"^pix2data must have one entry per pixel"),
+    ("wl_attach-pix2data-range", lambda g: g.wav.wl_attach(g.i(g.wav.npix, dtype=g.torch.int32) + 100, None, 100), V,
+     r"^wl_attach: pix2data holds an index >= ndata"),
     ("wl_attach-weight", lambda g: g.wav.wl_attach(None, g.r(5), g.wav.npix), V, r"^weight must have one entry per datum"),
     ("wl_forward-shape", lambda g: g.wav.wl_forward(g.c(C, g.wav.ncoefs + 1)), A, r"^wl_forward: shape mismatch"),
     ("wl_adjoint-shape", lambda g: g.wav.wl_adjoint(g.c(C, g.wav.npix + 1)), A, r"^wl_adjoint: shape mismatch"),
