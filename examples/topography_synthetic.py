@@ -29,7 +29,8 @@ from pxmcmc_amd.optim import FISTA  # noqa: E402
 from pxmcmc_amd.prior import S2_Wavelets_L1  # noqa: E402
 from pxmcmc_amd.sapg import SAPG  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
-from pxmcmc_amd.uncertainty import chain_to_images, credible_interval_range, local_credible_intervals, superpixel_regions  # noqa: E402
+from pxmcmc_amd.uncertainty import (chain_to_images, credible_interval_range, hypothesis_test, local_credible_intervals,  # noqa: E402
+                                    superpixel_regions)
 from pxmcmc_amd.utils import _multires_bandlimits  # noqa: E402
 
 
@@ -60,6 +61,22 @@ def local_ci_maps(forwardop, regulariser, params, x_map, L, size, base):
           f"level {lci.threshold:.6e}; median range {np.median(lci.range[ok]) if ok.any() else float('nan'):.4f}; "
           f"maps in {base}_lci_lower.npy / _upper.npy / _range.npy")
     return lci
+
+
+def hyp_test_maps(forwardop, regulariser, params, x_map, L, size, frac, base):
+    """--hyp-test SIZE: the hypothesis test of structure of every superpixel of SIZE x SIZE samples
+    at the approximate 95 % HPD level, with the inpainting threshold tau = frac max |A x*|; writes the physical (1 / 0) and
+    removable maps beside those of the local credible intervals"""
+    tr = forwardop.transform
+    X = ops.as_device(np.asarray(x_map).astype(complex))
+    tau = float(frac) * float(ops.as_device(tr.forward(ops.as_device(tr.inverse(X[None])))).abs().max())
+    hyp = hypothesis_test(forwardop, regulariser, params, x_map, superpixel_regions(L, size), tau=tau)
+    np.save(f"{base}_hyp_physical.npy", hyp.to_map(hyp.physical))
+    np.save(f"{base}_hyp_removable.npy", hyp.to_map(hyp.removable))
+    print(f"hypothesis tests: {int(hyp.physical.sum())} of {hyp.physical.size} superpixels of {size} x {size} samples hold "
+          f"structure that is physical at the level {hyp.threshold:.6e} (tau = {tau:.3e}; the others: inconclusive); "
+          f"maps in {base}_hyp_physical.npy / _removable.npy")
+    return hyp
 
 
 def estimate_mu(forwardop, regulariser, params, delta_myula, args, start_point):
@@ -109,6 +126,12 @@ def main(argv=None):
                     help="with --map-start: FISTA with adaptive (gradient) restart, decided per chain on the device")
     ap.add_argument("--local-ci", type=int, default=None, metavar="SIZE",
                     help="with --map-start: local credible intervals of the MAP point on superpixels of SIZE x SIZE samples")
+    ap.add_argument("--hyp-test", type=int, default=None, metavar="SIZE",
+                    help="with --map-start: hypothesis tests of structure (is it physical, or can it be removed inside the "
+                         "credible region?) on superpixels of SIZE x SIZE samples, by segment inpainting")
+    ap.add_argument("--hyp-tau-frac", type=float, default=0.1, metavar="F",
+                    help="with --hyp-test: the inpainting threshold tau = F max |A x*| (the default 0.1 is a choice, not a "
+                         "measured optimum)")
     ap.add_argument("--estimate-mu", action="store_true",
                     help="estimate the regularisation strength by SAPG first and sample with mu_hat = mu * theta_hat")
     ap.add_argument("--estimate-mu-per-scale", action="store_true",
@@ -135,6 +158,8 @@ def main(argv=None):
         ap.error("--map-restart needs --map-start")
     if args.local_ci is not None and not args.map_start:
         ap.error("--local-ci needs --map-start")
+    if args.hyp_test is not None and not args.map_start:
+        ap.error("--hyp-test needs --map-start")
 
     L, B, J_min, setting = args.L, 1.5, 2, args.setting  # B, J_min as in main.py:72-74
 
@@ -190,6 +215,9 @@ def main(argv=None):
                                 restart="gradient" if args.map_restart else None)
         if args.local_ci is not None:
             local_ci_maps(forwardop, regulariser, params, start_point, L, args.local_ci,
+                          os.path.join(args.outdir, f"{args.algo}_{setting}_{args.jobid}"))
+        if args.hyp_test is not None:
+            hyp_test_maps(forwardop, regulariser, params, start_point, L, args.hyp_test, args.hyp_tau_frac,
                           os.path.join(args.outdir, f"{args.algo}_{setting}_{args.jobid}"))
     start = datetime.now()
     mcmc.run(start_point=start_point)

@@ -37,7 +37,7 @@ from pxmcmc_amd.prior import L1, S2_Wavelets_L1  # noqa: E402
 from pxmcmc_amd.sapg import SAPG  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
 from pxmcmc_amd.transforms import SphericalWaveletTransform  # noqa: E402
-from pxmcmc_amd.uncertainty import local_credible_intervals, superpixel_regions  # noqa: E402
+from pxmcmc_amd.uncertainty import hypothesis_test, local_credible_intervals, superpixel_regions  # noqa: E402
 from pxmcmc_amd.utils import _multires_bandlimits, build_mask  # noqa: E402
 
 BEAM_SIGMA = np.radians(50 / 60)  # 50 arcmin (experiments/weaklensing/main.py:35)
@@ -109,6 +109,22 @@ def local_ci_maps(forward_operator, prior, params, x_map, L, size, base):
           f"level {lci.threshold:.6e}; median range {np.median(lci.range[ok]) if ok.any() else float('nan'):.4f}; "
           f"maps in {base}_lci_lower.npy / _upper.npy / _range.npy")
     return lci
+
+
+def hyp_test_maps(forward_operator, prior, params, x_map, L, size, frac, base):
+    """--hyp-test SIZE: the hypothesis test of structure of every superpixel of SIZE x SIZE samples
+    at the approximate 95 % HPD level, with the inpainting threshold tau = frac max |A x*|; writes the physical (1 / 0) and
+    removable maps beside those of the local credible intervals"""
+    tr = forward_operator.transform
+    X = ops.as_device(np.asarray(x_map).astype(complex))
+    tau = float(frac) * float(ops.as_device(tr.forward(ops.as_device(tr.inverse(X[None])))).abs().max())
+    hyp = hypothesis_test(forward_operator, prior, params, x_map, superpixel_regions(L, size), tau=tau)
+    np.save(f"{base}_hyp_physical.npy", hyp.to_map(hyp.physical))
+    np.save(f"{base}_hyp_removable.npy", hyp.to_map(hyp.removable))
+    print(f"hypothesis tests: {int(hyp.physical.sum())} of {hyp.physical.size} superpixels of {size} x {size} samples hold "
+          f"structure that is physical at the level {hyp.threshold:.6e} (tau = {tau:.3e}; the others: inconclusive); "
+          f"maps in {base}_hyp_physical.npy / _removable.npy")
+    return hyp
 
 
 def estimate_mu(forward_operator, prior, params, L_g, args, start_point=None):
@@ -200,6 +216,12 @@ def main(argv=None):
     ap.add_argument("--local-ci", type=int, default=None, metavar="SIZE",
                     help="with --map-start: local credible intervals of the MAP point on superpixels of SIZE x SIZE samples "
                          "(pixel-space posterior only)")
+    ap.add_argument("--hyp-test", type=int, default=None, metavar="SIZE",
+                    help="with --map-start: hypothesis tests of structure (is it physical, or can it be removed inside the "
+                         "credible region?) on superpixels of SIZE x SIZE samples, by segment inpainting (pixel-space posterior only)")
+    ap.add_argument("--hyp-tau-frac", type=float, default=0.1, metavar="F",
+                    help="with --hyp-test: the inpainting threshold tau = F max |A x*| (the default 0.1 is a choice, not a "
+                         "measured optimum)")
     ap.add_argument("--estimate-mu", action="store_true",
                     help="estimate the regularisation strength by SAPG first and sample with mu_hat = mu * theta_hat")
     ap.add_argument("--estimate-mu-per-scale", action="store_true",
@@ -227,6 +249,8 @@ def main(argv=None):
         ap.error("--map-restart needs --map-start")
     if args.local_ci is not None and (not args.map_start or args.harmonic):
         ap.error("--local-ci needs --map-start and the pixel-space posterior (no --harmonic)")
+    if args.hyp_test is not None and (not args.map_start or args.harmonic):
+        ap.error("--hyp-test needs --map-start and the pixel-space posterior (no --harmonic)")
     if args.summary not in (None, True, "state" if args.harmonic else "image"):
         ap.error("--summary %s: the summary is of the %s" % (args.summary, "state with --harmonic" if args.harmonic else "image without --harmonic"))
 
@@ -254,6 +278,9 @@ def main(argv=None):
     start_point = map_start(forward_operator, prior, params, L_g, restart="gradient" if args.map_restart else None) if args.map_start else None
     if args.local_ci is not None:
         local_ci_maps(forward_operator, prior, params, start_point, L, args.local_ci,
+                      os.path.join(args.outdir, f"{args.algo}_{setting}_{args.jobid}"))
+    if args.hyp_test is not None:
+        hyp_test_maps(forward_operator, prior, params, start_point, L, args.hyp_test, args.hyp_tau_frac,
                       os.path.join(args.outdir, f"{args.algo}_{setting}_{args.jobid}"))
     mcmc = build_sampler(args, forward_operator, prior, params, "image")
 

@@ -573,6 +573,21 @@ int pxm_lci_eval(const void* a, const void* b, const double* T, double T_scalar,
 int pxm_lci_search(const void* a, const void* b, const double* T, double T_scalar, const double* quad, double lmda,
                    const double* gamma, int rounds, double* out, int* status, double* scratch, int64_t n, int C, int dtype,
                    pxm_stream_t stream);
+/* One iteration of segment inpainting for the hypothesis test of image structure (Cai, Pereyra & McEwen 2018 II section 4.2;
+ * DESIGN.md section 14c).  Slot c of a batch is one region of an integer label image:
+ *   x_next[c][k] = done[c] ? x_prev[c][k] : (labels[k] == region[c] && labels[k] >= 0 ? y[c][k] : x_map[k])
+ * (a select: bit-exact), y = Psi soft_tau(A x_prev) formed by the caller.  y, x_prev, x_next [C][npix] (f64 or c128), x_map
+ * [npix] of the same dtype and labels int32 [npix] shared by the slots, region int32 [C]; done, iters int32 [C] and stat
+ * float64 [C][2] are read and updated.  For a slot that is not done: d2 = sum |x_next - x_prev|^2 and n2 = sum |x_next|^2
+ * over the whole image, added in a fixed order that depends on npix only (a slot's numbers do not depend on its batch);
+ * then iters[c] += 1, stat[c] = (d2, n2), done[c] = (d2 <= tol2 * n2): one multiply and one compare, tol2 = tol^2 formed by
+ * the caller; a NaN compares false and never freezes a slot.  Of a slot that is done only x_next[c] is written.  Two
+ * kernels, no trip count that depends on data, nothing waits: capturable.  x_next must not overlap x_prev or y.  scratch:
+ * caller-owned, pxm_inpaint_scratch_doubles(npix, C) doubles. */
+int64_t pxm_inpaint_scratch_doubles(int64_t npix, int C);
+int pxm_inpaint_step(const void* y, const void* x_prev, const void* x_map, const int* labels, const int* region, double tol2,
+                     void* x_next, int* done, int* iters, double* stat, double* scratch, int64_t npix, int C, int dtype,
+                     pxm_stream_t stream);
 /* N(0,1) draws of the Philox4x32-10 stream keyed (seed, chain0+c, iter): out [C][n] (f64 or c128) */
 int pxm_randn(void* out, int64_t n, int C, int dtype, uint64_t seed, uint64_t chain0, uint64_t iter,
               pxm_stream_t stream);

@@ -173,6 +173,8 @@ SIGNATURES = {
     "pxm_lci_data_terms": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_lci_eval": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_lci_search": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_dbl, c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_inpaint_scratch_doubles": (c_i64, [c_i64, c_int]),
+    "pxm_inpaint_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_sapg_step": (
         c_int,
         [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_int, c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i64, c_dbl, c_dbl,

@@ -7,8 +7,8 @@ float64 or complex128; outputs are fresh tensors (the reference never mutates in
 SURVEY.md section 8b).
 
 One module per concern, as the kernel files are: ``steps`` (elementwise.hip, skrock.hip, fista.hip, sapg.hip), ``reduce``
-(reduce.hip), ``pxmala`` (pxmala.hip), ``summary`` (moments.hip, tails.hip, acov.hip), ``lci`` (lci.hip), ``sparse``
-(spmv.hip), ``plans`` (the plan sources), ``host`` (tables.cpp, host_api.cpp); ``_args`` holds what they do to their arguments
+(reduce.hip), ``pxmala`` (pxmala.hip), ``summary`` (moments.hip, tails.hip, acov.hip), ``lci`` (lci.hip), ``inpaint`` (inpaint.hip),
+``sparse`` (spmv.hip), ``plans`` (the plan sources), ``host`` (tables.cpp, host_api.cpp); ``_args`` holds what they do to their arguments
 and the checks they share.  Callers use the names below as ``ops.<name>``.
 """
 # flake8: noqa: F401  (every import below is a re-export)
@@ -17,6 +17,7 @@ from .._lib import (FISTA_SLICES_MAX, LCI_EMPTY, LCI_NONFINITE, LCI_POINTS, LCI_
 from ._args import GEMM_KINDS, _batched, _p, _stream, as_device, device
 from .host import (DFT_STEP_FIELDS, DFT_UNITS, GEMM_TASK_FIELDS, dft_geometry, dft_step_is_stock, gemm_plan_geometry, gemm_report, j_max, mw_ring_weights, noise_bits, rec_geometry, tiling_axisym,
                    wav_bandlimits)
+from .inpaint import inpaint_scratch, inpaint_step
 from .lci import lci_data_terms, lci_eval, lci_scratch, lci_search
 from .plans import (DftPlan, DirWavPlan, GemmPlan, HarmWavPlan, IterCounter, ShtPlan, WavPlan, _Plan, capture_scope, live_plans, raise_on_status,
                     tables_trim)
