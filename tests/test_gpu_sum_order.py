@@ -52,14 +52,15 @@ def _same_bits(got, want):
     return np.array_equal(got.view(np.int64), want.view(np.int64))
 
 
-@pytest.mark.parametrize("n", [133121, 300])
+@pytest.mark.parametrize("n", [133121, 300, 1024 * 2048 + 2049])
 def test_reduce_l1(n):
     """terms |x|; 133121 elements: 66 slices (the slice stage wraps past lane 63) and the grid strides; 300: 64 slices, most
-    of them empty, and a partial last wave"""
+    of them empty, and a partial last wave; 2099201: the slice count stops at RED_SLICES_MAX = 1024 (uncapped it would be
+    1026), which the caller-owned scratch is sized by -- 9 passes of the grid, 16 rows of slices in the finishing kernel"""
     from pxmcmc_amd import ops
 
     C = 3
-    assert red_slices(n) == (66 if n == 133121 else 64)
+    assert red_slices(n) == {133121: 66, 300: 64, 2099201: 1024}[n]
     X = np.random.default_rng(n).normal(size=(C, n))
     got = ops.reduce_l1(ops.as_device(X)).cpu().numpy()
     want = [fixed_order_sum(np.abs(X[c]), red_slices(n)) for c in range(C)]
