@@ -146,11 +146,11 @@ class PxMCMC:
             tail_capacity(summary_alpha, self.nsamples)  # (validates alpha and nsamples)
         self.summary_alpha = None if summary_alpha is None else float(summary_alpha)
         if summary_ess is not None:
-            from .uncertainty import _ess_lags
+            from .uncertainty import ess_lag_count
 
             if not self._summary_spaces:
                 raise ValueError("summary_ess needs summary: the lagged products are part of the streaming summaries")
-            summary_ess = _ess_lags(summary_ess)
+            summary_ess = ess_lag_count(summary_ess)
         self.summary_ess = summary_ess
         self._initialise_tracking_arrays()
 

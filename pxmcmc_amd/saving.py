@@ -12,9 +12,12 @@ import os
 
 import numpy as np
 
-_SUMMARY_FIELDS = ("count", "mean", "m2", "best", "best_logpi")  # uncertainty.PosteriorSummary.to_host()
-_TAIL_FIELDS = ("q_lo", "q_hi")  # ... of a summary built with alpha (its ``alpha`` becomes the attribute summary_alpha)
-_ESS_FIELDS = ("ess", "ess_lag")  # ... of a summary built with ess_lags (which becomes the attribute summary_ess_lags)
+from .uncertainty import PosteriorSummary
+
+_SUMMARY_FIELDS = PosteriorSummary.FIELDS  # the datasets of PosteriorSummary.to_host()
+# ... of a summary built with alpha / with ess_lags; the scalar of either group becomes the attribute summary_alpha / summary_ess_lags
+_TAIL_FIELDS = tuple(k for k in PosteriorSummary.TAIL_FIELDS if k != "alpha")
+_ESS_FIELDS = tuple(k for k in PosteriorSummary.ESS_FIELDS if k != "ess_lags")
 
 _DATASETS = (
     ("logPi", "logposterior", None),

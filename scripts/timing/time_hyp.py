@@ -26,7 +26,8 @@ from pxmcmc_amd import ops  # noqa: E402
 from pxmcmc_amd.forward import SphericalWaveletTransformOperator  # noqa: E402
 from pxmcmc_amd.mcmc import PxMCMCParams  # noqa: E402
 from pxmcmc_amd.prior import S2_Wavelets_L1  # noqa: E402
-from pxmcmc_amd.uncertainty import _InpaintBatches, hypothesis_test, superpixel_regions  # noqa: E402
+from pxmcmc_amd.uncertainty import hypothesis_test, superpixel_regions  # noqa: E402
+from pxmcmc_amd.uncertainty.hyp import _InpaintBatches  # noqa: E402
 
 B, J_MIN, C = 2.0, 2, 16
 LMDA, SIGMA = 1e-3, 0.1

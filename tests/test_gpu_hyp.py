@@ -376,7 +376,8 @@ def _path_instances(op, reg, p, X, images, x_map):
     """per region the instance (a, b, T, q, lmda) of the path as the device forms it, r + s and the linearity defect
     forward(X* + b) - (forward(X*) + forward(b)) -> list of dicts, and the device's F(X* + b)"""
     from pxmcmc_amd import ops
-    from pxmcmc_amd.uncertainty import _lci_preds, _lci_weights, lci_terms_np, map_objective
+    from pxmcmc_amd.uncertainty import lci_terms_np, map_objective
+    from pxmcmc_amd.uncertainty.regions import _lci_preds, _lci_weights
 
     tr = op.transform
     Xd = ops.as_device(np.asarray(X).astype(complex))

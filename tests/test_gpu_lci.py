@@ -282,7 +282,7 @@ def _device_inputs(op, X, labels, batch=3):
     import torch
 
     from pxmcmc_amd import ops
-    from pxmcmc_amd.uncertainty import _lci_preds, _lci_weights
+    from pxmcmc_amd.uncertainty.regions import _lci_preds, _lci_weights
 
     tr = op.transform
     Xd = ops.as_device(np.asarray(X).astype(complex))

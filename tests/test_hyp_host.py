@@ -1,4 +1,4 @@
-"""Host model of the hypothesis tests of image structure (pxmcmc_amd/uncertainty.py, csrc/inpaint.hip):
+"""Host model of the hypothesis tests of image structure (pxmcmc_amd/uncertainty/hyp.py, csrc/inpaint.hip):
 the numpy statement of the step kernel, the properties of segment inpainting on the oracle's wavelet transform, and the
 decision on a planted structure, formed in numpy from lci_terms_np / lci_eval_np.  tests/test_gpu_hyp.py holds the kernel
 and the device route to the same statements and the same planted structure."""

@@ -1,4 +1,4 @@
-"""Host model of the local credible intervals (pxmcmc_amd/uncertainty.py, csrc/lci.hip): the superpixel
+"""Host model of the local credible intervals (pxmcmc_amd/uncertainty/lci.py, csrc/lci.hip): the superpixel
 labels, the construction X(xi) = a + xi b on the oracle's wavelet transform, and the numpy statement of the search held to a
 long-double bisection on random convex instances and on one designed case per status.  tests/test_gpu_lci.py holds the
 kernels to the same instances, cases and properties."""
