@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from .forward import InverseCovariance
-from .mcmc import PxMCMC, PxMCMCParams
+from .mcmc import PxMCMCParams, Stepper
 
 
 def gradient_operator(forward):
@@ -56,7 +56,7 @@ def fista_momentum(n, momentum=True):
     return beta
 
 
-class FISTA(PxMCMC):
+class FISTA(Stepper):
     """
     MAP point of the posterior of ``(forward, prior, mcmcparams)`` -- the arguments of the samplers -- by FISTA::
 
@@ -123,9 +123,6 @@ class FISTA(PxMCMC):
         self.check_every = int(check_every)
         self.beta = fista_momentum(self.max_iter, self.momentum)
 
-    def _initialise_tracking_arrays(self):
-        """no chain is kept: the traces are per check (run)"""
-
     def _engine_start(self, X, preds, i0):
         """static state (XA, XB, P) plus the extrapolated point in YA / YB -- Y of the state in XA lives in YA, of XB in YB --
         the per-chain sums and the momentum table on the device; the kernel reads beta_k at the engine's device counter, or,
@@ -145,9 +142,9 @@ class FISTA(PxMCMC):
         self._restarts = torch.zeros(C, dtype=torch.int64, device=X.device) if restart else None
 
         def step(eng, src, dst):
-            Y, Y_next = (YA, YB) if src is eng["XA"] else (YB, YA)
+            Y, Y_next = (YA, YB) if src is eng.XA else (YB, YA)
             g = ops.as_device(f.calc_gradg(ops.as_device(f.forward(Y))), src.dtype)
-            kw = dict(out=(dst, Y_next), sums=self._sums[0 if dst is eng["XA"] else 1], scratch=scratch)
+            kw = dict(out=(dst, Y_next), sums=self._sums[0 if dst is eng.XA else 1], scratch=scratch)
             if self._stock_prox:
                 kw["T"] = T
             else:
@@ -156,13 +153,13 @@ class FISTA(PxMCMC):
             if restart:  # Y is passed next to a given proxf too: the restart sum reads it
                 ops.fista_step_restart(Y, g, src, gamma, lmda, beta, self._momentum_index, restarts=self._restarts, **kw)
             elif self._stock_prox:
-                ops.fista_step(Y, g, src, gamma, lmda, beta, iter_dev=eng["cnt"].t, **kw)
+                ops.fista_step(Y, g, src, gamma, lmda, beta, iter_dev=eng.cnt.t, **kw)
             else:
-                ops.fista_step(None, None, src, gamma, lmda, beta, iter_dev=eng["cnt"].t, **kw)
-            eng["cnt"].add(1)
+                ops.fista_step(None, None, src, gamma, lmda, beta, iter_dev=eng.cnt.t, **kw)
+            eng.cnt.add(1)
 
         def reset(eng):
-            YA.copy_(eng["XA"])
+            YA.copy_(eng.XA)
             self._sums.zero_()
             if restart:
                 self._momentum_index.zero_()
@@ -193,7 +190,7 @@ class FISTA(PxMCMC):
                 i += k
                 X, preds = self._engine_state()  # forward(X) is formed here, where the state is observed
                 self._check_device_status()
-                last = 0 if self._eng["side"] == "A" else 1
+                last = 0 if self._eng.side == "A" else 1
                 both = self._sums.cpu().numpy()
                 s, s_prev = both[last], both[1 - last]
                 with np.errstate(invalid="ignore", divide="ignore"):
@@ -212,8 +209,8 @@ class FISTA(PxMCMC):
                     break
             self.X_map, self.preds_map = X.clone(), preds.clone()
             self.last_steps = np.sqrt(np.stack([s[:, 0], s_prev[:, 0]], axis=1))
-            self.used_graph = self._eng["graph"] is not None
-            self.graph_error = self._eng["graph_error"]
+            self.used_graph = self._eng.graph is not None
+            self.graph_error = self._eng.graph_error
         finally:
             self._engine_stop()
         for key, rows in traces.items():

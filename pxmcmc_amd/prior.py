@@ -60,6 +60,11 @@ class L1:
         return to_like(x + ops.as_device(self.fwd(ops.soft(a, self.T_dev) - a)), X)
 
 
+def _is_stock_l1(prior):
+    """True when prior.proxf is the library's own synthesis soft threshold (safe to fuse)."""
+    return isinstance(prior, L1) and type(prior).proxf is L1.proxf and type(prior)._proxf_synthesis is L1._proxf_synthesis and prior.setting == "synthesis"
+
+
 class S2_Wavelets_L1(L1):
     """
     L1 regulariser for wavelets on S2 with MW quadrature weighting (pxmcmc/prior.py:56-84).

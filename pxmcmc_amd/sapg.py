@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .mcmc import PxMCMC, PxMCMCParams
+from .mcmc import PxMCMCParams, Stepper
 
 
 def sapg_rho_table(warmup, niter, ndim, scale=10.0, exponent=0.8):
@@ -39,7 +39,7 @@ def sapg_rho_table(warmup, niter, ndim, scale=10.0, exponent=0.8):
     return np.concatenate([np.zeros(warmup), scale * j ** (-exponent) / ndim])
 
 
-class SAPG(PxMCMC):
+class SAPG(Stepper):
     """
     Marginal maximum-likelihood estimate of the scale theta of the prior of ``(forward, prior, mcmcparams)`` -- the
     arguments of the samplers -- so that ``mu_hat = mcmcparams.mu * theta_hat`` is the regularisation strength the data ask
@@ -130,9 +130,6 @@ class SAPG(PxMCMC):
             raise ValueError("SAPG: with groups theta0 must be a float, [K] or [C, K]")
         return np.broadcast_to(t, (C, K)).copy()
 
-    def _initialise_tracking_arrays(self):
-        """no chain is kept: the traces are per iteration (run)"""
-
     def _engine_start(self, X, preds, i0):
         """static state (XA, XB, P) plus theta, eta, the trace and the step-size table on the device; both kernels read the
         iteration number from the engine's device counter"""
@@ -153,15 +150,15 @@ class SAPG(PxMCMC):
         lo, hi = float(np.log(self.theta_min)), float(np.log(self.theta_max))
 
         def step(eng, src, dst):
-            gradg = ops.as_device(f.calc_gradg(eng["P"]), src.dtype)
+            gradg = ops.as_device(f.calc_gradg(eng.P), src.dtype)
             if grouped:
                 ops.sapg_step_groups(src, gradg, T, delta, lmda, self._theta, self._eta, self.group_bounds, ndim, rho, lo, hi,
-                                     iter_dev=eng["cnt"].t, out=dst, **kw)
+                                     iter_dev=eng.cnt.t, out=dst, **kw)
             else:
-                ops.sapg_step(src, gradg, T, delta, lmda, self._theta, self._eta, ndim, rho, lo, hi, iter_dev=eng["cnt"].t,
+                ops.sapg_step(src, gradg, T, delta, lmda, self._theta, self._eta, ndim, rho, lo, hi, iter_dev=eng.cnt.t,
                               out=dst, **kw)
-            eng["P"].copy_(ops.as_device(f.forward(dst)))
-            eng["cnt"].add(1)
+            eng.P.copy_(ops.as_device(f.forward(dst)))
+            eng.cnt.add(1)
 
         def reset(eng):  # the capture warm-up moved them
             self._eta.copy_(eta0)
@@ -182,8 +179,8 @@ class SAPG(PxMCMC):
             self._check_device_status()
             trace = self._trace.cpu().numpy()
             self.X_curr, self.curr_preds = X.clone(), preds.clone()
-            self.used_graph = self._eng["graph"] is not None
-            self.graph_error = self._eng["graph_error"]
+            self.used_graph = self._eng.graph is not None
+            self.graph_error = self._eng.graph_error
         finally:
             self._engine_stop()
             self._theta = self._eta = self._trace = None

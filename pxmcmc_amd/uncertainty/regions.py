@@ -9,14 +9,13 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..prior import _is_stock_l1
 from .chains import approx_credible_region_threshold
 
 
 def _check_scope(fn, forward, *prior):
     """the scope of the tool ``fn``: synthesis setting and a pixel-space transform; given the prior (the tool forms the
     objective F) also the stock L1 prior and a diagonal inverse covariance"""
-    from ..mcmc import _is_stock_l1
-
     objective = bool(prior)
     if getattr(forward, "setting", None) != "synthesis":
         raise ValueError("%s is defined in the synthesis setting (X_map holds coefficients: the surrogate lives in coefficient space)" % fn)

@@ -75,7 +75,7 @@ def started(s, op):
     with contextlib.redirect_stdout(io.StringIO()):
         X, preds = s._initial_sample(np.zeros(op.nparams))
     s._engine_start(X, preds, 0)
-    assert s._eng["graph"] is not None, s._eng.get("graph_error")
+    assert s._eng["graph"] is not None, s._eng["graph_error"]
     return s
 
 

@@ -67,7 +67,7 @@ def myula_iteration(N, spin, generic, steps=64):
         X, preds = s._initial_sample(X0)
         s._engine_start(X, preds, 0)
     try:
-        assert s._eng["graph"] is not None, s._eng.get("graph_error")
+        assert s._eng["graph"] is not None, s._eng["graph_error"]
         assert s._fused_harm == (not generic)
         s._engine_advance(16)
         torch.cuda.synchronize()

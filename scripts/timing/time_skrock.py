@@ -51,7 +51,7 @@ def sampler(op, reg, s):
     with contextlib.redirect_stdout(io.StringIO()):
         X, preds = sk._initial_sample(np.zeros(op.nparams))
     sk._engine_start(X, preds, 0)
-    assert sk._eng["graph"] is not None, sk._eng.get("graph_error")
+    assert sk._eng["graph"] is not None, sk._eng["graph_error"]
     return sk
 
 

@@ -62,7 +62,7 @@ def myula_iteration(spin, vector_sig, steps=64):
             s._pairs_start()
         s._engine_start(X, preds, 0)
     try:
-        assert s._eng["graph"] is not None, s._eng.get("graph_error")
+        assert s._eng["graph"] is not None, s._eng["graph_error"]
         assert s._fused_wav and not s._pairs and s._eng["ring"] == (not vector_sig)
         s._engine_advance(16)
         torch.cuda.synchronize()

@@ -215,8 +215,8 @@ def test_wavelet_transform_literal_L512():
 
 # ---- (ii) the fused MYULA iteration of the benchmark ---------------------------------------------------------
 def _plan_steps(path, plan, X0, data_c, invcov, T_dev, delta, lmda, noises, pairs):
-    """K MYULA iterations through the very C-ABI calls the stepping engine makes (pxmcmc_amd/mcmc.py
-    _engine_start), with injected noise.  Returns (X, preds) in the plan's slot layout."""
+    """K MYULA iterations through the very C-ABI calls the stepping engine makes (pxmcmc_amd/mcmc/myula.py
+    _engine_start_fused), with injected noise.  Returns (X, preds) in the plan's slot layout."""
     import torch
 
     X = X0.clone()

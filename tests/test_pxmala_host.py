@@ -1,4 +1,4 @@
-"""Host model of one PxMALA iteration (pxmcmc_amd/mcmc.py PxMALA.run, csrc/pxmala.hip): the extended-precision
+"""Host model of one PxMALA iteration (pxmcmc_amd/mcmc/pxmala.py PxMALA.run, csrc/pxmala.hip): the extended-precision
 yardstick that tests/test_gpu_pxmala.py holds the proposal, tail and accept kernels to.
 
     p  = proxf (given) or soft(X, T)
