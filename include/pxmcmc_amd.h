@@ -493,6 +493,26 @@ int pxm_fista_step_restart(const void* Y, const void* gradg, const void* proxf, 
                            const void* X_prev, double gamma, double lmda, const double* beta_table, int64_t n_beta,
                            uint64_t* momentum_index, uint64_t* restarts, int restart_on, void* X_out, void* Y_out,
                            double* sums, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream);
+/* The two elementwise steps of the forward-backward primal-dual iteration (Condat 2013; Vu 2013) on
+ * g(x) + h(A x), h(u) = (1 / lmda) sum_i T_i |u_i|; every state array [C][n] (dual arrays [C][m]), float64 or complex128.
+ * pxm_pd_primal_step, with G = gradg(X) and U = A^H v:
+ *   s = G + U (rounded);  X1_out = fma(-tau, s, X);  Xbar_out = fma(2, X1_out, -X), per component;
+ *   sums [C][2] = per chain sum |X1_out - X|^2, sum |X1_out|^2.
+ *   scratch: caller-owned, 2 * PXM_FISTA_SLICES_MAX * C doubles.
+ * pxm_pd_dual_step, with W = A xbar (T [m] shared by chains, or T_scalar; rscale = 1 / lmda in the iteration):
+ *   w = fma(sigma, W, V) per component;  r_i = T_i rscale (rounded once);
+ *   complex: a = sqrt(re(w)^2 + im(w)^2) (plain products and sum, no hypot), V1_out = a > r_i ? w (r_i / a) : w, one division
+ *   per element (a == 0 keeps w, T_i == 0 gives 0);  real: V1_out = min(max(w, -r_i), r_i)
+ *   -- the projection onto |v_i| <= r_i, which is the prox of sigma h^* for every sigma;
+ *   sums [C][3] = per chain sum |V1_out - V|^2, sum |V1_out|^2 and sum T_i |W_i| (the prior sum of the point W analyses).
+ *   scratch: caller-owned, 3 * PXM_FISTA_SLICES_MAX * C doubles.
+ * The sums are added in a fixed order that depends on n (m) only: a chain's sums do not depend on its batch; with n == 0
+ * (m == 0) they are written as zeros.  An output must not overlap an input or the other output (only equal base pointers
+ * are detected and refused).  No atomics and no host read: a HIP graph replays both. */
+int pxm_pd_primal_step(const void* X, const void* G, const void* U, double tau, void* X1_out, void* Xbar_out,
+                       double* sums, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream);
+int pxm_pd_dual_step(const void* V, const void* W, const double* T, double T_scalar, double sigma, double rscale,
+                     void* V1_out, double* sums, double* scratch, int64_t m, int C, int dtype, pxm_stream_t stream);
 /* One SAPG iteration (Vidal, De Bortoli, Pereyra & Durmus 2020): a MYULA step of every chain on the
  * posterior whose prior is scaled by the chain's theta, then the move of theta towards the marginal maximum-likelihood
  * value of the regularisation strength.  Every state array [C][n]; theta, eta [C] float64 on the device, updated in place.

@@ -169,6 +169,8 @@ SIGNATURES = {
         [c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_dbl, c_dbl, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_int,
          c_int, c_vp],
     ),
+    "pxm_pd_primal_step": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_pd_dual_step": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_lci_scratch_doubles": (c_i64, [c_i64, c_int]),
     "pxm_lci_data_terms": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_lci_eval": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),

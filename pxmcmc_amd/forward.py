@@ -60,6 +60,37 @@ class FullInverseCovariance:
     dot = __matmul__
 
 
+def power_iteration(A, n, dt, iters, tol, seed, name):
+    """The norm of the linear part of the affine map ``A`` on device vectors of length ``n`` and dtype ``dt`` (Hermitian
+    positive semidefinite linear part), by the power iteration, its stopping rule and its warning that
+    :meth:`ForwardOperator.gradient_lipschitz` documents; ``name`` is the caller's, for the warning.  Returns a float that
+    approaches the norm from below."""
+    gen = torch.Generator().manual_seed(int(seed))
+    x = ops.as_device(torch.randn(int(n), dtype=dt, generator=gen), dt)
+    g0 = A(torch.zeros_like(x))
+    norm = lambda v: float(ops.reduce_vdot(v, v)[0].real) ** 0.5  # noqa: E731
+    nx = norm(x)
+    ests, met = [], 0
+    for _ in range(int(iters)):
+        y = A(x / nx) - g0
+        ny = norm(y)
+        if ny == 0.0:
+            return 0.0
+        ests.append(ny)
+        if len(ests) >= 3:
+            d, d_prev = ests[-1] - ests[-2], ests[-2] - ests[-3]
+            r = d / d_prev if d_prev > 0 else 1.0
+            met = met + 1 if d <= 0.0 or (r < 1.0 and 2.0 * d * r / (1.0 - r) <= tol * ny) else 0
+            if met >= 5:
+                break
+        x, nx = y, ny
+    else:
+        import warnings
+
+        warnings.warn(f"{name}: {iters} iterations did not reach tol = {tol:g}; the estimate is a lower bound")
+    return ests[-1]
+
+
 class ForwardOperator:
     """
     Base forward operator = Transform o Measurement + Gaussian inverse covariance
@@ -137,33 +168,9 @@ class ForwardOperator:
         the gap like ``1 / k``, twice the geometric extrapolation.  A warning is issued when ``iters`` products (two operator
         calls each) do not get there: the value returned is then a lower bound whose gap is unknown.  ``seed`` fixes the
         start vector.  Returns a float."""
-        n = int(self.nparams)
         dt = self._state_dtype()
-        gen = torch.Generator().manual_seed(int(seed))
-        x = ops.as_device(torch.randn(n, dtype=dt, generator=gen), dt)
         A = lambda v: ops.as_device(self.calc_gradg(ops.as_device(self.forward(v))), dt)  # noqa: E731
-        g0 = A(torch.zeros_like(x))
-        norm = lambda v: float(ops.reduce_vdot(v, v)[0].real) ** 0.5  # noqa: E731
-        nx = norm(x)
-        ests, met = [], 0
-        for _ in range(int(iters)):
-            y = A(x / nx) - g0
-            ny = norm(y)
-            if ny == 0.0:
-                return 0.0
-            ests.append(ny)
-            if len(ests) >= 3:
-                d, d_prev = ests[-1] - ests[-2], ests[-2] - ests[-3]
-                r = d / d_prev if d_prev > 0 else 1.0
-                met = met + 1 if d <= 0.0 or (r < 1.0 and 2.0 * d * r / (1.0 - r) <= tol * ny) else 0
-                if met >= 5:
-                    break
-            x, nx = y, ny
-        else:
-            import warnings
-
-            warnings.warn(f"gradient_lipschitz: {iters} iterations did not reach tol = {tol:g}; the estimate is a lower bound")
-        return ests[-1]
+        return power_iteration(A, int(self.nparams), dt, iters, tol, seed, "gradient_lipschitz")
 
     def _forward_analysis(self, X):
         return self.measurement.forward(X)

@@ -6,7 +6,7 @@ Conventions: arrays are ``[C, n]`` (chain batch first) or ``[n]`` (one chain); d
 float64 or complex128; outputs are fresh tensors (the reference never mutates inputs,
 SURVEY.md section 8b).
 
-One module per concern, as the kernel files are: ``steps`` (elementwise.hip, skrock.hip, fista.hip, sapg.hip), ``reduce``
+One module per concern, as the kernel files are: ``steps`` (elementwise.hip, skrock.hip, fista.hip, primal_dual.hip, sapg.hip), ``reduce``
 (reduce.hip), ``pxmala`` (pxmala.hip), ``summary`` (moments.hip, tails.hip, acov.hip), ``lci`` (lci.hip), ``inpaint`` (inpaint.hip),
 ``sparse`` (spmv.hip), ``plans`` (the plan sources), ``host`` (tables.cpp, host_api.cpp); ``_args`` holds what they do to their arguments
 and the checks they share.  Callers use the names below as ``ops.<name>``.
@@ -25,7 +25,7 @@ from .pxmala import logtransition, pxmala_accept, pxmala_finish, pxmala_propose,
 from .reduce import quantile_range, reduce_l1, reduce_l2, reduce_scratch_doubles, reduce_vdot
 from .sparse import CsrMatrix
 from .steps import (box_muller, chain_step, counter_add, fista_restart_scratch, fista_scratch, fista_step, fista_step_restart,
-                    myula_step, randn, residual_grad, sapg_group_bounds, sapg_groups_scratch, sapg_scratch, sapg_step,
+                    myula_step, pd_dual_step, pd_primal_step, pd_scratch, randn, residual_grad, sapg_group_bounds, sapg_groups_scratch, sapg_scratch, sapg_step,
                     sapg_step_groups, select_copy_many, skrock_stage, soft)
 from .summary import (acov_ess, acov_stage_depth, acov_update, moments_finalize, moments_update, tails_quantiles,
                       tails_stage_depth, tails_update)

@@ -1,4 +1,4 @@
-"""The elementwise steps of the samplers and optimisers (csrc/elementwise.hip, skrock.hip, fista.hip, sapg.hip)."""
+"""The elementwise steps of the samplers and optimisers (csrc/elementwise.hip, skrock.hip, fista.hip, primal_dual.hip, sapg.hip)."""
 import ctypes as C
 
 import numpy as np
@@ -165,6 +165,55 @@ def fista_step_restart(Y, gradg, X_prev, gamma, lmda, beta, momentum_index, T=No
         )
     )
     return (x1[0], y1[0], sums) if squeeze else (x1, y1, sums)
+
+
+def pd_scratch(C_, dev):
+    """scratch of :func:`pd_primal_step` and :func:`pd_dual_step` for C_ chains (the larger of the two: three partial sums
+    per slice and chain; calls on one stream may share it)"""
+    return _scratch(None, 3 * FISTA_SLICES_MAX * int(C_), dev)
+
+
+def pd_primal_step(X, G, U, tau, out=None, sums=None, scratch=None):
+    """The primal half of one primal-dual iteration in one launch: ``X1 = X - tau (G + U)`` with
+    ``G = gradg(X)`` and ``U = A^H v``, and ``Xbar = 2 X1 - X``.
+
+    ``out``: the pair of result buffers ``(X1, Xbar)`` (neither may alias an input or the other).  Returns ``(X1, Xbar, sums)``
+    with ``sums`` float64 [C, 2]: per chain ``sum |X1 - X|^2`` and ``sum |X1|^2``.  ``scratch``: :func:`pd_scratch`."""
+    name = "pd_primal_step"
+    x, squeeze = _batched(as_device(X))
+    g, u = (_companion(t, x, f"{name}: G and U must have the state's shape") for t in (G, U))
+    C_ = x.shape[0]
+    if out is None:
+        x1, xbar = torch.empty_like(x), torch.empty_like(x)
+    else:
+        x1, xbar = _state_out(out[0], x), _state_out(out[1], x)
+    sums = _result(sums, (C_, 2), _REAL, x.device, f"{name}: sums must be a contiguous float64 [C, 2] device array")
+    scratch = _scratch(scratch, 2 * FISTA_SLICES_MAX * C_, x.device, f"{name}: scratch is too small", any_layout=True)
+    check(lib.pxm_pd_primal_step(_p(x), _p(g), _p(u), float(tau), _p(x1), _p(xbar), _p(sums), _p(scratch), x.shape[1], C_, _dt(x),
+                                 _stream()))
+    return (x1[0], xbar[0], sums) if squeeze else (x1, xbar, sums)
+
+
+def pd_dual_step(V, W, T, sigma, rscale, out=None, sums=None, scratch=None):
+    """The dual half of one primal-dual iteration in one launch: ``V1`` is ``V + sigma W`` projected
+    element by element onto ``|v_i| <= T_i rscale`` (``W = A xbar``; ``rscale = 1 / lmda`` in the iteration, 1 in the dual
+    iteration of the analysis prox).
+
+    ``out``: the result buffer (must not alias an input).  Returns ``(V1, sums)`` with ``sums`` float64 [C, 3]: per chain
+    ``sum |V1 - V|^2``, ``sum |V1|^2`` and ``sum T_i |W_i|``.  ``scratch``: :func:`pd_scratch`."""
+    name = "pd_dual_step"
+    v, squeeze = _batched(as_device(V))
+    w = _companion(W, v, f"{name}: W must have the shape of V")
+    if T is None:
+        raise ValueError(f"{name}: the threshold T is needed")
+    Tv, Ts = _vecT(T, v.shape[1], v.device)
+    C_ = v.shape[0]
+    v1 = torch.empty_like(v) if out is None else _state_out(out, v)
+    sums = _result(sums, (C_, 3), _REAL, v.device, f"{name}: sums must be a contiguous float64 [C, 3] device array")
+    scratch = _scratch(scratch, 3 * FISTA_SLICES_MAX * C_, v.device, f"{name}: scratch is too small", any_layout=True)
+    check(lib.pxm_pd_dual_step(_p(v), _p(w), _p(Tv), Ts, float(sigma), float(rscale), _p(v1), _p(sums), _p(scratch), v.shape[1], C_,
+                               _dt(v), _stream()))
+    return (v1[0], sums) if squeeze else (v1, sums)
 
 
 def sapg_scratch(C_, dev):

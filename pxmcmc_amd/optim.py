@@ -10,6 +10,11 @@ its weights twice, and the estimator minimises the function its prox belongs to.
 
 One iteration is one fused HIP launch (``pxm_fista_step``, or ``pxm_fista_step_restart`` with adaptive restart) around the two
 operator calls, replayed from a captured HIP graph by the samplers' stepping engine.
+
+In the analysis setting the prior acts on ``A X`` (``A = prior.adj``, ``A^H = prior.fwd``) and the soft threshold is not its
+prox unless ``A A^H = I``: :class:`PrimalDual` minimises ``g(X) + (1 / lmda) sum_i T_i |(A X)_i|`` exactly by primal-dual
+splitting on two fused HIP launches per iteration, and :func:`analysis_prox` is the exact prox of the analysis prior
+(DESIGN.md section 14d).  ``optim_np`` states both in numpy.
 """
 import copy
 import warnings
@@ -18,8 +23,9 @@ import numpy as np
 import torch
 
 from . import ops
-from .forward import InverseCovariance
+from .forward import InverseCovariance, power_iteration
 from .mcmc import PxMCMCParams, Stepper
+from .utils import to_like
 
 
 def gradient_operator(forward):
@@ -219,6 +225,240 @@ class FISTA(Stepper):
         if self.restart:
             self.restarts = np.stack(restarts)
             self.nrestarts = self.restarts[-1]
+        self.objective_map = self.objective[-1]
+        out = self.X_map if C > 1 else self.X_map[0]
+        return out.clone() if as_torch else out.cpu().numpy()
+
+
+# ---- analysis setting: primal-dual splitting and the exact prox ---------------------------------------
+def operator_norm2(fwd, adj, n, dtype=torch.complex128, iters=1000, tol=1e-4, seed=0):
+    """``||A||^2`` of the analysis operator ``A = adj`` (state of length ``n`` -> coefficients) with ``A^H = fwd``: the power
+    iteration of :meth:`ForwardOperator.gradient_lipschitz` on ``x -> fwd(adj(x))``, with its stopping rule and its caveat --
+    the estimate approaches ``||A||^2`` from below, so ``||A||^2 (1 + tol)`` is the safe value.  ``fwd is None and adj is
+    None`` means ``A = I``: exactly 1.  Returns a float."""
+    if fwd is None and adj is None:
+        return 1.0
+    if fwd is None or adj is None:
+        raise ValueError("operator_norm2: fwd and adj are given together (both None: A = I)")
+    AHA = lambda v: ops.as_device(fwd(ops.as_device(adj(v))), dtype)  # noqa: E731
+    return power_iteration(AHA, int(n), dtype, iters, tol, seed, "operator_norm2")
+
+
+def _analysis_pair(prior, dtype):
+    """(A, A^H) of an analysis prior as maps between device arrays of ``dtype`` (``fwd is None and adj is None``: A = I)"""
+    if prior.fwd is None and prior.adj is None:
+        return (lambda x: x), (lambda v: v)
+    return (lambda x: ops.as_device(prior.adj(x), dtype)), (lambda v: ops.as_device(prior.fwd(v), dtype))
+
+
+def _weighted_l1(U, T):
+    """``sum_i T_i |U_i|`` per chain through ``reduce_l1`` (T: python float or float64 device vector)"""
+    return ops.reduce_l1(U) * T if isinstance(T, float) else ops.reduce_l1(U, T)
+
+
+def analysis_prox(prior, Z, iters, sigma=None, return_dual=False):
+    """The prox of the analysis prior at ``Z``, ``argmin_p 1/2 ||p - Z||^2 + sum_i T_i |(A p)_i|`` (``A = prior.adj``,
+    ``A^H = prior.fwd``, ``T = prior.T``: the prox of ``lmda f`` that the samplers' drift takes), by ``iters`` iterations of
+    projected gradient on its dual from ``v = 0``::
+
+        v <- proj_{|v_i| <= T_i}(v + sigma A (Z - A^H v)),        returns Z - A^H v
+
+    ``sigma``: ``None`` takes ``1 / (||A||^2 (1 + tol))`` from :func:`operator_norm2` (1 for ``A = I``), found once per prior and state shape
+    and kept on the prior.  The tight-frame formula of ``L1.proxf`` is one such iteration at ``sigma = 1``, exact only when
+    ``A A^H = I``.  Cold-started and stateless: a pure function of ``Z`` on fixed launches (``ops.skrock_stage`` for
+    ``Z - A^H v``, ``ops.pd_dual_step`` with ``rscale = 1`` for the projection), so a captured graph replays it.
+    Returns the point in the caller's array kind; with ``return_dual`` also the dual ``v`` (device array)."""
+    z, squeeze = ops._batched(ops.as_device(Z))
+    A, AH = _analysis_pair(prior, z.dtype)
+    if sigma is None:
+        key = (z.shape[1], z.dtype)
+        cache = prior.__dict__.setdefault("_prox_sigma", {})
+        if key not in cache:
+            tol = PrimalDual.lipschitz_tol  # (A = I: the norm is known exactly, sigma = 1 and one iteration is the prox)
+            cache[key] = 1.0 if prior.fwd is None else 1.0 / (operator_norm2(prior.fwd, prior.adj, z.shape[1], z.dtype, tol=tol) * (1.0 + tol))
+        sigma = cache[key]
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError("analysis_prox needs a positive step sigma")
+    T = prior.T_dev
+    w = A(z)
+    v, v1 = torch.zeros_like(w), torch.empty_like(w)
+    p = z.clone()
+    if int(iters) > 0:
+        scratch = ops.pd_scratch(z.shape[0], z.device)
+        sums = torch.empty((z.shape[0], 3), dtype=torch.float64, device=z.device)
+        for k in range(int(iters)):
+            if k:
+                ops.skrock_stage(z, 1.0, e=-1.0, V=AH(v), out=p)
+                w = A(p)
+            ops.pd_dual_step(v, w, T, sigma, 1.0, out=v1, sums=sums, scratch=scratch)
+            v, v1 = v1, v
+        ops.skrock_stage(z, 1.0, e=-1.0, V=AH(v), out=p)
+    out = p[0] if squeeze else p
+    out = to_like(out, Z)
+    return (out, v[0] if squeeze else v) if return_dual else out
+
+
+class PrimalDual(Stepper):
+    """
+    MAP point of the analysis-setting posterior of ``(forward, prior, mcmcparams)``,
+
+        F(X) = g(X) + h(A X),   g = 1/2 Re L2,   h(u) = (1 / lmda) sum_i T_i |u_i|,   A = prior.adj,  A^H = prior.fwd,
+
+    by the forward-backward primal-dual iteration of Condat (2013) and Vu (2013)::
+
+        X1   = X - tau (calc_gradg(forward(X)) + A^H V)
+        Xbar = 2 X1 - X
+        V1   = proj_{|v_i| <= T_i / lmda}(V + sigma A Xbar)
+
+    which needs no prox of ``h o A`` and converges for ``1 / tau - sigma ||A||^2 >= L_g / 2``.  The two elementwise updates are
+    one HIP launch each (``pxm_pd_primal_step``, ``pxm_pd_dual_step``) around the four operator calls; the iteration is
+    replayed from a captured HIP graph between checks.
+
+    :param forward: an operator with ``setting == "analysis"`` (the state is the image)
+    :param prior: a prior with ``fwd``, ``adj`` and ``T`` (float, or a vector of the coefficient length), such as
+        ``L1("analysis", tr.inverse, tr.inverse_adjoint, T)``; ``fwd is None and adj is None``: ``A = I``
+    :param tau, sigma: the steps.  ``None``: ``sigma = balance L_g / (2 ||A||^2)``, ``tau = 1 / (L_g / 2 + sigma ||A||^2)``, with
+        ``L_g = gradient_lipschitz (1 + lipschitz_tol)`` and ``||A||^2 =`` :func:`operator_norm2` ``(1 + lipschitz_tol)`` (both
+        power iterations approach their value from below).  One given: the other follows from the condition with equality.
+        Given steps that violate the condition are refused
+    :param balance: ratio of the dual term ``sigma ||A||^2`` to ``L_g / 2`` in ``1 / tau``
+    :param tol: stop when ``||X1 - X|| <= tol ||X1||`` and ``||V1 - V|| <= tol ||V1||`` hold for every chain (a zero norm
+        counts as met)
+    :param max_iter, check_every, use_graph, nchains: as :class:`FISTA`
+
+    The gradient is taken on :func:`gradient_operator` ``(forward)``, as FISTA does.
+
+    After :meth:`run`: ``objective``, ``data_term``, ``prior_term`` (``reduce_l1(A X, T) / lmda``), ``rel_change``,
+    ``rel_change_dual`` and ``stationarity`` (arrays ``[nchecks, C]``; the last is ``||X1 - X|| / tau``, the norm of
+    ``gradg + A^H V`` at the previous iterate), ``checks``, ``niter``, ``converged``, ``X_map``, ``V_map`` (the dual
+    certificate: ``|V_i| <= T_i / lmda`` and ``gradg(X) + A^H V -> 0``), ``preds_map``, ``objective_map``, ``last_steps``
+    (``[C, 2]``: ``||X_K - X_{K-1}||`` and ``||V_K - V_{K-1}||``), ``used_graph``, ``tau``, ``sigma``, ``A_norm2``, ``L_g``.
+    """
+
+    lipschitz_tol = 1e-4
+
+    def __init__(self, forward, prior, mcmcparams=PxMCMCParams(), nchains=1, tau=None, sigma=None, balance=1.0, max_iter=10000,
+                 tol=1e-4, check_every=10, use_graph=True):
+        if getattr(forward, "setting", None) != "analysis":
+            raise ValueError('PrimalDual needs an analysis-setting operator (forward.setting == "analysis"); FISTA solves the '
+                             "synthesis setting")
+        if not all(hasattr(prior, a) for a in ("fwd", "adj", "T")) or prior.T is None:
+            raise ValueError("PrimalDual needs a prior with fwd, adj and the threshold T (an L1 in the analysis setting)")
+        if (prior.fwd is None) != (prior.adj is None):
+            raise ValueError("PrimalDual: the prior's fwd and adj are given together (both None: A = I)")
+        if getattr(prior, "setting", "analysis") != "analysis":
+            raise ValueError('PrimalDual needs an analysis prior (prior.setting == "analysis")')
+        super().__init__(forward, prior, mcmcparams, nchains=nchains, use_graph=use_graph)
+        if int(max_iter) < 1 or int(check_every) < 1:
+            raise ValueError("PrimalDual needs max_iter >= 1 and check_every >= 1")
+        if not (np.isfinite(balance) and balance > 0):
+            raise ValueError("PrimalDual needs a positive balance")
+        self.gradient_op = gradient_operator(forward)
+        dt, n = self._state_dtype(), int(forward.nparams)
+        self._A, self._AH = _analysis_pair(prior, dt)
+        self.ncoefs = int(self._A(torch.zeros((1, n), dtype=dt, device=ops.device())).shape[-1])
+        T = prior.T_dev if hasattr(prior, "T_dev") else (float(prior.T) if np.ndim(prior.T) == 0 else
+                                                          ops.as_device(np.asarray(prior.T, dtype=float), torch.float64))
+        if not isinstance(T, float) and T.numel() != self.ncoefs:
+            raise ValueError(f"PrimalDual: T has {T.numel()} entries, the coefficients A X have {self.ncoefs}")
+        self._T = T
+        tl = self.lipschitz_tol
+        self.L_g = float(self.gradient_op.gradient_lipschitz(iters=1000, tol=tl) * (1.0 + tl))
+        identity = prior.fwd is None
+        self.A_norm2 = 1.0 if identity else float(operator_norm2(prior.fwd, prior.adj, n, dt, tol=tl) * (1.0 + tl))
+        if not (self.L_g > 0 and self.A_norm2 > 0):
+            raise ValueError("PrimalDual: the data term and the analysis operator must not vanish")
+        half, a2 = 0.5 * self.L_g, self.A_norm2
+        if tau is None:
+            sigma = balance * half / a2 if sigma is None else float(sigma)
+            tau = 1.0 / (half + sigma * a2) if np.isfinite(sigma) and sigma > 0 else np.nan
+        elif sigma is None:
+            sigma = (1.0 / tau - half) / a2 if np.isfinite(tau) and tau > 0 else np.nan
+        if not (np.isfinite(tau) and tau > 0 and np.isfinite(sigma) and sigma > 0 and 1.0 / tau - sigma * a2 >= half * (1 - 1e-12)):
+            raise ValueError(f"PrimalDual: the steps must be positive with 1 / tau - sigma ||A||^2 >= L_g / 2 (tau = {tau:g}, sigma = "
+                             f"{sigma:g}, ||A||^2 = {a2:g}, L_g = {self.L_g:g})")
+        self.tau, self.sigma, self.balance = float(tau), float(sigma), float(balance)
+        self.max_iter = int(max_iter)
+        self.tol = float(tol)
+        self.check_every = int(check_every)
+
+    def _engine_start(self, X, preds, i0):
+        """static state (XA, XB, P) plus the dual in VA / VB -- V of the state in XA lives in VA, of XB in VB -- Xbar, and the
+        per-chain sums of the two launches by the side they wrote"""
+        self._engine_stop()
+        X = ops.as_device(X).contiguous()
+        f, tau, sigma, rscale, T, A, AH = self.gradient_op, self.tau, self.sigma, 1.0 / self.lmda, self._T, self._A, self._AH
+        C = X.shape[0]
+        VA = torch.zeros((C, self.ncoefs), dtype=X.dtype, device=X.device)
+        VB, Xbar = torch.empty_like(VA), torch.empty_like(X)
+        self._V = (VA, VB)
+        # sums of the step that wrote XA (VA) in [0], of the step that wrote XB (VB) in [1]
+        self._psums = torch.zeros((2, C, 2), dtype=torch.float64, device=X.device)
+        self._dsums = torch.zeros((2, C, 3), dtype=torch.float64, device=X.device)
+        scratch = ops.pd_scratch(C, X.device)
+
+        def step(eng, src, dst):
+            V, V_next = (VA, VB) if src is eng.XA else (VB, VA)
+            k = 0 if dst is eng.XA else 1
+            g = ops.as_device(f.calc_gradg(ops.as_device(f.forward(src))), src.dtype)
+            ops.pd_primal_step(src, g, AH(V), tau, out=(dst, Xbar), sums=self._psums[k], scratch=scratch)
+            ops.pd_dual_step(V, A(Xbar), T, sigma, rscale, out=V_next, sums=self._dsums[k], scratch=scratch)
+
+        def reset(eng):
+            VA.zero_()
+            self._psums.zero_()
+            self._dsums.zero_()
+
+        return self._engine_start_generic(X, preds, i0, step, lazy=True, graph_ok=self.use_graph, reset=reset)
+
+    def run(self, start_point=None):
+        """Iterate from ``start_point`` (``[N]``, or ``[C, N]`` with one row per chain; ``None``: zero) and ``V = 0`` until every
+        chain meets the stopping rule or ``max_iter`` is reached.  Returns the MAP image in the caller's array kind (numpy,
+        or a device tensor for a tensor start point): ``[N]`` for one chain, ``[C, N]`` for a batch."""
+        C = self.nchains
+        as_torch = isinstance(start_point, torch.Tensor)
+        if start_point is None:
+            start_point = np.zeros(self.forward.nparams)
+        X, preds = self._initial_sample(start_point)
+        self._engine_start(X, preds, 0)
+        keys = ("objective", "data_term", "prior_term", "rel_change", "rel_change_dual", "stationarity")
+        traces = {k: [] for k in keys}
+        self.checks = []
+        niter = np.zeros(C, dtype=int)
+        met = np.zeros(C, dtype=bool)
+        try:
+            i = 0
+            while i < self.max_iter:
+                k = min(self.check_every, self.max_iter - i)
+                self._engine_advance(k)
+                i += k
+                X, preds = self._engine_state()  # forward(X) is formed here, where the state is observed
+                self._check_device_status()
+                last = 0 if self._eng.side == "A" else 1
+                ps, ds = self._psums[last].cpu().numpy(), self._dsums[last].cpu().numpy()
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    rel_x = np.where(ps[:, 0] == 0.0, 0.0, np.sqrt(ps[:, 0]) / np.sqrt(ps[:, 1]))
+                    rel_v = np.where(ds[:, 0] == 0.0, 0.0, np.sqrt(ds[:, 0]) / np.sqrt(ds[:, 1]))
+                data_term = 0.5 * self._l2_dev(preds).real.cpu().numpy()
+                prior_term = _weighted_l1(self._A(X), self._T).cpu().numpy() / self.lmda
+                now = (rel_x <= self.tol) & (rel_v <= self.tol)
+                niter = np.where(now & met, niter, i)  # iterations done when the chain first met (and kept) the rule
+                met = now
+                self.checks.append(i)
+                for key, v in zip(keys, (data_term + prior_term, data_term, prior_term, rel_x, rel_v, np.sqrt(ps[:, 0]) / self.tau)):
+                    traces[key].append(np.array(v, dtype=float))
+                if met.all():
+                    break
+            self.X_map, self.preds_map, self.V_map = X.clone(), preds.clone(), self._V[last].clone()
+            self.last_steps = np.sqrt(np.stack([ps[:, 0], ds[:, 0]], axis=1))
+            self.used_graph = self._eng.graph is not None
+            self.graph_error = self._eng.graph_error
+        finally:
+            self._engine_stop()
+            self._V = None
+        for key, rows in traces.items():
+            setattr(self, key, np.stack(rows))
+        self.niter, self.converged = niter, met
         self.objective_map = self.objective[-1]
         out = self.X_map if C > 1 else self.X_map[0]
         return out.clone() if as_torch else out.cpu().numpy()

@@ -65,6 +65,40 @@ def _is_stock_l1(prior):
     return isinstance(prior, L1) and type(prior).proxf is L1.proxf and type(prior)._proxf_synthesis is L1._proxf_synthesis and prior.setting == "synthesis"
 
 
+class L1_Analysis(L1):
+    """
+    Analysis-setting L1 prior ``sum_i T_i |(A X)_i|`` (``A = adj``, ``A^H = fwd``) with its exact prox (extension; DESIGN.md
+    section 14d).  ``L1("analysis", ...)`` applies the tight-frame formula ``X + A^H (soft(A X) - A X)`` of the reference
+    (pxmcmc/prior.py:52-53), which is the prox only when ``A A^H = I``; this class runs ``prox_iters`` iterations of
+    projected gradient on the prox's dual (:func:`pxmcmc_amd.optim.analysis_prox`): fixed launches and no host read, so the
+    samplers replay it from their captured graph.
+
+    :param fwd: ``A^H``, coefficients -> state (e.g. ``Transform.inverse``)
+    :param adj: ``A``, state -> coefficients (e.g. ``Transform.inverse_adjoint``)
+    :param T: threshold, float or vector of the coefficient length
+    :param prox_iters: dual iterations per prox
+    """
+
+    def __init__(self, fwd, adj, T, prox_iters=16):
+        super().__init__("analysis", fwd, adj, T)
+        if int(prox_iters) < 1:
+            raise ValueError("L1_Analysis needs prox_iters >= 1")
+        self.prox_iters = int(prox_iters)
+
+    def prior(self, X):
+        """sum_i T_i |(A X)_i| per chain; float for one chain, float64 tensor [C] for a batch (as ``L1.prior``)."""
+        x = ops.as_device(X)
+        u = x if self.adj is None else ops.as_device(self.adj(x))
+        T = self.T_dev
+        r = ops.reduce_l1(u) * T if isinstance(T, float) else ops.reduce_l1(u, T)
+        return r if x.dim() == 2 else float(r[0])
+
+    def proxf(self, X):
+        from .optim import analysis_prox  # (optim imports the samplers, which import this module)
+
+        return analysis_prox(self, X, self.prox_iters)
+
+
 class S2_Wavelets_L1(L1):
     """
     L1 regulariser for wavelets on S2 with MW quadrature weighting (pxmcmc/prior.py:56-84).
