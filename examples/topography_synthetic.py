@@ -15,6 +15,10 @@ the two files are equal.
 ``--analysis-map`` runs no chain: it finds the MAP image of the analysis-setting posterior by primal-dual splitting
 (``pxmcmc_amd.optim.PrimalDual``) and writes it as ``analysis_map_<jobid>.npy``; ``--mu`` scales the prior,
 ``--analysis-balance`` the ratio of the two steps.
+
+``--tv-map`` does the same with the total-variation prior ``pxmcmc_amd.prior.TV_S2`` on the image itself (no wavelet plan) and
+writes ``tv_map_<jobid>.npy``; ``--tv`` samples that posterior in the analysis setting (``--algo`` as usual) and writes the
+posterior mean and the credible-interval map.  ``--tv-strength`` is the threshold T per unit of ``lmda * mu``.
 """
 import argparse
 import copy
@@ -27,12 +31,14 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from pxmcmc_amd import ops  # noqa: E402
-from pxmcmc_amd.forward import SphericalWaveletTransformOperator  # noqa: E402
+from pxmcmc_amd.forward import ForwardOperator, SphericalWaveletTransformOperator  # noqa: E402
+from pxmcmc_amd.measurements import Identity  # noqa: E402
 from pxmcmc_amd.mcmc import MYULA, SKROCK, PxMALA, PxMCMCParams  # noqa: E402
 from pxmcmc_amd.optim import FISTA, PrimalDual  # noqa: E402
-from pxmcmc_amd.prior import L1, S2_Wavelets_L1  # noqa: E402
+from pxmcmc_amd.prior import L1, S2_Wavelets_L1, TV_S2  # noqa: E402
 from pxmcmc_amd.sapg import SAPG  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
+from pxmcmc_amd.transforms import IdentityTransform  # noqa: E402
 from pxmcmc_amd.uncertainty import (chain_to_images, credible_interval_range, hypothesis_test, local_credible_intervals,  # noqa: E402
                                     superpixel_regions)
 from pxmcmc_amd.utils import _multires_bandlimits  # noqa: E402
@@ -74,6 +80,60 @@ def analysis_map(data, args, L, B, J_min, truth):
           f"{est.objective_map[0]:.6e} = {est.data_term[-1, 0]:.6e} + {est.prior_term[-1, 0]:.6e}, stationarity "
           f"{est.stationarity[-1, 0]:.3e}; error against the truth {rel:.3f} (noise {args.sigma:.3f}); image in {path}")
     return path, rel, est
+
+
+def tv_operators(data, args, L, lmda, prox_iters=16):
+    """the analysis-setting operator whose state is the image itself (identity measurement, float64 state for real data) and
+    the isotropic TV prior on the MW grid"""
+    P = data.size
+    forwardop = ForwardOperator(data, args.sigma, "analysis", IdentityTransform(), Identity(P, P), nparams=P)
+    return forwardop, TV_S2(L, lmda * args.mu * args.tv_strength, prox_iters=prox_iters)
+
+
+def tv_map(data, args, L, truth):
+    """--tv-map: the MAP image of 1/2 Re L2(x) + (1 / lmda) T TV(x) by primal-dual splitting on the fused TV launches.
+    Writes the image beside the run."""
+    lmda = 1e-3
+    forwardop, regulariser = tv_operators(data, args, L, lmda)
+    params = PxMCMCParams(lmda=lmda, mu=args.mu, verbosity=0)
+    est = PrimalDual(forwardop, regulariser, params, balance=args.analysis_balance, tol=1e-6, max_iter=20000)
+    x = est.run(start_point=np.zeros(forwardop.nparams))
+    rel = np.sqrt(np.mean(np.abs(x.real - truth) ** 2)) / np.sqrt(np.mean(np.abs(truth) ** 2))
+    path = os.path.join(args.outdir, f"tv_map_{args.jobid}.npy")
+    np.save(path, x.real)
+    print(f"TV MAP: tau = {est.tau:.4e}, sigma = {est.sigma:.4e} (||A||^2 = {est.A_norm2:.4e}, L_g = {est.L_g:.4e}); "
+          f"{int(est.niter[0])} iterations (converged: {bool(est.converged[0])}, graph replay: {est.used_graph}, fused launches: "
+          f"{est.fused}), objective {est.objective_map[0]:.6e} = {est.data_term[-1, 0]:.6e} + {est.prior_term[-1, 0]:.6e}, "
+          f"stationarity {est.stationarity[-1, 0]:.3e}; error against the truth {rel:.3f} (noise {args.sigma:.3f}); image in {path}")
+    return path, rel, est
+
+
+def tv_sample(data, args, L, truth):
+    """--tv: sample the TV posterior in the analysis setting on the generic stepping engine; the prox is the exact one
+    (TV_S2.proxf), replayed from the captured graph.  Writes the chain, the posterior mean and the credible-interval map."""
+    lmda = 1e-3
+    forwardop, regulariser = tv_operators(data, args, L, lmda)
+    delta = 0.8 / (1.0 / args.sigma ** 2 + 1.0 / lmda)
+    if args.algo == "skrock":
+        delta *= args.s ** 2
+    params = PxMCMCParams(nsamples=args.nsamples, nburn=args.nburn, ngap=args.ngap, delta=delta, lmda=lmda, mu=args.mu, s=args.s,
+                          verbosity=max(1, args.ngap * 10))
+    cls = {"myula": MYULA, "pxmala": PxMALA, "skrock": SKROCK}[args.algo]
+    mcmc = cls(forwardop, regulariser, params, nchains=args.chains)
+    start = datetime.now()
+    mcmc.run(start_point=np.asarray(data, dtype=float).copy())
+    elapsed = datetime.now() - start
+    base = os.path.join(args.outdir, f"{args.algo}_tv_{args.jobid}")
+    path = save_mcmc(mcmc, params, args.outdir, filename=f"{args.algo}_tv_{args.jobid}", L=L, sigma=args.sigma,
+                     nparams=forwardop.nparams, setting="analysis", time=str(elapsed), chains=args.chains)
+    images = np.asarray(mcmc.chain if args.chains == 1 else mcmc.chain[0]).real  # the state is the image
+    mean, ci = images.mean(axis=0), credible_interval_range(images)
+    np.save(base + "_mean.npy", mean)
+    np.save(base + "_ci.npy", ci)
+    rel = np.sqrt(np.mean(np.abs(mean - truth) ** 2)) / np.sqrt(np.mean(np.abs(truth) ** 2))
+    print(f"saved {path}; {mcmc.niter} iterations x {args.chains} chain(s) in {elapsed} (graph replay: {mcmc.used_graph}); "
+          f"posterior-mean error {rel:.3f} (noise {args.sigma:.3f}); median 95% CI width {np.median(ci):.3f}")
+    return path, rel, ci
 
 
 def local_ci_maps(forwardop, regulariser, params, x_map, L, size, base):
@@ -155,6 +215,12 @@ def main(argv=None):
                          "and write it; no chain is run")
     ap.add_argument("--analysis-balance", type=float, default=1.0, metavar="R",
                     help="with --analysis-map: the ratio sigma ||A||^2 / (L_g / 2) of the two steps (PrimalDual's balance)")
+    ap.add_argument("--tv-map", action="store_true",
+                    help="only find the MAP image under the total-variation prior TV_S2 by primal-dual splitting (spin 0) and "
+                         "write it; no chain is run")
+    ap.add_argument("--tv", action="store_true", help="sample the image under the total-variation prior TV_S2 (spin 0)")
+    ap.add_argument("--tv-strength", type=float, default=1.0, metavar="T",
+                    help="with --tv-map / --tv: the TV threshold per unit of lmda * mu")
     ap.add_argument("--local-ci", type=int, default=None, metavar="SIZE",
                     help="with --map-start: local credible intervals of the MAP point on superpixels of SIZE x SIZE samples")
     ap.add_argument("--hyp-test", type=int, default=None, metavar="SIZE",
@@ -220,6 +286,11 @@ def main(argv=None):
         if spin != 0 or args.dirs != 1:
             ap.error("--analysis-map takes spin 0 and dirs 1")
         return analysis_map(data, args, L, B, J_min, truth)
+
+    if args.tv_map or args.tv:
+        if spin != 0:
+            ap.error("--tv-map and --tv take spin 0")
+        return (tv_map if args.tv_map else tv_sample)(data, args, L, truth)
 
     forwardop = SphericalWaveletTransformOperator(data, args.sigma, setting, L, B, J_min, dirs=args.dirs, spin=spin,
                                                  max_chains=args.chains)

@@ -513,6 +513,39 @@ int pxm_pd_primal_step(const void* X, const void* G, const void* U, double tau, 
                        double* sums, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream);
 int pxm_pd_dual_step(const void* V, const void* W, const double* T, double T_scalar, double sigma, double rscale,
                      void* V1_out, double* sums, double* scratch, int64_t m, int C, int dtype, pxm_stream_t stream);
+/* Total variation on the MW grid.  Images are spin-0 MW maps [C][L n], n = 2L - 1, float64 or
+ * complex128; coefficients are plane-major per chain, [C][2][L n].  ab: float64 [2][L] on the device, the ring coefficients
+ * a_t = q_t / D, b_t = q_t / (D sin theta_t) for t < L - 1 and a_{L-1} = b_{L-1} = 0, with q_t the ring weights of
+ * pxm_mw_ring_weights, D = 2 pi / n and theta_t = pi (2t + 1) / n (the quadrature weight is folded into the operator).
+ *   (A x)[0][t][p] = a_t (x[t+1][p] - x[t][p])                 (A x)[1][t][p] = b_t (x[t][(p+1) mod n] - x[t][p])
+ *   (A^H v)[t][p]  = a_{t-1} v0[t-1][p] - a_t v0[t][p] + b_t (v1[t][(p-1) mod n] - v1[t][p]),   a_{-1} = 0
+ * Per real component A rounds the difference and the product; A^H is fma(a_{t-1}, v0[t-1], fma(-a_t, v0[t], s)) with
+ * s = b_t (v1[t][p-1] - v1[t][p]), difference and product rounded.  A row that does not exist is not read.
+ * pxm_tv_grad: out = A x.   pxm_tv_grad_adjoint: out = A^H v.
+ * pxm_tv_value: out[c] = sum_i T_i sqrt(|(A x)[0]_i|^2 + |(A x)[1]_i|^2) (squares and sums rounded one by one; T [L n]
+ *   shared by chains, or T_scalar), formed from the image with no coefficient array.  scratch: PXM_FISTA_SLICES_MAX * C.
+ * pxm_pd_dual_step_pairs: pxm_pd_dual_step on V, W, V1_out [C][2][m] with the projection onto the pair norm:
+ *   w = fma(sigma, W, V) per component;  r_i = T_i rscale;  a = sqrt(sum of the squares of the pair's 2 (real) or 4 (complex)
+ *   components);  V1_out = a > r_i ? w (r_i / a) : w on both planes (a == r_i and a == 0 keep w, T_i == 0 gives 0, r_i = inf
+ *   never binds);  T is [m] or T_scalar;  sums [C][3] = sum |V1_out - V|^2, sum |V1_out|^2 (both planes), sum_i T_i ||W_i||.
+ *   m <= 2^30.  scratch: 3 * PXM_FISTA_SLICES_MAX * C doubles.
+ * pxm_tv_primal_step: pxm_pd_primal_step with U = A^H V formed in the kernel (same arithmetic, same sums [C][2]).  G may be
+ *   NULL (zero) and Xbar_out may be NULL (not written): with both and tau = 1 it is X - A^H V.
+ * pxm_tv_dual_step: pxm_pd_dual_step_pairs with W = A Xbar formed in the kernel, m = L n.
+ * The fused steps equal the composed ones bit for bit, sums included.  2 <= L <= 16384, C <= 65535, positive finite steps; an
+ * output must not overlap an input or the other output (only equal base pointers are detected and refused).  The sums are
+ * added in a fixed order that depends on L (m) only.  No atomics and no host read: a HIP graph replays all of them. */
+int pxm_tv_grad(const void* x, const double* ab, void* out, int L, int C, int dtype, pxm_stream_t stream);
+int pxm_tv_grad_adjoint(const void* v, const double* ab, void* out, int L, int C, int dtype, pxm_stream_t stream);
+int pxm_tv_value(const void* x, const double* ab, const double* T, double T_scalar, double* out, double* scratch, int L,
+                 int C, int dtype, pxm_stream_t stream);
+int pxm_pd_dual_step_pairs(const void* V, const void* W, const double* T, double T_scalar, double sigma, double rscale,
+                           void* V1_out, double* sums, double* scratch, int64_t m, int C, int dtype, pxm_stream_t stream);
+int pxm_tv_primal_step(const void* X, const void* G, const void* V, const double* ab, double tau, void* X1_out,
+                       void* Xbar_out, double* sums, double* scratch, int L, int C, int dtype, pxm_stream_t stream);
+int pxm_tv_dual_step(const void* V, const void* Xbar, const double* ab, const double* T, double T_scalar, double sigma,
+                     double rscale, void* V1_out, double* sums, double* scratch, int L, int C, int dtype,
+                     pxm_stream_t stream);
 /* One SAPG iteration (Vidal, De Bortoli, Pereyra & Durmus 2020): a MYULA step of every chain on the
  * posterior whose prior is scaled by the chain's theta, then the move of theta towards the marginal maximum-likelihood
  * value of the regularisation strength.  Every state array [C][n]; theta, eta [C] float64 on the device, updated in place.

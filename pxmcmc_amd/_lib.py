@@ -171,6 +171,12 @@ SIGNATURES = {
     ),
     "pxm_pd_primal_step": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_pd_dual_step": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_tv_grad": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "pxm_tv_grad_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "pxm_tv_value": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "pxm_pd_dual_step_pairs": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_tv_primal_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "pxm_tv_dual_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "pxm_lci_scratch_doubles": (c_i64, [c_i64, c_int]),
     "pxm_lci_data_terms": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_lci_eval": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),

@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..prior import L1
+from ..prior import L1, L1_Analysis
 from .engine import _Counter, capture
 from .myula import MYULA
 from .params import PxMCMCParams
@@ -89,7 +89,8 @@ class PxMALA(MYULA):
 
     One iteration is a fixed sequence of device operations on the static buffers of a ``_PxmalaState``, by the route
     chosen once per run (``_route``): ``_iteration_fused`` or ``_iteration_separate`` (the library's own prior), or
-    ``_iteration_plugin`` (a user-supplied prior or ``chain_step``).  ``run`` keeps the schedule: a chain saves on an
+    ``_iteration_plugin`` (a user-supplied prior or ``chain_step``; replayed from a graph too when the prior is the library's
+    exact analysis prox, ``_plugin_replayable``).  ``run`` keeps the schedule: a chain saves on an
     accepted candidate.
 
     :param bool tune_delta: tune ``delta`` towards an acceptance probability of 0.5
@@ -186,13 +187,18 @@ class PxMALA(MYULA):
         if bump is not None:
             st.cnt.add(1)
 
+    def _plugin_replayable(self):
+        """the plugin route on fixed launches with no host read: the library's exact analysis prox (``prior.L1_Analysis`` and
+        its subclasses, ``prior.TV_S2`` among them) under the library's own chain step"""
+        return isinstance(self.prior, L1_Analysis) and not self._own_step
+
     def _iteration_plugin(self, st, i_host, counter, bump=None):
         """user-supplied prior / chain_step: the reference's own sequence of calls (pxmcmc/mcmc.py:231-242)"""
         dt, kw = st.X.dtype, self._philox_kw(i_host)
         noise = self._draw_noise(st)  # (drawn whoever steps: the stream does not depend on the route)
         if not self._own_step:
             Xp = ops.chain_step(st.X, st.proxf, st.gradg, st.delta, self.lmda, noise=noise,
-                                noise_complex=bool(self.complex), noise64=self.noise64, **kw)
+                                noise_complex=bool(self.complex), noise64=self.noise64, iter_dev=counter, **kw)
         else:
             Xp = ops.as_device(self.chain_step(st.X, st.proxf, st.gradg), dt)
         pxp = ops.as_device(self.prior.proxf(Xp), dt)
@@ -201,6 +207,8 @@ class PxMALA(MYULA):
         if not isinstance(prp, torch.Tensor):
             prp = torch.as_tensor(np.atleast_1d(np.asarray(prp, dtype=float)), device=ops.device())
         self._tail_separate(st, counter, kw, Xp, pxp, ltc, prp.to(torch.float64).contiguous())
+        if bump is not None:
+            st.cnt.add(1)
 
     def _tail_separate(self, st, counter, kw, Xp, pxp, ltc, prp):
         """from the proposal's forward model to the conditional copy of the accepted states, one call per step"""
@@ -215,11 +223,12 @@ class PxMALA(MYULA):
         ops.select_copy_many(st.accept, [(Xp, st.X), (pp.to(st.preds.dtype), st.preds), (gp, st.gradg), (pxp, st.proxf)])
 
     def _capture(self, st, route, iteration):
-        """HIP graph of one iteration reading the device counter, which it advances itself (device Philox stream and stock
-        prior only; any operator that synchronises or cannot be captured falls back to eager stepping -- same results)"""
+        """HIP graph of one iteration reading the device counter, which it advances itself (device Philox stream; the stock
+        prior, or the library's exact analysis prox on the plugin route; any operator that synchronises or cannot be captured
+        falls back to eager stepping -- same results)"""
         self.graph_error = None
         graph = None
-        if self.use_graph and self.rng != "numpy" and route != "plugin":
+        if self.use_graph and self.rng != "numpy" and (route != "plugin" or self._plugin_replayable()):
             snap = [t.clone() for t in st.current()]
 
             def restore():

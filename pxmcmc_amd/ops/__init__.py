@@ -8,7 +8,7 @@ SURVEY.md section 8b).
 
 One module per concern, as the kernel files are: ``steps`` (elementwise.hip, skrock.hip, fista.hip, primal_dual.hip, sapg.hip), ``reduce``
 (reduce.hip), ``pxmala`` (pxmala.hip), ``summary`` (moments.hip, tails.hip, acov.hip), ``lci`` (lci.hip), ``inpaint`` (inpaint.hip),
-``sparse`` (spmv.hip), ``plans`` (the plan sources), ``host`` (tables.cpp, host_api.cpp); ``_args`` holds what they do to their arguments
+``tv`` (tv.hip), ``sparse`` (spmv.hip), ``plans`` (the plan sources), ``host`` (tables.cpp, host_api.cpp); ``_args`` holds what they do to their arguments
 and the checks they share.  Callers use the names below as ``ops.<name>``.
 """
 # flake8: noqa: F401  (every import below is a re-export)
@@ -27,5 +27,6 @@ from .sparse import CsrMatrix
 from .steps import (box_muller, chain_step, counter_add, fista_restart_scratch, fista_scratch, fista_step, fista_step_restart,
                     myula_step, pd_dual_step, pd_primal_step, pd_scratch, randn, residual_grad, sapg_group_bounds, sapg_groups_scratch, sapg_scratch, sapg_step,
                     sapg_step_groups, select_copy_many, skrock_stage, soft)
+from .tv import pd_dual_step_pairs, tv_dual_step, tv_grad, tv_grad_adjoint, tv_primal_step, tv_ring_coefs, tv_value
 from .summary import (acov_ess, acov_stage_depth, acov_update, moments_finalize, moments_update, tails_quantiles,
                       tails_stage_depth, tails_update)

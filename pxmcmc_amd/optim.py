@@ -15,6 +15,11 @@ In the analysis setting the prior acts on ``A X`` (``A = prior.adj``, ``A^H = pr
 prox unless ``A A^H = I``: :class:`PrimalDual` minimises ``g(X) + (1 / lmda) sum_i T_i |(A X)_i|`` exactly by primal-dual
 splitting on two fused HIP launches per iteration, and :func:`analysis_prox` is the exact prox of the analysis prior
 (DESIGN.md section 14d).  ``optim_np`` states both in numpy.
+
+A prior with ``pairs = True`` (isotropic total variation, ``prior.TV_S2``) has two-plane coefficients
+``[C, 2 m]`` and takes the norm over a pixel's pair: ``h(u) = (1 / lmda) sum_i T_i ||u_i||``, ``T`` a float or ``[m]``.  Both
+solvers then project pair by pair (``ops.pd_dual_step_pairs``), and run on the prior's own fused launches when it offers them
+(``fused_primal_step``, ``fused_dual_step``).  ``tv_np`` states the pair forms in numpy.
 """
 import copy
 import warnings
@@ -256,7 +261,20 @@ def _weighted_l1(U, T):
     return ops.reduce_l1(U) * T if isinstance(T, float) else ops.reduce_l1(U, T)
 
 
-def analysis_prox(prior, Z, iters, sigma=None, return_dual=False):
+def _is_pairs(prior):
+    return bool(getattr(prior, "pairs", False))
+
+
+def _has_fused_steps(prior):
+    return _is_pairs(prior) and hasattr(prior, "fused_primal_step") and hasattr(prior, "fused_dual_step")
+
+
+def _weighted_pairs(U, T):
+    """``sum_i T_i ||U_i||`` per chain for two-plane coefficients ``[C, 2 m]``: the third sum of ``ops.pd_dual_step_pairs``"""
+    return ops.pd_dual_step_pairs(torch.zeros_like(U), U, T, 1.0, 1.0)[1][:, 2]
+
+
+def analysis_prox(prior, Z, iters, sigma=None, return_dual=False, fused=True):
     """The prox of the analysis prior at ``Z``, ``argmin_p 1/2 ||p - Z||^2 + sum_i T_i |(A p)_i|`` (``A = prior.adj``,
     ``A^H = prior.fwd``, ``T = prior.T``: the prox of ``lmda f`` that the samplers' drift takes), by ``iters`` iterations of
     projected gradient on its dual from ``v = 0``::
@@ -267,18 +285,15 @@ def analysis_prox(prior, Z, iters, sigma=None, return_dual=False):
     and kept on the prior.  The tight-frame formula of ``L1.proxf`` is one such iteration at ``sigma = 1``, exact only when
     ``A A^H = I``.  Cold-started and stateless: a pure function of ``Z`` on fixed launches (``ops.skrock_stage`` for
     ``Z - A^H v``, ``ops.pd_dual_step`` with ``rscale = 1`` for the projection), so a captured graph replays it.
+    A prior with ``pairs`` is projected pair by pair (``ops.pd_dual_step_pairs``, ``T`` per pixel), and with ``fused`` the
+    iteration runs on the prior's fused launches when it has them: two launches per iteration, no coefficient-sized
+    temporaries, the same bits.
     Returns the point in the caller's array kind; with ``return_dual`` also the dual ``v`` (device array)."""
     z, squeeze = ops._batched(ops.as_device(Z))
+    if _is_pairs(prior):
+        return _analysis_prox_pairs(prior, Z, z, squeeze, iters, sigma, return_dual, fused and _has_fused_steps(prior))
     A, AH = _analysis_pair(prior, z.dtype)
-    if sigma is None:
-        key = (z.shape[1], z.dtype)
-        cache = prior.__dict__.setdefault("_prox_sigma", {})
-        if key not in cache:
-            tol = PrimalDual.lipschitz_tol  # (A = I: the norm is known exactly, sigma = 1 and one iteration is the prox)
-            cache[key] = 1.0 if prior.fwd is None else 1.0 / (operator_norm2(prior.fwd, prior.adj, z.shape[1], z.dtype, tol=tol) * (1.0 + tol))
-        sigma = cache[key]
-    if not (np.isfinite(sigma) and sigma > 0):
-        raise ValueError("analysis_prox needs a positive step sigma")
+    sigma = _prox_sigma(prior, z, sigma)
     T = prior.T_dev
     w = A(z)
     v, v1 = torch.zeros_like(w), torch.empty_like(w)
@@ -295,6 +310,56 @@ def analysis_prox(prior, Z, iters, sigma=None, return_dual=False):
         ops.skrock_stage(z, 1.0, e=-1.0, V=AH(v), out=p)
     out = p[0] if squeeze else p
     out = to_like(out, Z)
+    return (out, v[0] if squeeze else v) if return_dual else out
+
+
+def _prox_sigma(prior, z, sigma):
+    """the dual step of :func:`analysis_prox`: the given one checked, or ``1 / (||A||^2 (1 + tol))``, kept on the prior"""
+    if sigma is None:
+        key = (z.shape[1], z.dtype)
+        cache = prior.__dict__.setdefault("_prox_sigma", {})
+        if key not in cache:
+            tol = PrimalDual.lipschitz_tol  # (A = I: the norm is known exactly, sigma = 1 and one iteration is the prox)
+            cache[key] = 1.0 if prior.fwd is None else 1.0 / (operator_norm2(prior.fwd, prior.adj, z.shape[1], z.dtype, tol=tol) * (1.0 + tol))
+        sigma = cache[key]
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError("analysis_prox needs a positive step sigma")
+    return sigma
+
+
+def _analysis_prox_pairs(prior, Z, z, squeeze, iters, sigma, return_dual, fused):
+    """:func:`analysis_prox` for a prior with ``pairs``: the same iteration with the pair projection; ``fused``: ``Z - A^H v``
+    and ``A (.)`` are formed inside the prior's two launches"""
+    sigma = _prox_sigma(prior, z, sigma)
+    T = prior.T_dev
+    A, AH = _analysis_pair(prior, z.dtype)
+    C = z.shape[0]
+    p = z.clone()
+    scratch = ops.pd_scratch(C, z.device)
+    sums = torch.empty((C, 3), dtype=torch.float64, device=z.device)
+    if fused:
+        psums = torch.empty((C, 2), dtype=torch.float64, device=z.device)
+        v = torch.zeros((C, 2 * z.shape[1]), dtype=z.dtype, device=z.device)
+        v1 = torch.empty_like(v)
+        for k in range(int(iters)):
+            if k:
+                prior.fused_primal_step(z, None, v, 1.0, out=p, xbar=False, sums=psums, scratch=scratch)
+            prior.fused_dual_step(v, p if k else z, T, sigma, 1.0, out=v1, sums=sums, scratch=scratch)
+            v, v1 = v1, v
+        if int(iters) > 0:
+            prior.fused_primal_step(z, None, v, 1.0, out=p, xbar=False, sums=psums, scratch=scratch)
+    else:
+        w = A(z)
+        v, v1 = torch.zeros_like(w), torch.empty_like(w)
+        for k in range(int(iters)):
+            if k:
+                ops.skrock_stage(z, 1.0, e=-1.0, V=AH(v), out=p)
+                w = A(p)
+            ops.pd_dual_step_pairs(v, w, T, sigma, 1.0, out=v1, sums=sums, scratch=scratch)
+            v, v1 = v1, v
+        if int(iters) > 0:
+            ops.skrock_stage(z, 1.0, e=-1.0, V=AH(v), out=p)
+    out = to_like(p[0] if squeeze else p, Z)
     return (out, v[0] if squeeze else v) if return_dual else out
 
 
@@ -325,6 +390,14 @@ class PrimalDual(Stepper):
     :param tol: stop when ``||X1 - X|| <= tol ||X1||`` and ``||V1 - V|| <= tol ||V1||`` hold for every chain (a zero norm
         counts as met)
     :param max_iter, check_every, use_graph, nchains: as :class:`FISTA`
+    :param fused: with a prior that has ``pairs`` and its own fused launches (``prior.TV_S2``): form ``A^H V`` and ``A Xbar``
+        inside the two step launches (two launches per iteration beside the data term, no coefficient-sized temporaries).
+        ``False`` keeps the composed route -- ``A``, ``A^H``, ``pd_primal_step``, ``pd_dual_step_pairs`` -- which gives the same
+        bits.  Ignored for every other prior
+
+    A prior with ``pairs = True`` has two-plane coefficients ``[C, 2 m]``, ``T`` a float or ``[m]``, and
+    ``h(u) = (1 / lmda) sum_i T_i ||u_i||`` with the norm over a pixel's pair: the projection is ``pd_dual_step_pairs`` and the
+    certificate reads ``||V_i|| <= T_i / lmda``.
 
     The gradient is taken on :func:`gradient_operator` ``(forward)``, as FISTA does.
 
@@ -338,7 +411,7 @@ class PrimalDual(Stepper):
     lipschitz_tol = 1e-4
 
     def __init__(self, forward, prior, mcmcparams=PxMCMCParams(), nchains=1, tau=None, sigma=None, balance=1.0, max_iter=10000,
-                 tol=1e-4, check_every=10, use_graph=True):
+                 tol=1e-4, check_every=10, use_graph=True, fused=True):
         if getattr(forward, "setting", None) != "analysis":
             raise ValueError('PrimalDual needs an analysis-setting operator (forward.setting == "analysis"); FISTA solves the '
                              "synthesis setting")
@@ -359,8 +432,14 @@ class PrimalDual(Stepper):
         self.ncoefs = int(self._A(torch.zeros((1, n), dtype=dt, device=ops.device())).shape[-1])
         T = prior.T_dev if hasattr(prior, "T_dev") else (float(prior.T) if np.ndim(prior.T) == 0 else
                                                           ops.as_device(np.asarray(prior.T, dtype=float), torch.float64))
-        if not isinstance(T, float) and T.numel() != self.ncoefs:
-            raise ValueError(f"PrimalDual: T has {T.numel()} entries, the coefficients A X have {self.ncoefs}")
+        self._pair_prior = _is_pairs(prior)
+        self.fused = bool(fused) and _has_fused_steps(prior)
+        if self._pair_prior and self.ncoefs % 2:
+            raise ValueError(f"PrimalDual: a prior with pairs has two planes of coefficients, A X has {self.ncoefs}")
+        nT = self.ncoefs // 2 if self._pair_prior else self.ncoefs
+        if not isinstance(T, float) and T.numel() != nT:
+            raise ValueError(f"PrimalDual: T has {T.numel()} entries, the coefficients A X have {self.ncoefs}"
+                             + (f" in two planes of {nT}" if self._pair_prior else ""))
         self._T = T
         tl = self.lipschitz_tol
         self.L_g = float(self.gradient_op.gradient_lipschitz(iters=1000, tol=tl) * (1.0 + tl))
@@ -404,12 +483,35 @@ class PrimalDual(Stepper):
             ops.pd_primal_step(src, g, AH(V), tau, out=(dst, Xbar), sums=self._psums[k], scratch=scratch)
             ops.pd_dual_step(V, A(Xbar), T, sigma, rscale, out=V_next, sums=self._dsums[k], scratch=scratch)
 
+        def step_pairs(eng, src, dst):
+            V, V_next = (VA, VB) if src is eng.XA else (VB, VA)
+            k = 0 if dst is eng.XA else 1
+            g = ops.as_device(f.calc_gradg(ops.as_device(f.forward(src))), src.dtype)
+            ops.pd_primal_step(src, g, AH(V), tau, out=(dst, Xbar), sums=self._psums[k], scratch=scratch)
+            ops.pd_dual_step_pairs(V, A(Xbar), T, sigma, rscale, out=V_next, sums=self._dsums[k], scratch=scratch)
+
+        def step_fused(eng, src, dst):
+            V, V_next = (VA, VB) if src is eng.XA else (VB, VA)
+            k = 0 if dst is eng.XA else 1
+            g = ops.as_device(f.calc_gradg(ops.as_device(f.forward(src))), src.dtype)
+            self.prior.fused_primal_step(src, g, V, tau, out=(dst, Xbar), sums=self._psums[k], scratch=scratch)
+            self.prior.fused_dual_step(V, Xbar, T, sigma, rscale, out=V_next, sums=self._dsums[k], scratch=scratch)
+
+        if self._pair_prior:
+            step = step_fused if self.fused else step_pairs
+
         def reset(eng):
             VA.zero_()
             self._psums.zero_()
             self._dsums.zero_()
 
         return self._engine_start_generic(X, preds, i0, step, lazy=True, graph_ok=self.use_graph, reset=reset)
+
+    def _prior_sum(self, X):
+        """``sum_i T_i |(A X)_i|`` per chain (pairs: ``sum_i T_i ||(A X)_i||``)"""
+        if self._pair_prior:
+            return _weighted_pairs(self._A(X), self._T)
+        return _weighted_l1(self._A(X), self._T)
 
     def run(self, start_point=None):
         """Iterate from ``start_point`` (``[N]``, or ``[C, N]`` with one row per chain; ``None``: zero) and ``V = 0`` until every
@@ -440,7 +542,7 @@ class PrimalDual(Stepper):
                     rel_x = np.where(ps[:, 0] == 0.0, 0.0, np.sqrt(ps[:, 0]) / np.sqrt(ps[:, 1]))
                     rel_v = np.where(ds[:, 0] == 0.0, 0.0, np.sqrt(ds[:, 0]) / np.sqrt(ds[:, 1]))
                 data_term = 0.5 * self._l2_dev(preds).real.cpu().numpy()
-                prior_term = _weighted_l1(self._A(X), self._T).cpu().numpy() / self.lmda
+                prior_term = self._prior_sum(X).cpu().numpy() / self.lmda
                 now = (rel_x <= self.tol) & (rel_v <= self.tol)
                 niter = np.where(now & met, niter, i)  # iterations done when the chain first met (and kept) the rule
                 met = now

@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .transforms import SphericalGradientTransform
 from .utils import _multires_bandlimits, mw_map_weights, mw_size, sample_positions, to_like, wavelet_tiling
 
 
@@ -97,6 +98,48 @@ class L1_Analysis(L1):
         from .optim import analysis_prox  # (optim imports the samplers, which import this module)
 
         return analysis_prox(self, X, self.prox_iters)
+
+
+class TV_S2(L1_Analysis):
+    """
+    Isotropic total variation on the MW grid (extension; DESIGN.md section 14e)::
+
+        TV(X) = sum_{t,p} T_{t,p} sqrt(|(A X)[0][t][p]|^2 + |(A X)[1][t][p]|^2)   ~   T int |grad X| dOmega
+
+    with ``A`` the discrete gradient of :class:`pxmcmc_amd.transforms.SphericalGradientTransform` (the quadrature weight is
+    folded into ``A``).  An analysis prior: ``adj = A``, ``fwd = A^H``, and ``pairs = True`` -- the norm of ``h`` and the
+    projection of its dual act on the two gradient components of a pixel together.  ``proxf`` is the exact prox by
+    ``prox_iters`` dual iterations (:func:`pxmcmc_amd.optim.analysis_prox`) on the fused launches ``ops.tv_primal_step`` /
+    ``ops.tv_dual_step``; ``prior`` is ``ops.tv_value``.  No plan and no tables beyond ``2 L`` ring coefficients.
+
+    :param int L: bandlimit of the image, ``[L (2L - 1)]`` samples, real or complex
+    :param T: threshold, float or one value per pixel ``[L (2L - 1)]``
+    :param prox_iters: dual iterations per prox
+    """
+
+    pairs = True
+
+    def __init__(self, L, T, prox_iters=16):
+        self.transform = SphericalGradientTransform(L)
+        self.L = self.transform.L
+        if np.ndim(T) != 0:
+            T = np.asarray(T, dtype=float).reshape(-1)
+            if T.size != self.transform.npix:
+                raise ValueError(f"TV_S2: T is a float or one value per pixel ({self.transform.npix}), got {T.size}")
+        super().__init__(self.transform.forward_adjoint, self.transform.forward, T, prox_iters=prox_iters)
+
+    def prior(self, X):
+        """TV(X) per chain; float for one chain, float64 tensor [C] for a batch (as ``L1.prior``)."""
+        x = ops.as_device(X)
+        r = ops.tv_value(x, self.transform.ab, self.T_dev)
+        return r if x.dim() == 2 else float(r[0])
+
+    # the fused launches of the primal-dual iteration and of the prox's dual iteration (optim.PrimalDual, optim.analysis_prox)
+    def fused_primal_step(self, X, G, V, tau, **kw):
+        return ops.tv_primal_step(X, G, V, self.transform.ab, tau, **kw)
+
+    def fused_dual_step(self, V, Xbar, T, sigma, rscale, **kw):
+        return ops.tv_dual_step(V, Xbar, self.transform.ab, T, sigma, rscale, **kw)
 
 
 class S2_Wavelets_L1(L1):
