@@ -14,6 +14,10 @@ reads a HEALPix kappa map with healpy, absent here):
 With --harmonic the posterior lives in harmonic space: the data are the shear harmonics of the smoothed field (full sky,
 no mask), the operator is WeakLensingHarmonic with SphericalWaveletTransform(harmonic=True), the prior L1, and the chain
 starts from the wavelet analysis of the Kaiser-Squires estimate (WeakLensingHarmonic.sks_estimate).
+With --healpix NSIDE the shear is read at the pixel centres of a HEALPix map in RING order, as a catalogue binned with healpy
+is: the data are WeakLensingHealpix.forward of the smoothed field (an exact synthesis at the pixel centres, no map2alm), the
+mask is |galactic latitude| < --mask-size computed from the pixel centres, and the samplers run on WeakLensingHealpix with
+S2_Wavelets_L1 (every --algo; the generic stepping engine).
 
     python examples/weaklensing_synthetic.py --L 64 --algo pxmala --nsamples 20 --ngap 20 --nburn 100 --outdir /tmp
 """
@@ -31,14 +35,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pxmcmc_amd import ops  # noqa: E402
 from pxmcmc_amd.forward import ForwardOperator  # noqa: E402
 from pxmcmc_amd.mcmc import MYULA, SKROCK, PxMALA, PxMCMCParams  # noqa: E402
-from pxmcmc_amd.measurements import WeakLensing, WeakLensingHarmonic  # noqa: E402
+from pxmcmc_amd.measurements import WeakLensing, WeakLensingHarmonic, WeakLensingHealpix  # noqa: E402
 from pxmcmc_amd.optim import FISTA  # noqa: E402
 from pxmcmc_amd.prior import L1, S2_Wavelets_L1  # noqa: E402
 from pxmcmc_amd.sapg import SAPG  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
 from pxmcmc_amd.transforms import SphericalWaveletTransform  # noqa: E402
 from pxmcmc_amd.uncertainty import hypothesis_test, local_credible_intervals, superpixel_regions  # noqa: E402
-from pxmcmc_amd.utils import _multires_bandlimits, build_mask  # noqa: E402
+from pxmcmc_amd.utils import _multires_bandlimits, build_mask, galactic_latitude, healpix_pixel_centres  # noqa: E402
 
 BEAM_SIGMA = np.radians(50 / 60)  # 50 arcmin (experiments/weaklensing/main.py:35)
 
@@ -239,8 +243,12 @@ def main(argv=None):
                          "effective sample size and the standard error of the mean map")
     ap.add_argument("--harmonic", action="store_true",
                     help="harmonic-space posterior: WeakLensingHarmonic + harmonic wavelets + L1, started from sks_estimate")
+    ap.add_argument("--healpix", type=int, default=None, metavar="NSIDE",
+                    help="read the shear at the pixel centres of a HEALPix map (RING order) of this nside: WeakLensingHealpix")
     args = ap.parse_args(argv)
     args.estimate_mu = args.estimate_mu or args.estimate_mu_per_scale
+    if args.healpix is not None and (args.harmonic or args.local_ci is not None or args.hyp_test is not None):
+        ap.error("--healpix runs the pixel-space posterior without --local-ci / --hyp-test (their regions are MW superpixels of the data grid)")
     if args.summary_alpha is not None and not args.summary:
         ap.error("--summary-alpha needs --summary")
     if args.summary_ess is not None and not args.summary:
@@ -258,9 +266,17 @@ def main(argv=None):
     if args.harmonic:
         return _main_harmonic(args, L, B, J_min, setting)
 
-    # Euclid-like mask and synthetic shear data (main.py:90-93)
-    mask = build_mask(L, size=args.mask_size)
-    measurement = WeakLensing(L, mask, ngal=np.full_like(mask, 30), max_chains=args.chains)
+    if args.healpix is not None:
+        # galactic-plane mask from the pixel centres (lon = phi - 180, lat = 90 - theta degrees), shear at the pixel centres
+        theta, phi = healpix_pixel_centres(args.healpix)
+        hmask = np.abs(galactic_latitude(np.degrees(phi) - 180, 90 - np.degrees(theta))) >= args.mask_size
+        measurement = WeakLensingHealpix(L, args.healpix, mask=hmask, ngal=np.full(hmask.size, 30.0), max_chains=args.chains)
+        mask = np.ones((L, 2 * L - 1))  # (the kappa error below is taken on the whole MW grid)
+        print(f"HEALPix data: nside = {args.healpix}, {hmask.size} pixels, masked fraction {1 - hmask.mean():.3f}")
+    else:
+        # Euclid-like mask and synthetic shear data (main.py:90-93)
+        mask = build_mask(L, size=args.mask_size)
+        measurement = WeakLensing(L, mask, ngal=np.full_like(mask, 30), max_chains=args.chains)
     gammas_truth, kappa_truth = prepare_gammas(synthetic_kappa_lm(L, args.seed), L, measurement)
 
     transform = SphericalWaveletTransform(L, B, J_min, dirs=args.dirs, max_chains=args.chains)
@@ -273,6 +289,9 @@ def main(argv=None):
     print(f"Number of data points: {gammas_truth.size}")
     print(f"Number of model parameters: {forward_operator.nparams}")
     L_g = step_hint(forward_operator, params, args)
+    if args.healpix is not None and args.delta * L_g > 1:
+        print(f"--delta {args.delta:.3e} is above 1 / L_g = {1 / L_g:.3e} for these data (12 nside^2 weighted pixels): MYULA and SKROCK "
+              f"diverge there; pass a --delta near the bound above")
     if args.estimate_mu:
         prior, params = estimate_mu(forward_operator, prior, params, L_g, args)
     start_point = map_start(forward_operator, prior, params, L_g, restart="gradient" if args.map_restart else None) if args.map_start else None

@@ -38,6 +38,7 @@ typedef struct pxm_dwav_plan_s* pxm_dwav_plan_t;
 typedef struct pxm_hwav_plan_s* pxm_hwav_plan_t;
 typedef struct pxm_dft_plan_s* pxm_dft_plan_t;
 typedef struct pxm_gemm_plan_s* pxm_gemm_plan_t;
+typedef struct pxm_hpx_plan_s* pxm_hpx_plan_t;
 typedef void* pxm_stream_t; /* hipStream_t */
 
 /* ---- library ------------------------------------------------------------ */
@@ -184,6 +185,32 @@ int pxm_dft_ring2px_ex(pxm_dft_plan_t plan, const void* G, int ncol, void* f, in
                        const void* invcov, int invcov_complex, const int32_t* gidx, const double* gw, int64_t ndata, int C,
                        pxm_stream_t stream);
 int pxm_dft_status(pxm_dft_plan_t plan, int clear, pxm_stream_t stream);
+
+/* ---- HEALPix ring synthesis (csrc/healpix.hip) ---------------------------------------------------
+ * The measurement "band-limited signal -> values at the HEALPix pixel centres" and its exact adjoint, RING order (what the
+ * reference prepares with healpy.map2alm, experiments/weaklensing/main.py:23-37, without the inexact analysis):
+ *   pxm_hpx_synthesis          v[c][p]   = sum_lm sY_lm(theta_p, phi_p) flm[c][l^2 + l + m]
+ *   pxm_hpx_synthesis_adjoint  flm[c][.] = sum_p conj(sY_lm(theta_p, phi_p)) v[c][p]          (no quadrature weight)
+ *   flm : [C][L*L] c128,  v : [C][12 nside^2] c128, both 16-byte aligned; every element of the output is written.
+ * There are R = 4 nside - 1 rings, north to south, i = 1 .. R with i' = min(i, 4 nside - i): polar caps (i' < nside) have
+ * nphi = 4 i', z = 1 - i'^2 / (3 nside^2), phi_j = (pi / (2 i')) (j + 1/2); the belt has nphi = 4 nside,
+ * z = 4/3 - 2 i' / (3 nside), phi_j = (pi / (2 nside)) (j + 1/2) for even i' - nside and (pi / (2 nside)) j for odd; the
+ * southern rings change the sign of z.  Refused: L > 1024, |spin| >= L, nside < 1, nside above out[3] of
+ * pxm_host_hpx_geometry (the longest ring must fit the LDS of a phi-stage workgroup).
+ *   pxm_host_hpx_geometry  out[6] = rings, pixels, LDS bytes of a phi-stage workgroup, largest nside, threads, padded rings
+ *   pxm_host_hpx_rings     per ring: nphi, theta, phi of the first pixel, index of the first pixel     (arrays of 4 nside - 1)
+ *   pxm_host_hpx_lambda    out[t][l] = (-1)^s sqrt((2l+1)/4pi) d^l_{m,-s}(theta[t]), l < L: the table recursion the plan uses
+ *   pxm_hpx_table_bytes    device bytes of the Legendre table and twiddles the plan holds
+ *   pxm_hpx_status         the plan's status word, as pxm_sht_status (no kernel of this plan has a bounded wait: always 0) */
+int pxm_host_hpx_geometry(int L, int nside, int64_t* out);
+int pxm_host_hpx_rings(int nside, int* nphi, double* theta, double* phi0, int64_t* start);
+int pxm_host_hpx_lambda(int L, int spin, int m, const double* theta, int nt, double* out);
+int pxm_hpx_plan_create(int L, int nside, int spin, int max_chains, pxm_hpx_plan_t* plan);
+int pxm_hpx_plan_destroy(pxm_hpx_plan_t plan);
+int pxm_hpx_synthesis(pxm_hpx_plan_t plan, const void* flm, void* v, int C, pxm_stream_t stream);
+int pxm_hpx_synthesis_adjoint(pxm_hpx_plan_t plan, const void* v, void* flm, int C, pxm_stream_t stream);
+int64_t pxm_hpx_table_bytes(pxm_hpx_plan_t plan);
+int pxm_hpx_status(pxm_hpx_plan_t plan, int clear, pxm_stream_t stream);
 
 /* ---- the ring-GEMM stage on its own -------------------------------------------------------------------------------
  * The Legendre stage of every transform above (csrc/sht_gemm.hip) as a plan without DFT stage, wavelet kernels or samplers:

@@ -85,6 +85,15 @@ SIGNATURES = {
     "pxm_dft_px2ring_ex": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp]),
     "pxm_dft_ring2px_ex": (c_int, [c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_vp]),
     "pxm_dft_status": (c_int, [c_vp, c_int, c_vp]),
+    "pxm_host_hpx_geometry": (c_int, [c_int, c_int, c_vp]),
+    "pxm_host_hpx_rings": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp]),
+    "pxm_host_hpx_lambda": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_vp]),
+    "pxm_hpx_plan_create": (c_int, [c_int, c_int, c_int, c_int, C.POINTER(c_vp)]),
+    "pxm_hpx_plan_destroy": (c_int, [c_vp]),
+    "pxm_hpx_synthesis": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_hpx_synthesis_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "pxm_hpx_table_bytes": (c_i64, [c_vp]),
+    "pxm_hpx_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_gemm_plan_create": (c_int, [c_int, c_int, c_int, c_vp, c_int, C.POINTER(c_vp)]),
     "pxm_gemm_plan_destroy": (c_int, [c_vp]),
     "pxm_gemm_plan_report": (c_i64, [c_vp, c_int, c_int, c_vp, c_i64]),

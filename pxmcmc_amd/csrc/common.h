@@ -97,6 +97,8 @@ void tiling_axisym(int L, double B, int J_min, std::vector<double>& kappa0, std:
 void mw_ring_weights(int L, double* q);
 // B^m[t][el] = (-1)^s sqrt((2el+1)/4pi) d^el_{m,-s}(theta_t), written with leading dimension ld (>= L)
 void wigner_ring_table(int L, int spin, int m, double* out, int ld);
+// the same values at the colatitudes theta[nt] instead of the MW rings: out[t * t_stride + el * l_stride], el >= max(|m|, |s|) only
+void wigner_colat_table(int L, int spin, int m, const long double* theta, int nt, double* out, int64_t t_stride, int64_t l_stride);
 // the same table as the recursion kernels (csrc/sht_rec.hip) generate it: double precision, scaled state (rec_core.h)
 void rec_emulate_table(int L, int spin, int m, double* out, int ld);
 // Q^{par}[t'][t] (L x L, leading dimension ld): MW exact-quadrature Gram matrix, par = +1 / -1

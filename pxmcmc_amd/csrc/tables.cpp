@@ -137,6 +137,54 @@ void wigner_ring_table(int L, int spin, int m, double* out, int ld) {
   }
 }
 
+// The recursion of wigner_ring_table at any list of colatitudes (the HEALPix ring centres of csrc/healpix.hip):
+// out[t * t_stride + el * l_stride] = (-1)^s sqrt((2el+1)/4pi) d^el_{m,-s}(theta[t]) for el0 <= el < L; el < el0 is left
+// as the caller filled it.
+void wigner_colat_table(int L, int spin, int m, const long double* theta, int nt, double* out, int64_t t_stride, int64_t l_stride) {
+  const int nn = -spin;
+  const int el0 = std::max(std::abs(m), std::abs(nn));
+  if (el0 >= L) return;
+  const int k = std::max(0, nn - m);  // the single term of the explicit sum for d^{el0}_{m nn}
+  const int pc = 2 * el0 + nn - m - 2 * k, ps = m - nn + 2 * k;
+  const long double sgn = ((m - nn + k) % 2) ? -1.0L : 1.0L;
+  const int a = (el0 == std::abs(m)) ? nn : m;
+  const long double coef =
+      sgn * expl(0.5L * (lgammal(2.0L * el0 + 1) - lgammal((long double)el0 + a + 1) - lgammal((long double)el0 - a + 1)));
+  std::vector<long double> c1(L, 0), c2(L, 0), c3(L, 0), nrm(L);
+  const long double mm = m, nl = nn;
+  for (int l = el0 + 1; l < L; ++l) {
+    long double lm1 = l - 1, ll = l;
+    if (l == 1) {  // only (m, nn) = (0, 0): Legendre P_1 = cos
+      c1[l] = 1;
+      continue;
+    }
+    long double A = sqrtl((ll * ll - mm * mm) * (ll * ll - nl * nl));
+    long double Bq = sqrtl((lm1 * lm1 - mm * mm) * (lm1 * lm1 - nl * nl));
+    long double den = lm1 * A;
+    c1[l] = (2 * lm1 + 1) * lm1 * ll / den;
+    c2[l] = (2 * lm1 + 1) * mm * nl / den;
+    c3[l] = ll * Bq / den;
+  }
+  const long double sfac = (spin % 2) ? -1.0L : 1.0L;
+  for (int l = 0; l < L; ++l) nrm[l] = sfac * sqrtl((2.0L * l + 1) / (4 * PI_L));
+  for (int t = 0; t < nt; ++t) {
+    const long double th = theta[t];
+    const long double hc = cosl(th / 2), hs = sinl(th / 2), ct = cosl(th);
+    long double cur = coef;
+    if (pc) cur *= powl(hc, pc);
+    if (ps) cur *= powl(hs, ps);
+    long double prev = 0;
+    double* row = out + (int64_t)t * t_stride;
+    row[(int64_t)el0 * l_stride] = (double)(nrm[el0] * cur);
+    for (int l = el0 + 1; l < L; ++l) {
+      long double nxt = (c1[l] * ct - c2[l]) * cur - c3[l] * prev;
+      prev = cur;
+      cur = nxt;
+      row[(int64_t)l * l_stride] = (double)(nrm[l] * cur);
+    }
+  }
+}
+
 // ---- table-free ring stage (rec_core.h): coefficients, normalisation and scaled seeds of one order ----------------
 void rec_ring_zeta(int L, double* zeta, int* north, int Tp) {
   const int n = 2 * L - 1;

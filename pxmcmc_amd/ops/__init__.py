@@ -15,11 +15,11 @@ and the checks they share.  Callers use the names below as ``ops.<name>``.
 from .._lib import (FISTA_SLICES_MAX, LCI_EMPTY, LCI_NONFINITE, LCI_POINTS, LCI_UNCONSTRAINED, SAPG_GROUPS_MAX, SAPG_SLICES_MAX,
                     PxmError, check, require_gpu)
 from ._args import GEMM_KINDS, _batched, _p, _stream, as_device, device
-from .host import (DFT_STEP_FIELDS, DFT_UNITS, GEMM_TASK_FIELDS, dft_geometry, dft_step_is_stock, gemm_plan_geometry, gemm_report, j_max, mw_ring_weights, noise_bits, rec_geometry, tiling_axisym,
+from .host import (DFT_STEP_FIELDS, DFT_UNITS, GEMM_TASK_FIELDS, dft_geometry, dft_step_is_stock, gemm_plan_geometry, gemm_report, hpx_geometry, hpx_lambda, hpx_rings, j_max, mw_ring_weights, noise_bits, rec_geometry, tiling_axisym,
                    wav_bandlimits)
 from .inpaint import inpaint_scratch, inpaint_step
 from .lci import lci_data_terms, lci_eval, lci_scratch, lci_search
-from .plans import (DftPlan, DirWavPlan, GemmPlan, HarmWavPlan, IterCounter, ShtPlan, WavPlan, _Plan, capture_scope, live_plans, raise_on_status,
+from .plans import (DftPlan, DirWavPlan, GemmPlan, HarmWavPlan, HpxPlan, IterCounter, ShtPlan, WavPlan, _Plan, capture_scope, live_plans, raise_on_status,
                     tables_trim)
 from .pxmala import logtransition, pxmala_accept, pxmala_finish, pxmala_propose, pxmala_propose_scratch
 from .reduce import quantile_range, reduce_l1, reduce_l2, reduce_scratch_doubles, reduce_vdot

@@ -52,6 +52,32 @@ def dft_geometry(L):
     return (DFT_UNITS[out[0]], int(out[1]), int(out[2]), int(out[3]), int(out[4]), bool(out[5]))
 
 
+def hpx_geometry(L, nside):
+    """``dict(rings, npix, lds_bytes, nside_max, threads, rings_padded)`` of ``ops.HpxPlan(L, nside)`` (csrc/healpix.hip):
+    ``lds_bytes`` the LDS of a phi-stage workgroup (the longest ring, 4 nside points), ``nside_max`` the largest nside whose
+    longest ring fits a CU's LDS.  Raises PxmError, in the words the plan refuses with, for L >= 1025, nside < 1 and
+    nside > nside_max."""
+    out = (C.c_int64 * 6)()
+    check(lib.pxm_host_hpx_geometry(int(L), int(nside), out))
+    return dict(zip(("rings", "npix", "lds_bytes", "nside_max", "threads", "rings_padded"), (int(v) for v in out)))
+
+
+def hpx_rings(nside):
+    """(nphi, theta, phi0, start) per ring as the library's host code computes them (utils.healpix_rings is the numpy statement)"""
+    R = 4 * int(nside) - 1
+    nphi, theta, phi0, start = np.zeros(max(R, 1), np.int32), np.zeros(max(R, 1)), np.zeros(max(R, 1)), np.zeros(max(R, 1), np.int64)
+    check(lib.pxm_host_hpx_rings(int(nside), nphi.ctypes.data, theta.ctypes.data, phi0.ctypes.data, start.ctypes.data))
+    return nphi, theta, phi0, start
+
+
+def hpx_lambda(L, spin, m, theta):
+    """lam[t, l] = (-1)^s sqrt((2l+1)/4pi) d^l_{m,-s}(theta[t]), l < L: the long-double recursion the plan fills its table with"""
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    out = np.zeros((theta.size, int(L)))
+    check(lib.pxm_host_hpx_lambda(int(L), int(spin), int(m), theta.ctypes.data, theta.size, out.ctypes.data))
+    return out
+
+
 DFT_STEP_FIELDS = ("X", "T", "noise", "iter_dev", "rdata", "rinvcov", "gidx", "gw")  # bits of pxm_host_dft_step_is_stock
 
 

@@ -1,6 +1,6 @@
-"""The transform plans -- spherical-harmonic, the phi-DFT stage alone, the ring-GEMM stage alone, axisymmetric, directional and harmonic-space wavelets --
-with the fused sampler steps of the wavelet plan, the live-plan registry, the device iteration counter and the capture scope
-(csrc/sht_plan.hip, dft_plan.hip, gemm_plan.hip, wav_plan.hip, wav_ops.hip, wav_wl.hip, dirwav.hip, harmwav.hip)."""
+"""The transform plans -- spherical-harmonic, the phi-DFT stage alone, the ring-GEMM stage alone, HEALPix ring synthesis, axisymmetric, directional and
+harmonic-space wavelets -- with the fused sampler steps of the wavelet plan, the live-plan registry, the device iteration counter and the capture scope
+(csrc/sht_plan.hip, dft_plan.hip, gemm_plan.hip, healpix.hip, wav_plan.hip, wav_ops.hip, wav_wl.hip, dirwav.hip, harmwav.hip)."""
 import ctypes as C
 import threading
 import weakref
@@ -214,6 +214,31 @@ class DftPlan(_Plan):
         raw = self.ring_array()
         raw[:, :self.L, :g.shape[0]] = g.permute(2, 1, 0)
         return self.pixels_raw(raw, g.shape[0])
+
+
+class HpxPlan(_Plan):
+    """HEALPix ring synthesis and its adjoint at bandlimit L (include/pxmcmc_amd.h, pxm_hpx_*): the
+    exact maps between f_lm [L*L] and the values at the 12 nside^2 pixel centres of a RING-ordered map, spin ``spin`` in
+    the ssht convention.  There is no HEALPix analysis here: ``synthesis_adjoint`` carries no quadrature weight."""
+
+    def __init__(self, L, nside, spin=0, max_chains=1):
+        require_gpu()
+        self.L, self.nside, self.spin, self.max_chains = int(L), int(nside), int(spin), int(max_chains)
+        self.nlm, self.npix = self.L * self.L, 12 * self.nside * self.nside
+        super().__init__(lib.pxm_hpx_plan_create, (self.L, self.nside, self.spin, self.max_chains), lib.pxm_hpx_plan_destroy,
+                         lib.pxm_hpx_status, f"HpxPlan(L={self.L}, nside={self.nside}, spin={self.spin})")
+
+    def synthesis(self, flm, out=None):
+        """[C, L*L] -> [C, 12 nside^2]: v_p = sum_lm sY_lm(theta_p, phi_p) f_lm"""
+        return self._run(lib.pxm_hpx_synthesis, flm, self.nlm, self.npix, out=out)
+
+    def synthesis_adjoint(self, v, out=None):
+        """[C, 12 nside^2] -> [C, L*L]: f_lm = sum_p conj(sY_lm(theta_p, phi_p)) v_p"""
+        return self._run(lib.pxm_hpx_synthesis_adjoint, v, self.npix, self.nlm, out=out)
+
+    def table_bytes(self):
+        """device bytes of the Legendre table and the twiddles the plan holds"""
+        return int(lib.pxm_hpx_table_bytes(self._h))
 
 
 class GemmPlan(_Plan):

@@ -180,3 +180,37 @@ def build_mask(L, size=20):
     thetaarray, phiarray = np.meshgrid(np.degrees(thetas) - 90, np.degrees(phis) - 180, indexing="ij")
     mask[np.abs(galactic_latitude(phiarray, thetaarray)) < size] = 0
     return mask
+
+
+def healpix_rings(nside, dtype=np.float64):
+    """[ext] the rings of a HEALPix map in RING order (what healpy.ringinfo reports): ``(nphi, theta, phi0, start)``, one
+    entry per ring i = 1 .. 4 nside - 1, north to south -- pixels on the ring, colatitude of the ring, azimuth of its first
+    pixel, index of its first pixel.  With i' = min(i, 4 nside - i): polar caps (i' < nside) nphi = 4 i',
+    z = 1 - i'^2 / (3 nside^2), phi0 = pi / (4 i'); belt nphi = 4 nside, z = 4/3 - 2 i' / (3 nside), phi0 = pi / (4 nside) for
+    even i' - nside and 0 for odd; the southern rings have -z.  Evaluated in long double and returned as ``dtype``.  NESTED
+    order and reading FITS files are out of scope: reorder a NESTED map to RING order before it comes here."""
+    nside = int(nside)
+    if nside < 1:
+        raise ValueError("healpix_rings: need nside >= 1")
+    ld = np.longdouble
+    i = np.arange(1, 4 * nside)
+    ip = np.minimum(i, 4 * nside - i)
+    cap = ip < nside
+    nphi = np.where(cap, 4 * ip, 4 * nside).astype(np.int64)
+    ipl, ns = ip.astype(ld), ld(nside)
+    z = np.where(cap, 1 - ipl * ipl / (3 * ns * ns), ld(4) / 3 - 2 * ipl / (3 * ns))
+    z = np.where(i > 2 * nside, -z, z)
+    shifted = cap | ((ip - nside) % 2 == 0)
+    pi = ld("3.141592653589793238462643383279502884")
+    phi0 = np.where(shifted, pi / nphi.astype(ld), ld(0))
+    start = np.concatenate([[0], np.cumsum(nphi)[:-1]]).astype(np.int64)
+    return nphi, np.arccos(z).astype(dtype), phi0.astype(dtype), start
+
+
+def healpix_pixel_centres(nside, dtype=np.float64):
+    """[ext] ``(theta, phi)`` of the 12 nside^2 pixel centres in RING order (healpy.pix2ang of every pixel): ring by ring
+    north to south, phi ascending on a ring (:func:`healpix_rings`).  NESTED order and FITS files are out of scope."""
+    nphi, theta, phi0, _ = healpix_rings(nside, np.longdouble)
+    pi = np.longdouble("3.141592653589793238462643383279502884")
+    phi = np.concatenate([p0 + 2 * pi * np.arange(n) / np.longdouble(n) for n, p0 in zip(nphi, phi0)])
+    return np.repeat(theta, nphi).astype(dtype), phi.astype(dtype)
