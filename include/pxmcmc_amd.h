@@ -354,6 +354,11 @@ int pxm_wav_exact_dft_scales(pxm_wav_plan_t plan);
 /* 1 when that launch runs stock MYULA updates (pxm_host_dft_step_is_stock) on the STOCK kernel instantiation; 0 with
  * PXM_DFT_STOCK=0 at plan creation or without a grouped launch: every update on the generic kernels */
 int pxm_wav_dft_stock(pxm_wav_plan_t plan);
+/* Cache policies of the plan's ring-space step (csrc/mem_policy.h): a mask of the streams whose accesses the plan's launches
+ * issue non-temporal -- bit 0: the X' stores of the fused phi-DFT step (its STOCK kernel instantiation).
+ * 0 with PXM_MEM_POLICY=0 at plan creation, or without that instantiation (pxm_wav_dft_stock): every launch on the
+ * default-policy kernels (the identity test). */
+int pxm_wav_mem_policy(pxm_wav_plan_t plan);
 
 /* Live kernel timing of one plan (bench.py roofline leg).  pxm_wav_profile_enable(plan, n) with n > 0 creates
  * n event pairs per kernel class; while enabled every SHT ring-GEMM launch and every grouped phi-DFT launch of
@@ -373,6 +378,9 @@ int pxm_wav_profile_read_launches(pxm_wav_plan_t plan, double* launch_ms, double
 /* test aid: number of non-finite doubles in the plan's workspace (ring / harmonic arrays incl. the padding
  * chains' columns); synchronises the stream */
 int64_t pxm_wav_workspace_nonfinite(pxm_wav_plan_t plan, pxm_stream_t stream);
+/* test aid: the plan's workspace -- every ring and harmonic array of its stages, padding columns included -- copied to the
+ * device array out (at most cap doubles); returns the number of doubles the workspace holds, < 0 on error */
+int64_t pxm_wav_workspace_read(pxm_wav_plan_t plan, double* out, int64_t cap, pxm_stream_t stream);
 
 /* Fused MYULA half-steps (pxmcmc/mcmc.py:158-161 with forward.py:66-72, prior.py:49-50):
  *   pxm_wav_gradg_step: X_out = (1-d/l) X + (d/l) soft(X,T) - d * S^H( invcov .* (preds - data) ) + sqrt(2 d) w

@@ -36,6 +36,7 @@ SIGNATURES = {
     "pxm_wav_iter_counter_add": (c_int, [c_vp, c_u64, c_vp]),
     "pxm_wav_exact_dft_scales": (c_int, [c_vp]),
     "pxm_wav_dft_stock": (c_int, [c_vp]),
+    "pxm_wav_mem_policy": (c_int, [c_vp]),
     "pxm_wav_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_sht_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_wav_profile_enable": (c_int, [c_vp, c_int]),
@@ -43,6 +44,7 @@ SIGNATURES = {
     "pxm_wav_profile_read_launches": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "pxm_wav_profile_read_dft": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "pxm_wav_workspace_nonfinite": (c_i64, [c_vp, c_vp]),
+    "pxm_wav_workspace_read": (c_i64, [c_vp, c_vp, c_i64, c_vp]),
     "pxm_reduce_scratch_doubles": (c_i64, [c_int]),
     "pxm_j_max": (c_int, [c_int, c_dbl]),
     "pxm_wav_bandlimits": (c_int, [c_int, c_dbl, c_int, c_vp, c_int]),

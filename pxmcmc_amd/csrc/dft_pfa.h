@@ -184,10 +184,12 @@ static_assert(4 * PFA_STAGE_S <= 4 * PFA_PLANE, "a ring group's stage fits in it
 // scales are resident from the start of the launch instead of forming a second round).
 // STOCK: the launch is the stock MYULA update (dft_step_is_stock, sht_core.h; fp64 noise): its epilogue is
 // px_stock_update4 (update.h) and none of the mode fields of PxOut is read.
-template <bool RING_OUT, bool N64, bool STOCK = false>
+// XOUT: cache policy of the X' stores (mem_policy.h); STOCK only.
+template <bool RING_OUT, bool N64, bool STOCK = false, int XOUT = MEM_DEFAULT>
 __device__ __forceinline__ void ring2px_body_pfa(const Dft5Args& a, const PfaTabs& pt, double* __restrict__ G, int ncol,
                                                  const PxOut& out, int C, int bxw, int by, int passes, double2* lds5) {
   static_assert(!STOCK || (RING_OUT && N64), "the stock instantiation is the fused step with the fp64 noise stream");
+  static_assert(STOCK || XOUT == MEM_DEFAULT, "only the stock instantiation carries a cache policy");
   if ((by << 2) >= C) return;
 #ifdef PXM_D5_TRACE
   unsigned long long d5_stamp[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -299,7 +301,7 @@ __device__ __forceinline__ void ring2px_body_pfa(const Dft5Args& a, const PfaTab
       double2* park = plane + lane + 64 * g0;
       if (act) {
         const bool ok[4] = {true, true, true, g0 + 3 < 7 || last_ok};  // (lane 63, p = 7: slot 511, never an element)
-        px_stock_update4<64>(out, ok, e0 + 64 * g0, ce0 + 64 * g0, -lane - 64 * g0, ch_s, it_eff, park, logt, sct);
+        px_stock_update4<64, XOUT>(out, ok, e0 + 64 * g0, ce0 + 64 * g0, -lane - 64 * g0, ch_s, it_eff, park, logt, sct);
       } else {
 #pragma unroll
         for (int u = 0; u < 4; ++u) park[64 * u] = double2{0.0, 0.0};  // padding chains / rings: their rings are kept at zero

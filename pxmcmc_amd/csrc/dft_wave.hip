@@ -244,9 +244,11 @@ __device__ unsigned long long* g_dft_trace = nullptr;
 // fp64 evaluation holds ~40 registers and the update epilogue sits at the 128-VGPR budget of four waves per SIMD)
 // STOCK: the launch is the stock MYULA update (dft_step_is_stock, sht_core.h; fp64 noise): its epilogue is px_stock_update4
 // (update.h) on elements parked in the wave's plane, and none of the mode fields of PxOut is read
-template <int R0, bool RING_OUT, bool N64, bool STOCK = false>
+// XOUT: cache policy of the X' stores (mem_policy.h); STOCK only.
+template <int R0, bool RING_OUT, bool N64, bool STOCK = false, int XOUT = MEM_DEFAULT>
 __device__ __forceinline__ void ring2px_body5(const Dft5Args& a, double* __restrict__ G, int ncol, const PxOut& out, int C,
                                               int bx, int by, double2* lds5) {
+  static_assert(STOCK || XOUT == MEM_DEFAULT, "only the stock instantiation carries a cache policy");
   // chain groups without a live chain do nothing (see run_tasks / GemmAffine::ncol_live: nothing iterates on them)
   if ((by << 2) >= C) return;
 #ifdef PXM_D5_TRACE
@@ -314,7 +316,7 @@ __device__ __forceinline__ void ring2px_body5(const Dft5Args& a, double* __restr
       bool ok[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) ok[u] = jb + 8 * R0 * (pb + u) < n;
-      px_stock_update4<8 * R0>(out, ok, e0, ce0, -(jb + 8 * R0 * pb), __builtin_amdgcn_readfirstlane(ch), out.iter + *out.iter_dev, park,
+      px_stock_update4<8 * R0, XOUT>(out, ok, e0, ce0, -(jb + 8 * R0 * pb), __builtin_amdgcn_readfirstlane(ch), out.iter + *out.iter_dev, park,
                                reinterpret_cast<const double2*>(&NOISE_LOG_TAB[0][0]), reinterpret_cast<const double2*>(&NOISE_SINCOS_TAB[0][0]));
     }
   } else if (act && out.X) {  // fused prox + MYULA update (pxmcmc/mcmc.py:185-201, prior.py:49-50)
@@ -519,7 +521,7 @@ extern "C" int pxm_debug_set_dft_trace(unsigned long long* buf) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_dft_trace), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
 }
 #endif
-template <bool RING_OUT, bool N64, bool STOCK = false>
+template <bool RING_OUT, bool N64, bool STOCK = false, int XOUT = MEM_DEFAULT>
 __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_ring2px_group5(const Dft5Group* __restrict__ ents, int nent,
                                                                                        double* __restrict__ ws, int ncol, PxOut out,
                                                                                        int C) {
@@ -535,14 +537,14 @@ __global__ __launch_bounds__(128 * D5_RMAX, 4) void k_ring2px_group5(const Dft5G
                      reinterpret_cast<const double2*>(pb + PFA_TAB_B2)};
     // (pfa_passes = 2: half as many workgroups, each taking two ring pairs in turn -- with one such workgroup per CU the
     // latency-bound workgroups of the small scales are resident from the start instead of forming a second round)
-    ring2px_body_pfa<RING_OUT, N64, STOCK>(a, pt, G, ncol, out, C, bx, by, g.pfa_passes, lds5);
+    ring2px_body_pfa<RING_OUT, N64, STOCK, XOUT>(a, pt, G, ncol, out, C, bx, by, g.pfa_passes, lds5);
   }
   switch (g.r0) {
     case 9: break;  // (done above)
-    case 8: ring2px_body5<8, RING_OUT, N64, STOCK>(a, G, ncol, out, C, bx, by, lds5); break;
-    case 4: ring2px_body5<4, RING_OUT, N64, STOCK>(a, G, ncol, out, C, bx, by, lds5); break;
-    case 2: ring2px_body5<2, RING_OUT, N64, STOCK>(a, G, ncol, out, C, bx, by, lds5); break;
-    default: ring2px_body5<1, RING_OUT, N64, STOCK>(a, G, ncol, out, C, bx, by, lds5); break;
+    case 8: ring2px_body5<8, RING_OUT, N64, STOCK, XOUT>(a, G, ncol, out, C, bx, by, lds5); break;
+    case 4: ring2px_body5<4, RING_OUT, N64, STOCK, XOUT>(a, G, ncol, out, C, bx, by, lds5); break;
+    case 2: ring2px_body5<2, RING_OUT, N64, STOCK, XOUT>(a, G, ncol, out, C, bx, by, lds5); break;
+    default: ring2px_body5<1, RING_OUT, N64, STOCK, XOUT>(a, G, ncol, out, C, bx, by, lds5); break;
   }
 #ifdef PXM_D5_TRACE
   if (threadIdx.x == 0 && g_dft_trace) {
@@ -1098,10 +1100,12 @@ int dft_group_create(const std::vector<const DftPlan*>& plans, const std::vector
   out->all = v.size() == plans.size();
   out->blocks = b0;
   out->stock = plans[order[0]]->stock;  // (PXM_DFT_STOCK, read by make_dft_plan: the same for every scale of a plan)
+  out->mem_policy = mem_policy_from_env();
   if (int rc = dev_table(&out->d, v, "DFT group entries")) return rc;
   static std::atomic<uint64_t> lds_done{0};
   return allow_dynamic_lds(lds_done, {reinterpret_cast<const void*>(k_ring2px_group5<true, false>), reinterpret_cast<const void*>(k_ring2px_group5<true, true>),
                                       reinterpret_cast<const void*>(k_ring2px_group5<true, true, true>),
+                                      reinterpret_cast<const void*>(k_ring2px_group5<true, true, true, DFT_X_OUT_POLICY>),
                                       reinterpret_cast<const void*>(k_ring2px_group5<false, false>), reinterpret_cast<const void*>(k_ring2px_group5<false, true>),
                                       reinterpret_cast<const void*>(k_px2ring_group5)});
 }
@@ -1122,7 +1126,7 @@ int dft_group_launch(const DftGroupList& g, double* ws, int ncol, const PxOut& o
   if (prof) prof->next(prof->dft, &ev0, &ev1, bytes, 0.0);
   const Dft5Group* ents = reinterpret_cast<const Dft5Group*>(g.d);
   if (g.stock && out.noise64 && dft_step_is_stock(out))  // the stock update: its mode is part of the instantiation
-    hipExtLaunchKernelGGL((k_ring2px_group5<true, true, true>), dim3(g.blocks), dim3(128 * D5_RMAX), D5_LDS, st, ev0, ev1, 0,
+    hipExtLaunchKernelGGL((g.mem_policy ? k_ring2px_group5<true, true, true, DFT_X_OUT_POLICY> : k_ring2px_group5<true, true, true>), dim3(g.blocks), dim3(128 * D5_RMAX), D5_LDS, st, ev0, ev1, 0,
                           ents, g.n, ws, ncol, out, C);
   else if (out.X && !out.noise && out.noise64)
     hipExtLaunchKernelGGL((k_ring2px_group5<true, true>), dim3(g.blocks), dim3(128 * D5_RMAX), D5_LDS, st, ev0, ev1, 0,

@@ -247,6 +247,7 @@ struct DftGroupList {
   std::vector<char> member;  // per scale: its rings <-> pixels launches are part of this group
   bool all = false;          // every scale is a member (needed by the fused rings -> X' -> rings step)
   bool stock = true;         // stock launches take the STOCK instantiation (PXM_DFT_STOCK is not 0 at creation)
+  bool mem_policy = true;    // ... with the build's cache policy of the X' stores (mem_policy.h; PXM_MEM_POLICY is not 0 at creation)
 };
 int dft_group_create(const std::vector<const DftPlan*>& plans, const std::vector<int64_t>& g_off,
                      const std::vector<int64_t>& ring0, int ncol, const double* ws_base,

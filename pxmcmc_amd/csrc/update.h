@@ -10,6 +10,7 @@
 //                            applied per component (real soft threshold, one noise draw per chain).
 #pragma once
 #include "elem.h"
+#include "mem_policy.h"
 #include "sht_core.h"
 
 namespace pxm {
@@ -238,7 +239,8 @@ __device__ __forceinline__ double px_uniform(double v) {
 //     forms them again for every element (a division and a square root, ~25 fp64 operations).
 // Every element sees the operations of px_update / px_noise_philox_t<true> in their order: the same bits
 // (tests/test_gpu_dft_stock.py).  logt / sct: the Box-Muller tables (philox.h), the global ones or a kernel's LDS copies.
-template <int ES>
+// XOUT: cache policy (mem_policy.h) of the X' stores -- the new state is next read one whole iteration later.
+template <int ES, int XOUT = MEM_DEFAULT>
 __device__ __forceinline__ void px_stock_update4(const PxOut& out, const bool (&ok)[4], int64_t e0, int64_t ce0, int zoff, int ch_s,
                                                  uint64_t it, double2* park, const double2* logt, const double2* sct) {
   const double delta = out.delta, r_dl = px_uniform(out.delta / out.lmda), s_2d = px_uniform(sqrt(2 * out.delta));
@@ -262,7 +264,7 @@ __device__ __forceinline__ void px_stock_update4(const PxOut& out, const bool (&
       const double2 xv = park[64 * u];
       xn = double2{chain_step_real_rs(xs[u].x, soft_real(xs[u].x, Ts[u]), xv.x, q.z0, delta, r_dl, s_2d),
                    chain_step_real_rs(xs[u].y, soft_real(xs[u].y, Ts[u]), -xv.y, q.z1, delta, r_dl, s_2d)};
-      reinterpret_cast<double2*>(out.f)[ce0 + ES * u] = xn;
+      PXM_MEM_STORE(XOUT, reinterpret_cast<double2*>(out.f), ce0 + ES * u, xn)
     }
     park[64 * u] = xn;
   };

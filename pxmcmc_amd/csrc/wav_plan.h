@@ -85,6 +85,7 @@ struct pxm_wav_plan_s {
   bool plain_group = true;  // blocks <-> rings of the member scales in one grid (PXM_NO_PLAIN_DFT_GROUP=1: per scale)
   std::vector<int> lane_of;  // per scale: -1 = caller's stream, else side stream index
   pxm::DftGroupList dft_group;   // every scale's rings -> X' -> rings kernel in one grid (ring-space step)
+  bool mem_policy = true;    // the plan's lists were made with the build's cache policies (mem_policy.h; PXM_MEM_POLICY is not 0)
   int pk = 0;                // live columns per slab of the packed per-scale lists, 0 = unpacked (more than 2 chains)
   std::vector<int> el_lo_s;  // per scale: first degree of the support (rows / contraction steps below it are skipped)
   pxm::WlAttach* wl = nullptr;   // weak-lensing attachment (owned), null = none attached

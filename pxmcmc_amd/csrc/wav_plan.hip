@@ -1,5 +1,6 @@
 // Wavelet plan: tables, workspace and static task lists; create / destroy and the plan's housekeeping entry points.
 #include "wav_plan.h"
+#include "mem_policy.h"
 
 #include <cmath>
 #include <memory>
@@ -129,6 +130,7 @@ static int wav_plan_create_impl(const char* who, int L, double B, int J_min, int
     if ((rc = dft_geometry(L, &g))) return rc;
   }
   if ((rc = status_alloc(&p->d_status))) return rc;
+  p->mem_policy = mem_policy_from_env();  // (read again, to the same effect, by dft_group_create below)
   // tables: every scale needs the forward pair (synthesis: FWD, its adjoint: FWD_ADJ) and, for the
   // analysis setting, the inverse pair at its own bandlimit (spin 0); L needs all four, at the plan's spin.
   p->T.resize(p->nsc);
@@ -361,6 +363,17 @@ int64_t pxm_wav_workspace_nonfinite(pxm_wav_plan_t p, pxm_stream_t stream) {
   return (int64_t)h;
 }
 
+// test aid: the arrays of the workspace (everything in front of the scratch row block) -> out, at most cap doubles
+int64_t pxm_wav_workspace_read(pxm_wav_plan_t p, double* out, int64_t cap, pxm_stream_t stream) {
+  PXM_REQUIRE(p, "pxm_wav_workspace_read: null plan");
+  const int64_t n = std::min<int64_t>(cap, p->offS);
+  if (n > 0) {
+    PXM_REQUIRE(out, "pxm_wav_workspace_read: null destination");
+    PXM_HIP(hipMemcpyAsync(out, p->ws, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  }
+  return p->offS;
+}
+
 // bit mask of the bounded waits of this plan's kernels that EXPIRED since the last clear (0 = none): bit 1 a wave-pair
 // wait of the fused phi-DFT kernels.  Synchronises the stream.
 int pxm_wav_status(pxm_wav_plan_t p, int clear, pxm_stream_t stream) {
@@ -379,6 +392,13 @@ int pxm_wav_exact_dft_scales(pxm_wav_plan_t p) {
 int pxm_wav_dft_stock(pxm_wav_plan_t p) {
   PXM_REQUIRE(p, "pxm_wav_dft_stock: null plan");
   return (p->dft_group.d && p->dft_group.stock) ? 1 : 0;
+}
+
+// mask of the streams this plan's launches access non-temporally (include/pxmcmc_amd.h); 0 with PXM_MEM_POLICY=0 at creation
+int pxm_wav_mem_policy(pxm_wav_plan_t p) {
+  PXM_REQUIRE(p, "pxm_wav_mem_policy: null plan");
+  if (!p->mem_policy) return 0;
+  return (p->dft_group.d && p->dft_group.stock && DFT_X_OUT_POLICY == MEM_STREAM) ? 1 : 0;  // bit 0: the X' stores
 }
 
 int64_t pxm_wav_table_bytes(pxm_wav_plan_t p, int op) {

@@ -456,6 +456,16 @@ class WavPlan(_WaveletPlan):
         phi-DFT stage; False with PXM_DFT_STOCK=0 at creation"""
         return bool(check(lib.pxm_wav_dft_stock(self._h)))
 
+    def mem_policy(self):
+        """mask of the streams of the ring-space step that the plan's launches access non-temporally (csrc/mem_policy.h:
+        bit 0 the X' stores of the fused phi-DFT step, on its STOCK instantiation); 0 with PXM_MEM_POLICY=0 at creation,
+        when every launch takes the default-policy kernel instantiations"""
+        return int(check(lib.pxm_wav_mem_policy(self._h)))
+
+    def info(self):
+        """what the plan's fused launches run on: exact-length DFT scales, STOCK instantiation, cache-policy mask"""
+        return {"exact_dft_scales": self.exact_dft_scales(), "dft_stock": self.dft_stock(), "mem_policy": self.mem_policy()}
+
     # ---- weak-lensing measurement fused with the synthesis (pxm_wav_wl_*) ----
     def wl_attach(self, pix2data, weight, ndata):
         """pix2data: int32 [npix] pixel -> index in the masked data vector (< 0 masked) or None; weight: float64
@@ -501,6 +511,13 @@ class WavPlan(_WaveletPlan):
     def workspace_nonfinite(self):
         """test aid: non-finite values anywhere in the plan's workspace (padding chains' columns included)"""
         return int(check(lib.pxm_wav_workspace_nonfinite(self._h, _stream())))
+
+    def workspace_read(self):
+        """test aid: a copy of the plan's workspace (every ring and harmonic array of its stages), float64 on the device"""
+        n = int(check(lib.pxm_wav_workspace_read(self._h, None, 0, _stream())))
+        out = torch.empty(n, dtype=_REAL, device=device())
+        check(lib.pxm_wav_workspace_read(self._h, _p(out), n, _stream()))
+        return out
 
     # ---- live kernel timing of this plan (bench.py roofline leg) ----
     def profile_enable(self, max_launches):
