@@ -245,8 +245,16 @@ def main(argv=None):
                     help="harmonic-space posterior: WeakLensingHarmonic + harmonic wavelets + L1, started from sks_estimate")
     ap.add_argument("--healpix", type=int, default=None, metavar="NSIDE",
                     help="read the shear at the pixel centres of a HEALPix map (RING order) of this nside: WeakLensingHealpix")
+    ap.add_argument("--wiener", action="store_true",
+                    help="Gaussian prior 1 / C_l on kappa_lm: the Wiener map by batched conjugate gradients (optim.GaussianPosterior)")
+    ap.add_argument("--wiener-draws", type=int, default=0, metavar="N",
+                    help="--wiener: also N exact posterior draws (--chains per solve) and the standard-deviation map of kappa")
     args = ap.parse_args(argv)
     args.estimate_mu = args.estimate_mu or args.estimate_mu_per_scale
+    if args.wiener_draws and not args.wiener:
+        ap.error("--wiener-draws needs --wiener")
+    if args.wiener and (args.harmonic or args.healpix is not None or args.map_start or args.estimate_mu or args.summary):
+        ap.error("--wiener runs on its own: the MW pixel-space data, no sampler options")
     if args.healpix is not None and (args.harmonic or args.local_ci is not None or args.hyp_test is not None):
         ap.error("--healpix runs the pixel-space posterior without --local-ci / --hyp-test (their regions are MW superpixels of the data grid)")
     if args.summary_alpha is not None and not args.summary:
@@ -279,6 +287,8 @@ def main(argv=None):
         measurement = WeakLensing(L, mask, ngal=np.full_like(mask, 30), max_chains=args.chains)
     gammas_truth, kappa_truth = prepare_gammas(synthetic_kappa_lm(L, args.seed), L, measurement)
 
+    if args.wiener:
+        return _main_wiener(args, L, measurement, mask, gammas_truth, kappa_truth)
     transform = SphericalWaveletTransform(L, B, J_min, dirs=args.dirs, max_chains=args.chains)
     forward_operator = ForwardOperator(gammas_truth, 1 / measurement.inv_cov, setting, transform=transform,
                                        measurement=measurement, nparams=transform.ncoefs)
@@ -323,6 +333,61 @@ def main(argv=None):
           f"per iteration; posterior-mean kappa error on the unmasked sky {rel:.3f}; masked fraction {1 - seen.mean():.3f}")
     return {"path": path, "rel_err": rel, "ms_per_iter": elapsed / max(niter, 1) * 1e3, "mcmc": mcmc,
             "operator": forward_operator, "mask": mask, "gammas": gammas_truth}
+
+
+def synthetic_cl(L, sigma=BEAM_SIGMA):
+    """the power spectrum of the smoothed field of :func:`synthetic_kappa_lm`; the monopole and dipole, which it leaves out and
+    the shear does not see, get the quadrupole's power so that the prior pins them near zero with a finite precision"""
+    el = np.arange(L, dtype=float)
+    cl = (1.0 + el) ** -1.5 * np.exp(-((el / 200.0) ** 2)) * np.exp(-el * (el + 1.0) * sigma ** 2)
+    cl[:2] = cl[min(2, L - 1)]
+    return cl
+
+
+def _main_wiener(args, L, measurement, mask, gammas_truth, kappa_truth):
+    """--wiener: harmonic state kappa_lm with the 1 / C_l prior of the synthetic spectrum; the Wiener map is the exact
+    posterior mean, --wiener-draws N adds the exact standard-deviation map from N independent posterior draws"""
+    from pxmcmc_amd.optim import GaussianPosterior
+    from pxmcmc_amd.prior import Gaussian
+    from pxmcmc_amd.transforms import SphericalHarmonicTransform
+
+    if args.setting != "synthesis":
+        raise ValueError("--wiener runs the synthesis setting")
+    transform = SphericalHarmonicTransform(L, max_chains=args.chains)
+    forward_operator = ForwardOperator(gammas_truth, 1 / measurement.inv_cov, "synthesis", transform=transform,
+                                       measurement=measurement, nparams=L * L)
+    params = PxMCMCParams(nsamples=args.nsamples, nburn=args.nburn, ngap=args.ngap, delta=args.delta, lmda=args.delta / 2,
+                          mu=args.mu, s=args.s, complex=True, verbosity=0)
+    # T / lmda = mu: the posterior is 1/2 Re L2 + mu 1/2 sum |kappa_lm|^2 / C_l
+    prior = Gaussian.from_power_spectrum(synthetic_cl(L), L, params.lmda * params.mu)
+    print(f"Number of data points: {gammas_truth.size}")
+    print(f"Number of model parameters: {forward_operator.nparams}")
+    step_hint(forward_operator, params, args)
+    post = GaussianPosterior(forward_operator, prior, params, nchains=args.chains, seed=args.seed)
+    t0 = time.perf_counter()
+    klm = post.run()
+    elapsed = time.perf_counter() - t0
+    klm = klm if args.chains == 1 else klm[0]
+    kappa = np.asarray(transform.inverse(klm)).real.reshape(L, 2 * L - 1)
+    seen = mask.astype(bool)
+    rel = np.linalg.norm((kappa - kappa_truth.real)[seen]) / np.linalg.norm(kappa_truth.real[seen])
+    base = os.path.join(args.outdir, f"wiener_{args.jobid}")
+    np.save(base + "_kappa.npy", kappa)
+    print(f"Wiener filter: {int(post.niter.max())} CG iterations (converged: {bool(post.converged.all())}, relative residual "
+          f"{float(post.rel_residual[-1].max()):.2e}, graph replay: {post.used_graph}) in {elapsed:.2f} s; kappa error on the "
+          f"unmasked sky {rel:.3f}; saved {base}_kappa.npy")
+    out = {"rel_err": rel, "niter": post.niter, "solver": post, "operator": forward_operator, "mask": mask, "kappa": kappa}
+    if args.wiener_draws:
+        t0 = time.perf_counter()
+        summary = post.sample(args.wiener_draws, summary="image")
+        elapsed = time.perf_counter() - t0
+        std = np.sqrt(summary.pooled_variance().cpu().numpy()).reshape(L, 2 * L - 1)
+        np.save(base + "_kappa_std.npy", std)
+        print(f"{args.wiener_draws} exact posterior draws in {post.solve_iterations.shape[0]} solves of {args.chains} ("
+              f"{int(post.solve_iterations.max())} iterations at most) in {elapsed:.2f} s; standard deviation of kappa: median "
+              f"{np.median(std):.3e} seen, {np.median(std[~seen]) if (~seen).any() else float('nan'):.3e} masked; saved {base}_kappa_std.npy")
+        out["kappa_std"] = std
+    return out
 
 
 def _main_harmonic(args, L, B, J_min, setting):

@@ -581,6 +581,46 @@ int pxm_tv_primal_step(const void* X, const void* G, const void* V, const double
 int pxm_tv_dual_step(const void* V, const void* Xbar, const double* ab, const double* T, double T_scalar, double sigma,
                      double rscale, void* V1_out, double* sums, double* scratch, int L, int C, int dtype,
                      pxm_stream_t stream);
+/* The Gaussian posterior: preconditioned conjugate gradients on H x = b per chain, H = D + A Hermitian
+ * positive definite, D the prior precision ([n] shared by chains, or D_scalar) and A the linear part of
+ * x -> calc_gradg(forward(x)).  The single-reduction recurrences of Chronopoulos & Gear (1989): one iteration is the
+ * operator pair q = calc_gradg(forward(U)) and the two entry points below.  Every state array is [C][n], float64 or
+ * complex128; every per-chain scalar is real.
+ * coef [C][PXM_CG_COEF] float64 on the device, a chain's row: alpha, beta, gamma_old, alpha_old, rho = sum |r|^2 of the last
+ *   pxm_cg_apply, ||b||^2 (set by the caller), flags (0, PXM_CG_FROZEN, or PXM_CG_FROZEN | PXM_CG_BREAKDOWN, as a double) and
+ *   the iterations taken (as a double).  A solve starts from a row that is zero but for ||b||^2.
+ * pxm_cg_apply, with Q = q, B0 = -calc_gradg(forward(0)) ([n] shared by chains; NULL: zero) and R the residual:
+ *   W_out = fma(D_i, U, Q + B0) per component (the sum rounded first);
+ *   per chain gamma = sum Re conj(R) U, delta = sum Re conj(U) W_out, rho = sum |R|^2: plain products and sums without
+ *   contraction, added in a fixed order that depends on n only (a chain's sums do not depend on its batch);
+ *   then, per chain, on the device: flags != 0 -> alpha = beta = 0, the rest of the row as it was (the sums are not formed);
+ *   rho <= tol^2 ||b||^2 -> alpha = beta = 0, flags = PXM_CG_FROZEN;
+ *   else beta = gamma / gamma_old (0 when iterations == 0), denom = delta - beta gamma / alpha_old (delta when iterations
+ *   == 0); denom not > 0, or gamma or delta not finite -> alpha = beta = 0, flags = PXM_CG_FROZEN | PXM_CG_BREAKDOWN;
+ *   else alpha = gamma / denom, gamma_old = gamma, alpha_old = alpha, iterations += 1.
+ *   With n == 0 the sums are zero, so every chain freezes.  W_out of a frozen chain is not written.
+ *   scratch: caller-owned, 3 * PXM_FISTA_SLICES_MAX * C doubles.
+ * pxm_cg_update, per component and in place but for X (Minv [n] shared by chains, or Minv_scalar):
+ *   P = fma(beta, P, U);  S = fma(beta, S, W);  X_dst = fma(alpha, P, X_src);  R = fma(-alpha, S, R);  U = Minv_i R;
+ *   a chain with flags != 0: X_dst = X_src, and none of its other arrays is read or written.
+ *   The eight arrays must all be different (only equal base pointers are detected and refused).
+ * pxm_gauss_prox: out = X / (1 + T p_i) per component, p [n] shared by chains or precision_scalar; the sum 1 + T p_i is
+ *   rounded (product, then sum), one division per component: the prox of T 1/2 sum_i p_i |x_i|^2.  out must not alias X.
+ * pxm_cg_rhs: out = B_i + g_scale G + (z_scale S_i) Z, per component acc = B_i; acc = fma(g_scale, G, acc); acc =
+ *   fma(z_scale S_i (rounded), Z, acc).  B [n] shared by chains, G and Z [C][n], S [n] or S_scalar; B, G, Z may each be NULL
+ *   (no term).  out must not alias an input.
+ * No atomics and no host read: a HIP graph replays all of them. */
+#define PXM_CG_COEF 8
+#define PXM_CG_FROZEN 1
+#define PXM_CG_BREAKDOWN 2
+int pxm_cg_apply(const void* U, const void* Q, const void* B0, const double* D, double D_scalar, const void* R, void* W_out,
+                 double* coef, double tol, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream);
+int pxm_cg_update(void* U, const void* W, void* P, void* S, const void* X_src, void* X_dst, void* R, const double* Minv,
+                  double Minv_scalar, const double* coef, int64_t n, int C, int dtype, pxm_stream_t stream);
+int pxm_gauss_prox(const void* X, const double* precision, double precision_scalar, double T, void* out, int64_t n, int C,
+                   int dtype, pxm_stream_t stream);
+int pxm_cg_rhs(const void* B, const void* G, double g_scale, const void* Z, const double* S, double S_scalar, double z_scale,
+               void* out, int64_t n, int C, int dtype, pxm_stream_t stream);
 /* One SAPG iteration (Vidal, De Bortoli, Pereyra & Durmus 2020): a MYULA step of every chain on the
  * posterior whose prior is scaled by the chain's theta, then the move of theta towards the marginal maximum-likelihood
  * value of the regularisation strength.  Every state array [C][n]; theta, eta [C] float64 on the device, updated in place.

@@ -182,6 +182,10 @@ SIGNATURES = {
     ),
     "pxm_pd_primal_step": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_pd_dual_step": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_cg_apply": (c_int, [c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_cg_update": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_gauss_prox": (c_int, [c_vp, c_vp, c_dbl, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_cg_rhs": (c_int, [c_vp, c_vp, c_dbl, c_vp, c_vp, c_dbl, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_tv_grad": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "pxm_tv_grad_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "pxm_tv_value": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
@@ -248,6 +252,9 @@ CONSTANTS = dict(
     MODE_CPLX_NOISE=1,  # complex noise,
     MODE_REAL_PAIRS=2,  # two real chains per complex slot
     FISTA_SLICES_MAX=256,  # partial sums per chain of pxm_fista_step
+    CG_COEF=8,  # doubles per chain of the coefficient array of pxm_cg_apply / pxm_cg_update
+    CG_FROZEN=1,  # bits of a chain's flags entry there
+    CG_BREAKDOWN=2,
     SAPG_SLICES_MAX=256,  # partial sums per chain of pxm_sapg_step (per chain and group of pxm_sapg_step_groups)
     SAPG_GROUPS_MAX=32,  # most groups of pxm_sapg_step_groups
     LCI_POINTS=32,  # values of xi per slot and pass of pxm_lci_eval

@@ -30,6 +30,7 @@ import torch
 from . import ops
 from .forward import InverseCovariance, power_iteration
 from .mcmc import PxMCMCParams, Stepper
+from .ops.cg import CG_BNORM2, CG_FLAGS, CG_ITERS, CG_RHO
 from .utils import to_like
 
 
@@ -232,6 +233,304 @@ class FISTA(Stepper):
             self.nrestarts = self.restarts[-1]
         self.objective_map = self.objective[-1]
         out = self.X_map if C > 1 else self.X_map[0]
+        return out.clone() if as_torch else out.cpu().numpy()
+
+
+# ---- Gaussian prior: the exact posterior by batched conjugate gradients --------------------------------
+class GaussianPosterior(Stepper):
+    """
+    The posterior of ``(forward, prior, mcmcparams)`` with a :class:`pxmcmc_amd.prior.Gaussian` prior,
+
+        F(X) = 1/2 Re L2(X) + (T / lmda) 1/2 sum_i p_i |X_i|^2,
+
+    is Gaussian with precision ``H = D + A``: ``D = (T / lmda) p`` and ``A`` the linear part of
+    ``x -> calc_gradg(forward(x))``, taken on :func:`gradient_operator` ``(forward)``.  :meth:`run` solves ``H x = b0``,
+    ``b0 = -calc_gradg(forward(0))``, for the MAP point, which is the posterior mean (the Wiener filter); :meth:`sample` gives
+    exact, independent draws by perturbation-optimisation (Papandreou & Yuille 2010; Orieux, Feron & Giovannelli 2012): the
+    same system with the right-hand side ``b0 + Phi^H sqrt(W) omega_1 + sqrt(D) omega_2``, whose covariance is ``H``.
+
+    Every chain of the batch is its own system, solved by the single-reduction preconditioned conjugate gradients of
+    Chronopoulos & Gear (1989): one iteration is the operator pair and two HIP launches (``pxm_cg_apply``,
+    ``pxm_cg_update``); the step lengths, the convergence freeze and the breakdown guard are per chain and on the device, so
+    the iteration is replayed from a captured HIP graph between checks.  ``cg_np`` states it in numpy.
+
+    :param nchains: C systems solved together as one ``[C, N]`` batch (C draws per solve)
+    :param tol: a chain is frozen once its recurrence residual satisfies ``||r|| <= tol ||b||``
+    :param max_iter: iteration limit
+    :param check_every: iterations between two reads of the per-chain coefficients by the host
+    :param precond: ``"diag"``: ``M = D + h`` with ``h`` a Hutchinson estimate of ``trace(A) / N`` from 8 Philox Gaussian
+        probes through the operator, formed once here; ``None``: the identity; a positive vector ``[N]``: ``M^-1`` itself
+    :param use_graph: replay from a captured HIP graph (``False``: the same launches one by one, same results)
+    :param seed, chain_offset: draw ``k`` of chain ``c`` uses the float64 Philox stream at ``(seed, chain_offset + c)``,
+        iterations ``2 k`` (``omega_1``, data length) and ``2 k + 1`` (``omega_2``, state length)
+
+    Real states (``params.complex = False``, real data, an operator that keeps them real) and complex128 states are both
+    supported.  After :meth:`run`: ``niter``, ``converged``, ``breakdown`` (per chain), ``rel_residual`` (``[nchecks, C]``:
+    ``||r|| / ||b||`` of the recurrence residual at the last decision before each check), ``checks``, ``X_map`` / ``preds_map``
+    (device arrays), ``objective_map`` (``[C]``) and ``used_graph``.  After :meth:`sample`: the same per-chain records of the
+    last solve, and ``solve_iterations`` and ``solve_converged`` (``[nsolves, C]``).
+    """
+
+    HUTCHINSON_PROBES = 8
+    _PROBE_ITER = 1 << 62  # Philox iteration of the probes: off the draws' iterations 2 k, 2 k + 1
+
+    def __init__(self, forward, prior, mcmcparams=PxMCMCParams(), nchains=1, tol=1e-8, max_iter=1000, check_every=10,
+                 precond="diag", use_graph=True, seed=0, chain_offset=0):
+        if not hasattr(prior, "precision") or getattr(prior, "T", None) is None:
+            raise ValueError("GaussianPosterior needs a prior with precision and T (prior.Gaussian)")
+        super().__init__(forward, prior, mcmcparams, nchains=nchains, seed=seed, chain_offset=chain_offset, use_graph=use_graph)
+        if int(max_iter) < 1 or int(check_every) < 1:
+            raise ValueError("GaussianPosterior needs max_iter >= 1 and check_every >= 1")
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError("GaussianPosterior needs a finite tol >= 0")
+        self.tol, self.max_iter, self.check_every = float(tol), int(max_iter), int(check_every)
+        self.gradient_op = gradient_operator(forward)
+        n, dt = int(forward.nparams), self._state_dtype()
+        self._n, self._dt = n, dt
+        p = np.asarray(prior.precision, dtype=float)
+        if p.ndim and p.size != n:
+            raise ValueError(f"GaussianPosterior: the precision has {p.size} entries, the state {n}")
+        if not np.all(np.isfinite(p)) or np.any(p < 0):
+            raise ValueError("GaussianPosterior: the precision must be finite and not negative")
+        scale = float(prior.T) / float(self.lmda)
+        self._D = float(p.reshape(-1)[0]) * scale if p.ndim == 0 or n == 1 else ops.as_device(p * scale, torch.float64)
+        zero = torch.zeros((1, n), dtype=dt, device=ops.device())
+        self._b0 = torch.zeros(n, dtype=dt, device=zero.device)
+        ops.skrock_stage(self._linear(zero), -1.0, out=self._b0)  # b0 = -calc_gradg(forward(0))
+        self.precond = precond if precond is None or isinstance(precond, str) else "given"
+        self._minv = self._preconditioner(precond)
+
+    def _state_dtype(self, start=None):
+        """complex128 when ``params.complex``, the data or the start point is complex, or when the state is the coefficients
+        of a wavelet or harmonic transform (synthesis setting); float64 otherwise"""
+        from .transforms import SphericalHarmonicTransform, SphericalWaveletTransform
+
+        f = self.forward
+        cplx = bool(self.complex) or (getattr(f, "setting", "synthesis") == "synthesis" and isinstance(
+            getattr(f, "transform", None), (SphericalWaveletTransform, SphericalHarmonicTransform)))
+        for a in (f.data, start):
+            if a is not None:
+                cplx = cplx or (a.is_complex() if isinstance(a, torch.Tensor) else np.iscomplexobj(a))
+        return torch.complex128 if cplx else torch.float64
+
+    def _linear(self, v):
+        """``calc_gradg(forward(v)) = A v - b0`` of a ``[C, N]`` device batch, in the state's dtype"""
+        f = self.gradient_op
+        return ops.as_device(f.calc_gradg(ops.as_device(f.forward(v))), self._dt)
+
+    def _preconditioner(self, precond):
+        """``M^-1`` as the update launch takes it: a float or a float64 ``[N]`` device vector"""
+        n, D = self._n, self._D
+        if precond is None:
+            self.trace_estimate = None
+            return 1.0
+        if isinstance(precond, str):
+            if precond != "diag":
+                raise ValueError('GaussianPosterior: precond is "diag", None or a positive vector [nparams]')
+            num = den = 0.0
+            for k in range(self.HUTCHINSON_PROBES):
+                z = ops.randn(n, 1, complex_=self._dt.is_complex, seed=self.seed, chain0=k, it=self._PROBE_ITER, noise64=True)
+                Az = ops.cg_rhs(z, B=self._b0, G=self._linear(z))
+                num += float(ops.reduce_vdot(z, Az)[0].real)
+                den += float(ops.reduce_vdot(z, z)[0].real)
+            h = num / den if den > 0 else 0.0
+            self.trace_estimate = h
+            M = D + h
+            if isinstance(M, float):
+                if not (np.isfinite(M) and M > 0):
+                    raise ValueError("GaussianPosterior: the diagonal preconditioner D + trace(A) / N is not positive")
+                return 1.0 / M
+            if not bool((M > 0).all()):
+                raise ValueError("GaussianPosterior: the diagonal preconditioner D + trace(A) / N is not positive")
+            return (1.0 / M).contiguous()
+        m = np.asarray(precond.cpu() if isinstance(precond, torch.Tensor) else precond, dtype=float)
+        if m.ndim != 1 or m.size != n:
+            raise ValueError(f"GaussianPosterior: a given precond is M^-1 as a vector of the state's length {n}, got shape {m.shape}")
+        if not np.all(np.isfinite(m)) or np.any(m <= 0):
+            raise ValueError("GaussianPosterior: a given precond must be positive and finite")
+        self.trace_estimate = None
+        return float(m[0]) if n == 1 else ops.as_device(m, torch.float64)
+
+    # ---- the iteration on the stepping engine -----------------------------------------------------------------------------
+    def _engine_start(self, X, preds=None, i0=0):
+        """static state (XA, XB) plus the residual R, U = M^-1 R, the directions P and S, the work array W and the per-chain
+        coefficients; P of the engine is not carried (the solver forms forward(X) once, at the end of :meth:`run`).
+        :meth:`_load` puts the system into the static buffers; every solve starts an engine of its own"""
+        self._engine_stop()
+        X = ops.as_device(X).contiguous()
+        C = X.shape[0]
+        self._R, self._U, self._P, self._S, self._W = (torch.zeros_like(X) for _ in range(5))
+        self._R0, self._U0 = torch.zeros_like(X), torch.zeros_like(X)
+        self._coef = ops.cg_coef(torch.zeros(C, dtype=torch.float64, device=X.device))
+        self._coef0 = self._coef.clone()
+        scratch = ops.cg_scratch(C, X.device)
+        R, U, P, S, W, coef, b0, D, minv, tol = self._R, self._U, self._P, self._S, self._W, self._coef, self._b0, self._D, self._minv, self.tol
+
+        def step(eng, src, dst):
+            ops.cg_apply(U, self._linear(U), b0, D, R, coef, tol, out=W, scratch=scratch)
+            ops.cg_update(U, W, P, S, src, R, minv, coef, out=dst)
+
+        def reset(eng):
+            R.copy_(self._R0)
+            U.copy_(self._U0)
+            P.zero_()
+            S.zero_()
+            coef.copy_(self._coef0)
+
+        no_preds = torch.zeros((C, 0), dtype=X.dtype, device=X.device)
+        return self._engine_start_generic(X, no_preds, i0, step, lazy=False, graph_ok=self.use_graph, reset=reset)
+
+    def _load(self, B, X0=None):
+        """a new system into the engine: right-hand sides ``B`` ``[C, N]``, start ``X0`` (None: zero, so ``r = b``)"""
+        eng = self._eng
+        if X0 is None:
+            eng.XA.zero_()
+            self._R0.copy_(B)
+        else:
+            eng.XA.copy_(X0)
+            HX = ops.cg_rhs(B, B=self._b0, G=self._linear(eng.XA), Z=eng.XA, S=self._D)
+            ops.skrock_stage(B, 1.0, e=-1.0, V=HX, out=self._R0)
+        ops.cg_rhs(B, Z=self._R0, S=self._minv, out=self._U0)
+        self._coef0.zero_()
+        self._coef0[:, CG_BNORM2] = ops.reduce_vdot(B, B).real
+        eng.side = "A"
+        eng.reset()
+
+    def _iterate(self):
+        """advance until every chain is frozen or ``max_iter`` -> (X, coefficients on the host, residual rows, checks)"""
+        rows, checks, i = [], [], 0
+        while i < self.max_iter:
+            k = min(self.check_every, self.max_iter - i)
+            self._engine_advance(k)
+            i += k
+            self._check_device_status()
+            coef = self._coef.cpu().numpy()
+            with np.errstate(invalid="ignore", divide="ignore"):
+                rows.append(np.where(coef[:, CG_BNORM2] > 0, np.sqrt(coef[:, CG_RHO] / coef[:, CG_BNORM2]), 0.0))
+            checks.append(i)
+            if (coef[:, CG_FLAGS] != 0).all():
+                break
+        eng = self._eng
+        return (eng.XA if eng.side == "A" else eng.XB), coef, np.stack(rows), checks
+
+    def _record(self, coef, rows, checks):
+        flags = coef[:, CG_FLAGS].astype(int)
+        self.niter = coef[:, CG_ITERS].astype(int)
+        self.breakdown = (flags & ops.CG_BREAKDOWN) != 0
+        self.converged = ((flags & ops.CG_FROZEN) != 0) & ~self.breakdown
+        self.rel_residual, self.checks = rows, checks
+        self.used_graph = self._eng.graph is not None
+        self.graph_error = self._eng.graph_error
+
+    def run(self, start_point=None):
+        """Solve ``H x = b0`` from ``start_point`` (``[N]``, or ``[C, N]`` with one row per chain; ``None``: zero).  Returns the
+        MAP point, which is the posterior mean, in the caller's array kind (numpy, or a device tensor for a tensor start
+        point): ``[N]`` for one chain, ``[C, N]`` for a batch."""
+        C = self.nchains
+        as_torch = isinstance(start_point, torch.Tensor)
+        zero_start = start_point is None
+        if zero_start:
+            start_point = np.zeros(self.forward.nparams)
+        X0, _ = self._initial_sample(start_point)
+        self._engine_start(X0)
+        try:
+            B = ops.cg_rhs(X0, B=self._b0)
+            self._load(B, None if zero_start else X0)
+            X, coef, rows, checks = self._iterate()
+            self._record(coef, rows, checks)
+            self.X_map = X.clone()
+            self.preds_map = ops.as_device(self.forward.forward(self.X_map)).clone()
+        finally:
+            self._engine_stop()
+        data_term = 0.5 * self._l2_dev(self.preds_map).real.cpu().numpy()
+        prior_term = np.atleast_1d(ops.as_device(self.prior.prior(self.X_map)).cpu().numpy()) * (float(self.prior.T) / self.lmda)
+        self.data_term, self.prior_term = data_term, prior_term
+        self.objective_map = data_term + prior_term
+        out = self.X_map if C > 1 else self.X_map[0]
+        return out.clone() if as_torch else out.cpu().numpy()
+
+    def _draw_operands(self):
+        """``(s, sqrt(D))`` of the draws' right-hand sides: ``s = 1 / sqrt(w)`` where the data weight ``w = Re(invcov) > 0``,
+        else 0 (masked data need no special case)"""
+        inv = self.gradient_op.invcov
+        if hasattr(inv, "matvec") or not hasattr(inv, "diag"):
+            raise ValueError("GaussianPosterior.sample needs a diagonal inverse covariance: the data perturbation "
+                             "sqrt(W) omega_1 is formed element by element (run() accepts a full covariance)")
+        w = ops.as_device(inv.diag).real.to(torch.float64).reshape(-1)
+        if bool((w < 0).any()):
+            raise ValueError("GaussianPosterior.sample: the data weights Re(invcov) must not be negative")
+        s = torch.where(w > 0, 1.0 / torch.sqrt(torch.where(w > 0, w, torch.ones_like(w))), torch.zeros_like(w)).contiguous()
+        D = self._D
+        return s, (float(np.sqrt(D)) if isinstance(D, float) else torch.sqrt(D).contiguous())
+
+    def draw_rhs(self, k):
+        """the right-hand sides ``[C, N]`` of draw ``k`` of every chain (device array): ``b0 + calc_gradg(data + s o omega_1)
+        + sqrt(D) o omega_2`` with the deviates of the Philox iterations ``2 k`` and ``2 k + 1``.  ``omega_2``, and ``omega_1``
+        with it, is complex when the state is: the perturbations then cover the real and the imaginary part of ``F``."""
+        if getattr(self, "_draw_ops", None) is None:
+            self._draw_ops = self._draw_operands()
+        s, sqrtD = self._draw_ops
+        C, cplx = self.nchains, self._dt.is_complex
+        kw = dict(complex_=cplx, seed=self.seed, chain0=self.chain_offset, noise64=True)
+        w1 = ops.randn(s.numel(), C, it=2 * int(k), **kw)
+        if self.forward.data_dev.is_complex() and not cplx:  # (real state, complex data: the predictions carry the data)
+            w1 = w1.to(torch.complex128)
+        g = ops.as_device(self.gradient_op.calc_gradg(ops.cg_rhs(w1, B=self.forward.data_dev, Z=w1, S=s)), self._dt)
+        w2 = ops.randn(self._n, C, it=2 * int(k) + 1, **kw)
+        return ops.cg_rhs(w2, B=self._b0, G=g, Z=w2, S=sqrtD)
+
+    def sample(self, ndraws, summary=None, summary_ess=None, summary_alpha=None, first_draw=0, as_torch=False):
+        """``ndraws`` exact, independent draws of the posterior, C per solve (draw ``first_draw + k`` of chain ``c`` is row
+        ``k C + c``).  Returns them as ``[ndraws, N]`` (numpy, or a device tensor with ``as_torch``).  With ``summary="state"``
+        or ``"image"`` (``transform.inverse`` of the draws) every batch of C draws is folded into a
+        :class:`pxmcmc_amd.uncertainty.PosteriorSummary` instead, which is returned: its moments, R-hat, ESS (with
+        ``summary_ess`` lags) and tails (with ``summary_alpha``) read out as after a sampler run, ``ceil(ndraws / C)`` samples
+        per chain.  Two calls with the same ``seed``, ``chain_offset`` and ``first_draw`` return the same bits."""
+        if summary not in (None, "state", "image"):
+            raise ValueError("summary must be None, 'state' or 'image'")
+        if int(ndraws) < 1:
+            raise ValueError("sample needs ndraws >= 1")
+        self._draw_ops = self._draw_operands()
+        C, n = self.nchains, self._n
+        nsolves = -(-int(ndraws) // C)
+        tr = getattr(self.forward, "transform", None)
+        if summary == "image" and (getattr(self.forward, "setting", "synthesis") == "analysis" or not hasattr(tr, "inverse")):
+            raise ValueError("summary='image' needs forward.transform.inverse in the synthesis setting")
+        post = None
+        out = None if summary else torch.empty((nsolves * C, n), dtype=self._dt, device=ops.device())
+        start = torch.zeros((C, n), dtype=self._dt, device=ops.device())
+        self._engine_start(start)
+        its, ok = [], []
+        try:
+            for k in range(nsolves):
+                # one engine, and so one capture, per solve: the first iterations of a system loaded into an engine whose graph
+                # had replayed before came out wrong on the MI355X (DESIGN.md section 23)
+                if k:
+                    self._engine_start(start)
+                self._load(self.draw_rhs(int(first_draw) + k))
+                X, coef, rows, checks = self._iterate()
+                self._record(coef, rows, checks)
+                its.append(self.niter.copy())
+                ok.append(self.converged.copy())
+                if self.breakdown.any() or not self.converged.all():
+                    warnings.warn(f"GaussianPosterior.sample: solve {k} did not converge for every chain (breakdown: "
+                                  f"{self.breakdown.tolist()}, relative residuals {rows[-1].tolist()})")
+                if summary is None:
+                    out[k * C:(k + 1) * C].copy_(X)
+                    continue
+                S = X if summary == "state" else ops.as_device(tr.inverse(X))
+                if post is None:
+                    from .uncertainty import PosteriorSummary
+
+                    post = PosteriorSummary(C, S.shape[1], S.is_complex(), best=False, alpha=summary_alpha, nsamples=nsolves,
+                                            ess_lags=summary_ess)
+                post.update(S)
+        finally:
+            self._engine_stop()
+        self.solve_iterations, self.solve_converged = np.stack(its), np.stack(ok)
+        if summary:
+            return post
+        out = out[:int(ndraws)]
         return out.clone() if as_torch else out.cpu().numpy()
 
 

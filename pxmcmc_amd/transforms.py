@@ -142,3 +142,47 @@ class SphericalGradientTransform(Transform):
 
     def inverse_adjoint(self, X):
         raise NotImplementedError("SphericalGradientTransform has no inverse: the gradient annihilates constants")
+
+
+class SphericalHarmonicTransform(Transform):
+    """
+    The MW spherical-harmonic transform as a :class:`Transform` whose state is ``f_lm [L^2]`` in ssht index order
+    (extension): ``inverse`` is the synthesis ``f_lm -> f [L (2L - 1)]``, ``forward`` the analysis, and
+    the two adjoints are those of :class:`pxmcmc_amd.ops.ShtPlan`.  With ``measurements.WeakLensing``, ``Identity``,
+    ``HealpixSampling`` or ``WeakLensingHealpix`` and ``prior.Gaussian.from_power_spectrum`` it is the classic Wiener setting:
+    harmonic state, ``1 / C_l`` prior, masks and noise diagonal in data space.
+
+    :param int max_chains: largest chain batch the transform will be called with
+    """
+
+    def __init__(self, L, spin=0, max_chains=1):
+        if int(L) != L or L < 1:
+            raise ValueError("L must be a positive integer")
+        if int(spin) != spin or abs(spin) >= L:
+            raise ValueError("spin must be an integer with |spin| < L")
+        self.L, self.spin, self.max_chains = int(L), int(spin), int(max_chains)
+        self.ncoefs = self.L * self.L
+        self.npix = self.L * (2 * self.L - 1)
+        self._plan = ops.ShtPlan(self.L, self.spin, max_chains=self.max_chains)
+
+    def ensure_chains(self, C):
+        """Grow the plan's chain capacity (workspace is allocated at plan creation)."""
+        if C > self.max_chains:
+            self.max_chains = int(C)
+            self._plan = ops.ShtPlan(self.L, self.spin, max_chains=self.max_chains)
+
+    def forward(self, X):
+        """image -> f_lm"""
+        return to_like(self._plan.forward(X), X)
+
+    def inverse(self, X):
+        """f_lm -> image"""
+        return to_like(self._plan.inverse(X), X)
+
+    def inverse_adjoint(self, X):
+        """image -> f_lm, the adjoint of :meth:`inverse`"""
+        return to_like(self._plan.inverse_adjoint(X), X)
+
+    def forward_adjoint(self, X):
+        """f_lm -> image, the adjoint of :meth:`forward`"""
+        return to_like(self._plan.forward_adjoint(X), X)
