@@ -249,10 +249,17 @@ def main(argv=None):
                     help="Gaussian prior 1 / C_l on kappa_lm: the Wiener map by batched conjugate gradients (optim.GaussianPosterior)")
     ap.add_argument("--wiener-draws", type=int, default=0, metavar="N",
                     help="--wiener: also N exact posterior draws (--chains per solve) and the standard-deviation map of kappa")
+    ap.add_argument("--gibbs-cl", type=int, default=0, metavar="NSWEEPS",
+                    help="--wiener: also sample the power spectrum C_l jointly with the map by NSWEEPS Gibbs sweeps of --chains chains "
+                         "(optim.GaussianGibbs; the first quarter is burn-in) and write its posterior mean and 95 %% band")
     args = ap.parse_args(argv)
     args.estimate_mu = args.estimate_mu or args.estimate_mu_per_scale
     if args.wiener_draws and not args.wiener:
         ap.error("--wiener-draws needs --wiener")
+    if args.gibbs_cl and not args.wiener:
+        ap.error("--gibbs-cl needs --wiener")
+    if args.gibbs_cl and args.gibbs_cl < 4:
+        ap.error("--gibbs-cl needs at least 4 sweeps")
     if args.wiener and (args.harmonic or args.healpix is not None or args.map_start or args.estimate_mu or args.summary):
         ap.error("--wiener runs on its own: the MW pixel-space data, no sampler options")
     if args.healpix is not None and (args.harmonic or args.local_ci is not None or args.hyp_test is not None):
@@ -387,7 +394,37 @@ def _main_wiener(args, L, measurement, mask, gammas_truth, kappa_truth):
               f"{int(post.solve_iterations.max())} iterations at most) in {elapsed:.2f} s; standard deviation of kappa: median "
               f"{np.median(std):.3e} seen, {np.median(std[~seen]) if (~seen).any() else float('nan'):.3e} masked; saved {base}_kappa_std.npy")
         out["kappa_std"] = std
+    if args.gibbs_cl:
+        out.update(_gibbs_cl(args, L, forward_operator, prior, params, base))
     return out
+
+
+def _gibbs_cl(args, L, forward_operator, prior, params, base):
+    """--gibbs-cl NSWEEPS: the joint posterior of kappa_lm and its variances by Gibbs sampling from the synthetic spectrum as
+    the start; the monopole and dipole, which the shear does not see, keep their prior variance (lmin = 2).  The posterior of
+    DESIGN.md section 23 gives the real and the imaginary part of kappa_lm the variance v_l each, E |kappa_lm|^2 = 2 v_l, so
+    the sampled v_l is set next to C_l / 2 of the spectrum the field was drawn from."""
+    from pxmcmc_amd.optim import GaussianGibbs
+
+    # (the masked weak-lensing system is badly conditioned: a draw solved to 1e-6 of its right-hand side takes thousands of
+    # iterations, and is exact for every purpose of a Monte-Carlo estimate)
+    gibbs = GaussianGibbs(forward_operator, prior, params, nchains=args.chains, groups="degree", lmin=2, seed=args.seed, tol=1e-6,
+                          max_iter=6000, check_every=50)
+    nburn = args.gibbs_cl // 4
+    t0 = time.perf_counter()
+    gibbs.run(args.gibbs_cl, nburn=nburn, summary="state")
+    elapsed = time.perf_counter() - t0
+    cl = gibbs.cl_chain.reshape(-1, L)  # (reported in the units of prior.Gaussian: 1 / precision = C_l)
+    lo, hi = np.quantile(cl, [0.025, 0.975], axis=0)
+    rhat = gibbs.hyper_summary.rhat().cpu().numpy() if args.chains > 1 else np.full(L, np.nan)
+    table = np.stack([np.arange(L), synthetic_cl(L) / 2, cl.mean(axis=0), lo, hi, rhat], axis=1)
+    np.save(base + "_cl.npy", table)
+    inside = float(np.mean((table[2:, 1] >= lo[2:]) & (table[2:, 1] <= hi[2:])))
+    print(f"Gibbs C_l: {args.gibbs_cl} sweeps ({nburn} burn-in) of {args.chains} chain(s) in {elapsed:.2f} s, "
+          f"{int(gibbs.solve_iterations.max())} CG iterations at most (all converged: {bool(gibbs.solve_converged.all())}); half the spectrum "
+          f"of the field lies in the 95 % band at {inside:.0%} of the degrees l >= 2; largest R-hat of log C_l "
+          f"{np.nanmax(rhat[2:]) if args.chains > 1 else float('nan'):.3f}; saved {base}_cl.npy (l, C_l / 2 of the field, mean, 2.5 %, 97.5 %, R-hat)")
+    return {"cl_table": table, "gibbs": gibbs}
 
 
 def _main_harmonic(args, L, B, J_min, setting):

@@ -609,18 +609,48 @@ int pxm_tv_dual_step(const void* V, const void* Xbar, const double* ab, const do
  * pxm_cg_rhs: out = B_i + g_scale G + (z_scale S_i) Z, per component acc = B_i; acc = fma(g_scale, G, acc); acc =
  *   fma(z_scale S_i (rounded), Z, acc).  B [n] shared by chains, G and Z [C][n], S [n] or S_scalar; B, G, Z may each be NULL
  *   (no term).  out must not alias an input.
+ * D_stride, Minv_stride, S_stride: the chain stride of the vector in doubles -- 0: one [n] vector shared by the chains; n: one
+ *   row per chain ([C][n], the arrays pxm_group_variance_draw writes); chain c reads element c * stride + i.  Any other
+ *   value is refused.
  * No atomics and no host read: a HIP graph replays all of them. */
 #define PXM_CG_COEF 8
 #define PXM_CG_FROZEN 1
 #define PXM_CG_BREAKDOWN 2
-int pxm_cg_apply(const void* U, const void* Q, const void* B0, const double* D, double D_scalar, const void* R, void* W_out,
-                 double* coef, double tol, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream);
+int pxm_cg_apply(const void* U, const void* Q, const void* B0, const double* D, double D_scalar, int64_t D_stride, const void* R,
+                 void* W_out, double* coef, double tol, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream);
 int pxm_cg_update(void* U, const void* W, void* P, void* S, const void* X_src, void* X_dst, void* R, const double* Minv,
-                  double Minv_scalar, const double* coef, int64_t n, int C, int dtype, pxm_stream_t stream);
+                  double Minv_scalar, int64_t Minv_stride, const double* coef, int64_t n, int C, int dtype, pxm_stream_t stream);
 int pxm_gauss_prox(const void* X, const double* precision, double precision_scalar, double T, void* out, int64_t n, int C,
                    int dtype, pxm_stream_t stream);
-int pxm_cg_rhs(const void* B, const void* G, double g_scale, const void* Z, const double* S, double S_scalar, double z_scale,
-               void* out, int64_t n, int C, int dtype, pxm_stream_t stream);
+int pxm_cg_rhs(const void* B, const void* G, double g_scale, const void* Z, const double* S, double S_scalar, int64_t S_stride,
+               double z_scale, void* out, int64_t n, int C, int dtype, pxm_stream_t stream);
+/* The conditional draw of the prior precisions given the field, the second half of a Gibbs sweep on the Gaussian posterior
+ * (Wandelt, Larson & Lakshminarayanan 2004).  The state X [C][n] (float64 or complex128) is cut into K
+ * contiguous groups by the device offsets bounds [K + 1], 0 = b_0 < ... < b_K = n; group k has n_k = b_{k+1} - b_k elements.
+ *   nu_k = dof n_k + two_q - 2, dof = 2 for complex128 and 1 for float64, two_q = 2 q of the hyper-prior p(v) ~ v^-q;
+ *   sigma_k = sum_{i in k} |X_i|^2 (products and sums rounded, no contraction);
+ *   chi2_k = sum_{t < nu_k} z_t^2, z_t component t & 1 of the fp64 complex-stream Philox pair keyed (seed, chain0 + c) at
+ *     counter (b_k + k + (t >> 1), iter): element b_k + k + (t >> 1) of pxm_randn(n + K + 1, dtype 1 | PXM_NOISE_F64);
+ *   Dg[c][k] = min(max(chi2_k / sigma_k, d_lo), d_hi), and d_hi when sigma_k is not > 0.
+ *   A group with fixed[k] != 0 or nu_k < 1 keeps Dg[c][k]; nothing of it is summed or drawn.
+ * Both sums are added in a fixed order that depends on n_k only.  The groups are cut into slices of PXM_GIBBS_SLICE elements,
+ * one workgroup each: slice_tab [nslices][2] int64 on the device holds (k, j) of every slice -- elements b_k + j S ... of
+ * group k, S = PXM_GIBBS_SLICE -- ordered by k, then j, and group_slice0 [K + 1] the index of every group's first slice
+ * (group_slice0[K] = nslices = sum_k ceil(n_k / S)).  A slice whose (k, j) lies outside the groups is skipped.
+ * Then, for every element i of group k:  D[c][i] = Dg[c][k], sqrtD[c][i] = sqrt(Dg[c][k]), Minv[c][i] = 1 / (Dg[c][k] + h_c)
+ * (h [C] on the device, or h_scalar; the sum rounded, then one division): the arrays pxm_cg_apply, pxm_cg_rhs and
+ * pxm_cg_update read with chain stride n.  expand_only != 0: only this last launch (Dg as given).
+ *   sums [C][K][2] (or NULL): receives (sigma_k, chi2_k) of every sampled group.
+ *   trace [n_trace][C][K] (or NULL with n_trace 0): row trace_row, when there is one, receives Dg after the draw.
+ *   scratch: caller-owned, 2 * nslices * C doubles.
+ * d_lo, d_hi finite, 0 < d_lo <= d_hi.  Three launches at most, no atomics and no host read: a HIP graph replays the call.
+ * The outputs must not overlap an input or each other (only equal base pointers are detected and refused). */
+#define PXM_GIBBS_SLICE 1024
+int pxm_group_variance_draw(const void* X, const int64_t* bounds, int K, const int64_t* slice_tab, const int64_t* group_slice0,
+                            int64_t nslices, const int32_t* fixed, int two_q, const double* h, double h_scalar, double d_lo,
+                            double d_hi, uint64_t seed, uint64_t chain0, uint64_t iter, double* Dg, double* sums, double* trace,
+                            int64_t n_trace, int64_t trace_row, double* D, double* sqrtD, double* Minv, double* scratch,
+                            int64_t n, int C, int dtype, int expand_only, pxm_stream_t stream);
 /* One SAPG iteration (Vidal, De Bortoli, Pereyra & Durmus 2020): a MYULA step of every chain on the
  * posterior whose prior is scaled by the chain's theta, then the move of theta towards the marginal maximum-likelihood
  * value of the regularisation strength.  Every state array [C][n]; theta, eta [C] float64 on the device, updated in place.

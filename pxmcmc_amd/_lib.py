@@ -182,10 +182,15 @@ SIGNATURES = {
     ),
     "pxm_pd_primal_step": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_pd_dual_step": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
-    "pxm_cg_apply": (c_int, [c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
-    "pxm_cg_update": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_cg_apply": (c_int, [c_vp, c_vp, c_vp, c_vp, c_dbl, c_i64, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_cg_update": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i64, c_vp, c_i64, c_int, c_int, c_vp]),
     "pxm_gauss_prox": (c_int, [c_vp, c_vp, c_dbl, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
-    "pxm_cg_rhs": (c_int, [c_vp, c_vp, c_dbl, c_vp, c_vp, c_dbl, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_cg_rhs": (c_int, [c_vp, c_vp, c_dbl, c_vp, c_vp, c_dbl, c_i64, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
+    "pxm_group_variance_draw": (
+        c_int,
+        [c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_dbl, c_dbl, c_dbl, c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_i64,
+         c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp],
+    ),
     "pxm_tv_grad": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "pxm_tv_grad_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "pxm_tv_value": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
@@ -255,6 +260,7 @@ CONSTANTS = dict(
     CG_COEF=8,  # doubles per chain of the coefficient array of pxm_cg_apply / pxm_cg_update
     CG_FROZEN=1,  # bits of a chain's flags entry there
     CG_BREAKDOWN=2,
+    GIBBS_SLICE=1024,  # elements per workgroup of pxm_group_variance_draw: the slice length of its table
     SAPG_SLICES_MAX=256,  # partial sums per chain of pxm_sapg_step (per chain and group of pxm_sapg_step_groups)
     SAPG_GROUPS_MAX=32,  # most groups of pxm_sapg_step_groups
     LCI_POINTS=32,  # values of xi per slot and pass of pxm_lci_eval

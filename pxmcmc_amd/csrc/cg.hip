@@ -1,5 +1,5 @@
 // The Gaussian posterior: preconditioned conjugate gradients on H x = b, H = D + A, per chain of a batch.  D = (T / lmda) p is
-// the prior precision (a vector shared by the chains, or a scalar) and A the linear part of x -> calc_gradg(forward(x)), which
+// the prior precision (a vector shared by the chains, one row per chain, or a scalar) and A the linear part of x -> calc_gradg(forward(x)), which
 // the operators apply between the two launches below.  The iteration is the single-reduction PCG of Chronopoulos & Gear (J.
 // Comput. Appl. Math. 25, 1989): all three inner products of an iteration are taken in one pass, so one iteration is one
 // operator pair and two launches,
@@ -44,7 +44,7 @@ static_assert(CG_ITERS + 1 == PXM_CG_COEF, "coef row");
 template <bool CPLX>
 __global__ __launch_bounds__(256) void k_cg_apply(const double* __restrict__ U, const double* __restrict__ Q,
                                                   const double* __restrict__ B0, const double* __restrict__ D, double Ds,
-                                                  const double* __restrict__ R, double* __restrict__ W,
+                                                  int64_t Dst, const double* __restrict__ R, double* __restrict__ W,
                                                   const double* __restrict__ coef, double* __restrict__ part, int64_t n) {
 #pragma clang fp contract(off)  // sums and products as written; the fma calls stay
   const int c = blockIdx.y;
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void k_cg_apply(const double* __restrict__ U, 
   const int64_t base = (int64_t)c * n;
   double gam = 0.0, del = 0.0, rho = 0.0;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const double d = D ? D[i] : Ds;
+    const double d = D ? D[c * Dst + i] : Ds;
     if constexpr (CPLX) {
       const double2 u = reinterpret_cast<const double2*>(U)[base + i];
       const double2 q = reinterpret_cast<const double2*>(Q)[base + i];
@@ -119,7 +119,7 @@ template <bool CPLX>
 __global__ __launch_bounds__(256) void k_cg_update(double* __restrict__ U, const double* __restrict__ W, double* __restrict__ P,
                                                    double* __restrict__ S, const double* __restrict__ X0,
                                                    double* __restrict__ X1, double* __restrict__ R,
-                                                   const double* __restrict__ Minv, double Ms,
+                                                   const double* __restrict__ Minv, double Ms, int64_t Mst,
                                                    const double* __restrict__ coef, int64_t n) {
 #pragma clang fp contract(off)
   const int c = blockIdx.y;
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void k_cg_update(double* __restrict__ U, const
         reinterpret_cast<double2*>(X1)[base + i] = reinterpret_cast<const double2*>(X0)[base + i];
         continue;
       }
-      const double m = Minv ? Minv[i] : Ms;
+      const double m = Minv ? Minv[c * Mst + i] : Ms;
       const double2 u = reinterpret_cast<double2*>(U)[base + i];
       const double2 w = reinterpret_cast<const double2*>(W)[base + i];
       double2 p = reinterpret_cast<double2*>(P)[base + i];
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void k_cg_update(double* __restrict__ U, const
         X1[base + i] = X0[base + i];
         continue;
       }
-      const double m = Minv ? Minv[i] : Ms;
+      const double m = Minv ? Minv[c * Mst + i] : Ms;
       const double p = fma(beta, P[base + i], U[base + i]);
       const double s = fma(beta, S[base + i], W[base + i]);
       const double r = fma(-alpha, s, R[base + i]);
@@ -184,15 +184,16 @@ __global__ __launch_bounds__(256) void k_gauss_prox(const double* __restrict__ X
 }
 
 // out = B_i + gs G + (zs S_i) Z per component: acc = B_i (0 without B); with G: acc = fma(gs, G, acc); with Z:
-// acc = fma(zs S_i (rounded), Z, acc).  B [n] is shared by the chains, G and Z are [C][n], S is [n] or the scalar Ss.
+// acc = fma(zs S_i (rounded), Z, acc).  B [n] is shared by the chains, G and Z are [C][n], S is [n], [C][n] (chain stride Sst) or the
+// scalar Ss.
 template <bool CPLX>
 __global__ __launch_bounds__(256) void k_cg_rhs(const double* __restrict__ B, const double* __restrict__ G, double gs,
                                                 const double* __restrict__ Z, const double* __restrict__ S, double Ss,
-                                                double zs, double* __restrict__ out, int64_t n) {
+                                                int64_t Sst, double zs, double* __restrict__ out, int64_t n) {
 #pragma clang fp contract(off)
-  const int64_t base = (int64_t)blockIdx.y * n;
+  const int64_t base = (int64_t)blockIdx.y * n, sbase = (int64_t)blockIdx.y * Sst;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const double f = zs * (S ? S[i] : Ss);
+    const double f = zs * (S ? S[sbase + i] : Ss);
     if constexpr (CPLX) {
       double2 a = B ? reinterpret_cast<const double2*>(B)[i] : double2{0.0, 0.0};
       if (G) {
@@ -219,11 +220,12 @@ using namespace pxm;
 
 extern "C" {
 
-int pxm_cg_apply(const void* U, const void* Q, const void* B0, const double* D, double D_scalar, const void* R, void* W_out,
-                 double* coef, double tol, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream) {
+int pxm_cg_apply(const void* U, const void* Q, const void* B0, const double* D, double D_scalar, int64_t D_stride, const void* R,
+                 void* W_out, double* coef, double tol, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream) {
   PXM_REQUIRE(n >= 0 && C >= 1 && C <= 65535 && (dtype == 0 || dtype == 1), "pxm_cg_apply: bad n / C / dtype");
   PXM_REQUIRE(coef && scratch, "pxm_cg_apply: null buffer");
   PXM_REQUIRE(std::isfinite(tol) && tol >= 0, "pxm_cg_apply: tol must be finite and not negative");
+  PXM_REQUIRE(D_stride == 0 || D_stride == n, "pxm_cg_apply: D_stride is 0 (shared) or n (one row per chain)");
   hipStream_t st = (hipStream_t)stream;
   int slices = 0;
   if (n > 0) {
@@ -233,8 +235,8 @@ int pxm_cg_apply(const void* U, const void* Q, const void* B0, const double* D, 
     slices = cg_slices(n);
     const dim3 g((unsigned)slices, (unsigned)C);
     const double *u = (const double*)U, *q = (const double*)Q, *b = (const double*)B0, *r = (const double*)R;
-    if (dtype) hipLaunchKernelGGL(k_cg_apply<true>, g, dim3(256), 0, st, u, q, b, D, D_scalar, r, (double*)W_out, coef, scratch, n);
-    else hipLaunchKernelGGL(k_cg_apply<false>, g, dim3(256), 0, st, u, q, b, D, D_scalar, r, (double*)W_out, coef, scratch, n);
+    if (dtype) hipLaunchKernelGGL(k_cg_apply<true>, g, dim3(256), 0, st, u, q, b, D, D_scalar, D_stride, r, (double*)W_out, coef, scratch, n);
+    else hipLaunchKernelGGL(k_cg_apply<false>, g, dim3(256), 0, st, u, q, b, D, D_scalar, D_stride, r, (double*)W_out, coef, scratch, n);
   }
   hipLaunchKernelGGL(k_cg_finish, dim3(C), dim3(64), 0, st, scratch, slices, tol * tol, coef);
   PXM_HIP(hipGetLastError());
@@ -242,9 +244,10 @@ int pxm_cg_apply(const void* U, const void* Q, const void* B0, const double* D, 
 }
 
 int pxm_cg_update(void* U, const void* W, void* P, void* S, const void* X_src, void* X_dst, void* R, const double* Minv,
-                  double Minv_scalar, const double* coef, int64_t n, int C, int dtype, pxm_stream_t stream) {
+                  double Minv_scalar, int64_t Minv_stride, const double* coef, int64_t n, int C, int dtype, pxm_stream_t stream) {
   PXM_REQUIRE(n >= 0 && C >= 1 && C <= 65535 && (dtype == 0 || dtype == 1), "pxm_cg_update: bad n / C / dtype");
   PXM_REQUIRE(coef, "pxm_cg_update: null buffer");
+  PXM_REQUIRE(Minv_stride == 0 || Minv_stride == n, "pxm_cg_update: Minv_stride is 0 (shared) or n (one row per chain)");
   if (n == 0) return 0;
   PXM_REQUIRE(U && W && P && S && X_src && X_dst && R, "pxm_cg_update: null buffer");
   const void* arrays[] = {U, W, P, S, X_src, X_dst, R, (const void*)Minv};
@@ -255,8 +258,8 @@ int pxm_cg_update(void* U, const void* W, void* P, void* S, const void* X_src, v
   hipStream_t st = (hipStream_t)stream;
   double *u = (double*)U, *p = (double*)P, *s = (double*)S, *x1 = (double*)X_dst, *r = (double*)R;
   const double *w = (const double*)W, *x0 = (const double*)X_src;
-  if (dtype) hipLaunchKernelGGL(k_cg_update<true>, g, dim3(256), 0, st, u, w, p, s, x0, x1, r, Minv, Minv_scalar, coef, n);
-  else hipLaunchKernelGGL(k_cg_update<false>, g, dim3(256), 0, st, u, w, p, s, x0, x1, r, Minv, Minv_scalar, coef, n);
+  if (dtype) hipLaunchKernelGGL(k_cg_update<true>, g, dim3(256), 0, st, u, w, p, s, x0, x1, r, Minv, Minv_scalar, Minv_stride, coef, n);
+  else hipLaunchKernelGGL(k_cg_update<false>, g, dim3(256), 0, st, u, w, p, s, x0, x1, r, Minv, Minv_scalar, Minv_stride, coef, n);
   PXM_HIP(hipGetLastError());
   return 0;
 }
@@ -278,17 +281,18 @@ int pxm_gauss_prox(const void* X, const double* precision, double precision_scal
   return 0;
 }
 
-int pxm_cg_rhs(const void* B, const void* G, double g_scale, const void* Z, const double* S, double S_scalar, double z_scale,
-               void* out, int64_t n, int C, int dtype, pxm_stream_t stream) {
+int pxm_cg_rhs(const void* B, const void* G, double g_scale, const void* Z, const double* S, double S_scalar, int64_t S_stride,
+               double z_scale, void* out, int64_t n, int C, int dtype, pxm_stream_t stream) {
   PXM_REQUIRE(n >= 0 && C >= 1 && C <= 65535 && (dtype == 0 || dtype == 1), "pxm_cg_rhs: bad n / C / dtype");
+  PXM_REQUIRE(S_stride == 0 || S_stride == n, "pxm_cg_rhs: S_stride is 0 (shared) or n (one row per chain)");
   if (n == 0) return 0;
   PXM_REQUIRE(out, "pxm_cg_rhs: null buffer");
   PXM_REQUIRE(out != B && out != G && out != Z && out != (const void*)S, "pxm_cg_rhs: out must not alias an input");
   const dim3 g((unsigned)cg_slices(n), (unsigned)C);
   hipStream_t st = (hipStream_t)stream;
   const double *b = (const double*)B, *gg = (const double*)G, *z = (const double*)Z;
-  if (dtype) hipLaunchKernelGGL(k_cg_rhs<true>, g, dim3(256), 0, st, b, gg, g_scale, z, S, S_scalar, z_scale, (double*)out, n);
-  else hipLaunchKernelGGL(k_cg_rhs<false>, g, dim3(256), 0, st, b, gg, g_scale, z, S, S_scalar, z_scale, (double*)out, n);
+  if (dtype) hipLaunchKernelGGL(k_cg_rhs<true>, g, dim3(256), 0, st, b, gg, g_scale, z, S, S_scalar, S_stride, z_scale, (double*)out, n);
+  else hipLaunchKernelGGL(k_cg_rhs<false>, g, dim3(256), 0, st, b, gg, g_scale, z, S, S_scalar, S_stride, z_scale, (double*)out, n);
   PXM_HIP(hipGetLastError());
   return 0;
 }

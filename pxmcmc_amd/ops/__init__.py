@@ -8,14 +8,15 @@ SURVEY.md section 8b).
 
 One module per concern, as the kernel files are: ``steps`` (elementwise.hip, skrock.hip, fista.hip, primal_dual.hip, sapg.hip), ``reduce``
 (reduce.hip), ``pxmala`` (pxmala.hip), ``summary`` (moments.hip, tails.hip, acov.hip), ``lci`` (lci.hip), ``inpaint`` (inpaint.hip),
-``tv`` (tv.hip), ``cg`` (cg.hip), ``sparse`` (spmv.hip), ``plans`` (the plan sources), ``host`` (tables.cpp, host_api.cpp); ``_args`` holds what they do to their arguments
+``tv`` (tv.hip), ``cg`` (cg.hip), ``gibbs`` (gibbs.hip), ``sparse`` (spmv.hip), ``plans`` (the plan sources), ``host`` (tables.cpp, host_api.cpp); ``_args`` holds what they do to their arguments
 and the checks they share.  Callers use the names below as ``ops.<name>``.
 """
 # flake8: noqa: F401  (every import below is a re-export)
-from .._lib import (CG_BREAKDOWN, CG_COEF, CG_FROZEN, FISTA_SLICES_MAX, LCI_EMPTY, LCI_NONFINITE, LCI_POINTS, LCI_UNCONSTRAINED, SAPG_GROUPS_MAX, SAPG_SLICES_MAX,
+from .._lib import (CG_BREAKDOWN, CG_COEF, CG_FROZEN, FISTA_SLICES_MAX, GIBBS_SLICE, LCI_EMPTY, LCI_NONFINITE, LCI_POINTS, LCI_UNCONSTRAINED, SAPG_GROUPS_MAX, SAPG_SLICES_MAX,
                     PxmError, check, require_gpu)
 from ._args import GEMM_KINDS, _batched, _p, _stream, as_device, device
 from .cg import cg_apply, cg_coef, cg_rhs, cg_scratch, cg_update, gauss_prox
+from .gibbs import GibbsGroups, group_variance_draw
 from .host import (DFT_STEP_FIELDS, DFT_UNITS, GEMM_TASK_FIELDS, dft_geometry, dft_step_is_stock, gemm_plan_geometry, gemm_report, hpx_geometry, hpx_lambda, hpx_rings, j_max, mw_ring_weights, noise_bits, rec_geometry, tiling_axisym,
                    wav_bandlimits)
 from .inpaint import inpaint_scratch, inpaint_step

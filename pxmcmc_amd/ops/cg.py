@@ -40,6 +40,18 @@ def _shared(b, x, msg):
     return t
 
 
+def _diag(v, C_, n, dev, name):
+    """a diagonal of the launches -> (vector or None, scalar, chain stride): a float, an ``[n]`` vector shared by the chains
+    (stride 0), or one row per chain, which the kernels read in place: a contiguous float64 ``[C, n]`` device array (stride n)"""
+    if isinstance(v, torch.Tensor) and v.dim() == 2:
+        rows = tuple(v.shape) == (C_, n) and v.dtype == _REAL and v.is_contiguous() and v.device == dev
+        if rows:
+            return v, 0.0, n
+        if v.shape[0] != 1:
+            raise ValueError(f"{name}: a per-chain diagonal must be a contiguous float64 [C, n] device array")
+    return (*_vecT(v, n, dev), 0)  # (any other [1, n] array is the shared vector, as before)
+
+
 def _state_inplace(t, x, msg):
     """an array the launch updates in place: the caller's contiguous device array of the state's shape and dtype"""
     if not isinstance(t, torch.Tensor):
@@ -55,18 +67,19 @@ def cg_apply(U, Q, B0, D, R, coef, tol, out=None, scratch=None):
     ``gamma = sum Re conj(r) u``, ``delta = sum Re conj(u) w``, ``rho = sum |r|^2``, from which the device sets the chain's
     ``alpha`` and ``beta`` in ``coef``, freezes it when ``rho <= tol^2 ||b||^2`` and flags a breakdown.
 
-    ``B0``: ``[n]`` shared by the chains, or None; ``D``: float or ``[n]``; ``coef``: :func:`cg_coef`, updated in place.
+    ``B0``: ``[n]`` shared by the chains, or None; ``D``: float, ``[n]``, or one row per chain (a contiguous float64 ``[C, n]``
+    device array, read in place); ``coef``: :func:`cg_coef`, updated in place.
     ``out``: the buffer of ``W`` (must not alias an input).  Returns ``(W, coef)``.  ``scratch``: :func:`cg_scratch`."""
     name = "cg_apply"
     u, squeeze = _batched(as_device(U))
     q, r = (_companion(t, u, f"{name}: Q and R must have the shape of U") for t in (Q, R))
     b0 = _shared(B0, u, f"{name}: B0 must have one entry per element of a chain")
-    Dv, Ds = _vecT(D, u.shape[1], u.device)
     C_ = u.shape[0]
+    Dv, Ds, Dst = _diag(D, C_, u.shape[1], u.device, name)
     coef = _coef(coef, C_, u.device, name)
     w = torch.empty_like(u) if out is None else _state_out(out, u)
     scratch = _scratch(scratch, 3 * FISTA_SLICES_MAX * C_, u.device, f"{name}: scratch is too small", any_layout=True)
-    check(lib.pxm_cg_apply(_p(u), _p(q), _p(b0), _p(Dv), Ds, _p(r), _p(w), _p(coef), float(tol), _p(scratch), u.shape[1], C_,
+    check(lib.pxm_cg_apply(_p(u), _p(q), _p(b0), _p(Dv), Ds, Dst, _p(r), _p(w), _p(coef), float(tol), _p(scratch), u.shape[1], C_,
                            _dt(u), _stream()))
     return (w[0] if squeeze else w), coef
 
@@ -75,16 +88,16 @@ def cg_update(U, W, P, S, X, R, Minv, coef, out=None):
     """The second launch of a CG iteration: ``p = u + beta p``, ``s = w + beta s``, ``x1 = x + alpha p``, ``r -= alpha s``,
     ``u = Minv r`` with the chain's ``alpha``, ``beta`` of ``coef``.  ``U``, ``P``, ``S`` and ``R`` are device arrays updated
     in place; ``out``: the buffer of ``x1``.  A frozen chain is copied ``X -> x1`` and otherwise left as it is.  ``Minv``:
-    float or ``[n]``.  Returns ``x1``."""
+    float, ``[n]`` or ``[C, n]`` (as ``D`` of :func:`cg_apply`).  Returns ``x1``."""
     name = "cg_update"
     x, squeeze = _batched(as_device(X))
     w = _companion(W, x, f"{name}: W must have the state's shape")
     u, p, s, r = (_state_inplace(t, x, f"{name}: U, P, S and R must be contiguous device arrays of the state's shape and dtype")
                   for t in (U, P, S, R))
-    Mv, Ms = _vecT(Minv, x.shape[1], x.device)
+    Mv, Ms, Mst = _diag(Minv, x.shape[0], x.shape[1], x.device, name)
     coef = _coef(coef, x.shape[0], x.device, name)
     x1 = torch.empty_like(x) if out is None else _state_out(out, x)
-    check(lib.pxm_cg_update(_p(u), _p(w), _p(p), _p(s), _p(x), _p(x1), _p(r), _p(Mv), Ms, _p(coef), x.shape[1], x.shape[0], _dt(x),
+    check(lib.pxm_cg_update(_p(u), _p(w), _p(p), _p(s), _p(x), _p(x1), _p(r), _p(Mv), Ms, Mst, _p(coef), x.shape[1], x.shape[0], _dt(x),
                             _stream()))
     return x1[0] if squeeze else x1
 
@@ -100,14 +113,14 @@ def gauss_prox(X, precision, T, out=None):
 
 def cg_rhs(like, B=None, G=None, g_scale=1.0, Z=None, S=1.0, z_scale=1.0, out=None):
     """``B + g_scale G + z_scale (S o Z)`` in one launch, shaped and typed like the ``[C, n]`` device array ``like``: ``B``
-    ``[n]`` is shared by the chains, ``G`` and ``Z`` are ``[C, n]``, ``S`` is a float or ``[n]``; a term that is None is left
-    out.  The right-hand sides of the Gaussian posterior's draws, ``H x`` for a start point, ``M^-1 r``."""
+    ``[n]`` is shared by the chains, ``G`` and ``Z`` are ``[C, n]``, ``S`` is a float, ``[n]`` or one row per chain ``[C, n]``; a
+    term that is None is left out.  The right-hand sides of the Gaussian posterior's draws, ``H x`` for a start point, ``M^-1 r``."""
     x, squeeze = _batched(like)
     b = _shared(B, x, "cg_rhs: B must have one entry per element of a chain")
     g, z = (t if t is None else _companion(t, x, "cg_rhs: G and Z must have the shape of the result") for t in (G, Z))
-    Sv, Ss = _vecT(S, x.shape[1], x.device)
+    Sv, Ss, Sst = _diag(S, x.shape[0], x.shape[1], x.device, "cg_rhs")
     o = _result(out if out is None or out.dim() == 2 else out.unsqueeze(0), tuple(x.shape), x.dtype, x.device,
                 "cg_rhs: out must be a contiguous device array of the result's shape and dtype", on_device=True)
-    check(lib.pxm_cg_rhs(_p(b), _p(g), float(g_scale), _p(z), _p(Sv), Ss, float(z_scale), _p(o), x.shape[1], x.shape[0], _dt(x),
+    check(lib.pxm_cg_rhs(_p(b), _p(g), float(g_scale), _p(z), _p(Sv), Ss, Sst, float(z_scale), _p(o), x.shape[1], x.shape[0], _dt(x),
                          _stream()))
     return o[0] if squeeze else o

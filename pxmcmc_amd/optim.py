@@ -534,6 +534,184 @@ class GaussianPosterior(Stepper):
         return out.clone() if as_torch else out.cpu().numpy()
 
 
+# ---- Gaussian prior with unknown variances: the Gibbs sampler on the batched solver --------------------
+class GaussianGibbs(GaussianPosterior):
+    """
+    The joint posterior of the field and of the prior variances: the Gibbs sampler of Wandelt, Larson & Lakshminarayanan
+    (2004) and Jewell, Levin & Anderson (2004) on the solver of :class:`GaussianPosterior`.  The state is cut into K contiguous
+    groups with one precision ``D_k`` each, constant inside the group,
+
+        F(X) = 1/2 Re L2(X) + 1/2 sum_k D_k sum_{i in k} |X_i|^2,   p(v_k) ~ v_k^-q  on the variance  v_k = 1 / D_k,
+
+    and a sweep alternates the exact draw ``x | v, d`` (perturbation-optimisation, one batched CG solve) with the conditional
+    ``D_k | x = chi2_nu / sum_{i in k} |x_i|^2``, ``nu_k = dof n_k + 2 q - 2`` (``dof = 2`` for a complex state, 1 for a real
+    one), drawn on the device from the Philox stream (``pxm_group_variance_draw``).  Every chain carries its own variances:
+    the launches of the solver read per-chain diagonals ``[C, N]``, which the draw rewrites in place.  ``gibbs_np`` states
+    the sampler in numpy.
+
+    Takes the arguments of :class:`GaussianPosterior` (``precond`` must be ``"diag"``) and
+
+    :param groups: ``"degree"``: one group per degree l of a :class:`SphericalHarmonicTransform` state (offsets ``l^2``),
+        which samples the power spectrum ``C_l``; ``"scale"``: one per wavelet scale (``utils.wavelet_scale_bounds`` of the
+        operator's transform), a Gaussian scale model; or K + 1 offsets increasing strictly from 0 to ``nparams``
+    :param hyper_q: ``q`` of the hyper-prior: 0 flat, 1 Jeffreys; real with ``2 q`` an integer, at most 2
+    :param fixed: indices of groups that keep their initial precision; a group with ``nu_k < 1`` cannot be sampled and must
+        be listed (the monopole of degree groups at ``q = 0``)
+    :param lmin: with degree groups: fixes the degrees below ``lmin`` (added to ``fixed``)
+    :param precision_bounds: ``(d_lo, d_hi)``, finite and positive: the clamp of ``D_k`` (a group whose field is exactly zero
+        gets ``d_hi``)
+
+    The initial precisions are the prior's, which must be constant inside every group.  Sweep ``t`` of chain ``c`` uses the
+    float64 Philox stream at ``(seed, chain_offset + c)``: iterations ``2 t`` and ``2 t + 1`` for the field draw, iteration
+    ``2^61 + t`` for the variances, so ranks that share ``seed`` and number their chains through ``chain_offset`` run
+    independent chains, whose summaries merge with ``PosteriorSummary.merge``.
+
+    :meth:`run` here is the sampler, ``run(nsweeps, nburn, ...)``: it replaces the MAP solve ``run(start_point)`` of
+    :class:`GaussianPosterior`, which a ``GaussianGibbs`` does not offer (``X_map`` and ``objective_map`` are not set; build a
+    ``GaussianPosterior`` with ``prior.Gaussian(precision, T)`` of a sample or of the posterior mean for the Wiener map at
+    fixed variances).  :meth:`sample` draws the field at the precisions as the last run left them.
+
+    After :meth:`run`: ``precision_chain`` and ``variance_chain`` (numpy ``[nsweeps - nburn, C, K]``, in the units of
+    ``prior.Gaussian``: ``Gaussian(precision_chain[t, c] repeated over the groups, T)`` is that sample's prior), ``cl_chain``
+    (the variances, with degree groups), ``hyper_summary`` (a ``PosteriorSummary(C, K)`` over ``log v``: R-hat, ESS and
+    quantiles of the spectrum), ``solve_iterations`` and ``solve_converged`` (``[nsweeps, C]``).  The columns of
+    ``hyper_summary`` that belong to fixed groups carry no information: their ``log v`` never moves (R-hat and ESS are
+    undefined there), and a fixed group whose precision is 0 has ``log v = inf``, which leaves NaN in its column.
+    """
+
+    _VAR_ITER = 1 << 61  # Philox iterations of the variance draws: off the field draws (2 t, 2 t + 1) and off _PROBE_ITER
+
+    def __init__(self, forward, prior, mcmcparams=PxMCMCParams(), nchains=1, groups="degree", hyper_q=0.0, fixed=(), lmin=None,
+                 precision_bounds=(1e-30, 1e30), tol=1e-8, max_iter=1000, check_every=10, precond="diag", use_graph=True, seed=0,
+                 chain_offset=0):
+        from . import gibbs_np
+
+        if not (isinstance(precond, str) and precond == "diag"):
+            raise ValueError('GaussianGibbs: precond must be "diag" (M = D + trace(A) / N follows the sampled D)')
+        super().__init__(forward, prior, mcmcparams, nchains=nchains, tol=tol, max_iter=max_iter, check_every=check_every,
+                         precond=precond, use_graph=use_graph, seed=seed, chain_offset=chain_offset)
+        n, C = self._n, self.nchains
+        self.group_kind = groups if isinstance(groups, str) else "offsets"
+        bounds = self._group_offsets(forward, groups)
+        fixed = list(fixed)
+        if lmin is not None:
+            if self.group_kind != "degree":
+                raise ValueError('GaussianGibbs: lmin goes with groups="degree"')
+            fixed += list(range(min(int(lmin), len(bounds) - 1)))
+        self._scale = float(prior.T) / float(self.lmda)
+        setup = gibbs_np.check_setup(n, 2 if self._dt.is_complex else 1, bounds, hyper_q, fixed,
+                                     np.asarray(prior.precision, dtype=float) * self._scale, precision_bounds)
+        self.group_bounds, self.sampled, self.nu = setup["bounds"], setup["sampled"], setup["nu"]
+        self.hyper_q, self.precision_bounds = float(hyper_q), (float(precision_bounds[0]), float(precision_bounds[1]))
+        self.K = self.group_bounds.size - 1
+        self._groups = ops.GibbsGroups(self.group_bounds, n, np.nonzero(~self.sampled)[0])
+        dev = ops.device()
+        self._Dg0 = ops.as_device(np.tile(setup["D_groups"], (C, 1)), torch.float64)
+        self._Dg = self._Dg0.clone()
+        # the per-chain diagonals the launches of the solver read in place: the variance draw rewrites them, at these addresses
+        self._D, self._sqrtD, self._minv = (torch.empty((C, n), dtype=torch.float64, device=dev) for _ in range(3))
+        self._gibbs_scratch = self._groups.scratch(C)
+        self._expand()
+
+    @staticmethod
+    def _group_offsets(forward, groups):
+        """the ``groups`` argument -> K + 1 offsets (checked by ``gibbs_np.check_setup``)"""
+        if not isinstance(groups, str):
+            return groups
+        from .transforms import SphericalHarmonicTransform, SphericalWaveletTransform
+        from .utils import wavelet_scale_bounds
+
+        t = getattr(forward, "transform", None)
+        if groups == "degree" and isinstance(t, SphericalHarmonicTransform):
+            return np.arange(int(t.L) + 1, dtype=np.int64) ** 2
+        if groups == "scale" and isinstance(t, SphericalWaveletTransform):
+            return wavelet_scale_bounds(t.L, t.B, t.J_min, t.dirs, t.spin, t.harmonic)
+        raise ValueError('GaussianGibbs: groups="degree" needs a forward operator whose transform is a SphericalHarmonicTransform, '
+                         'groups="scale" one whose transform is a SphericalWaveletTransform (other groups: a sequence of '
+                         "offsets from 0 to nparams)")
+
+    def _variance_draw(self, X, it, trace=None, row=0, expand_only=False):
+        ops.group_variance_draw(X, self._groups, self._Dg, self._D, self._sqrtD, self._minv, q=self.hyper_q,
+                                h=float(self.trace_estimate), d_lo=self.precision_bounds[0], d_hi=self.precision_bounds[1],
+                                seed=self.seed, chain0=self.chain_offset, it=it, trace=trace, trace_row=row,
+                                scratch=self._gibbs_scratch, expand_only=expand_only)
+
+    def _expand(self):
+        """``D``, ``sqrt(D)`` and ``M^-1`` of every element from the group precisions as they stand"""
+        self._variance_draw(None, 0, expand_only=True)
+
+    def _draw_operands(self):
+        s, _ = super()._draw_operands()
+        return s, self._sqrtD
+
+    def run(self, nsweeps, nburn=0, summary=None, summary_ess=None, summary_alpha=None, as_torch=False):
+        """``nsweeps`` sweeps of every chain from the prior's precisions; the first ``nburn`` are dropped.  Returns the field
+        draws ``[nsweeps - nburn, C, N]`` (numpy, or a device tensor with ``as_torch``); with ``summary="state"`` or ``"image"``
+        they are folded into a :class:`pxmcmc_amd.uncertainty.PosteriorSummary` instead, which is returned, as
+        :meth:`GaussianPosterior.sample` does.  The variances of the kept sweeps fold into ``hyper_summary`` either way.  Two
+        runs with the same ``seed`` and ``chain_offset`` return the same bits."""
+        from .uncertainty import PosteriorSummary
+
+        if summary not in (None, "state", "image"):
+            raise ValueError("summary must be None, 'state' or 'image'")
+        nsweeps, nburn = int(nsweeps), int(nburn)
+        if nsweeps < 1 or not 0 <= nburn < nsweeps:
+            raise ValueError("run needs nsweeps >= 1 and 0 <= nburn < nsweeps")
+        tr = getattr(self.forward, "transform", None)
+        if summary == "image" and (getattr(self.forward, "setting", "synthesis") == "analysis" or not hasattr(tr, "inverse")):
+            raise ValueError("summary='image' needs forward.transform.inverse in the synthesis setting")
+        C, n, K, keep = self.nchains, self._n, self.K, nsweeps - nburn
+        dev = ops.device()
+        self._Dg.copy_(self._Dg0)
+        self._expand()
+        self._draw_ops = self._draw_operands()
+        trace = torch.zeros((nsweeps, C, K), dtype=torch.float64, device=dev)
+        post = None
+        hyper = PosteriorSummary(C, K, False, best=False, alpha=summary_alpha, nsamples=keep, ess_lags=summary_ess)
+        out = None if summary else torch.empty((keep, C, n), dtype=self._dt, device=dev)
+        start = torch.zeros((C, n), dtype=self._dt, device=dev)
+        self._engine_start(start)
+        its, ok = [], []
+        try:
+            for t in range(nsweeps):
+                # one engine, and so one capture, per solve: the first iterations of a system loaded into an engine whose graph
+                # had replayed before came out wrong on the MI355X (DESIGN.md section 23)
+                if t:
+                    self._engine_start(start)
+                self._load(self.draw_rhs(t))
+                X, coef, rows, checks = self._iterate()
+                self._record(coef, rows, checks)
+                its.append(self.niter.copy())
+                ok.append(self.converged.copy())
+                if self.breakdown.any() or not self.converged.all():
+                    warnings.warn(f"GaussianGibbs.run: the solve of sweep {t} did not converge for every chain (breakdown: "
+                                  f"{self.breakdown.tolist()}, relative residuals {rows[-1].tolist()})")
+                self._variance_draw(X, self._VAR_ITER + t, trace=trace, row=t)
+                if t < nburn:
+                    continue
+                hyper.update(-torch.log(trace[t] / self._scale))  # log v, v = 1 / precision in the prior's units
+                if summary is None:
+                    out[t - nburn].copy_(X)
+                    continue
+                S = X if summary == "state" else ops.as_device(tr.inverse(X))
+                if post is None:
+                    post = PosteriorSummary(C, S.shape[1], S.is_complex(), best=False, alpha=summary_alpha, nsamples=keep,
+                                            ess_lags=summary_ess)
+                post.update(S)
+        finally:
+            self._engine_stop()
+        self.solve_iterations, self.solve_converged = np.stack(its), np.stack(ok)
+        self.precision_chain = trace[nburn:].cpu().numpy() / self._scale
+        with np.errstate(divide="ignore"):
+            self.variance_chain = 1.0 / self.precision_chain
+        if self.group_kind == "degree":
+            self.cl_chain = self.variance_chain
+        self.hyper_summary = hyper
+        if summary:
+            return post
+        return out.clone() if as_torch else out.cpu().numpy()
+
+
 # ---- analysis setting: primal-dual splitting and the exact prox (DESIGN.md section 14d) ---------------------------------------
 def operator_norm2(fwd, adj, n, dtype=torch.complex128, iters=1000, tol=1e-4, seed=0):
     """``||A||^2`` of the analysis operator ``A = adj`` (state of length ``n`` -> coefficients) with ``A^H = fwd``: the power
