@@ -34,7 +34,7 @@ from pxmcmc_amd import ops  # noqa: E402
 from pxmcmc_amd.forward import ForwardOperator, SphericalWaveletTransformOperator  # noqa: E402
 from pxmcmc_amd.measurements import Identity  # noqa: E402
 from pxmcmc_amd.mcmc import MYULA, SKROCK, PxMALA, PxMCMCParams  # noqa: E402
-from pxmcmc_amd.optim import FISTA, PrimalDual  # noqa: E402
+from pxmcmc_amd.optim import FISTA, LassoGibbs, PrimalDual  # noqa: E402
 from pxmcmc_amd.prior import L1, S2_Wavelets_L1, TV_S2  # noqa: E402
 from pxmcmc_amd.sapg import SAPG  # noqa: E402
 from pxmcmc_amd.saving import save_mcmc  # noqa: E402
@@ -193,6 +193,39 @@ def print_theta_per_scale(sapg, transform):
         print(f"  {name:>8}: bandlimit {int(bl):4d}, {int(size):8d} coefficients, theta_hat = {th:.6g}")
 
 
+def lasso_gibbs(forwardop, regulariser, params, args, L_g, truth):
+    """--lasso-gibbs NSWEEPS: exact draws of the L1 posterior itself by the Gibbs sampler on the batched CG solver (no step size,
+    no Moreau-Yosida envelope): a quarter of the sweeps are burn-in, the rest fold into a PosteriorSummary of the images"""
+    nsweeps = args.lasso_gibbs
+    nburn = nsweeps // 4
+    las = LassoGibbs(forwardop, regulariser, params, nchains=args.chains, tol=1e-6, max_iter=2000)
+    start_point = None
+    if args.map_start:
+        start_point = map_start(forwardop, regulariser, params, L_g, np.zeros(forwardop.nparams, dtype=complex),
+                                restart="gradient" if args.map_restart else None)
+    start = datetime.now()
+    summ = las.run(nsweeps, nburn=nburn, start_point=start_point, summary="image", summary_ess=args.summary_ess,
+                   summary_alpha=args.summary_alpha)
+    elapsed = datetime.now() - start
+    base = os.path.join(args.outdir, f"lassogibbs_{args.setting}_{args.jobid}")
+    mean, std = summ.pooled_mean().cpu().numpy().real, np.sqrt(summ.pooled_variance().cpu().numpy())
+    np.save(base + "_mean.npy", mean)
+    np.save(base + "_std.npy", std)
+    its = las.solve_iterations.max(axis=1)
+    print(f"LassoGibbs: {nsweeps} sweeps ({nburn} burn-in) x {args.chains} chain(s) in {elapsed}; CG iterations per sweep: median "
+          f"{int(np.median(its))}, range {int(its.min())}-{int(its.max())} (all converged: {bool(las.solve_converged.all())}); "
+          f"clamped precisions per sweep and chain: {las.clamped_chain.mean():.1f}")
+    if args.chains > 1:
+        rmax, nundef = summ.max_rhat()
+        print(f"max R-hat over the image ({args.chains} chains): {rmax:.4f} ({nundef} components undefined)")
+    if args.summary_ess is not None:
+        print(summ.ess_report("image"))
+    rel = np.sqrt(np.mean(np.abs(mean - truth) ** 2)) / np.sqrt(np.mean(np.abs(truth) ** 2))
+    print(f"saved {base}_mean.npy / _std.npy; posterior-mean error {rel:.3f} (noise {args.sigma:.3f}); median posterior std "
+          f"{np.median(std):.3f}; mean prior term {las.prior_term_chain.mean():.6e}")
+    return base, rel, std
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--L", type=int, default=32, help="Angular bandlimit. Default 32.")
@@ -236,6 +269,10 @@ def main(argv=None):
                          "samples with every scale's thresholds and weights scaled by its own theta_hat")
     ap.add_argument("--sapg-warmup", type=int, default=100, help="--estimate-mu: MYULA iterations before theta moves")
     ap.add_argument("--sapg-iters", type=int, default=600, help="--estimate-mu: iterations with a moving theta")
+    ap.add_argument("--lasso-gibbs", type=int, default=None, metavar="NSWEEPS",
+                    help="sample the L1 posterior exactly with the Gibbs sampler on the batched CG solver instead of --algo: NSWEEPS "
+                         "sweeps, a quarter of them burn-in, folded into the image summary (synthesis setting, spin 0, dirs 1; "
+                         "honours --chains, --map-start, --summary-ess and --summary-alpha; --summary is implied)")
     ap.add_argument("--summary", nargs="?", const="image", default=None, choices=("image",),
                     help="accumulate the posterior mean / standard deviation / R-hat on the GPU instead of saving the chain")
     ap.add_argument("--summary-alpha", type=float, default=None,
@@ -247,6 +284,10 @@ def main(argv=None):
     ap.add_argument("--jobid", type=str, default="0")
     args = ap.parse_args(argv)
     args.estimate_mu = args.estimate_mu or args.estimate_mu_per_scale
+    if args.lasso_gibbs is not None:
+        if args.lasso_gibbs < 4 or args.setting != "synthesis" or args.spin != 0 or args.dirs != 1 or args.estimate_mu:
+            ap.error("--lasso-gibbs takes at least 4 sweeps, the synthesis setting, spin 0 and dirs 1, and not --estimate-mu")
+        args.summary = "image"
     if args.summary_alpha is not None and not args.summary:
         ap.error("--summary-alpha needs --summary")
     if args.summary_ess is not None and not args.summary:
@@ -310,6 +351,8 @@ def main(argv=None):
                                  params.lmda * params.mu, L=L, B=B, J_min=J_min, dirs=args.dirs, spin=spin)
     print(f"Number of data points: {len(data)}")
     print(f"Number of model parameters: {forwardop.nparams}")
+    if args.lasso_gibbs is not None:
+        return lasso_gibbs(forwardop, regulariser, params, args, L_g, truth)
     cls = {"myula": MYULA, "pxmala": PxMALA, "skrock": SKROCK}[args.algo]
     start_point = np.zeros(forwardop.nparams)
     if args.estimate_mu:

@@ -651,6 +651,30 @@ int pxm_group_variance_draw(const void* X, const int64_t* bounds, int K, const i
                             double d_hi, uint64_t seed, uint64_t chain0, uint64_t iter, double* Dg, double* sums, double* trace,
                             int64_t n_trace, int64_t trace_row, double* D, double* sqrtD, double* Minv, double* scratch,
                             int64_t n, int C, int dtype, int expand_only, pxm_stream_t stream);
+/* The conditional draw of the prior precisions given the field for the L1 prior (1 / lmda) sum_i T_i |X_i|, the second half of
+ * a Gibbs sweep on the sparse posterior (Park & Casella 2008): the Laplace prior as a Gaussian scale
+ * mixture, under which every precision is an inverse-Gaussian variate given the field.  One pass over X [C][n] (float64 or
+ * complex128); per element i of chain c, with plain products and sums and no contraction:
+ *   t = tscale T_i (T [n] on the device, shared by the chains, or T_scalar; every t must be positive -- only tscale and
+ *     T_scalar can be checked here -- and a t that is not leaves an unspecified value inside the clamp);
+ *   |x| = sqrt(re^2 + im^2) for complex128, fabs for float64;
+ *   z = component 0 of the fp64 complex-stream Philox pair keyed (seed, chain0 + c) at counter (i, iter): the real part of
+ *     element i of pxm_randn(n, dtype 1 | PXM_NOISE_F64) at that iteration, for either dtype;
+ *   u = (a + 1/2) 2^-52, a the first 52 bits of the Philox block at counter (i, iter + 1) (words 1 and 0 as one 64-bit number,
+ *     shifted right by 12): exact, in (0, 1).  The call owns the iterations iter and iter + 1;
+ *   rt = 1 / t;  a = |x| rt;  zt = z rt;  g = 0.5 (zt zt);  D1 = 1 / ((a + g) + sqrt(g (g + 2 a)));
+ *   raw = D1 unless u (1 + a D1) > 1, then 1 / (a (a D1))   (Michael, Schucany & Haas 1976: IG(mean t / |x|, shape t^2));
+ *   D[c][i] = min(max(raw, d_lo), d_hi) (NaN or overflow: d_hi from the first branch), sqrtD[c][i] = sqrt(D[c][i]),
+ *   Minv[c][i] = 1 / (D[c][i] + h_c) (h [C] on the device, or h_scalar): the arrays pxm_cg_apply, pxm_cg_rhs and pxm_cg_update
+ *   read with chain stride n.
+ *   sums [C][2] (or NULL): receives sum_i t |x_i| -- the prior term of the objective at X -- and the number of elements whose
+ *     raw value the clamp changed, as a double; added in a fixed order that depends on n only.
+ *   scratch: caller-owned, 2 * PXM_FISTA_SLICES_MAX * C doubles; NULL without sums.
+ * d_lo, d_hi finite, 0 < d_lo <= d_hi.  One launch, two with sums; no atomics and no host read: a HIP graph replays the call.
+ * The outputs must not overlap an input or each other (only equal base pointers are detected and refused). */
+int pxm_lasso_precision_draw(const void* X, const double* T, double T_scalar, double tscale, const double* h, double h_scalar,
+                             double d_lo, double d_hi, uint64_t seed, uint64_t chain0, uint64_t iter, double* D, double* sqrtD,
+                             double* Minv, double* sums, double* scratch, int64_t n, int C, int dtype, pxm_stream_t stream);
 /* One SAPG iteration (Vidal, De Bortoli, Pereyra & Durmus 2020): a MYULA step of every chain on the
  * posterior whose prior is scaled by the chain's theta, then the move of theta towards the marginal maximum-likelihood
  * value of the regularisation strength.  Every state array [C][n]; theta, eta [C] float64 on the device, updated in place.

@@ -191,6 +191,11 @@ SIGNATURES = {
         [c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_dbl, c_dbl, c_dbl, c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_i64,
          c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp],
     ),
+    "pxm_lasso_precision_draw": (
+        c_int,
+        [c_vp, c_vp, c_dbl, c_dbl, c_vp, c_dbl, c_dbl, c_dbl, c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int,
+         c_vp],
+    ),
     "pxm_tv_grad": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "pxm_tv_grad_adjoint": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "pxm_tv_value": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

@@ -83,9 +83,10 @@ def cg_update_np(u, w, p, s, x, r, minv, row):
     return p, s, x, r, minv * r
 
 
-def pcg_np(A, D, b, x0=None, minv=1.0, tol=1e-8, max_iter=1000):
+def pcg_np(A, D, b, x0=None, minv=1.0, tol=1e-8, max_iter=1000, bnorm2=None):
     """Solve ``(D + A) x = b`` for one chain by the iteration above.  ``A``: a callable ``v -> A v`` (the linear part; the
-    solver's ``q + b0``), or a dense matrix.  Returns ``(x, info)`` with ``niter``, ``frozen``, ``breakdown`` and
+    solver's ``q + b0``), or a dense matrix.  ``bnorm2``: the reference of the stop rule ``rho <= tol^2 bnorm2`` (None:
+    ``||b||^2``).  Returns ``(x, info)`` with ``niter``, ``frozen``, ``breakdown`` and
     ``rel_residual`` (``sqrt(rho) / ||b||`` of the recurrence residual at the last decision)."""
     Av = A if callable(A) else (lambda v: A @ v)
     b = np.asarray(b)
@@ -93,7 +94,7 @@ def pcg_np(A, D, b, x0=None, minv=1.0, tol=1e-8, max_iter=1000):
     r = b - (D * x + Av(x))
     u = minv * r
     p, s = np.zeros_like(b), np.zeros_like(b)
-    row = new_coef(float(np.sum(np.abs(b) ** 2)))
+    row = new_coef(float(np.sum(np.abs(b) ** 2)) if bnorm2 is None else float(bnorm2))
     for _ in range(int(max_iter)):
         w, sums = cg_apply_np(u, Av(u), None, D, r)
         row = cg_decide_np(row, sums, tol)

@@ -34,16 +34,6 @@ constexpr int GIBBS_S = PXM_GIBBS_SLICE;
 constexpr int GIBBS_PER = GIBBS_S / 256;  // elements (and Philox pairs) per lane of a slice
 static_assert(GIBBS_S % 256 == 0 && GIBBS_PER >= 1, "a slice is a whole number of passes of the workgroup");
 
-// the pair pxm_randn writes for the same counter with dtype 1 | PXM_NOISE_F64, from its bits
-__device__ __forceinline__ NormalPair gibbs_pair(const uint4 bits) {
-#ifdef PXM_NOISE_F64_POLY
-  return normal_pair_from_bits_poly(bits);
-#else
-  return normal_pair_from_bits_tabs(bits, reinterpret_cast<const double2*>(&NOISE_LOG_TAB[0][0]),
-                                    reinterpret_cast<const double2*>(&NOISE_SINCOS_TAB[0][0]));
-#endif
-}
-
 // What a workgroup or wave needs to know of its group.  `inside`: the offsets lie in the state; `sampled`: and it is drawn.
 struct GibbsGroup {
   int64_t b0, nk, nu;
@@ -96,14 +86,14 @@ __global__ __launch_bounds__(256) void k_gibbs_slices(const double* __restrict__
       sig += x * x;
     }
     if (2 * jl < g.nu) {
-      const NormalPair z = gibbs_pair(bits[r]);
+      const NormalPair z = normal_pair_from_bits(bits[r]);
       chi += z.z0 * z.z0;
       if (2 * jl + 1 < g.nu) chi += z.z1 * z.z1;
     }
   }
   // the pair past the group's elements: the last slice's, added by its first lane after that lane's own terms
   if (threadIdx.x == 0 && lo + GIBBS_S >= g.nk && 2 * g.nk < g.nu) {
-    const NormalPair z = gibbs_pair(philox_bits(seed, chain, idx0 + (uint64_t)g.nk, iter));
+    const NormalPair z = normal_pair_from_bits(philox_bits(seed, chain, idx0 + (uint64_t)g.nk, iter));
     chi += z.z0 * z.z0;
     if (2 * g.nk + 1 < g.nu) chi += z.z1 * z.z1;
   }

@@ -283,6 +283,22 @@ __device__ inline NormalPair normal_pair_from_bits_poly(const uint4 c) {  // (-D
   const uint64_t b = (((uint64_t)c.w << 32) | c.z) >> 11;
   return box_muller_f64_poly(((double)a + 0.5) * 0x1.0p-53, ((double)b + 0.5) * 0x1.0p-53);
 }
+// the pair pxm_randn writes for the same counter with dtype 1 | PXM_NOISE_F64, from its bits (the global tables)
+__device__ __forceinline__ NormalPair normal_pair_from_bits(const uint4 bits) {
+#ifdef PXM_NOISE_F64_POLY
+  return normal_pair_from_bits_poly(bits);
+#else
+  return normal_pair_from_bits_tabs(bits, reinterpret_cast<const double2*>(&NOISE_LOG_TAB[0][0]),
+                                    reinterpret_cast<const double2*>(&NOISE_SINCOS_TAB[0][0]));
+#endif
+}
+// One uniform in (0, 1) from the first 52 bits of a block: (a + 1/2) 2^-52 = (2 a + 1) 2^-53 with a < 2^52, so the conversion,
+// the sum and the scaling are all exact -- every value is a double, none is 0 or 1, and a host rebuilds it from the bits.
+// (The 53-bit uniforms above round a + 1/2 for a >= 2^52; Box-Muller does not mind, a threshold test would.)
+__device__ __forceinline__ double uniform52_from_bits(const uint4 c) {
+  const uint64_t a = (((uint64_t)c.y << 32) | c.x) >> 12;
+  return ((double)a + 0.5) * 0x1.0p-52;
+}
 // the fp64 form with the caller's copies of the Box-Muller tables (same deviates, bit for bit)
 __device__ inline NormalPair philox_normal_pair_tabs(uint64_t seed, uint64_t chain, uint64_t index, uint64_t iter, const double2* logt,
                                                      const double2* sct) {

@@ -8,7 +8,7 @@ SURVEY.md section 8b).
 
 One module per concern, as the kernel files are: ``steps`` (elementwise.hip, skrock.hip, fista.hip, primal_dual.hip, sapg.hip), ``reduce``
 (reduce.hip), ``pxmala`` (pxmala.hip), ``summary`` (moments.hip, tails.hip, acov.hip), ``lci`` (lci.hip), ``inpaint`` (inpaint.hip),
-``tv`` (tv.hip), ``cg`` (cg.hip), ``gibbs`` (gibbs.hip), ``sparse`` (spmv.hip), ``plans`` (the plan sources), ``host`` (tables.cpp, host_api.cpp); ``_args`` holds what they do to their arguments
+``tv`` (tv.hip), ``cg`` (cg.hip), ``gibbs`` (gibbs.hip), ``lasso`` (lasso.hip), ``sparse`` (spmv.hip), ``plans`` (the plan sources), ``host`` (tables.cpp, host_api.cpp); ``_args`` holds what they do to their arguments
 and the checks they share.  Callers use the names below as ``ops.<name>``.
 """
 # flake8: noqa: F401  (every import below is a re-export)
@@ -20,6 +20,7 @@ from .gibbs import GibbsGroups, group_variance_draw
 from .host import (DFT_STEP_FIELDS, DFT_UNITS, GEMM_TASK_FIELDS, dft_geometry, dft_step_is_stock, gemm_plan_geometry, gemm_report, hpx_geometry, hpx_lambda, hpx_rings, j_max, mw_ring_weights, noise_bits, rec_geometry, tiling_axisym,
                    wav_bandlimits)
 from .inpaint import inpaint_scratch, inpaint_step
+from .lasso import lasso_precision_draw, lasso_scratch
 from .lci import lci_data_terms, lci_eval, lci_scratch, lci_search
 from .plans import (DftPlan, DirWavPlan, GemmPlan, HarmWavPlan, HpxPlan, IterCounter, ShtPlan, WavPlan, _Plan, capture_scope, live_plans, raise_on_status,
                     tables_trim)

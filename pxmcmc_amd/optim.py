@@ -279,14 +279,8 @@ class GaussianPosterior(Stepper):
         if not hasattr(prior, "precision") or getattr(prior, "T", None) is None:
             raise ValueError("GaussianPosterior needs a prior with precision and T (prior.Gaussian)")
         super().__init__(forward, prior, mcmcparams, nchains=nchains, seed=seed, chain_offset=chain_offset, use_graph=use_graph)
-        if int(max_iter) < 1 or int(check_every) < 1:
-            raise ValueError("GaussianPosterior needs max_iter >= 1 and check_every >= 1")
-        if not (np.isfinite(tol) and tol >= 0):
-            raise ValueError("GaussianPosterior needs a finite tol >= 0")
-        self.tol, self.max_iter, self.check_every = float(tol), int(max_iter), int(check_every)
-        self.gradient_op = gradient_operator(forward)
-        n, dt = int(forward.nparams), self._state_dtype()
-        self._n, self._dt = n, dt
+        self._solver_setup(tol, max_iter, check_every)
+        n, dt = self._n, self._dt
         p = np.asarray(prior.precision, dtype=float)
         if p.ndim and p.size != n:
             raise ValueError(f"GaussianPosterior: the precision has {p.size} entries, the state {n}")
@@ -294,11 +288,26 @@ class GaussianPosterior(Stepper):
             raise ValueError("GaussianPosterior: the precision must be finite and not negative")
         scale = float(prior.T) / float(self.lmda)
         self._D = float(p.reshape(-1)[0]) * scale if p.ndim == 0 or n == 1 else ops.as_device(p * scale, torch.float64)
-        zero = torch.zeros((1, n), dtype=dt, device=ops.device())
-        self._b0 = torch.zeros(n, dtype=dt, device=zero.device)
-        ops.skrock_stage(self._linear(zero), -1.0, out=self._b0)  # b0 = -calc_gradg(forward(0))
+        self._solver_rhs()
         self.precond = precond if precond is None or isinstance(precond, str) else "given"
         self._minv = self._preconditioner(precond)
+
+    def _solver_setup(self, tol, max_iter, check_every):
+        """what the solver needs of its arguments whatever the prior: the limits, the gradient operator, the state's size and dtype"""
+        name = type(self).__name__
+        if int(max_iter) < 1 or int(check_every) < 1:
+            raise ValueError(f"{name} needs max_iter >= 1 and check_every >= 1")
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError(f"{name} needs a finite tol >= 0")
+        self.tol, self.max_iter, self.check_every = float(tol), int(max_iter), int(check_every)
+        self.gradient_op = gradient_operator(self.forward)
+        self._n, self._dt = int(self.forward.nparams), self._state_dtype()
+
+    def _solver_rhs(self):
+        """``b0 = -calc_gradg(forward(0))``"""
+        zero = torch.zeros((1, self._n), dtype=self._dt, device=ops.device())
+        self._b0 = torch.zeros(self._n, dtype=self._dt, device=zero.device)
+        ops.skrock_stage(self._linear(zero), -1.0, out=self._b0)
 
     def _state_dtype(self, start=None):
         """complex128 when ``params.complex``, the data or the start point is complex, or when the state is the coefficients
@@ -392,9 +401,13 @@ class GaussianPosterior(Stepper):
             ops.skrock_stage(B, 1.0, e=-1.0, V=HX, out=self._R0)
         ops.cg_rhs(B, Z=self._R0, S=self._minv, out=self._U0)
         self._coef0.zero_()
-        self._coef0[:, CG_BNORM2] = ops.reduce_vdot(B, B).real
+        self._coef0[:, CG_BNORM2] = self._reference_norm2(B)
         eng.side = "A"
         eng.reset()
+
+    def _reference_norm2(self, B):
+        """``||b||^2`` of the stop rule ``||r|| <= tol ||b||``, per chain: of the right-hand sides themselves"""
+        return ops.reduce_vdot(B, B).real
 
     def _iterate(self):
         """advance until every chain is frozen or ``max_iter`` -> (X, coefficients on the host, residual rows, checks)"""
@@ -467,6 +480,11 @@ class GaussianPosterior(Stepper):
         """the right-hand sides ``[C, N]`` of draw ``k`` of every chain (device array): ``b0 + calc_gradg(data + s o omega_1)
         + sqrt(D) o omega_2`` with the deviates of the Philox iterations ``2 k`` and ``2 k + 1``.  ``omega_2``, and ``omega_1``
         with it, is complex when the state is: the perturbations then cover the real and the imaginary part of ``F``."""
+        g, w2, sqrtD = self._draw_parts(k)
+        return ops.cg_rhs(w2, B=self._b0, G=g, Z=w2, S=sqrtD)
+
+    def _draw_parts(self, k):
+        """``(calc_gradg(data + s o omega_1), omega_2, sqrt(D))`` of draw ``k``"""
         if getattr(self, "_draw_ops", None) is None:
             self._draw_ops = self._draw_operands()
         s, sqrtD = self._draw_ops
@@ -476,8 +494,7 @@ class GaussianPosterior(Stepper):
         if self.forward.data_dev.is_complex() and not cplx:  # (real state, complex data: the predictions carry the data)
             w1 = w1.to(torch.complex128)
         g = ops.as_device(self.gradient_op.calc_gradg(ops.cg_rhs(w1, B=self.forward.data_dev, Z=w1, S=s)), self._dt)
-        w2 = ops.randn(self._n, C, it=2 * int(k) + 1, **kw)
-        return ops.cg_rhs(w2, B=self._b0, G=g, Z=w2, S=sqrtD)
+        return g, ops.randn(self._n, C, it=2 * int(k) + 1, **kw), sqrtD
 
     def sample(self, ndraws, summary=None, summary_ess=None, summary_alpha=None, first_draw=0, as_torch=False):
         """``ndraws`` exact, independent draws of the posterior, C per solve (draw ``first_draw + k`` of chain ``c`` is row
@@ -531,6 +548,65 @@ class GaussianPosterior(Stepper):
         if summary:
             return post
         out = out[:int(ndraws)]
+        return out.clone() if as_torch else out.cpu().numpy()
+
+
+    def _gibbs_run(self, nsweeps, nburn, summary, summary_ess, summary_alpha, as_torch, prepare, draw):
+        """The sweep loop the Gibbs samplers on this solver share (:class:`GaussianGibbs`, :class:`LassoGibbs`): the exact draw
+        of the field at the chains' current diagonals, then ``draw(t, X, kept)``, the conditional draw of the precisions given
+        the field ``X`` of sweep ``t``, which rewrites the diagonals in place.  ``prepare(nsweeps, keep)`` runs once the
+        arguments are checked and sets the initial diagonals.  Returns what ``run`` returns: the kept field draws, or their
+        ``PosteriorSummary``."""
+        name = type(self).__name__
+        if summary not in (None, "state", "image"):
+            raise ValueError("summary must be None, 'state' or 'image'")
+        nsweeps, nburn = int(nsweeps), int(nburn)
+        if nsweeps < 1 or not 0 <= nburn < nsweeps:
+            raise ValueError("run needs nsweeps >= 1 and 0 <= nburn < nsweeps")
+        tr = getattr(self.forward, "transform", None)
+        if summary == "image" and (getattr(self.forward, "setting", "synthesis") == "analysis" or not hasattr(tr, "inverse")):
+            raise ValueError("summary='image' needs forward.transform.inverse in the synthesis setting")
+        C, n, keep = self.nchains, self._n, nsweeps - nburn
+        dev = ops.device()
+        prepare(nsweeps, keep)
+        self._draw_ops = self._draw_operands()
+        post = None
+        out = None if summary else torch.empty((keep, C, n), dtype=self._dt, device=dev)
+        start = torch.zeros((C, n), dtype=self._dt, device=dev)
+        self._engine_start(start)
+        its, ok = [], []
+        try:
+            for t in range(nsweeps):
+                # one engine, and so one capture, per solve: the first iterations of a system loaded into an engine whose graph
+                # had replayed before came out wrong on the MI355X (DESIGN.md section 23)
+                if t:
+                    self._engine_start(start)
+                self._load(self.draw_rhs(t))
+                X, coef, rows, checks = self._iterate()
+                self._record(coef, rows, checks)
+                its.append(self.niter.copy())
+                ok.append(self.converged.copy())
+                if self.breakdown.any() or not self.converged.all():
+                    warnings.warn(f"{name}.run: the solve of sweep {t} did not converge for every chain (breakdown: "
+                                  f"{self.breakdown.tolist()}, relative residuals {rows[-1].tolist()})")
+                draw(t, X, t >= nburn)
+                if t < nburn:
+                    continue
+                if summary is None:
+                    out[t - nburn].copy_(X)
+                    continue
+                S = X if summary == "state" else ops.as_device(tr.inverse(X))
+                if post is None:
+                    from .uncertainty import PosteriorSummary
+
+                    post = PosteriorSummary(C, S.shape[1], S.is_complex(), best=False, alpha=summary_alpha, nsamples=keep,
+                                            ess_lags=summary_ess)
+                post.update(S)
+        finally:
+            self._engine_stop()
+        self.solve_iterations, self.solve_converged = np.stack(its), np.stack(ok)
+        if summary:
+            return post
         return out.clone() if as_torch else out.cpu().numpy()
 
 
@@ -652,64 +728,171 @@ class GaussianGibbs(GaussianPosterior):
         runs with the same ``seed`` and ``chain_offset`` return the same bits."""
         from .uncertainty import PosteriorSummary
 
-        if summary not in (None, "state", "image"):
-            raise ValueError("summary must be None, 'state' or 'image'")
-        nsweeps, nburn = int(nsweeps), int(nburn)
-        if nsweeps < 1 or not 0 <= nburn < nsweeps:
-            raise ValueError("run needs nsweeps >= 1 and 0 <= nburn < nsweeps")
-        tr = getattr(self.forward, "transform", None)
-        if summary == "image" and (getattr(self.forward, "setting", "synthesis") == "analysis" or not hasattr(tr, "inverse")):
-            raise ValueError("summary='image' needs forward.transform.inverse in the synthesis setting")
-        C, n, K, keep = self.nchains, self._n, self.K, nsweeps - nburn
-        dev = ops.device()
-        self._Dg.copy_(self._Dg0)
-        self._expand()
-        self._draw_ops = self._draw_operands()
-        trace = torch.zeros((nsweeps, C, K), dtype=torch.float64, device=dev)
-        post = None
-        hyper = PosteriorSummary(C, K, False, best=False, alpha=summary_alpha, nsamples=keep, ess_lags=summary_ess)
-        out = None if summary else torch.empty((keep, C, n), dtype=self._dt, device=dev)
-        start = torch.zeros((C, n), dtype=self._dt, device=dev)
-        self._engine_start(start)
-        its, ok = [], []
-        try:
-            for t in range(nsweeps):
-                # one engine, and so one capture, per solve: the first iterations of a system loaded into an engine whose graph
-                # had replayed before came out wrong on the MI355X (DESIGN.md section 23)
-                if t:
-                    self._engine_start(start)
-                self._load(self.draw_rhs(t))
-                X, coef, rows, checks = self._iterate()
-                self._record(coef, rows, checks)
-                its.append(self.niter.copy())
-                ok.append(self.converged.copy())
-                if self.breakdown.any() or not self.converged.all():
-                    warnings.warn(f"GaussianGibbs.run: the solve of sweep {t} did not converge for every chain (breakdown: "
-                                  f"{self.breakdown.tolist()}, relative residuals {rows[-1].tolist()})")
-                self._variance_draw(X, self._VAR_ITER + t, trace=trace, row=t)
-                if t < nburn:
-                    continue
-                hyper.update(-torch.log(trace[t] / self._scale))  # log v, v = 1 / precision in the prior's units
-                if summary is None:
-                    out[t - nburn].copy_(X)
-                    continue
-                S = X if summary == "state" else ops.as_device(tr.inverse(X))
-                if post is None:
-                    post = PosteriorSummary(C, S.shape[1], S.is_complex(), best=False, alpha=summary_alpha, nsamples=keep,
-                                            ess_lags=summary_ess)
-                post.update(S)
-        finally:
-            self._engine_stop()
-        self.solve_iterations, self.solve_converged = np.stack(its), np.stack(ok)
-        self.precision_chain = trace[nburn:].cpu().numpy() / self._scale
+        C, K = self.nchains, self.K
+        made = {}
+
+        def prepare(nsweeps, keep):
+            self._Dg.copy_(self._Dg0)
+            self._expand()
+            made["trace"] = torch.zeros((nsweeps, C, K), dtype=torch.float64, device=ops.device())
+            made["hyper"] = PosteriorSummary(C, K, False, best=False, alpha=summary_alpha, nsamples=keep, ess_lags=summary_ess)
+
+        def draw(t, X, kept):
+            self._variance_draw(X, self._VAR_ITER + t, trace=made["trace"], row=t)
+            if kept:
+                made["hyper"].update(-torch.log(made["trace"][t] / self._scale))  # log v, v = 1 / precision in the prior's units
+
+        out = self._gibbs_run(nsweeps, nburn, summary, summary_ess, summary_alpha, as_torch, prepare, draw)
+        self.precision_chain = made["trace"][int(nburn):].cpu().numpy() / self._scale
         with np.errstate(divide="ignore"):
             self.variance_chain = 1.0 / self.precision_chain
         if self.group_kind == "degree":
             self.cl_chain = self.variance_chain
-        self.hyper_summary = hyper
-        if summary:
-            return post
-        return out.clone() if as_torch else out.cpu().numpy()
+        self.hyper_summary = made["hyper"]
+        return out
+
+
+# ---- L1 prior: the exact Gibbs sampler of the sparse posterior on the batched solver (DESIGN.md section 25) -------------------
+class LassoGibbs(GaussianPosterior):
+    """
+    The posterior of the L1 prior itself -- the objective of :class:`FISTA`,
+
+        F(X) = 1/2 Re L2(X) + (1 / lmda) sum_i T_i |X_i|,
+
+    sampled exactly by data augmentation (Park & Casella 2008; Kyung et al. 2010) on the solver of
+    :class:`GaussianPosterior`.  The Laplace prior is a Gaussian scale mixture: every coefficient carries a variance
+    ``v_i`` of its own, given which the field is Gaussian with precision ``D_i = 1 / v_i``, and given the field every
+    precision is an independent inverse-Gaussian variate, ``D_i | x ~ IG(t_i / |x_i|, t_i^2)`` with ``t_i = T_i / lmda``, for
+    real and complex coefficients alike.  A sweep is the exact draw ``x | D, d`` (perturbation-optimisation, one batched CG
+    solve) and one element-wise draw on the device (``pxm_lasso_precision_draw``): no step size, no rejection, and no bias
+    -- MYULA and SKROCK sample the Moreau-Yosida envelope of this density, PxMALA samples it with a tuned step.
+    ``lasso_np`` states the sampler in numpy.
+
+    :param prior: the stock synthesis-setting L1 family (``L1``, ``S2_Wavelets_L1``, ``S2_Wavelets_L1_Power_Weights``) with a
+        positive threshold ``T``, a float or one value per coefficient.  Refused: a threshold with an entry that is not
+        positive (``T_i = 0`` is a flat prior, which the mixture cannot express), the analysis setting and TV (the mixture
+        would be over ``A X``, whose conditional is not diagonal) and a prior with a prox of its own
+    :param precision_bounds: ``(d_lo, d_hi)``, finite and positive: the clamp of every ``D_i``.  ``clamped_chain`` counts the
+        elements it changed: that many conditionals per sweep were not the model's
+    :param tol: a chain's solve stops at ``||r|| <= tol ||b_data||``, ``b_data = b0 + calc_gradg(data + s o omega_1)`` the part
+        of the right-hand side that does not depend on ``D``: the precisions of one chain span many decades, and the
+        perturbation ``sqrt(D) o omega_2`` of the coefficients near zero would otherwise set the scale of the stop rule for
+        the coefficients that matter
+    :param max_iter, check_every, use_graph: as for :class:`GaussianPosterior`; the preconditioner is ``M = D + trace(A) / N``
+    :param seed, chain_offset: sweep ``t`` of chain ``c`` uses the float64 Philox stream at ``(seed, chain_offset + c)``:
+        iterations ``2 t`` and ``2 t + 1`` for the field draw, ``2^60 + 2 t`` and ``2^60 + 2 t + 1`` for the normals and the
+        uniforms of the precisions (``2^60 - 2``, ``2^60 - 1`` for the precisions drawn from a start point)
+
+    The forward operator needs a diagonal inverse covariance (the data perturbation is formed element by element).
+
+    :meth:`run` here is the sampler, ``run(nsweeps, nburn, start_point, ...)``, as for :class:`GaussianGibbs`.  After it:
+    ``solve_iterations`` and ``solve_converged`` (``[nsweeps, C]``), ``prior_term_chain`` (``[nsweeps - nburn, C]``:
+    ``(1 / lmda) sum_i T_i |X_i|`` of every kept draw, the prior term of ``F``) and ``clamped_chain`` (same shape).
+    :meth:`sample` draws the field at the precisions as the last run left them.
+    """
+
+    def __init__(self, forward, prior, mcmcparams=PxMCMCParams(), nchains=1, precision_bounds=(1e-30, 1e30), tol=1e-8, max_iter=1000,
+                 check_every=10, use_graph=True, seed=0, chain_offset=0):
+        from . import lasso_np
+
+        if getattr(prior, "pairs", False):
+            raise ValueError("LassoGibbs: a total-variation prior is not supported: its norm couples the pair of a pixel and acts "
+                             "on A X, so the conditional of the field is not the diagonal system the sampler solves")
+        if getattr(prior, "setting", "synthesis") != "synthesis":
+            raise ValueError("LassoGibbs: the analysis setting is not supported: the scale mixture would be over the coefficients "
+                             "A X, and the prior precision A^H D A is not diagonal in the state")
+        inv = getattr(forward, "invcov", None)
+        if hasattr(inv, "matvec") or not hasattr(inv, "diag"):
+            raise ValueError("LassoGibbs needs a diagonal inverse covariance: the data perturbation sqrt(W) omega_1 of the field "
+                             "draw is formed element by element")
+        Stepper.__init__(self, forward, prior, mcmcparams, nchains=nchains, seed=seed, chain_offset=chain_offset, use_graph=use_graph)
+        if not self._stock_prox or getattr(prior, "T", None) is None:
+            raise ValueError("LassoGibbs needs the stock synthesis-setting L1 prior (prior.L1 and its wavelet subclasses, with "
+                             "their own prox): the conditionals are those of (1 / lmda) sum_i T_i |X_i|")
+        self._solver_setup(tol, max_iter, check_every)
+        n, C = self._n, self.nchains
+        setup = lasso_np.check_setup(n, prior.T, float(self.lmda), precision_bounds)
+        self.precision_bounds = setup["precision_bounds"]
+        self._T, self._tscale = prior.T_dev, 1.0 / float(self.lmda)
+        D0 = lasso_np.initial_precision(setup["t"], self._dt.is_complex)
+        self._D = float(D0) if D0.ndim == 0 or n == 1 else ops.as_device(D0, torch.float64)
+        self._solver_rhs()
+        self.precond = "diag"
+        self._preconditioner("diag")  # (for trace_estimate: M^-1 itself follows the sampled D)
+        # the per-chain diagonals the launches of the solver read in place: the precision draw rewrites them, at these addresses
+        dev = ops.device()
+        self._D0 = ops.as_device(np.broadcast_to(D0, (n,)), torch.float64)
+        self._D, self._sqrtD, self._minv = (torch.empty((C, n), dtype=torch.float64, device=dev) for _ in range(3))
+        self._lasso_scratch = ops.lasso_scratch(C, dev)
+        self._reset_precisions()
+
+    def _reset_precisions(self):
+        """``D = t^2 / (m + 1)``, the reciprocal of the prior mean of the variance, in every chain"""
+        self._D.copy_(self._D0.unsqueeze(0).expand_as(self._D))
+        torch.sqrt(self._D, out=self._sqrtD)
+        torch.reciprocal(self._D + float(self.trace_estimate), out=self._minv)
+
+    def _precision_draw(self, X, it, sums=None):
+        ops.lasso_precision_draw(X, self._T, self._D, self._sqrtD, self._minv, tscale=self._tscale, h=float(self.trace_estimate),
+                                 d_lo=self.precision_bounds[0], d_hi=self.precision_bounds[1], seed=self.seed,
+                                 chain0=self.chain_offset, it=it, sums=sums, scratch=self._lasso_scratch)
+
+    def _draw_operands(self):
+        s, _ = super()._draw_operands()
+        return s, self._sqrtD
+
+    def draw_rhs(self, k):
+        """as :meth:`GaussianPosterior.draw_rhs`; also notes the squared norm of the part that does not depend on ``D``, ``b0 +
+        calc_gradg(data + s o omega_1)``, for the stop rule of the solve"""
+        g, w2, sqrtD = self._draw_parts(k)
+        data_part = ops.cg_rhs(w2, B=self._b0, G=g)
+        self._data_norm2 = ops.reduce_vdot(data_part, data_part).real
+        return ops.cg_rhs(w2, B=self._b0, G=g, Z=w2, S=sqrtD)
+
+    def _reference_norm2(self, B):
+        """the stop rule's ``||b||^2``: of the data part of the right-hand side (of all of it where that part vanishes)"""
+        full = super()._reference_norm2(B)
+        ref = getattr(self, "_data_norm2", None)
+        return full if ref is None else torch.where(ref > 0, ref, full)
+
+    def _start_state(self, start_point):
+        C, n = self.nchains, self._n
+        X0 = ops.as_device(start_point)
+        if X0.dim() == 1:
+            X0 = X0.unsqueeze(0).expand(C, -1)
+        if tuple(X0.shape) != (C, n):
+            raise ValueError(f"LassoGibbs.run: the start point is [N] or [C, N] with N = {n}, C = {C}")
+        if X0.is_complex() and not self._dt.is_complex:
+            raise ValueError("LassoGibbs.run: a complex start point needs a complex state")
+        return X0.to(self._dt).contiguous()
+
+    def run(self, nsweeps, nburn=0, start_point=None, summary=None, summary_ess=None, summary_alpha=None, as_torch=False):
+        """``nsweeps`` sweeps of every chain; the first ``nburn`` are dropped.  Without a ``start_point`` the precisions start at
+        ``t^2 / (m + 1)``; with one (``[N]``, or ``[C, N]`` with one row per chain -- a MAP point of :class:`FISTA`, say, whose
+        exact zeros are the ``x = 0`` case of the draw) they are drawn from it.  Returns the field draws ``[nsweeps - nburn, C,
+        N]`` (numpy, or a device tensor with ``as_torch``); with ``summary="state"`` or ``"image"`` they are folded into a
+        :class:`pxmcmc_amd.uncertainty.PosteriorSummary` instead, which is returned.  Two runs with the same ``seed``,
+        ``chain_offset`` and start return the same bits."""
+        from . import lasso_np
+
+        made = {}
+
+        def prepare(nsweeps, keep):
+            X0 = None if start_point is None else self._start_state(start_point)
+            made["sums"] = torch.zeros((nsweeps, self.nchains, 2), dtype=torch.float64, device=ops.device())
+            self._data_norm2 = None
+            if X0 is None:
+                self._reset_precisions()
+            else:
+                self._precision_draw(X0, lasso_np.DRAW_ITER - 2)
+
+        def draw(t, X, kept):
+            self._precision_draw(X, lasso_np.draw_iterations(t)[0], sums=made["sums"][t])
+
+        out = self._gibbs_run(nsweeps, nburn, summary, summary_ess, summary_alpha, as_torch, prepare, draw)
+        sums = made["sums"][int(nburn):].cpu().numpy()
+        self.prior_term_chain, self.clamped_chain = sums[:, :, 0].copy(), sums[:, :, 1].copy()
+        return out
 
 
 # ---- analysis setting: primal-dual splitting and the exact prox (DESIGN.md section 14d) ---------------------------------------
