@@ -291,6 +291,36 @@ int64_t pxm_dwav_table_bytes(pxm_dwav_plan_t plan);
 int pxm_dwav_status(pxm_dwav_plan_t plan, int clear, pxm_stream_t stream);
 /* launch shapes (test / timing aid): (block, n) items, workgroups per chain of the harmonic-split and gamma launches */
 int pxm_dwav_plan_info(pxm_dwav_plan_t plan, int* nitems, int* split_blocks, int* gamma_blocks);
+/* Test hooks of the directional plan: its workspace and one stage of one operator at a time ("Error model and
+ * tests of the orientation stages").  The workspace is one complex128 array; offsets and sizes count complex elements.
+ * pxm_dwav_workspace_layout writes min(cap, n) of its n int64 words to out and returns n:
+ *   {workspace elements, offset and elements of the flm region [max_chains][L*L], offset of the harmonic arena, of the pixel
+ *    arena, items, blocks, max_chains}, then 8 per item in plan order: {block, n, bl, offset of chain 0 of the harmonic
+ *    operand, its elements per chain (bl^2), offset of chain 0 of the pixel operand, its elements per chain (bl (2 bl - 1)),
+ *    0}; chain c of an operand follows chain c - 1; then 8 per block of the gamma stage: {offset in a chain's coefficient
+ *    vector, pixels per plane, planes, orientations, first workgroup, first entry of its row of the g-offset table, 0, 0};
+ *    then the g-offset table as uploaded, blocks * N entries: per orientation of a block the offset of g_n in the pixel
+ *    arena, or -1 for a skipped pair.
+ * pxm_dwav_workspace_write / _read copy n elements device-to-device into / out of the workspace at `offset` (refused
+ * outside it).  pxm_dwav_run_stage enqueues stage 0 .. 3 of operator op (0 analysis, 1 analysis_adjoint, 2 synthesis,
+ * 3 synthesis_adjoint) alone, through the calls the operator makes, in the operator's order: the SHT at L (reads or writes
+ * f = x, [C][L (2L-1)]), the harmonic split or merge, the inner SHTs of every item, the gamma stage (reads or writes
+ * X = x, [C][ncoefs]); x may be null for the two inner stages. */
+int64_t pxm_dwav_workspace_layout(pxm_dwav_plan_t plan, int64_t* out, int64_t cap);
+int pxm_dwav_workspace_write(pxm_dwav_plan_t plan, int64_t offset, const void* src, int64_t n, pxm_stream_t stream);
+int pxm_dwav_workspace_read(pxm_dwav_plan_t plan, int64_t offset, void* dst, int64_t n, pxm_stream_t stream);
+int pxm_dwav_run_stage(pxm_dwav_plan_t plan, int op, int stage, void* x, int C, pxm_stream_t stream);
+/* host-only: the tables the harmonic and gamma stages read, as the plans upload them.
+ *   pxm_host_harm_weights  the rows of the split (wa) and merge (ws) weights, [rows][L] complex each, item by item in plan
+ *                          order: harmonic = 0 the directional plan (spin 0; the pairs |n| >= bl_j are skipped), 1 the
+ *                          harmonic plan; rows[3 i ..] = (block, n, bl) of row i.  Returns the number of rows; writes only
+ *                          when cap >= that number.
+ *   pxm_host_dir_component the directionality component s_lm [L*L] complex that the rows are built from
+ *   pxm_host_dwav_phases   ph[q][k] = e^{i n_k gamma_q}, [2N-1][N] complex, n_k = -(N-1) + 2k, gamma_q = 2 pi q / (2N-1) */
+int64_t pxm_host_harm_weights(int L, double B, int J_min, int N, int spin, int harmonic, double* wa, double* ws, int* rows,
+                              int64_t cap);
+int pxm_host_dir_component(int L, int N, double* s);
+int pxm_host_dwav_phases(int N, double* ph);
 
 /* Harmonic-space wavelet transforms (pys2let analysis_lm2lmn / synthesis_lmn2lm and their adjoints):
  * inputs and outputs are spherical-harmonic coefficients.  f_lm [C][L*L] (ssht index l^2 + l + m, spin-s coefficients);

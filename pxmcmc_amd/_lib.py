@@ -114,6 +114,13 @@ SIGNATURES = {
     "pxm_dwav_table_bytes": (c_i64, [c_vp]),
     "pxm_dwav_status": (c_int, [c_vp, c_int, c_vp]),
     "pxm_dwav_plan_info": (c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "pxm_dwav_workspace_layout": (c_i64, [c_vp, c_vp, c_i64]),
+    "pxm_dwav_workspace_write": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "pxm_dwav_workspace_read": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "pxm_dwav_run_stage": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp]),
+    "pxm_host_harm_weights": (c_i64, [c_int, c_dbl, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64]),
+    "pxm_host_dir_component": (c_int, [c_int, c_int, c_vp]),
+    "pxm_host_dwav_phases": (c_int, [c_int, c_vp]),
     "pxm_hwav_plan_create": (c_int, [c_int, c_dbl, c_int, c_int, c_int, c_int, C.c_uint, C.POINTER(c_vp)]),
     "pxm_hwav_plan_destroy": (c_int, [c_vp]),
     "pxm_hwav_synthesis": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),

@@ -154,7 +154,9 @@ struct pxm_dwav_plan_s {
   };
   std::vector<Item> items;
   double2* ws = nullptr;           // [flm: Cmax L^2 | harmonic arena | pixel arena]
-  int64_t off_harm = 0, off_pix = 0;
+  int64_t off_harm = 0, off_pix = 0, ws_elems = 0;
+  std::vector<DwBlock> blocks;     // the host copies of d_blocks and d_goff (pxm_dwav_workspace_layout)
+  std::vector<int64_t> goff;
   HarmStage hs;                    // items in the harmonic arena; wa = (-1)^n kappa_j conj(s_ln) / sqrt(2 pi),
                                    // ws = (-1)^n kappa_j s_ln sqrt(2 pi); kappa_0 for the scaling function in both
   DwBlock* d_blocks = nullptr;
@@ -209,31 +211,28 @@ int pxm_dwav_plan_create(int L, double B, int J_min, int N, int max_chains, unsi
   if ((rc = pxm_sht_plan_create(L, 0, max_chains, 0, &p->shtL))) return rc;
 
   // items: (scaling, n = 0), then (j, n) for |n| < bl_j; arenas laid out item after item
-  const DwTiling tw(L, B, J_min, N, 0);
   std::vector<double2> wa, wsy;
+  const std::vector<HarmRow> wrows = harm_weight_rows(L, B, J_min, N, 0, false, wa, wsy);
   std::vector<DwItem> hitems;
-  std::vector<int64_t> goff((size_t)nb * N, -1);
+  std::vector<int64_t>& goff = p->goff;
+  goff.assign((size_t)nb * N, -1);
   int64_t harm = 0, pix = 0;
   int blk = 0;
-  for (int b = 0; b < nb; ++b) {
-    const int bl = p->bl[b];
-    for (int k = 0; k < harm_orients(b, N); ++k) {
-      const int n = harm_n(b, k, N);
-      if (std::abs(n) >= bl) continue;
-      pxm_sht_plan_t& sp = p->sht[{bl, -n}];
-      if (!sp && (rc = pxm_sht_plan_create(bl, -n, max_chains, 0, &sp))) return rc;
-      p->items.push_back({b, n, bl, harm, pix, sp});
-      hitems.push_back({harm, (int64_t)bl * bl, (int64_t)wa.size(), bl, blk});
-      goff[(size_t)b * N + k] = pix;
-      tw.rows(b, n, false, wa, wsy);
-      harm += (int64_t)max_chains * bl * bl;
-      pix += (int64_t)max_chains * bl * (2 * bl - 1);
-      blk += (bl * bl + DW_THREADS - 1) / DW_THREADS;
-    }
+  for (size_t d = 0; d < wrows.size(); ++d) {
+    const int b = wrows[d].block, n = wrows[d].n, bl = wrows[d].bl;
+    PXM_REQUIRE(b < nb && bl == p->bl[b], "pxm_dwav_plan_create: layout mismatch");
+    pxm_sht_plan_t& sp = p->sht[{bl, -n}];
+    if (!sp && (rc = pxm_sht_plan_create(bl, -n, max_chains, 0, &sp))) return rc;
+    p->items.push_back({b, n, bl, harm, pix, sp});
+    hitems.push_back({harm, (int64_t)bl * bl, (int64_t)d * L, bl, blk});
+    goff[(size_t)b * N + (b ? (n + N - 1) / 2 : 0)] = pix;
+    harm += (int64_t)max_chains * bl * bl;
+    pix += (int64_t)max_chains * bl * (2 * bl - 1);
+    blk += (bl * bl + DW_THREADS - 1) / DW_THREADS;
   }
   p->hs.nitems = (int)hitems.size();
   p->hs.split_blocks = blk;
-  std::vector<DwBlock> hblocks;
+  std::vector<DwBlock>& hblocks = p->blocks;
   int64_t coef = 0;
   blk = 0;
   for (int b = 0; b < nb; ++b) {
@@ -245,19 +244,12 @@ int pxm_dwav_plan_create(int L, double B, int J_min, int N, int max_chains, unsi
   }
   p->gamma_blocks = blk;
   PXM_REQUIRE(p->hs.split_blocks < (1 << 30) && p->gamma_blocks < (1 << 30), "pxm_dwav_plan_create: grid too large");
-  std::vector<double2> ph((size_t)(2 * N - 1) * N);
-  for (int q = 0; q < 2 * N - 1; ++q)
-    for (int k = 0; k < N; ++k) {
-      // e^{i n gamma_q}, n gamma_q = 2 pi (n q mod (2N-1)) / (2N-1): the angle reduced exactly before the sincos
-      const int n = harm_n(1, k, N);
-      const int r = (((n * q) % (2 * N - 1)) + (2 * N - 1)) % (2 * N - 1);
-      const double a = 2.0 * M_PI * r / (2 * N - 1);
-      ph[(size_t)q * N + k] = double2{std::cos(a), std::sin(a)};
-    }
+  const std::vector<double2> ph = dw_phases(N);
 
   p->off_harm = (int64_t)max_chains * L * L;
   p->off_pix = p->off_harm + harm;
-  const size_t wsb = (size_t)(p->off_pix + pix) * sizeof(double2);
+  p->ws_elems = p->off_pix + pix;
+  const size_t wsb = (size_t)p->ws_elems * sizeof(double2);
   if ((rc = dev_alloc(&p->ws, wsb, "directional wavelet plan workspace"))) return rc;
   if ((rc = dev_zero(p->ws, wsb))) return rc;
   // (the split writes every item operand in full and the SHT stages every g_n: the zeroing only keeps unused tails clean)
@@ -390,6 +382,70 @@ int pxm_dwav_plan_info(pxm_dwav_plan_t p, int* nitems, int* split_blocks, int* g
   if (split_blocks) *split_blocks = p->hs.split_blocks;
   if (gamma_blocks) *gamma_blocks = p->gamma_blocks;
   return 0;
+}
+
+// ---- test hooks: the workspace and one stage of one operator at a time (include/pxmcmc_amd.h) ----
+int64_t pxm_dwav_workspace_layout(pxm_dwav_plan_t p, int64_t* out, int64_t cap) {
+  PXM_REQUIRE(p, "pxm_dwav_workspace_layout: null plan");
+  std::vector<int64_t> w = {p->ws_elems, 0, (int64_t)p->Cmax * p->L * p->L, p->off_harm, p->off_pix, (int64_t)p->items.size(),
+                            (int64_t)p->blocks.size(), p->Cmax};
+  for (const auto& it : p->items)
+    w.insert(w.end(), {it.block, it.n, it.bl, p->off_harm + it.a_off, (int64_t)it.bl * it.bl, p->off_pix + it.g_off,
+                       (int64_t)it.bl * (2 * it.bl - 1), 0});
+  for (const DwBlock& b : p->blocks) w.insert(w.end(), {b.coef_off, b.npix, b.nplanes, b.nn, b.blk0, b.goff, 0, 0});
+  w.insert(w.end(), p->goff.begin(), p->goff.end());  // the table as uploaded
+  const int64_t n = (int64_t)w.size();
+  if (cap > 0) {
+    PXM_REQUIRE(out, "pxm_dwav_workspace_layout: null destination");
+    std::copy(w.begin(), w.begin() + std::min(cap, n), out);
+  }
+  return n;
+}
+
+int pxm_dwav_workspace_write(pxm_dwav_plan_t p, int64_t offset, const void* src, int64_t n, pxm_stream_t stream) {
+  PXM_REQUIRE(p && src, "pxm_dwav_workspace_write: null argument");
+  PXM_REQUIRE(offset >= 0 && n >= 0 && offset <= p->ws_elems && n <= p->ws_elems - offset,
+              "pxm_dwav_workspace_write: range outside the workspace");
+  note_stream((hipStream_t)stream);
+  PXM_HIP(hipMemcpyAsync(p->ws + offset, src, (size_t)n * sizeof(double2), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+int pxm_dwav_workspace_read(pxm_dwav_plan_t p, int64_t offset, void* dst, int64_t n, pxm_stream_t stream) {
+  PXM_REQUIRE(p && dst, "pxm_dwav_workspace_read: null argument");
+  PXM_REQUIRE(offset >= 0 && n >= 0 && offset <= p->ws_elems && n <= p->ws_elems - offset,
+              "pxm_dwav_workspace_read: range outside the workspace");
+  note_stream((hipStream_t)stream);
+  PXM_HIP(hipMemcpyAsync(dst, p->ws + offset, (size_t)n * sizeof(double2), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+int pxm_dwav_run_stage(pxm_dwav_plan_t p, int op, int stage, void* x, int C, pxm_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  PXM_REQUIRE(p, "pxm_dwav_run_stage: null plan");
+  PXM_REQUIRE(op >= 0 && op < 4 && stage >= 0 && stage < 4, "pxm_dwav_run_stage: op and stage must be 0 .. 3");
+  PXM_REQUIRE(C >= 1 && C <= p->Cmax, "pxm_dwav_run_stage: C outside [1, max_chains]");
+  PXM_REQUIRE(x || stage == 1 || stage == 2, "pxm_dwav_run_stage: the first and the last stage need X or f");
+  note_stream(st);
+  double2* harm = p->ws + p->off_harm;
+  switch (4 * op + stage) {  // (the calls of pxm_dwav_analysis, _analysis_adjoint, _synthesis, _synthesis_adjoint, in their order)
+    case 0: return pxm_sht_forward(p->shtL, x, p->ws, C, stream);
+    case 1: return harm_split(p->hs, p->ws, harm, 0, 0, C, st);
+    case 2: return dw_items_sht(p, 0, C, st);
+    case 3: return dw_gamma(p, true, nullptr, (double2*)x, 0, C, st);
+    case 4: return dw_gamma(p, false, (const double2*)x, nullptr, 0, C, st);
+    case 5: return dw_items_sht(p, 2, C, st);
+    case 6: return harm_merge(p->hs, harm, p->ws, 0, 1, C, st);
+    case 7: return pxm_sht_forward_adjoint(p->shtL, p->ws, x, C, stream);
+    case 8: return dw_gamma(p, false, (const double2*)x, nullptr, 1, C, st);
+    case 9: return dw_items_sht(p, 1, C, st);
+    case 10: return harm_merge(p->hs, harm, p->ws, 1, 0, C, st);
+    case 11: return pxm_sht_inverse(p->shtL, p->ws, x, C, stream);
+    case 12: return pxm_sht_inverse_adjoint(p->shtL, x, p->ws, C, stream);
+    case 13: return harm_split(p->hs, p->ws, harm, 1, 1, C, st);
+    case 14: return dw_items_sht(p, 3, C, st);
+    default: return dw_gamma(p, true, nullptr, (double2*)x, 1, C, st);
+  }
 }
 
 }  // extern "C"

@@ -76,4 +76,17 @@ struct DwTiling {
   void rows(int b, int n, bool harmonic, std::vector<double2>& wa, std::vector<double2>& ws) const;
 };
 
+// The weight tables of a plan as it uploads them: one row of L entries per item, appended to wa / ws in plan order, with
+// the (block, n, bl) of every row returned.  Pixel space (harmonic = false) skips the pairs |n| >= bl_j, whose s_ln
+// vanishes for every l < bl_j; harmonic space stores every pair.  Both plans and pxm_host_harm_weights build from this.
+struct HarmRow {
+  int block, n, bl;
+};
+std::vector<HarmRow> harm_weight_rows(int L, double B, int J_min, int N, int spin, bool harmonic, std::vector<double2>& wa,
+                                      std::vector<double2>& ws);
+
+// The phases of the gamma stage, ph[q][k] = e^{i n_k gamma_q} with gamma_q = 2 pi q / (2N-1): [2N-1][N], what the
+// directional plan uploads and pxm_host_dwav_phases exports.
+std::vector<double2> dw_phases(int N);
+
 }  // namespace pxm

@@ -82,11 +82,15 @@ static std::vector<double2> dir_component(int L, int N) {
     int g = std::min(N - 1, el);
     if ((N - 1 - g) % 2) --g;
     if (g < 0) continue;
-    for (int m = -g; m <= g; m += 2) {
-      // C(g, k) 2^-g through lgamma: exact enough for g < 1000 (the values are O(1) and below)
-      const int k = (g - m) / 2;
-      const double v = std::sqrt(std::exp(std::lgamma(g + 1.0) - std::lgamma(k + 1.0) - std::lgamma(g - k + 1.0) - g * std::log(2.0)));
+    // C(g, k) by the recurrence C(g, k + 1) = C(g, k) (g - k) / (k + 1) in long double (64-bit mantissa: exact while the
+    // binomial fits, within a few 2^-64 per step beyond, g <= 1023 steps at most), scaled by 2^-g exactly, one square root:
+    // within 1 ulp of the exact value after the rounding to double
+    long double c = 1.0L;
+    for (int k = 0; k <= g; ++k) {
+      const int m = g - 2 * k;
+      const double v = (double)sqrtl(ldexpl(c, -g));
       s[(size_t)el * el + el + m] = (N % 2) ? double2{v, 0.0} : double2{0.0, v};
+      c = c * (long double)(g - k) / (long double)(k + 1);
     }
   }
   return s;
@@ -119,4 +123,69 @@ void DwTiling::rows(int b, int n, bool harmonic, std::vector<double2>& wa, std::
   }
 }
 
+std::vector<HarmRow> harm_weight_rows(int L, double B, int J_min, int N, int spin, bool harmonic, std::vector<double2>& wa,
+                                      std::vector<double2>& ws) {
+  const std::vector<int> bls = wav_bandlimits(L, B, J_min);
+  const DwTiling tw(L, B, J_min, N, spin);
+  std::vector<HarmRow> out;
+  for (int b = 0; b < (int)bls.size(); ++b)
+    for (int k = 0; k < harm_orients(b, N); ++k) {
+      const int n = harm_n(b, k, N);
+      if (!harmonic && std::abs(n) >= bls[b]) continue;
+      out.push_back({b, n, bls[b]});
+      tw.rows(b, n, harmonic, wa, ws);
+    }
+  return out;
+}
+
+std::vector<double2> dw_phases(int N) {
+  std::vector<double2> ph((size_t)(2 * N - 1) * N);
+  for (int q = 0; q < 2 * N - 1; ++q)
+    for (int k = 0; k < N; ++k) {
+      // e^{i n gamma_q}, n gamma_q = 2 pi (n q mod (2N-1)) / (2N-1): the angle reduced exactly, then formed and its
+      // cosine and sine taken in long double (a double angle alone is off by several 2^-52), rounded to double once
+      const int n = harm_n(1, k, N);
+      const int r = (((n * q) % (2 * N - 1)) + (2 * N - 1)) % (2 * N - 1);
+      const long double a = 2.0L * 3.141592653589793238462643383279502884L * (long double)r / (long double)(2 * N - 1);
+      ph[(size_t)q * N + k] = double2{(double)cosl(a), (double)sinl(a)};
+    }
+  return ph;
+}
+
 }  // namespace pxm
+
+extern "C" {
+
+int64_t pxm_host_harm_weights(int L, double B, int J_min, int N, int spin, int harmonic, double* wa, double* ws, int* rows,
+                              int64_t cap) {
+  PXM_REQUIRE(L >= 1 && B > 1.0 && J_min >= 0 && J_min <= pxm::j_max(L, B), "pxm_host_harm_weights: bad (L, B, J_min)");
+  PXM_REQUIRE(N >= 1 && N <= L, "pxm_host_harm_weights: need 1 <= N <= L");
+  PXM_REQUIRE(std::abs(spin) < L && (spin == 0 || N == 1), "pxm_host_harm_weights: need |spin| < L, and N = 1 with a spin");
+  std::vector<double2> a, s;
+  const std::vector<pxm::HarmRow> r = pxm::harm_weight_rows(L, B, J_min, N, spin, harmonic != 0, a, s);
+  const int64_t n = (int64_t)r.size();
+  if (cap < n) return n;
+  PXM_REQUIRE(wa && ws && rows, "pxm_host_harm_weights: null destination");
+  for (size_t i = 0; i < a.size(); ++i) {
+    wa[2 * i] = a[i].x, wa[2 * i + 1] = a[i].y;
+    ws[2 * i] = s[i].x, ws[2 * i + 1] = s[i].y;
+  }
+  for (int64_t i = 0; i < n; ++i) rows[3 * i] = r[i].block, rows[3 * i + 1] = r[i].n, rows[3 * i + 2] = r[i].bl;
+  return n;
+}
+
+int pxm_host_dir_component(int L, int N, double* s) {
+  PXM_REQUIRE(L >= 1 && L <= 1024 && N >= 1 && N <= L && s, "pxm_host_dir_component: need 1 <= N <= L <= 1024 and a destination");
+  const std::vector<double2> v = pxm::dir_component(L, N);
+  for (size_t i = 0; i < v.size(); ++i) s[2 * i] = v[i].x, s[2 * i + 1] = v[i].y;
+  return 0;
+}
+
+int pxm_host_dwav_phases(int N, double* ph) {
+  PXM_REQUIRE(N >= 1 && N <= 1024 && ph, "pxm_host_dwav_phases: need 1 <= N <= 1024 and a destination");
+  const std::vector<double2> p = pxm::dw_phases(N);
+  for (size_t i = 0; i < p.size(); ++i) ph[2 * i] = p[i].x, ph[2 * i + 1] = p[i].y;
+  return 0;
+}
+
+}  // extern "C"

@@ -153,22 +153,17 @@ int pxm_hwav_plan_create(int L, double B, int J_min, int N, int spin, int max_ch
   p->spin = spin;
   p->Cmax = max_chains;
   p->bl = hw_sizes(L, B, J_min, N, &p->ncoefs, &p->nscal);
-  const int nb = (int)p->bl.size();
   // items: (scaling, n = 0), then (j, n) for every n -- the layout stores every block, s_ln = 0 ones included
-  const DwTiling tw(L, B, J_min, N, spin);
   std::vector<double2> wa, wsy;
+  const std::vector<HarmRow> wrows = harm_weight_rows(L, B, J_min, N, spin, true, wa, wsy);
   std::vector<DwItem> hitems;
   int64_t off = 0;
   int blk = 0;
-  for (int b = 0; b < nb; ++b) {
-    const int bl = p->bl[b];
-    for (int k = 0; k < harm_orients(b, N); ++k) {
-      const int n = harm_n(b, k, N);
-      hitems.push_back({off, p->ncoefs, (int64_t)wa.size(), bl, blk});
-      tw.rows(b, n, true, wa, wsy);
-      off += (int64_t)bl * bl;
-      blk += (bl * bl + DW_THREADS - 1) / DW_THREADS;
-    }
+  for (size_t d = 0; d < wrows.size(); ++d) {
+    const int bl = wrows[d].bl;
+    hitems.push_back({off, p->ncoefs, (int64_t)d * L, bl, blk});
+    off += (int64_t)bl * bl;
+    blk += (bl * bl + DW_THREADS - 1) / DW_THREADS;
   }
   PXM_REQUIRE(off == p->ncoefs, "pxm_hwav_plan_create: layout mismatch");
   PXM_REQUIRE(blk < (1 << 30), "pxm_hwav_plan_create: grid too large");

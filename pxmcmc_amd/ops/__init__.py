@@ -17,7 +17,7 @@ from .._lib import (CG_BREAKDOWN, CG_COEF, CG_FROZEN, FISTA_SLICES_MAX, GIBBS_SL
 from ._args import GEMM_KINDS, _batched, _p, _stream, as_device, device
 from .cg import cg_apply, cg_coef, cg_rhs, cg_scratch, cg_update, gauss_prox
 from .gibbs import GibbsGroups, group_variance_draw
-from .host import (DFT_STEP_FIELDS, DFT_UNITS, GEMM_TASK_FIELDS, dft_geometry, dft_step_is_stock, gemm_plan_geometry, gemm_report, hpx_geometry, hpx_lambda, hpx_rings, j_max, mw_ring_weights, noise_bits, rec_geometry, tiling_axisym,
+from .host import (DFT_STEP_FIELDS, DFT_UNITS, GEMM_TASK_FIELDS, dft_geometry, dft_step_is_stock, dir_component, dwav_phases, gemm_plan_geometry, gemm_report, harm_weights, hpx_geometry, hpx_lambda, hpx_rings, j_max, mw_ring_weights, noise_bits, rec_geometry, tiling_axisym,
                    wav_bandlimits)
 from .inpaint import inpaint_scratch, inpaint_step
 from .lasso import lasso_precision_draw, lasso_scratch

@@ -78,6 +78,33 @@ def hpx_lambda(L, spin, m, theta):
     return out
 
 
+def harm_weights(L, B, J_min, N=1, spin=0, harmonic=False):
+    """(wa, ws, rows): the split and merge weights of the harmonic stage as ``ops.DirWavPlan(L, B, J_min, N)`` (``harmonic``
+    False; spin 0, the pairs |n| >= bl_j skipped) or ``ops.HarmWavPlan(L, B, J_min, N, spin)`` (True) uploads them, complex
+    [rows, L] each, item by item in plan order; ``rows`` int [rows, 3] = (block, n, bl) of each (csrc/harm_stage.hip)"""
+    args = (int(L), float(B), int(J_min), int(N), int(spin), int(bool(harmonic)))
+    n = int(check(lib.pxm_host_harm_weights(*args, None, None, None, 0)))
+    wa, ws, rows = np.zeros((n, int(L)), dtype=complex), np.zeros((n, int(L)), dtype=complex), np.zeros((n, 3), dtype=np.int32)
+    check(lib.pxm_host_harm_weights(*args, wa.ctypes.data, ws.ctypes.data, rows.ctypes.data, n))
+    return wa, ws, rows
+
+
+def dir_component(L, N):
+    """the directionality component s_lm [L*L] as the library builds it for the weight rows (utils.dir_component is the numpy
+    statement; csrc/harm_stage.hip: dir_component)"""
+    s = np.zeros(int(L) * int(L), dtype=complex)
+    check(lib.pxm_host_dir_component(int(L), int(N), s.ctypes.data))
+    return s
+
+
+def dwav_phases(N):
+    """ph[q, k] = e^{i n_k gamma_q}, [2N-1, N], n_k = -(N-1) + 2k, gamma_q = 2 pi q / (2N-1): the table the gamma stage of
+    ``ops.DirWavPlan`` reads (csrc/harm_stage.hip: dw_phases)"""
+    ph = np.zeros((2 * int(N) - 1, int(N)), dtype=complex)
+    check(lib.pxm_host_dwav_phases(int(N), ph.ctypes.data))
+    return ph
+
+
 DFT_STEP_FIELDS = ("X", "T", "noise", "iter_dev", "rdata", "rinvcov", "gidx", "gw")  # bits of pxm_host_dft_step_is_stock
 
 

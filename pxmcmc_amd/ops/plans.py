@@ -566,6 +566,59 @@ class DirWavPlan(_WaveletPlan):
         check(lib.pxm_dwav_plan_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    # ---- test aids: the workspace and one stage at a time (pxm_dwav_workspace_*, pxm_dwav_run_stage) ----
+    OPS = ("analysis", "analysis_adjoint", "synthesis", "synthesis_adjoint")  # op of run_stage, by index
+
+    def layout(self):
+        """the workspace (one complex128 array, offsets in elements) as ``dict(size, flm=(offset, elements), harm, pix,
+        max_chains, items, blocks)``: ``items`` one dict per (block, n) item in plan order with the offset of chain 0 of its
+        harmonic (``a_off``, ``a_n`` = bl^2 per chain) and pixel (``g_off``, ``g_n`` = bl (2 bl - 1) per chain) operand;
+        ``blocks`` one dict per block of the gamma stage, ``goff_row`` the first entry of its row of ``goff``; ``goff`` the
+        g-offset table as uploaded: per orientation of a block the offset of g_n in the pixel arena, -1 for a skipped pair"""
+        n = int(check(lib.pxm_dwav_workspace_layout(self._h, None, 0)))
+        w = (C.c_int64 * n)()
+        check(lib.pxm_dwav_workspace_layout(self._h, w, n))
+        w = [int(v) for v in w]
+        ni, nb = w[5], w[6]
+        items = [dict(zip(("block", "n", "bl", "a_off", "a_n", "g_off", "g_n"), w[8 + 8 * i:15 + 8 * i])) for i in range(ni)]
+        o = 8 + 8 * ni
+        blocks = [dict(zip(("coef_off", "npix", "nplanes", "nn", "blk0", "goff_row"), w[o + 8 * i:o + 8 * i + 6])) for i in range(nb)]
+        return dict(size=w[0], flm=(w[1], w[2]), harm=w[3], pix=w[4], max_chains=w[7], items=items, blocks=blocks, goff=w[o + 8 * nb:])
+
+    def write(self, offset, src):
+        """copies the complex128 device tensor ``src`` into the workspace at ``offset`` (elements)"""
+        _dev_tensors("DirWavPlan.write", "src must be a contiguous complex128 device tensor", (src, _CPLX, tuple(getattr(src, "shape", ()))))
+        check(lib.pxm_dwav_workspace_write(self._h, int(offset), _p(src), src.numel(), _stream()))
+
+    def read(self, offset=0, n=None):
+        """``n`` elements of the workspace from ``offset`` on (default: to its end) -> a fresh complex128 device tensor"""
+        n = self.layout()["size"] - int(offset) if n is None else int(n)
+        if n < 0:
+            raise ValueError("DirWavPlan.read: negative length")
+        out = torch.empty(n, dtype=_CPLX, device=device())
+        check(lib.pxm_dwav_workspace_read(self._h, int(offset), _p(out), n, _stream()))
+        return out
+
+    def run_stage(self, op, stage, x, C_):
+        """enqueues stage 0 .. 3 of operator ``op`` (a name of ``OPS``) alone for ``C_`` chains, as the operator runs it: the
+        SHT at L (``x``: the images f, read or written in place), the harmonic split / merge and the inner SHTs (``x``
+        None), the gamma stage (``x``: the coefficients X, read or written in place).  ``x``: a contiguous complex128
+        device tensor [rows >= C_, npix or ncoefs]; rows >= C_ are not touched."""
+        op, stage = self.OPS.index(op), int(stage)
+        if not 1 <= int(C_) <= self.max_chains:
+            raise ValueError("more chains than the plan was created for")
+        outer = stage == (0 if op in (0, 3) else 3)  # the stage that speaks images
+        if stage in (0, 3):
+            n = self.npix if outer else self.ncoefs
+            rows = x.shape[0] if isinstance(x, torch.Tensor) and x.dim() == 2 else 0
+            _dev_tensors("DirWavPlan.run_stage", f"x must be a contiguous complex128 [rows >= C, {n}] device tensor", (x, _CPLX, (rows, n)))
+            if rows < int(C_):
+                raise ValueError("DirWavPlan.run_stage: x has fewer rows than chains")
+        else:
+            x = None
+        check(lib.pxm_dwav_run_stage(self._h, op, stage, _p(x), int(C_), _stream()))
+        return x
+
 
 class HarmWavPlan(_WaveletPlan):
     """Harmonic-space scale-discretised wavelet transforms (replaces pys2let's analysis_lm2lmn / synthesis_lmn2lm and

@@ -270,6 +270,36 @@ def test_model_analysis_equals_literal_so3_sum(L, B, J_min, N):
     assert np.abs(a - b).max() < 1e-12 * np.abs(b).max()
 
 
+# the tilings test_gpu_dirwav.py adds to the dyadic ones: non-dyadic B, odd L, J_min = 0 (a scaling band-limit of 1), N = L
+OTHER_TILINGS = [(13, 1.5, 1), (33, 1.7, 2), (16, 2.0, 0), (13, 3.0, 1)]
+
+
+@pytest.mark.parametrize("L,B,J_min", OTHER_TILINGS)
+@pytest.mark.parametrize("N", [2, 5, "L"])
+def test_model_on_other_tilings(L, B, J_min, N):
+    """the model on the cases the device is held to it at: exact left inverse, both adjoint pairs, and at L = 13 the
+    literal SO(3) sum"""
+    N = L if N == "L" else N
+    rng = np.random.default_rng(100 * L + 10 * J_min + N)
+    M = DirWavModel(L, B, J_min, N)
+    assert M.bls[0] >= 1 and M.ncoefs == M.offsets[-1]
+    if J_min == 0:
+        assert M.bls[0] == 1  # the scaling function is the l = 0 term alone
+    f = bandlimited_image(L, rng)
+    X = M.analysis(f)
+    assert np.abs(M.synthesis(X) - f).max() < 1e-12 * np.abs(f).max()
+    Y = rng.normal(size=M.ncoefs) + 1j * rng.normal(size=M.ncoefs)
+    g = rng.normal(size=f.size) + 1j * rng.normal(size=f.size)
+    assert abs(np.vdot(Y, M.analysis(g)) - np.vdot(M.analysis_adjoint(Y), g)) < 1e-11 * abs(np.vdot(Y, M.analysis(g)))
+    assert abs(np.vdot(g, M.synthesis(Y)) - np.vdot(M.synthesis_adjoint(g), Y)) < 1e-11 * abs(np.vdot(g, M.synthesis(Y)))
+    if L == 13:
+        b = M.analysis_literal(f)
+        assert np.abs(X - b).max() < 1e-12 * np.abs(b).max()
+        for i in range(len(M.bls)):  # and block by block, against the block's own largest entry
+            sl = slice(M.offsets[i], M.offsets[i + 1])
+            assert np.abs(X[sl] - b[sl]).max() <= 1e-12 * np.abs(b[sl]).max(), i
+
+
 @pytest.mark.parametrize("N", [1, 2, 3, 4, 5])
 def test_model_properties(N):
     L, B, J_min = 12, 2.0, 1

@@ -7,7 +7,7 @@ import io
 import numpy as np
 import pytest
 
-from test_dirwav_host import DirWavModel, bandlimited_image
+from test_dirwav_host import OTHER_TILINGS, DirWavModel, bandlimited_image
 
 pytestmark = pytest.mark.gpu
 
@@ -113,6 +113,48 @@ def test_dirwav_four_ops_match_model_gamma_variants(N, J_min):
     """with N = 2, 3, 4 above and 7, 9 below: every instantiation of the gamma stage (N = 1 .. 8 unrolled, the generic one
     beyond) runs against the model"""
     _four_ops_vs_model(16, 2.0, J_min, N, 2, [0, 1], 1e-12)
+
+
+@pytest.mark.parametrize("L,B,J_min", OTHER_TILINGS)
+@pytest.mark.parametrize("N", [2, 5, "L"])
+@pytest.mark.parametrize("C", [1, 3])
+def test_dirwav_four_ops_match_model_other_tilings(L, B, J_min, N, C):
+    """non-dyadic B, odd L (partial last workgroups), J_min = 0 and N = L, with C = 1 and 3 chains on a plan of 5 and
+    outputs of 5 rows (the rows past C stay as they were); and per block: every (scale, plane) block of the coefficient
+    vector to 1e-12 of its own largest entry, so that the top scale cannot hide the others"""
+    import ctypes
+
+    import torch
+
+    from pxmcmc_amd import ops
+    from pxmcmc_amd._lib import check, lib
+
+    N = L if N == "L" else N
+    CMAX = 5
+    rng = np.random.default_rng(1000 * L + 100 * J_min + 10 * N + C)
+    M = DirWavModel(L, B, J_min, N)
+    plan = ops.DirWavPlan(L, B, J_min, N, max_chains=CMAX)
+    assert (plan.ncoefs, plan.nscal) == (M.ncoefs, M.nscal)
+    X = _cplx(rng, C, M.ncoefs)
+    f = _cplx(rng, C, L * (2 * L - 1))
+    vp = ctypes.c_void_p
+    for name, arg in (("synthesis", X), ("synthesis_adjoint", f), ("analysis", f), ("analysis_adjoint", X)):
+        ref = np.stack([getattr(M, name)(arg[c]) for c in range(C)])
+        src = torch.as_tensor(arg).cuda()
+        out = torch.full((CMAX, ref.shape[1]), complex(np.nan, np.nan), dtype=torch.complex128, device="cuda")
+        check(getattr(lib, "pxm_dwav_" + name)(plan._h, vp(src.data_ptr()), vp(out.data_ptr()), C, None))
+        out = out.cpu().numpy()
+        assert np.isnan(out[C:].real).all() and np.isnan(out[C:].imag).all(), name
+        got = out[:C]
+        assert _rel(got, ref) < 1e-12, (name, _rel(got, ref))
+        if ref.shape[1] == M.ncoefs:
+            for i in range(len(M.bls)):
+                npl = 1 if i == 0 else M.npl
+                a, b = M.offsets[i], M.offsets[i + 1]
+                gb, rb = got[:, a:b].reshape(C, npl, -1), ref[:, a:b].reshape(C, npl, -1)
+                for q in range(npl):
+                    scale = np.abs(rb[:, q]).max()
+                    assert np.abs(gb[:, q] - rb[:, q]).max() <= 1e-12 * scale, (name, i, q)
 
 
 def test_dirwav_skipped_pairs_match_model():
